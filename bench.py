@@ -51,6 +51,8 @@ KFLOP_PER_FRAME = 45.0                # ~35-55 kflop of FP64 per 800/
 CFG4_TOTAL_CLIPS = 100000
 PROFILE_ROUND = "r06"                 # profiles/latest_traffic.json must come from this round's PMC pass of the headline
                                       # kernel (scripts/profile.sh r04): an older file is reported, flagged traffic_stale
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: at most this much on disk
+DUMP_CHUNK_DOUBLES = 32 << 20         # ... read back from the device in copies of at most 256 MB
 XGMI_LINK_GBS = 76.8                  # one xGMI link, one direction (7 links into the root at N = 8)
 
 
@@ -482,6 +484,41 @@ def write_side_record(result, world):
     return None
 
 
+def dump_outputs(out_dir, fetch, rows, frames, slab_offsets, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what one step computed, as a caller of the path receives it -- the [rows][T_c] feature matrix of every
+    clip, side by side in clip order -- as out_dir/features.npy (float64, rows x K) and out_dir/frame_index.npy (float64, the
+    job-wide frame number of every column).  When all frames would exceed `limit` bytes, K frames of the job are drawn with
+    numpy's default_rng(0) and kept in frame order, so that two builds dump the same entries.  frames[c] / slab_offsets[c]:
+    frames and first double of clip c in the device buffer; fetch(offset, count) returns `count` doubles from double `offset`."""
+    frames = np.asarray(frames, dtype=np.int64)
+    slab_offsets = np.asarray(slab_offsets, dtype=np.int64)
+    first = np.zeros(len(frames) + 1, dtype=np.int64)
+    np.cumsum(frames, out=first[1:])
+    total = int(first[-1])
+    k_max = (limit - 4096) // (8 * (rows + 1))          # (a column of features + its frame number; 4 KB for the two headers)
+    pick = np.arange(total) if total <= k_max else np.sort(np.random.default_rng(0).choice(total, k_max, replace=False))
+    clip_of = np.searchsorted(first, pick, side="right") - 1
+    cols = np.empty((rows, len(pick)), dtype=np.float64)
+    clips = np.unique(clip_of)
+    i = 0
+    while i < len(clips):                               # neighbouring clips in one copy of at most DUMP_CHUNK_DOUBLES
+        lo = int(slab_offsets[clips[i]])
+        j = i + 1
+        while j < len(clips) and int(slab_offsets[clips[j]] + rows * frames[clips[j]]) - lo <= DUMP_CHUNK_DOUBLES:
+            j += 1
+        block = fetch(lo, int(slab_offsets[clips[j - 1]] + rows * frames[clips[j - 1]]) - lo)
+        for c in clips[i:j]:
+            t_c = int(frames[c])
+            m = block[int(slab_offsets[c]) - lo:int(slab_offsets[c]) - lo + rows * t_c].reshape(rows, t_c)
+            a, b = np.searchsorted(clip_of, [c, c + 1])
+            cols[:, a:b] = m[:, pick[a:b] - first[c]]
+        i = j
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "features.npy"), cols)
+    np.save(os.path.join(out_dir, "frame_index.npy"), pick.astype(np.float64))
+    return {"dir": out_dir, "rows": int(rows), "frames": total, "frames_dumped": int(len(pick)), "sampled": bool(len(pick) < total)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -508,10 +545,15 @@ def main():
     ap.add_argument("--prewarm-seconds", type=float, default=0.3,
                     help="untimed device work before the --warmup steps (the engine clock of a fresh box ramps over the "
                          "first ~0.2 s of load; reported in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (rank 0; at most 64 MB, a seeded sample of "
+                         "the frames beyond that)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: no launcher exported RANK / WORLD_SIZE -- this process becomes the launcher
         raise SystemExit(self_launch(args))
@@ -682,6 +724,7 @@ def main():
                 step()
             device_sync()
         gather = saved_gather
+        state["k"] = 0                                # (a time-based count: the steps below start from the first input again)
     for _ in range(args.warmup):
         step()
     barrier()
@@ -700,6 +743,25 @@ def main():
     kn = ctypes.c_int64()
     _ffi.check(lib.paa_prof_read(ctypes.byref(kms), ctypes.byref(kn)))
     _ffi.check(lib.paa_prof_enable(0))
+
+    # --dump-outputs: the result of the last timed step, before any later leg reuses the buffers -- what rank 0 holds: the
+    # gathered job with the gather, else its own clips
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if gather:
+            d_res = d_full if d_full is not None else d_all
+            rows = 2 * 34 if d_full is not None else F
+            if workload == "cfg4":
+                clip_frames = np.full(int(job_clips), (10 * FS - WINDOW) // STEP + 1, dtype=np.int64)
+            else:
+                clip_frames = np.array([s[0] for s in sizes], dtype=np.int64)
+            slab_offsets = np.concatenate([[0], np.cumsum(rows * clip_frames)[:-1]])
+        else:
+            d_res, rows = bufs[(state["k"] - 1) & 1], F
+            slab_offsets = plan.out_offsets()
+            clip_frames = np.diff(np.append(slab_offsets, plan.out_doubles)) // F
+        dumped = dump_outputs(args.dump_outputs, lambda off, cnt: d_res.to_host(np.float64, cnt, 8 * off),
+                              rows, clip_frames, slab_offsets)
 
     # N > 1: also time the same steps without the gather, and the cheap gather (reported beside the headline value)
     value_no_gather = None
@@ -822,6 +884,8 @@ def main():
                 "bound": "xgmi link into the root" if t_link > t1 / world else "compute",
                 "note": "arithmetic, not a measurement: per-GPU compute rate from this run's no-gather leg, one xGMI link "
                         "per peer at %.1f GB/s, gather of step k fully overlapped with step k+1" % XGMI_LINK_GBS}
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if sustained:
             result["sustained_frames_per_s"] = sustained["frames_per_s"]
             result["sustained"] = sustained

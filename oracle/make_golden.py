@@ -114,7 +114,8 @@ def main():
     print("total %.2f MB" % (tot / 1e6))
 
 
-if __name__ == "__main__" and not any(a in sys.argv for a in ("--dir", "--thumb", "--wide", "--silence", "--round3", "--round4", "--round5", "--round6")):
+if __name__ == "__main__" and not any(a in sys.argv for a in ("--dir", "--thumb", "--wide", "--silence", "--round3", "--round4", "--round5", "--round6",
+                                                   "--live")):
     main()
 
 
@@ -484,3 +485,73 @@ def round6_goldens():
 
 if __name__ == "__main__" and "--round6" in sys.argv:
     round6_goldens()
+
+
+def _test_module(name):
+    """A module of tests/ (its case lists are the single source of the cases stored below)."""
+    import importlib.util
+    if os.path.dirname(HERE) not in sys.path:
+        sys.path.insert(0, os.path.dirname(HERE))
+    path = os.path.join(os.path.dirname(HERE), "tests", name + ".py")
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def live_goldens():
+    """Outputs of the unmodified reference for the seeded sweeps of tests/test_oracle_vs_live_reference.py and the glue cases of
+    tests/test_silence_glue_cpu.py, so that those tests run without the reference tree.  One npz per test module; every array
+    of a case is stored under "<case key>__<name>", a raised exception as its type name ("<key>__error"), and the input as its
+    SHA-256 ("<key>__input_sha256": the tests re-synthesise it with oracle/synth.py and check that it is the same clip)."""
+    import hashlib
+    from synth import synth_clip
+    ref_st, ref_mt, _ = load_reference.load()
+    sha = lambda a: np.array(hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest())   # noqa: E731
+
+    live = _test_module("test_oracle_vs_live_reference")
+    out = {"kind": np.array("live_sweep")}
+    for seed, fs, window, step, n in live._cases():
+        key = live.feature_case_key(seed, fs, window, step, n)
+        x = synth_clip(7000 + seed, n, fs)
+        out[key + "__input_sha256"] = sha(x)
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                F, names = ref_st.feature_extraction(x.astype(np.float64), fs, window, step)
+        except Exception as exc:
+            out[key + "__error"] = np.array(type(exc).__name__)
+            continue
+        out[key + "__features"], out[key + "__names"] = F, np.array(names)
+        with contextlib.redirect_stdout(io.StringIO()):
+            out[key + "__specgram"] = ref_st.spectrogram(x.astype(np.float64), fs, window, step)[0]
+        if F.shape[1] >= 4:
+            mid_w, mid_s = live.mid_term_window(window, step)
+            mid, _, mid_names = ref_mt.mid_feature_extraction(x.astype(np.float64), fs, mid_w, mid_s, window, step)
+            out[key + "__mid"], out[key + "__mid_names"] = mid, np.array(mid_names)
+    for fs, window, step, n in live.CHROMA_TAIL_CASES:
+        key = live.chroma_case_key(fs, window, step, n)
+        x = synth_clip(7300 + step, n, fs)
+        out[key + "__input_sha256"] = sha(x)
+        try:
+            out[key + "__chromagram"] = ref_st.chromagram(x.astype(np.float64), fs, window, step)[0]
+        except Exception as exc:
+            out[key + "__error"] = np.array(type(exc).__name__)
+    np.savez_compressed(os.path.join(OUT, "live_reference_sweep.npz"), **out)
+    print("live_reference_sweep.npz", len(out))
+
+    glue = _test_module("test_silence_glue_cpu")
+    ref_seg = load_reference.load_segmentation()
+    out = {"kind": np.array("silence_glue")}
+    for seed, st_win, st_step, smooth, weight in glue.GLUE_CASES:
+        key = glue.glue_case_key(seed)
+        x = glue.glue_signal(seed)
+        out[key + "__input_sha256"] = sha(x)
+        np.random.seed(99)
+        segs = ref_seg.silence_removal(x, glue.GLUE_FS, st_win, st_step, smooth, weight)
+        out[key + "__segments"] = np.array(segs, dtype=np.float64).reshape(-1, 2)
+    np.savez_compressed(os.path.join(OUT, "live_reference_silence_glue.npz"), **out)
+    print("live_reference_silence_glue.npz", len(out))
+
+
+if __name__ == "__main__" and "--live" in sys.argv:
+    live_goldens()

@@ -1,11 +1,14 @@
 """CPU tests of the host-side glue of audioSegmentation.silence_removal (row f4): smoothing, thresholds and the grouping
 of frame indices into segments.  The GPU pieces (short-term features, per-frame SVM probability) are replaced by their
 CPU checkers here -- the oracle's feature_extraction and scikit-learn's predict_proba -- so that the glue can be compared
-with the UNMODIFIED reference running in the same process (skipped where /root/reference is absent)."""
+with what the UNMODIFIED reference returned on the same signals (tests/golden/live_reference_silence_glue.npz, written by
+`python oracle/make_golden.py --live` from GLUE_CASES)."""
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
-import load_reference
 import paa_oracle as O
 from pyaudioanalysis_amd import audioSegmentation
 from synth import synth_clip
@@ -55,18 +58,33 @@ def test_onset_threshold_mixes_the_extreme_tenths():
     assert abs(thr - (0.75 * p[:10].mean() + 0.25 * p[-10:].mean())) < 1e-15
 
 
-@pytest.mark.skipif(not load_reference.reference_available(), reason="needs the reference tree")
-@pytest.mark.parametrize("seed,st_win,st_step,smooth,weight", [(1, 0.050, 0.050, 0.5, 0.5), (2, 0.020, 0.020, 1.0, 0.3),
-                                                              (3, 0.050, 0.025, 0.5, 0.7), (4, 0.050, 0.050, 0.3, 1.5)])
-def test_glue_matches_live_reference(monkeypatch, seed, st_win, st_step, smooth, weight):
-    pytest.importorskip("sklearn.svm")
-    ref_seg = load_reference.load_segmentation()
-    fs = 16000
-    x = synth_clip(500 + seed, 6 * fs).copy()
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_reference_silence_glue.npz")
+GLUE_FS = 16000
+GLUE_CASES = [(1, 0.050, 0.050, 0.5, 0.5), (2, 0.020, 0.020, 1.0, 0.3), (3, 0.050, 0.025, 0.5, 0.7), (4, 0.050, 0.050, 0.3, 1.5)]
+
+
+def glue_case_key(seed):
+    return "glue_%d" % seed
+
+
+def glue_signal(seed):
+    x = synth_clip(500 + seed, 6 * GLUE_FS).copy()
     rng = np.random.default_rng(seed)
     for _ in range(4):                                                      # digital silence between bursts
-        a = int(rng.integers(0, 5 * fs))
-        x[a:a + int(rng.integers(fs // 4, fs))] = 0
+        a = int(rng.integers(0, 5 * GLUE_FS))
+        x[a:a + int(rng.integers(GLUE_FS // 4, GLUE_FS))] = 0
+    return x
+
+
+@pytest.mark.parametrize("seed,st_win,st_step,smooth,weight", GLUE_CASES)
+def test_glue_matches_live_reference(monkeypatch, seed, st_win, st_step, smooth, weight):
+    pytest.importorskip("sklearn.svm")
+    fs = GLUE_FS
+    x = glue_signal(seed)
+    key = glue_case_key(seed)
+    with np.load(GOLDEN, allow_pickle=False) as z:
+        assert str(z[key + "__input_sha256"]) == hashlib.sha256(x.tobytes()).hexdigest(), key
+        want = z[key + "__segments"]
 
     from pyaudioanalysis_amd import ShortTermFeatures as product_stf
     monkeypatch.setattr(product_stf, "feature_extraction",
@@ -77,11 +95,8 @@ def test_glue_matches_live_reference(monkeypatch, seed, st_win, st_step, smooth,
                          for i in range(st_feats.shape[1])])
     monkeypatch.setattr(audioSegmentation, "svm_onset_probability", predict_loop)
 
-    np.random.seed(99)
-    want = ref_seg.silence_removal(x, fs, st_win, st_step, smooth, weight)
-    np.random.seed(99)
+    np.random.seed(99)        # (the reference's segments were computed after the same seed)
     got = audioSegmentation.silence_removal(x, fs, st_win, st_step, smooth, weight)
-    want = np.array(want, dtype=np.float64).reshape(-1, 2)
     got = np.array(got, dtype=np.float64).reshape(-1, 2)
     assert got.shape == want.shape and got.shape[0] >= 1, (got, want)
     assert np.allclose(got, want, rtol=0, atol=1e-9), (got, want)
