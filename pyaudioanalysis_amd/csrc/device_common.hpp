@@ -319,6 +319,15 @@ __device__ __forceinline__ double mag_sqrt(double x) {
     const double r = fma(-h, g, 0.5);
     return fma(g, r, g);
 }
+// s * mag_sqrt(x) with the scale folded into the Newton step: g (1 + r) s = g (1.5 s - 0.5 s g y), i.e. g * fma(g, y c1, c2)
+// with the wave-uniform c1 = -0.5 s, c2 = 1.5 s -- four FP64 operations instead of five (same seed, same single step;
+// one rounding more than mag_sqrt(x) * s, a few 1e-16 relative).  x = 0 gives exactly 0.
+__device__ __forceinline__ double mag_sqrt_scaled(double x, double c1, double c2) {
+    const unsigned hi_ = max((unsigned)__double2hiint(x), 0x01a56e1fu);         // high dword of 1e-300 (see mag_sqrt)
+    const double y = __builtin_amdgcn_rsq(__hiloint2double((int)hi_, __double2loint(x)));
+    const double g = x * y;
+    return g * fma(g, y * c1, c2);
+}
 
 // a / b for finite b != 0 to ~1 ulp: v_rcp_f64 seed, two Newton steps, one residual correction (the IEEE
 // division sequence -- div_scale / div_fmas / div_fixup -- is a ~150-cycle dependent chain per quotient)

@@ -177,6 +177,59 @@ __device__ __forceinline__ void dft25_tail(double2 *v) {
 }
 #define PAA_DFT25_POS(q) (5 * ((q) % 5) + (q) / 5)
 
+// a + w x and 2 a - (a + w x) = a - w x: two FMA chains and one FMA per component instead of cmul + add + sub
+__device__ __forceinline__ void tw_butterfly(double2 &a, double2 &x, double2 w) {
+    const double2 p = make_double2(fma(w.x, x.x, fma(-w.y, x.y, a.x)), fma(w.x, x.y, fma(w.y, x.x, a.y)));
+    x = make_double2(fma(2.0, a.x, -p.x), fma(2.0, a.y, -p.y));
+    a = p;
+}
+// dft5r from the butterfly sums t1 = a1 + a4, t2 = a2 + a3 and differences t3 = a1 - a4, t4 = a2 - a3 (same operations)
+__device__ __forceinline__ void dft5r_sums(double2 &a0, double2 t1, double2 t2, double2 t3, double2 t4, double2 &a1,
+                                           double2 &a2, double2 &a3, double2 &a4) {
+    const double c1 = 0.30901699437494742410;
+    const double s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;
+    const double2 d = csub(t1, t2);
+    const double2 h1 = make_double2(fma(-0.5, t1.x, a0.x), fma(-0.5, t1.y, a0.y));
+    const double2 h2 = make_double2(fma(-0.5, t2.x, a0.x), fma(-0.5, t2.y, a0.y));
+    const double2 m1 = make_double2(fma(c1, d.x, h2.x), fma(c1, d.y, h2.y));
+    const double2 m2 = make_double2(fma(-c1, d.x, h1.x), fma(-c1, d.y, h1.y));
+    const double2 n1 = make_double2(fma(s2, t4.x, s1 * t3.x), fma(s2, t4.y, s1 * t3.y));
+    const double2 n2 = make_double2(fma(-s1, t4.x, s2 * t3.x), fma(-s1, t4.y, s2 * t3.y));
+    a0 = make_double2(a0.x + t1.x + t2.x, a0.y + t1.y + t2.y);
+    a1 = sub_i(m1, n1);
+    a4 = add_i(m1, n1);
+    a2 = sub_i(m2, n2);
+    a3 = add_i(m2, n2);
+}
+// W25^m as literal constants (folded at compile time), m = r2 q1 in 1..16
+__device__ __forceinline__ double2 w25_const(int m) {
+    const double cr = (m == 1) ? 0.96858316112863108 : (m == 2) ? 0.87630668004386358 : (m == 3) ? 0.72896862742141155
+                    : (m == 4) ? 0.53582679497899666 : (m == 6) ? 0.06279051952931337 : (m == 8) ? -0.42577929156507272
+                    : (m == 9) ? -0.63742398974868975 : (m == 12) ? -0.99211470131447788 : -0.63742398974868975;
+    const double ci = (m == 1) ? -0.24868988716485479 : (m == 2) ? -0.48175367410171532 : (m == 3) ? -0.68454710592868873
+                    : (m == 4) ? -0.84432792550201508 : (m == 6) ? -0.99802672842827156 : (m == 8) ? -0.90482705246601958
+                    : (m == 9) ? -0.77051324277578925 : (m == 12) ? -0.12533323356430426 : 0.77051324277578925;
+    return make_double2(cr, ci);
+}
+// dft25_tail with the twiddles W25^(r2 q1) folded into the second stage's butterflies: a1 +- a4 = w1 x1 +- w4 x4 and
+// a2 +- a3 as one complex multiply and one tw_butterfly each (10 FP64 operations per pair instead of 12).  Row q1 = 0 has
+// no twiddles and keeps dft5r (five equal inputs -> exact zeros).
+template <int SERIAL>
+__device__ __forceinline__ void dft25_tail_tw(double2 *v) {
+    dft5r(v[0], v[1], v[2], v[3], v[4]);
+    if (SERIAL) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q1 = 1; q1 < 5; ++q1) {
+        double2 *u = v + 5 * q1;
+        double2 t1 = cmul(u[1], w25_const(q1)), t3 = u[4];
+        double2 t2 = cmul(u[2], w25_const(2 * q1)), t4 = u[3];
+        tw_butterfly(t1, t3, w25_const(4 * q1));
+        tw_butterfly(t2, t4, w25_const(3 * q1));
+        dft5r_sums(u[0], t1, t2, t3, t4, u[1], u[2], u[3], u[4]);
+        if (SERIAL) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // First-stage radix-5 butterfly straight from five packed int16 pairs (lo = real, hi = imaginary part) minus the
 // integer clip mean m: the sums and differences a1 +- a4, a2 +- a3 and a0 + a1 + .. + a4 are whole numbers, so they
 // are formed in 32-bit integer arithmetic (half the issue cost of FP64 on gfx950) and converted once.  Same values as
@@ -215,18 +268,25 @@ __device__ __forceinline__ void dft25_packed(const int *w, int m, double2 *v) {
         dft5r_first(w[r2], w[5 + r2], w[10 + r2], w[15 + r2], w[20 + r2], m, v[r2], v[5 + r2], v[10 + r2], v[15 + r2], v[20 + r2]);
         if (SERIAL) __builtin_amdgcn_sched_barrier(0);
     }
-    dft25_tail<SERIAL>(v);
+    dft25_tail_tw<SERIAL>(v);
 }
 
 // v[r], r = 4 r1 + r2  ->  result for output q stored at v[4 (q % 4) + q / 4]
+template <int SERIAL>
+__device__ __forceinline__ void dft16_tail(double2 *v);
 template <int SERIAL = 0>
 __device__ __forceinline__ void dft16(double2 *v) {
-    const double c = 0.92387953251128676, s = 0.38268343236508977, h = 0.70710678118654752;
 #pragma unroll
     for (int r2 = 0; r2 < 4; ++r2) {
         dft4r(v[r2], v[4 + r2], v[8 + r2], v[12 + r2]);
         if (SERIAL) __builtin_amdgcn_sched_barrier(0);
     }
+    dft16_tail<SERIAL>(v);
+}
+// internal twiddles W16^(r2 q1) and the second radix-4 stage of dft16
+template <int SERIAL>
+__device__ __forceinline__ void dft16_tail(double2 *v) {
+    const double c = 0.92387953251128676, s = 0.38268343236508977, h = 0.70710678118654752;
     // twiddles W16^(r2 q1) at index 4 q1 + r2
     v[5] = cmul(v[5], make_double2(c, -s));        // m = 1
     v[6] = make_double2(h * (v[6].x + v[6].y), h * (v[6].y - v[6].x));    // m = 2: (h, -h)
@@ -243,6 +303,38 @@ __device__ __forceinline__ void dft16(double2 *v) {
         dft4r(v[4 * q1], v[4 * q1 + 1], v[4 * q1 + 2], v[4 * q1 + 3]);
         if (SERIAL) __builtin_amdgcn_sched_barrier(0);
     }
+}
+// dft16 of the twiddled inputs a[r] W^r and b[r] conj(W^r) (pass 2 of the 400-point transform: columns p and 25 - p share
+// conjugate twiddles; tw(r) returns W^r for r = 1..15, a[0] / b[0] are not twiddled).  The twiddles are folded into the first
+// radix-4 stage: its butterflies a0 +- a2, a1 +- a3 become a0 +- w x2 (tw_butterfly), so only the inputs r = 1..7 pay a
+// complex multiply.  SERIAL = 1: one butterfly pair at a time, its four twiddles fetched right before it.
+template <int SERIAL, typename TwF>
+__device__ __forceinline__ void dft16_tw_pair(double2 *a, double2 *b, TwF tw) {
+#pragma unroll
+    for (int r2 = 0; r2 < 4; ++r2) {
+        const double2 w1 = tw(4 + r2), w2 = tw(8 + r2), w3 = tw(12 + r2);
+        const double2 w0 = (r2 == 0) ? make_double2(1.0, 0.0) : tw(r2);
+        const double2 w0c = make_double2(w0.x, -w0.y), w1c = make_double2(w1.x, -w1.y);
+        const double2 w2c = make_double2(w2.x, -w2.y), w3c = make_double2(w3.x, -w3.y);
+        double2 a0 = (r2 == 0) ? a[0] : cmul(a[r2], w0), a1 = cmul(a[4 + r2], w1), a2 = a[8 + r2], a3 = a[12 + r2];
+        double2 b0 = (r2 == 0) ? b[0] : cmul(b[r2], w0c), b1 = cmul(b[4 + r2], w1c), b2 = b[8 + r2], b3 = b[12 + r2];
+        // dft4r with t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = a1 - a3
+        tw_butterfly(a0, a2, w2);
+        tw_butterfly(a1, a3, w3);
+        tw_butterfly(b0, b2, w2c);
+        tw_butterfly(b1, b3, w3c);
+        a[r2] = cadd(a0, a1);
+        a[8 + r2] = csub(a0, a1);
+        a[4 + r2] = sub_i(a2, a3);
+        a[12 + r2] = add_i(a2, a3);
+        b[r2] = cadd(b0, b1);
+        b[8 + r2] = csub(b0, b1);
+        b[4 + r2] = sub_i(b2, b3);
+        b[12 + r2] = add_i(b2, b3);
+        if (SERIAL) __builtin_amdgcn_sched_barrier(0);
+    }
+    dft16_tail<SERIAL>(a);
+    dft16_tail<SERIAL>(b);
 }
 #define PAA_DFT16_POS(q) (4 * ((q) % 4) + (q) / 4)
 
@@ -471,6 +563,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     const double delta_mu = nm.delta_mu;                                         // |.| <= 1/2
     const double y_scale2 = nm.y_scale2;                                         // y = (x' - delta) * inv / 2^15
     const double mag_scale = nm.mag_scale;                                       // 0.5: E and O carry a factor 1/2
+    const double mag_c1 = uni(-0.5 * mag_scale), mag_c2 = uni(1.5 * mag_scale);  // mag_sqrt_scaled's Newton constants
     const double dc_shift = nm.dc_shift;
     // sign(x/2^15 - mean) = sign(x - mu) in packed 16-bit integers (mu lies inside the int16 range: it is a mean of int16)
     // as non-negative sign CODES (device_common.hpp: only |differences| are summed): code = clamp(sat(x - (zb - 1)), lo, 2),
@@ -677,52 +770,41 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
                 const int k = pa + 25 * (q);                                                               \
                 const double2 e = make_double2(zk.x + zb.x, zk.y - zb.y);                                  \
                 const double2 o = make_double2(zk.y + zb.y, zb.x - zk.x);                                  \
-                const double2 t = cmul((wpq), o);                                                          \
-                double xr = e.x + t.x, xi = e.y + t.y;                                                     \
-                const double yr = e.x - t.x, yi = e.y - t.y;                                               \
+                /* X[k] = E + w O as two FMA chains, conj X[400 - k] = E - w O = 2 E - X[k] */             \
+                const double2 w_ = (wpq);                                                                  \
+                double xr = fma(w_.x, o.x, fma(-w_.y, o.y, e.x)), xi = fma(w_.x, o.y, fma(w_.y, o.x, e.y)); \
+                const double yr = fma(2.0, e.x, -xr), yi = fma(2.0, e.y, -xi);                             \
                 /* DC bin (q = 0 in lane 0): remove the residual clip mean; straight-line selects, no branch */ \
                 const bool dc_ = ((q) == 0) && (i == 0);                                                   \
                 xr = dc_ ? xr - dc_shift : xr;                                                             \
                 xi = dc_ ? 0.0 : xi;                                                                       \
-                const double mk_ = mag_sqrt(fma(xr, xr, xi * xi)) * mag_scale;                             \
+                const double mk_ = mag_sqrt_scaled(fma(xr, xr, xi * xi), mag_c1, mag_c2);                 \
                 sp[k] = mk_;                                                                               \
                 /* bin 400 - k; the DC lane has no partner bin and stores |X[0]| to bin 0 a second time */ \
-                const double mm_ = mag_sqrt(fma(yr, yr, yi * yi)) * mag_scale;                             \
+                const double mm_ = mag_sqrt_scaled(fma(yr, yr, yi * yi), mag_c1, mag_c2);                 \
                 if ((q) == 0) sp[dc_ ? 0 : NF - k] = dc_ ? mk_ : mm_;                                      \
                 else sp[NF - k] = mm_;                                                                     \
             }
-            if (NW == 4) {
 #pragma unroll
-                for (int r = 1; r < 16; ++r) {
-                    a[r] = cmul(make_double2(ax[r], ay[r]), w2[r]);
-                    b[r] = cmul(make_double2(bx[r], by[r]), make_double2(w2[r].x, -w2[r].y));
-                }
+            for (int r = 1; r < 16; ++r) {
+                a[r] = make_double2(ax[r], ay[r]);
+                b[r] = make_double2(bx[r], by[r]);
+            }
+            // the input twiddles W400^(r p) (conjugated for column 25 - p) are applied inside the transforms' first stage
+            if (NW == 4) {
                 double2 wp[16];   // W800^(p + 25 q): in flight during the two radix-16 transforms
 #pragma unroll
                 for (int q = 0; q < 16; ++q) wp[q] = t_twp[q * TW_STRIDE + itw];
-                dft16<0>(a);
-                dft16<0>(b);
+                dft16_tw_pair<0>(a, b, [&](int r) { return w2[r]; });
 #pragma unroll
                 for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(a[r].x), "+v"(a[r].y), "+v"(b[r].x), "+v"(b[r].y));
 #pragma unroll
                 for (int q = 0; q < 16; ++q) PAA_F800_BIN(q, wp[q])
             } else {
                 // two waves per SIMD: registers matter more than latency (the partner wave hides it), so the table
-                // values are fetched in small groups right before their use and the scheduler may not hoist them
-#pragma unroll
-                for (int r0 = 1; r0 < 16; r0 += 3) {
-                    double2 wg[3];
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) wg[u] = t_tw2[(r0 + u) * TW_STRIDE + itw];
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) {
-                        a[r0 + u] = cmul(make_double2(ax[r0 + u], ay[r0 + u]), wg[u]);
-                        b[r0 + u] = cmul(make_double2(bx[r0 + u], by[r0 + u]), make_double2(wg[u].x, -wg[u].y));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                dft16<1>(a);
-                dft16<1>(b);
+                // values are fetched in small groups right before their use (per first-stage butterfly of dft16_tw_pair)
+                // and the scheduler may not hoist them
+                dft16_tw_pair<1>(a, b, [&](int r) { return t_tw2[r * TW_STRIDE + itw]; });
                 // pin the transforms here: without it the optimiser sinks their second stages into the bin loop below
                 // and both input sets stay live next to the partial results
 #pragma unroll
@@ -758,7 +840,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // sum(ind * X) with ind = (k+1) f0 is f0 * [(25 i + 1) * sum X + sum m X]   (small exact integers)
         // X^2 is accumulated in five 5-bin chunks: their sum is the lane total (roll-off scan), and cut at the lane's
         // 40-bin block boundary they give the spectral-entropy block energies (:85-107) without a second sweep.
-        double sXa = 0.0, sXb = 0.0, sMa = 0.0, sMb = 0.0, sVa = 0.0, sVb = 0.0, mx = 0.0;
+        // sum(m^2 X) (spread, below) rides along: m^2 is a compile-time constant
+        double sXa = 0.0, sXb = 0.0, sMa = 0.0, sMb = 0.0, sQa = 0.0, sQb = 0.0, sVa = 0.0, sVb = 0.0, mx = 0.0;
         double c5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int m = 0; m < 24; m += 2) {
@@ -766,10 +849,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             sXa += X0; sXb += X1;
             sVa += Xv[m]; sVb += Xv[m + 1];
             sMa = fma((double)m, X0, sMa); sMb = fma((double)(m + 1), X1, sMb);
+            sQa = fma((double)(m * m), X0, sQa); sQb = fma((double)((m + 1) * (m + 1)), X1, sQb);
             c5[m / 5] = fma(X0, X0, c5[m / 5]); c5[(m + 1) / 5] = fma(X1, X1, c5[(m + 1) / 5]);
             mx = fmax(mx, fmax(X0, X1));
         }
-        sXa += Xc[24]; sVa += Xv[24]; sMa = fma(24.0, Xc[24], sMa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = fmax(mx, Xc[24]);
+        sXa += Xc[24]; sVa += Xv[24]; sMa = fma(24.0, Xc[24], sMa); sQa = fma(576.0, Xc[24], sQa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = fmax(mx, Xc[24]);
         const double cs = ((c5[0] + c5[1]) + (c5[2] + c5[3])) + c5[4];
         // Lane i holds bins [25 i, 25 i + 25); block b holds bins [40 b, 40 b + 40).  The first kcut chunks of the lane
         // lie in block floor(25 i / 40), the rest in the next one; the pattern repeats every 8 lanes (200 bins):
@@ -791,7 +875,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         const bool home = ((0xB5u >> (i & 7)) & 1u) != 0;          // i & 7 in {0, 2, 4, 5, 7}
         const double base_k = (double)(25 * i + 1);
         double sX = sXa + sXb;
-        double sIX = f0 * fma(base_k, sX, sMa + sMb);
+        const double sXl = sX, sMl = sMa + sMb;        // the lane's own sum X, sum m X (spread)
+        double sIX = f0 * fma(base_k, sX, sMl);
         double sXp = sVa + sVb;
         sX = group_sum(sX); sXp = group_sum(sXp);
         sIX = group_sum(sIX); mx = group_max(mx);
@@ -821,25 +906,23 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         const double rden = fast_div(1.0, den);
         const double cen = (sIX * r) * rden;
         const double rX = fast_div(1.0, sXe), rXp = fast_div(1.0, sXp);
-        // spread: sum (ind - C)^2 X / max = f0^2/max * sum ((k+1) - C/f0)^2 X
+        // spread: sum (ind - C)^2 X / max = f0^2/max * sum ((k+1) - C/f0)^2 X; over the lane's bins k + 1 = base_k + m:
+        // sum (cb + m)^2 X = cb (cb sum X + 2 sum m X) + sum m^2 X from the sums of sweep A (|cb + m| < 400, so the terms
+        // exceed the result by at most 400^2 / (smallest (cb + m)^2) where that bin dominates: far below T_ROW_SPREAD)
         const double cb = base_k - cen * rf0;
-        double sSa = 0.0, sSb = 0.0, sFa = 0.0, sFb = 0.0;
+        double sFa = 0.0, sFb = 0.0;
 #pragma unroll
         for (int m = 0; m < 24; m += 2) {
-            const double d0 = cb + (double)m, d1 = cb + (double)(m + 1);
-            sSa = fma(d0 * d0, Xc[m], sSa);
-            sSb = fma(d1 * d1, Xc[m + 1], sSb);
             const double f0d = Xc[m] * rX - Xv[m] * rXp, f1d = Xc[m + 1] * rX - Xv[m + 1] * rXp;
             sFa = fma(f0d, f0d, sFa);
             sFb = fma(f1d, f1d, sFb);
         }
         {
-            const double d0 = cb + 24.0;
-            sSa = fma(d0 * d0, Xc[24], sSa);
             const double f0d = Xc[24] * rX - Xv[24] * rXp;
             sFa = fma(f0d, f0d, sFa);
         }
-        double sSp = (sSa + sSb) * (f0sq * r), sFl = sFa + sFb;
+        const double sSl = fma(cb, fma(cb, sXl, 2.0 * sMl), sQa + sQb);
+        double sSp = sSl * (f0sq * r), sFl = sFa + sFb;
         sSp = group_sum(sSp);
         sFl = group_sum(sFl);
         const double spread = fast_sqrt(sSp * rden);
