@@ -220,6 +220,30 @@ int paa_svm_binary_proba_f64(const double *feats, int n_dims, int64_t n_frames, 
                              const double *support_vectors, const double *dual_coef, int n_sv, double intercept,
                              double gamma, double prob_a, double prob_b, double *prob1);
 
+/* ---- audioTrainTest.classifier_wrapper for SVM models (audioTrainTest.py:84-93) --------------------------------------
+ * predict() and predict_proba() of a TRAINED multi-class probabilistic scikit-learn SVC (SVC(probability=True), kernel
+ * 'rbf' or 'linear') for many feature vectors at once: what mid_term_file_classification (audioSegmentation.py:583-594) and
+ * file_classification (audioTrainTest.py:1091-1095) ask for once per vector.  The model is libsvm's as scikit-learn holds
+ * it: support_vectors [n_sv][n_dims] grouped by class, n_support [n_classes], dual_coef [n_classes - 1][n_sv] (libsvm's
+ * sv_coef = scikit-learn's _dual_coef_), rho / prob_a / prob_b [n_classes (n_classes - 1) / 2] (rho = -_intercept_),
+ * kernel_type 0 (LINEAR) or 2 (RBF, with gamma = _gamma).  2 <= n_classes <= 16, n_dims <= 256: anything else returns
+ * PAA_ERR_ARG.  The model is uploaded once (paa_svc_create) and stays on the device until paa_svc_destroy.
+ * feats is feature-major [n_dims][ld] (the mid-term matrix layout), vector v in column v; each is standardised on load,
+ * (x - mean) / std (audioSegmentation.py:586).  label_index [n_vec] receives libsvm's vote winner (first maximum; the
+ * caller maps it through classes_), proba [n_vec][n_classes] predict_proba's row.                                    */
+int paa_svc_create(const double *support_vectors, int n_sv, int n_dims, const int32_t *n_support, int n_classes,
+                   const double *dual_coef, const double *rho, const double *prob_a, const double *prob_b, int kernel_type,
+                   double gamma, void **out_handle);
+int paa_svc_destroy(void *handle);
+int paa_svc_num_classes(const void *handle);
+/* host buffers in and out (synchronous) */
+int paa_svc_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, const double *mean,
+                        const double *std, int32_t *label_index, double *proba);
+/* device buffers in and out (the resident mid-term matrix of a plan, paa_plan_mid_execute), asynchronous on the library
+ * stream; at most one of these is in flight per process (they share a scratch buffer, in stream order)                */
+int paa_svc_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
+                            const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

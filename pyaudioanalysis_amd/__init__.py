@@ -8,7 +8,7 @@ fallback: importing works anywhere, computing needs the built library and a HIP 
 
     from pyaudioanalysis_amd import ShortTermFeatures, MidTermFeatures
 """
-from . import MidTermFeatures, ShortTermFeatures, audioSegmentation  # noqa: F401
+from . import MidTermFeatures, ShortTermFeatures, audioSegmentation, audioTrainTest  # noqa: F401
 
-__all__ = ["ShortTermFeatures", "MidTermFeatures", "audioSegmentation"]
+__all__ = ["ShortTermFeatures", "MidTermFeatures", "audioSegmentation", "audioTrainTest"]
 __version__ = "0.1.0"

@@ -95,6 +95,13 @@ _SIGNATURES = {
                                            C.c_void_p, c_i64p]),
     "paa_svm_binary_proba_f64": (C.c_int, [c_f64p, C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_double,
                                            C.c_double, C.c_double, C.c_double, c_f64p]),
+    "paa_svc_create": (C.c_int, [c_f64p, C.c_int, C.c_int, c_i32p, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int,
+                                 C.c_double, C.POINTER(C.c_void_p)]),
+    "paa_svc_destroy": (C.c_int, [C.c_void_p]),
+    "paa_svc_num_classes": (C.c_int, [C.c_void_p]),
+    "paa_svc_predict_f64": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int64, C.c_int64, c_f64p, c_f64p, c_i32p, c_f64p]),
+    "paa_svc_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "paa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "paa_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "paa_comm_destroy": (C.c_int, []),

@@ -235,3 +235,235 @@ def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, w
     if plot:
         _plot_segments(mono, sampling_rate, prob, st_step, seg_limits)
     return seg_limits
+
+
+# ---------------------------------------------------------------------------------------------------------
+# fix-sized segment classification with the shipped SVM models (reference :58-125, :150-175, :495-633)
+# ---------------------------------------------------------------------------------------------------------
+def labels_to_segments(labels, window):
+    """Fix-sized class labels -> (segments [n][2] of start / end in seconds, class of each segment) (reference :58-98)."""
+    if len(labels) == 1:
+        segs = [0, window]
+        classes = labels
+        return segs, classes
+    num_segs = 0
+    index = 0
+    classes = []
+    segment_list = []
+    cur_label = labels[index]
+    while index < len(labels) - 1:
+        previous_value = cur_label
+        while True:
+            index += 1
+            compare_flag = labels[index]
+            if (compare_flag != cur_label) | (index == len(labels) - 1):
+                num_segs += 1
+                cur_label = labels[index]
+                segment_list.append((index * window))
+                classes.append(previous_value)
+                break
+    segments = np.zeros((len(segment_list), 2))
+    for i in range(len(segment_list)):
+        if i > 0:
+            segments[i, 0] = segment_list[i - 1]
+        segments[i, 1] = segment_list[i]
+    return segments, classes
+
+
+def segments_to_labels(start_times, end_times, labels, window):
+    """Segment end points and labels -> (fix-sized class indices, class names) (reference :101-125).  The class names
+    come from list(set(labels)), so their order follows Python's string hashing, as in the reference."""
+    flags = []
+    class_names = list(set(labels))
+    index = window / 2.0
+    while index < end_times[-1]:
+        for i in range(len(start_times)):
+            if start_times[i] < index <= end_times[i]:
+                break
+        flags.append(class_names.index(labels[i]))
+        index += window
+    return np.array(flags), class_names
+
+
+def read_segmentation_gt(gt_file):
+    """<start>\\t<end>\\t<label> rows of a ground-truth file -> (starts, ends, labels) (reference :150-175)."""
+    import csv
+    with open(gt_file, 'rt') as f_handle:
+        reader = csv.reader(f_handle, delimiter='\t')
+        start_times = []
+        end_times = []
+        labels = []
+        for row in reader:
+            if len(row) == 3:
+                start_times.append(float(row[0]))
+                end_times.append(float(row[1]))
+                labels.append((row[2]))
+    return np.array(start_times), np.array(end_times), labels
+
+
+def plot_segmentation_results(flags_ind, flags_ind_gt, class_names, mt_step, evaluate_only=False):
+    """Accuracy of fix-sized labels against the ground truth (reference :178-247); the per-class statistics and the
+    matplotlib figure only when evaluate_only is False."""
+    flags = [class_names[int(f)] for f in flags_ind]
+    segments, classes = labels_to_segments(flags, mt_step)
+    min_len = min(flags_ind.shape[0], flags_ind_gt.shape[0])
+    if min_len > 0:
+        accuracy = np.sum(flags_ind[0:min_len] == flags_ind_gt[0:min_len]) / float(min_len)
+    else:
+        accuracy = -1
+    if not evaluate_only:
+        import matplotlib.pyplot as plt
+        duration = segments[-1, 1]
+        s_percentages = np.zeros((len(class_names), ))
+        percentages = np.zeros((len(class_names), ))
+        av_durations = np.zeros((len(class_names), ))
+        for i_seg in range(segments.shape[0]):
+            s_percentages[class_names.index(classes[i_seg])] += (segments[i_seg, 1] - segments[i_seg, 0])
+        for i in range(s_percentages.shape[0]):
+            percentages[i] = 100.0 * s_percentages[i] / duration
+            class_sum = sum(1 for c in classes if c == class_names[i])
+            av_durations[i] = s_percentages[i] / class_sum if class_sum > 0 else 0.0
+        for i in range(percentages.shape[0]):
+            print(class_names[i], percentages[i], av_durations[i])
+        fig = plt.figure()
+        ax1 = fig.add_subplot(211)
+        ax1.set_yticks(np.array(range(len(class_names))))
+        ax1.axis((0, duration, -1, len(class_names)))
+        ax1.set_yticklabels(class_names)
+        ax1.plot(np.array(range(len(flags_ind))) * mt_step + mt_step / 2.0, flags_ind)
+        if flags_ind_gt.shape[0] > 0:
+            ax1.plot(np.array(range(len(flags_ind_gt))) * mt_step + mt_step / 2.0, flags_ind_gt + 0.05, '--r')
+        plt.xlabel("time (seconds)")
+        if accuracy >= 0:
+            plt.title('Accuracy = {0:.1f}%'.format(100.0 * accuracy))
+        ax2 = fig.add_subplot(223)
+        plt.title("Classes percentage durations")
+        ax2.bar(np.array(range(len(class_names))) + 0.5, percentages)
+        ax3 = fig.add_subplot(224)
+        plt.title("Segment average duration per class")
+        ax3.bar(np.array(range(len(class_names))) + 0.5, av_durations)
+        fig.tight_layout()
+        plt.show()
+    return accuracy
+
+
+def load_ground_truth_segments(gt_file, mt_step):
+    """Reference :495-508."""
+    seg_start, seg_end, seg_labels = read_segmentation_gt(gt_file)
+    labels, class_names = segments_to_labels(seg_start, seg_end, seg_labels, mt_step)
+    labels_temp = []
+    for index, label in enumerate(labels):
+        if class_names[labels[index]] in class_names:
+            labels_temp.append(class_names.index(class_names[labels[index]]))
+        else:
+            labels_temp.append(-1)
+    return np.array(labels_temp), class_names
+
+
+def calculate_confusion_matrix(predictions, ground_truth, classes):
+    """Reference :511-516: rows ground truth, columns predictions."""
+    cm = np.zeros((len(classes), len(classes)))
+    for index in range(min(predictions.shape[0], ground_truth.shape[0])):
+        cm[int(ground_truth[index]), int(predictions[index])] += 1
+    return cm
+
+
+def load_ground_truth(gt_file, labels, class_names, mid_step, plot_results):
+    """Reference :606-633: (ground-truth labels, class names, accuracy, confusion matrix) when gt_file exists."""
+    import os
+    accuracy = 0
+    cm = np.array([])
+    labels_gt = np.array([])
+    if os.path.isfile(gt_file):
+        labels_gt, class_names_gt = load_ground_truth_segments(gt_file, mid_step)
+        labels_new = []
+        for il, l in enumerate(labels):
+            if class_names[int(l)] in class_names_gt:
+                labels_new.append(class_names_gt.index(class_names[int(l)]))
+            else:
+                labels_new.append(-1)
+        labels_new = np.array(labels_new)
+        cm = calculate_confusion_matrix(labels_new, labels_gt, class_names_gt)
+        accuracy = plot_segmentation_results(labels_new, labels_gt, class_names_gt, mid_step, not plot_results)
+        if accuracy >= 0:
+            print("Overall Accuracy: {0:.2f}".format(accuracy))
+    return labels_gt, class_names, accuracy, cm
+
+
+def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_step, st_win, st_step):
+    """Labels and max-probabilities of every mid-term window of a mono signal (reference :574-594): the mid-term matrix
+    stays in HBM and goes straight into the SVC kernel (one launch for all windows).  Returns (labels, posterior max)."""
+    from . import MidTermFeatures, audioTrainTest
+    ratio, step_ratio = MidTermFeatures._ratios(mt_win * sampling_rate, mid_step * sampling_rate,
+                                                round(sampling_rate * st_win), round(sampling_rate * st_step))
+    if step_ratio < 1:
+        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
+    window, step = int(round(sampling_rate * st_win)), int(round(sampling_rate * st_step))
+    kind, sig = _ffi.classify_signal(signal)
+    if kind == 2:
+        raise ValueError("mono signal expected (audioBasicIO.stereo_to_mono first)")
+    n = sig.shape[0]
+    if window < 1 or step < 1 or n < window:
+        raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
+    model = audioTrainTest.svc_model(classifier)
+    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
+    try:
+        d_in = _ffi.DeviceBuffer.from_host(sig)
+        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
+        plan.execute(d_in, d_st)
+        n_mid = plan.mid_doubles(step_ratio)
+        d_mid = _ffi.DeviceBuffer(n_mid * 8)
+        plan.mid_execute(d_st, ratio, step_ratio, d_mid)
+        M = n_mid // (2 * 68)
+        idx, proba = model.predict_device(d_mid, M, M, mean, std)
+        for b in (d_in, d_st, d_mid):
+            b.free()
+    finally:
+        plan.destroy()
+    return model.classes[idx], np.max(proba, axis=1)
+
+
+def mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step,
+                            compute_beat=False, plot_results=False, gt_file=""):
+    """mid_term_file_classification on a signal and a loaded SVM model (reference :518-604 from :562 on):
+    returns (labels, class_names, accuracy, cm)."""
+    labels = []
+    accuracy = 0.0
+    cm = np.array([])
+    if compute_beat:
+        print("Model contains long-term music features (beat etc) and cannot be used in segmentation")
+        return labels, class_names, accuracy, cm
+    signal = audioBasicIO.stereo_to_mono(signal)
+    labels, _ = mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_step, st_win, st_step)
+    segs, classes = labels_to_segments(labels, mid_step)
+    for i in range(len(segs)):
+        print(segs[i], classes[i])
+    segs[-1] = len(signal) / float(sampling_rate)
+    labels_gt, class_names_gt, accuracy, cm = load_ground_truth(gt_file, labels, class_names, mid_step, plot_results)
+    return labels, class_names, accuracy, cm
+
+
+def mid_term_file_classification(input_file, model_name, model_type, plot_results=False, gt_file=""):
+    """Mid-term classification of an audio file with a trained SVM model (reference :518-604): returns
+    (labels, class_names, accuracy, cm).  Models with compute_beat are refused, as in the reference."""
+    import os
+    from . import audioTrainTest
+    labels = []
+    accuracy = 0.0
+    class_names = []
+    cm = np.array([])
+    if not os.path.isfile(model_name):
+        print("mtFileClassificationError: input model_type not found!")
+        return labels, class_names, accuracy, cm
+    if model_type not in ("svm", "svm_rbf"):
+        raise NotImplementedError("model type %r: the GPU path serves the SVM models" % (model_type,))
+    classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step, compute_beat = \
+        audioTrainTest.load_model(model_name)
+    if compute_beat:
+        print("Model " + model_name + " contains long-term music features (beat etc) and cannot be used in segmentation")
+        return labels, class_names, accuracy, cm
+    sampling_rate, signal = audioBasicIO.read_audio_file(input_file)
+    if sampling_rate == 0:
+        return labels, class_names, accuracy, cm
+    return mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win,
+                                   st_step, False, plot_results, gt_file)

@@ -1,0 +1,283 @@
+"""Drop-in for the classification half of pyAudioAnalysis.audioTrainTest (reference: pyAudioAnalysis/audioTrainTest.py).
+
+    load_model(model_name, is_regression=False)                  audioTrainTest.py:523-553
+    classifier_wrapper(classifier, classifier_type, test_sample) audioTrainTest.py:52-94
+    file_classification(input_file, model_name, model_type)      audioTrainTest.py:1052-1096
+    file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one SVC launch
+
+For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
+predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
+pairwise coupling for every vector in one launch.  Only the fitted model's arrays are read (support_vectors_,
+n_support_, _dual_coef_, _intercept_, probA_, probB_, _gamma, kernel, classes_), so a model given as those arrays
+(SvcArrays) works without scikit-learn.  Every other classifier type is called exactly as the reference calls it.
+Unpickling a model needs scikit-learn exactly where the reference needs it (load_model).  Training stays with
+scikit-learn.
+"""
+import ctypes as C
+import os
+import pickle as cPickle
+import weakref
+
+import numpy as np
+
+from . import MidTermFeatures as aF
+from . import _ffi, audioBasicIO
+
+_SVM_TYPES = ("svm", "svm_rbf")
+_KERNEL_TYPES = {"linear": 0, "rbf": 2}          # libsvm's LINEAR / RBF
+
+
+class SvcArrays:
+    """A fitted multi-class probabilistic SVC given by its arrays in scikit-learn's attribute names (e.g. from an .npz);
+    dual_coef / intercept are the PRIVATE _dual_coef_ / _intercept_ (libsvm's sv_coef and -rho)."""
+
+    def __init__(self, support_vectors, n_support, dual_coef, intercept, prob_a, prob_b, gamma, kernel, classes):
+        self.support_vectors_ = np.asarray(support_vectors, dtype=np.float64)
+        self.n_support_ = np.asarray(n_support, dtype=np.int32)
+        self._dual_coef_ = np.asarray(dual_coef, dtype=np.float64)
+        self._intercept_ = np.asarray(intercept, dtype=np.float64)
+        self.probA_ = np.asarray(prob_a, dtype=np.float64)
+        self.probB_ = np.asarray(prob_b, dtype=np.float64)
+        self._gamma = float(gamma)
+        self.kernel = str(kernel)
+        self.classes_ = np.asarray(classes)
+
+
+class SvcModel:
+    """A model uploaded to the device once (paa_svc_create); freed with the object."""
+
+    def __init__(self, classifier):
+        kernel = str(getattr(classifier, "kernel", ""))
+        if kernel not in _KERNEL_TYPES:
+            raise NotImplementedError("SVC kernel %r: the GPU path serves 'rbf' and 'linear' models" % (kernel,))
+        sv = np.ascontiguousarray(classifier.support_vectors_, dtype=np.float64)
+        n_support = np.ascontiguousarray(classifier.n_support_, dtype=np.int32)
+        coef = np.ascontiguousarray(classifier._dual_coef_, dtype=np.float64)
+        rho = np.ascontiguousarray(-np.asarray(classifier._intercept_, dtype=np.float64).reshape(-1))
+        prob_a = np.ascontiguousarray(np.asarray(classifier.probA_, dtype=np.float64).reshape(-1))
+        prob_b = np.ascontiguousarray(np.asarray(classifier.probB_, dtype=np.float64).reshape(-1))
+        k = n_support.shape[0]
+        pairs = k * (k - 1) // 2
+        if sv.ndim != 2 or coef.shape != (k - 1, sv.shape[0]) or rho.shape[0] != pairs or prob_a.shape[0] != pairs \
+                or prob_b.shape[0] != pairs:
+            raise ValueError("not a fitted probabilistic SVC (SVC(probability=True)): inconsistent arrays")
+        self.classes = np.asarray(classifier.classes_)
+        self.n_classes = k
+        self.n_dims = sv.shape[1]
+        gamma = float(classifier._gamma) if kernel == "rbf" else 0.0
+        lib = _ffi.lib()
+        handle = C.c_void_p()
+        _ffi.check(lib.paa_svc_create(_ffi.as_f64p(sv), sv.shape[0], sv.shape[1], n_support.ctypes.data_as(_ffi.c_i32p), k,
+                                      _ffi.as_f64p(coef), _ffi.as_f64p(rho), _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b),
+                                      _KERNEL_TYPES[kernel], gamma, C.byref(handle)))
+        self.handle = handle
+        self._finalizer = weakref.finalize(self, lib.paa_svc_destroy, handle)
+
+    def predict(self, feats, mean, std):
+        """feats [n_dims][n_vec] (feature-major) -> (label indices [n_vec], probabilities [n_vec][k]) of
+        (feats[:, v] - mean) / std."""
+        F = np.ascontiguousarray(feats, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
+            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
+        mean, std = self._stats(mean, std)
+        n = F.shape[1]
+        idx = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, self.n_classes), dtype=np.float64)
+        _ffi.check(_ffi.lib().paa_svc_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
+                                                  _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba)))
+        return idx, proba
+
+    def predict_device(self, d_feats, ld, n_vec, mean, std):
+        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
+        mean, std = self._stats(mean, std)
+        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
+        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
+        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
+        _ffi.check(_ffi.lib().paa_svc_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
+                                                      C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr, d_proba.ptr))
+        idx = d_idx.to_host(np.int32, n_vec)
+        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
+        for b in (d_stats, d_idx, d_proba):
+            b.free()
+        return idx, proba
+
+    def _stats(self, mean, std):
+        mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
+        std = np.ascontiguousarray(np.asarray(std, dtype=np.float64).reshape(-1))
+        if mean.shape[0] != self.n_dims or std.shape[0] != self.n_dims:
+            raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], self.n_dims))
+        return mean, std
+
+
+_uploaded = weakref.WeakKeyDictionary()
+
+
+def svc_model(classifier):
+    """The device copy of a fitted SVC (uploaded at the first use, kept while the classifier lives)."""
+    if isinstance(classifier, SvcModel):
+        return classifier
+    try:
+        m = _uploaded.get(classifier)
+    except TypeError:
+        m = None
+    if m is None:
+        m = SvcModel(classifier)
+        try:
+            _uploaded[classifier] = m
+        except TypeError:
+            pass
+    return m
+
+
+def svm_predict(classifier, feats, mean, std):
+    """Classify every column of feats [n_dims][n_vec] after (x - mean) / std: (classes_ of the winners, probabilities)."""
+    m = svc_model(classifier)
+    idx, proba = m.predict(feats, mean, std)
+    return m.classes[idx], proba
+
+
+def load_model(model_name, is_regression=False):
+    """Loads an SVM model either for classification or regression (reference :523-553): the pickled classifier and its
+    MEANS file (mean, std, class names, mid / short windows and steps, compute_beat)."""
+    with open(model_name + "MEANS", "rb") as fo:
+        mean = cPickle.load(fo)
+        std = cPickle.load(fo)
+        if not is_regression:
+            classNames = cPickle.load(fo)
+        mid_window = cPickle.load(fo)
+        mid_step = cPickle.load(fo)
+        short_window = cPickle.load(fo)
+        short_step = cPickle.load(fo)
+        compute_beat = cPickle.load(fo)
+
+    mean = np.array(mean)
+    std = np.array(std)
+
+    with open(model_name, 'rb') as fid:
+        svm_model = cPickle.load(fid)
+
+    if is_regression:
+        return svm_model, mean, std, mid_window, mid_step, short_window, short_step, compute_beat
+    return svm_model, mean, std, classNames, mid_window, mid_step, short_window, short_step, compute_beat
+
+
+def classifier_wrapper(classifier, classifier_type, test_sample):
+    """(class id, probability estimate) of one feature vector (reference :52-94).  "svm" / "svm_rbf": predict() and
+    predict_proba() on the GPU; the other types call the classifier object as the reference does."""
+    class_id = -1
+    probability = -1
+    if classifier_type in _SVM_TYPES:
+        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+        m = svc_model(classifier)
+        idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))       # (x - 0) / 1 == x
+        return m.classes[idx[0]], proba[0]
+    if classifier_type == "knn":
+        class_id, probability = classifier.classify(test_sample)
+    elif classifier_type in ("randomforest", "gradientboosting", "extratrees"):
+        class_id = classifier.predict(test_sample.reshape(1, -1))[0]
+        probability = classifier.predict_proba(test_sample.reshape(1, -1))[0]
+    return class_id, probability
+
+
+def _long_term_vector(signal, sampling_rate, mid_window, mid_step, short_window, short_step, compute_beat):
+    """file_classification's feature vector (reference :1077-1090): short-file mid_window clamp, long-term mean of the
+    mid-term matrix, beat and its confidence appended when compute_beat."""
+    if signal.shape[0] / float(sampling_rate) < mid_window:
+        mid_window = signal.shape[0] / float(sampling_rate)
+    mid_features, s, _ = aF.mid_feature_extraction(signal, sampling_rate, mid_window * sampling_rate,
+                                                   mid_step * sampling_rate, round(sampling_rate * short_window),
+                                                   round(sampling_rate * short_step))
+    mid_features = mid_features.mean(axis=1)
+    if compute_beat:
+        beat, beat_conf = aF.beat_extraction(s, short_step)
+        mid_features = np.append(mid_features, beat)
+        mid_features = np.append(mid_features, beat_conf)
+    return mid_features
+
+
+def file_classification_signal(signal, sampling_rate, classifier, mean, std, mid_window, mid_step, short_window,
+                               short_step, compute_beat, model_type="svm_rbf"):
+    """file_classification on a mono signal and a loaded model: (class id, probabilities)."""
+    mid_features = _long_term_vector(signal, sampling_rate, mid_window, mid_step, short_window, short_step, compute_beat)
+    feature_vector = (mid_features - mean) / std    # normalization (:1091)
+    return classifier_wrapper(classifier, model_type, feature_vector)
+
+
+def file_classification(input_file, model_name, model_type):
+    """(class id, probabilities, class names) of one audio file (reference :1052-1096); the reference's error returns
+    (-1, -1, -1) for a missing model or file and an unreadable file."""
+    if not os.path.isfile(model_name):
+        print("fileClassification: input model_name not found!")
+        return -1, -1, -1
+    if isinstance(input_file, str) and not os.path.isfile(input_file):
+        print("fileClassification: wav file not found!")
+        return -1, -1, -1
+    if model_type == 'knn':
+        raise NotImplementedError("kNN models (load_model_knn) are not part of this package")
+    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = load_model(model_name)
+    sampling_rate, signal = audioBasicIO.read_audio_file(input_file)
+    signal = audioBasicIO.stereo_to_mono(signal)
+    if sampling_rate == 0:
+        return -1, -1, -1
+    class_id, probability = file_classification_signal(signal, sampling_rate, classifier, mean, std, mid_window, mid_step,
+                                                       short_window, short_step, compute_beat, model_type)
+    return class_id, probability, classes
+
+
+def file_classification_signals(signals, sampling_rate, classifier, mean, std, mid_window, mid_step, short_window,
+                                short_step, compute_beat):
+    """file_classification for many mono signals of one sampling rate and an SVM model: the clips go through ONE
+    batched mid-term (+ beat) plan, the long-term vectors through ONE SVC launch.  Clips shorter than mid_window take
+    the reference's clamp (:1077-1078, a window of their own length) through the single-clip path.
+    Returns (class ids [n], probabilities [n][k])."""
+    if len(signals) == 0:
+        return np.array([]), np.zeros((0, 0))
+    fs = sampling_rate
+    vectors = [None] * len(signals)
+    regular = [i for i, s in enumerate(signals) if s.shape[0] / float(fs) >= mid_window]
+    by_kind = {}
+    for i in regular:
+        by_kind.setdefault(np.asarray(signals[i]).dtype == np.int16, []).append(i)
+    for _, members in by_kind.items():
+        mids, beats = aF.mid_and_beat_batch([signals[i] for i in members], fs, mid_window * fs, mid_step * fs,
+                                            round(fs * short_window), round(fs * short_step),
+                                            beat_window_seconds=short_step if compute_beat else None)
+        for j, i in enumerate(members):
+            v = mids[j].mean(axis=1)
+            if compute_beat:
+                v = np.append(v, beats[j, 0])
+                v = np.append(v, beats[j, 1])
+            vectors[i] = v
+    for i, v in enumerate(vectors):
+        if v is None:
+            vectors[i] = _long_term_vector(signals[i], fs, mid_window, mid_step, short_window, short_step, compute_beat)
+    feats = np.stack(vectors, axis=1)
+    return svm_predict(classifier, feats, mean, std)
+
+
+def file_classification_batch(files, model_name, model_type):
+    """file_classification over many files with one model: returns a list of (class id, probabilities, class names)
+    per file, equal to one-file calls.  Files are grouped by sampling rate; each group is one batched mid-term plan and
+    one SVC launch.  Missing / unreadable files give the reference's (-1, -1, -1)."""
+    if model_type not in _SVM_TYPES:
+        return [file_classification(f, model_name, model_type) for f in files]
+    if not os.path.isfile(model_name):
+        print("fileClassification: input model_name not found!")
+        return [(-1, -1, -1) for _ in files]
+    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = load_model(model_name)
+    out = [(-1, -1, -1)] * len(files)
+    groups = {}
+    for i, f in enumerate(files):
+        if isinstance(f, str) and not os.path.isfile(f):
+            print("fileClassification: wav file not found!")
+            continue
+        fs, sig = audioBasicIO.read_audio_file(f)
+        if fs == 0:
+            continue
+        groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
+    for fs, members in groups.items():
+        ids, proba = file_classification_signals([s for _, s in members], fs, classifier, mean, std, mid_window, mid_step,
+                                                 short_window, short_step, compute_beat)
+        for j, (i, _) in enumerate(members):
+            out[i] = (ids[j], proba[j], classes)
+    return out

@@ -15,6 +15,20 @@
 
 namespace paa {
 namespace wgr { struct WgrTab; }
+namespace svc {
+constexpr int kMaxClasses = 16;
+constexpr int kMaxDims = 256;
+// one uploaded model (libsvm's svm_model as scikit-learn holds it): device pointers
+struct SvcDev {
+    const double *sv;         // [n_sv][n_dims] support vectors, grouped by class
+    const double *coef;       // [k - 1][n_sv] sv_coef (scikit-learn's _dual_coef_)
+    const int *class_end;     // [k] end of class c's range of support vectors (cumulative n_support)
+    const double *rho;        // [k (k - 1) / 2] (= -_intercept_)
+    const double *prob_a, *prob_b;
+    int n_sv, n_dims, k, rbf;
+    double gamma;
+};
+}  // namespace svc
 namespace launch {
 
 // kernels_fast.hpp: window 800, step 400 / 800, int16
@@ -62,6 +76,10 @@ int generic(const GenLayout &gl, size_t lds, int sample_kind, const PlanDev &P, 
             const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles,
             double *d_out, hipStream_t stream);
 
+// kernels_svc.hpp: multi-class probabilistic SVC over the columns of feats [n_dims][ld] (two kernels: the per-class sums go to
+// `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
+int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
+        double *d_sums, int *d_label, double *d_proba, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Measure the SVM classification path (not part of bench.py).
+
+    python scripts/bench_classify.py                       # GPU: SVC kernel rate per shipped model, 1 h clip end to end
+    python scripts/bench_classify.py --reference-loop DIR  # host: the reference's per-window scikit-learn loop
+                                                           # (DIR = pyAudioAnalysis/data/models; needs scikit-learn)
+
+The models: svm_rbf_sm, svm_rbf_speaker_male_female and svm_rbf_musical_genre_6 from the svc_* goldens (tests/golden, arrays
+only); svm_rbf_speaker_10 and svm_rbf_movie8class, whose arrays are too large for a golden file, as seeded models of exactly their
+shape (tests/svc_libsvm.synthetic_model: same classes, support vectors per class and dims -- the work per window is the same).
+All five use 1 s / 1 s mid-term and 50 ms / 50 ms short-term windows, as the shipped models do.  Rates are medians over --reps
+calls after one warm-up.  Prints one JSON line.
+"""
+import argparse
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import svc_libsvm  # noqa: E402
+
+GOLDEN_MODELS = {"svm_rbf_sm": "svc_sm_speech_music", "svm_rbf_speaker_male_female": "svc_malefemale_diarization",
+                 "svm_rbf_musical_genre_6": "svc_genre6_files"}
+SHAPED_MODELS = {"svm_rbf_speaker_10": svc_libsvm.SPEAKER_10_N_SUPPORT, "svm_rbf_movie8class": svc_libsvm.MOVIE8CLASS_N_SUPPORT}
+MODELS = ["svm_rbf_sm", "svm_rbf_speaker_male_female", "svm_rbf_speaker_10", "svm_rbf_movie8class", "svm_rbf_musical_genre_6"]
+
+
+def golden(name):
+    with np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"), allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
+def median_time(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts))
+
+
+def one_hour_clip(fs=16000, seconds=3600):
+    rng = np.random.default_rng(5)
+    t = np.arange(seconds * fs, dtype=np.float64) / fs
+    x = 8000 * np.sin(2 * np.pi * 220 * t * (1 + 0.3 * np.sin(2 * np.pi * t / 97))) * (0.5 + 0.5 * np.sin(2 * np.pi * t / 13))
+    x += rng.normal(0, 1500, t.shape[0]) * (np.sin(2 * np.pi * t / 41) > 0)
+    return np.clip(x, -32768, 32767).astype(np.int16)
+
+
+def gpu(args):
+    from pyaudioanalysis_amd import MidTermFeatures, _ffi, audioSegmentation, audioTrainTest
+    _ffi.init(0)
+    out = {"kernel_windows_per_s": {}, "one_hour_s": {}}
+    rng = np.random.default_rng(1)
+    clip = one_hour_clip()
+    mid, _, _ = MidTermFeatures.mid_feature_extraction(clip, 16000, 16000, 16000, 800, 800)
+    clip_mean, clip_std = mid.mean(axis=1), np.where(mid.std(axis=1) > 0, mid.std(axis=1), 1.0)
+    for model in MODELS:
+        if model in GOLDEN_MODELS:
+            g = golden(GOLDEN_MODELS[model])
+            arrays = (g["sv"], g["n_support"], g["dual_coef"], -g["rho"], g["prob_a"], g["prob_b"], g["gamma"], str(g["kernel"]),
+                      g["classes"])
+            mean, std, beat = g["mean"], g["std"], "compute_beat" in g and bool(g["compute_beat"])
+        else:
+            m = svc_libsvm.synthetic_model(SHAPED_MODELS[model], 136, 3)
+            arrays = (m["support_vectors"], m["n_support"], m["dual_coef"], -m["rho"], m["prob_a"], m["prob_b"], m["gamma"],
+                      "rbf", np.arange(len(m["n_support"]), dtype=np.float64))
+            mean, std, beat = clip_mean, clip_std, False
+        svc = audioTrainTest.SvcModel(audioTrainTest.SvcArrays(*arrays))
+        n_dims = svc.n_dims
+        X = rng.standard_normal((n_dims, args.windows))
+        d_x = _ffi.DeviceBuffer.from_host(X)
+        zeros, ones = np.zeros(n_dims), np.ones(n_dims)
+        t = median_time(lambda: svc.predict_device(d_x, args.windows, args.windows, zeros, ones), args.reps)
+        out["kernel_windows_per_s"][model] = args.windows / t
+        d_x.free()
+        if not beat:           # mid_term_file_classification refuses beat models (audioSegmentation.py:566-570)
+            t = median_time(lambda: audioSegmentation.mid_term_labels(clip, 16000, svc, mean, std, 1.0, 1.0, 0.05, 0.05),
+                            max(1, args.reps // 4))
+            out["one_hour_s"][model] = t
+        print(model, {k: v.get(model) for k, v in out.items()}, file=sys.stderr)
+    out["windows_per_call"] = args.windows
+    return out
+
+
+def reference_loop(args):
+    import pickle
+    import warnings
+    warnings.simplefilter("ignore")
+    out = {"reference_sklearn_windows_per_s": {}}
+    rng = np.random.default_rng(1)
+    for model in MODELS:
+        with open(os.path.join(args.reference_loop, model), "rb") as f:
+            clf = pickle.load(f)
+        X = rng.standard_normal((args.loop_windows, clf.support_vectors_.shape[1]))
+
+        def loop():          # audioSegmentation.py:583-594 -> audioTrainTest.classifier_wrapper (:84-93)
+            for v in X:
+                clf.predict(v.reshape(1, -1))[0]
+                clf.predict_proba(v.reshape(1, -1))[0]
+        t = median_time(loop, 3)
+        out["reference_sklearn_windows_per_s"][model] = args.loop_windows / t
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=16384)
+    ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--reference-loop", default=None)
+    ap.add_argument("--loop-windows", type=int, default=200)
+    args = ap.parse_args()
+    print(json.dumps(reference_loop(args) if args.reference_loop else gpu(args)))
+
+
+if __name__ == "__main__":
+    main()
