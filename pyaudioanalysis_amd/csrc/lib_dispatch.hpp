@@ -1,6 +1,6 @@
-// Kernel choice of a plan: one table entry per feature-kernel family -- does it take this (window, step, sample type, mode)?
-// how long are its runs? how is it launched? -- walked in order by plan_build; the first family that accepts owns the plan.
-// Adding a family = one more entry (and its family_<name>.hip).  Included by paa_lib.hip after the plan structure.
+// Kernel choice of a plan: one table entry per feature-kernel path, walked in order by choose_family; the first entry whose
+// select() takes the (window, step, sample type, mode, rows) owns the plan.  plan_build, paa_plan_execute and run_host_st only
+// call through the entry.  Adding a path = one more entry.  Included by lib_plan.hpp after the plan structure and its launchers.
 #pragma once
 
 struct FamilyCtx {
@@ -25,14 +25,19 @@ struct RunRule {
 };
 struct Family {
     const char *id;
-    // 1: takes the shape (layout + tables are in the plan, kernel_name and lds set), 0: declines, < 0: error code
-    int (*select)(FamilyCtx &c);
-    void (*run_rule)(FamilyCtx &c, RunRule &r);
-    int (*launch)(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles, hipStream_t stream);
+    // 1: takes the shape (layout, lds and kernel_name set in `f`, the device tables -- if any -- in `blob`), 0: declines, < 0: error
+    // code.  Depends only on the table set, the mode and the rows (and the fast family's step): choose_family caches the result
+    int (*select)(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob);
+    // per plan, after the choice: the work list -- the tile list (one-wave families; wgr's runs) or the path's own lists on the plan
+    int (*work)(FamilyCtx &c, std::vector<Tile> &tiles);
+    // queues the plan's kernels on cs(); tiles / n_tiles: the plan's tile list, or a range of it
+    int (*execute)(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles);
+    bool ranged;          // the tile list may be launched in consecutive ranges (run_host_st's copy-back pipeline)
+    bool norms_inline;    // the kernel folds the statistics partials into the clip constants (else clip_params_kernel runs first)
 };
 
-static int upload_blob(paa_plan *p, const std::vector<unsigned char> &blob) {
-    return upload_pooled(&p->d_gen_blob, blob.data(), blob.size());
+static std::string mode_kernel_name(int mode, const std::string &suffix) {
+    return std::string(mode == 0 ? "st_" : (mode == 1 ? "spectrogram_" : "chromagram_")) + suffix;
 }
 // the usual rule of the one-frame-per-iteration kernels: about two chip-wide rounds, 8 .. 64 frames per run
 static int two_round_run(long long total_frames, int waves, int num_cu) {
@@ -41,37 +46,85 @@ static int two_round_run(long long total_frames, int waves, int num_cu) {
     return (int)std::min<long long>(64, std::max<long long>(8, (per + 3) / 4 * 4));
 }
 
+// the tile list of a one-wave family: runs of its RunRule, balanced or equal, clip after clip in frame order
+static void build_tiles(FamilyCtx &c, const RunRule &rr, std::vector<Tile> &tiles) {
+    const std::vector<ClipDev> &clips = c.p->clips;
+    const int run = rr.run, run_quantum = rr.quantum, run_halo = rr.halo_inside;
+    tiles.reserve((size_t)(c.total_frames / run + clips.size()));
+    std::vector<std::vector<int>> run_lens;
+#ifndef PAA_BALANCED_RUNS
+#define PAA_BALANCED_RUNS 1           // (0: A/B build of scripts/rounds/r05/gpu_r05w.sh -- equal runs, 250 workgroups for the one-hour clip)
+#endif
+    const bool balanced = PAA_BALANCED_RUNS && rr.fill_wg_runs > 0 && c.ranges <= 1 &&
+                          balanced_runs(clips, run, run_quantum, run_halo, rr.fill_wg_runs, g_num_cu, rr.fill_min_run, run_lens);
+    for (size_t ci = 0; ci < clips.size(); ++ci) {
+        const long long T = clips[ci].T;
+        if (T <= 0) continue;
+        if (balanced) {
+            long long t0 = 0;
+            for (int cnt : run_lens[ci]) {
+                Tile tl; tl.clip = (int)ci; tl.t0 = (int)t0; tl.cnt = cnt; tl.pad = 0;
+                tiles.push_back(tl);
+                t0 += cnt;
+            }
+            continue;
+        }
+        const int len = clip_run_length(T, run, run_quantum);          // equal runs per clip
+        for (long long t0 = 0; t0 < T;) {
+            const long long want = (t0 > 0) ? len - run_halo : len;
+            Tile tl; tl.clip = (int)ci; tl.t0 = (int)t0; tl.cnt = (int)std::min<long long>(want, T - t0); tl.pad = 0;
+            tiles.push_back(tl);
+            t0 += tl.cnt;
+        }
+    }
+}
+template <void (*Rule)(FamilyCtx &, RunRule &)>
+static int tile_work(FamilyCtx &c, std::vector<Tile> &tiles) {
+    RunRule rr;
+    Rule(c, rr);
+    build_tiles(c, rr, tiles);
+    return PAA_OK;
+}
+// one launch of a one-wave family over a range of tiles
+typedef int (*TileLaunch)(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s);
+template <TileLaunch Launch>
+static int tile_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles) {
+    if (n_tiles == 0) return PAA_OK;
+    ProfScope prof_scope;
+    { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
+    if (Launch(p, d_packed, d_out, tiles, n_tiles, cs()))
+        return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+    return PAA_OK;
+}
+
 // ---- kernels_fast.hpp: int16, window 800, step 400 / 800, features only
-static int fam_fast_select(FamilyCtx &c) {
+static int fam_fast_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &) {
     if (c.mode != 0 || g_force_generic) return 0;
-    const int rc = fast_select(c.window, c.step, c.sample_kind, c.fs, c.tab->fast, c.tab->fft, c.tab->mel, c.tab->chroma, c.p->fl,
+    const int rc = fast_select(c.window, c.step, c.sample_kind, c.fs, c.tab->fast, c.tab->fft, c.tab->mel, c.tab->chroma, f.fl,
                                g_f800_waves);
     if (rc < 0) return fail(rc, "building the tables of the specialised kernel failed");
-    if (rc) { c.p->fast = 1; c.p->lds = c.p->fl.lds; c.p->kernel_name = c.p->fl.name; }
+    if (rc) { f.lds = f.fl.lds; f.kernel_name = f.fl.name; }
     return rc;
 }
 static void fam_fast_rule(FamilyCtx &c, RunRule &r) {
     // one wave per run of whole 4-frame quads, at most fl.run frames; a run after a clip's first starts its first quad one frame
     // early (two with deltas: the flux of the last halo frame feeds a delta) -- the halo rides inside the first iteration, the run
     // stores that many frames less (kernels_fast.hpp: HALO); see choose_run_cap
+    const FastLaunch &fl = c.p->fam.fl;
     r.quantum = 4;
     r.halo_inside = c.deltas ? 2 : 1;
-    r.run = choose_run_cap(c.p->clips, 4, 16, c.p->fl.run, 0, c.p->fl.waves_per_cu, c.num_cu(), r.halo_inside);
-    r.fill_wg_runs = c.p->fl.waves_per_cu;
+    r.run = choose_run_cap(c.p->clips, 4, 16, fl.run, 0, fl.waves_per_cu, c.num_cu(), r.halo_inside);
+    r.fill_wg_runs = fl.waves_per_cu;
     if (const char *rc_env = experiment_env("PAA_RUN_CAP")) r.run = std::max(16, atoi(rc_env) / 4 * 4);      // A/B experiments only
 }
 static int fam_fast_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::fast(p->fl, p->P, p->tab->fast, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::fast(p->fam.fl, p->P, p->tab->fast, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
 // ---- kernels_ct.hpp: windows 2 RA RB (800, 640, 400, 320), any step / sample type / mode
-static int fam_ct_select(FamilyCtx &c) {
-    if (g_force_generic) return 0;
-    std::vector<unsigned char> blob;
-    if (!ct::ct_select(c.window, c.mode, c.fs, c.tab->fft, c.mel(), c.chroma(), c.p->cl, blob)) return 0;
-    const int rc = upload_blob(c.p, blob);
-    if (rc) return rc;
-    c.p->ct = 1; c.p->lds = c.p->cl.lds; c.p->kernel_name = c.p->cl.name;
+static int fam_ct_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
+    if (g_force_generic || !ct::ct_select(c.window, c.mode, c.fs, c.tab->fft, c.mel(), c.chroma(), f.cl, blob)) return 0;
+    f.lds = f.cl.lds; f.kernel_name = f.cl.name;
     return 1;
 }
 static void fam_ct_rule(FamilyCtx &c, RunRule &r) {
@@ -79,142 +132,242 @@ static void fam_ct_rule(FamilyCtx &c, RunRule &r) {
     // iteration, so the first run of a clip gets `run` frames and the others run - halo: every run is whole iterations
     r.quantum = 4;
     r.halo_inside = (c.mode == 0) ? (c.deltas ? 2 : 1) : 0;
-    r.run = choose_run_cap(c.p->clips, 4, 16, 256, 0, c.p->cl.waves, c.num_cu(), r.halo_inside);
-    r.fill_wg_runs = c.p->cl.waves;          // (one workgroup per CU; A/B scripts/rounds/r05/gpu_r05aj.sh: -0.4 ... -2.0 % on the feature shapes)
+    r.run = choose_run_cap(c.p->clips, 4, 16, 256, 0, c.p->fam.cl.waves, c.num_cu(), r.halo_inside);
+    r.fill_wg_runs = c.p->fam.cl.waves;          // (one workgroup per CU; A/B scripts/rounds/r05/gpu_r05aj.sh: -0.4 ... -2.0 % on the feature shapes)
 }
 static int fam_ct_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::ct(p->cl, p->sample_kind, p->P, p->d_gen_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::ct(p->fam.cl, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
 // ---- kernels_tri.hpp: three-pass register FFT -- the reference's default 50 ms windows at 48 / 44.1 kHz (2400, 2205), the
 // 40 ms ones (1920, 1764), 1600, 1200, config 5's feature matrix (1102) and the odd 551 (50 ms at 11.025 kHz)
-static int fam_tri_select(FamilyCtx &c) {
-    if (g_force_generic) return 0;
-    std::vector<unsigned char> blob;
-    if (!tri::tri_select(c.window, c.mode, c.fs, c.mel(), c.chroma(), c.p->trl, blob)) return 0;
-    const int rc = upload_blob(c.p, blob);
-    if (rc) return rc;
-    c.p->tri = 1; c.p->lds = c.p->trl.lds; c.p->kernel_name = c.p->trl.name;
+static int fam_tri_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
+    if (g_force_generic || !tri::tri_select(c.window, c.mode, c.fs, c.mel(), c.chroma(), f.trl, blob)) return 0;
+    f.lds = f.trl.lds; f.kernel_name = f.trl.name;
     return 1;
 }
 static void fam_tri_rule(FamilyCtx &c, RunRule &r) {
     // one wave per run, one frame per iteration; a run with t0 > 0 recomputes 1 frame (2 with deltas) first
     r.quantum = 1;
-    r.run = choose_run_cap(c.p->clips, 1, 8, 96, (c.mode == 0) ? (c.deltas ? 2 : 1) : 0, c.p->trl.waves, c.num_cu());
+    r.run = choose_run_cap(c.p->clips, 1, 8, 96, (c.mode == 0) ? (c.deltas ? 2 : 1) : 0, c.p->fam.trl.waves, c.num_cu());
     // (balanced runs -- RunRule::fill_wg_runs = trl.waves -- were A/B-ed here too, scripts/rounds/r05/gpu_r05ad.sh: 3072 runs of 19 / 20
     // frames instead of 3000 of 20 for config 5 changed nothing beyond the noise, 0.3202 / 0.3184 ms: the equal runs stay)
 }
 static int fam_tri_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::tri(p->trl, p->sample_kind, p->P, p->d_gen_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::tri(p->fam.trl, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
 // ---- kernels_mix.hpp: in-place mixed-radix transform for every other length made of 2, 3, 5, 7, 11, 13
-static int fam_mix_select(FamilyCtx &c) {
+static int fam_mix_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
     if (g_force_generic || experiment_env("PAA_NO_MIX")) return 0;
-    std::vector<unsigned char> blob;
-    if (!mix::mix_layout(c.tab->fft, c.mel(), c.chroma(), c.F, c.p->ml, &blob)) return 0;
-    const int rc = upload_blob(c.p, blob);
-    if (rc) return rc;
-    c.p->mixk = 1;
-    c.p->lds = mix::mix_lds_bytes(c.p->ml);
-    c.p->kernel_name = (c.mode == 0) ? "st_mix" : (c.mode == 1 ? "spectrogram_mix" : "chromagram_mix");
+    if (!mix::mix_layout(c.tab->fft, c.mel(), c.chroma(), c.F, f.ml, &blob)) return 0;
+    f.lds = mix::mix_lds_bytes(f.ml);
+    f.kernel_name = mode_kernel_name(c.mode, "mix");
     return 1;
 }
 static void fam_mix_rule(FamilyCtx &c, RunRule &r) {
     // one wave per run, one frame at a time (halo: 1 frame, 2 with deltas)
     r.quantum = 4;
-    r.run = two_round_run(c.total_frames, c.p->ml.waves, c.num_cu());
+    r.run = two_round_run(c.total_frames, c.p->fam.ml.waves, c.num_cu());
 }
 static int fam_mix_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::mix(p->ml, p->lds, p->sample_kind, p->P, p->d_gen_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::mix(p->fam.ml, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
 // ---- kernels_blu.hpp: lengths with a prime factor above 13 (661, 1103, 736 ...): Bluestein's convolution on power-of-two transforms
-static int fam_blu_select(FamilyCtx &c) {
+static int fam_blu_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
     if (g_force_generic || experiment_env("PAA_NO_BLU")) return 0;
-    std::vector<unsigned char> blob;
-    if (!blu::blu_layout(c.tab->fft, c.mel(), c.chroma(), c.F, c.p->bl, &blob)) return 0;
-    const int rc = upload_blob(c.p, blob);
-    if (rc) return rc;
-    c.p->bluk = 1;
-    c.p->lds = blu::blu_lds_bytes(c.p->bl);
-    static const char *names[3][6] = {{"st_blu_256", "st_blu_512", "st_blu_1024", "st_blu_2048", "st_blu_4096", "st_blu_8192"},
-                                      {"spectrogram_blu_256", "spectrogram_blu_512", "spectrogram_blu_1024", "spectrogram_blu_2048", "spectrogram_blu_4096",
-                                       "spectrogram_blu_8192"},
-                                      {"chromagram_blu_256", "chromagram_blu_512", "chromagram_blu_1024", "chromagram_blu_2048", "chromagram_blu_4096",
-                                       "chromagram_blu_8192"}};
-    static const char *names_p[3][4] = {{"st_blu_512p", "st_blu_1024p", "st_blu_2048p", "st_blu_4096p"},
-                                        {"spectrogram_blu_512p", "spectrogram_blu_1024p", "spectrogram_blu_2048p", "spectrogram_blu_4096p"},
-                                        {"chromagram_blu_512p", "chromagram_blu_1024p", "chromagram_blu_2048p", "chromagram_blu_4096p"}};
-    c.p->kernel_name = c.p->bl.packed ? names_p[c.mode][c.p->bl.log2m - 9] : names[c.mode][c.p->bl.log2m - 8];
+    if (!blu::blu_layout(c.tab->fft, c.mel(), c.chroma(), c.F, f.bl, &blob)) return 0;
+    f.lds = blu::blu_lds_bytes(f.bl);
+    f.kernel_name = mode_kernel_name(c.mode, "blu_" + std::to_string(1 << f.bl.log2m) + (f.bl.packed ? "p" : ""));
     return 1;
 }
 static void fam_blu_rule(FamilyCtx &c, RunRule &r) {
     // one wave per run, one frame at a time (halo: 1 frame, 2 with deltas)
     r.quantum = 4;
-    r.run = two_round_run(c.total_frames, c.p->bl.waves, c.num_cu());
+    r.run = two_round_run(c.total_frames, c.p->fam.bl.waves, c.num_cu());
 }
 static int fam_blu_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::blu(p->bl, p->lds, p->sample_kind, p->P, p->d_gen_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::blu(p->fam.bl, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
-// ---- kernels_generic.hpp: Stockham passes in LDS (what no other family takes: tiny windows, prime factors above 13 beyond 2730 samples); windows beyond the
-// LDS envelope take the same passes through HBM scratch (kernels_big.hpp: plan->big, no CPU fallback)
-static int fam_generic_select(FamilyCtx &c) {
-    std::vector<unsigned char> blob;
-    generic_layout(c.tab->fft, c.mel(), c.chroma(), c.F, c.p->gl, &blob);
-    c.p->lds = generic_lds_bytes(c.p->gl);
-    if (c.p->lds > 160 * 1024) {
-        c.p->big = 1;
-        c.p->lds = 0;
-    } else {
-        const int rc = upload_blob(c.p, blob);
-        if (rc) return rc;
-    }
-    c.p->kernel_name = c.p->big ? "big_window_hbm_passes"
-                                : (c.mode == 0) ? "st_generic" : (c.mode == 1 ? "spectrogram_generic" : "chromagram_generic");
+// ---- kernels_generic.hpp: Stockham passes in LDS (what no other one-wave family takes: tiny windows, prime factors above 13
+// beyond 2730 samples), as long as the layout fits 160 KB of LDS
+static int fam_generic_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
+    generic_layout(c.tab->fft, c.mel(), c.chroma(), c.F, f.gl, &blob);
+    f.lds = generic_lds_bytes(f.gl);
+    if (f.lds > 160 * 1024) return 0;
+    f.kernel_name = mode_kernel_name(c.mode, "generic");
     return 1;
 }
 static void fam_generic_rule(FamilyCtx &c, RunRule &r) {
     r.quantum = 4;
-    r.run = two_round_run(c.total_frames, c.p->gl.waves, c.num_cu());
+    r.run = two_round_run(c.total_frames, c.p->fam.gl.waves, c.num_cu());
 }
 static int fam_generic_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::generic(p->gl, p->lds, p->sample_kind, p->P, p->d_gen_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+    return launch::generic(p->fam.gl, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
 }
 
+// ---- windows beyond the LDS envelope of the one-wave kernels --------------------------------------------------------------------
+// kernels_wgr.hpp: the 1 s windows of music_thumbnailing at 16 / 8 kHz -- one fused launch, the transform in registers; its table
+// (mel lane jobs + chroma lists) is the blob
+static int fam_wgr_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
+    const int id = wgr::wgr_shape_id(c.window);
+    if (!id) return 0;
+    wgr::WgrTab tab;
+    if (!wgr::wgr_build_tab(wgr::wgr_threads(id), c.mel(), c.chroma(), tab)) return 0;   // (a mel bank its lane jobs cannot hold)
+    blob.assign(reinterpret_cast<const unsigned char *>(&tab), reinterpret_cast<const unsigned char *>(&tab) + sizeof(tab));
+    f.kernel_name = mode_kernel_name(c.mode, std::string("wgr_") + wgr::wgr_shape_name(id));
+    return 1;
+}
+static int fam_wgr_work(FamilyCtx &c, std::vector<Tile> &runs) {
+    wgr::wgr_build_runs(c.p->clips, g_num_cu, runs);          // runs of consecutive frames, about one per CU
+    return PAA_OK;
+}
+
+// kernels_wgs.hpp / kernels_wg.hpp: the transform fits ONE WORKGROUP's LDS (split transforms: one radix-r0 pass straight from the
+// samples, then one sub-transform at a time); the digit-reversal permutation is the blob of kernels_wg.hpp
+static int wg_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> *perm_blob) {
+    std::vector<unsigned short> perm;
+    if (!wg::wg_layout(c.tab->fft, f.wl, perm)) return 0;
+    if (perm_blob)
+        perm_blob->assign(reinterpret_cast<const unsigned char *>(perm.data()), reinterpret_cast<const unsigned char *>(perm.data() + perm.size()));
+    return 1;
+}
+// the real-input split on register passes (r0 x q samples: 44 100, 22 050, 48 000, 32 000, 24 000)
+static int fam_wgs_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &) {
+    const wgs::Sel sel = wgs::wgs_select(c.window);
+    if (!wg_select(c, f, nullptr) || !f.wl.r0 || !sel.r0) return 0;
+    f.kernel_name = mode_kernel_name(c.mode, "wgs_" + std::to_string(sel.r0) + "x" + std::to_string(sel.q));
+    return 1;
+}
+static int fam_wg_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
+    if (!wg_select(c, f, &blob)) return 0;
+    f.kernel_name = mode_kernel_name(c.mode, f.wl.r0 ? "wg_split_fft" : "wg_lds_fft");
+    return 1;
+}
+// the frame list, cut in chunks whose spectrum rows fit the scratch, and the task lists of the split transforms (wgs_r0: the
+// register split of kernels_wgs.hpp, else kernels_wg.hpp's)
+static int wg_build_work(paa_plan *p, int wgs_r0) {
+    // spectrum scratch: one row of Nf doubles per frame of a chunk, at most 1 GiB; a chunk that starts inside a clip
+    // begins with that clip's previous frame once more (halo: only its spectrum row is wanted)
+    const long long cap = std::max<long long>(2, ((long long)1 << 30) / ((long long)p->P.Nf * 8));
+    long long first = 0;
+    for (size_t c = 0; c < p->clips.size(); ++c)
+        for (long long t = 0; t < p->clips[c].T; ++t) {
+            long long in_chunk = (long long)p->wg_frames.size() - first;
+            if (in_chunk >= cap) {
+                p->wg_chunks.emplace_back(first, (long long)p->wg_frames.size());
+                first = (long long)p->wg_frames.size();
+                in_chunk = 0;
+                if (t > 0 && p->mode != 1) p->wg_frames.push_back(wg::FrameRef{(int)c, (int)(t - 1), 0, 1});
+            }
+            p->wg_frames.push_back(wg::FrameRef{(int)c, (int)t, (int)((long long)p->wg_frames.size() - first), 0});
+        }
+    if ((long long)p->wg_frames.size() > first) p->wg_chunks.emplace_back(first, (long long)p->wg_frames.size());
+    for (auto &ch : p->wg_chunks) {
+        p->wg_rows = std::max(p->wg_rows, ch.second - ch.first);
+        for (long long i = ch.first; i < ch.second; ++i) p->wg_frames[(size_t)i].row = (int)(i - ch.first);
+    }
+    int rc = upload_pooled(&p->d_wg_frames, p->wg_frames.data(), std::max<size_t>(p->wg_frames.size(), 1));
+    if (rc) return rc;
+    if (wgs_r0) {
+        // the tasks of a frame side by side (FrameRef::halo = halo | type << 8)
+        const int n_types = wgs::wgs_task_types(wgs_r0);
+        for (auto &ch : p->wg_chunks) {
+            const long long t0 = (long long)p->wg_tasks.size();
+            auto push = [&](long long i, int ty) {
+                wg::FrameRef f = p->wg_frames[(size_t)i];
+                f.halo |= ty << 8;
+                p->wg_tasks.push_back(f);
+            };
+            if (wgs_r0 == 6) {
+                // three sub-transforms per frame: {1, 2} and the packed one -- the packed units of two CONSECUTIVE frames of a clip (consecutive
+                // rows) share a task (type 1, on the first frame's record); a frame without such a partner runs its packed unit alone (type 2)
+                for (long long i = ch.first; i < ch.second;) {
+                    const wg::FrameRef &a = p->wg_frames[(size_t)i];
+                    const bool pair = i + 1 < ch.second && p->wg_frames[(size_t)i + 1].clip == a.clip && p->wg_frames[(size_t)i + 1].t == a.t + 1 &&
+                                      p->wg_frames[(size_t)i + 1].row == a.row + 1;
+                    push(i, 0);
+                    if (pair) { push(i + 1, 0); push(i, 1); i += 2; }
+                    else { push(i, 2); i += 1; }
+                }
+            } else {
+                for (long long i = ch.first; i < ch.second; ++i)
+                    for (int ty = 0; ty < n_types; ++ty) push(i, ty);
+            }
+            p->wg_task_chunks.emplace_back(t0, (long long)p->wg_tasks.size());
+        }
+    } else if (p->fam.wl.r0) {
+        // tasks of a frame: sub-transform 0 alone, the pairs {q, r0 - q}, r0 / 2 alone (FrameRef::halo = halo | q << 8)
+        const int r0 = p->fam.wl.r0;
+        for (auto &ch : p->wg_chunks) {
+            const long long t0 = (long long)p->wg_tasks.size();
+            // (the pairs first: they cost twice what the single sub-transforms do, and tasks are handed out in list order)
+            for (int pairs = 1; pairs >= 0; --pairs)
+                for (long long i = ch.first; i < ch.second; ++i)
+                    for (int q = 0; 2 * q <= r0; ++q) {
+                        if ((q != 0 && 2 * q != r0) != (pairs != 0)) continue;
+                        wg::FrameRef f = p->wg_frames[(size_t)i];
+                        f.halo |= q << 8;
+                        p->wg_tasks.push_back(f);
+                    }
+            p->wg_task_chunks.emplace_back(t0, (long long)p->wg_tasks.size());
+        }
+    } else {
+        return PAA_OK;
+    }
+    if (p->wg_tasks.size() > 0x7fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many frames for the split transform");
+    return upload_pooled(&p->d_wg_tasks, p->wg_tasks.data(), std::max<size_t>(p->wg_tasks.size(), 1));
+}
+static int fam_wgs_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, wgs::wgs_select(c.window).r0); }
+static int fam_wg_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, 0); }
+static int run_wg_any(paa_plan *p, const void *d_packed, double *d_out, const wgs::Sel &sel) {
+    return p->sample_kind == 0 ? run_wg<int16_t>(p, d_packed, d_out, sel)
+         : p->sample_kind == 2 ? run_wg<stereo16>(p, d_packed, d_out, sel) : run_wg<double>(p, d_packed, d_out, sel);
+}
+static int fam_wgs_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
+    return run_wg_any(p, d_packed, d_out, wgs::wgs_select(p->P.W));
+}
+static int fam_wg_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
+    return run_wg_any(p, d_packed, d_out, wgs::Sel{0, 0});
+}
+
+// kernels_big.hpp: chunked Stockham passes through HBM scratch (what nothing else takes; no CPU fallback)
+static int fam_hbm_select(const FamilyCtx &, FamilyChoice &f, std::vector<unsigned char> &) {
+    f.kernel_name = "big_window_hbm_passes";
+    return 1;
+}
+static int no_work(FamilyCtx &, std::vector<Tile> &) { return PAA_OK; }
+static int fam_hbm_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
+    return p->sample_kind == 0 ? run_big<int16_t>(p, d_packed, d_out)
+         : p->sample_kind == 2 ? run_big<stereo16>(p, d_packed, d_out) : run_big<double>(p, d_packed, d_out);
+}
+
+// in choice order; ranged / norms_inline: the one-wave families only
 static const Family kFamilies[] = {
-    {"fast", fam_fast_select, fam_fast_rule, fam_fast_launch},
-    {"ct", fam_ct_select, fam_ct_rule, fam_ct_launch},
-    {"tri", fam_tri_select, fam_tri_rule, fam_tri_launch},
-    {"mix", fam_mix_select, fam_mix_rule, fam_mix_launch},
-    {"blu", fam_blu_select, fam_blu_rule, fam_blu_launch},
-    {"generic", fam_generic_select, fam_generic_rule, fam_generic_launch},
+    {"fast", fam_fast_select, tile_work<fam_fast_rule>, tile_execute<fam_fast_launch>, true, true},
+    {"ct", fam_ct_select, tile_work<fam_ct_rule>, tile_execute<fam_ct_launch>, true, true},
+    {"tri", fam_tri_select, tile_work<fam_tri_rule>, tile_execute<fam_tri_launch>, true, true},
+    {"mix", fam_mix_select, tile_work<fam_mix_rule>, tile_execute<fam_mix_launch>, true, true},
+    {"blu", fam_blu_select, tile_work<fam_blu_rule>, tile_execute<fam_blu_launch>, true, true},
+    {"generic", fam_generic_select, tile_work<fam_generic_rule>, tile_execute<fam_generic_launch>, true, true},
+    {"wgr", fam_wgr_select, fam_wgr_work, run_wgr, false, false},
+    {"wgs", fam_wgs_select, fam_wgs_work, fam_wgs_execute, false, false},
+    {"wg", fam_wg_select, fam_wg_work, fam_wg_execute, false, false},
+    {"hbm", fam_hbm_select, no_work, fam_hbm_execute, false, false},
 };
 constexpr int kNumFamilies = (int)(sizeof(kFamilies) / sizeof(kFamilies[0]));
 
-// what a select() left in the plan, kept with the table set of (fs, window): the next plan of the same (mode, rows) copies
-// it back instead of rebuilding the layout and uploading the table blob again
-struct FamilyChoice {
-    int family = -1;
-    int fast = 0, ct = 0, tri = 0, mixk = 0, bluk = 0, big = 0;
-    FastLaunch fl;
-    ct::CtLaunch cl;
-    tri::TriLaunch trl;
-    mix::MixLayout ml;
-    blu::BluLayout bl;
-    GenLayout gl;
-    size_t lds = 0;
-    std::string kernel_name;
-    unsigned char *d_blob = nullptr;       // owned here (pool_free in free_family_choices)
-};
 static void free_family_choices(TableSet &t) {
     for (auto &kv : t.choices)
         if (kv.second && kv.second->d_blob) pool_free(kv.second->d_blob);
     t.choices.clear();
 }
 
-static int choose_family(FamilyCtx &c, RunRule &rr) {
+// the first entry of kFamilies that takes the shape -> c.p->fam.  The choice is kept with the table set of (fs, window): the next
+// plan of the same (mode, rows) copies it back instead of rebuilding the layout and uploading the table blob again
+static int choose_family(FamilyCtx &c) {
     paa_plan *p = c.p;
     // the fast family looks at (step, sample type) too; nobody else does
     const int fast_key = (c.mode == 0 && c.window == 800 && c.sample_kind == 0 && (c.step == 400 || c.step == 800)) ? c.step : 0;
@@ -222,32 +375,23 @@ static int choose_family(FamilyCtx &c, RunRule &rr) {
 #ifndef PAA_EXPERIMENTS          // (experiment switches change the choice from plan to plan: no cache in those builds)
     auto it = c.tab->choices.find(key);
     if (it != c.tab->choices.end() && !g_force_generic) {
-        const FamilyChoice &fc = *it->second;
-        p->family = fc.family;
-        p->fast = fc.fast; p->ct = fc.ct; p->tri = fc.tri; p->mixk = fc.mixk; p->bluk = fc.bluk; p->big = fc.big;
-        p->fl = fc.fl; p->cl = fc.cl; p->trl = fc.trl; p->ml = fc.ml; p->bl = fc.bl; p->gl = fc.gl;
-        p->lds = fc.lds; p->kernel_name = fc.kernel_name;
-        p->d_gen_blob = fc.d_blob; p->blob_cached = true;
-        kFamilies[p->family].run_rule(c, rr);
+        p->fam = *it->second;
+        p->blob_cached = true;
         return PAA_OK;
     }
 #endif
     for (int i = 0; i < kNumFamilies; ++i) {
-        const int rc = kFamilies[i].select(c);
+        std::vector<unsigned char> blob;
+        p->fam = FamilyChoice();
+        int rc = kFamilies[i].select(c, p->fam, blob);
         if (rc < 0) return rc;
         if (rc == 0) continue;
-        p->family = i;
-        kFamilies[i].run_rule(c, rr);
+        p->fam.family = i;
+        if (!blob.empty() && (rc = upload_pooled(&p->fam.d_blob, blob.data(), blob.size()))) return rc;
 #ifndef PAA_EXPERIMENTS
         if (!g_force_generic) {
-            auto fc = std::make_shared<FamilyChoice>();
-            fc->family = i;
-            fc->fast = p->fast; fc->ct = p->ct; fc->tri = p->tri; fc->mixk = p->mixk; fc->bluk = p->bluk; fc->big = p->big;
-            fc->fl = p->fl; fc->cl = p->cl; fc->trl = p->trl; fc->ml = p->ml; fc->bl = p->bl; fc->gl = p->gl;
-            fc->lds = p->lds; fc->kernel_name = p->kernel_name;
-            fc->d_blob = p->d_gen_blob;            // ownership moves to the table set
+            c.tab->choices[key] = std::make_shared<FamilyChoice>(p->fam);      // (the blob now belongs to the table set)
             p->blob_cached = true;
-            c.tab->choices[key] = fc;
         }
 #endif
         return PAA_OK;

@@ -58,7 +58,7 @@ static int run_host_st(const void *packed, const int64_t *offsets, int64_t n_cli
     HIP_TRY(hipMemcpyAsync(lane.l->in.p, (const char *)packed + (size_t)base * esz, (size_t)n_total * esz,
                            hipMemcpyHostToDevice, cs()));
     const void *d_samples = lane.l->in.p;
-    if (ranged && plan->family >= 0 && !plan->big && !plan->tiles_host.empty()) {
+    if (ranged && !plan->tiles_host.empty()) {          // (plan_build keeps the host tile list for a family that launches ranges)
         double *d_out = (double *)lane.l->out.p;
         const long long T = plan->clips[0].T;
         const int F = plan->P.F;
@@ -80,12 +80,10 @@ static int run_host_st(const void *packed, const int64_t *offsets, int64_t n_cli
             if (last == first) continue;
             t_begin[used] = plan->tiles_host[(size_t)first].t0;
             {
-                std::lock_guard<std::mutex> lk(g_mu);
-                ProfScope prof_scope;          // (paa_prof_read counts the ranged launches like any other)
-                if ((rc = prof_scope.begin())) return rc;
-                rc = kFamilies[plan->family].launch(plan, d_samples, d_out, plan->d_tiles + first, last - first, cs());
+                std::lock_guard<std::mutex> lk(g_mu);          // (paa_prof_read counts the ranged launches like any other)
+                rc = kFamilies[plan->fam.family].execute(plan, d_samples, d_out, plan->d_tiles + first, last - first);
             }
-            if (rc) return fail(PAA_ERR_HIP, "launch of %s failed: %s", plan->kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+            if (rc) return rc;
             HIP_TRY(hipEventRecord(lane.l->range_done[used], cs()));
             first = last;
             ++used;

@@ -127,6 +127,23 @@ static bool balanced_runs(const std::vector<ClipDev> &clips, int run, int quantu
     return true;
 }
 
+// the kernel choice of a plan: its entry of kFamilies (lib_dispatch.hpp), the layout of that entry's kernel (only its own member
+// is meaningful) and the table blob on the device.  Cached per (table set, mode, rows) in TableSet::choices.
+struct FamilyChoice {
+    int family = -1;                 // index into kFamilies
+    FastLaunch fl;                   // kernels_fast.hpp
+    ct::CtLaunch cl;                 // kernels_ct.hpp
+    tri::TriLaunch trl;              // kernels_tri.hpp
+    mix::MixLayout ml;               // kernels_mix.hpp
+    blu::BluLayout bl;               // kernels_blu.hpp
+    GenLayout gl;                    // kernels_generic.hpp
+    wg::WgLayout wl;                 // kernels_wg.hpp / kernels_wgs.hpp
+    size_t lds = 0;
+    std::string kernel_name;
+    unsigned char *d_blob = nullptr;       // the entry's device tables (ct, tri, mix, blu, generic: LDS + global tables; wgr: WgrTab;
+                                           // wg: the digit-reversal permutation), or none
+};
+
 struct paa_plan {
     long long n_clips = 0;
     int sample_kind = 0;
@@ -144,44 +161,21 @@ struct paa_plan {
     StatChunk *d_chunks = nullptr;
     void *d_psum = nullptr, *d_pmin = nullptr, *d_pmax = nullptr;
     long long *d_mid_off = nullptr;
-    GenLayout gl;                    // generic kernel: LDS layout + table blob
-    unsigned char *d_gen_blob = nullptr;
-    bool blob_cached = false;        // d_gen_blob belongs to the table set's FamilyChoice (not freed with the plan)
+    FamilyChoice fam;                // the kernel that runs the plan (lib_dispatch.hpp)
+    bool blob_cached = false;        // fam.d_blob belongs to the table set's cached FamilyChoice (not freed with the plan)
     void *d_block = nullptr;         // the plan's one device block: d_clips, d_tiles, d_chunks, d_norms, d_psum / pmin / pmax point into it
-    int big = 0;                     // window beyond the LDS envelope of the one-wave-per-frame kernels
-    void *d_big = nullptr;
+    void *d_big = nullptr;           // scratch of the big-window paths (run_wg, run_big)
     size_t big_bytes = 0;
-    int wg = 0;                      // ... whose transform still fits ONE WORKGROUP's LDS (kernels_wg.hpp); else HBM passes (kernels_big.hpp)
-    wg::WgLayout wl;
     std::vector<wg::FrameRef> wg_frames;              // every frame of the plan, chunk after chunk (a chunk's rows fit the scratch)
     std::vector<std::pair<long long, long long>> wg_chunks;     // [first, last) into wg_frames
     wg::FrameRef *d_wg_frames = nullptr;
     std::vector<wg::FrameRef> wg_tasks;               // split transforms (wl.r0 > 0): (frame, sub-transform pair) records, chunk after chunk
     std::vector<std::pair<long long, long long>> wg_task_chunks;
     wg::FrameRef *d_wg_tasks = nullptr;
-    unsigned short *d_wg_perm = nullptr;
     long long wg_rows = 0;           // spectrum rows of the largest chunk
-    int wgs_r0 = 0, wgs_q = 0;       // r0 > 0: the split runs on kernels_wgs.hpp (r0 x q samples: 44 100, 22 050, 48 000, 32 000, 24 000): wg_tasks holds (frame, task type) records
-    int wgr = 0;                     // > 0: shape id of the fused three-pass kernel (kernels_wgr.hpp): 16 000- / 8 000-sample windows
-    std::vector<Tile> wgr_runs;      // runs of consecutive frames, about one per CU
-    Tile *d_wgr_runs = nullptr;
-    wgr::WgrTab *d_wgr_tab = nullptr;      // mel constants + chroma lists of the plan's (fs, window)
     long long mid_off_step = -1;
     long long n_tiles = 0, n_chunks = 0;
-    size_t lds = 0;
-    int fast = 0;                    // 1: specialised kernel
-    FastLaunch fl;
-    int mixk = 0;                    // 1: in-place mixed-radix kernel (kernels_mix.hpp); table blob in d_gen_blob
-    mix::MixLayout ml;
-    int bluk = 0;                    // 1: Bluestein kernel (kernels_blu.hpp); table blob (LDS + global tables) in d_gen_blob
-    blu::BluLayout bl;
-    int ct = 0;                      // 1: register-FFT family for windows 2 RA RB (kernels_ct.hpp); table blob in d_gen_blob
-    ct::CtLaunch cl;
-    int tri = 0;                     // 1: three-pass register FFT for the large default windows (kernels_tri.hpp); blob in d_gen_blob
-    tri::TriLaunch trl;
-    int family = -1;                 // index into kFamilies (lib_dispatch.hpp); -1: the big-window path
     std::vector<Tile> tiles_host;    // host copy of the tile list (plans built for a ranged launch only)
-    std::string kernel_name;
 };
 
 static std::atomic<int> g_live_plans{0};          // plans hold raw pointers into the device's table sets (freed outside g_mu too)
@@ -193,10 +187,7 @@ static void plan_free(paa_plan *p) {
     pool_free(p->d_mid_off);
     pool_free(p->d_wg_frames);
     pool_free(p->d_wg_tasks);
-    pool_free(p->d_wg_perm);
-    pool_free(p->d_wgr_runs);
-    pool_free(p->d_wgr_tab);
-    if (!p->blob_cached) pool_free(p->d_gen_blob);
+    if (!p->blob_cached) pool_free(p->fam.d_blob);
     if (p->d_big) (void)hipFree(p->d_big);
     delete p;
 }
@@ -207,271 +198,6 @@ static void plan_free_synced(paa_plan *p) {
     if (!p) return;
     if (cs()) (void)hipStreamSynchronize(cs());
     plan_free(p);
-}
-
-#include "lib_dispatch.hpp"
-
-// ranges > 1: the caller will launch the plan's tiles in that many consecutive groups (run_host_st's copy-back pipeline)
-static int plan_build(const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window, int step,
-                      int deltas, int mode, paa_plan **out, int ranges = 1) {
-    int rc = ensure_init();
-    if (rc) return rc;
-    if (!offsets || n_clips < 1 || !out) return fail(PAA_ERR_ARG, "null offsets / no clips");
-    if (window < 2 || step < 1) return fail(PAA_ERR_ARG, "window=%d step=%d: need window >= 2, step >= 1", window, step);
-    if (sample_kind < 0 || sample_kind > 2)
-        return fail(PAA_ERR_ARG, "sample_kind must be 0 (int16), 1 (float64) or 2 (interleaved stereo int16)");
-    if (!(fs > 0)) return fail(PAA_ERR_ARG, "sampling rate must be positive");
-    std::unique_ptr<paa_plan, void (*)(paa_plan *)> p(new paa_plan(), plan_free);
-    ++g_live_plans;
-    p->n_clips = n_clips;
-    p->sample_kind = sample_kind;
-    p->mode = mode;
-    TableSet *tab = nullptr;
-    if ((rc = get_tables(fs, window, mode == 0, mode != 1, &tab))) return rc;
-    p->tab = tab;
-    const int Nf = window / 2;
-    const int F = (mode == 0) ? kBase * (deltas ? 2 : 1) : 0;
-    p->row_width = (mode == 1) ? Nf : (mode == 2 ? 12 : 0);
-
-    // ---- clips
-    p->clips.resize(n_clips);
-    p->alloc_rows.assign(n_clips, 0);
-    long long out_off = 0, total_frames = 0, n_chunks = 0;
-    p->stat_chunk = stat_chunk_for(offsets[n_clips] - offsets[0], g_num_cu);
-    const int kChunk = p->stat_chunk;
-    for (int64_t c = 0; c < n_clips; ++c) {
-        const long long n = offsets[c + 1] - offsets[c];
-        if (n < 0) return fail(PAA_ERR_ARG, "offsets must be non-decreasing (clip %lld)", (long long)c);
-        ClipDev &cd = p->clips[c];
-        cd.sample_off = offsets[c];
-        cd.n = n;
-        cd.out_off = out_off;
-        long long T = 0, rows = 0;
-        if (mode == 0) {
-            T = paa_num_frames(n, window, step);
-            if (T < 1)
-                return fail(PAA_ERR_TOO_SHORT, "need at least one array to concatenate (clip %lld has %lld samples, "
-                            "window %d)", (long long)c, n, window);
-            rows = T;
-            out_off += (long long)F * T;
-        } else {
-            int64_t filled = 0;
-            rows = (mode == 1) ? paa_spectrogram_rows(n, window, step, &filled)
-                               : paa_chromagram_rows(n, window, step, &filled);
-            if (rows < 1)
-                return fail(PAA_ERR_TOO_SHORT, "signal too short for window %d / step %d (clip %lld, %lld samples)",
-                            window, step, (long long)c, n);
-            // full-length frames only; a truncated chromagram tail frame is added by the caller
-            long long full = 0;
-            for (long long pos = window; pos + window <= n && full < filled; pos += step) ++full;
-            T = full;
-            out_off += rows * p->row_width;
-        }
-        if (T > 0x7fffffffLL) return fail(PAA_ERR_ARG, "clip %lld has too many frames", (long long)c);
-        p->alloc_rows[c] = rows;
-        cd.T = (int)T;
-        cd.stat_first = (int)n_chunks;
-        cd.stat_count = (int)((n + kChunk - 1) / kChunk);
-        cd.pad = 0;
-        n_chunks += cd.stat_count;
-        total_frames += T;
-    }
-    p->total_frames = total_frames;
-    p->out_doubles = out_off;
-    p->n_chunks = n_chunks;
-
-    // ---- device plan
-    PlanDev &P = p->P;
-    memset(&P, 0, sizeof(P));
-    P.W = window; P.S = step; P.Nf = Nf; P.Nc = tab->fft.len; P.even = tab->fft.even;
-    P.n_pass = (int)tab->fft.radix.size();
-    if (P.n_pass > 24) return fail(PAA_ERR_UNSUPPORTED, "window %d needs more than 24 FFT passes", window);
-    for (int i = 0; i < P.n_pass; ++i) P.radix[i] = tab->fft.radix[i];
-    P.tw = tab->d_tw; P.post = tab->d_post;
-    P.mel_lo = tab->d_mel_lo; P.mel_cnt = tab->d_mel_cnt; P.mel_off = tab->d_mel_off; P.mel_w = tab->d_mel_w;
-    P.dct = tab->d_dct; P.ch_start = tab->d_ch_start; P.ch_src = tab->d_ch_src; P.ch_w = tab->d_ch_w;
-    P.fs = fs; P.deltas = deltas ? 1 : 0; P.F = F;
-    P.blk_t = window / 10; P.blk_f = Nf / 10;
-    P.mode = mode;
-    P.frame_origin = (mode == 0) ? 0 : window;
-    { const char *dbg = experiment_env("PAA_KERNEL_DEBUG"); P.debug = dbg ? atoi(dbg) : 0; }
-
-    // ---- kernel choice + tiles: the first family of kFamilies (lib_dispatch.hpp) that takes the shape; its run rule
-    FamilyCtx fc{p.get(), tab, fs, window, step, deltas, mode, sample_kind, F, total_frames, ranges};
-    RunRule rr;
-    rc = choose_family(fc, rr);
-    if (rc) return rc;
-    const int run = rr.run, run_quantum = rr.quantum, run_halo = rr.halo_inside;
-    std::vector<Tile> tiles;
-    tiles.reserve((size_t)(total_frames / run + n_clips));
-    std::vector<std::vector<int>> run_lens;
-#ifndef PAA_BALANCED_RUNS
-#define PAA_BALANCED_RUNS 1           // (0: A/B build of scripts/rounds/r05/gpu_r05w.sh -- equal runs, 250 workgroups for the one-hour clip)
-#endif
-    const bool balanced = PAA_BALANCED_RUNS && rr.fill_wg_runs > 0 && ranges <= 1 &&
-                          balanced_runs(p->clips, run, run_quantum, run_halo, rr.fill_wg_runs, g_num_cu, rr.fill_min_run, run_lens);
-    for (int64_t c = 0; c < n_clips; ++c) {
-        const long long T = p->clips[c].T;
-        if (T <= 0) continue;
-        if (balanced) {
-            long long t0 = 0;
-            for (int cnt : run_lens[(size_t)c]) {
-                Tile tl; tl.clip = (int)c; tl.t0 = (int)t0; tl.cnt = cnt; tl.pad = 0;
-                tiles.push_back(tl);
-                t0 += cnt;
-            }
-            continue;
-        }
-        const int len = clip_run_length(T, run, run_quantum);          // equal runs per clip
-        for (long long t0 = 0; t0 < T;) {
-            const long long want = (t0 > 0) ? len - run_halo : len;
-            Tile tl; tl.clip = (int)c; tl.t0 = (int)t0; tl.cnt = (int)std::min<long long>(want, T - t0); tl.pad = 0;
-            tiles.push_back(tl);
-            t0 += tl.cnt;
-        }
-    }
-    p->n_tiles = (long long)tiles.size();
-    if (ranges > 1) p->tiles_host = tiles;          // (the host pipeline cuts the list at frame boundaries)
-    if (p->n_tiles > 0x7fffffffLL || n_chunks > 0x7fffffffLL || n_clips > 0x7fffffffLL)
-        return fail(PAA_ERR_UNSUPPORTED, "batch too large for one launch (%lld runs, %lld statistics chunks, %lld clips)",
-                    p->n_tiles, n_chunks, (long long)n_clips);
-    std::vector<StatChunk> chunks;
-    chunks.reserve((size_t)n_chunks);
-    for (int64_t c = 0; c < n_clips; ++c)
-        for (int i = 0; i < p->clips[c].stat_count; ++i) {
-            StatChunk ch; ch.start = p->clips[c].sample_off + (long long)i * kChunk;
-            ch.len = (int)std::min<long long>(kChunk, p->clips[c].n - (long long)i * kChunk);
-            ch.clip = (int)c;
-            chunks.push_back(ch);
-        }
-    // ONE pooled device block and ONE upload per plan (the host-buffer entry points build a plan per call):
-    //   [clip descriptors | tiles | statistics chunks] (uploaded) [clip constants | partial sums | minima | maxima]
-    {
-        const size_t nch = (size_t)std::max<long long>(n_chunks, 1);
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_clips = 0, o_tiles = o_clips + up(p->clips.size() * sizeof(ClipDev));
-        const size_t o_chunks = o_tiles + up(std::max<size_t>(tiles.size(), 1) * sizeof(Tile));
-        const size_t o_norms = o_chunks + up(std::max<size_t>(chunks.size(), 1) * sizeof(StatChunk));
-        const size_t o_sum = o_norms + up((size_t)n_clips * sizeof(ClipNorm));
-        const size_t o_min = o_sum + up(nch * 8), o_max = o_min + up(nch * 8), total = o_max + up(nch * 8);
-        if ((rc = pool_alloc(&p->d_block, total))) return rc;
-        std::vector<unsigned char> stage(o_norms, 0);
-        memcpy(stage.data() + o_clips, p->clips.data(), p->clips.size() * sizeof(ClipDev));
-        if (!tiles.empty()) memcpy(stage.data() + o_tiles, tiles.data(), tiles.size() * sizeof(Tile));
-        if (!chunks.empty()) memcpy(stage.data() + o_chunks, chunks.data(), chunks.size() * sizeof(StatChunk));
-        HIP_TRY(hipMemcpy(p->d_block, stage.data(), o_norms, hipMemcpyHostToDevice));
-        unsigned char *b = reinterpret_cast<unsigned char *>(p->d_block);
-        p->d_clips = reinterpret_cast<ClipDev *>(b + o_clips);
-        p->d_tiles = reinterpret_cast<Tile *>(b + o_tiles);
-        p->d_chunks = reinterpret_cast<StatChunk *>(b + o_chunks);
-        p->d_norms = reinterpret_cast<ClipNorm *>(b + o_norms);
-        p->d_psum = b + o_sum; p->d_pmin = b + o_min; p->d_pmax = b + o_max;
-    }
-    // windows beyond the one-wave kernels whose transform fits one workgroup's LDS: the frame list of kernels_wg.hpp
-    std::unique_ptr<wgr::WgrTab> wgr_tab;
-    if (p->big && wgr::wgr_shape_id(window)) {
-        wgr_tab.reset(new wgr::WgrTab());
-        if (!wgr::wgr_build_tab(wgr::wgr_threads(wgr::wgr_shape_id(window)), mode == 0 ? &tab->mel : nullptr,
-                                mode != 1 ? &tab->chroma : nullptr, *wgr_tab))
-            wgr_tab.reset();          // (a mel bank this kernel's lane jobs cannot hold: kernels_wg.hpp takes the window)
-    }
-    if (wgr_tab) {
-        // the 1 s windows of music_thumbnailing at 16 / 8 kHz: one fused launch, the transform in registers (kernels_wgr.hpp)
-        p->wgr = wgr::wgr_shape_id(window);
-        if ((rc = upload_pooled(&p->d_wgr_tab, wgr_tab.get(), 1))) return rc;
-        wgr::wgr_build_runs(p->clips, g_num_cu, p->wgr_runs);
-        if (p->wgr_runs.size() > 0x7fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many runs for one launch");
-        if ((rc = upload_pooled(&p->d_wgr_runs, p->wgr_runs.data(), std::max<size_t>(p->wgr_runs.size(), 1)))) return rc;
-        p->kernel_name = std::string(mode == 0 ? "st" : (mode == 1 ? "spectrogram" : "chromagram")) + "_wgr_" + wgr::wgr_shape_name(p->wgr);
-    } else if (p->big) {
-        std::vector<unsigned short> perm;
-        if (wg::wg_layout(tab->fft, p->wl, perm)) {
-            // spectrum scratch: one row of Nf doubles per frame of a chunk, at most 1 GiB; a chunk that starts inside a clip
-            // begins with that clip's previous frame once more (halo: only its spectrum row is wanted)
-            const long long cap = std::max<long long>(2, ((long long)1 << 30) / ((long long)Nf * 8));
-            long long first = 0;
-            for (int64_t c = 0; c < n_clips; ++c)
-                for (long long t = 0; t < p->clips[c].T; ++t) {
-                    long long in_chunk = (long long)p->wg_frames.size() - first;
-                    if (in_chunk >= cap) {
-                        p->wg_chunks.emplace_back(first, (long long)p->wg_frames.size());
-                        first = (long long)p->wg_frames.size();
-                        in_chunk = 0;
-                        if (t > 0 && mode != 1) p->wg_frames.push_back(wg::FrameRef{(int)c, (int)(t - 1), 0, 1});
-                    }
-                    p->wg_frames.push_back(wg::FrameRef{(int)c, (int)t, (int)((long long)p->wg_frames.size() - first), 0});
-                }
-            if ((long long)p->wg_frames.size() > first) p->wg_chunks.emplace_back(first, (long long)p->wg_frames.size());
-            for (auto &ch : p->wg_chunks) {
-                p->wg_rows = std::max(p->wg_rows, ch.second - ch.first);
-                for (long long i = ch.first; i < ch.second; ++i) p->wg_frames[(size_t)i].row = (int)(i - ch.first);
-            }
-            if ((rc = upload_pooled(&p->d_wg_frames, p->wg_frames.data(), std::max<size_t>(p->wg_frames.size(), 1)))) return rc;
-            if (p->wl.r0 && wgs::wgs_select(window).r0) {
-                // the real-input split on register passes (kernels_wgs.hpp): the tasks of a frame side by side (FrameRef::halo = halo | type << 8)
-                p->wgs_r0 = wgs::wgs_select(window).r0;
-                p->wgs_q = wgs::wgs_select(window).q;
-                const int n_types = wgs::wgs_task_types(p->wgs_r0);
-                for (auto &ch : p->wg_chunks) {
-                    const long long t0 = (long long)p->wg_tasks.size();
-                    auto push = [&](long long i, int ty) {
-                        wg::FrameRef f = p->wg_frames[(size_t)i];
-                        f.halo |= ty << 8;
-                        p->wg_tasks.push_back(f);
-                    };
-                    if (p->wgs_r0 == 6) {
-                        // three sub-transforms per frame: {1, 2} and the packed one -- the packed units of two CONSECUTIVE frames of a clip (consecutive
-                        // rows) share a task (type 1, on the first frame's record); a frame without such a partner runs its packed unit alone (type 2)
-                        for (long long i = ch.first; i < ch.second;) {
-                            const wg::FrameRef &a = p->wg_frames[(size_t)i];
-                            const bool pair = i + 1 < ch.second && p->wg_frames[(size_t)i + 1].clip == a.clip && p->wg_frames[(size_t)i + 1].t == a.t + 1 &&
-                                              p->wg_frames[(size_t)i + 1].row == a.row + 1;
-                            push(i, 0);
-                            if (pair) { push(i + 1, 0); push(i, 1); i += 2; }
-                            else { push(i, 2); i += 1; }
-                        }
-                    } else {
-                        for (long long i = ch.first; i < ch.second; ++i)
-                            for (int ty = 0; ty < n_types; ++ty) push(i, ty);
-                    }
-                    p->wg_task_chunks.emplace_back(t0, (long long)p->wg_tasks.size());
-                }
-                if (p->wg_tasks.size() > 0x7fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many frames for the split transform");
-                if ((rc = upload_pooled(&p->d_wg_tasks, p->wg_tasks.data(), std::max<size_t>(p->wg_tasks.size(), 1)))) return rc;
-            } else if (p->wl.r0) {
-                // tasks of a frame: sub-transform 0 alone, the pairs {q, r0 - q}, r0 / 2 alone (FrameRef::halo = halo | q << 8)
-                const int r0 = p->wl.r0;
-                for (auto &ch : p->wg_chunks) {
-                    const long long t0 = (long long)p->wg_tasks.size();
-                    // (the pairs first: they cost twice what the single sub-transforms do, and tasks are handed out in list order)
-                    for (int pairs = 1; pairs >= 0; --pairs)
-                        for (long long i = ch.first; i < ch.second; ++i)
-                            for (int q = 0; 2 * q <= r0; ++q) {
-                                if ((q != 0 && 2 * q != r0) != (pairs != 0)) continue;
-                                wg::FrameRef f = p->wg_frames[(size_t)i];
-                                f.halo |= q << 8;
-                                p->wg_tasks.push_back(f);
-                            }
-                    p->wg_task_chunks.emplace_back(t0, (long long)p->wg_tasks.size());
-                }
-                if (p->wg_tasks.size() > 0x7fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many frames for the split transform");
-                if ((rc = upload_pooled(&p->d_wg_tasks, p->wg_tasks.data(), std::max<size_t>(p->wg_tasks.size(), 1)))) return rc;
-            }
-            if ((rc = upload_pooled(&p->d_wg_perm, perm.data(), perm.size()))) return rc;
-            p->wg = 1;
-            p->kernel_name = p->wgs_r0 ? std::string(mode == 0 ? "st" : (mode == 1 ? "spectrogram" : "chromagram")) + "_wgs_" + std::to_string(p->wgs_r0) + "x" + std::to_string(p->wgs_q)
-                           : p->wl.r0 ? ((mode == 0) ? "st_wg_split_fft" : (mode == 1 ? "spectrogram_wg_split_fft" : "chromagram_wg_split_fft"))
-                                      : ((mode == 0) ? "st_wg_lds_fft" : (mode == 1 ? "spectrogram_wg_lds_fft" : "chromagram_wg_lds_fft"));
-        }
-    }
-    // every one-launch feature kernel folds the statistics partials into the clip constants itself (its waves' prologue);
-    // chromagram plans keep clip_params_kernel (the truncated-tail kernel of the host entry point reads its output), and so
-    // does the big-window path (a chain of small kernels)
-    P.st_sum = p->d_psum; P.st_min = p->d_pmin; P.st_max = p->d_pmax;
-    P.st_scale = sample_kind == 1 ? sample_scale<double>() : (sample_kind == 2 ? sample_scale<stereo16>() : sample_scale<int16_t>());
-    P.norms_inline = (!p->big && mode != 2) ? 1 : 0;
-    *out = p.release();
-    return PAA_OK;
 }
 
 static int launch_stats(paa_plan *p, const void *d_packed) {
@@ -589,12 +315,33 @@ struct ProfScope {
     ~ProfScope() { if (stop) (void)hipEventRecord(stop, cs()); }
 };
 
-// windows beyond the one-wave kernels whose transform fits one workgroup's LDS (kernels_wg.hpp): per chunk of frames one
-// launch for the spectra of ALL its frames and one for their features, then one for the delta rows of all clips
+// the delta rows of every clip of a features plan with deltas (kernels_wg.hpp: wg_delta_kernel), behind run_wg / run_wgr
+static int launch_wg_deltas(paa_plan *p, double *d_out) {
+    if (p->P.mode != 0 || !p->P.deltas) return PAA_OK;
+    long long maxT = 0;
+    for (auto &cd : p->clips) maxT = std::max<long long>(maxT, cd.T);
+    const long long gx = ((long long)kBase * maxT + 255) / 256;
+    if (gx > 0x7fffffffLL)
+        return fail(PAA_ERR_UNSUPPORTED, "delta grid too large (%lld frames in one clip)", maxT);
+    // gridDim.y holds at most 65 535 clips: larger batches go in blocks (advisor, round 5: they used to be refused here
+    // although run_big, which took them before round 5, loops the same way)
+    for (long long c0 = 0; c0 < p->n_clips; c0 += 65535) {
+        const unsigned ny = (unsigned)std::min<long long>(65535, p->n_clips - c0);
+        hipLaunchKernelGGL(wg::wg_delta_kernel, dim3((unsigned)gx, ny), dim3(256), 0, cs(), p->d_clips + c0, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return PAA_OK;
+}
+
+// windows beyond the one-wave kernels whose transform fits one workgroup's LDS (kernels_wg.hpp; ws.r0 > 0: the split runs on
+// kernels_wgs.hpp, r0 x q samples): per chunk of frames one launch for the spectra of ALL its frames and one for their
+// features, then one for the delta rows of all clips
 template <typename T>
-static int run_wg(paa_plan *p, const void *d_packed, double *d_out) {
+static int run_wg(paa_plan *p, const void *d_packed, double *d_out, const wgs::Sel &ws) {
     const PlanDev &P = p->P;
-    const size_t psum_row = p->wgs_r0 ? (size_t)(p->wgs_r0 / 2) * 4 : 0;                            // kernels_wgs.hpp: the units' partial sums of a row
+    const wg::WgLayout &wl = p->fam.wl;
+    const unsigned short *d_perm = reinterpret_cast<const unsigned short *>(p->fam.d_blob);
+    const size_t psum_row = ws.r0 ? (size_t)(ws.r0 / 2) * 4 : 0;                            // kernels_wgs.hpp: the units' partial sums of a row
     const size_t need = (size_t)p->wg_rows * ((size_t)P.Nf * 8 + 24 + psum_row * 8) + 256;       // (+ the task counter of the split transform)
     bool fresh = false;
     if (need > p->big_bytes) {
@@ -608,24 +355,24 @@ static int run_wg(paa_plan *p, const void *d_packed, double *d_out) {
     double *psum = tfeat + 3 * (size_t)p->wg_rows;
     int *task_counter = reinterpret_cast<int *>(psum + psum_row * (size_t)p->wg_rows);
     // (kernels_wgs.hpp: one counter per XCD segment + the workgroups that are done; its last workgroup leaves them at zero)
-    if (fresh && p->wgs_r0) HIP_TRY(hipMemsetAsync(task_counter, 0, 16 * sizeof(int), cs()));
+    if (fresh && ws.r0) HIP_TRY(hipMemsetAsync(task_counter, 0, 16 * sizeof(int), cs()));
     static LdsAttrCache attr;
-    if (!attr.covers((size_t)p->wl.lds_bytes)) {
+    if (!attr.covers((size_t)wl.lds_bytes)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_spectrum_kernel<T, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, p->wl.lds_bytes));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_spectrum_kernel<T, 768>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, p->wl.lds_bytes));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_split_kernel<T, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, p->wl.lds_bytes));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_split_kernel<T, 768>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, p->wl.lds_bytes));
-        attr.set((size_t)p->wl.lds_bytes);
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
+        attr.set((size_t)wl.lds_bytes);
     }
     static LdsAttrCache attr_feat;
-    if (!attr_feat.covers((size_t)p->wl.feat_lds_bytes)) {
+    if (!attr_feat.covers((size_t)wl.feat_lds_bytes)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_feat_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    p->wl.feat_lds_bytes));
-        attr_feat.set((size_t)p->wl.feat_lds_bytes);
+                                    wl.feat_lds_bytes));
+        attr_feat.set((size_t)wl.feat_lds_bytes);
     }
     for (size_t ci = 0; ci < p->wg_chunks.size(); ++ci) {
         const auto &ch = p->wg_chunks[ci];
@@ -633,89 +380,204 @@ static int run_wg(paa_plan *p, const void *d_packed, double *d_out) {
         const wg::FrameRef *fr = p->d_wg_frames + ch.first;
         ProfScope prof_scope;          // (bench.py's event pairs bracket the spectrum kernel: the dominant one of this path)
         { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-        if (p->wl.r0) {
+        if (wl.r0) {
             // split transforms: persistent workgroups over (frame, sub-transform pair) tasks, one per CU
             const auto &tc = p->wg_task_chunks[ci];
             const unsigned nt = (unsigned)(tc.second - tc.first);
             const wg::FrameRef *tk = p->d_wg_tasks + tc.first;
             const unsigned grid = std::min<unsigned>(nt, (unsigned)g_num_cu);
-            if (!p->wgs_r0) HIP_TRY(hipMemsetAsync(task_counter, 0, sizeof(int), cs()));
-            if (p->wgs_r0) {
-                if (launch::wgs(p->wgs_r0, p->wgs_q, p->sample_kind, P, d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, g_num_cu, spec, tfeat, psum, d_out, cs()))
-                    return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
-            } else if (p->wl.threads == 768)
-                hipLaunchKernelGGL((wg::wg_split_kernel<T, 768>), dim3(grid), dim3(768), (size_t)p->wl.lds_bytes, cs(), P, p->wl,
-                                   p->d_wg_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
+            if (!ws.r0) HIP_TRY(hipMemsetAsync(task_counter, 0, sizeof(int), cs()));
+            if (ws.r0) {
+                if (launch::wgs(ws.r0, ws.q, p->sample_kind, P, d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, g_num_cu, spec, tfeat, psum, d_out, cs()))
+                    return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+            } else if (wl.threads == 768)
+                hipLaunchKernelGGL((wg::wg_split_kernel<T, 768>), dim3(grid), dim3(768), (size_t)wl.lds_bytes, cs(), P, wl,
+                                   d_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
             else
-                hipLaunchKernelGGL((wg::wg_split_kernel<T, 512>), dim3(grid), dim3(512), (size_t)p->wl.lds_bytes, cs(), P, p->wl,
-                                   p->d_wg_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
+                hipLaunchKernelGGL((wg::wg_split_kernel<T, 512>), dim3(grid), dim3(512), (size_t)wl.lds_bytes, cs(), P, wl,
+                                   d_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
             if (prof_scope.stop) { (void)hipEventRecord(prof_scope.stop, cs()); prof_scope.stop = nullptr; }
-            if (P.mode == 0 && !p->wgs_r0)          // (kernels_wgs.hpp forms the time-domain features in its {1, 2} tasks)
+            if (P.mode == 0 && !ws.r0)          // (kernels_wgs.hpp forms the time-domain features in its {1, 2} tasks)
                 hipLaunchKernelGGL((wg::wg_time_kernel<T>), dim3(n), dim3(64 * wg::kTimeWaves), 0, cs(), P, (const T *)d_packed, p->d_clips, p->d_norms,
                                    fr, tfeat);
         } else {
         // persistent workgroups: as many as the LDS footprint lets the chip hold at once, each walks frames b, b + grid, ...
-        const unsigned per_cu = (unsigned)std::max<size_t>(1, ((size_t)160 * 1024) / (size_t)p->wl.lds_bytes);
-        const unsigned grid = std::min<unsigned>(n, (unsigned)g_num_cu * std::min<unsigned>(per_cu, p->wl.threads == 768 ? 2u : 4u));
-        if (p->wl.threads == 768)
-            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 768>), dim3(grid), dim3(768), (size_t)p->wl.lds_bytes, cs(), P, p->wl,
-                               p->d_wg_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
+        const unsigned per_cu = (unsigned)std::max<size_t>(1, ((size_t)160 * 1024) / (size_t)wl.lds_bytes);
+        const unsigned grid = std::min<unsigned>(n, (unsigned)g_num_cu * std::min<unsigned>(per_cu, wl.threads == 768 ? 2u : 4u));
+        if (wl.threads == 768)
+            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 768>), dim3(grid), dim3(768), (size_t)wl.lds_bytes, cs(), P, wl,
+                               d_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
         else
-            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 512>), dim3(grid), dim3(512), (size_t)p->wl.lds_bytes, cs(), P, p->wl,
-                               p->d_wg_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
+            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 512>), dim3(grid), dim3(512), (size_t)wl.lds_bytes, cs(), P, wl,
+                               d_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
         if (prof_scope.stop) { (void)hipEventRecord(prof_scope.stop, cs()); prof_scope.stop = nullptr; }
         }
-        if (P.mode != 1 && p->wgs_r0) {
-            if (launch::wgs_feat(p->wgs_r0, p->wgs_q, P, fr, (int)n, p->d_clips, spec, tfeat, psum, d_out, cs()))
-                return fail(PAA_ERR_HIP, "launch of the feature kernel of %s failed: %s", p->kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+        if (P.mode != 1 && ws.r0) {
+            if (launch::wgs_feat(ws.r0, ws.q, P, fr, (int)n, p->d_clips, spec, tfeat, psum, d_out, cs()))
+                return fail(PAA_ERR_HIP, "launch of the feature kernel of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
         } else if (P.mode != 1) {
-            if (p->wl.feat_staged)
-                hipLaunchKernelGGL(wg::wg_feat_kernel<true>, dim3(n), dim3(wg::kFeatThreads), (size_t)p->wl.feat_lds_bytes, cs(), P, fr,
+            if (wl.feat_staged)
+                hipLaunchKernelGGL(wg::wg_feat_kernel<true>, dim3(n), dim3(wg::kFeatThreads), (size_t)wl.feat_lds_bytes, cs(), P, fr,
                                    p->d_clips, spec, tfeat, d_out);
             else
-                hipLaunchKernelGGL(wg::wg_feat_kernel<false>, dim3(n), dim3(wg::kFeatThreads), (size_t)p->wl.feat_lds_bytes, cs(), P, fr,
+                hipLaunchKernelGGL(wg::wg_feat_kernel<false>, dim3(n), dim3(wg::kFeatThreads), (size_t)wl.feat_lds_bytes, cs(), P, fr,
                                    p->d_clips, spec, tfeat, d_out);
         }
         HIP_TRY(hipGetLastError());
     }
-    if (P.mode == 0 && P.deltas) {
-        long long maxT = 0;
-        for (auto &cd : p->clips) maxT = std::max<long long>(maxT, cd.T);
-        const long long gx = ((long long)kBase * maxT + 255) / 256;
-        if (gx > 0x7fffffffLL)
-            return fail(PAA_ERR_UNSUPPORTED, "delta grid too large (%lld frames in one clip)", maxT);
-        // gridDim.y holds at most 65 535 clips: larger batches go in blocks (advisor, round 5: they used to be refused here
-        // although run_big, which took them before round 5, loops the same way)
-        for (long long c0 = 0; c0 < p->n_clips; c0 += 65535) {
-            const unsigned ny = (unsigned)std::min<long long>(65535, p->n_clips - c0);
-            hipLaunchKernelGGL(wg::wg_delta_kernel, dim3((unsigned)gx, ny), dim3(256), 0, cs(), p->d_clips + c0, d_out);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return PAA_OK;
+    return launch_wg_deltas(p, d_out);
 }
 
 // the fused three-pass kernel (kernels_wgr.hpp): ONE launch for all frames of all clips, then the delta rows
-static int run_wgr(paa_plan *p, const void *d_packed, double *d_out) {
+static int run_wgr(paa_plan *p, const void *d_packed, double *d_out, const Tile *runs, long long n_runs) {
     const PlanDev &P = p->P;
-    if (!p->wgr_runs.empty()) {
+    if (n_runs > 0) {
         ProfScope prof_scope;
         { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-        if (launch::wgr(p->wgr, p->sample_kind, P.mode, P, d_packed, p->d_clips, p->d_norms, p->d_wgr_runs, (long long)p->wgr_runs.size(),
-                        g_num_cu, p->d_wgr_tab, d_out, cs()))
-            return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+        if (launch::wgr(wgr::wgr_shape_id(P.W), p->sample_kind, P.mode, P, d_packed, p->d_clips, p->d_norms, runs, n_runs, g_num_cu,
+                        reinterpret_cast<const wgr::WgrTab *>(p->fam.d_blob), d_out, cs()))
+            return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
     }
-    if (P.mode == 0 && P.deltas) {
-        long long maxT = 0;
-        for (auto &cd : p->clips) maxT = std::max<long long>(maxT, cd.T);
-        const long long gx = ((long long)kBase * maxT + 255) / 256;
-        if (gx > 0x7fffffffLL) return fail(PAA_ERR_UNSUPPORTED, "delta grid too large (%lld frames in one clip)", maxT);
-        for (long long c0 = 0; c0 < p->n_clips; c0 += 65535) {
-            const unsigned ny = (unsigned)std::min<long long>(65535, p->n_clips - c0);
-            hipLaunchKernelGGL(wg::wg_delta_kernel, dim3((unsigned)gx, ny), dim3(256), 0, cs(), p->d_clips + c0, d_out);
-            HIP_TRY(hipGetLastError());
+    return launch_wg_deltas(p, d_out);
+}
+
+#include "lib_dispatch.hpp"
+
+// ranges > 1: the caller will launch the plan's tiles in that many consecutive groups (run_host_st's copy-back pipeline)
+static int plan_build(const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window, int step,
+                      int deltas, int mode, paa_plan **out, int ranges = 1) {
+    int rc = ensure_init();
+    if (rc) return rc;
+    if (!offsets || n_clips < 1 || !out) return fail(PAA_ERR_ARG, "null offsets / no clips");
+    if (window < 2 || step < 1) return fail(PAA_ERR_ARG, "window=%d step=%d: need window >= 2, step >= 1", window, step);
+    if (sample_kind < 0 || sample_kind > 2)
+        return fail(PAA_ERR_ARG, "sample_kind must be 0 (int16), 1 (float64) or 2 (interleaved stereo int16)");
+    if (!(fs > 0)) return fail(PAA_ERR_ARG, "sampling rate must be positive");
+    std::unique_ptr<paa_plan, void (*)(paa_plan *)> p(new paa_plan(), plan_free);
+    ++g_live_plans;
+    p->n_clips = n_clips;
+    p->sample_kind = sample_kind;
+    p->mode = mode;
+    TableSet *tab = nullptr;
+    if ((rc = get_tables(fs, window, mode == 0, mode != 1, &tab))) return rc;
+    p->tab = tab;
+    const int Nf = window / 2;
+    const int F = (mode == 0) ? kBase * (deltas ? 2 : 1) : 0;
+    p->row_width = (mode == 1) ? Nf : (mode == 2 ? 12 : 0);
+
+    // ---- clips
+    p->clips.resize(n_clips);
+    p->alloc_rows.assign(n_clips, 0);
+    long long out_off = 0, total_frames = 0, n_chunks = 0;
+    p->stat_chunk = stat_chunk_for(offsets[n_clips] - offsets[0], g_num_cu);
+    const int kChunk = p->stat_chunk;
+    for (int64_t c = 0; c < n_clips; ++c) {
+        const long long n = offsets[c + 1] - offsets[c];
+        if (n < 0) return fail(PAA_ERR_ARG, "offsets must be non-decreasing (clip %lld)", (long long)c);
+        ClipDev &cd = p->clips[c];
+        cd.sample_off = offsets[c];
+        cd.n = n;
+        cd.out_off = out_off;
+        long long T = 0, rows = 0;
+        if (mode == 0) {
+            T = paa_num_frames(n, window, step);
+            if (T < 1)
+                return fail(PAA_ERR_TOO_SHORT, "need at least one array to concatenate (clip %lld has %lld samples, "
+                            "window %d)", (long long)c, n, window);
+            rows = T;
+            out_off += (long long)F * T;
+        } else {
+            int64_t filled = 0;
+            rows = (mode == 1) ? paa_spectrogram_rows(n, window, step, &filled)
+                               : paa_chromagram_rows(n, window, step, &filled);
+            if (rows < 1)
+                return fail(PAA_ERR_TOO_SHORT, "signal too short for window %d / step %d (clip %lld, %lld samples)",
+                            window, step, (long long)c, n);
+            // full-length frames only; a truncated chromagram tail frame is added by the caller
+            long long full = 0;
+            for (long long pos = window; pos + window <= n && full < filled; pos += step) ++full;
+            T = full;
+            out_off += rows * p->row_width;
         }
+        if (T > 0x7fffffffLL) return fail(PAA_ERR_ARG, "clip %lld has too many frames", (long long)c);
+        p->alloc_rows[c] = rows;
+        cd.T = (int)T;
+        cd.stat_first = (int)n_chunks;
+        cd.stat_count = (int)((n + kChunk - 1) / kChunk);
+        cd.pad = 0;
+        n_chunks += cd.stat_count;
+        total_frames += T;
     }
+    p->total_frames = total_frames;
+    p->out_doubles = out_off;
+    p->n_chunks = n_chunks;
+
+    // ---- device plan
+    PlanDev &P = p->P;
+    memset(&P, 0, sizeof(P));
+    P.W = window; P.S = step; P.Nf = Nf; P.Nc = tab->fft.len; P.even = tab->fft.even;
+    P.n_pass = (int)tab->fft.radix.size();
+    if (P.n_pass > 24) return fail(PAA_ERR_UNSUPPORTED, "window %d needs more than 24 FFT passes", window);
+    for (int i = 0; i < P.n_pass; ++i) P.radix[i] = tab->fft.radix[i];
+    P.tw = tab->d_tw; P.post = tab->d_post;
+    P.mel_lo = tab->d_mel_lo; P.mel_cnt = tab->d_mel_cnt; P.mel_off = tab->d_mel_off; P.mel_w = tab->d_mel_w;
+    P.dct = tab->d_dct; P.ch_start = tab->d_ch_start; P.ch_src = tab->d_ch_src; P.ch_w = tab->d_ch_w;
+    P.fs = fs; P.deltas = deltas ? 1 : 0; P.F = F;
+    P.blk_t = window / 10; P.blk_f = Nf / 10;
+    P.mode = mode;
+    P.frame_origin = (mode == 0) ? 0 : window;
+    { const char *dbg = experiment_env("PAA_KERNEL_DEBUG"); P.debug = dbg ? atoi(dbg) : 0; }
+
+    // ---- kernel choice (the first entry of kFamilies that takes the shape) and its work list
+    FamilyCtx fc{p.get(), tab, fs, window, step, deltas, mode, sample_kind, F, total_frames, ranges};
+    if ((rc = choose_family(fc))) return rc;
+    const Family &fam = kFamilies[p->fam.family];
+    std::vector<Tile> tiles;
+    if ((rc = fam.work(fc, tiles))) return rc;
+    p->n_tiles = (long long)tiles.size();
+    if (ranges > 1 && fam.ranged) p->tiles_host = tiles;          // (the host pipeline cuts the list at frame boundaries)
+    if (p->n_tiles > 0x7fffffffLL || n_chunks > 0x7fffffffLL || n_clips > 0x7fffffffLL)
+        return fail(PAA_ERR_UNSUPPORTED, "batch too large for one launch (%lld runs, %lld statistics chunks, %lld clips)",
+                    p->n_tiles, n_chunks, (long long)n_clips);
+    std::vector<StatChunk> chunks;
+    chunks.reserve((size_t)n_chunks);
+    for (int64_t c = 0; c < n_clips; ++c)
+        for (int i = 0; i < p->clips[c].stat_count; ++i) {
+            StatChunk ch; ch.start = p->clips[c].sample_off + (long long)i * kChunk;
+            ch.len = (int)std::min<long long>(kChunk, p->clips[c].n - (long long)i * kChunk);
+            ch.clip = (int)c;
+            chunks.push_back(ch);
+        }
+    // ONE pooled device block and ONE upload per plan (the host-buffer entry points build a plan per call):
+    //   [clip descriptors | tiles | statistics chunks] (uploaded) [clip constants | partial sums | minima | maxima]
+    {
+        const size_t nch = (size_t)std::max<long long>(n_chunks, 1);
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_clips = 0, o_tiles = o_clips + up(p->clips.size() * sizeof(ClipDev));
+        const size_t o_chunks = o_tiles + up(std::max<size_t>(tiles.size(), 1) * sizeof(Tile));
+        const size_t o_norms = o_chunks + up(std::max<size_t>(chunks.size(), 1) * sizeof(StatChunk));
+        const size_t o_sum = o_norms + up((size_t)n_clips * sizeof(ClipNorm));
+        const size_t o_min = o_sum + up(nch * 8), o_max = o_min + up(nch * 8), total = o_max + up(nch * 8);
+        if ((rc = pool_alloc(&p->d_block, total))) return rc;
+        std::vector<unsigned char> stage(o_norms, 0);
+        memcpy(stage.data() + o_clips, p->clips.data(), p->clips.size() * sizeof(ClipDev));
+        if (!tiles.empty()) memcpy(stage.data() + o_tiles, tiles.data(), tiles.size() * sizeof(Tile));
+        if (!chunks.empty()) memcpy(stage.data() + o_chunks, chunks.data(), chunks.size() * sizeof(StatChunk));
+        HIP_TRY(hipMemcpy(p->d_block, stage.data(), o_norms, hipMemcpyHostToDevice));
+        unsigned char *b = reinterpret_cast<unsigned char *>(p->d_block);
+        p->d_clips = reinterpret_cast<ClipDev *>(b + o_clips);
+        p->d_tiles = reinterpret_cast<Tile *>(b + o_tiles);
+        p->d_chunks = reinterpret_cast<StatChunk *>(b + o_chunks);
+        p->d_norms = reinterpret_cast<ClipNorm *>(b + o_norms);
+        p->d_psum = b + o_sum; p->d_pmin = b + o_min; p->d_pmax = b + o_max;
+    }
+    // the one-wave feature kernels fold the statistics partials into the clip constants themselves (their waves' prologue);
+    // chromagram plans keep clip_params_kernel (the truncated-tail kernel of the host entry point reads its output), and so
+    // do the big-window paths
+    P.st_sum = p->d_psum; P.st_min = p->d_pmin; P.st_max = p->d_pmax;
+    P.st_scale = sample_kind == 1 ? sample_scale<double>() : (sample_kind == 2 ? sample_scale<stereo16>() : sample_scale<int16_t>());
+    P.norms_inline = (fam.norms_inline && mode != 2) ? 1 : 0;
+    *out = p.release();
     return PAA_OK;
 }
 
@@ -727,20 +589,7 @@ extern "C" int paa_plan_execute(paa_plan_t *plan, const void *d_packed, double *
     if (rc) return rc;
     rc = launch_stats(plan, d_packed);
     if (rc) return rc;
-    if (plan->wgr) return run_wgr(plan, d_packed, d_out);
-    if (plan->wg)
-        return plan->sample_kind == 0 ? run_wg<int16_t>(plan, d_packed, d_out)
-             : plan->sample_kind == 2 ? run_wg<stereo16>(plan, d_packed, d_out) : run_wg<double>(plan, d_packed, d_out);
-    if (plan->big)
-        return plan->sample_kind == 0 ? run_big<int16_t>(plan, d_packed, d_out)
-             : plan->sample_kind == 2 ? run_big<stereo16>(plan, d_packed, d_out) : run_big<double>(plan, d_packed, d_out);
-    if (plan->n_tiles == 0) return PAA_OK;
-    ProfScope prof_scope;
-    { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-    if (plan->family < 0) return fail(PAA_ERR_UNSUPPORTED, "plan without a kernel family");
-    rc = kFamilies[plan->family].launch(plan, d_packed, d_out, plan->d_tiles, plan->n_tiles, cs());
-    if (rc) return fail(PAA_ERR_HIP, "launch of %s failed: %s", plan->kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
-    return PAA_OK;
+    return kFamilies[plan->fam.family].execute(plan, d_packed, d_out, plan->d_tiles, plan->n_tiles);
 }
 
 extern "C" int paa_plan_create(const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window,
@@ -769,7 +618,7 @@ extern "C" int paa_plan_destroy(paa_plan_t *plan) {
 
 extern "C" int64_t paa_plan_total_frames(const paa_plan_t *plan) { return plan ? plan->total_frames : 0; }
 extern "C" int64_t paa_plan_out_doubles(const paa_plan_t *plan) { return plan ? plan->out_doubles : 0; }
-extern "C" const char *paa_plan_kernel_name(const paa_plan_t *plan) { return plan ? plan->kernel_name.c_str() : ""; }
+extern "C" const char *paa_plan_kernel_name(const paa_plan_t *plan) { return plan ? plan->fam.kernel_name.c_str() : ""; }
 
 extern "C" int paa_plan_out_offsets(const paa_plan_t *plan, int64_t *out_offsets) {
     if (!plan || !out_offsets) return fail(PAA_ERR_ARG, "null plan / buffer");

@@ -37,6 +37,31 @@ def test_plans_dispatch_the_real_input_split(gpu_lib):
     assert kernel_name(24000, 24000, 12000, kind=1) == "st_wgs_6x4000"
 
 
+@pytest.mark.parametrize("fs,window,step,name", [
+    (17000, 16000, 8000, "st_wgr_20x20x20"),     # kernels_wgr.hpp: its WgrTab is the choice's table blob
+    (45000, 44100, 22050, "st_wgs_12x3675"),     # kernels_wgs.hpp
+    (16500, 9009, 4500, "st_wg_lds_fft"),        # kernels_wg.hpp: its digit-reversal permutation is the blob
+])
+def test_cached_choice_outlives_the_plan_that_built_it(gpu_lib, fs, window, step, name):
+    """The kernel choice of a big-window shape, its device tables included, is cached with the (fs, window) tables: a second plan of
+    the shape runs on what the first plan built and uploaded, after that plan is destroyed, and computes the same bits.  (Sampling
+    rates no other test uses: the first plan is the one that builds the choice.)"""
+    x = synth_clip(4400 + window, 7 * fs, fs)
+    offs = np.array([0, len(x)], dtype=np.int64)
+    d_in = _ffi.DeviceBuffer.from_host(x)
+    outs = []
+    for _ in range(2):
+        plan = _ffi.Plan(offs, fs, window, step, deltas=True)
+        assert plan.kernel_name == name
+        d_out = _ffi.DeviceBuffer(plan.out_doubles * 8)
+        plan.execute(d_in, d_out)
+        _ffi.sync()
+        outs.append(d_out.to_host(np.float64, plan.out_doubles))
+        plan.destroy()
+    assert outs[0].size == 68 * ((len(x) - window) // step + 1) and np.all(np.isfinite(outs[0]))
+    assert np.array_equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("kind,fs,window,step,seconds,deltas", [
     ("i16", 44100, 44100, 22050, 9.0, True),         # 17 frames x 3 tasks {1,2} {3,4} {5,packed}
     ("stereo", 44100, 44100, 30000, 7.3, False),     # interleaved stereo samples summed in the loads, a step that is no multiple of anything
