@@ -14,16 +14,21 @@ N = 1 (the headline): BASELINE config 2 -- one synthetic 1-hour 16 kHz mono clip
 N > 1 (default): BASELINE config 4, strong scaling -- 100 000 synthetic 10 s clips (64 distinct seeded clips, tiled)
   split into contiguous ranges with distributed.partition_by_frames, every rank extracts its range and the [34][399]
   slabs are gathered to rank 0 with RCCL (paa_comm_gather_f64, own stream, overlapping the next step) inside the timed
-  region; the same job is also timed without the gather and with the cheap gather (68 short-term rows stay in HBM, the
-  (136, 10) mid-term matrices of 1.0 s / 1.0 s go to rank 0: config 3's product on config 4's clips).  --workload cfg2
-  gives one 1-hour clip per rank instead (weak scaling).
+  region; with --full the same job is also timed without the gather and with the cheap gather (68 short-term rows stay
+  in HBM, the (136, 10) mid-term matrices of 1.0 s / 1.0 s go to rank 0: config 3's product on config 4's clips; --gather
+  mid makes that the headline and runs it in a plain run too).  --workload cfg2 gives one 1-hour clip per rank instead
+  (weak scaling).
 
-The line also carries (N = 1): the other BASELINE configurations kernel-resident (config.others: config 3 mid-term
-batch, a config-4 shard, config 5 features / spectrogram / chromagram starting from the interleaved stereo int16 samples,
-the shapes of the reference's other callers -- 40 ms windows, float64 / stereo input at 50 ms, 8 kHz and 48 kHz), the
-host-to-host rate of the drop-in API, a >= 2 s sustained loop, a full-matrix parity check against the plain-C oracle,
-the CPU ports on one core and on all host cores of THIS box, and the unmodified reference's own timings (measured in the
-build container, profiles/reference_cpu_r03.json: /root/reference does not exist on the GPU box).
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs if asked
+and prints the line (roofline.kernel_avg_ms comes from event pairs inside the timed steps, the traffic and FP64 figures
+are quoted from committed profiles).  Everything else runs with --full, which also writes the full record to a side file.
+With --full the line also carries (N = 1): the other BASELINE configurations kernel-resident (config.others: config 3
+mid-term batch, a config-4 shard, config 5 features / spectrogram / chromagram starting from the interleaved stereo int16
+samples, the shapes of the reference's other callers -- 40 ms windows, float64 / stereo input at 50 ms, 8 kHz and
+48 kHz), the host-to-host rate of the drop-in API, a >= 2 s sustained loop, a full-matrix parity check against the
+plain-C oracle, the CPU ports on one core and on all host cores of THIS box, and the unmodified reference's own timings
+(measured where the reference is installed, profiles/reference_cpu_r03.json: the benchmark host need not have it);
+(N > 1) the parity check and the same job timed without the gather and with the mid-term gather.
 
 The control plane for N > 1 (rendezvous, barrier, max over ranks) is pyaudioanalysis_amd/_rendezvous.py (TCP sockets,
 standard library); the compute path is ctypes -> libpaa_hip.so -> RCCL.  Prints ONE JSON line on rank 0.  Nothing here
@@ -131,6 +136,45 @@ def shape_bytes_per_frame(name, rows):
     """SURVEY 8d's accounting: the samples of one step in once, the rows of one frame out once."""
     fs, W, S, seconds, clips, kind, mode, deltas = SHAPES[name]
     return SAMPLE_BYTES[kind] * S + 8 * rows
+
+
+def synth_clips(seeds, n, fs=FS, chunk=1 << 18, workers=None):
+    """[synth.synth_clip(seed, n, fs) for seed in seeds] -- the same int16 samples, made on a thread pool: every clip's
+    random draws are taken in synth_clip's order, then its element-wise arithmetic (the same operations in the same order)
+    runs in chunks of `chunk` samples, during which NumPy releases the GIL.  synth_clip takes several seconds of one core
+    per 1-hour clip: serially, the three clips of cfg2 were most of a plain run's set-up."""
+    from concurrent.futures import ThreadPoolExecutor
+    import cpu_bench
+    span = int(0.5 * fs)
+
+    def draws(seed):
+        rng = np.random.default_rng(seed)
+        f = rng.uniform(80.0, 0.45 * fs, 5)
+        a = rng.uniform(0.2, 1.0, 5)
+        ph = rng.uniform(0.0, 2.0 * np.pi, 5)
+        noise = rng.standard_normal(n)
+        s0 = int(rng.integers(0, n - span)) if n > span else None
+        return f, a, ph, noise, s0
+
+    def fill(c, lo):
+        f, a, ph, noise, s0 = params[c]
+        hi = min(n, lo + chunk)
+        t = np.arange(lo, hi, dtype=np.float64) / fs
+        env = 0.5 * (1.0 + np.sin(2.0 * np.pi * 0.25 * t))
+        x = np.zeros(hi - lo)
+        for j in range(5):
+            x += a[j] * np.sin(2.0 * np.pi * f[j] * t + ph[j])
+        x = 6000.0 * x + 1500.0 * noise[lo:hi]
+        x *= env
+        if s0 is not None and s0 < hi and s0 + span > lo:
+            x[max(s0, lo) - lo:min(s0 + span, hi) - lo] = 0.0
+        outs[c][lo:hi] = np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+    outs = [np.empty(n, dtype=np.int16) for _ in seeds]
+    with ThreadPoolExecutor(workers or min(16, cpu_bench.usable_cores())) as pool:
+        params = list(pool.map(draws, seeds))
+        list(pool.map(lambda task: fill(*task), [(c, lo) for c in range(len(seeds)) for lo in range(0, n, chunk)]))
+    return outs
 
 
 def replicate_on_device(ffi, pool_host, n_units):
@@ -535,13 +579,17 @@ def main():
                          "link-bound, see expected_speedup_short_gather); mid: 68 rows are computed and kept, the (136, 10) "
                          "mid-term matrices travel (the near-linear configuration, DESIGN section 6)")
     ap.add_argument("--comm-timeout", type=int, default=180, help="N>1: seconds allowed for the RCCL rendezvous")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity check, the CPU baselines, config.others, host_to_host, the "
+                         "sustained loop, (N>1) the no-gather and mid-gather legs, and the full record in a side file; "
+                         "the --no-* / --check options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--event-every", type=int, default=4,
                     help="HIP-event pair around every n-th feature-kernel launch of the timed region (roofline.kernel_avg_ms)")
     ap.add_argument("--no-extras", action="store_true", help="skip config.others, host_to_host and the sustained loop")
     ap.add_argument("--cpu-frames", type=int, default=60000, help="frames of the clip prefix timed on one CPU core")
     ap.add_argument("--sustain-seconds", type=float, default=2.5)
-    ap.add_argument("--check", type=int, default=1, help="verify the clip against the oracle after timing")
+    ap.add_argument("--check", type=int, default=1, help="--full: verify the clip against the oracle after timing")
     ap.add_argument("--prewarm-seconds", type=float, default=0.3,
                     help="untimed device work before the --warmup steps (the engine clock of a fresh box ramps over the "
                          "first ~0.2 s of load; reported in the line)")
@@ -563,6 +611,9 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: the line would claim GPUs that did not run" % (args.gpus, world))
     workload = args.workload or ("cfg2" if world == 1 else "cfg4")
+    if not args.full:                   # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extras = True
+        args.check = 0
 
     group = None                        # control plane: TCP sockets on the launcher's environment (no torch)
     if world > 1:
@@ -584,7 +635,6 @@ def main():
 
     from pyaudioanalysis_amd import _ffi
     from pyaudioanalysis_amd import distributed as D
-    from synth import synth_clip
     lib = _ffi.lib()
     if _ffi.device_count() < 1:
         raise SystemExit("bench.py needs a HIP device (no CPU fallback)")
@@ -598,12 +648,10 @@ def main():
     if workload == "cfg2":
         n = int(args.seconds * FS)
         seeds = [2 + rank, 1002 + rank, 2002 + rank]          # three distinct clips: inputs rotate through > 256 MiB
-        d_inputs = []
-        for sd in seeds:
-            x = synth_clip(sd, n, FS)
-            if host_clip is None:
-                host_clip = x
-            d_inputs.append(_ffi.DeviceBuffer.from_host(x))
+        clips = synth_clips(seeds, n)
+        host_clip = clips[0]
+        d_inputs = [_ffi.DeviceBuffer.from_host(x) for x in clips]
+        del clips
         offsets = np.array([0, n], dtype=np.int64)
         desc = "cfg2: 1 clip x %d s, 16 kHz mono int16, 800/400, %d rows; 3 distinct clips rotate (seeds %s)" % (
             args.seconds, 68 if args.deltas else 34, seeds)
@@ -614,7 +662,7 @@ def main():
         frames_all = np.full(args.clips, (n - WINDOW) // STEP + 1, dtype=np.int64)
         a, b = D.partition_by_frames(frames_all, world)[rank]
         my_clips = b - a
-        pool = np.stack([synth_clip(40000 + i, n, FS) for i in range(64)])
+        pool = np.stack(synth_clips(range(40000, 40064), n))
         # clip k of the job is pool[k % 64]: rotate the pool so that this rank's first clip lines up
         pool = np.roll(pool, -(a % 64), axis=0)
         host_clip = pool[0].copy()
@@ -763,10 +811,11 @@ def main():
         dumped = dump_outputs(args.dump_outputs, lambda off, cnt: d_res.to_host(np.float64, cnt, 8 * off),
                               rows, clip_frames, slab_offsets)
 
-    # N > 1: also time the same steps without the gather, and the cheap gather (reported beside the headline value)
+    # N > 1, --full: also time the same steps without the gather, and the cheap gather (reported beside the headline value;
+    # --gather mid makes the cheap gather the headline, so that leg runs in a plain run too)
     value_no_gather = None
     mid_gather = None
-    if gather:
+    if gather and args.full:
         saved, gather = gather, False
         barrier()
         t1 = time.perf_counter()
@@ -777,6 +826,7 @@ def main():
         group.barrier()
         value_no_gather = total_frames * args.steps / max_over_ranks(el2)
         gather = saved
+    if gather and (args.full or args.gather == "mid"):
         # the cheap gather: 68 short-term rows stay in HBM, the (136, M) mid-term matrices (1.0 s / 1.0 s) travel
         plan68 = _ffi.Plan(offsets, FS, WINDOW, STEP, deltas=True, sample_kind=0)
         d_st68 = _ffi.DeviceBuffer(plan68.out_doubles * 8)
@@ -1034,7 +1084,7 @@ def main():
                 result["config"][key + "_hbm_frac"] = configs[key][2]
         result["configs_columns"] = ["frames_per_s", "ms_per_step", "hbm_frac", "kernel"]
         result["configs"] = configs
-        print(format_line(result, write_side_record(result, world)))
+        print(format_line(result, write_side_record(result, world) if args.full else None))
         sys.stdout.flush()
     if comm is not None:
         comm.close()

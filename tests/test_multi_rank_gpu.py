@@ -164,7 +164,7 @@ def test_bench_n2_socket_control_plane_without_rccl(gpu_lib, tmp_path):
                    MASTER_PORT=str(port))
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-gather", "--clips", "2000", "--steps", "5",
-             "--warmup", "2", "--prewarm-seconds", "0", "--no-cpu-baseline"],
+             "--warmup", "2", "--prewarm-seconds", "0", "--no-cpu-baseline", "--full"],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT))
     outs = []
     for p in procs:
@@ -193,7 +193,7 @@ def _run_bare_bench(extra, timeout=420):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--clips", "2000", "--steps", "5", "--warmup", "2",
-           "--prewarm-seconds", "0", "--no-cpu-baseline"] + extra
+           "--prewarm-seconds", "0", "--no-cpu-baseline", "--full"] + extra
     try:
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT, timeout=timeout)
     except subprocess.TimeoutExpired:
