@@ -104,7 +104,8 @@ int paa_mid_features_stereo_i16(const int16_t *interleaved, int64_t n, double fs
                                 int64_t mid_ratio, int64_t mid_step_ratio, double *mid_out, double *st_out);
 
 /* ---- MidTermFeatures.mid_feature_extraction (MidTermFeatures.py:87-127) ----------------- */
-/* mid_ratio / mid_step_ratio are computed by the caller with Python round() (:100-102).
+/* mid_ratio / mid_step_ratio are computed by the caller with Python round() (:100-102).  Any mid_ratio is accepted:
+ * window m is row[m*step : min(m*step + mid_ratio, T)] with Python's slice rules (a negative end counts from the row's end).
  * st_out: [68][T] (deltas always on, :93-95), may be NULL; mid_out: [136][M].               */
 int paa_mid_features_i16(const int16_t *signal, int64_t n, double fs, int window, int step,
                          int64_t mid_ratio, int64_t mid_step_ratio, double *mid_out, double *st_out);
@@ -172,9 +173,13 @@ int64_t paa_plan_mid_doubles(const paa_plan_t *plan, int64_t mid_step_ratio);
 int paa_plan_mid_execute(paa_plan_t *plan, const double *d_st, int64_t mid_ratio,
                          int64_t mid_step_ratio, double *d_mid);
 /* MidTermFeatures.beat_extraction (MidTermFeatures.py:18-84) for every clip of an executed plan:
- * d_beat receives [n_clips][2] = (bpm, confidence); window_size = short-term step in seconds          */
+ * d_beat receives [n_clips][2] = (bpm, confidence); window_size = short-term step in seconds.
+ * The histogram has round(2 / window_size) bins.  No bins (window_size >= 4 s) -> PAA_ERR_ARG (the reference raises
+ * ValueError).  One workgroup holds every row's histogram in LDS next to its frame tile:
+ * 18 * 129 * 8 + 18 * 4 * bins bytes, at most the 160 KB of a gfx950 workgroup, i.e. at most 2 017 bins (a step longer
+ * than about 0.9913 ms).  More bins -> PAA_ERR_UNSUPPORTED; this limit is the library's own, the reference has none. */
 int paa_plan_beat_execute(paa_plan_t *plan, const double *d_st, double window_size, double *d_beat);
-/* the same for ONE short-term matrix in host memory (the reference's own signature, MidTermFeatures.py:18): feats is
+/* the same (same limits) for ONE short-term matrix in host memory (the reference's own signature, MidTermFeatures.py:18): feats is
  * [n_rows][n_frames] feature-major (n_rows >= 19: rows 0..18 are read, :30-31); bpm_ratio receives (bpm, confidence) */
 int paa_beat_extraction_f64(const double *feats, int n_rows, int64_t n_frames, double window_size, double *bpm_ratio);
 /* name of the feature kernel the plan dispatches ("st_fast_800", "st_generic", ...)          */

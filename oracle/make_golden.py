@@ -553,5 +553,38 @@ def live_goldens():
     print("live_reference_silence_glue.npz", len(out))
 
 
+def live_mid_beat_goldens():
+    """The reference's mid-term loop and beat_extraction on the designed matrices of tests/test_oracle_mid_beat_live.py (its
+    case lists are the single source of the cases).  Mid-term cases are stored as "<case key>__mid"; the beat results of one
+    matrix as arrays over BEAT_WINDOWS ("beat_<T>__bpm", "__ratio", and "__error": the type name of what the reference raised,
+    "" where it returned); the SHA-256 of every input matrix once, under matrix_key (the test re-creates the matrix)."""
+    ref_st, ref_mt, _ = load_reference.load()
+    t = _test_module("test_oracle_mid_beat_live")
+    out = {"kind": np.array("live_mid_beat")}
+    for T, ratio, step in t.mid_cases():
+        x = t.mid_matrix(T)
+        out[t.matrix_key("mid", T)] = np.array(t.sha(x))
+        out[t.mid_case_key(T, ratio, step) + "__mid"] = t.reference_mid(ref_st, ref_mt, x, ratio, step, 1, 1)
+    for args in t.RATIO_ARGS:
+        x = t.ratio_matrix()
+        out[t.matrix_key("ratio", x.shape[1])] = np.array(t.sha(x))
+        out[t.ratio_case_key(args) + "__mid"] = t.reference_mid(ref_st, ref_mt, x, *args)
+    for T in t.BEAT_FRAMES:
+        x = t.beat_matrix(T)
+        out[t.matrix_key("beat", T)] = np.array(t.sha(x))
+        bpm, ratio, err = [], [], []
+        for window in t.BEAT_WINDOWS:
+            try:
+                b, r = t.reference_beat(ref_mt, x, window)
+                bpm.append(b), ratio.append(r), err.append("")
+            except Exception as exc:
+                bpm.append(np.nan), ratio.append(np.nan), err.append(type(exc).__name__)
+        out["beat_%d__bpm" % T], out["beat_%d__ratio" % T] = np.array(bpm), np.array(ratio)
+        out["beat_%d__error" % T] = np.array(err)
+    np.savez_compressed(os.path.join(OUT, "live_reference_mid_beat.npz"), **out)
+    print("live_reference_mid_beat.npz", len(out))
+
+
 if __name__ == "__main__" and "--live" in sys.argv:
     live_goldens()
+    live_mid_beat_goldens()

@@ -67,3 +67,44 @@ def synth_song(seed, seconds, fs=16000, section=4.0):
             x[sl] += a[j] * np.sin(2.0 * np.pi * f[j] * t[sl])
     x = 5000.0 * x + 800.0 * rng.standard_normal(n)
     return np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+
+DESIGNED_KINDS = ("constant", "ramp", "alternating", "offset", "noise", "plateau", "spikes", "periodic", "nonfinite")
+
+
+def designed_matrix(seed, n_rows, n_frames, nonfinite=True):
+    """A seeded short-term-like matrix [n_rows][n_frames] of hand-shaped rows for the mid-term and beat kernels, row r of
+    kind DESIGNED_KINDS[r % 9]: constants, ramps, alternating +-1, 1e6 + 1e-6 noise (large offset, tiny spread), noise of a
+    random scale, integer plateaus (exact ties), isolated spikes with gaps from 1 to 90 frames, a noisy periodic row, and
+    noise with one NaN, one +inf and one -inf (plain noise when nonfinite is False)."""
+    rng = np.random.default_rng(seed)
+    T = int(n_frames)
+    t = np.arange(T, dtype=np.float64)
+    out = np.empty((n_rows, T))
+    for r in range(n_rows):
+        kind = DESIGNED_KINDS[r % len(DESIGNED_KINDS)]
+        if kind == "constant":
+            row = np.full(T, rng.normal(0.0, 3.0))
+        elif kind == "ramp":
+            row = rng.normal(0.0, 1.0) + rng.uniform(-0.5, 0.5) * t
+        elif kind == "alternating":
+            row = np.where(t % 2 == 0, 1.0, -1.0)
+        elif kind == "offset":
+            row = 1e6 + 1e-6 * rng.standard_normal(T)
+        elif kind == "noise":
+            row = rng.standard_normal(T) * 10.0 ** rng.uniform(-3.0, 3.0)
+        elif kind == "plateau":
+            row = np.repeat(rng.integers(0, 3, T // 3 + 1), 3)[:T].astype(np.float64)
+        elif kind == "spikes":
+            row = np.zeros(T)
+            pos = np.cumsum(rng.choice([1, 2, 7, 30, 45, 61, 90], T))
+            pos = pos[pos < T]
+            row[pos] = 1.0 + rng.uniform(0.0, 0.1, pos.shape[0])
+        elif kind == "periodic":
+            row = np.sin(2.0 * np.pi * t / rng.integers(3, 12)) + 0.05 * rng.standard_normal(T)
+        else:
+            row = rng.standard_normal(T)
+            if nonfinite:
+                row[rng.integers(0, T, 3)] = [np.nan, np.inf, -np.inf]
+        out[r] = row
+    return out

@@ -117,6 +117,11 @@ def beat_extraction(short_features, window_size, plot=False):
     batched directory walkers run on matrices that never leave HBM.  `plot` is accepted and ignored (the reference opens
     a matplotlib window with the histogram).
 
+    The histogram has int(round(2.0 / window_size)) bins.  With none (window_size >= 4 s) this raises ValueError, as the
+    reference's argmax of the empty histogram does.  Unlike the reference, the kernel keeps every row's histogram in the
+    160 KB of LDS of one workgroup: at most 2 017 bins, i.e. window_size above about 0.9913 ms.  Finer steps raise
+    NotImplementedError.
+
     ARGUMENTS: short_features (n_feats x numOfShortTermWindows), window_size = short-term step in seconds
     RETURNS:   bpm (beats per minute), ratio (confidence)
     """

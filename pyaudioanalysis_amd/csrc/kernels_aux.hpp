@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void clip_params_kernel(const ClipDev *__restri
 }
 
 // ---- mid-term statistics (MidTermFeatures.py:110-126): mean and population std of every
-// short-term row over windows [m*step, min(m*step+ratio, T)), then nan_to_num.
+// short-term row over windows [m*step, min(m*step+ratio, T)) (Python slice semantics), then nan_to_num.
 __device__ __forceinline__ double nan_to_num(double v) {
     if (isnan(v)) return 0.0;
     if (isinf(v)) return v > 0 ? DBL_MAX : -DBL_MAX;
@@ -210,13 +210,17 @@ __global__ __launch_bounds__(256) void mid_stats_kernel(const ClipDev *__restric
     const long long row = live ? idx / M : 0, m = live ? idx % M : 0;
     const double *x = st + cd.out_off + row * T;
     const long long b = m * step;
+    // the reference slices row[b:end], end = min(b + ratio, T) (:117-121), with Python's slice rules: a negative end counts
+    // from the end of the row (ratio < 0 still gives non-empty first windows), end <= b is an empty window (NaN -> 0)
     long long e = b + ratio;
     if (e > T) e = T;
+    if (e < 0) e += T;
+    if (e < b) e = b;
     if (!live) e = b;
     double s = 0.0, v = 0.0;
     const double n = (double)(e - b);
     double mean;
-    if (ratio <= 64) {
+    if (ratio >= 0 && ratio <= 64) {
         // the usual shapes (40 or 20 frames per mid-term window): the lane's <= 4 values are loaded once, all at once, and
         // serve both passes from registers (same operations in the same order as the general loop below)
         double xv[4];

@@ -326,7 +326,9 @@ extern "C" int paa_beat_extraction_f64(const double *feats, int n_rows, int64_t 
     if (!(window_size > 0)) return fail(PAA_ERR_ARG, "window_size must be positive");
     { const int rc0 = ensure_init(); if (rc0) return rc0; }
     const int max_beat = (int)nearbyint(2.0 / window_size);          // int(round(2.0 / window_size)), :33
-    if (max_beat < 1 || max_beat > 4096) return fail(PAA_ERR_UNSUPPORTED, "beat histogram of %d bins", max_beat);
+    // no bins (window_size >= 4 s): the reference's np.argmax of the empty histogram raises ValueError (:68)
+    if (max_beat < 1) return fail(PAA_ERR_ARG, "attempt to get argmax of an empty sequence (beat histogram of %d bins)", max_beat);
+    if (max_beat > 4096) return fail(PAA_ERR_UNSUPPORTED, "beat histogram of %d bins", max_beat);
     const size_t lds = (size_t)kBeatRows * (kBeatTile + 1) * 8 + (size_t)kBeatRows * max_beat * 4;
     if (lds > 160 * 1024)
         return fail(PAA_ERR_UNSUPPORTED, "beat histogram of %d bins needs %zu bytes of LDS (160 KB per workgroup)", max_beat, lds);

@@ -676,7 +676,9 @@ extern "C" int paa_plan_beat_execute(paa_plan_t *plan, const double *d_st, doubl
     if (!(window_size > 0)) return fail(PAA_ERR_ARG, "window_size must be positive");
     { const int rc_init = ensure_init(); if (rc_init) return rc_init; }
     const int max_beat = (int)nearbyint(2.0 / window_size);          // int(round(2.0 / window_size)), :33
-    if (max_beat < 1 || max_beat > 4096) return fail(PAA_ERR_UNSUPPORTED, "beat histogram of %d bins", max_beat);
+    // no bins (window_size >= 4 s): the reference's np.argmax of the empty histogram raises ValueError (:68)
+    if (max_beat < 1) return fail(PAA_ERR_ARG, "attempt to get argmax of an empty sequence (beat histogram of %d bins)", max_beat);
+    if (max_beat > 4096) return fail(PAA_ERR_UNSUPPORTED, "beat histogram of %d bins", max_beat);
     std::lock_guard<std::mutex> lk(g_mu);
     { const int rc_w = comm_wait_buffer_free(d_beat); if (rc_w) return rc_w; }
     const size_t lds = (size_t)kBeatRows * (kBeatTile + 1) * 8 + (size_t)kBeatRows * max_beat * 4;

@@ -19,8 +19,14 @@ def _reference_segmentation():
     return load_reference.load_segmentation()
 
 
+def saturated_pairs(m, dec):
+    """Number of (window, pair) Platt probabilities outside [1e-7, 1 - 1e-7], i.e. clamped by libsvm."""
+    r = svc_libsvm.sigmoid_predict(dec, m["prob_a"], m["prob_b"])
+    return int(np.sum((r < 1e-7) | (r > 1 - 1e-7)))
+
+
 @pytest.mark.parametrize("kernel", ["rbf", "linear"])
-@pytest.mark.parametrize("k", list(range(2, 11)))
+@pytest.mark.parametrize("k", list(range(2, 17)))
 def test_restatement_matches_sklearn(k, kernel):
     sklearn_svm = pytest.importorskip("sklearn.svm")
     rng = np.random.default_rng(100 * k + len(kernel))
@@ -36,6 +42,32 @@ def test_restatement_matches_sklearn(k, kernel):
     assert np.max(np.abs(proba - clf.predict_proba(T))) <= 1e-12
     if k == 2:              # scikit-learn's public decision_function is -(libsvm's) for two classes
         assert np.allclose(clf.decision_function(T), -dec[:, 0], rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("kernel", ["rbf", "linear"])
+@pytest.mark.parametrize("k", list(range(2, 17)))
+def test_restatement_matches_sklearn_on_separated_classes(k, kernel):
+    """Clusters far apart; windows at the centres and far outside every cluster.  Linear kernel: the far windows' decision
+    values are large and their Platt probabilities are clamped to [1e-7, 1 - 1e-7].  RBF: a trained model's Platt fit keeps
+    |A dec + B| small (the clamp is reached only by the seeded models of tests/test_svc_gpu.py), but at the far windows
+    every kernel value underflows to 0, so the decision values are exactly -rho."""
+    sklearn_svm = pytest.importorskip("sklearn.svm")
+    rng = np.random.default_rng(7000 + 100 * k + len(kernel))
+    n_dims = int(rng.integers(3, 20))
+    centres = rng.standard_normal((k, n_dims)) * 40.0
+    y = np.repeat(np.arange(k), 20)
+    X = centres[y] + 0.5 * rng.standard_normal((y.shape[0], n_dims))
+    clf = sklearn_svm.SVC(kernel=kernel, probability=True, gamma="scale", random_state=0).fit(X, y)
+    T = np.concatenate([centres[rng.integers(0, k, 40)] + 0.5 * rng.standard_normal((40, n_dims)),
+                        1e3 * rng.standard_normal((8, n_dims))])
+    m = svc_libsvm.model_arrays(clf)
+    idx, proba, dec = svc_libsvm.predict(m, T)
+    if kernel == "linear":
+        assert saturated_pairs(m, dec[40:]) > 0
+    else:
+        assert np.array_equal(dec[40:], np.broadcast_to(-m["rho"], dec[40:].shape))
+    assert np.array_equal(clf.classes_[idx], clf.predict(T))
+    assert np.max(np.abs(proba - clf.predict_proba(T))) <= 1e-12
 
 
 def test_svc_goldens_are_plain_arrays():

@@ -136,8 +136,9 @@ def test_file_classification_batch_equals_single_calls(gpu_lib):
         assert cid == ids[i] and np.array_equal(p, proba[i]), i
 
 
-def _synthetic(n_support, n_dims, seed, kernel="rbf"):
+def _synthetic(n_support, n_dims, seed, kernel="rbf", platt_scale=1.0):
     m = svc_libsvm.synthetic_model(n_support, n_dims, seed, kernel)
+    m["prob_a"] = m["prob_a"] * platt_scale
     model = audioTrainTest.SvcArrays(m["support_vectors"], m["n_support"], m["dual_coef"], -m["rho"], m["prob_a"],
                                      m["prob_b"], m["gamma"], kernel, np.arange(len(n_support), dtype=np.float64))
     return m, model
@@ -151,13 +152,21 @@ SYNTHETIC = {
     "k16_d256": (tuple(range(5, 21)), 256, "rbf"),
     "k5_empty_class_linear": ((40, 0, 33, 17, 60), 71, "linear"),
     "k2_d1": ((9, 14), 1, "rbf"),
+    # layouts training does not produce: classes ending exactly on the 16-vector LDS tiles, empty first and last classes,
+    # fewer support vectors than one tile, Platt parameters that saturate every pair (r_ij clamped to 1e-7 / 1 - 1e-7)
+    "k4_ends_on_tiles": ((16, 16, 5, 11), 9, "rbf"),
+    "k13_ends_on_tiles_linear": ((16, 16, 3, 13, 16, 16, 16, 2, 14, 16, 16, 16, 16), 7, "linear"),
+    "k7_empty_first_and_last": ((0, 12, 16, 4, 20, 9, 0), 255, "rbf"),
+    "k3_five_vectors": ((2, 1, 2), 7, "rbf"),
+    "k14_saturated": (tuple(range(3, 17)), 136, "rbf", 1e4),
+    "k15_saturated_linear": (tuple(range(2, 17)), 9, "linear", 1e4),
 }
 
 
 @pytest.mark.parametrize("name", sorted(SYNTHETIC))
 def test_svc_kernel_matches_restatement_on_model_shapes(gpu_lib, name):
-    n_support, n_dims, kernel = SYNTHETIC[name]
-    m, model = _synthetic(n_support, n_dims, 7, kernel)
+    n_support, n_dims, kernel, *platt = SYNTHETIC[name]
+    m, model = _synthetic(n_support, n_dims, 7, kernel, *platt)
     rng = np.random.default_rng(8)
     n_vec = 203                                           # not a multiple of the 32 windows of a workgroup
     mean, std = rng.normal(0, 2, n_dims), rng.uniform(0.5, 3.0, n_dims)
@@ -169,6 +178,49 @@ def test_svc_kernel_matches_restatement_on_model_shapes(gpu_lib, name):
     err = float(np.max(np.abs(proba - want)))
     print("%s: %d classes, %d support vectors, max |proba - restatement| = %.3g"
           % (name, len(n_support), sum(n_support), err))
+    assert err <= PROBA_TOL
+    if platt:
+        r = svc_libsvm.sigmoid_predict(dec, m["prob_a"], m["prob_b"])
+        assert np.mean((r < 1e-7) | (r > 1 - 1e-7)) > 0.99
+
+
+# ---- trained models at every class count the kernels are instantiated for ---------------------------------------------------
+TRAINED_DIMS = (1, 7, 9, 136, 255, 256)
+TRAINED_NVEC = (1, 33, 65, 3001)
+
+
+def _trained_case(k, kernel):
+    """A seeded scikit-learn SVC(probability=True) on k clusters, and windows near the centres, far outside every cluster
+    (RBF values of exactly 0) and from clusters far apart (linear: clamped probabilities), as a [n_dims][n_vec] matrix."""
+    sklearn_svm = pytest.importorskip("sklearn.svm")
+    i = 2 * k + (kernel == "linear")
+    n_dims, n_vec = TRAINED_DIMS[i % len(TRAINED_DIMS)], TRAINED_NVEC[(i // 2) % len(TRAINED_NVEC)]
+    rng = np.random.default_rng(600 + i)
+    centres = rng.standard_normal((k, n_dims)) * 2.0
+    y = np.repeat(np.arange(k), 12)
+    X = centres[y] + rng.standard_normal((y.shape[0], n_dims))
+    clf = sklearn_svm.SVC(kernel=kernel, probability=True, gamma="scale", random_state=0).fit(X, y)
+    n_near = max(1, n_vec - 2 * (n_vec // 3))
+    W = np.concatenate([centres[rng.integers(0, k, n_near)] + 0.7 * rng.standard_normal((n_near, n_dims)),
+                        1e3 * rng.standard_normal((n_vec // 3, n_dims)),
+                        40.0 * centres[rng.integers(0, k, n_vec // 3)] + rng.standard_normal((n_vec // 3, n_dims))])[:n_vec]
+    mean, std = rng.normal(0, 0.5, n_dims), rng.uniform(0.5, 2.0, n_dims)
+    return clf, W.T * std[:, None] + mean[:, None], mean, std, W
+
+
+@pytest.mark.parametrize("kernel", ["rbf", "linear"])
+@pytest.mark.parametrize("k", list(range(2, 17)))
+def test_svc_kernel_matches_sklearn_at_every_class_count(gpu_lib, k, kernel):
+    """svc_proba_kernel<K> for every K = 2..16 (blocks of 64, 32 and 16 threads) against scikit-learn's own predict /
+    predict_proba; n_dims 1..256 (partial groups of 8 lanes), n_vec 1..3 001 (partial blocks of both kernels)."""
+    clf, feats, mean, std, W = _trained_case(k, kernel)
+    labels, proba = audioTrainTest.svm_predict(clf, feats, mean, std)
+    X = (feats.T - mean) / std
+    want = clf.predict_proba(X)
+    _, _, dec = svc_libsvm.predict(svc_libsvm.model_arrays(clf), X)
+    _labels_agree(labels, clf.predict(X), dec, "K=%d %s" % (k, kernel))
+    err = float(np.max(np.abs(proba - want)))
+    print("SVC K=%d %s n_dims=%d n_vec=%d: max |proba - sklearn| = %.3g" % (k, kernel, X.shape[1], X.shape[0], err))
     assert err <= PROBA_TOL
 
 
