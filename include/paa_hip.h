@@ -249,6 +249,31 @@ int paa_svc_predict_f64(const void *handle, const double *feats, int n_dims, int
 int paa_svc_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                             const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba);
 
+/* ---- audioTrainTest.Knn.classify for the kNN models (audioTrainTest.py:33-49) -------------------------------------------
+ * k-nearest-neighbour classification of many feature vectors at once: what mid_term_file_classification
+ * (audioSegmentation.py:583-594) and file_classification (audioTrainTest.py:1091-1095) ask for once per vector with a
+ * knn_* model.  The model: train [n_train][n_dims], labels [n_train] (the class INDEX of every row; a value outside
+ * 0..n_classes-1 votes for no class), n_classes = the number of distinct labels, k = `neighbors`.  1 <= k <= 32,
+ * 1 <= n_classes <= 64, 1 <= n_dims <= 256: anything else returns PAA_ERR_ARG.  Uploaded once (paa_knn_create), on the
+ * device until paa_knn_destroy.
+ * feats is feature-major [n_dims][ld], vector v in column v, standardised on load, (x - mean) / std.  Neighbours are ranked
+ * by the squared Euclidean distance sum_d (t_d - x_d)^2, ties by the training index (ascending (d^2, index)).
+ * label_index [n_vec] receives the first class with the most votes, proba [n_vec][n_classes] P[c] = votes(c) / k (as in
+ * the reference, also when n_train < k), neighbors [n_vec][k] (may be NULL) the neighbour indices in that order, -1 where
+ * n_train < k.  A vector with NaN distances (a NaN query) gets no neighbours: P = 0, label 0.                          */
+int paa_knn_create(const double *train, const int32_t *labels, int n_train, int n_dims, int n_classes, int k,
+                   void **out_handle);
+int paa_knn_destroy(void *handle);
+int paa_knn_num_classes(const void *handle);
+/* host buffers in and out (synchronous) */
+int paa_knn_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, const double *mean,
+                        const double *std, int32_t *label_index, double *proba, int32_t *neighbors);
+/* device buffers in and out (the resident mid-term matrix of a plan, paa_plan_mid_execute), asynchronous on the library
+ * stream                                                                                                              */
+int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
+                            const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
+                            int32_t *d_neighbors);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

@@ -3,15 +3,18 @@
     load_model(model_name, is_regression=False)                  audioTrainTest.py:523-553
     classifier_wrapper(classifier, classifier_type, test_sample) audioTrainTest.py:52-94
     file_classification(input_file, model_name, model_type)      audioTrainTest.py:1052-1096
-    file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one SVC launch
+    file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one SVC / kNN launch
+    Knn(features, labels, neighbors), load_model_knn(name)       audioTrainTest.py:33-49, :492-520
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
 pairwise coupling for every vector in one launch.  Only the fitted model's arrays are read (support_vectors_,
 n_support_, _dual_coef_, _intercept_, probA_, probB_, _gamma, kernel, classes_), so a model given as those arrays
-(SvcArrays) works without scikit-learn.  Every other classifier type is called exactly as the reference calls it.
-Unpickling a model needs scikit-learn exactly where the reference needs it (load_model).  Training stays with
-scikit-learn.
+(SvcArrays) works without scikit-learn.  For "knn" (the shipped knn_* models: pickled NumPy arrays, no scikit-learn)
+Knn.classify runs on the GPU (kernels_knn.hpp through paa_knn_*): distances to every training row, the k nearest in
+ascending (squared distance, training index) and the votes, for every vector in one launch.  Every other classifier
+type is called exactly as the reference calls it.  Unpickling an SVM model needs scikit-learn exactly where the
+reference needs it (load_model).  Training stays with scikit-learn.
 """
 import ctypes as C
 import os
@@ -136,6 +139,159 @@ def svm_predict(classifier, feats, mean, std):
     return m.classes[idx], proba
 
 
+class KnnModel:
+    """A kNN model uploaded to the device once (paa_knn_create); freed with the object.  Reads the classifier's features,
+    labels and neighbors, as the reference's Knn.classify does: n_classes = the number of distinct labels, and a label
+    that is not one of the integers 0..n_classes-1 is counted for no class."""
+
+    def __init__(self, classifier):
+        train = np.ascontiguousarray(classifier.features, dtype=np.float64)
+        raw = np.asarray(classifier.labels).reshape(-1)
+        if train.ndim != 2 or raw.shape[0] != train.shape[0]:
+            raise ValueError("kNN model: features %s and %d labels" % (train.shape, raw.shape[0]))
+        self.n_classes = int(np.unique(raw).shape[0])
+        labels = np.full(raw.shape[0], -1, dtype=np.int32)
+        if raw.dtype.kind in "biuf":
+            v = raw.astype(np.float64)
+            ok = (v == np.floor(v)) & (v >= 0) & (v < self.n_classes)
+            labels[ok] = v[ok].astype(np.int32)
+        self.k = int(classifier.neighbors)
+        self.n_dims = train.shape[1]
+        lib = _ffi.lib()
+        handle = C.c_void_p()
+        _ffi.check(lib.paa_knn_create(_ffi.as_f64p(train), labels.ctypes.data_as(_ffi.c_i32p), train.shape[0], self.n_dims,
+                                      self.n_classes, self.k, C.byref(handle)))
+        self.handle = handle
+        self._finalizer = weakref.finalize(self, lib.paa_knn_destroy, handle)
+
+    def predict(self, feats, mean, std, neighbors=False):
+        """feats [n_dims][n_vec] (feature-major) -> (class indices [n_vec], P [n_vec][n_classes]) of (feats[:, v] - mean) /
+        std, plus the neighbour indices [n_vec][k] in ascending (squared distance, index) when neighbors is true."""
+        F = np.ascontiguousarray(feats, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
+            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
+        mean, std = _stats(mean, std, self.n_dims)
+        n = F.shape[1]
+        idx = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, self.n_classes), dtype=np.float64)
+        nb = np.empty((n, self.k), dtype=np.int32) if neighbors else None
+        _ffi.check(_ffi.lib().paa_knn_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
+                                                  _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba),
+                                                  nb.ctypes.data_as(_ffi.c_i32p) if neighbors else None))
+        if neighbors:
+            return idx.astype(np.int64), proba, nb
+        return idx.astype(np.int64), proba
+
+    def predict_device(self, d_feats, ld, n_vec, mean, std):
+        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
+        mean, std = _stats(mean, std, self.n_dims)
+        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
+        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
+        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
+        _ffi.check(_ffi.lib().paa_knn_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
+                                                      C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr, d_proba.ptr,
+                                                      None))
+        idx = d_idx.to_host(np.int32, n_vec)
+        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
+        for b in (d_stats, d_idx, d_proba):
+            b.free()
+        return idx.astype(np.int64), proba
+
+
+def _stats(mean, std, n_dims):
+    mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
+    std = np.ascontiguousarray(np.asarray(std, dtype=np.float64).reshape(-1))
+    if mean.shape[0] != n_dims or std.shape[0] != n_dims:
+        raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], n_dims))
+    return mean, std
+
+
+class Knn:
+    """The reference's k-nearest-neighbour classifier (audioTrainTest.py:33-49); classify runs on the GPU."""
+
+    def __init__(self, features, labels, neighbors):
+        self.features = features
+        self.labels = labels
+        self.neighbors = neighbors
+
+    def classify(self, test_sample):
+        """(first arg-max of P, P) of one feature vector: P[c] = the share of the `neighbors` nearest training rows
+        labelled c (divided by `neighbors` also when there are fewer rows)."""
+        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+        idx, proba = knn_model(self).predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))     # (x - 0) / 1 == x
+        return idx[0], proba[0]
+
+
+_uploaded_knn = weakref.WeakKeyDictionary()
+
+
+def is_knn(classifier):
+    """A kNN classifier: this package's Knn / KnnModel, or any object with the reference Knn's attributes."""
+    return isinstance(classifier, (Knn, KnnModel)) or all(hasattr(classifier, a) for a in ("features", "labels", "neighbors"))
+
+
+def knn_model(classifier):
+    """The device copy of a kNN classifier (uploaded at the first use, kept while the classifier lives)."""
+    if isinstance(classifier, KnnModel):
+        return classifier
+    try:
+        m = _uploaded_knn.get(classifier)
+    except TypeError:
+        m = None
+    if m is None:
+        m = KnnModel(classifier)
+        try:
+            _uploaded_knn[classifier] = m
+        except TypeError:
+            pass
+    return m
+
+
+def knn_predict(classifier, feats, mean, std):
+    """Classify every column of feats [n_dims][n_vec] after (x - mean) / std with a kNN model: (class indices, P)."""
+    return knn_model(classifier).predict(feats, mean, std)
+
+
+def load_model_knn(knn_model_name, is_regression=False):
+    """Loads a kNN model (reference :492-520): eleven pickles -- features, labels, mean, std, class names (not when
+    is_regression), neighbors, mid / short windows and steps, compute_beat."""
+    with open(knn_model_name, "rb") as fo:
+        features = cPickle.load(fo)
+        labels = cPickle.load(fo)
+        mean = cPickle.load(fo)
+        std = cPickle.load(fo)
+        if not is_regression:
+            classes = cPickle.load(fo)
+        neighbors = cPickle.load(fo)
+        mid_window = cPickle.load(fo)
+        mid_step = cPickle.load(fo)
+        short_window = cPickle.load(fo)
+        short_step = cPickle.load(fo)
+        compute_beat = cPickle.load(fo)
+
+    features = np.array(features)
+    labels = np.array(labels)
+    mean = np.array(mean)
+    std = np.array(std)
+
+    classifier = Knn(features, labels, neighbors)
+    if is_regression:
+        return classifier, mean, std, mid_window, mid_step, short_window, short_step, compute_beat
+    return classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat
+
+
+def _load(model_name, model_type):
+    return load_model_knn(model_name) if model_type == "knn" else load_model(model_name)
+
+
+def predict(classifier, model_type, feats, mean, std):
+    """classifier_wrapper for every column of feats [n_dims][n_vec] after (x - mean) / std, in one launch: "knn" gives
+    (class indices, P), the SVM types (classes_ of the winners, probabilities)."""
+    if model_type == "knn":
+        return knn_predict(classifier, feats, mean, std)
+    return svm_predict(classifier, feats, mean, std)
+
+
 def load_model(model_name, is_regression=False):
     """Loads an SVM model either for classification or regression (reference :523-553): the pickled classifier and its
     MEANS file (mean, std, class names, mid / short windows and steps, compute_beat)."""
@@ -163,7 +319,8 @@ def load_model(model_name, is_regression=False):
 
 def classifier_wrapper(classifier, classifier_type, test_sample):
     """(class id, probability estimate) of one feature vector (reference :52-94).  "svm" / "svm_rbf": predict() and
-    predict_proba() on the GPU; the other types call the classifier object as the reference does."""
+    predict_proba() on the GPU; "knn": Knn.classify on the GPU (the class INDEX and P); the other types call the
+    classifier object as the reference does."""
     class_id = -1
     probability = -1
     if classifier_type in _SVM_TYPES:
@@ -172,8 +329,10 @@ def classifier_wrapper(classifier, classifier_type, test_sample):
         idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))       # (x - 0) / 1 == x
         return m.classes[idx[0]], proba[0]
     if classifier_type == "knn":
-        class_id, probability = classifier.classify(test_sample)
-    elif classifier_type in ("randomforest", "gradientboosting", "extratrees"):
+        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+        idx, proba = knn_model(classifier).predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))
+        return idx[0], proba[0]
+    if classifier_type in ("randomforest", "gradientboosting", "extratrees"):
         class_id = classifier.predict(test_sample.reshape(1, -1))[0]
         probability = classifier.predict_proba(test_sample.reshape(1, -1))[0]
     return class_id, probability
@@ -212,9 +371,8 @@ def file_classification(input_file, model_name, model_type):
     if isinstance(input_file, str) and not os.path.isfile(input_file):
         print("fileClassification: wav file not found!")
         return -1, -1, -1
-    if model_type == 'knn':
-        raise NotImplementedError("kNN models (load_model_knn) are not part of this package")
-    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = load_model(model_name)
+    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = \
+        _load(model_name, model_type)
     sampling_rate, signal = audioBasicIO.read_audio_file(input_file)
     signal = audioBasicIO.stereo_to_mono(signal)
     if sampling_rate == 0:
@@ -225,9 +383,9 @@ def file_classification(input_file, model_name, model_type):
 
 
 def file_classification_signals(signals, sampling_rate, classifier, mean, std, mid_window, mid_step, short_window,
-                                short_step, compute_beat):
-    """file_classification for many mono signals of one sampling rate and an SVM model: the clips go through ONE
-    batched mid-term (+ beat) plan, the long-term vectors through ONE SVC launch.  Clips shorter than mid_window take
+                                short_step, compute_beat, model_type="svm_rbf"):
+    """file_classification for many mono signals of one sampling rate and an SVM or kNN model: the clips go through ONE
+    batched mid-term (+ beat) plan, the long-term vectors through ONE SVC / kNN launch.  Clips shorter than mid_window take
     the reference's clamp (:1077-1078, a window of their own length) through the single-clip path.
     Returns (class ids [n], probabilities [n][k])."""
     if len(signals) == 0:
@@ -252,19 +410,20 @@ def file_classification_signals(signals, sampling_rate, classifier, mean, std, m
         if v is None:
             vectors[i] = _long_term_vector(signals[i], fs, mid_window, mid_step, short_window, short_step, compute_beat)
     feats = np.stack(vectors, axis=1)
-    return svm_predict(classifier, feats, mean, std)
+    return predict(classifier, model_type, feats, mean, std)
 
 
 def file_classification_batch(files, model_name, model_type):
     """file_classification over many files with one model: returns a list of (class id, probabilities, class names)
     per file, equal to one-file calls.  Files are grouped by sampling rate; each group is one batched mid-term plan and
-    one SVC launch.  Missing / unreadable files give the reference's (-1, -1, -1)."""
-    if model_type not in _SVM_TYPES:
+    one SVC / kNN launch.  Missing / unreadable files give the reference's (-1, -1, -1)."""
+    if model_type not in _SVM_TYPES and model_type != "knn":
         return [file_classification(f, model_name, model_type) for f in files]
     if not os.path.isfile(model_name):
         print("fileClassification: input model_name not found!")
         return [(-1, -1, -1) for _ in files]
-    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = load_model(model_name)
+    classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = \
+        _load(model_name, model_type)
     out = [(-1, -1, -1)] * len(files)
     groups = {}
     for i, f in enumerate(files):
@@ -277,7 +436,7 @@ def file_classification_batch(files, model_name, model_type):
         groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
     for fs, members in groups.items():
         ids, proba = file_classification_signals([s for _, s in members], fs, classifier, mean, std, mid_window, mid_step,
-                                                 short_window, short_step, compute_beat)
+                                                 short_window, short_step, compute_beat, model_type)
         for j, (i, _) in enumerate(members):
             out[i] = (ids[j], proba[j], classes)
     return out

@@ -29,6 +29,18 @@ struct SvcDev {
     double gamma;
 };
 }  // namespace svc
+namespace knn {
+constexpr int kMaxK = 32;
+constexpr int kMaxClasses = 64;
+constexpr int kMaxDims = 256;
+constexpr int kQueriesPerBlock = 16;      // kernels_knn.hpp: one query per group of 8 lanes, 128 threads
+// one uploaded kNN model (audioTrainTest.Knn): device pointers
+struct KnnDev {
+    const double *train;      // [n_train][n_dims] training vectors
+    const int *labels;        // [n_train] class index of every row (a value outside 0..n_classes-1 votes for no class)
+    int n_train, n_dims, n_classes, k;
+};
+}  // namespace knn
 namespace launch {
 
 // kernels_fast.hpp: window 800, step 400 / 800, int16
@@ -80,6 +92,10 @@ int generic(const GenLayout &gl, size_t lds, int sample_kind, const PlanDev &P, 
 // `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
         double *d_sums, int *d_label, double *d_proba, hipStream_t stream);
+// kernels_knn.hpp: k-nearest-neighbour classification of the columns of feats [n_dims][ld] (one kernel: labels [n_vec],
+// P [n_vec][n_classes] and, when d_neighbors is not null, the k neighbour indices [n_vec][k] in ascending (d^2, index))
+int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
+        int *d_label, double *d_proba, int *d_neighbors, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

@@ -527,6 +527,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 
 #include "lib_host_api.hpp"
 #include "lib_svc.hpp"
+#include "lib_knn.hpp"
 
 // ------------------------------------------------------------------------------------------
 // RCCL gather (one process per GPU; librccl is loaded lazily so CPU-only hosts can load us)

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""Measure the SVM classification path (not part of bench.py).
+"""Measure the SVM and kNN classification paths (not part of bench.py).
 
-    python scripts/bench_classify.py                       # GPU: SVC kernel rate per shipped model, 1 h clip end to end
-    python scripts/bench_classify.py --reference-loop DIR  # host: the reference's per-window scikit-learn loop
-                                                           # (DIR = pyAudioAnalysis/data/models; needs scikit-learn)
+    python scripts/bench_classify.py                       # GPU: SVC and kNN kernel rates per shipped model, 1 h clip end
+                                                           # to end
+    python scripts/bench_classify.py --reference-loop DIR  # host: the reference's per-window loops (SVM: scikit-learn;
+                                                           # kNN: NumPy + SciPy) (DIR = pyAudioAnalysis/data/models)
 
 The models: svm_rbf_sm, svm_rbf_speaker_male_female and svm_rbf_musical_genre_6 from the svc_* goldens (tests/golden, arrays
 only); svm_rbf_speaker_10 and svm_rbf_movie8class, whose arrays are too large for a golden file, as seeded models of exactly their
 shape (tests/svc_libsvm.synthetic_model: same classes, support vectors per class and dims -- the work per window is the same).
-All five use 1 s / 1 s mid-term and 50 ms / 50 ms short-term windows, as the shipped models do.  Rates are medians over --reps
+The kNN models: knn_musical_genre_6 from the knn_genre6_files golden (the real model); knn_sm, knn_speaker_male_female,
+knn_speaker_10 and knn_movie8class as seeded models of exactly their shape (training rows x dims, k, classes: the work per
+window is the same).  The kNN entry also gives the FP64 work per window, 3 n_train n_dims (a subtraction, a multiply and an
+add per training row and dimension).
+All use 1 s / 1 s mid-term and 50 ms / 50 ms short-term windows, as the shipped models do.  Rates are medians over --reps
 calls after one warm-up.  Prints one JSON line.
 """
 import argparse
@@ -29,6 +34,10 @@ GOLDEN_MODELS = {"svm_rbf_sm": "svc_sm_speech_music", "svm_rbf_speaker_male_fema
                  "svm_rbf_musical_genre_6": "svc_genre6_files"}
 SHAPED_MODELS = {"svm_rbf_speaker_10": svc_libsvm.SPEAKER_10_N_SUPPORT, "svm_rbf_movie8class": svc_libsvm.MOVIE8CLASS_N_SUPPORT}
 MODELS = ["svm_rbf_sm", "svm_rbf_speaker_male_female", "svm_rbf_speaker_10", "svm_rbf_movie8class", "svm_rbf_musical_genre_6"]
+# kNN: (training rows, dims, k, classes) of the shipped models; knn_musical_genre_6 is the real one (golden)
+KNN_SHAPES = {"knn_sm": (2422, 136, 5, 2), "knn_speaker_male_female": (1498, 136, 1, 2), "knn_speaker_10": (1294, 136, 9, 10),
+              "knn_movie8class": (3040, 136, 9, 8), "knn_musical_genre_6": (581, 138, 5, 6)}
+KNN_GOLDEN = {"knn_musical_genre_6": "knn_genre6_files"}
 
 
 def golden(name):
@@ -86,8 +95,43 @@ def gpu(args):
                             max(1, args.reps // 4))
             out["one_hour_s"][model] = t
         print(model, {k: v.get(model) for k, v in out.items()}, file=sys.stderr)
+    knn(args, out, clip, clip_mean, clip_std)
     out["windows_per_call"] = args.windows
     return out
+
+
+def knn_seeded(n_train, n_dims, k, n_classes, seed=3):
+    rng = np.random.default_rng(seed)
+    labels = rng.integers(0, n_classes, n_train).astype(np.float64)
+    labels[:n_classes] = np.arange(n_classes)
+    return rng.standard_normal((n_train, n_dims)), labels, k
+
+
+def knn(args, out, clip, clip_mean, clip_std):
+    from pyaudioanalysis_amd import _ffi, audioSegmentation, audioTrainTest
+    rng = np.random.default_rng(2)
+    out.update({"knn_windows_per_s": {}, "knn_one_hour_s": {}, "knn_fp64_flop_per_window": {}})
+    for model, (n_train, n_dims, k, n_classes) in KNN_SHAPES.items():
+        if model in KNN_GOLDEN:
+            g = golden(KNN_GOLDEN[model])
+            clf = audioTrainTest.Knn(g["features"], g["labels"], int(g["neighbors"]))
+            mean, std, beat = g["mean"], g["std"], bool(g["compute_beat"])
+        else:
+            clf = audioTrainTest.Knn(*knn_seeded(n_train, n_dims, k, n_classes))
+            mean, std, beat = clip_mean, clip_std, False
+        m = audioTrainTest.knn_model(clf)
+        assert (m.n_dims, m.k, m.n_classes) == (n_dims, k, n_classes)
+        d_x = _ffi.DeviceBuffer.from_host(rng.standard_normal((n_dims, args.windows)))
+        zeros, ones = np.zeros(n_dims), np.ones(n_dims)
+        t = median_time(lambda: m.predict_device(d_x, args.windows, args.windows, zeros, ones), args.reps)
+        out["knn_windows_per_s"][model] = args.windows / t
+        out["knn_fp64_flop_per_window"][model] = 3 * n_train * n_dims
+        d_x.free()
+        if not beat:           # mid_term_file_classification refuses beat models (audioSegmentation.py:566-570)
+            t = median_time(lambda: audioSegmentation.mid_term_labels(clip, 16000, clf, mean, std, 1.0, 1.0, 0.05, 0.05, "knn"),
+                            max(1, args.reps // 4))
+            out["knn_one_hour_s"][model] = t
+        print(model, {key: out[key].get(model) for key in ("knn_windows_per_s", "knn_one_hour_s")}, file=sys.stderr)
 
 
 def reference_loop(args):
@@ -107,6 +151,24 @@ def reference_loop(args):
                 clf.predict_proba(v.reshape(1, -1))[0]
         t = median_time(loop, 3)
         out["reference_sklearn_windows_per_s"][model] = args.loop_windows / t
+    out["reference_knn_windows_per_s"] = {}
+    from scipy.spatial import distance
+    for model in KNN_SHAPES:
+        with open(os.path.join(args.reference_loop, model), "rb") as f:
+            features, labels = np.array(pickle.load(f)), np.array(pickle.load(f))
+            for _ in range(3):          # mean, std, class names
+                pickle.load(f)
+            k = pickle.load(f)
+        n_classes = np.unique(labels).shape[0]
+        X = rng.standard_normal((args.loop_windows, features.shape[1]))
+
+        def loop():          # audioSegmentation.py:583-594 -> Knn.classify (audioTrainTest.py:39-49): cdist, argsort, votes
+            for v in X:
+                order = np.argsort(distance.cdist(features, v.reshape(1, -1), "euclidean").T)
+                P = np.array([np.count_nonzero(labels[order[0][:k]] == c) / float(k) for c in range(n_classes)])
+                np.argmax(P)
+        t = median_time(loop, 3)
+        out["reference_knn_windows_per_s"][model] = args.loop_windows / t
     return out
 
 
