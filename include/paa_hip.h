@@ -274,6 +274,40 @@ int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dim
                             const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                             int32_t *d_neighbors);
 
+/* ---- audioTrainTest.classifier_wrapper for the tree ensembles (audioTrainTest.py:84-93) -------------------------------
+ * scikit-learn's RandomForestClassifier / ExtraTreesClassifier (kind PAA_FOREST_AVERAGED) and GradientBoostingClassifier
+ * (kind PAA_FOREST_BOOSTED) over many feature vectors at once, as mid_term_file_classification (audioSegmentation.py:583-594)
+ * and file_classification (audioTrainTest.py:1091-1095) ask for them once per vector.  The model is scikit-learn's raw
+ * per-tree arrays, trees concatenated: tree t owns nodes node_offsets[t] .. node_offsets[t + 1] - 1 and its child indices
+ * are local to it (children_left / right = -1 on both sides marks a leaf), feature [nodes] (any value at a leaf),
+ * threshold [nodes], missing_go_to_left [nodes] (may be NULL: NaN goes right), value [nodes][n_classes] (averaged: the
+ * class fractions of tree_.value) or [nodes] (boosted).  Boosted trees are stage-major: tree s * n_outputs + k is stage s,
+ * output k, with n_outputs = 1 for two classes and n_classes otherwise; init [n_outputs] is the constant initial raw score
+ * and learning_rate the shrinkage.  Everything is validated before any device work (PAA_ERR_ARG with a message): every
+ * child in range and every node reached exactly once from its tree's root, features in 0..n_dims-1, 2 <= n_classes <= 64,
+ * 1 <= n_dims <= 256, 1 .. 200 000 trees of at least one node, fewer than 2^31 nodes, whole boosting stages.
+ * feats is feature-major [n_dims][ld], vector v in column v; x = (feats - mean) / std in FP64, rounded to float32, and a
+ * split goes left when (double)x <= threshold.  label_index [n_vec] receives the class index (-1: a value of x is
+ * infinite in float32; -2: a boosted model and a value is NaN -- both are ValueErrors in scikit-learn), proba
+ * [n_vec][n_classes] predict_proba, raw [n_vec][n_outputs] (may be NULL) the tree sums in tree order (averaged: before the
+ * division by n_trees; boosted: the raw scores before the link).                                                        */
+#define PAA_FOREST_AVERAGED 0
+#define PAA_FOREST_BOOSTED  1
+int paa_forest_create(int kind, int n_trees, const int64_t *node_offsets, const int64_t *children_left,
+                      const int64_t *children_right, const int64_t *feature, const double *threshold,
+                      const uint8_t *missing_go_to_left, const double *value, int n_classes, int n_dims, double learning_rate,
+                      const double *init, void **out_handle);
+int paa_forest_destroy(void *handle);
+int paa_forest_num_classes(const void *handle);
+/* host buffers in and out (synchronous) */
+int paa_forest_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, const double *mean,
+                           const double *std, int32_t *label_index, double *proba, double *raw);
+/* device buffers in and out (the resident mid-term matrix of a plan, paa_plan_mid_execute), asynchronous on the library
+ * stream                                                                                                              */
+int paa_forest_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
+                               const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
+                               double *d_raw);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

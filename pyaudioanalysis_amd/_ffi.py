@@ -109,6 +109,14 @@ _SIGNATURES = {
                                       c_i32p]),
     "paa_knn_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "paa_forest_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.c_void_p,
+                                    c_f64p, C.c_int, C.c_int, C.c_double, c_f64p, C.POINTER(C.c_void_p)]),
+    "paa_forest_destroy": (C.c_int, [C.c_void_p]),
+    "paa_forest_num_classes": (C.c_int, [C.c_void_p]),
+    "paa_forest_predict_f64": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int64, C.c_int64, c_f64p, c_f64p, c_i32p, c_f64p,
+                                         c_f64p]),
+    "paa_forest_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "paa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "paa_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "paa_comm_destroy": (C.c_int, []),

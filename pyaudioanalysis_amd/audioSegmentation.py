@@ -238,7 +238,7 @@ def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, w
 
 
 # ---------------------------------------------------------------------------------------------------------
-# fix-sized segment classification with the shipped SVM and kNN models (reference :58-125, :150-175, :495-633)
+# fix-sized segment classification with the SVM, kNN and tree-ensemble models (reference :58-125, :150-175, :495-633)
 # ---------------------------------------------------------------------------------------------------------
 def labels_to_segments(labels, window):
     """Fix-sized class labels -> (segments [n][2] of start / end in seconds, class of each segment) (reference :58-98)."""
@@ -392,9 +392,9 @@ def load_ground_truth(gt_file, labels, class_names, mid_step, plot_results):
 
 def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_step, st_win, st_step, model_type=None):
     """Labels and max-probabilities of every mid-term window of a mono signal (reference :574-594): the mid-term matrix
-    stays in HBM and goes straight into the SVC or kNN kernel (one launch for all windows).  Returns (labels, posterior
-    max): an SVM's classes_, a kNN model's class indices.  model_type "knn" or an SVM type; None takes the model's
-    kind (audioTrainTest.is_knn)."""
+    stays in HBM and goes straight into the SVC, kNN or tree-ensemble kernels (one launch for all windows).  Returns
+    (labels, posterior max): an SVM's or tree ensemble's classes_, a kNN model's class indices.  model_type "knn", a
+    tree-ensemble type or an SVM type; None takes the model's kind (audioTrainTest.is_knn / is_forest)."""
     from . import MidTermFeatures, audioTrainTest
     ratio, step_ratio = MidTermFeatures._ratios(mt_win * sampling_rate, mid_step * sampling_rate,
                                                 round(sampling_rate * st_win), round(sampling_rate * st_step))
@@ -407,8 +407,16 @@ def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_st
     n = sig.shape[0]
     if window < 1 or step < 1 or n < window:
         raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
-    knn = model_type == "knn" or (model_type is None and audioTrainTest.is_knn(classifier))
-    model = audioTrainTest.knn_model(classifier) if knn else audioTrainTest.svc_model(classifier)
+    if model_type is None:
+        model_type = "knn" if audioTrainTest.is_knn(classifier) else \
+            "randomforest" if audioTrainTest.is_forest(classifier) else "svm_rbf"
+    knn = model_type == "knn"
+    if knn:
+        model = audioTrainTest.knn_model(classifier)
+    elif model_type in audioTrainTest._FOREST_TYPES:
+        model = audioTrainTest.forest_model(classifier)
+    else:
+        model = audioTrainTest.svc_model(classifier)
     plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
     try:
         d_in = _ffi.DeviceBuffer.from_host(sig)
@@ -428,7 +436,8 @@ def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_st
 
 def mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step,
                             compute_beat=False, plot_results=False, gt_file="", model_type=None):
-    """mid_term_file_classification on a signal and a loaded SVM or kNN model (reference :518-604 from :562 on):
+    """mid_term_file_classification on a signal and a loaded SVM, kNN or tree-ensemble model (reference :518-604 from
+    :562 on):
     returns (labels, class_names, accuracy, cm)."""
     labels = []
     accuracy = 0.0
@@ -448,7 +457,7 @@ def mid_term_classification(signal, sampling_rate, classifier, mean, std, class_
 
 
 def mid_term_file_classification(input_file, model_name, model_type, plot_results=False, gt_file=""):
-    """Mid-term classification of an audio file with a trained SVM or kNN model (reference :518-604): returns
+    """Mid-term classification of an audio file with a trained SVM, kNN or tree-ensemble model (reference :518-604): returns
     (labels, class_names, accuracy, cm).  Models with compute_beat are refused, as in the reference."""
     import os
     from . import audioTrainTest
@@ -459,8 +468,8 @@ def mid_term_file_classification(input_file, model_name, model_type, plot_result
     if not os.path.isfile(model_name):
         print("mtFileClassificationError: input model_type not found!")
         return labels, class_names, accuracy, cm
-    if model_type not in ("svm", "svm_rbf", "knn"):
-        raise NotImplementedError("model type %r: the GPU path serves the SVM and kNN models" % (model_type,))
+    if model_type not in ("svm", "svm_rbf", "knn") + audioTrainTest._FOREST_TYPES:
+        raise NotImplementedError("model type %r: the GPU path serves the SVM, kNN and tree-ensemble models" % (model_type,))
     if model_type == "knn":
         classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step, compute_beat = \
             audioTrainTest.load_model_knn(model_name)
@@ -474,4 +483,4 @@ def mid_term_file_classification(input_file, model_name, model_type, plot_result
     if sampling_rate == 0:
         return labels, class_names, accuracy, cm
     return mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win,
-                                   st_step, False, plot_results, gt_file, "knn" if model_type == "knn" else "svm_rbf")
+                                   st_step, False, plot_results, gt_file, model_type)

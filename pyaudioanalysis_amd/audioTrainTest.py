@@ -3,8 +3,9 @@
     load_model(model_name, is_regression=False)                  audioTrainTest.py:523-553
     classifier_wrapper(classifier, classifier_type, test_sample) audioTrainTest.py:52-94
     file_classification(input_file, model_name, model_type)      audioTrainTest.py:1052-1096
-    file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one SVC / kNN launch
+    file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one classifier launch
     Knn(features, labels, neighbors), load_model_knn(name)       audioTrainTest.py:33-49, :492-520
+    forest_model(classifier), forest_predict(...), ForestArrays   the tree ensembles of classifier_wrapper (:84-93)
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -12,9 +13,13 @@ pairwise coupling for every vector in one launch.  Only the fitted model's array
 n_support_, _dual_coef_, _intercept_, probA_, probB_, _gamma, kernel, classes_), so a model given as those arrays
 (SvcArrays) works without scikit-learn.  For "knn" (the shipped knn_* models: pickled NumPy arrays, no scikit-learn)
 Knn.classify runs on the GPU (kernels_knn.hpp through paa_knn_*): distances to every training row, the k nearest in
-ascending (squared distance, training index) and the votes, for every vector in one launch.  Every other classifier
-type is called exactly as the reference calls it.  Unpickling an SVM model needs scikit-learn exactly where the
-reference needs it (load_model).  Training stays with scikit-learn.
+ascending (squared distance, training index) and the votes, for every vector in one launch.  For "randomforest",
+"extratrees" and "gradientboosting" (scikit-learn's RandomForestClassifier, ExtraTreesClassifier and
+GradientBoostingClassifier, as the reference's trainers make them) predict() and predict_proba() run on the GPU
+(kernels_forest.hpp through paa_forest_*): every tree walked for every vector, the leaf values summed in tree order,
+bit-identical to scikit-learn; only the trees' tree_ arrays, classes_ and (boosted) learning_rate / init_ are read, so a
+model given as arrays (ForestArrays) works without scikit-learn.  Unpickling an SVM or tree-ensemble model needs
+scikit-learn exactly where the reference needs it (load_model).  Training stays with scikit-learn.
 """
 import ctypes as C
 import os
@@ -27,6 +32,7 @@ from . import MidTermFeatures as aF
 from . import _ffi, audioBasicIO
 
 _SVM_TYPES = ("svm", "svm_rbf")
+_FOREST_TYPES = ("randomforest", "extratrees", "gradientboosting")
 _KERNEL_TYPES = {"linear": 0, "rbf": 2}          # libsvm's LINEAR / RBF
 
 
@@ -289,7 +295,195 @@ def predict(classifier, model_type, feats, mean, std):
     (class indices, P), the SVM types (classes_ of the winners, probabilities)."""
     if model_type == "knn":
         return knn_predict(classifier, feats, mean, std)
+    if model_type in _FOREST_TYPES:
+        return forest_predict(classifier, feats, mean, std)
     return svm_predict(classifier, feats, mean, std)
+
+
+class ForestArrays:
+    """A fitted tree ensemble given as plain arrays (e.g. from an .npz), so that no scikit-learn is needed: kind "averaged"
+    (RandomForestClassifier / ExtraTreesClassifier: value [nodes][n_classes], the class fractions of tree_.value) or
+    "boosted" (GradientBoostingClassifier: value [nodes], trees stage-major, n_outputs = 1 for two classes, else
+    n_classes; init [n_outputs] the constant initial raw score).  Trees are concatenated: tree t owns nodes
+    node_offsets[t] .. node_offsets[t + 1] - 1, and its children_left / children_right / feature index are local to it, in
+    scikit-learn's tree_ arrays' terms (-1 children: a leaf)."""
+
+    def __init__(self, kind, node_offsets, children_left, children_right, feature, threshold, missing_go_to_left, value,
+                 classes, n_dims, learning_rate=0.0, init=None):
+        if kind not in ("averaged", "boosted"):
+            raise ValueError("tree ensemble kind %r: 'averaged' or 'boosted'" % (kind,))
+        self.kind = kind
+        self.node_offsets = np.ascontiguousarray(node_offsets, dtype=np.int64)
+        self.children_left = np.ascontiguousarray(children_left, dtype=np.int64)
+        self.children_right = np.ascontiguousarray(children_right, dtype=np.int64)
+        self.feature = np.ascontiguousarray(feature, dtype=np.int64)
+        self.threshold = np.ascontiguousarray(threshold, dtype=np.float64)
+        n = self.threshold.shape[0]
+        self.missing_go_to_left = np.ascontiguousarray(np.zeros(n) if missing_go_to_left is None else missing_go_to_left,
+                                                       dtype=np.uint8)
+        self.value = np.ascontiguousarray(value, dtype=np.float64)
+        self.classes_ = np.asarray(classes)
+        self.n_dims = int(n_dims)
+        self.learning_rate = float(learning_rate)
+        self.init = None if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
+
+    @property
+    def n_classes(self):
+        return int(self.classes_.shape[0])
+
+    @property
+    def n_outputs(self):
+        return 1 if self.kind == "boosted" and self.n_classes == 2 else self.n_classes
+
+
+def _tree_arrays(trees, width):
+    """Concatenated tree_ arrays of fitted scikit-learn trees (value rows of `width`)."""
+    parts = [t.tree_ for t in trees]
+    offsets = np.concatenate([[0], np.cumsum([p.node_count for p in parts])]).astype(np.int64)
+    cat = lambda get: np.concatenate([np.asarray(get(p)) for p in parts])          # noqa: E731
+    missing = cat(lambda p: getattr(p, "missing_go_to_left", np.zeros(p.node_count, dtype=np.uint8)))
+    value = cat(lambda p: np.asarray(p.value, dtype=np.float64).reshape(p.node_count, -1)[:, :width])
+    return offsets, cat(lambda p: p.children_left), cat(lambda p: p.children_right), cat(lambda p: p.feature), \
+        cat(lambda p: p.threshold), missing, value
+
+
+def forest_arrays(classifier):
+    """ForestArrays of a fitted RandomForestClassifier, ExtraTreesClassifier or GradientBoostingClassifier (only its
+    estimators_' tree_ arrays, classes_, n_features_in_ and, boosted, learning_rate and init_ are read)."""
+    if isinstance(classifier, ForestArrays):
+        return classifier
+    est = classifier.estimators_
+    classes = np.asarray(classifier.classes_)
+    n_dims = int(classifier.n_features_in_)
+    if isinstance(est, np.ndarray) and est.ndim == 2:                 # GradientBoostingClassifier: [n_stages][n_outputs]
+        init_ = classifier.init_
+        if isinstance(init_, str) and init_ == "zero":
+            init = np.zeros(est.shape[1])
+        elif type(init_).__name__ == "DummyClassifier" and getattr(init_, "strategy", None) == "prior":
+            init = np.asarray(classifier._raw_predict_init(np.zeros((1, n_dims), dtype=np.float32)), dtype=np.float64)[0]
+        else:
+            raise NotImplementedError("gradient boosting with init=%r: the GPU path serves the default prior and 'zero'"
+                                      % (init_,))
+        arrays = _tree_arrays([e for stage in est for e in stage], 1)
+        return ForestArrays("boosted", *arrays[:6], arrays[6][:, 0], classes, n_dims, classifier.learning_rate, init)
+    if getattr(classifier, "n_outputs_", 1) != 1:
+        raise NotImplementedError("multi-output forests are not served by the GPU path")
+    arrays = _tree_arrays(list(est), classes.shape[0])
+    return ForestArrays("averaged", *arrays, classes, n_dims)
+
+
+class ForestModel:
+    """A tree ensemble uploaded to the device once (paa_forest_create, which validates and re-lays every tree in preorder);
+    freed with the object."""
+
+    def __init__(self, classifier):
+        a = forest_arrays(classifier)
+        self.classes = a.classes_
+        self.n_classes = a.n_classes
+        self.n_outputs = a.n_outputs
+        self.n_dims = a.n_dims
+        self.boosted = a.kind == "boosted"
+        n_trees = a.node_offsets.shape[0] - 1
+        n_nodes = a.threshold.shape[0]
+        width = 1 if self.boosted else self.n_classes
+        for name in ("children_left", "children_right", "feature", "missing_go_to_left"):
+            if getattr(a, name).shape != (n_nodes,):
+                raise ValueError("tree ensemble: %s has shape %s for %d nodes" % (name, getattr(a, name).shape, n_nodes))
+        if a.value.reshape(n_nodes, -1).shape[1] != width or a.value.size != n_nodes * width or n_trees < 1 \
+                or a.node_offsets[-1] != n_nodes:
+            raise ValueError("tree ensemble: inconsistent arrays (%d trees, %d nodes, value %s)" % (n_trees, n_nodes,
+                                                                                                   a.value.shape))
+        init = a.init if self.boosted else np.zeros(1)
+        if self.boosted and (init is None or init.shape[0] != self.n_outputs):
+            raise ValueError("boosted ensemble: init of %s values for %d outputs" % (
+                None if init is None else init.shape[0], self.n_outputs))
+        ptr = lambda x: x.ctypes.data_as(C.c_void_p)                       # noqa: E731
+        lib = _ffi.lib()
+        handle = C.c_void_p()
+        _ffi.check(lib.paa_forest_create(1 if self.boosted else 0, n_trees, ptr(a.node_offsets), ptr(a.children_left),
+                                         ptr(a.children_right), ptr(a.feature), _ffi.as_f64p(a.threshold),
+                                         ptr(a.missing_go_to_left), _ffi.as_f64p(a.value), self.n_classes, self.n_dims,
+                                         a.learning_rate, _ffi.as_f64p(np.ascontiguousarray(init)), C.byref(handle)))
+        self.handle = handle
+        self._finalizer = weakref.finalize(self, lib.paa_forest_destroy, handle)
+
+    @staticmethod
+    def _raise_invalid(idx):
+        """scikit-learn's input validation, for the whole call: NaN (boosted) before infinity."""
+        if np.any(idx == -2):
+            raise ValueError("Input X contains NaN.")
+        if np.any(idx == -1):
+            raise ValueError("Input X contains infinity or a value too large for dtype('float32').")
+
+    def predict(self, feats, mean, std, raw=False):
+        """feats [n_dims][n_vec] (feature-major) -> (class indices [n_vec], probabilities [n_vec][n_classes]) of
+        (feats[:, v] - mean) / std, plus the raw tree sums [n_vec][n_outputs] when raw is true (averaged: before the
+        division by the number of trees; boosted: the decision function)."""
+        F = np.ascontiguousarray(feats, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
+            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
+        mean, std = _stats(mean, std, self.n_dims)
+        n = F.shape[1]
+        idx = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, self.n_classes), dtype=np.float64)
+        sums = np.empty((n, self.n_outputs), dtype=np.float64)
+        _ffi.check(_ffi.lib().paa_forest_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
+                                                     _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba),
+                                                     _ffi.as_f64p(sums)))
+        self._raise_invalid(idx)
+        if raw:
+            return idx.astype(np.int64), proba, sums
+        return idx.astype(np.int64), proba
+
+    def predict_device(self, d_feats, ld, n_vec, mean, std):
+        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
+        mean, std = _stats(mean, std, self.n_dims)
+        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
+        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
+        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
+        _ffi.check(_ffi.lib().paa_forest_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
+                                                         C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr,
+                                                         d_proba.ptr, None))
+        idx = d_idx.to_host(np.int32, n_vec)
+        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
+        for b in (d_stats, d_idx, d_proba):
+            b.free()
+        self._raise_invalid(idx)
+        return idx.astype(np.int64), proba
+
+
+_uploaded_forest = weakref.WeakKeyDictionary()
+
+
+def is_forest(classifier):
+    """A tree ensemble: ForestArrays / ForestModel, or a fitted scikit-learn ensemble (estimators_ and classes_)."""
+    return isinstance(classifier, (ForestArrays, ForestModel)) or (hasattr(classifier, "estimators_") and
+                                                                   hasattr(classifier, "classes_"))
+
+
+def forest_model(classifier):
+    """The device copy of a fitted tree ensemble (uploaded at the first use, kept while the classifier lives)."""
+    if isinstance(classifier, ForestModel):
+        return classifier
+    try:
+        m = _uploaded_forest.get(classifier)
+    except TypeError:
+        m = None
+    if m is None:
+        m = ForestModel(classifier)
+        try:
+            _uploaded_forest[classifier] = m
+        except TypeError:
+            pass
+    return m
+
+
+def forest_predict(classifier, feats, mean, std):
+    """Classify every column of feats [n_dims][n_vec] after (x - mean) / std with a tree ensemble: (classes_ of the
+    predictions, predict_proba)."""
+    m = forest_model(classifier)
+    idx, proba = m.predict(feats, mean, std)
+    return m.classes[idx], proba
 
 
 def load_model(model_name, is_regression=False):
@@ -319,8 +513,9 @@ def load_model(model_name, is_regression=False):
 
 def classifier_wrapper(classifier, classifier_type, test_sample):
     """(class id, probability estimate) of one feature vector (reference :52-94).  "svm" / "svm_rbf": predict() and
-    predict_proba() on the GPU; "knn": Knn.classify on the GPU (the class INDEX and P); the other types call the
-    classifier object as the reference does."""
+    predict_proba() on the GPU; "knn": Knn.classify on the GPU (the class INDEX and P); "randomforest" / "extratrees" /
+    "gradientboosting": predict() and predict_proba() on the GPU (classes_ and the probabilities); any other type gives
+    the reference's (-1, -1)."""
     class_id = -1
     probability = -1
     if classifier_type in _SVM_TYPES:
@@ -332,9 +527,11 @@ def classifier_wrapper(classifier, classifier_type, test_sample):
         x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
         idx, proba = knn_model(classifier).predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))
         return idx[0], proba[0]
-    if classifier_type in ("randomforest", "gradientboosting", "extratrees"):
-        class_id = classifier.predict(test_sample.reshape(1, -1))[0]
-        probability = classifier.predict_proba(test_sample.reshape(1, -1))[0]
+    if classifier_type in _FOREST_TYPES:
+        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+        m = forest_model(classifier)
+        idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))
+        return m.classes[idx[0]], proba[0]
     return class_id, probability
 
 
@@ -384,8 +581,8 @@ def file_classification(input_file, model_name, model_type):
 
 def file_classification_signals(signals, sampling_rate, classifier, mean, std, mid_window, mid_step, short_window,
                                 short_step, compute_beat, model_type="svm_rbf"):
-    """file_classification for many mono signals of one sampling rate and an SVM or kNN model: the clips go through ONE
-    batched mid-term (+ beat) plan, the long-term vectors through ONE SVC / kNN launch.  Clips shorter than mid_window take
+    """file_classification for many mono signals of one sampling rate and an SVM, kNN or tree-ensemble model: the clips
+    go through ONE batched mid-term (+ beat) plan, the long-term vectors through ONE classifier launch.  Clips shorter than mid_window take
     the reference's clamp (:1077-1078, a window of their own length) through the single-clip path.
     Returns (class ids [n], probabilities [n][k])."""
     if len(signals) == 0:
@@ -416,8 +613,8 @@ def file_classification_signals(signals, sampling_rate, classifier, mean, std, m
 def file_classification_batch(files, model_name, model_type):
     """file_classification over many files with one model: returns a list of (class id, probabilities, class names)
     per file, equal to one-file calls.  Files are grouped by sampling rate; each group is one batched mid-term plan and
-    one SVC / kNN launch.  Missing / unreadable files give the reference's (-1, -1, -1)."""
-    if model_type not in _SVM_TYPES and model_type != "knn":
+    one classifier launch.  Missing / unreadable files give the reference's (-1, -1, -1)."""
+    if model_type not in _SVM_TYPES + _FOREST_TYPES + ("knn",):
         return [file_classification(f, model_name, model_type) for f in files]
     if not os.path.isfile(model_name):
         print("fileClassification: input model_name not found!")

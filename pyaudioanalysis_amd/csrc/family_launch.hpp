@@ -41,6 +41,28 @@ struct KnnDev {
     int n_train, n_dims, n_classes, k;
 };
 }  // namespace knn
+namespace forest {
+constexpr int kMaxClasses = 64;
+constexpr int kMaxDims = 256;
+constexpr int kWin = 64;                  // kernels_forest.hpp: windows per traversal workgroup, one per lane
+constexpr int kChunk = 32768;             // windows per traversal / reduction pass (bounds the leaf-slot scratch)
+// a packed tree node (preorder: the left child of node i is node i + 1): 16 bytes, one load per visited node
+constexpr int kFeatureMask = 0xffff, kMissingLeft = 1 << 16, kLeaf = 1 << 17;
+struct Node {
+    double threshold;         // go left when (double)x32[feature] <= threshold
+    int meta;                 // feature | kMissingLeft (NaN goes left) | kLeaf
+    int next;                 // internal: the right child's node index; leaf: its leaf slot (row of leaf_values)
+};
+// one uploaded tree ensemble (scikit-learn's RandomForest / ExtraTrees / GradientBoosting classifiers): device pointers
+struct ForestDev {
+    const Node *nodes;        // every tree's nodes, tree after tree, each in preorder
+    const int *roots;         // [n_trees] node index of every root
+    const double *leaf_values;    // [n_leaves][n_outputs] averaged forest: class fractions; boosted: [n_leaves] values
+    const double *init;       // [n_outputs] boosted: the constant initial raw score
+    int n_trees, n_dims, n_classes, n_outputs, boosted;
+    double learning_rate;
+};
+}  // namespace forest
 namespace launch {
 
 // kernels_fast.hpp: window 800, step 400 / 800, int16
@@ -96,6 +118,12 @@ int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_v
 // P [n_vec][n_classes] and, when d_neighbors is not null, the k neighbour indices [n_vec][k] in ascending (d^2, index))
 int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
         int *d_label, double *d_proba, int *d_neighbors, hipStream_t stream);
+// kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
+// two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
+// infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the
+// probabilities proba [n_vec][n_classes])
+int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean,
+           const double *d_scale, int *d_leaves, int *d_label, double *d_raw, double *d_proba, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

@@ -138,6 +138,7 @@ struct LaneGuard {
 };
 static Scratch g_sim_z, g_sim_small, g_sim_cand, g_sim_in, g_sim_out, g_sim_filt;     // self-similarity row
 static Scratch g_svc_sums;        // per-class sums of the SVC device-buffer entry point (lib_svc.hpp)
+static Scratch g_forest_scratch;  // leaf slots and raw scores of the tree-ensemble device-buffer entry point (lib_forest.hpp)
 static int g_force_generic = 0;
 static int g_f800_waves = 8;          // PAA_F800_WAVES: waves per workgroup of the 800/400 kernel (4 or 8)
 static int g_num_cu = 256;       // multiProcessorCount of the selected device (MI355X: 256)
@@ -385,7 +386,7 @@ extern "C" void paa_shutdown(void) {
     for (auto &kv : g_tables) free_tables(*kv.second);
     g_tables.clear();
     pool_release_all();
-    for (Scratch *s : {&g_sim_z, &g_sim_small, &g_sim_cand, &g_sim_in, &g_sim_out, &g_sim_filt, &g_svc_sums}) { if (s->p) (void)hipFree(s->p); s->p = nullptr; s->cap = 0; }
+    for (Scratch *s : {&g_sim_z, &g_sim_small, &g_sim_cand, &g_sim_in, &g_sim_out, &g_sim_filt, &g_svc_sums, &g_forest_scratch}) { if (s->p) (void)hipFree(s->p); s->p = nullptr; s->cap = 0; }
     for (Lane &ln : g_lanes) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); ln.stream = nullptr; }
         if (ln.copy_stream) { (void)hipStreamSynchronize(ln.copy_stream); (void)hipStreamDestroy(ln.copy_stream); ln.copy_stream = nullptr; }
@@ -528,6 +529,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_host_api.hpp"
 #include "lib_svc.hpp"
 #include "lib_knn.hpp"
+#include "lib_forest.hpp"
 
 // ------------------------------------------------------------------------------------------
 // RCCL gather (one process per GPU; librccl is loaded lazily so CPU-only hosts can load us)

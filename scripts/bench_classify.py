@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Measure the SVM and kNN classification paths (not part of bench.py).
+"""Measure the SVM, kNN and tree-ensemble classification paths (not part of bench.py).
 
     python scripts/bench_classify.py                       # GPU: SVC and kNN kernel rates per shipped model, 1 h clip end
                                                            # to end
+    python scripts/bench_classify.py --forest              # GPU: tree-ensemble rates per model shape, 1 h clip end to end
     python scripts/bench_classify.py --reference-loop DIR  # host: the reference's per-window loops (SVM: scikit-learn;
                                                            # kNN: NumPy + SciPy) (DIR = pyAudioAnalysis/data/models)
 
@@ -13,6 +14,9 @@ The kNN models: knn_musical_genre_6 from the knn_genre6_files golden (the real m
 knn_speaker_10 and knn_movie8class as seeded models of exactly their shape (training rows x dims, k, classes: the work per
 window is the same).  The kNN entry also gives the FP64 work per window, 3 n_train n_dims (a subtraction, a multiply and an
 add per training row and dimension).
+The tree ensembles (--forest): seeded models (tests/forest_ref.synthetic_forest) of the shapes that the reference's own
+trainers give on the shipped kNN models' training rows (trees, nodes per tree, depth, classes, dims), plus
+RandomForest-500 at knn_movie8class's shape and a 64-class x 256-dim forest.
 All use 1 s / 1 s mid-term and 50 ms / 50 ms short-term windows, as the shipped models do.  Rates are medians over --reps
 calls after one warm-up.  Prints one JSON line.
 """
@@ -134,6 +138,48 @@ def knn(args, out, clip, clip_mean, clip_std):
         print(model, {key: out[key].get(model) for key in ("knn_windows_per_s", "knn_one_hour_s")}, file=sys.stderr)
 
 
+# name: (kind, trees or stages, mean nodes per tree, max depth, classes, dims)
+FOREST_SHAPES = {"sm_rf25": ("averaged", 25, 204, 23, 2, 136), "sm_rf100": ("averaged", 100, 204, 23, 2, 136),
+                 "sm_et25": ("averaged", 25, 603, 25, 2, 136), "sm_gb100": ("boosted", 100, 14, 3, 2, 136),
+                 "movie8_rf25": ("averaged", 25, 1150, 27, 8, 136), "movie8_rf100": ("averaged", 100, 1150, 27, 8, 136),
+                 "movie8_et25": ("averaged", 25, 2692, 33, 8, 136), "movie8_gb100": ("boosted", 100, 14, 3, 8, 136),
+                 "movie8_rf500": ("averaged", 500, 1150, 27, 8, 136),
+                 "genre6_rf100": ("averaged", 100, 157, 18, 6, 138), "genre6_gb100": ("boosted", 100, 14, 3, 6, 138),
+                 "c64_d256_rf100": ("averaged", 100, 1000, 24, 64, 256)}
+
+
+def forest(args):
+    import forest_ref
+    from pyaudioanalysis_amd import MidTermFeatures, _ffi, audioSegmentation, audioTrainTest
+    _ffi.init(0)
+    out = {"forest_windows_per_s": {}, "forest_one_hour_s": {}, "forest_nodes": {}}
+    rng = np.random.default_rng(2)
+    clip = one_hour_clip()
+    mid, _, _ = MidTermFeatures.mid_feature_extraction(clip, 16000, 16000, 16000, 800, 800)
+    clip_mean, clip_std = mid.mean(axis=1), np.where(mid.std(axis=1) > 0, mid.std(axis=1), 1.0)
+    for name, (kind, trees, nodes, depth, n_classes, n_dims) in FOREST_SHAPES.items():
+        a = forest_ref.synthetic_forest(kind, trees, (int(nodes * 0.7), int(nodes * 1.3)), depth, n_classes, n_dims, 9)
+        m = audioTrainTest.forest_model(a)
+        out["forest_nodes"][name] = int(a.threshold.shape[0])
+        d_x = _ffi.DeviceBuffer.from_host(rng.standard_normal((n_dims, args.windows)))
+        zeros, ones = np.zeros(n_dims), np.ones(n_dims)
+        t = median_time(lambda: m.predict_device(d_x, args.windows, args.windows, zeros, ones), args.reps)
+        out["forest_windows_per_s"][name] = args.windows / t
+        d_x.free()
+        if n_dims == 136:
+            model_type = "gradientboosting" if kind == "boosted" else "randomforest"
+            t = median_time(lambda: audioSegmentation.mid_term_labels(clip, 16000, a, clip_mean, clip_std, 1.0, 1.0, 0.05, 0.05,
+                                                                      model_type), max(1, args.reps // 4))
+            out["forest_one_hour_s"][name] = t
+            if name == "movie8_rf100":       # the 0.1 s mid-term step: 36 000 windows
+                t = median_time(lambda: audioSegmentation.mid_term_labels(clip, 16000, a, clip_mean, clip_std, 1.0, 0.1, 0.05,
+                                                                          0.05, model_type), max(1, args.reps // 4))
+                out["forest_one_hour_s"][name + "_step0.1"] = t
+        print(name, {k: v.get(name) for k, v in out.items()}, file=sys.stderr)
+    out["windows_per_call"] = args.windows
+    return out
+
+
 def reference_loop(args):
     import pickle
     import warnings
@@ -178,8 +224,9 @@ def main():
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--reference-loop", default=None)
     ap.add_argument("--loop-windows", type=int, default=200)
+    ap.add_argument("--forest", action="store_true", help="the tree-ensemble shapes only")
     args = ap.parse_args()
-    print(json.dumps(reference_loop(args) if args.reference_loop else gpu(args)))
+    print(json.dumps(reference_loop(args) if args.reference_loop else forest(args) if args.forest else gpu(args)))
 
 
 if __name__ == "__main__":
