@@ -308,6 +308,51 @@ int paa_forest_dev_predict_f64(const void *handle, const double *d_feats, int n_
                                const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                                double *d_raw);
 
+/* ---- audioSegmentation.hmm_segmentation / train_hmm_compute_statistics (audioSegmentation.py:287-492) -------------------
+ * Gaussian hidden Markov models with one diagonal Gaussian per state, as the reference trains them and hmmlearn's
+ * GaussianHMM.predict decodes them.  The model: startprob [K], transmat [K][K], means [K][n_dims], covars [K][n_dims] --
+ * covars is what the reference stores in covars_, the per-class STANDARD DEVIATION (audioSegmentation.py:340), and the
+ * frame log-likelihood is  B[t][k] = -0.5 (n_dims log 2 pi + sum_d log covars[k][d] + sum_d (x[t][d] - means[k][d])^2 /
+ * covars[k][d]).  paa_hmm_create returns PAA_ERR_ARG for K outside 1..32, n_dims outside 1..256, a parameter that is not
+ * finite, a covars value <= 0, and a startprob or a transmat row that has a negative entry or does not sum to 1 within
+ * 1e-8 (so the 0 / 0 row that the training statistics give for a state that is never left is refused here).
+ * feats is feature-major [n_dims][ld], window t in column t, as the mid-term matrix of a plan.  offsets [n_seq + 1] (host
+ * memory, also for the device-buffer call) cuts the n_vec windows into independent sequences: offsets[0] = 0,
+ * offsets[n_seq] = n_vec, every sequence at least one window (PAA_ERR_ARG otherwise).  Decoding is Viterbi with hmmlearn's
+ * semantics: lat[0][j] = log startprob[j] + B[0][j], lat[t][j] = max_i (lat[t-1][i] + log transmat[i][j]) + B[t][j], the
+ * last state arg max_j lat[T-1][j], back through arg max_i (lat[t][i] + log transmat[i][s[t+1]]); every arg max is the LOWEST
+ * index among equal maxima; log 0 = -inf.  states [n_vec] receives the state of every window, logprob [n_seq] the
+ * log-probability of every sequence's best path.  Sequences longer than 256 windows are decoded by blocks of 256 in (max,+)
+ * form, which changes the association of the additions: logprob agrees with the serial recursion to rounding, and states
+ * agree wherever the serial recursion's decisions are not within rounding of a tie; exact ties between states with
+ * identical parameters still resolve to the lowest index.  One decode call per handle at a time (the handle owns the
+ * scratch).                                                                                                             */
+int paa_hmm_create(const double *startprob, const double *transmat, const double *means, const double *covars, int n_states,
+                   int n_dims, void **out_handle);
+int paa_hmm_destroy(void *handle);
+int paa_hmm_num_states(const void *handle);
+/* host buffers in and out (synchronous) */
+int paa_hmm_decode_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, const int64_t *offsets,
+                       int64_t n_seq, int32_t *states, double *logprob);
+/* device buffers in and out (offsets on the host), asynchronous on the library stream */
+int paa_hmm_dev_decode_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
+                           const int64_t *offsets, int64_t n_seq, int32_t *d_states, double *d_logprob);
+/* the frame log-likelihoods B [n_vec][n_states] alone (device buffers, asynchronous) */
+int paa_hmm_dev_loglik_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec, double *d_loglik);
+/* train_hmm_compute_statistics: labels [n_vec] (host) in 0..n_states-1 (PAA_ERR_ARG otherwise); priors [K] = class counts /
+ * n_vec, transmat [K][K] = counts of consecutive label pairs divided by their row sums (a state that is never left gives a
+ * 0 / 0 = NaN row, as in the reference), means [K][n_dims] and covars [K][n_dims] = np.std (population, two passes) of every
+ * feature row over the class's windows.  All four outputs are host arrays; both calls are synchronous.                 */
+int paa_hmm_train_stats_f64(const double *feats, int n_dims, int64_t ld, int64_t n_vec, const int32_t *labels, int n_states,
+                            double *priors, double *transmat, double *means, double *covars);
+int paa_hmm_dev_train_stats_f64(const double *d_feats, int n_dims, int64_t ld, int64_t n_vec, const int32_t *labels,
+                                int n_states, double *priors, double *transmat, double *means, double *covars);
+/* paa_hmm_dev_decode_f64 with sequences cut every block_rows windows (<= 0: 256); at least the longest sequence: the serial
+ * recursion, one wave per sequence                                                                                     */
+int paa_debug_hmm_dev_decode_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
+                                 const int64_t *offsets, int64_t n_seq, int32_t *d_states, double *d_logprob,
+                                 int64_t block_rows);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

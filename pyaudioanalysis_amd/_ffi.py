@@ -117,6 +117,19 @@ _SIGNATURES = {
                                          c_f64p]),
     "paa_forest_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "paa_hmm_create": (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "paa_hmm_destroy": (C.c_int, [C.c_void_p]),
+    "paa_hmm_num_states": (C.c_int, [C.c_void_p]),
+    "paa_hmm_decode_f64": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64, c_i32p, c_f64p]),
+    "paa_hmm_dev_decode_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64, C.c_void_p,
+                                         C.c_void_p]),
+    "paa_hmm_dev_loglik_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "paa_hmm_train_stats_f64": (C.c_int, [c_f64p, C.c_int, C.c_int64, C.c_int64, c_i32p, C.c_int, c_f64p, c_f64p, c_f64p,
+                                          c_f64p]),
+    "paa_hmm_dev_train_stats_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i32p, C.c_int, c_f64p, c_f64p,
+                                              c_f64p, c_f64p]),
+    "paa_debug_hmm_dev_decode_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_int64]),
     "paa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "paa_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "paa_comm_destroy": (C.c_int, []),

@@ -12,8 +12,10 @@ SVM probability of silence_removal); there is no CPU fallback for those.  `music
 features and the similarity matrix in HBM: only the filtered matrix it returns comes back to the host.
 `silence_removal` trains its two-class SVM exactly where the reference does -- with scikit-learn (:739,
 audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744-748) by one kernel over all frames
-(svm_onset_probability).  The rest of audioSegmentation (HMM segmentation, diarisation, plotting) is out of scope
-(control plane / third-party models).
+(svm_onset_probability).  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
+hmm_segmentation, :287-492) runs on the GPU as well: class GaussianHmm stands in for hmmlearn's GaussianHMM (hmmlearn is not
+needed, also not to read a model file the reference wrote).  The rest of audioSegmentation (diarisation, plotting) is out
+of scope (control plane / third-party models).
 """
 import ctypes as C
 
@@ -484,3 +486,322 @@ def mid_term_file_classification(input_file, model_name, model_type, plot_result
         return labels, class_names, accuracy, cm
     return mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win,
                                    st_step, False, plot_results, gt_file, model_type)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# joint segmentation-classification with a Gaussian HMM (reference :287-492)
+# ---------------------------------------------------------------------------------------------------------
+def _release_hmm(handle):
+    _ffi.lib().paa_hmm_destroy(handle)
+
+
+class GaussianHmm:
+    """A Gaussian HMM with one diagonal Gaussian per state, with the attributes the reference sets on hmmlearn's
+    GaussianHMM (startprob_, transmat_, means_, covars_ -- the latter holds what the reference puts there, the per-class
+    standard deviation, :340).  predict / decode are hmmlearn's (Viterbi, lowest index among equal maxima) on the GPU;
+    the model is uploaded at the first call (ValueError when paa_hmm_create refuses it) and freed with the object."""
+    covariance_type = "diag"
+
+    def __init__(self, startprob, transmat, means, covars):
+        self.startprob_ = np.ascontiguousarray(np.asarray(startprob, dtype=np.float64).reshape(-1))
+        self.means_ = np.ascontiguousarray(np.atleast_2d(np.asarray(means, dtype=np.float64)))
+        self.covars_ = np.ascontiguousarray(np.atleast_2d(np.asarray(covars, dtype=np.float64)))
+        self.n_components = self.startprob_.shape[0]
+        self.transmat_ = np.ascontiguousarray(np.asarray(transmat, dtype=np.float64).reshape(self.n_components, -1))
+        k = self.n_components
+        if self.transmat_.shape != (k, k) or self.means_.shape[0] != k or self.covars_.shape != self.means_.shape:
+            raise ValueError("HMM arrays disagree: startprob %s, transmat %s, means %s, covars %s"
+                             % (self.startprob_.shape, self.transmat_.shape, self.means_.shape, self.covars_.shape))
+        self.n_features = self.means_.shape[1]
+        self._handle = None
+
+    def __getstate__(self):
+        return {"startprob_": self.startprob_, "transmat_": self.transmat_, "means_": self.means_, "covars_": self.covars_}
+
+    def __setstate__(self, state):
+        self.__init__(state["startprob_"], state["transmat_"], state["means_"], state["covars_"])
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            import weakref
+            lib = _ffi.lib()
+            handle = C.c_void_p()
+            rc = lib.paa_hmm_create(_ffi.as_f64p(self.startprob_), _ffi.as_f64p(self.transmat_), _ffi.as_f64p(self.means_),
+                                    _ffi.as_f64p(self.covars_), self.n_components, self.n_features, C.byref(handle))
+            if rc == _ffi.ERR_ARG:
+                raise ValueError("not a valid Gaussian HMM: " + _ffi.last_error())
+            _ffi.check(rc)
+            self._handle = handle
+            self._finalizer = weakref.finalize(self, _release_hmm, handle)
+        return self._handle
+
+    @staticmethod
+    def _offsets(lengths, n):
+        if lengths is None:
+            return np.array([0, n], dtype=np.int64)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if lengths.shape[0] < 1 or np.any(lengths < 1) or int(lengths.sum()) != n:
+            raise ValueError("lengths must be positive and sum to the %d rows of X" % n)
+        return np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+
+    def decode(self, X, lengths=None):
+        """X [n_windows][n_dims] -> (log-probability of the best path, states); with lengths, the log-probabilities of
+        the sequences summed, as hmmlearn's decode."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        if X.shape[1] != self.n_features or X.shape[0] < 1:
+            raise ValueError("X of shape %s for a model of %d dims" % (X.shape, self.n_features))
+        logprob, states = self.decode_sequences(X, lengths)
+        return float(logprob.sum()), states
+
+    def decode_sequences(self, X, lengths=None):
+        """(log-probability of every sequence, states) of the rows of X [n_windows][n_dims]."""
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        F = np.ascontiguousarray(X.T)
+        n = F.shape[1]
+        offsets = self._offsets(lengths, n)
+        states = np.empty(n, dtype=np.int32)
+        logprob = np.empty(offsets.shape[0] - 1)
+        _ffi.check(_ffi.lib().paa_hmm_decode_f64(self.handle, _ffi.as_f64p(F), self.n_features, n, n, _ffi.as_i64p(offsets),
+                                                 offsets.shape[0] - 1, states.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(logprob)))
+        return logprob, states.astype(np.int64)
+
+    def predict(self, X, lengths=None):
+        return self.decode(X, lengths)[1]
+
+    def predict_device(self, d_feats, ld, n_vec, offsets=None, block_rows=None):
+        """The same on a device-resident feature-major matrix (a DeviceBuffer of [n_dims][ld] doubles): (log-probability of
+        every sequence, states).  offsets [n_seq + 1] cuts the windows into sequences; block_rows (tests): the block
+        length of the decoder instead of its own."""
+        offsets = np.array([0, n_vec], dtype=np.int64) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        n_seq = offsets.shape[0] - 1
+        d_states = _ffi.DeviceBuffer(max(4 * n_vec, 8))
+        d_logprob = _ffi.DeviceBuffer(8 * max(n_seq, 1))
+        try:
+            lib = _ffi.lib()
+            if block_rows is None:
+                rc = lib.paa_hmm_dev_decode_f64(self.handle, d_feats.ptr, self.n_features, ld, n_vec, _ffi.as_i64p(offsets),
+                                                n_seq, d_states.ptr, d_logprob.ptr)
+            else:
+                rc = lib.paa_debug_hmm_dev_decode_f64(self.handle, d_feats.ptr, self.n_features, ld, n_vec,
+                                                      _ffi.as_i64p(offsets), n_seq, d_states.ptr, d_logprob.ptr, block_rows)
+            _ffi.check(rc)
+            states = d_states.to_host(np.int32, n_vec)
+            logprob = d_logprob.to_host(np.float64, n_seq)
+        finally:
+            d_states.free()
+            d_logprob.free()
+        return logprob, states.astype(np.int64)
+
+    def log_likelihood_device(self, d_feats, ld, n_vec):
+        """Frame log-likelihoods [n_vec][n_states] of a device-resident feature-major matrix."""
+        d_out = _ffi.DeviceBuffer(8 * n_vec * self.n_components)
+        try:
+            _ffi.check(_ffi.lib().paa_hmm_dev_loglik_f64(self.handle, d_feats.ptr, self.n_features, ld, n_vec, d_out.ptr))
+            return d_out.to_host(np.float64, n_vec * self.n_components).reshape(n_vec, self.n_components)
+        finally:
+            d_out.free()
+
+
+def as_gaussian_hmm(model):
+    """A GaussianHmm as it is; any other object (hmmlearn's GaussianHMM, the stand-in load_hmm builds from a reference
+    file) through its startprob_, transmat_, means_ and _covars_ (hmmlearn's storage of covars_) attributes."""
+    if isinstance(model, GaussianHmm):
+        return model
+    state = getattr(model, "__dict__", {})
+    covars = state["_covars_"] if "_covars_" in state else getattr(model, "covars_")
+    return GaussianHmm(model.startprob_, model.transmat_, model.means_, covars)
+
+
+def _stats_labels(features, labels):
+    """The reference's label handling (:302-309, :319-320): K = the number of distinct labels, labels longer than the
+    matrix are cut; the transition matrix is indexed by the raw labels, so anything but 0..K-1 is an IndexError."""
+    labels = np.asarray(labels)
+    unique_labels = np.unique(labels)
+    n_comps = len(unique_labels)
+    if features.shape[1] < labels.shape[0]:
+        print("trainHMM warning: number of short-term feature vectors "
+              "must be greater or equal to the labels length!")
+        labels = labels[0:features.shape[1]]
+    if labels.shape[0] < 1:
+        raise ValueError("no labelled windows")
+    as_int = labels.astype(np.int64)
+    if np.any(as_int != labels) or not np.array_equal(unique_labels, np.arange(n_comps)):
+        raise IndexError("labels must be the integers 0..%d: the transition matrix is indexed by them" % (n_comps - 1))
+    return np.ascontiguousarray(as_int, dtype=np.int32), n_comps
+
+
+def train_hmm_compute_statistics(features, labels):
+    """(class priors [K], transition matrix [K][K], means [K][n_dims], standard deviations [K][n_dims]) of a feature
+    matrix [n_dims][n_windows] and its class indices, on the GPU (reference :287-344)."""
+    F = np.ascontiguousarray(np.asarray(features, dtype=np.float64))
+    if F.ndim != 2:
+        raise ValueError("features must be (n_dims x n_windows)")
+    lab, k = _stats_labels(F, labels)
+    n = lab.shape[0]
+    priors, trans = np.empty(k), np.empty((k, k))
+    means, cov = np.empty((k, F.shape[0])), np.empty((k, F.shape[0]))
+    _ffi.check(_ffi.lib().paa_hmm_train_stats_f64(_ffi.as_f64p(F), F.shape[0], F.shape[1], n, lab.ctypes.data_as(_ffi.c_i32p),
+                                                  k, _ffi.as_f64p(priors), _ffi.as_f64p(trans), _ffi.as_f64p(means),
+                                                  _ffi.as_f64p(cov)))
+    return priors, trans, means, cov
+
+
+def train_hmm_compute_statistics_device(d_feats, n_dims, ld, n_vec, labels):
+    """The same on a device-resident feature-major matrix (labels no longer than n_vec)."""
+    lab, k = _stats_labels(np.empty((n_dims, n_vec)), labels)
+    priors, trans = np.empty(k), np.empty((k, k))
+    means, cov = np.empty((k, n_dims)), np.empty((k, n_dims))
+    _ffi.check(_ffi.lib().paa_hmm_dev_train_stats_f64(d_feats.ptr, n_dims, ld, lab.shape[0], lab.ctypes.data_as(_ffi.c_i32p), k,
+                                                      _ffi.as_f64p(priors), _ffi.as_f64p(trans), _ffi.as_f64p(means),
+                                                      _ffi.as_f64p(cov)))
+    return priors, trans, means, cov
+
+
+def save_hmm(hmm_model_name, model, classes, mid_window, mid_step):
+    """Four consecutive pickles, as the reference (:455-461): model, class names, mid-term window, mid-term step."""
+    import pickle
+    with open(hmm_model_name, "wb") as f_handle:
+        for obj in (model, classes, mid_window, mid_step):
+            pickle.dump(obj, f_handle, protocol=pickle.HIGHEST_PROTOCOL)
+
+
+class _HmmStandIn:
+    """What a pickled hmmlearn object is rebuilt as: a bare attribute holder."""
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
+
+def _hmm_unpickler(f_handle):
+    import pickle
+
+    class Unpickler(pickle.Unpickler):
+        def find_class(self, module, name):
+            if (module, name) in (("hmmlearn.hmm", "GaussianHMM"), ("hmmlearn.base", "ConvergenceMonitor")):
+                return type(name, (_HmmStandIn,), {})
+            if (module, name) == (__name__, "GaussianHmm"):
+                return GaussianHmm
+            if (module, name) == ("collections", "deque"):
+                import collections
+                return collections.deque
+            if (module, name) in (("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
+                                  ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
+                                  ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer"),
+                                  ("numpy", "ndarray"), ("numpy", "dtype")):
+                return pickle.Unpickler.find_class(self, module, name)
+            raise pickle.UnpicklingError("HMM model file names %s.%s, which a model file has no use for" % (module, name))
+    return Unpickler(f_handle)
+
+
+def load_hmm(hmm_model_name):
+    """(GaussianHmm, class names, mid-term window, mid-term step) of a file written by save_hmm here or by the reference
+    (a pickled hmmlearn GaussianHMM; hmmlearn is not needed).  Any other global in the file is refused."""
+    with open(hmm_model_name, "rb") as f_handle:
+        unpickler = _hmm_unpickler(f_handle)
+        model = unpickler.load()
+        class_names = unpickler.load()
+        mid_window = unpickler.load()
+        mid_step = unpickler.load()
+    return as_gaussian_hmm(model), class_names, mid_window, mid_step
+
+
+def _train_and_save(features, flags, class_names, hmm_model_name, mid_window, mid_step):
+    class_priors, transmutation_matrix, means, cov = train_hmm_compute_statistics(features, flags)
+    hmm = GaussianHmm(class_priors, transmutation_matrix, means, cov)
+    save_hmm(hmm_model_name, hmm, class_names, mid_window, mid_step)
+    return hmm, class_names
+
+
+def train_hmm_from_file(wav_file, gt_file, hmm_model_name, mid_window, mid_step):
+    """Train an HMM segmenter on one annotated file and store it (reference :347-388): returns (hmm, class_names)."""
+    from . import MidTermFeatures
+    seg_start, seg_end, seg_labs = read_segmentation_gt(gt_file)
+    flags, class_names = segments_to_labels(seg_start, seg_end, seg_labs, mid_step)
+    sampling_rate, signal = audioBasicIO.read_audio_file(wav_file)
+    results, _ = MidTermFeatures._mid_for_files([(sampling_rate, signal)], mid_window, mid_step, 0.050, 0.050, False)
+    return _train_and_save(results[0][0], flags, class_names, hmm_model_name, mid_window, mid_step)
+
+
+def train_hmm_from_directory(folder_path, hmm_model_name, mid_window, mid_step):
+    """Train an HMM segmenter on every WAV of a folder that has a .segments file and store it (reference :391-452).  The
+    mid-term matrices of all files come from one batched plan per sampling rate and sample layout."""
+    import glob
+    import os
+    from . import MidTermFeatures
+    flags_all = np.array([])
+    class_names_all = []
+    per_file, entries = [], []
+    for f in glob.glob(folder_path + os.sep + '*.wav'):
+        gt_file = f.replace('.wav', '.segments')
+        if os.path.isfile(gt_file):
+            seg_start, seg_end, seg_labs = read_segmentation_gt(gt_file)
+            flags, class_names = segments_to_labels(seg_start, seg_end, seg_labs, mid_step)
+            for c in class_names:
+                if c not in class_names_all:
+                    class_names_all.append(c)
+            # the reference's re-indexing (:430-433) maps an index of class_names_all onto itself
+            flags_new = [class_names_all.index(class_names_all[fl]) for fl in flags]
+            per_file.append(np.array(flags_new))
+            entries.append(audioBasicIO.read_audio_file(f))
+    results, _ = MidTermFeatures._mid_for_files(entries, mid_window, mid_step, 0.050, 0.050, False) if entries else ([], None)
+    f_all = None
+    for flags, (feature_vector, _) in zip(per_file, results):
+        min_sm = min(feature_vector.shape[1], len(flags))
+        flags_all = np.append(flags_all, flags[0:min_sm])
+        feature_vector = feature_vector[:, 0:min_sm]
+        f_all = feature_vector if f_all is None else np.concatenate((f_all, feature_vector), axis=1)
+    if f_all is None:
+        raise UnboundLocalError("no annotated WAV file in %s" % folder_path)      # f_all is unbound in the reference (:446)
+    return _train_and_save(f_all, flags_all, class_names_all, hmm_model_name, mid_window, mid_step)
+
+
+def hmm_labels(signal, sampling_rate, hmm, mid_window, mid_step):
+    """hmm.predict of every mid-term window of a signal (reference :472-481): the mid-term matrix stays in HBM and goes
+    straight into the emission and Viterbi kernels; only the labels come back."""
+    from . import MidTermFeatures
+    hmm = as_gaussian_hmm(hmm)
+    st = round(sampling_rate * 0.050)
+    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st, st)
+    if step_ratio < 1:
+        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
+    signal = audioBasicIO.stereo_to_mono(signal)
+    kind, sig = _ffi.classify_signal(signal)
+    n = sig.shape[0]
+    window = step = int(st)
+    if window < 1 or n < window:
+        raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
+    handle = hmm.handle                   # a model the library refuses fails before any feature work
+    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
+    bufs = []
+    try:
+        d_in = _ffi.DeviceBuffer.from_host(sig)
+        bufs.append(d_in)
+        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
+        bufs.append(d_st)
+        plan.execute(d_in, d_st)
+        n_mid = plan.mid_doubles(step_ratio)
+        d_mid = _ffi.DeviceBuffer(n_mid * 8)
+        bufs.append(d_mid)
+        plan.mid_execute(d_st, ratio, step_ratio, d_mid)
+        M = n_mid // (2 * 68)
+        _, labels = hmm.predict_device(d_mid, M, M)
+    finally:
+        for b in bufs:
+            b.free()
+        plan.destroy()
+    return labels
+
+
+def hmm_segmentation_signal(signal, sampling_rate, hmm, class_names, mid_window, mid_step, plot_results=False, gt_file=""):
+    """hmm_segmentation on a signal and a loaded model: returns (labels, class_names, accuracy, cm)."""
+    labels = hmm_labels(signal, sampling_rate, hmm, mid_window, mid_step)
+    labels_gt, class_names_gt, accuracy, cm = load_ground_truth(gt_file, labels, class_names, mid_step, plot_results)
+    return labels, class_names, accuracy, cm
+
+
+def hmm_segmentation(audio_file, hmm_model_name, plot_results=False, gt_file=""):
+    """Segment an audio file with a stored HMM (reference :464-492): returns (labels, class_names, accuracy, cm)."""
+    sampling_rate, signal = audioBasicIO.read_audio_file(audio_file)
+    hmm, class_names, mid_window, mid_step = load_hmm(hmm_model_name)
+    return hmm_segmentation_signal(signal, sampling_rate, hmm, class_names, mid_window, mid_step, plot_results, gt_file)

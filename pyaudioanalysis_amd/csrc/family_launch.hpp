@@ -63,6 +63,25 @@ struct ForestDev {
     double learning_rate;
 };
 }  // namespace forest
+namespace hmm {
+constexpr int kMaxStates = 32;
+constexpr int kMaxDims = 256;
+constexpr int kBlockRows = 256;           // rows per segment of a long sequence (kernels_hmm.hpp); shorter sequences are one segment
+// one uploaded Gaussian HMM (diagonal): device pointers; kp = n_states rounded up to a power of two (>= 2), padded
+// states have log-probability -inf
+struct HmmDev {
+    const double *mu, *inv;   // [n_dims][kp] means and 1 / covars_ (the reference's covars_ hold standard deviations)
+    const double *cst;        // [kp] n_dims log(2 pi) + sum_d log covars_[k][d]
+    const double *logpi;      // [kp] log startprob
+    const double *logA;       // [kp][kp] log transmat
+    int n_states, n_dims, kp;
+};
+// rows r0 .. r1 - 1 of the stacked sequences; first / last: the segment begins / ends its sequence
+struct Segment {
+    long long r0, r1;
+    int first, last;
+};
+}  // namespace hmm
 namespace launch {
 
 // kernels_fast.hpp: window 800, step 400 / 800, int16
@@ -124,6 +143,18 @@ int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_v
 // probabilities proba [n_vec][n_classes])
 int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean,
            const double *d_scale, int *d_leaves, int *d_label, double *d_raw, double *d_proba, hipStream_t stream);
+// kernels_hmm.hpp: frame log-likelihoods loglik [n_vec][n_states] of the columns of feats [n_dims][ld] (one kernel)
+int hmm_emission(const hmm::HmmDev &m, const double *d_feats, long long ld, long long n_vec, double *d_loglik, hipStream_t stream);
+// ... and Viterbi over n_seq sequences cut into n_seg segments (segment s of sequence q: seq_seg[q] <= s < seq_seg[q + 1]):
+// states [rows] and logprob [n_seq].  multi: some sequence has more than one segment (two more kernels: M [n_seg][kp][kp],
+// V [n_seg][kp]); Vout [n_seg][kp], psi [rows][kp] bytes, emap [n_seg][kp] bytes, seg_end [n_seg] are scratch
+int hmm_decode(const hmm::HmmDev &m, const double *d_loglik, const hmm::Segment *d_segs, long long n_seg,
+               const long long *d_seq_seg, long long n_seq, int multi, double *d_M, double *d_V, double *d_Vout,
+               unsigned char *d_psi, unsigned char *d_emap, int *d_seg_end, int *d_states, double *d_logprob, hipStream_t stream);
+// ... and the training statistics of labelled windows: counts [K + K K] (zero on entry: class counts, transition counts),
+// means / stds [K][n_dims] (two kernels)
+int hmm_stats(const double *d_feats, long long ld, long long n_vec, const int *d_labels, int n_states, int n_dims,
+              int *d_counts, double *d_means, double *d_stds, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

@@ -8,7 +8,9 @@
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -530,6 +532,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_svc.hpp"
 #include "lib_knn.hpp"
 #include "lib_forest.hpp"
+#include "lib_hmm.hpp"
 
 // ------------------------------------------------------------------------------------------
 // RCCL gather (one process per GPU; librccl is loaded lazily so CPU-only hosts can load us)

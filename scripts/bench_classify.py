@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Measure the SVM, kNN and tree-ensemble classification paths (not part of bench.py).
 
+    python scripts/bench_classify.py --hmm                 # GPU: the HMM segmenter (emission + Viterbi)
     python scripts/bench_classify.py                       # GPU: SVC and kNN kernel rates per shipped model, 1 h clip end
                                                            # to end
     python scripts/bench_classify.py --forest              # GPU: tree-ensemble rates per model shape, 1 h clip end to end
@@ -180,6 +181,62 @@ def forest(args):
     return out
 
 
+def hmm(args):
+    """Emission + Viterbi rates (device-resident windows), the block decode against the one-wave serial decode of the same
+    sequence, the ragged batch, hmm_segmentation's labels of the 1-hour clip beside mid_term_labels with svm_rbf_sm, and the
+    NumPy restatement on one core for scale.  Runs on the GPU."""
+    import hmm_ref
+    from pyaudioanalysis_amd import _ffi, audioSegmentation, audioTrainTest
+    _ffi.init(0)
+    out = {"hmm_windows_per_s": {}, "hmm_block_s": {}, "hmm_one_wave_s": {}, "hmm_emission_s": {}, "hmm_one_hour_s": {},
+           "hmm_numpy_windows_per_s": {}}
+    T, D = 36000, 136
+    for K in (2, 4, 8, 32):
+        model = hmm_ref.synthetic_model(K, D, 40 + K)
+        X = hmm_ref.synthetic_sequence(model, T, 50 + K)
+        h = audioSegmentation.GaussianHmm(*model)
+        d_x = _ffi.DeviceBuffer.from_host(np.ascontiguousarray(X.T))
+        t_block = median_time(lambda: h.predict_device(d_x, T, T), args.reps)
+        t_wave = median_time(lambda: h.predict_device(d_x, T, T, None, T), max(2, args.reps // 2))
+        t_emit = median_time(lambda: h.log_likelihood_device(d_x, T, T), args.reps)
+        _, a = h.predict_device(d_x, T, T)
+        _, b = h.predict_device(d_x, T, T, None, T)
+        out["hmm_windows_per_s"][K] = T / t_block
+        out["hmm_block_s"][K], out["hmm_one_wave_s"][K], out["hmm_emission_s"][K] = t_block, t_wave, t_emit
+        out.setdefault("hmm_block_equals_one_wave", {})[K] = bool(np.array_equal(a, b))
+        d_x.free()
+        if K in (2, 8):
+            t0 = time.perf_counter()
+            hmm_ref.decode(*model, X[:6000])
+            out["hmm_numpy_windows_per_s"][K] = 6000 / (time.perf_counter() - t0)
+        print("hmm K", K, {k: v.get(K) for k, v in out.items() if isinstance(v, dict)}, file=sys.stderr)
+    out["hmm_emission_bytes"] = T * D * 8
+    # ragged batch: 1 000 sequences of 1 .. 600 windows, K = 4, D = 8
+    model = hmm_ref.synthetic_model(4, 8, 31)
+    lengths = np.random.default_rng(31).integers(1, 601, 1000)
+    X = hmm_ref.synthetic_sequence(model, int(lengths.sum()), 1031)
+    h = audioSegmentation.GaussianHmm(*model)
+    d_x = _ffi.DeviceBuffer.from_host(np.ascontiguousarray(X.T))
+    offsets = np.concatenate(([0], np.cumsum(lengths))).astype(np.int64)
+    t = median_time(lambda: h.predict_device(d_x, X.shape[0], X.shape[0], offsets), args.reps)
+    out["hmm_ragged_windows_per_s"] = X.shape[0] / t
+    d_x.free()
+    # one hour, host to host: the shipped model's shape (K = 2) beside the SVM path at the same steps
+    clip = one_hour_clip()
+    model = hmm_ref.synthetic_model(2, 136, 7)
+    h = audioSegmentation.GaussianHmm(*model)
+    g = golden(GOLDEN_MODELS["svm_rbf_sm"])
+    svc = audioTrainTest.SvcModel(audioTrainTest.SvcArrays(g["sv"], g["n_support"], g["dual_coef"], -g["rho"], g["prob_a"],
+                                                           g["prob_b"], g["gamma"], str(g["kernel"]), g["classes"]))
+    for step in (1.0, 0.1):
+        out["hmm_one_hour_s"]["hmm_step%g" % step] = median_time(
+            lambda: audioSegmentation.hmm_labels(clip, 16000, h, 1.0, step), max(1, args.reps // 4))
+        out["hmm_one_hour_s"]["svm_rbf_sm_step%g" % step] = median_time(
+            lambda: audioSegmentation.mid_term_labels(clip, 16000, svc, g["mean"], g["std"], 1.0, step, 0.05, 0.05),
+            max(1, args.reps // 4))
+    return out
+
+
 def reference_loop(args):
     import pickle
     import warnings
@@ -225,8 +282,10 @@ def main():
     ap.add_argument("--reference-loop", default=None)
     ap.add_argument("--loop-windows", type=int, default=200)
     ap.add_argument("--forest", action="store_true", help="the tree-ensemble shapes only")
+    ap.add_argument("--hmm", action="store_true", help="the HMM segmenter only")
     args = ap.parse_args()
-    print(json.dumps(reference_loop(args) if args.reference_loop else forest(args) if args.forest else gpu(args)))
+    print(json.dumps(reference_loop(args) if args.reference_loop else forest(args) if args.forest else
+                     hmm(args) if args.hmm else gpu(args)))
 
 
 if __name__ == "__main__":
