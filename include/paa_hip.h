@@ -353,6 +353,39 @@ int paa_debug_hmm_dev_decode_f64(const void *handle, const double *d_feats, int 
                                  const int64_t *offsets, int64_t n_seq, int32_t *d_states, double *d_logprob,
                                  int64_t block_rows);
 
+/* ---- audioSegmentation.speaker_diarization (audioSegmentation.py:815-1056, lda_dim = 0) -----------------------------------
+ * The clustering between the mid-term matrix and the HMM smoothing; every matrix is a device buffer, feature-major
+ * [n_dims][ld] (n_dims 1..256), window t in column t; the small results are host arrays and every call is synchronous.
+ * standardize: scikit-learn's StandardScaler over the windows (population variance; a constant row gets scale 1); d_z has the
+ * layout of d_feats, stats [3][n_dims] = mean, variance, scale.  select_rows: d_out [n_rows][n_vec] = the rows `rows` of d_z.
+ * dim_distances: the reference's pdist(X.T) -- Euclidean distances between the n_dims FEATURE ROWS -- over the windows with
+ * d_labels[i][t] == c for every sweep entry i < nk and cluster c < ks[i] (d_labels [nk][n_vec] on the device; null: all
+ * windows, ks and nk ignored): colsum [nk][kmax][n_dims] the column sums of the distance matrix, pair_mean [nk][kmax] the
+ * mean over the n_dims (n_dims - 1) / 2 pairs, kmax = max ks (1 without labels).
+ * kmeans: Lloyd's algorithm as scikit-learn 1.7's KMeans(init = centres, n_init = 1) runs it, for all nk cluster counts ks[i]
+ * (1..32, at most n_vec) at once: nearest centre in the difference form sum_d (z_d - c_d)^2, lowest index among equal
+ * minima; an empty cluster takes the window farthest from its centre; stop when no label changes, or the summed squared
+ * centre shift is <= tol, or after max_iter iterations (then one more assignment).  centers [nk][32][n_dims] holds the
+ * initial centres on entry and the final ones on return; d_labels [nk][n_vec] (device), n_iter [nk], inertia [nk].  Sums
+ * are reduced in a fixed order: two runs give identical bits.
+ * sqdist_points: out [n_pts][n_vec] = squared distances of every window to the windows idx[p] (n_pts <= 8): the distance work
+ * of k-means++ seeding.  get_points: out [n_pts][n_dims] = the windows idx[p].
+ * pair_sums: sums [nk][32][32], sums[i][c][c2] = the sum of |z_a - z_b| over windows a with label c and b with label c2 of
+ * sweep entry i, all entries in one pass over the window pairs (difference form, fixed-order reductions).               */
+int paa_diar_dev_standardize_f64(const double *d_feats, int n_dims, int64_t ld, int64_t n_vec, double *d_z, double *stats);
+int paa_diar_dev_select_rows_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *rows, int n_rows,
+                                 double *d_out);
+int paa_diar_dev_dim_distances_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *d_labels,
+                                   const int32_t *ks, int nk, double *colsum, double *pair_mean);
+int paa_diar_dev_sqdist_points_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int64_t *idx, int n_pts,
+                                   double *out);
+int paa_diar_dev_get_points_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int64_t *idx, int n_pts,
+                                double *out);
+int paa_diar_dev_kmeans_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *ks, int nk, double *centers,
+                            double tol, int max_iter, int32_t *d_labels, int32_t *n_iter, double *inertia);
+int paa_diar_dev_pair_sums_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *d_labels,
+                               const int32_t *ks, int nk, double *sums);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

@@ -130,6 +130,15 @@ _SIGNATURES = {
                                               c_f64p, c_f64p]),
     "paa_debug_hmm_dev_decode_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64,
                                                C.c_void_p, C.c_void_p, C.c_int64]),
+    "paa_diar_dev_standardize_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, c_f64p]),
+    "paa_diar_dev_select_rows_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i32p, C.c_int, C.c_void_p]),
+    "paa_diar_dev_dim_distances_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, c_i32p, C.c_int, c_f64p,
+                                                 c_f64p]),
+    "paa_diar_dev_sqdist_points_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int, c_f64p]),
+    "paa_diar_dev_get_points_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int, c_f64p]),
+    "paa_diar_dev_kmeans_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i32p, C.c_int, c_f64p, C.c_double,
+                                          C.c_int, C.c_void_p, c_i32p, c_f64p]),
+    "paa_diar_dev_pair_sums_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, c_i32p, C.c_int, c_f64p]),
     "paa_comm_unique_id": (C.c_int, [C.c_void_p]),
     "paa_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "paa_comm_destroy": (C.c_int, []),

@@ -14,8 +14,9 @@ features and the similarity matrix in HBM: only the filtered matrix it returns c
 audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744-748) by one kernel over all frames
 (svm_onset_probability).  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
 hmm_segmentation, :287-492) runs on the GPU as well: class GaussianHmm stands in for hmmlearn's GaussianHMM (hmmlearn is not
-needed, also not to read a model file the reference wrote).  The rest of audioSegmentation (diarisation, plotting) is out
-of scope (control plane / third-party models).
+needed, also not to read a model file the reference wrote).  Speaker diarization (speaker_diarization, diarize_features,
+evaluate_speaker_diarization, speaker_diarization_evaluation, :251-284, :815-1090) runs its standardisation, k-means sweep and
+silhouettes on the GPU as well; its LDA branch (lda_dim > 0) is not ported.
 """
 import ctypes as C
 
@@ -805,3 +806,347 @@ def hmm_segmentation(audio_file, hmm_model_name, plot_results=False, gt_file="")
     sampling_rate, signal = audioBasicIO.read_audio_file(audio_file)
     hmm, class_names, mid_window, mid_step = load_hmm(hmm_model_name)
     return hmm_segmentation_signal(signal, sampling_rate, hmm, class_names, mid_window, mid_step, plot_results, gt_file)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# speaker diarization (reference :251-284, :815-1090; the LDA branch is not ported)
+# ---------------------------------------------------------------------------------------------------------
+DIAR_MODELS_ENV = "PAA_DIAR_MODELS"                  # directory that holds the two speaker SVM files
+DIAR_MODEL_FILES = ("svm_rbf_speaker_10", "svm_rbf_speaker_male_female")
+_DIAR_MAX_K = 32
+_DIAR_MAX_DIMS = 256
+
+
+def evaluate_speaker_diarization(labels, labels_gt):
+    """(cluster purity, speaker purity) of fix-sized cluster labels against ground-truth labels (reference :251-284): both
+    sequences are cut to the shorter one; every cluster (speaker) scores the share of its windows that fall into its most
+    frequent speaker (cluster), and the scores are averaged with the cluster (speaker) sizes as weights."""
+    labels, labels_gt = np.asarray(labels), np.asarray(labels_gt)
+    n = min(labels.shape[0], labels_gt.shape[0])
+    _, mine = np.unique(labels[:n], return_inverse=True)
+    _, truth = np.unique(labels_gt[:n], return_inverse=True)
+    table = np.zeros((mine.max() + 1 if n else 0, truth.max() + 1 if n else 0))
+    np.add.at(table, (mine, truth), 1.0)
+    per_cluster, per_speaker = table.sum(axis=1), table.sum(axis=0)
+    purity_cluster_m = np.sum(table.max(axis=1) / per_cluster * per_cluster) / table.sum()
+    purity_speaker_m = np.sum(table.max(axis=0) / per_speaker * per_speaker) / table.sum()
+    return purity_cluster_m, purity_speaker_m
+
+
+def _diar_seed(d_zk, dims, n, k, rs):
+    """Greedy k-means++ (2 + int(ln k) candidates per step): the k initial centres [k][dims].  All distance work runs on the
+    device (paa_diar_dev_sqdist_points_f64); the draws -- rs.randint for the first centre, rs.uniform * potential looked up in
+    the cumulative sum of the closest squared distances afterwards -- and the O(n) bookkeeping stay on the host."""
+    lib = _ffi.lib()
+    trials = 2 + int(np.log(k))
+    chosen = [int(rs.randint(n))]
+    first = np.array(chosen, dtype=np.int64)
+    closest = np.empty((1, n))
+    _ffi.check(lib.paa_diar_dev_sqdist_points_f64(d_zk.ptr, dims, n, n, _ffi.as_i64p(first), 1, _ffi.as_f64p(closest)))
+    closest = closest[0]
+    for _ in range(1, k):
+        vals = rs.uniform(size=trials) * closest.sum()
+        cand = np.ascontiguousarray(np.minimum(np.searchsorted(np.cumsum(closest), vals), n - 1), dtype=np.int64)
+        d2 = np.empty((trials, n))
+        _ffi.check(lib.paa_diar_dev_sqdist_points_f64(d_zk.ptr, dims, n, n, _ffi.as_i64p(cand), trials, _ffi.as_f64p(d2)))
+        new = np.minimum(closest[None, :], d2)
+        best = int(np.argmin(new.sum(axis=1)))
+        chosen.append(int(cand[best]))
+        closest = new[best]
+    idx = np.array(chosen, dtype=np.int64)
+    centers = np.empty((k, dims))
+    _ffi.check(lib.paa_diar_dev_get_points_f64(d_zk.ptr, dims, n, n, _ffi.as_i64p(idx), k, _ffi.as_f64p(centers)))
+    return centers
+
+
+def _diar_silhouette(n, k, labels, a_mean, pair_sum):
+    # reference :949-985 from the per-cluster pdist means and the cluster-pair distance sums
+    count = np.bincount(labels, minlength=k).astype(np.float64)
+    share = count / float(n)
+    a, b = np.zeros(k), np.zeros(k)
+    for c in range(k):
+        if share[c] < 0.020:
+            continue
+        a[c] = a_mean[c] * share[c]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            b[c] = min(pair_sum[c, c2] / (count[c] * count[c2]) * (share[c] + share[c2]) / 2.0 for c2 in range(k) if c2 != c)
+    sil = np.array([(b[c] - a[c]) / (max(b[c], a[c]) + 1e-5) for c in range(k)])
+    return a, b, sil
+
+
+def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, init_centers=None, max_iter=300, tol=1e-4):
+    """Steps 3-6 of diarize_features on a device-resident matrix (DeviceBuffer of [n_dims][n] doubles).  Returns (details, d_z):
+    the details dict of diarize_features without the HMM entries, and the DeviceBuffer of the standardised, UNFILTERED
+    matrix [n_dims][n] (the caller frees it)."""
+    lib = _ffi.lib()
+    ks = list(range(2, 10)) if n_speakers <= 0 else [int(n_speakers)]
+    if n < 1 or n_dims < 1 or n_dims > _DIAR_MAX_DIMS:
+        raise ValueError("feature matrix of %d dims x %d windows: 1..%d dims and at least one window" % (n_dims, n, _DIAR_MAX_DIMS))
+    if min(ks) < 1 or max(ks) > _DIAR_MAX_K:
+        raise ValueError("%d speakers: 1..%d clusters are supported" % (ks[0], _DIAR_MAX_K))
+    if n < max(ks):
+        raise ValueError("%d windows are fewer than %d clusters" % (n, max(ks)))
+    bufs = []
+    d_z = _ffi.DeviceBuffer(n_dims * n * 8)
+    try:
+        stats = np.empty((3, n_dims))
+        _ffi.check(lib.paa_diar_dev_standardize_f64(d_m.ptr, n_dims, n, n, d_z.ptr, _ffi.as_f64p(stats)))
+        colsum, pmean = np.empty(n_dims), np.empty(1)
+        _ffi.check(lib.paa_diar_dev_dim_distances_f64(d_z.ptr, n_dims, n, n, None, None, 0, _ffi.as_f64p(colsum), _ffi.as_f64p(pmean)))
+        kept = np.nonzero(colsum < 1.1 * np.mean(colsum))[0]
+        if kept.shape[0] < 1:
+            raise ValueError("no feature dimension passes the reference's distance filter (a single dimension never does)")
+        dims = int(kept.shape[0])
+        rows = np.ascontiguousarray(kept, dtype=np.int32)
+        d_zk = _ffi.DeviceBuffer(dims * n * 8)
+        bufs.append(d_zk)
+        _ffi.check(lib.paa_diar_dev_select_rows_f64(d_z.ptr, n_dims, n, n, rows.ctypes.data_as(_ffi.c_i32p), dims, d_zk.ptr))
+        # tol of scikit-learn: 1e-4 * mean(var(Zk, axis=0)); a standardised row has variance var / scale^2
+        tol_abs = tol * float(np.mean(stats[1, kept] / stats[2, kept] ** 2))
+        rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+        nk = len(ks)
+        centers = np.zeros((nk, _DIAR_MAX_K, dims))
+        for i, k in enumerate(ks):
+            if init_centers is not None and k in init_centers:
+                init = np.asarray(init_centers[k], dtype=np.float64)
+                if init.shape != (k, dims):
+                    raise ValueError("init_centers[%d] has shape %s, %s expected" % (k, init.shape, (k, dims)))
+                centers[i, :k] = init
+            else:
+                centers[i, :k] = _diar_seed(d_zk, dims, n, k, rs)
+        ks_arr = np.array(ks, dtype=np.int32)
+        ks_p = ks_arr.ctypes.data_as(_ffi.c_i32p)
+        d_labels = _ffi.DeviceBuffer(nk * n * 4)
+        bufs.append(d_labels)
+        n_iter, inertia = np.zeros(nk, dtype=np.int32), np.empty(nk)
+        _ffi.check(lib.paa_diar_dev_kmeans_f64(d_zk.ptr, dims, n, n, ks_p, nk, _ffi.as_f64p(centers), tol_abs, int(max_iter),
+                                               d_labels.ptr, n_iter.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(inertia)))
+        labels = d_labels.to_host(np.int32, nk * n).reshape(nk, n).astype(np.int64)
+        kmax = max(ks)
+        a_mean = np.empty((nk, kmax))
+        a_cols = np.empty((nk, kmax, dims))
+        _ffi.check(lib.paa_diar_dev_dim_distances_f64(d_zk.ptr, dims, n, n, d_labels.ptr, ks_p, nk, _ffi.as_f64p(a_cols),
+                                                      _ffi.as_f64p(a_mean)))
+        pair = np.empty((nk, _DIAR_MAX_K, _DIAR_MAX_K))
+        _ffi.check(lib.paa_diar_dev_pair_sums_f64(d_zk.ptr, dims, n, n, d_labels.ptr, ks_p, nk, _ffi.as_f64p(pair)))
+        details = {"kept_dims": kept, "dim_colsum": colsum, "mean": stats[0], "var": stats[1], "scale": stats[2], "ks": ks,
+                   "labels": {}, "centers": {}, "n_iter": {}, "inertia": {}, "sil_a": {}, "sil_b": {}, "sil": {}, "pair_sums": {}}
+        scores = []
+        for i, k in enumerate(ks):
+            a, b, sil = _diar_silhouette(n, k, labels[i], a_mean[i], pair[i])
+            details["labels"][k] = labels[i]
+            details["centers"][k] = centers[i, :k].copy()
+            details["n_iter"][k] = int(n_iter[i])
+            details["inertia"][k] = float(inertia[i])
+            details["sil_a"][k], details["sil_b"][k], details["sil"][k] = a, b, sil
+            details["pair_sums"][k] = pair[i, :k, :k].copy()
+            scores.append(np.mean(sil))
+        details["scores"] = np.array(scores)
+        details["imax"] = int(np.argmax(scores))
+    except BaseException:
+        d_z.free()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+    return details, d_z
+
+
+def _diarize_device(d_m, n_dims, n, n_speakers, random_state, init_centers, return_details):
+    details, d_z = diarize_clusters_device(d_m, n_dims, n, n_speakers, random_state=random_state, init_centers=init_centers)
+    try:
+        last = details["labels"][details["ks"][-1]]
+        # the reference trains the HMM on the labels its loop variable holds when the sweep ends: the LAST k, not imax
+        priors, trans, means, cov = train_hmm_compute_statistics_device(d_z, n_dims, n, n, last)
+        _, states = GaussianHmm(priors, trans, means, cov).predict_device(d_z, n, n)
+    finally:
+        d_z.free()
+    padded = np.concatenate((np.zeros(2), states.astype(np.float64), np.zeros(2)))
+    cls = np.median(np.stack([padded[i:i + n] for i in range(5)]), axis=0)        # scipy.signal.medfilt(states, 5)
+    if return_details:
+        details["hmm_states"] = states
+        return cls, details
+    return cls
+
+
+def diarize_features(M, n_speakers, *, random_state=None, init_centers=None, return_details=False):
+    """Steps 3-8 of the reference's speaker_diarization (:860-1012, lda_dim = 0) on a (n_dims x n_windows) matrix of mid-term
+    features and SVM probabilities, on the host or in a DeviceBuffer given as (buffer, n_dims, n_windows):
+
+      standardise over the windows (StandardScaler); keep the feature DIMENSIONS whose summed distance to the other
+      dimensions is below 1.1 times the mean (the reference's "outlier removal" acts on dimensions, windows are never
+      removed); k-means for k = 2..9 (or n_speakers when > 0), one initialisation each, from init_centers[k] ([k][kept
+      dims]) or greedy k-means++ seeded from numpy.random.RandomState(random_state); the reference's silhouette per k
+      and imax = its first maximum; then HMM smoothing (training statistics of the UNFILTERED standardised matrix and
+      Viterbi) and a 5-tap median filter (zero-padded).
+
+    As in the reference the HMM is trained on the labels of the LAST k tried (k = 9 when n_speakers <= 0), not on those of
+    imax; imax only tells how many speakers the silhouette prefers.  A k whose k-means left a cluster without windows
+    raises IndexError there, as train_hmm_compute_statistics does; a feature row that is constant over a cluster gives a
+    zero deviation, which the HMM refuses (ValueError).  Returns the filtered labels (float64) and, with return_details,
+    a dict: kept_dims, ks, per k labels / centers / n_iter / inertia / sil_a / sil_b / sil / pair_sums, scores, imax,
+    hmm_states (before the median filter)."""
+    if isinstance(M, tuple):
+        d_m, n_dims, n = M
+        return _diarize_device(d_m, int(n_dims), int(n), n_speakers, random_state, init_centers, return_details)
+    F = np.ascontiguousarray(np.asarray(M, dtype=np.float64))
+    if F.ndim != 2 or F.shape[1] < 1:
+        raise ValueError("M must be a (n_dims x n_windows) matrix with at least one window")
+    d_m = _ffi.DeviceBuffer.from_host(F)
+    try:
+        return _diarize_device(d_m, F.shape[0], F.shape[1], n_speakers, random_state, init_centers, return_details)
+    finally:
+        d_m.free()
+
+
+def _diar_models(models, models_dir=None):
+    """The 10-speaker and the male / female SVM as load_model 9-tuples: given, or read from two paths, or from the files
+    DIAR_MODEL_FILES of `models_dir` / the directory the environment variable PAA_DIAR_MODELS names."""
+    import os
+    from . import audioTrainTest
+    if models is None:
+        folder = models_dir or os.environ.get(DIAR_MODELS_ENV)
+        if not folder:
+            raise FileNotFoundError("speaker_diarization needs the SVM models %s and %s: pass models=, models_dir= or set %s to "
+                                    "the directory that holds them (the package ships no model files)"
+                                    % (DIAR_MODEL_FILES + (DIAR_MODELS_ENV,)))
+        models = tuple(os.path.join(folder, name) for name in DIAR_MODEL_FILES)
+    if len(models) != 2:
+        raise ValueError("models must be the pair (10-speaker SVM, male / female SVM)")
+    out = []
+    for m in models:
+        if isinstance(m, (str, bytes, os.PathLike)):
+            for path in (m, str(m) + "MEANS"):
+                if not os.path.isfile(path):
+                    raise FileNotFoundError("speaker diarization model file %s is missing" % path)
+            m = audioTrainTest.load_model(m)
+        out.append(m)
+    return out
+
+
+def speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=0, *,
+                               models=None, models_dir=None, random_state=None, init_centers=None, return_details=False):
+    """Steps 1-8 of speaker_diarization on an array: mid-term features (short window and step round(fs * 0.05); short_window
+    only matters to the LDA branch), the probabilities of the two speaker SVMs + 1e-4 below them, then diarize_features -- the
+    matrix never leaves the device.  models: see speaker_diarization."""
+    from . import MidTermFeatures, audioTrainTest
+    if lda_dim > 0:
+        raise NotImplementedError("the LDA branch of speaker_diarization (lda_dim > 0) is not ported")
+    loaded = _diar_models(models, models_dir)
+    svcs = [(audioTrainTest.svc_model(m[0]), np.asarray(m[1], dtype=np.float64), np.asarray(m[2], dtype=np.float64)) for m in loaded]
+    st = round(sampling_rate * 0.05)
+    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st, st)
+    if step_ratio < 1:
+        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
+    signal = audioBasicIO.stereo_to_mono(signal)
+    kind, sig = _ffi.classify_signal(signal)
+    n = sig.shape[0]
+    window = step = int(st)
+    if window < 1 or n < window:
+        raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
+    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
+    bufs = []
+    try:
+        d_in = _ffi.DeviceBuffer.from_host(sig)
+        bufs.append(d_in)
+        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
+        bufs.append(d_st)
+        plan.execute(d_in, d_st)
+        n_mid = plan.mid_doubles(step_ratio)
+        rows = 2 * 68
+        M = n_mid // rows
+        extra = sum(len(s[0].classes) for s in svcs)
+        d_all = _ffi.DeviceBuffer((rows + extra) * M * 8)          # mid-term rows, then the probability rows
+        bufs.append(d_all)
+        plan.mid_execute(d_st, ratio, step_ratio, d_all)
+        at = rows
+        for model, mean, std in svcs:
+            _, proba = model.predict_device(d_all, M, M, mean, std)
+            block = np.ascontiguousarray(proba.T + 1e-4)
+            _ffi.check(_ffi.lib().paa_memcpy_h2d(C.c_void_p(d_all.ptr.value + at * M * 8), block.ctypes.data_as(C.c_void_p),
+                                                 block.nbytes))
+            at += block.shape[0]
+        return _diarize_device(d_all, rows + extra, M, n_speakers, random_state, init_centers, return_details)
+    finally:
+        for b in bufs:
+            b.free()
+        plan.destroy()
+
+
+def _plot_diarization(cls, n_classes, duration, mid_step, flags_gt, purities, n_speakers, scores):
+    import matplotlib.pyplot as plt
+    names = ["speaker{0:d}".format(c) for c in range(n_classes)]
+    fig = plt.figure()
+    ax1 = fig.add_subplot(111 if n_speakers > 0 else 211)
+    ax1.set_yticks(np.arange(len(names)))
+    ax1.axis((0, duration, -1, len(names)))
+    ax1.set_yticklabels(names)
+    ax1.plot(np.arange(len(cls)) * mid_step + mid_step / 2.0, cls)
+    if flags_gt is not None:
+        ax1.plot(np.arange(len(flags_gt)) * mid_step + mid_step / 2.0, flags_gt, 'r')
+        plt.title("Cluster purity: {0:.1f}% - Speaker purity: {1:.1f}%".format(100 * purities[0], 100 * purities[1]))
+    plt.xlabel("time (seconds)")
+    if n_speakers <= 0:
+        plt.subplot(212)
+        plt.plot(list(range(2, 10)), scores)
+        plt.xlabel("number of clusters")
+        plt.ylabel("average clustering's sillouette")
+    plt.show()
+
+
+def speaker_diarization(filename, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=0, plot_res=False, *,
+                        models=None, models_dir=None, random_state=None, init_centers=None):
+    """Speaker diarization of a WAV file (reference :815-1056, lda_dim = 0 only): returns (cls, purity_cluster_m,
+    purity_speaker_m) -- the label of every mid-term window (float64) and, when <filename>.segments exists next to the file,
+    the cluster and speaker purity against it (printed as the reference prints them), else -1, -1.
+
+    n_speakers <= 0 sweeps k = 2..9.  As in the reference the returned labels come from the k-means of the LAST k tried,
+    smoothed by an HMM and a median filter (see diarize_features); the silhouette's choice only sets the number of class
+    names of the plot.  models: the pair (10-speaker SVM, male / female SVM) as load_model 9-tuples or as two paths; None
+    reads svm_rbf_speaker_10 and svm_rbf_speaker_male_female (and their MEANS files) from models_dir or the directory
+    named by the environment variable PAA_DIAR_MODELS -- FileNotFoundError says what is missing.  random_state seeds the
+    k-means++ initialisation (the reference leaves it unseeded); init_centers {k: [k][kept dims]} replaces it."""
+    import os
+    if lda_dim > 0:
+        raise NotImplementedError("the LDA branch of speaker_diarization (lda_dim > 0) is not ported")
+    loaded = _diar_models(models, models_dir)
+    sampling_rate, signal = audioBasicIO.read_audio_file(filename)
+    signal = audioBasicIO.stereo_to_mono(signal)
+    duration = len(signal) / sampling_rate
+    cls, details = speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window, mid_step, short_window, lda_dim,
+                                              models=loaded, random_state=random_state, init_centers=init_centers,
+                                              return_details=True)
+    purities = (-1, -1)
+    flags_gt = None
+    gt_file = filename.replace('.wav', '.segments')
+    if os.path.isfile(gt_file):
+        seg_start, seg_end, seg_labs = read_segmentation_gt(gt_file)
+        flags_gt, _ = segments_to_labels(seg_start, seg_end, seg_labs, mid_step)
+        purities = evaluate_speaker_diarization(cls, flags_gt)
+        print("{0:.1f}\t{1:.1f}".format(100 * purities[0], 100 * purities[1]))
+    if plot_res:
+        _plot_diarization(cls, details["ks"][details["imax"]], duration, mid_step, flags_gt, purities, n_speakers,
+                          details["scores"])
+    return cls, purities[0], purities[1]
+
+
+def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, models_dir=None, random_state=None):
+    """Prints the purities of every WAV file of a folder for every LDA dimension of the list (reference :1059-1090; only 0 is
+    supported): the number of speakers comes from the file's .segments ground truth (-1: unknown)."""
+    import glob
+    import os
+    wav_files = sorted(glob.glob(os.path.join(folder_name, '*.wav')))
+    loaded = _diar_models(models, models_dir)
+    num_speakers = []
+    for wav_file in wav_files:
+        gt_file = wav_file.replace('.wav', '.segments')
+        if os.path.isfile(gt_file):
+            _, _, seg_labs = read_segmentation_gt(gt_file)
+            num_speakers.append(len(set(seg_labs)))
+        else:
+            num_speakers.append(-1)
+    for dim in lda_dimensions:
+        print("LDA = {0:d}".format(dim))
+        for i, wav_file in enumerate(wav_files):
+            speaker_diarization(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
+                                random_state=random_state)

@@ -82,6 +82,15 @@ struct Segment {
     int first, last;
 };
 }  // namespace hmm
+namespace diar {
+// k-means of one k of a sweep (kernels_diar.hpp): written by finish_kernel, polled by the host after every iteration
+struct KmState {
+    int done, strict, n_iter, n_empty;
+    double shift;
+};
+constexpr int kMaxPoints = 8;                         // candidate windows per sqdist_points_kernel launch
+constexpr int kIntsPerK = hmm::kMaxStates + 1;      // cluster sizes and the number of changed labels of one assignment
+}  // namespace diar
 namespace launch {
 
 // kernels_fast.hpp: window 800, step 400 / 800, int16
@@ -155,6 +164,31 @@ int hmm_decode(const hmm::HmmDev &m, const double *d_loglik, const hmm::Segment 
 // means / stds [K][n_dims] (two kernels)
 int hmm_stats(const double *d_feats, long long ld, long long n_vec, const int *d_labels, int n_states, int n_dims,
               int *d_counts, double *d_means, double *d_stds, hipStream_t stream);
+// kernels_diar.hpp (speaker diarization); every matrix feature-major [n_dims][ld].  Z = StandardScaler of M, stats [3][n_dims]
+int diar_standardize(const double *d_M, long long ldm, long long n, int n_dims, double *d_Z, long long ldz, double *d_stats,
+                     hipStream_t stream);
+// out [n_rows][ldo] = the rows `d_rows` of Z
+int diar_select_rows(const double *d_Z, long long ldz, long long n, const int *d_rows, int n_rows, double *d_out, long long ldo,
+                     hipStream_t stream);
+// distances between feature rows over the windows labelled c of sweep entry kidx (d_labels [nk][n]; null: all windows, nk =
+// kmax = 1): dist [nk][kmax][D][D] (scratch), colsum [nk][kmax][D], pmean [nk][kmax]
+int diar_dim_distances(const double *d_Z, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk, int kmax,
+                       double *d_dist, double *d_colsum, double *d_pmean, hipStream_t stream);
+// one Lloyd iteration of every unfinished k (ints [nk][33] is zeroed here), and the last pass (labels, d2, inertia [nk])
+int diar_kmeans_step(const double *d_Zk, long long ld, long long n, int D, const int *d_ks, int nk, int kmax, double *d_centers,
+                     diar::KmState *d_state, int *d_labels, double *d_d2, int *d_ints, double *d_sums, double tol, int max_iter,
+                     hipStream_t stream);
+int diar_kmeans_last(const double *d_Zk, long long ld, long long n, int D, const int *d_ks, int nk, int kmax, const double *d_centers,
+                     const diar::KmState *d_state, int *d_labels, double *d_d2, double *d_inertia, hipStream_t stream);
+int diar_sqdist_points(const double *d_Zk, long long ld, long long n, int D, const long long *d_idx, int n_pts, double *d_out,
+                       hipStream_t stream);
+int diar_get_points(const double *d_Zk, long long ld, int D, const long long *d_idx, int n_pts, double *d_out, hipStream_t stream);
+// cluster-pair distance sums of every k of a sweep in one pass: S [binoff[nk]] (per k: [K][K]); partial and stage are scratch
+// of diar_pair_tiles(n) * nbins and diar_pair_chunks(n) * nbins doubles
+long long diar_pair_tiles(long long n);
+long long diar_pair_chunks(long long n);
+int diar_pair_sums(const double *d_Zk, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk,
+                   const int *d_binoff, int nbins, double *d_partial, double *d_stage, double *d_S, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

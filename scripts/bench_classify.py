@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Measure the SVM, kNN and tree-ensemble classification paths (not part of bench.py).
 
+    python scripts/bench_classify.py --diar                # GPU: speaker diarization (k-means sweep, silhouettes; DESIGN K11)
     python scripts/bench_classify.py --hmm                 # GPU: the HMM segmenter (emission + Viterbi)
     python scripts/bench_classify.py                       # GPU: SVC and kNN kernel rates per shipped model, 1 h clip end
                                                            # to end
@@ -237,6 +238,112 @@ def hmm(args):
     return out
 
 
+def event_time(fn, reps):
+    """Median device time in seconds between two events on the library stream around fn() (one warm-up call first)."""
+    import ctypes
+    from pyaudioanalysis_amd import _ffi
+    lib = _ffi.lib()
+    fn()
+    ts = []
+    for _ in range(reps):
+        ms = ctypes.c_float()
+        _ffi.check(lib.paa_timer_start())
+        fn()
+        _ffi.check(lib.paa_timer_stop(ctypes.byref(ms)))
+        ts.append(ms.value * 1e-3)
+    return float(np.median(ts))
+
+
+def planted_speakers(n, d, speakers, seed, dwell=40):
+    """(M [d][n], speaker of every window): Gaussian speakers that change about every `dwell` windows."""
+    rng = np.random.default_rng(seed)
+    means = rng.standard_normal((speakers, d)) * 1.5
+    path = np.empty(n, dtype=np.int64)
+    s = 0
+    for t in range(n):
+        if t % dwell == 0:
+            s = int(rng.integers(speakers))
+        path[t] = s
+    return np.ascontiguousarray((means[path] + rng.standard_normal((n, d))).T), path
+
+
+FP64_VECTOR_PEAK = 78.6e12        # MI355X data sheet, FP64 vector, FMA = 2 flop
+
+
+def diar(args):
+    """Speaker diarization at N = 36 000 windows x 148 dims (one hour at the default 0.1 s step): the cluster-pair kernel alone
+    (all k = 2..9 in one pass, and one k), the k = 2..9 sweep (steps 3-6, device-resident input), diarize_features host to
+    host, speaker_diarization_signal on the 1-hour clip with seeded SVMs of the shipped shapes, and the reference-side step
+    6 (cdist blocks) on one core at a smaller N.  Runs on the GPU."""
+    import ctypes
+    from scipy.spatial import distance
+    from pyaudioanalysis_amd import _ffi, audioSegmentation, audioTrainTest
+    _ffi.init(0)
+    lib = _ffi.lib()
+    N, D = args.diar_windows, 148
+    out = {"diar_windows": N, "diar_dims": D}
+    M, path = planted_speakers(N, D, 6, 17)
+    ks = np.arange(2, 10, dtype=np.int32)
+    labels = np.stack([path % k for k in ks]).astype(np.int32)
+    d_m, d_l = _ffi.DeviceBuffer.from_host(M), _ffi.DeviceBuffer.from_host(labels)
+    S = np.empty((len(ks), 32, 32))
+
+    def pair(nk):
+        _ffi.check(lib.paa_diar_dev_pair_sums_f64(d_m.ptr, D, N, N, ctypes.c_void_p(d_l.ptr.value + (len(ks) - nk) * N * 4),
+                                                  ks[len(ks) - nk:].ctypes.data_as(_ffi.c_i32p), nk, _ffi.as_f64p(S)))
+    tiles = ((N + 127) // 128) * ((N + 127) // 128 + 1) // 2
+    flop = 3.0 * tiles * 128 * 128 * D            # a subtraction and a fused multiply-add per pair and dimension
+    for nk, name in ((8, "pair_all_k_s"), (1, "pair_one_k_s")):
+        t = event_time(lambda: pair(nk), args.reps)
+        out[name] = t
+        out[name.replace("_s", "_fp64_share_of_vector_peak")] = flop / t / FP64_VECTOR_PEAK
+    out["pair_fp64_flop"] = flop
+    out["pair_algorithmic_bytes"] = N * D * 8 + len(ks) * N * 4
+    out["pair_panel_bytes_requested"] = tiles * 2 * 128 * D * 8          # what the tiles load (served by L2 / HBM: not measured)
+    out["pair_partial_bytes_written"] = tiles * int((ks.astype(np.int64) ** 2).sum()) * 8
+    d_l.free()
+    out["sweep_device_s"] = median_time(lambda: audioSegmentation.diarize_clusters_device(d_m, D, N, 0, random_state=3)[1].free(),
+                                        max(1, args.reps // 4))
+    det, d_z = audioSegmentation.diarize_clusters_device(d_m, D, N, 0, random_state=3)
+    d_z.free()
+    out["sweep_n_iter"] = {int(k): det["n_iter"][k] for k in det["ks"]}
+    d_m.free()
+    try:
+        out["diarize_features_host_s"] = median_time(lambda: audioSegmentation.diarize_features(M, 0, random_state=3),
+                                                     max(1, args.reps // 4))
+    except (ValueError, IndexError) as exc:          # a degenerate HMM of the k = 9 labels, as in the reference
+        out["diarize_features_host_s"] = "failed: %s" % exc
+    out["diarize_features_k6_host_s"] = median_time(lambda: audioSegmentation.diarize_features(M, 6, random_state=3),
+                                                    max(1, args.reps // 4))
+    # reference-side step 6 on one core: the cdist blocks of one k (N^2 D work: scale by (36 000 / n)^2 for the hour)
+    n = args.diar_reference_windows
+    Zs, ls = M[:, :n].T.copy(), path[:n] % 4
+    t0 = time.perf_counter()
+    for c in range(4):
+        for c2 in range(4):
+            if c != c2:
+                np.mean(distance.cdist(Zs[ls == c], Zs[ls == c2]))
+    out["reference_cdist_one_k_s"] = time.perf_counter() - t0
+    out["reference_cdist_windows"] = n
+    # one hour of audio, host to host, seeded SVMs of the shipped shapes
+    models = []
+    for n_support, seed in ((svc_libsvm.SPEAKER_10_N_SUPPORT, 3), ([120, 120], 4)):
+        m = svc_libsvm.synthetic_model(n_support, 136, seed)
+        clf = audioTrainTest.SvcArrays(m["support_vectors"], m["n_support"], m["dual_coef"], -m["rho"], m["prob_a"], m["prob_b"],
+                                       m["gamma"], "rbf", np.arange(len(m["n_support"]), dtype=np.float64))
+        models.append((clf, np.zeros(136), np.ones(136), ["c%d" % i for i in range(len(m["n_support"]))], 1.0, 0.1, 0.05, 0.05,
+                       False))
+    clip = one_hour_clip()
+    for n_speakers in (0, 4):
+        key = "one_hour_signal_s_n_speakers_%d" % n_speakers
+        try:
+            out[key] = median_time(lambda: audioSegmentation.speaker_diarization_signal(clip, 16000, n_speakers, models=models,
+                                                                                        random_state=3), 1)
+        except (ValueError, IndexError) as exc:
+            out[key] = "failed: %s" % exc
+    return out
+
+
 def reference_loop(args):
     import pickle
     import warnings
@@ -283,9 +390,12 @@ def main():
     ap.add_argument("--loop-windows", type=int, default=200)
     ap.add_argument("--forest", action="store_true", help="the tree-ensemble shapes only")
     ap.add_argument("--hmm", action="store_true", help="the HMM segmenter only")
+    ap.add_argument("--diar", action="store_true", help="speaker diarization only")
+    ap.add_argument("--diar-windows", type=int, default=36000)
+    ap.add_argument("--diar-reference-windows", type=int, default=6000)
     args = ap.parse_args()
     print(json.dumps(reference_loop(args) if args.reference_loop else forest(args) if args.forest else
-                     hmm(args) if args.hmm else gpu(args)))
+                     hmm(args) if args.hmm else diar(args) if args.diar else gpu(args)))
 
 
 if __name__ == "__main__":
