@@ -18,6 +18,7 @@ needed, also not to read a model file the reference wrote).  Speaker diarization
 evaluate_speaker_diarization, speaker_diarization_evaluation, :251-284, :815-1090) runs its standardisation, k-means sweep and
 silhouettes on the GPU as well; its LDA branch (lda_dim > 0) is not ported.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -393,48 +394,56 @@ def load_ground_truth(gt_file, labels, class_names, mid_step, plot_results):
     return labels_gt, class_names, accuracy, cm
 
 
-def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_step, st_win, st_step, model_type=None):
-    """Labels and max-probabilities of every mid-term window of a mono signal (reference :574-594): the mid-term matrix
-    stays in HBM and goes straight into the SVC, kNN or tree-ensemble kernels (one launch for all windows).  Returns
-    (labels, posterior max): an SVM's or tree ensemble's classes_, a kNN model's class indices.  model_type "knn", a
-    tree-ensemble type or an SVM type; None takes the model's kind (audioTrainTest.is_knn / is_forest)."""
-    from . import MidTermFeatures, audioTrainTest
-    ratio, step_ratio = MidTermFeatures._ratios(mt_win * sampling_rate, mid_step * sampling_rate,
-                                                round(sampling_rate * st_win), round(sampling_rate * st_step))
+def _mid_term_on_device(signal, sampling_rate, mid_window, mid_step, st_window_samples, st_step_samples, extra_rows=0):
+    """A context manager that yields (d_mid, M): the mid-term matrix of a mono signal left in HBM, a DeviceBuffer of
+    [136 + extra_rows][M] doubles whose first 136 rows are the features of the M mid-term windows.  The arguments are
+    tested at this call (every ValueError precedes any device work); the plan and the buffers are made when the with
+    block is entered and freed when it is left, whatever happened.  The short-term window and step come in samples, as
+    the caller rounds them."""
+    from . import MidTermFeatures
+    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st_window_samples,
+                                                st_step_samples)
     if step_ratio < 1:
         raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
-    window, step = int(round(sampling_rate * st_win)), int(round(sampling_rate * st_step))
+    window, step = int(st_window_samples), int(st_step_samples)
     kind, sig = _ffi.classify_signal(signal)
     if kind == 2:
         raise ValueError("mono signal expected (audioBasicIO.stereo_to_mono first)")
     n = sig.shape[0]
     if window < 1 or step < 1 or n < window:
         raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
-    if model_type is None:
-        model_type = "knn" if audioTrainTest.is_knn(classifier) else \
-            "randomforest" if audioTrainTest.is_forest(classifier) else "svm_rbf"
-    knn = model_type == "knn"
-    if knn:
-        model = audioTrainTest.knn_model(classifier)
-    elif model_type in audioTrainTest._FOREST_TYPES:
-        model = audioTrainTest.forest_model(classifier)
-    else:
-        model = audioTrainTest.svc_model(classifier)
-    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
-    try:
-        d_in = _ffi.DeviceBuffer.from_host(sig)
-        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
-        plan.execute(d_in, d_st)
-        n_mid = plan.mid_doubles(step_ratio)
-        d_mid = _ffi.DeviceBuffer(n_mid * 8)
-        plan.mid_execute(d_st, ratio, step_ratio, d_mid)
-        M = n_mid // (2 * 68)
+
+    @contextlib.contextmanager
+    def on_device():
+        plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
+        bufs = []
+        try:
+            bufs.append(_ffi.DeviceBuffer.from_host(sig))
+            bufs.append(_ffi.DeviceBuffer(plan.out_doubles * 8))
+            plan.execute(bufs[0], bufs[1])
+            n_mid = plan.mid_doubles(step_ratio)
+            M = n_mid // (2 * 68)
+            bufs.append(_ffi.DeviceBuffer((n_mid + extra_rows * M) * 8))
+            plan.mid_execute(bufs[1], ratio, step_ratio, bufs[2])
+            yield bufs[2], M
+        finally:
+            for b in bufs:
+                b.free()
+            plan.destroy()
+    return on_device()
+
+
+def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_step, st_win, st_step, model_type=None):
+    """Labels and max-probabilities of every mid-term window of a mono signal (reference :574-594): the mid-term matrix
+    stays in HBM and goes straight into the SVC, kNN or tree-ensemble kernels (one launch for all windows).  Returns
+    (labels, posterior max): an SVM's or tree ensemble's classes_, a kNN model's class indices.  model_type "knn", a
+    tree-ensemble type or an SVM type; None takes the model's kind (audioTrainTest.is_knn / is_forest)."""
+    from . import audioTrainTest
+    mid = _mid_term_on_device(signal, sampling_rate, mt_win, mid_step, round(sampling_rate * st_win), round(sampling_rate * st_step))
+    model = audioTrainTest.device_model(classifier, model_type)
+    with mid as (d_mid, M):
         idx, proba = model.predict_device(d_mid, M, M, mean, std)
-        for b in (d_in, d_st, d_mid):
-            b.free()
-    finally:
-        plan.destroy()
-    return (idx if knn else model.classes[idx]), np.max(proba, axis=1)
+    return model.labels(idx), np.max(proba, axis=1)
 
 
 def mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step,
@@ -473,12 +482,7 @@ def mid_term_file_classification(input_file, model_name, model_type, plot_result
         return labels, class_names, accuracy, cm
     if model_type not in ("svm", "svm_rbf", "knn") + audioTrainTest._FOREST_TYPES:
         raise NotImplementedError("model type %r: the GPU path serves the SVM, kNN and tree-ensemble models" % (model_type,))
-    if model_type == "knn":
-        classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step, compute_beat = \
-            audioTrainTest.load_model_knn(model_name)
-    else:
-        classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step, compute_beat = \
-            audioTrainTest.load_model(model_name)
+    classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step, compute_beat = audioTrainTest._load(model_name, model_type)
     if compute_beat:
         print("Model " + model_name + " contains long-term music features (beat etc) and cannot be used in segmentation")
         return labels, class_names, accuracy, cm
@@ -760,37 +764,12 @@ def train_hmm_from_directory(folder_path, hmm_model_name, mid_window, mid_step):
 def hmm_labels(signal, sampling_rate, hmm, mid_window, mid_step):
     """hmm.predict of every mid-term window of a signal (reference :472-481): the mid-term matrix stays in HBM and goes
     straight into the emission and Viterbi kernels; only the labels come back."""
-    from . import MidTermFeatures
     hmm = as_gaussian_hmm(hmm)
     st = round(sampling_rate * 0.050)
-    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st, st)
-    if step_ratio < 1:
-        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
-    signal = audioBasicIO.stereo_to_mono(signal)
-    kind, sig = _ffi.classify_signal(signal)
-    n = sig.shape[0]
-    window = step = int(st)
-    if window < 1 or n < window:
-        raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
-    handle = hmm.handle                   # a model the library refuses fails before any feature work
-    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
-    bufs = []
-    try:
-        d_in = _ffi.DeviceBuffer.from_host(sig)
-        bufs.append(d_in)
-        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
-        bufs.append(d_st)
-        plan.execute(d_in, d_st)
-        n_mid = plan.mid_doubles(step_ratio)
-        d_mid = _ffi.DeviceBuffer(n_mid * 8)
-        bufs.append(d_mid)
-        plan.mid_execute(d_st, ratio, step_ratio, d_mid)
-        M = n_mid // (2 * 68)
+    mid = _mid_term_on_device(audioBasicIO.stereo_to_mono(signal), sampling_rate, mid_window, mid_step, st, st)
+    hmm.handle                            # a model the library refuses fails before any feature work
+    with mid as (d_mid, M):
         _, labels = hmm.predict_device(d_mid, M, M)
-    finally:
-        for b in bufs:
-            b.free()
-        plan.destroy()
     return labels
 
 
@@ -1029,37 +1008,15 @@ def speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window=1.0
     """Steps 1-8 of speaker_diarization on an array: mid-term features (short window and step round(fs * 0.05); short_window
     only matters to the LDA branch), the probabilities of the two speaker SVMs + 1e-4 below them, then diarize_features -- the
     matrix never leaves the device.  models: see speaker_diarization."""
-    from . import MidTermFeatures, audioTrainTest
+    from . import audioTrainTest
     if lda_dim > 0:
         raise NotImplementedError("the LDA branch of speaker_diarization (lda_dim > 0) is not ported")
     loaded = _diar_models(models, models_dir)
     svcs = [(audioTrainTest.svc_model(m[0]), np.asarray(m[1], dtype=np.float64), np.asarray(m[2], dtype=np.float64)) for m in loaded]
     st = round(sampling_rate * 0.05)
-    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st, st)
-    if step_ratio < 1:
-        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
-    signal = audioBasicIO.stereo_to_mono(signal)
-    kind, sig = _ffi.classify_signal(signal)
-    n = sig.shape[0]
-    window = step = int(st)
-    if window < 1 or n < window:
-        raise ValueError("need at least one array to concatenate")          # ShortTermFeatures.py:684
-    plan = _ffi.Plan(np.array([0, n], dtype=np.int64), sampling_rate, window, step, deltas=True, sample_kind=kind)
-    bufs = []
-    try:
-        d_in = _ffi.DeviceBuffer.from_host(sig)
-        bufs.append(d_in)
-        d_st = _ffi.DeviceBuffer(plan.out_doubles * 8)
-        bufs.append(d_st)
-        plan.execute(d_in, d_st)
-        n_mid = plan.mid_doubles(step_ratio)
-        rows = 2 * 68
-        M = n_mid // rows
-        extra = sum(len(s[0].classes) for s in svcs)
-        d_all = _ffi.DeviceBuffer((rows + extra) * M * 8)          # mid-term rows, then the probability rows
-        bufs.append(d_all)
-        plan.mid_execute(d_st, ratio, step_ratio, d_all)
-        at = rows
+    rows, extra = 2 * 68, sum(len(s[0].classes) for s in svcs)
+    with _mid_term_on_device(audioBasicIO.stereo_to_mono(signal), sampling_rate, mid_window, mid_step, st, st, extra) as (d_all, M):
+        at = rows                                   # the probability rows go below the mid-term rows
         for model, mean, std in svcs:
             _, proba = model.predict_device(d_all, M, M, mean, std)
             block = np.ascontiguousarray(proba.T + 1e-4)
@@ -1067,10 +1024,6 @@ def speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window=1.0
                                                  block.nbytes))
             at += block.shape[0]
         return _diarize_device(d_all, rows + extra, M, n_speakers, random_state, init_centers, return_details)
-    finally:
-        for b in bufs:
-            b.free()
-        plan.destroy()
 
 
 def _plot_diarization(cls, n_classes, duration, mid_step, flags_gt, purities, n_speakers, scores):

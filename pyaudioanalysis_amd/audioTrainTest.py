@@ -52,8 +52,101 @@ class SvcArrays:
         self.classes_ = np.asarray(classes)
 
 
-class SvcModel:
-    """A model uploaded to the device once (paa_svc_create); freed with the object."""
+def _stats(mean, std, n_dims):
+    mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
+    std = np.ascontiguousarray(np.asarray(std, dtype=np.float64).reshape(-1))
+    if mean.shape[0] != n_dims or std.shape[0] != n_dims:
+        raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], n_dims))
+    return mean, std
+
+
+class _DeviceModel:
+    """A model uploaded to the device once and freed with the object.  A subclass sets n_dims, n_classes and the handle
+    (_adopt) and names what differs: _family ("svc": paa_svc_predict_f64, paa_svc_dev_predict_f64, paa_svc_destroy),
+    _index_dtype of the indices it returns, _extra (attribute holding the row width, dtype, pointer type) of the optional
+    third output of its entry points, classes (None: callers get the class index itself) and _raise_invalid for the raw indices of a call."""
+    _index_dtype = np.int64
+    _extra = None
+    classes = None
+
+    def _adopt(self, handle):
+        self.handle = handle
+        self._finalizer = weakref.finalize(self, getattr(_ffi.lib(), "paa_%s_destroy" % self._family), handle)
+
+    def _raise_invalid(self, idx):
+        pass
+
+    def labels(self, idx):
+        """What the reference's classifier_wrapper returns for these indices: classes_ of an SVM or tree ensemble, a kNN's
+        class index."""
+        return idx if self.classes is None else self.classes[idx]
+
+    def predict(self, feats, mean, std, extra=False):
+        """feats [n_dims][n_vec] (feature-major) -> (indices [n_vec], probabilities [n_vec][n_classes]) of
+        (feats[:, v] - mean) / std, plus the third output [n_vec][width] when extra is true."""
+        F = np.ascontiguousarray(feats, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
+            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
+        mean, std = _stats(mean, std, self.n_dims)
+        n = F.shape[1]
+        idx = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, self.n_classes), dtype=np.float64)
+        third = np.empty((n, getattr(self, self._extra[0])), dtype=self._extra[1]) if extra else None
+        tail = () if self._extra is None else (third.ctypes.data_as(self._extra[2]) if extra else None,)
+        _ffi.check(getattr(_ffi.lib(), "paa_%s_predict_f64" % self._family)(
+            self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean), _ffi.as_f64p(std),
+            idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba), *tail))
+        self._raise_invalid(idx)
+        idx = idx.astype(self._index_dtype, copy=False)
+        return (idx, proba, third) if extra else (idx, proba)
+
+    def predict_device(self, d_feats, ld, n_vec, mean, std):
+        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
+        mean, std = _stats(mean, std, self.n_dims)
+        bufs = []
+        try:
+            bufs.append(_ffi.DeviceBuffer.from_host(np.concatenate([mean, std])))
+            bufs.append(_ffi.DeviceBuffer(max(4 * n_vec, 8)))
+            bufs.append(_ffi.DeviceBuffer(8 * n_vec * self.n_classes))
+            d_stats, d_idx, d_proba = bufs
+            _ffi.check(getattr(_ffi.lib(), "paa_%s_dev_predict_f64" % self._family)(
+                self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr, C.c_void_p(d_stats.ptr.value + 8 * self.n_dims),
+                d_idx.ptr, d_proba.ptr, *(() if self._extra is None else (None,))))
+            idx = d_idx.to_host(np.int32, n_vec)
+            proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
+        finally:
+            for b in bufs:
+                b.free()
+        self._raise_invalid(idx)
+        return idx.astype(self._index_dtype, copy=False), proba
+
+
+_uploaded = {}          # model class -> WeakKeyDictionary: classifier -> its device model
+
+
+def _device_model(cls, classifier):
+    """The device copy of a classifier (uploaded at the first use, kept while the classifier lives; an object that cannot
+    be weakly referenced or hashed is uploaded at every call)."""
+    if isinstance(classifier, cls):
+        return classifier
+    cache = _uploaded.setdefault(cls, weakref.WeakKeyDictionary())
+    try:
+        m = cache.get(classifier)
+    except TypeError:
+        m = None
+    if m is None:
+        m = cls(classifier)
+        try:
+            cache[classifier] = m
+        except TypeError:
+            pass
+    return m
+
+
+class SvcModel(_DeviceModel):
+    """A fitted SVC on the device (paa_svc_create)."""
+    _family = "svc"
+    _index_dtype = np.int32
 
     def __init__(self, classifier):
         kernel = str(getattr(classifier, "kernel", ""))
@@ -74,68 +167,16 @@ class SvcModel:
         self.n_classes = k
         self.n_dims = sv.shape[1]
         gamma = float(classifier._gamma) if kernel == "rbf" else 0.0
-        lib = _ffi.lib()
         handle = C.c_void_p()
-        _ffi.check(lib.paa_svc_create(_ffi.as_f64p(sv), sv.shape[0], sv.shape[1], n_support.ctypes.data_as(_ffi.c_i32p), k,
-                                      _ffi.as_f64p(coef), _ffi.as_f64p(rho), _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b),
-                                      _KERNEL_TYPES[kernel], gamma, C.byref(handle)))
-        self.handle = handle
-        self._finalizer = weakref.finalize(self, lib.paa_svc_destroy, handle)
-
-    def predict(self, feats, mean, std):
-        """feats [n_dims][n_vec] (feature-major) -> (label indices [n_vec], probabilities [n_vec][k]) of
-        (feats[:, v] - mean) / std."""
-        F = np.ascontiguousarray(feats, dtype=np.float64)
-        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
-            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
-        mean, std = self._stats(mean, std)
-        n = F.shape[1]
-        idx = np.empty(n, dtype=np.int32)
-        proba = np.empty((n, self.n_classes), dtype=np.float64)
-        _ffi.check(_ffi.lib().paa_svc_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
-                                                  _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba)))
-        return idx, proba
-
-    def predict_device(self, d_feats, ld, n_vec, mean, std):
-        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
-        mean, std = self._stats(mean, std)
-        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
-        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
-        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
-        _ffi.check(_ffi.lib().paa_svc_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
-                                                      C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr, d_proba.ptr))
-        idx = d_idx.to_host(np.int32, n_vec)
-        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
-        for b in (d_stats, d_idx, d_proba):
-            b.free()
-        return idx, proba
-
-    def _stats(self, mean, std):
-        mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
-        std = np.ascontiguousarray(np.asarray(std, dtype=np.float64).reshape(-1))
-        if mean.shape[0] != self.n_dims or std.shape[0] != self.n_dims:
-            raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], self.n_dims))
-        return mean, std
-
-
-_uploaded = weakref.WeakKeyDictionary()
+        _ffi.check(_ffi.lib().paa_svc_create(_ffi.as_f64p(sv), sv.shape[0], sv.shape[1], n_support.ctypes.data_as(_ffi.c_i32p), k,
+                                             _ffi.as_f64p(coef), _ffi.as_f64p(rho), _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b),
+                                             _KERNEL_TYPES[kernel], gamma, C.byref(handle)))
+        self._adopt(handle)
 
 
 def svc_model(classifier):
-    """The device copy of a fitted SVC (uploaded at the first use, kept while the classifier lives)."""
-    if isinstance(classifier, SvcModel):
-        return classifier
-    try:
-        m = _uploaded.get(classifier)
-    except TypeError:
-        m = None
-    if m is None:
-        m = SvcModel(classifier)
-        try:
-            _uploaded[classifier] = m
-        except TypeError:
-            pass
-    return m
+    """The device copy of a fitted SVC."""
+    return _device_model(SvcModel, classifier)
 
 
 def svm_predict(classifier, feats, mean, std):
@@ -145,10 +186,12 @@ def svm_predict(classifier, feats, mean, std):
     return m.classes[idx], proba
 
 
-class KnnModel:
-    """A kNN model uploaded to the device once (paa_knn_create); freed with the object.  Reads the classifier's features,
+class KnnModel(_DeviceModel):
+    """A kNN model on the device (paa_knn_create): callers get class indices.  Reads the classifier's features,
     labels and neighbors, as the reference's Knn.classify does: n_classes = the number of distinct labels, and a label
     that is not one of the integers 0..n_classes-1 is counted for no class."""
+    _family = "knn"
+    _extra = ("k", np.int32, _ffi.c_i32p)
 
     def __init__(self, classifier):
         train = np.ascontiguousarray(classifier.features, dtype=np.float64)
@@ -163,53 +206,14 @@ class KnnModel:
             labels[ok] = v[ok].astype(np.int32)
         self.k = int(classifier.neighbors)
         self.n_dims = train.shape[1]
-        lib = _ffi.lib()
         handle = C.c_void_p()
-        _ffi.check(lib.paa_knn_create(_ffi.as_f64p(train), labels.ctypes.data_as(_ffi.c_i32p), train.shape[0], self.n_dims,
-                                      self.n_classes, self.k, C.byref(handle)))
-        self.handle = handle
-        self._finalizer = weakref.finalize(self, lib.paa_knn_destroy, handle)
+        _ffi.check(_ffi.lib().paa_knn_create(_ffi.as_f64p(train), labels.ctypes.data_as(_ffi.c_i32p), train.shape[0], self.n_dims,
+                                             self.n_classes, self.k, C.byref(handle)))
+        self._adopt(handle)
 
     def predict(self, feats, mean, std, neighbors=False):
-        """feats [n_dims][n_vec] (feature-major) -> (class indices [n_vec], P [n_vec][n_classes]) of (feats[:, v] - mean) /
-        std, plus the neighbour indices [n_vec][k] in ascending (squared distance, index) when neighbors is true."""
-        F = np.ascontiguousarray(feats, dtype=np.float64)
-        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
-            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
-        mean, std = _stats(mean, std, self.n_dims)
-        n = F.shape[1]
-        idx = np.empty(n, dtype=np.int32)
-        proba = np.empty((n, self.n_classes), dtype=np.float64)
-        nb = np.empty((n, self.k), dtype=np.int32) if neighbors else None
-        _ffi.check(_ffi.lib().paa_knn_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
-                                                  _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba),
-                                                  nb.ctypes.data_as(_ffi.c_i32p) if neighbors else None))
-        if neighbors:
-            return idx.astype(np.int64), proba, nb
-        return idx.astype(np.int64), proba
-
-    def predict_device(self, d_feats, ld, n_vec, mean, std):
-        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
-        mean, std = _stats(mean, std, self.n_dims)
-        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
-        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
-        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
-        _ffi.check(_ffi.lib().paa_knn_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
-                                                      C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr, d_proba.ptr,
-                                                      None))
-        idx = d_idx.to_host(np.int32, n_vec)
-        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
-        for b in (d_stats, d_idx, d_proba):
-            b.free()
-        return idx.astype(np.int64), proba
-
-
-def _stats(mean, std, n_dims):
-    mean = np.ascontiguousarray(np.asarray(mean, dtype=np.float64).reshape(-1))
-    std = np.ascontiguousarray(np.asarray(std, dtype=np.float64).reshape(-1))
-    if mean.shape[0] != n_dims or std.shape[0] != n_dims:
-        raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], n_dims))
-    return mean, std
+        """_DeviceModel.predict; neighbors: also the neighbour indices [n_vec][k] in ascending (squared distance, index)."""
+        return super().predict(feats, mean, std, neighbors)
 
 
 class Knn:
@@ -228,29 +232,14 @@ class Knn:
         return idx[0], proba[0]
 
 
-_uploaded_knn = weakref.WeakKeyDictionary()
-
-
 def is_knn(classifier):
     """A kNN classifier: this package's Knn / KnnModel, or any object with the reference Knn's attributes."""
     return isinstance(classifier, (Knn, KnnModel)) or all(hasattr(classifier, a) for a in ("features", "labels", "neighbors"))
 
 
 def knn_model(classifier):
-    """The device copy of a kNN classifier (uploaded at the first use, kept while the classifier lives)."""
-    if isinstance(classifier, KnnModel):
-        return classifier
-    try:
-        m = _uploaded_knn.get(classifier)
-    except TypeError:
-        m = None
-    if m is None:
-        m = KnnModel(classifier)
-        try:
-            _uploaded_knn[classifier] = m
-        except TypeError:
-            pass
-    return m
+    """The device copy of a kNN classifier."""
+    return _device_model(KnnModel, classifier)
 
 
 def knn_predict(classifier, feats, mean, std):
@@ -290,14 +279,22 @@ def _load(model_name, model_type):
     return load_model_knn(model_name) if model_type == "knn" else load_model(model_name)
 
 
+def device_model(classifier, model_type=None):
+    """The device model that serves (classifier, model_type): "knn", a tree-ensemble type, else an SVM; None takes the
+    object's kind (is_knn / is_forest)."""
+    if model_type == "knn" or (model_type is None and is_knn(classifier)):
+        return knn_model(classifier)
+    if model_type in _FOREST_TYPES or (model_type is None and is_forest(classifier)):
+        return forest_model(classifier)
+    return svc_model(classifier)
+
+
 def predict(classifier, model_type, feats, mean, std):
     """classifier_wrapper for every column of feats [n_dims][n_vec] after (x - mean) / std, in one launch: "knn" gives
-    (class indices, P), the SVM types (classes_ of the winners, probabilities)."""
-    if model_type == "knn":
-        return knn_predict(classifier, feats, mean, std)
-    if model_type in _FOREST_TYPES:
-        return forest_predict(classifier, feats, mean, std)
-    return svm_predict(classifier, feats, mean, std)
+    (class indices, P), the SVM and tree-ensemble types (classes_ of the winners, probabilities)."""
+    m = device_model(classifier, model_type)
+    idx, proba = m.predict(feats, mean, std)
+    return m.labels(idx), proba
 
 
 class ForestArrays:
@@ -372,9 +369,10 @@ def forest_arrays(classifier):
     return ForestArrays("averaged", *arrays, classes, n_dims)
 
 
-class ForestModel:
-    """A tree ensemble uploaded to the device once (paa_forest_create, which validates and re-lays every tree in preorder);
-    freed with the object."""
+class ForestModel(_DeviceModel):
+    """A tree ensemble on the device (paa_forest_create, which validates and re-lays every tree in preorder)."""
+    _family = "forest"
+    _extra = ("n_outputs", np.float64, _ffi.c_f64p)
 
     def __init__(self, classifier):
         a = forest_arrays(classifier)
@@ -398,14 +396,12 @@ class ForestModel:
             raise ValueError("boosted ensemble: init of %s values for %d outputs" % (
                 None if init is None else init.shape[0], self.n_outputs))
         ptr = lambda x: x.ctypes.data_as(C.c_void_p)                       # noqa: E731
-        lib = _ffi.lib()
         handle = C.c_void_p()
-        _ffi.check(lib.paa_forest_create(1 if self.boosted else 0, n_trees, ptr(a.node_offsets), ptr(a.children_left),
-                                         ptr(a.children_right), ptr(a.feature), _ffi.as_f64p(a.threshold),
-                                         ptr(a.missing_go_to_left), _ffi.as_f64p(a.value), self.n_classes, self.n_dims,
-                                         a.learning_rate, _ffi.as_f64p(np.ascontiguousarray(init)), C.byref(handle)))
-        self.handle = handle
-        self._finalizer = weakref.finalize(self, lib.paa_forest_destroy, handle)
+        _ffi.check(_ffi.lib().paa_forest_create(1 if self.boosted else 0, n_trees, ptr(a.node_offsets), ptr(a.children_left),
+                                                ptr(a.children_right), ptr(a.feature), _ffi.as_f64p(a.threshold),
+                                                ptr(a.missing_go_to_left), _ffi.as_f64p(a.value), self.n_classes, self.n_dims,
+                                                a.learning_rate, _ffi.as_f64p(np.ascontiguousarray(init)), C.byref(handle)))
+        self._adopt(handle)
 
     @staticmethod
     def _raise_invalid(idx):
@@ -416,43 +412,9 @@ class ForestModel:
             raise ValueError("Input X contains infinity or a value too large for dtype('float32').")
 
     def predict(self, feats, mean, std, raw=False):
-        """feats [n_dims][n_vec] (feature-major) -> (class indices [n_vec], probabilities [n_vec][n_classes]) of
-        (feats[:, v] - mean) / std, plus the raw tree sums [n_vec][n_outputs] when raw is true (averaged: before the
-        division by the number of trees; boosted: the decision function)."""
-        F = np.ascontiguousarray(feats, dtype=np.float64)
-        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
-            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
-        mean, std = _stats(mean, std, self.n_dims)
-        n = F.shape[1]
-        idx = np.empty(n, dtype=np.int32)
-        proba = np.empty((n, self.n_classes), dtype=np.float64)
-        sums = np.empty((n, self.n_outputs), dtype=np.float64)
-        _ffi.check(_ffi.lib().paa_forest_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(mean),
-                                                     _ffi.as_f64p(std), idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(proba),
-                                                     _ffi.as_f64p(sums)))
-        self._raise_invalid(idx)
-        if raw:
-            return idx.astype(np.int64), proba, sums
-        return idx.astype(np.int64), proba
-
-    def predict_device(self, d_feats, ld, n_vec, mean, std):
-        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles)."""
-        mean, std = _stats(mean, std, self.n_dims)
-        d_stats = _ffi.DeviceBuffer.from_host(np.concatenate([mean, std]))
-        d_idx = _ffi.DeviceBuffer(max(4 * n_vec, 8))
-        d_proba = _ffi.DeviceBuffer(8 * n_vec * self.n_classes)
-        _ffi.check(_ffi.lib().paa_forest_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_stats.ptr,
-                                                         C.c_void_p(d_stats.ptr.value + 8 * self.n_dims), d_idx.ptr,
-                                                         d_proba.ptr, None))
-        idx = d_idx.to_host(np.int32, n_vec)
-        proba = d_proba.to_host(np.float64, n_vec * self.n_classes).reshape(n_vec, self.n_classes)
-        for b in (d_stats, d_idx, d_proba):
-            b.free()
-        self._raise_invalid(idx)
-        return idx.astype(np.int64), proba
-
-
-_uploaded_forest = weakref.WeakKeyDictionary()
+        """_DeviceModel.predict; raw: also the raw tree sums [n_vec][n_outputs] (averaged: before the division by the number
+        of trees; boosted: the decision function)."""
+        return super().predict(feats, mean, std, raw)
 
 
 def is_forest(classifier):
@@ -462,20 +424,8 @@ def is_forest(classifier):
 
 
 def forest_model(classifier):
-    """The device copy of a fitted tree ensemble (uploaded at the first use, kept while the classifier lives)."""
-    if isinstance(classifier, ForestModel):
-        return classifier
-    try:
-        m = _uploaded_forest.get(classifier)
-    except TypeError:
-        m = None
-    if m is None:
-        m = ForestModel(classifier)
-        try:
-            _uploaded_forest[classifier] = m
-        except TypeError:
-            pass
-    return m
+    """The device copy of a fitted tree ensemble."""
+    return _device_model(ForestModel, classifier)
 
 
 def forest_predict(classifier, feats, mean, std):
@@ -516,23 +466,12 @@ def classifier_wrapper(classifier, classifier_type, test_sample):
     predict_proba() on the GPU; "knn": Knn.classify on the GPU (the class INDEX and P); "randomforest" / "extratrees" /
     "gradientboosting": predict() and predict_proba() on the GPU (classes_ and the probabilities); any other type gives
     the reference's (-1, -1)."""
-    class_id = -1
-    probability = -1
-    if classifier_type in _SVM_TYPES:
-        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
-        m = svc_model(classifier)
-        idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))       # (x - 0) / 1 == x
-        return m.classes[idx[0]], proba[0]
-    if classifier_type == "knn":
-        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
-        idx, proba = knn_model(classifier).predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))
-        return idx[0], proba[0]
-    if classifier_type in _FOREST_TYPES:
-        x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
-        m = forest_model(classifier)
-        idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))
-        return m.classes[idx[0]], proba[0]
-    return class_id, probability
+    if classifier_type not in _SVM_TYPES + _FOREST_TYPES + ("knn",):
+        return -1, -1
+    x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+    m = device_model(classifier, classifier_type)
+    idx, proba = m.predict(x, np.zeros(x.shape[0]), np.ones(x.shape[0]))       # (x - 0) / 1 == x
+    return m.labels(idx[0]), proba[0]
 
 
 def _long_term_vector(signal, sampling_rate, mid_window, mid_step, short_window, short_step, compute_beat):

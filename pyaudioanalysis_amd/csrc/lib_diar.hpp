@@ -4,16 +4,12 @@
 // silhouette's b terms.  Kernels: kernels_diar.hpp (family_diar.hip).  Every call is synchronous on cs().
 #pragma once
 
-static Scratch g_diar;                // work space of the call in flight
+static GlobalScratch g_diar;          // work space of the call in flight
 static std::mutex g_diar_mu;
-
-static size_t diar_up(size_t b) { return (b + 255) / 256 * 256; }
 
 static int diar_check(int n_dims, int64_t ld, int64_t n_vec) {
     if (n_dims < 1 || n_dims > hmm::kMaxDims) return fail(PAA_ERR_ARG, "%d feature dimensions: 1..%d are supported", n_dims, hmm::kMaxDims);
-    if (n_vec < 1 || ld < n_vec) return fail(PAA_ERR_ARG, "bad feature matrix: %lld vectors, ld %lld", (long long)n_vec, (long long)ld);
-    if (n_vec > 0x7fffffffLL / 64) return fail(PAA_ERR_ARG, "too many vectors");
-    return PAA_OK;
+    return check_matrix(ld, n_vec, 0x7fffffffLL / 64);
 }
 
 // ks [nk] in 1..32, none above n_vec; returns the largest through kmax
@@ -35,8 +31,7 @@ extern "C" int paa_diar_dev_standardize_f64(const double *d_feats, int n_dims, i
     if ((rc = ensure_init())) return rc;
     std::lock_guard<std::mutex> lk(g_diar_mu);
     if ((rc = scratch_reserve(g_diar, (size_t)3 * n_dims * 8))) return rc;
-    if (launch::diar_standardize(d_feats, ld, n_vec, n_dims, d_z, ld, (double *)g_diar.p, cs()))
-        return fail(PAA_ERR_HIP, "standardisation launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("standardisation", launch::diar_standardize(d_feats, ld, n_vec, n_dims, d_z, ld, (double *)g_diar.p, cs()));
     HIP_TRY(hipMemcpyAsync(stats, g_diar.p, (size_t)3 * n_dims * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
     return PAA_OK;
@@ -54,8 +49,7 @@ extern "C" int paa_diar_dev_select_rows_f64(const double *d_z, int n_dims, int64
     std::lock_guard<std::mutex> lk(g_diar_mu);
     if ((rc = scratch_reserve(g_diar, (size_t)n_rows * 4))) return rc;
     HIP_TRY(hipMemcpyAsync(g_diar.p, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, cs()));
-    if (launch::diar_select_rows(d_z, ld, n_vec, (const int *)g_diar.p, n_rows, d_out, n_vec, cs()))
-        return fail(PAA_ERR_HIP, "row selection launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("row selection", launch::diar_select_rows(d_z, ld, n_vec, (const int *)g_diar.p, n_rows, d_out, n_vec, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
     return PAA_OK;
 }
@@ -73,16 +67,16 @@ extern "C" int paa_diar_dev_dim_distances_f64(const double *d_z, int n_dims, int
     }
     if ((rc = ensure_init())) return rc;
     std::lock_guard<std::mutex> lk(g_diar_mu);
-    const size_t slots = (size_t)nk * kmax, b_ks = diar_up((size_t)nk * 4), b_dist = diar_up(slots * n_dims * n_dims * 8),
-                 b_col = diar_up(slots * n_dims * 8), b_pm = diar_up(slots * 8);
+    const size_t slots = (size_t)nk * kmax, b_ks = up256((size_t)nk * 4), b_dist = up256(slots * n_dims * n_dims * 8),
+                 b_col = up256(slots * n_dims * 8), b_pm = up256(slots * 8);
     if ((rc = scratch_reserve(g_diar, b_ks + b_dist + b_col + b_pm))) return rc;
     char *p = (char *)g_diar.p;
     int *d_ks = (int *)p;
     double *d_dist = (double *)(p + b_ks), *d_col = (double *)(p + b_ks + b_dist), *d_pm = (double *)(p + b_ks + b_dist + b_col);
     if (d_labels) HIP_TRY(hipMemcpyAsync(d_ks, ks, (size_t)nk * 4, hipMemcpyHostToDevice, cs()));
     HIP_TRY(hipMemsetAsync(d_col, 0, b_col + b_pm, cs()));
-    if (launch::diar_dim_distances(d_z, ld, n_vec, n_dims, d_labels, d_ks, nk, kmax, d_dist, d_col, d_pm, cs()))
-        return fail(PAA_ERR_HIP, "feature-row distance launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("feature-row distance",
+               launch::diar_dim_distances(d_z, ld, n_vec, n_dims, d_labels, d_ks, nk, kmax, d_dist, d_col, d_pm, cs()));
     HIP_TRY(hipMemcpyAsync(colsum, d_col, slots * n_dims * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(pair_mean, d_pm, slots * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
@@ -105,13 +99,12 @@ extern "C" int paa_diar_dev_sqdist_points_f64(const double *d_z, int n_dims, int
     if (!d_z || !out) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
     std::lock_guard<std::mutex> lk(g_diar_mu);
-    const size_t b_idx = diar_up((size_t)n_pts * 8), b_out = (size_t)n_pts * n_vec * 8;
+    const size_t b_idx = up256((size_t)n_pts * 8), b_out = (size_t)n_pts * n_vec * 8;
     if ((rc = scratch_reserve(g_diar, b_idx + b_out))) return rc;
     long long *d_idx = (long long *)g_diar.p;
     double *d_out = (double *)((char *)g_diar.p + b_idx);
     HIP_TRY(hipMemcpyAsync(d_idx, idx, (size_t)n_pts * 8, hipMemcpyHostToDevice, cs()));
-    if (launch::diar_sqdist_points(d_z, ld, n_vec, n_dims, d_idx, n_pts, d_out, cs()))
-        return fail(PAA_ERR_HIP, "seeding distance launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("seeding distance", launch::diar_sqdist_points(d_z, ld, n_vec, n_dims, d_idx, n_pts, d_out, cs()));
     HIP_TRY(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
     return PAA_OK;
@@ -126,13 +119,12 @@ extern "C" int paa_diar_dev_get_points_f64(const double *d_z, int n_dims, int64_
     if (!d_z || !out) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
     std::lock_guard<std::mutex> lk(g_diar_mu);
-    const size_t b_idx = diar_up((size_t)n_pts * 8), b_out = (size_t)n_pts * n_dims * 8;
+    const size_t b_idx = up256((size_t)n_pts * 8), b_out = (size_t)n_pts * n_dims * 8;
     if ((rc = scratch_reserve(g_diar, b_idx + b_out))) return rc;
     long long *d_idx = (long long *)g_diar.p;
     double *d_out = (double *)((char *)g_diar.p + b_idx);
     HIP_TRY(hipMemcpyAsync(d_idx, idx, (size_t)n_pts * 8, hipMemcpyHostToDevice, cs()));
-    if (launch::diar_get_points(d_z, ld, n_dims, d_idx, n_pts, d_out, cs()))
-        return fail(PAA_ERR_HIP, "point gather launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("point gather", launch::diar_get_points(d_z, ld, n_dims, d_idx, n_pts, d_out, cs()));
     HIP_TRY(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
     return PAA_OK;
@@ -153,8 +145,8 @@ extern "C" int paa_diar_dev_kmeans_f64(const double *d_z, int n_dims, int64_t ld
             if (!std::isfinite(centers[(size_t)i * hmm::kMaxStates * n_dims + j])) return fail(PAA_ERR_ARG, "an initial centre is not finite");
     if ((rc = ensure_init())) return rc;
     std::lock_guard<std::mutex> lk(g_diar_mu);
-    const size_t b_ks = diar_up((size_t)nk * 4), b_cen = diar_up(cells * 8), b_state = diar_up((size_t)nk * sizeof(diar::KmState)),
-                 b_d2 = diar_up((size_t)nk * n_vec * 8), b_ints = diar_up((size_t)nk * diar::kIntsPerK * 4), b_in = diar_up((size_t)nk * 8);
+    const size_t b_ks = up256((size_t)nk * 4), b_cen = up256(cells * 8), b_state = up256((size_t)nk * sizeof(diar::KmState)),
+                 b_d2 = up256((size_t)nk * n_vec * 8), b_ints = up256((size_t)nk * diar::kIntsPerK * 4), b_in = up256((size_t)nk * 8);
     if ((rc = scratch_reserve(g_diar, b_ks + 2 * b_cen + b_state + b_d2 + b_ints + b_in))) return rc;
     char *p = (char *)g_diar.p;
     int *d_ks = (int *)p;                                   p += b_ks;
@@ -171,17 +163,16 @@ extern "C" int paa_diar_dev_kmeans_f64(const double *d_z, int n_dims, int64_t ld
     HIP_TRY(hipMemsetAsync(d_labels, 0xff, (size_t)nk * n_vec * 4, cs()));       // -1: no window keeps its label in iteration 1
     std::vector<diar::KmState> state(nk);
     for (int it = 0; it < max_iter; ++it) {
-        if (launch::diar_kmeans_step(d_z, ld, n_vec, n_dims, d_ks, nk, kmax, d_cen, d_state, d_labels, d_d2, d_ints, d_sums, tol,
-                                     max_iter, cs()))
-            return fail(PAA_ERR_HIP, "k-means launch failed: %s", hipGetErrorString(hipGetLastError()));
+        LAUNCH_TRY("k-means", launch::diar_kmeans_step(d_z, ld, n_vec, n_dims, d_ks, nk, kmax, d_cen, d_state, d_labels, d_d2, d_ints,
+                                                       d_sums, tol, max_iter, cs()));
         HIP_TRY(hipMemcpyAsync(state.data(), d_state, (size_t)nk * sizeof(diar::KmState), hipMemcpyDeviceToHost, cs()));
         HIP_TRY(hipStreamSynchronize(cs()));
         bool all = true;
         for (int i = 0; i < nk; ++i) all = all && state[i].done;
         if (all) break;
     }
-    if (launch::diar_kmeans_last(d_z, ld, n_vec, n_dims, d_ks, nk, kmax, d_cen, d_state, d_labels, d_d2, d_inertia, cs()))
-        return fail(PAA_ERR_HIP, "k-means launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("k-means",
+               launch::diar_kmeans_last(d_z, ld, n_vec, n_dims, d_ks, nk, kmax, d_cen, d_state, d_labels, d_d2, d_inertia, cs()));
     HIP_TRY(hipMemcpyAsync(centers, d_cen, cells * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(inertia, d_inertia, (size_t)nk * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));
@@ -202,8 +193,8 @@ extern "C" int paa_diar_dev_pair_sums_f64(const double *d_z, int n_dims, int64_t
     const int nbins = binoff[nk];
     const long long tiles = launch::diar_pair_tiles(n_vec), chunks = launch::diar_pair_chunks(n_vec);
     std::lock_guard<std::mutex> lk(g_diar_mu);
-    const size_t b_ks = diar_up((size_t)nk * 4), b_off = diar_up((size_t)(nk + 1) * 4), b_part = diar_up((size_t)tiles * nbins * 8),
-                 b_stage = diar_up((size_t)chunks * nbins * 8), b_S = diar_up((size_t)nbins * 8);
+    const size_t b_ks = up256((size_t)nk * 4), b_off = up256((size_t)(nk + 1) * 4), b_part = up256((size_t)tiles * nbins * 8),
+                 b_stage = up256((size_t)chunks * nbins * 8), b_S = up256((size_t)nbins * 8);
     if ((rc = scratch_reserve(g_diar, b_ks + b_off + b_part + b_stage + b_S))) return rc;
     char *p = (char *)g_diar.p;
     int *d_ks = (int *)p;                p += b_ks;
@@ -213,8 +204,8 @@ extern "C" int paa_diar_dev_pair_sums_f64(const double *d_z, int n_dims, int64_t
     double *d_S = (double *)p;
     HIP_TRY(hipMemcpyAsync(d_ks, ks, (size_t)nk * 4, hipMemcpyHostToDevice, cs()));
     HIP_TRY(hipMemcpyAsync(d_off, binoff.data(), (size_t)(nk + 1) * 4, hipMemcpyHostToDevice, cs()));
-    if (launch::diar_pair_sums(d_z, ld, n_vec, n_dims, d_labels, d_ks, nk, d_off, nbins, d_part, d_stage, d_S, cs()))
-        return fail(PAA_ERR_HIP, "cluster-pair launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("cluster-pair",
+               launch::diar_pair_sums(d_z, ld, n_vec, n_dims, d_labels, d_ks, nk, d_off, nbins, d_part, d_stage, d_S, cs()));
     std::vector<double> flat(nbins);
     HIP_TRY(hipMemcpyAsync(flat.data(), d_S, (size_t)nbins * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipStreamSynchronize(cs()));

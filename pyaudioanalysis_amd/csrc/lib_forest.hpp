@@ -7,7 +7,7 @@
 
 struct PaaForest {
     forest::ForestDev dev{};
-    void *block = nullptr;        // one device allocation: nodes, leaf values, roots, init
+    DevBlock block;               // nodes, leaf values, init, roots
 };
 static std::mutex g_forest_mu;
 constexpr int kForestMaxTrees = 200000;       // grid limit of the traversal kernel (4 trees per workgroup row)
@@ -90,52 +90,35 @@ extern "C" int paa_forest_create(int kind, int n_trees, const int64_t *node_offs
 
     int rc = ensure_init();
     if (rc) return rc;
-    const size_t nb = (size_t)total * sizeof(forest::Node), vb = leaf_values.size() * 8, ib = (size_t)n_outputs * 8;
-    const size_t rb = (size_t)n_trees * sizeof(int);
+    std::vector<double> init_v(n_outputs, 0.0);
+    if (boosted) std::copy(init, init + n_outputs, init_v.begin());
     std::unique_ptr<PaaForest> h(new PaaForest());
-    HIP_TRY(hipMalloc(&h->block, nb + vb + ib + rb));
-    char *p = (char *)h->block;
-    h->dev.nodes = (const forest::Node *)p;
-    h->dev.leaf_values = (const double *)(p + nb);
-    h->dev.init = (const double *)(p + nb + vb);
-    h->dev.roots = (const int *)(p + nb + vb + ib);
+    BlockPart parts[] = {{nodes.data(), (size_t)total * sizeof(forest::Node), sizeof(forest::Node)},
+                         {leaf_values.data(), leaf_values.size() * 8, 8}, {init_v.data(), (size_t)n_outputs * 8, 8},
+                         {roots.data(), (size_t)n_trees * sizeof(int), 4}};
+    if ((rc = block_upload(h->block, parts, 4, "the tree ensemble"))) return rc;
+    h->dev.nodes = (const forest::Node *)parts[0].dev;
+    h->dev.leaf_values = (const double *)parts[1].dev;
+    h->dev.init = (const double *)parts[2].dev;
+    h->dev.roots = (const int *)parts[3].dev;
     h->dev.n_trees = n_trees;
     h->dev.n_dims = n_dims;
     h->dev.n_classes = n_classes;
     h->dev.n_outputs = n_outputs;
     h->dev.boosted = boosted;
     h->dev.learning_rate = boosted ? learning_rate : 0.0;
-    std::vector<double> init_v(n_outputs, 0.0);
-    if (boosted) std::copy(init, init + n_outputs, init_v.begin());
-    if (hipMemcpy(p, nodes.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p + nb, leaf_values.data(), vb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p + nb + vb, init_v.data(), ib, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(p + nb + vb + ib, roots.data(), rb, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(h->block);
-        return fail(PAA_ERR_HIP, "uploading the tree ensemble failed");
-    }
     *out_handle = h.release();
     return PAA_OK;
 }
 
-extern "C" int paa_forest_destroy(void *handle) {
-    if (!handle) return PAA_OK;
-    PaaForest *h = (PaaForest *)handle;
-    const hipError_t e = h->block ? hipFree(h->block) : hipSuccess;
-    delete h;
-    return e == hipSuccess ? PAA_OK : fail(PAA_ERR_HIP, "hipFree: %s", hipGetErrorString(e));
-}
+extern "C" int paa_forest_destroy(void *handle) { return model_destroy((PaaForest *)handle); }
 
 extern "C" int paa_forest_num_classes(const void *handle) {
     return handle ? ((const PaaForest *)handle)->dev.n_classes : fail(PAA_ERR_ARG, "null handle");
 }
 
 static int forest_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    if (!handle) return fail(PAA_ERR_ARG, "null handle");
-    const PaaForest *h = (const PaaForest *)handle;
-    if (n_dims != h->dev.n_dims) return fail(PAA_ERR_ARG, "feature vectors have %d dims, the model %d", n_dims, h->dev.n_dims);
-    if (n_vec < 1 || ld < n_vec) return fail(PAA_ERR_ARG, "bad feature matrix: %lld vectors, ld %lld", (long long)n_vec, (long long)ld);
-    return PAA_OK;
+    return check_model_matrix(handle ? &((const PaaForest *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec, 0);
 }
 
 static size_t forest_leaf_bytes(const forest::ForestDev &m, int64_t n_vec) {
@@ -151,15 +134,14 @@ extern "C" int paa_forest_dev_predict_f64(const void *handle, const double *d_fe
     if ((rc = ensure_init())) return rc;
     const forest::ForestDev &m = ((const PaaForest *)handle)->dev;
     std::lock_guard<std::mutex> lk(g_forest_mu);
-    const size_t lb = (forest_leaf_bytes(m, n_vec) + 255) / 256 * 256;
+    const size_t lb = up256(forest_leaf_bytes(m, n_vec));
     {
         std::lock_guard<std::mutex> lk2(g_mu);
         if ((rc = scratch_reserve(g_forest_scratch, lb + (d_raw ? 0 : (size_t)n_vec * m.n_outputs * 8)))) return rc;
     }
     double *raw = d_raw ? d_raw : (double *)((char *)g_forest_scratch.p + lb);
-    if (launch::forest(m, d_feats, (long long)ld, (long long)n_vec, d_mean, d_std, (int *)g_forest_scratch.p, d_label_index, raw,
-                       d_proba, cs()))
-        return fail(PAA_ERR_HIP, "tree-ensemble launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("tree-ensemble", launch::forest(m, d_feats, (long long)ld, (long long)n_vec, d_mean, d_std, (int *)g_forest_scratch.p,
+                                               d_label_index, raw, d_proba, cs()));
     return PAA_OK;
 }
 
@@ -170,29 +152,14 @@ extern "C" int paa_forest_predict_f64(const void *handle, const double *feats, i
     if (!feats || !mean || !std || !label_index || !proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
     const forest::ForestDev &m = ((const PaaForest *)handle)->dev;
-    LaneGuard lane;       // own stream + scratch for this call (see Lane)
-    const size_t fb = (size_t)n_dims * ld * 8;
-    const size_t lb = (forest_leaf_bytes(m, n_vec) + 255) / 256 * 256, rwb = (size_t)n_vec * m.n_outputs * 8;
-    const size_t lab = ((size_t)n_vec * 4 + 255) / 256 * 256, pb = (size_t)n_vec * m.n_classes * 8;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        if ((rc = scratch_reserve(lane.l->in, fb + (size_t)2 * n_dims * 8))) return rc;
-        if ((rc = scratch_reserve(lane.l->mid, lb + rwb))) return rc;
-        if ((rc = scratch_reserve(lane.l->out, lab + pb))) return rc;
-    }
-    double *d_feats = (double *)lane.l->in.p, *d_mean = d_feats + (size_t)n_dims * ld, *d_std = d_mean + n_dims;
-    int *d_leaves = (int *)lane.l->mid.p;
-    double *d_raw = (double *)((char *)lane.l->mid.p + lb);
-    int32_t *d_label = (int32_t *)lane.l->out.p;
-    double *d_proba = (double *)((char *)lane.l->out.p + lab);
-    HIP_TRY(hipMemcpyAsync(d_feats, feats, fb, hipMemcpyHostToDevice, cs()));
-    HIP_TRY(hipMemcpyAsync(d_mean, mean, (size_t)n_dims * 8, hipMemcpyHostToDevice, cs()));
-    HIP_TRY(hipMemcpyAsync(d_std, std, (size_t)n_dims * 8, hipMemcpyHostToDevice, cs()));
-    if (launch::forest(m, d_feats, (long long)ld, (long long)n_vec, d_mean, d_std, d_leaves, d_label, d_raw, d_proba, cs()))
-        return fail(PAA_ERR_HIP, "tree-ensemble launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipMemcpyAsync(label_index, d_label, (size_t)n_vec * 4, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipMemcpyAsync(proba, d_proba, pb, hipMemcpyDeviceToHost, cs()));
+    const size_t lb = up256(forest_leaf_bytes(m, n_vec)), rwb = (size_t)n_vec * m.n_outputs * 8;
+    Staged st;
+    if ((rc = stage(st, feats, n_dims, ld, mean, std, lb + rwb,
+                    {{label_index, (size_t)n_vec * 4}, {proba, (size_t)n_vec * m.n_classes * 8}})))
+        return rc;
+    double *d_raw = (double *)((char *)st.mid + lb);        // the raw scores live behind the leaf slots, not among the outputs
+    LAUNCH_TRY("tree-ensemble", launch::forest(m, st.feats, (long long)ld, (long long)n_vec, st.mean, st.std, (int *)st.mid,
+                                               (int32_t *)st.out[0], d_raw, (double *)st.out[1], cs()));
     if (raw) HIP_TRY(hipMemcpyAsync(raw, d_raw, rwb, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipStreamSynchronize(cs()));
-    return PAA_OK;
+    return finish(st);
 }

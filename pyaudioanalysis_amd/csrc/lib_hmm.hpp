@@ -5,13 +5,13 @@
 
 struct PaaHmm {
     hmm::HmmDev dev{};
-    void *block = nullptr;            // one device allocation: the model tables
+    DevBlock block;                   // the model tables
     Scratch work;                     // emission matrix, back-pointers, segment tables, block products: grown on demand
     std::vector<hmm::Segment> segs;   // host copies of the last call's tables: their upload is asynchronous
     std::vector<long long> seq_seg;
     std::mutex mu;
 };
-static Scratch g_hmm_stats;           // labels, counts, means, deviations of the training-statistics entry points
+static GlobalScratch g_hmm_stats;     // labels, counts, means, deviations of the training-statistics entry points
 static std::mutex g_hmm_stats_mu;
 
 static bool hmm_is_distribution(const double *p, int n) {
@@ -60,12 +60,9 @@ extern "C" int paa_hmm_create(const double *startprob, const double *transmat, c
         cst[k] = D * std::log(2.0 * M_PI) + sum_log;
     }
     std::unique_ptr<PaaHmm> h(new PaaHmm());
-    HIP_TRY(hipMalloc(&h->block, tab.size() * 8));
-    if (hipMemcpy(h->block, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(h->block);
-        return fail(PAA_ERR_HIP, "uploading the HMM failed");
-    }
-    const double *base = (const double *)h->block;
+    BlockPart part = {tab.data(), tab.size() * 8, 8};
+    if ((rc = block_upload(h->block, &part, 1, "the HMM"))) return rc;
+    const double *base = (const double *)part.dev;
     h->dev.mu = base;
     h->dev.inv = base + (size_t)D * kp;
     h->dev.cst = base + (size_t)2 * D * kp;
@@ -79,15 +76,7 @@ extern "C" int paa_hmm_create(const double *startprob, const double *transmat, c
 }
 
 extern "C" int paa_hmm_destroy(void *handle) {
-    if (!handle) return PAA_OK;
-    PaaHmm *h = (PaaHmm *)handle;
-    hipError_t e = h->block ? hipFree(h->block) : hipSuccess;
-    if (h->work.p) {
-        const hipError_t e2 = hipFree(h->work.p);
-        if (e == hipSuccess) e = e2;
-    }
-    delete h;
-    return e == hipSuccess ? PAA_OK : fail(PAA_ERR_HIP, "hipFree: %s", hipGetErrorString(e));
+    return model_destroy((PaaHmm *)handle, handle ? ((PaaHmm *)handle)->work.p : nullptr);
 }
 
 extern "C" int paa_hmm_num_states(const void *handle) {
@@ -95,12 +84,7 @@ extern "C" int paa_hmm_num_states(const void *handle) {
 }
 
 static int hmm_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    if (!handle) return fail(PAA_ERR_ARG, "null handle");
-    const PaaHmm *h = (const PaaHmm *)handle;
-    if (n_dims != h->dev.n_dims) return fail(PAA_ERR_ARG, "feature vectors have %d dims, the model %d", n_dims, h->dev.n_dims);
-    if (n_vec < 1 || ld < n_vec) return fail(PAA_ERR_ARG, "bad feature matrix: %lld vectors, ld %lld", (long long)n_vec, (long long)ld);
-    if (n_vec > 0x7fffffffLL) return fail(PAA_ERR_ARG, "too many vectors");
-    return PAA_OK;
+    return check_model_matrix(handle ? &((const PaaHmm *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec, 0x7fffffffLL);
 }
 
 static int hmm_check_offsets(const int64_t *offsets, int64_t n_seq, int64_t n_vec) {
@@ -111,8 +95,6 @@ static int hmm_check_offsets(const int64_t *offsets, int64_t n_seq, int64_t n_ve
         if (offsets[q + 1] <= offsets[q]) return fail(PAA_ERR_ARG, "sequence %lld is empty", (long long)q);
     return PAA_OK;
 }
-
-static size_t hmm_up(size_t b) { return (b + 255) / 256 * 256; }
 
 // emission + Viterbi on cs(); block_rows <= 0: hmm::kBlockRows
 static int hmm_decode_core(PaaHmm *h, const double *d_feats, int64_t ld, int64_t n_vec, const int64_t *offsets, int64_t n_seq,
@@ -134,10 +116,10 @@ static int hmm_decode_core(PaaHmm *h, const double *d_feats, int64_t ld, int64_t
     }
     const size_t n_seg = h->segs.size(), kp = m.kp;
     if (n_seg * m.n_states > 0x7fffffffULL) return fail(PAA_ERR_ARG, "too many segments");
-    const size_t b_B = hmm_up((size_t)n_vec * m.n_states * 8), b_M = multi ? hmm_up(n_seg * kp * kp * 8) : 0,
-                 b_V = hmm_up(n_seg * kp * 8), b_segs = hmm_up(n_seg * sizeof(hmm::Segment)),
-                 b_seq = hmm_up((size_t)(n_seq + 1) * 8), b_end = hmm_up(n_seg * 4), b_psi = hmm_up((size_t)n_vec * kp),
-                 b_map = hmm_up(n_seg * kp);
+    const size_t b_B = up256((size_t)n_vec * m.n_states * 8), b_M = multi ? up256(n_seg * kp * kp * 8) : 0,
+                 b_V = up256(n_seg * kp * 8), b_segs = up256(n_seg * sizeof(hmm::Segment)),
+                 b_seq = up256((size_t)(n_seq + 1) * 8), b_end = up256(n_seg * 4), b_psi = up256((size_t)n_vec * kp),
+                 b_map = up256(n_seg * kp);
     int rc = scratch_reserve(h->work, b_B + b_M + 2 * b_V + b_segs + b_seq + b_end + b_psi + b_map);
     if (rc) return rc;
     char *p = (char *)h->work.p;
@@ -152,11 +134,9 @@ static int hmm_decode_core(PaaHmm *h, const double *d_feats, int64_t ld, int64_t
     unsigned char *d_map = (unsigned char *)p;
     HIP_TRY(hipMemcpyAsync(d_segs, h->segs.data(), n_seg * sizeof(hmm::Segment), hipMemcpyHostToDevice, cs()));
     HIP_TRY(hipMemcpyAsync(d_seq, h->seq_seg.data(), (size_t)(n_seq + 1) * 8, hipMemcpyHostToDevice, cs()));
-    if (launch::hmm_emission(m, d_feats, (long long)ld, (long long)n_vec, d_B, cs()))
-        return fail(PAA_ERR_HIP, "HMM emission launch failed: %s", hipGetErrorString(hipGetLastError()));
-    if (launch::hmm_decode(m, d_B, d_segs, (long long)n_seg, d_seq, (long long)n_seq, multi, d_M, d_V, d_Vout, d_psi, d_map,
-                           d_end, d_states, d_logprob, cs()))
-        return fail(PAA_ERR_HIP, "HMM decode launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("HMM emission", launch::hmm_emission(m, d_feats, (long long)ld, (long long)n_vec, d_B, cs()));
+    LAUNCH_TRY("HMM decode", launch::hmm_decode(m, d_B, d_segs, (long long)n_seg, d_seq, (long long)n_seq, multi, d_M, d_V, d_Vout, d_psi,
+                                                d_map, d_end, d_states, d_logprob, cs()));
     return PAA_OK;
 }
 
@@ -188,8 +168,8 @@ extern "C" int paa_hmm_dev_loglik_f64(const void *handle, const double *d_feats,
     if (rc) return rc;
     if (!d_feats || !d_loglik) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
-    if (launch::hmm_emission(((const PaaHmm *)handle)->dev, d_feats, (long long)ld, (long long)n_vec, d_loglik, cs()))
-        return fail(PAA_ERR_HIP, "HMM emission launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("HMM emission",
+               launch::hmm_emission(((const PaaHmm *)handle)->dev, d_feats, (long long)ld, (long long)n_vec, d_loglik, cs()));
     return PAA_OK;
 }
 
@@ -200,28 +180,18 @@ extern "C" int paa_hmm_decode_f64(const void *handle, const double *feats, int n
     if ((rc = hmm_check_offsets(offsets, n_seq, n_vec))) return rc;
     if (!feats || !states || !logprob) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
-    LaneGuard lane;       // own stream + scratch for this call (see Lane)
-    const size_t fb = (size_t)n_dims * ld * 8, sb = hmm_up((size_t)n_vec * 4);
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        if ((rc = scratch_reserve(lane.l->in, fb))) return rc;
-        if ((rc = scratch_reserve(lane.l->out, sb + (size_t)n_seq * 8))) return rc;
-    }
-    double *d_feats = (double *)lane.l->in.p;
-    int32_t *d_states = (int32_t *)lane.l->out.p;
-    double *d_logprob = (double *)((char *)lane.l->out.p + sb);
-    HIP_TRY(hipMemcpyAsync(d_feats, feats, fb, hipMemcpyHostToDevice, cs()));
-    if ((rc = hmm_decode_core((PaaHmm *)handle, d_feats, ld, n_vec, offsets, n_seq, d_states, d_logprob, 0))) return rc;
-    HIP_TRY(hipMemcpyAsync(states, d_states, (size_t)n_vec * 4, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipMemcpyAsync(logprob, d_logprob, (size_t)n_seq * 8, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipStreamSynchronize(cs()));
-    return PAA_OK;
+    Staged st;
+    if ((rc = stage(st, feats, n_dims, ld, nullptr, nullptr, 0, {{states, (size_t)n_vec * 4}, {logprob, (size_t)n_seq * 8}}))) return rc;
+    if ((rc = hmm_decode_core((PaaHmm *)handle, st.feats, ld, n_vec, offsets, n_seq, (int32_t *)st.out[0], (double *)st.out[1], 0)))
+        return rc;
+    return finish(st);
 }
 
 static int hmm_stats_check(int n_dims, int64_t ld, int64_t n_vec, const int32_t *labels, int n_states) {
     if (n_states < 1 || n_states > hmm::kMaxStates) return fail(PAA_ERR_ARG, "%d states: 1..%d are supported", n_states, hmm::kMaxStates);
     if (n_dims < 1 || n_dims > hmm::kMaxDims) return fail(PAA_ERR_ARG, "%d feature dimensions: 1..%d are supported", n_dims, hmm::kMaxDims);
-    if (n_vec < 1 || ld < n_vec) return fail(PAA_ERR_ARG, "bad feature matrix: %lld vectors, ld %lld", (long long)n_vec, (long long)ld);
+    int rc = check_matrix(ld, n_vec, 0);
+    if (rc) return rc;
     if (!labels) return fail(PAA_ERR_ARG, "null labels");
     for (int64_t t = 0; t < n_vec; ++t)
         if (labels[t] < 0 || labels[t] >= n_states)
@@ -234,8 +204,8 @@ static int hmm_stats_check(int n_dims, int64_t ld, int64_t n_vec, const int32_t 
 static int hmm_stats_core(const double *d_feats, int n_dims, int64_t ld, int64_t n_vec, const int32_t *labels, int K,
                           double *priors, double *transmat, double *means, double *covars) {
     std::lock_guard<std::mutex> lk(g_hmm_stats_mu);
-    const size_t b_lab = hmm_up((size_t)n_vec * 4), cells = (size_t)K + (size_t)K * K, b_cnt = hmm_up(cells * 4),
-                 b_mom = hmm_up((size_t)K * n_dims * 8);
+    const size_t b_lab = up256((size_t)n_vec * 4), cells = (size_t)K + (size_t)K * K, b_cnt = up256(cells * 4),
+                 b_mom = up256((size_t)K * n_dims * 8);
     int rc = scratch_reserve(g_hmm_stats, b_lab + b_cnt + 2 * b_mom);
     if (rc) return rc;
     char *p = (char *)g_hmm_stats.p;
@@ -244,8 +214,8 @@ static int hmm_stats_core(const double *d_feats, int n_dims, int64_t ld, int64_t
     double *d_means = (double *)(p + b_lab + b_cnt), *d_stds = (double *)(p + b_lab + b_cnt + b_mom);
     HIP_TRY(hipMemcpyAsync(d_labels, labels, (size_t)n_vec * 4, hipMemcpyHostToDevice, cs()));
     HIP_TRY(hipMemsetAsync(d_counts, 0, cells * 4, cs()));
-    if (launch::hmm_stats(d_feats, (long long)ld, (long long)n_vec, d_labels, K, n_dims, d_counts, d_means, d_stds, cs()))
-        return fail(PAA_ERR_HIP, "HMM statistics launch failed: %s", hipGetErrorString(hipGetLastError()));
+    LAUNCH_TRY("HMM statistics",
+               launch::hmm_stats(d_feats, (long long)ld, (long long)n_vec, d_labels, K, n_dims, d_counts, d_means, d_stds, cs()));
     std::vector<int> counts(cells);
     HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, cells * 4, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(means, d_means, (size_t)K * n_dims * 8, hipMemcpyDeviceToHost, cs()));
@@ -277,12 +247,7 @@ extern "C" int paa_hmm_train_stats_f64(const double *feats, int n_dims, int64_t 
     if (rc) return rc;
     if (!feats || !priors || !transmat || !means || !covars) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
-    LaneGuard lane;       // own stream + scratch for this call (see Lane)
-    const size_t fb = (size_t)n_dims * ld * 8;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        if ((rc = scratch_reserve(lane.l->in, fb))) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(lane.l->in.p, feats, fb, hipMemcpyHostToDevice, cs()));
-    return hmm_stats_core((const double *)lane.l->in.p, n_dims, ld, n_vec, labels, n_states, priors, transmat, means, covars);
+    Staged st;
+    if ((rc = stage(st, feats, n_dims, ld, nullptr, nullptr, 0, {}))) return rc;
+    return hmm_stats_core(st.feats, n_dims, ld, n_vec, labels, n_states, priors, transmat, means, covars);
 }

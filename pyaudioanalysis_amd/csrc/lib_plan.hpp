@@ -552,12 +552,11 @@ static int plan_build(const int64_t *offsets, int64_t n_clips, int sample_kind, 
     //   [clip descriptors | tiles | statistics chunks] (uploaded) [clip constants | partial sums | minima | maxima]
     {
         const size_t nch = (size_t)std::max<long long>(n_chunks, 1);
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t o_clips = 0, o_tiles = o_clips + up(p->clips.size() * sizeof(ClipDev));
-        const size_t o_chunks = o_tiles + up(std::max<size_t>(tiles.size(), 1) * sizeof(Tile));
-        const size_t o_norms = o_chunks + up(std::max<size_t>(chunks.size(), 1) * sizeof(StatChunk));
-        const size_t o_sum = o_norms + up((size_t)n_clips * sizeof(ClipNorm));
-        const size_t o_min = o_sum + up(nch * 8), o_max = o_min + up(nch * 8), total = o_max + up(nch * 8);
+        const size_t o_clips = 0, o_tiles = o_clips + up256(p->clips.size() * sizeof(ClipDev));
+        const size_t o_chunks = o_tiles + up256(std::max<size_t>(tiles.size(), 1) * sizeof(Tile));
+        const size_t o_norms = o_chunks + up256(std::max<size_t>(chunks.size(), 1) * sizeof(StatChunk));
+        const size_t o_sum = o_norms + up256((size_t)n_clips * sizeof(ClipNorm));
+        const size_t o_min = o_sum + up256(nch * 8), o_max = o_min + up256(nch * 8), total = o_max + up256(nch * 8);
         if ((rc = pool_alloc(&p->d_block, total))) return rc;
         std::vector<unsigned char> stage(o_norms, 0);
         memcpy(stage.data() + o_clips, p->clips.data(), p->clips.size() * sizeof(ClipDev));

@@ -82,6 +82,14 @@ struct Scratch {
     void *p = nullptr;
     size_t cap = 0;
 };
+// A Scratch of static lifetime: it links itself into g_global_scratch where it is defined, and paa_shutdown frees and resets
+// every one of them (no buffer of an old device survives a device switch).  Lane scratch and PaaHmm::work have their own owners.
+struct GlobalScratch : Scratch {
+    GlobalScratch *next;
+    GlobalScratch();
+};
+static GlobalScratch *g_global_scratch = nullptr;
+inline GlobalScratch::GlobalScratch() : next(g_global_scratch) { g_global_scratch = this; }
 
 static std::mutex g_mu;
 static std::mutex g_api_mu;     // the self-similarity entry points share their scratch buffers: one call at a time
@@ -138,9 +146,9 @@ struct LaneGuard {
         g_lane_cv.notify_one();
     }
 };
-static Scratch g_sim_z, g_sim_small, g_sim_cand, g_sim_in, g_sim_out, g_sim_filt;     // self-similarity row
-static Scratch g_svc_sums;        // per-class sums of the SVC device-buffer entry point (lib_svc.hpp)
-static Scratch g_forest_scratch;  // leaf slots and raw scores of the tree-ensemble device-buffer entry point (lib_forest.hpp)
+static GlobalScratch g_sim_z, g_sim_small, g_sim_cand, g_sim_in, g_sim_out, g_sim_filt;     // self-similarity row
+static GlobalScratch g_svc_sums;        // per-class sums of the SVC device-buffer entry point (lib_svc.hpp)
+static GlobalScratch g_forest_scratch;  // leaf slots and raw scores of the tree-ensemble device-buffer entry point (lib_forest.hpp)
 static int g_force_generic = 0;
 static int g_f800_waves = 8;          // PAA_F800_WAVES: waves per workgroup of the 800/400 kernel (4 or 8)
 static int g_num_cu = 256;       // multiProcessorCount of the selected device (MI355X: 256)
@@ -186,9 +194,14 @@ static int upload(T **dst, const void *src, size_t count) {
     return PAA_OK;
 }
 
+static void scratch_release(Scratch &s) {
+    if (s.p) (void)hipFree(s.p);
+    s.p = nullptr;
+    s.cap = 0;
+}
 static int scratch_reserve(Scratch &s, size_t bytes) {
     if (bytes <= s.cap) return PAA_OK;
-    if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; }
+    scratch_release(s);
     size_t want = bytes + bytes / 8 + 4096;
     HIP_TRY(hipMalloc(&s.p, want));
     s.cap = want;
@@ -313,6 +326,7 @@ static int get_tables(double fs, int window, bool need_mel, bool need_chroma, Ta
     return PAA_OK;
 }
 
+#include "lib_model.hpp"
 #include "lib_plan.hpp"
 #include "lib_similarity.hpp"
 
@@ -388,12 +402,12 @@ extern "C" void paa_shutdown(void) {
     for (auto &kv : g_tables) free_tables(*kv.second);
     g_tables.clear();
     pool_release_all();
-    for (Scratch *s : {&g_sim_z, &g_sim_small, &g_sim_cand, &g_sim_in, &g_sim_out, &g_sim_filt, &g_svc_sums, &g_forest_scratch}) { if (s->p) (void)hipFree(s->p); s->p = nullptr; s->cap = 0; }
+    for (GlobalScratch *s = g_global_scratch; s; s = s->next) scratch_release(*s);
     for (Lane &ln : g_lanes) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); ln.stream = nullptr; }
         if (ln.copy_stream) { (void)hipStreamSynchronize(ln.copy_stream); (void)hipStreamDestroy(ln.copy_stream); ln.copy_stream = nullptr; }
         for (hipEvent_t &ev : ln.range_done) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
-        for (Scratch *s : {&ln.in, &ln.out, &ln.mid}) { if (s->p) (void)hipFree(s->p); s->p = nullptr; s->cap = 0; }
+        for (Scratch *s : {&ln.in, &ln.out, &ln.mid}) scratch_release(*s);
     }
     if (g_ev0) (void)hipEventDestroy(g_ev0);
     if (g_ev1) (void)hipEventDestroy(g_ev1);

@@ -123,6 +123,28 @@ def test_two_runs_are_bit_identical(gpu_lib):
         assert d0["inertia"][k] == d1["inertia"][k] and d0["n_iter"][k] == d1["n_iter"][k]
 
 
+def test_results_survive_shutdown_and_reinit(gpu_lib):
+    """paa_shutdown frees and resets every global scratch buffer -- the HMM statistics' and the diarization work space
+    register themselves like the others -- so the same calls after paa_init(0) allocate afresh and give the same bits."""
+    g = load_golden([p for p in GOLDENS if golden_id(p) == "diar_example"][0])
+    labels = (np.arange(g["M"].shape[1]) // 7) % 3
+
+    def run():
+        stats = aS.train_hmm_compute_statistics(g["M"], labels)
+        return stats, aS.diarize_features(g["M"], 0, random_state=11, return_details=True)
+
+    stats0, (c0, d0) = run()
+    gpu_lib.paa_shutdown()
+    _ffi.init(0)
+    stats1, (c1, d1) = run()
+    for a, b in zip(stats0, stats1):
+        assert np.asarray(a).tobytes() == np.asarray(b).tobytes()
+    assert np.array_equal(c0, c1) and d0["ks"] == d1["ks"]
+    for k in d0["ks"]:
+        for key in ("labels", "centers", "sil", "pair_sums"):
+            assert d0[key][k].tobytes() == d1[key][k].tobytes(), (key, k)
+
+
 def test_constant_row_is_refused_by_the_hmm(gpu_lib):
     g = load_golden([p for p in GOLDENS if golden_id(p) == "diar_const"][0])
     with pytest.raises(ValueError):
