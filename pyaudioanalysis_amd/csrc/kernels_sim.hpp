@@ -285,10 +285,19 @@ __global__ __launch_bounds__(256) void thumb_diag_kernel(const double *__restric
         const long long lo_ = lim_lo - i0, hi_ = lim_hi - d - i0;       // s range of the unmasked cells
         const int s_lo = lo_ < 0 ? 0 : (lo_ > kDiagRun ? kDiagRun : (int)lo_), s_hi = hi_ < 0 ? 0 : (hi_ > kDiagRun ? kDiagRun : (int)hi_);
         const double *pn = p + (long long)M * dstep;
-        // sliding update: + S[i + M][j + M] - S[i][j]; the loads do not depend on the running sum
+        // sliding update: + S[i + M][j + M] - S[i][j]; the loads do not depend on the running sum.  A NaN that LEAVES the
+        // window would stay in the running sum (the reference's window forgets it): the sum restarts there.
 #pragma unroll 8
         for (int s = 0; s < cnt; ++s) {
-            if (s > 0) run += pn[(s - 1) * dstep] - p[(s - 1) * dstep];
+            if (s > 0) {
+                const double gone = p[(s - 1) * dstep];
+                if (gone != gone) {
+                    run = 0.0;
+                    for (int k = 0; k < M; ++k) run += p[(s + k) * dstep];
+                } else {
+                    run += pn[(s - 1) * dstep] - gone;
+                }
+            }
             vmin = nan_min(vmin, run);
             // unmasked: lim_lo <= i and j = i + d < lim_hi (i <= j)
             if (!diag_masked && s >= s_lo && s < s_hi) {
