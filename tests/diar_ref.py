@@ -25,7 +25,11 @@ MARGINS say how far every decision is from flipping: step 4 min |s - 1.1 mean| /
 relative gap (d2_second - d2_best) / d2_second between a window's two nearest centres; for b_c the relative gap between the two
 smallest candidates; for imax the gap between the two best scores."""
 import numpy as np
-from scipy.spatial import distance
+
+try:
+    from scipy.spatial import distance
+except ImportError:          # the np.longdouble restatements and the generators below need NumPy alone
+    distance = None
 
 import hmm_ref
 
@@ -80,10 +84,11 @@ def _assign(Zk, C):
     return labels, d2[np.arange(Zk.shape[0]), labels], margin
 
 
-def kmeans(Zk, k, init, max_iter=300, tol=1e-4):
-    """Lloyd from the initial centres `init` [k][D'].  Returns a dict: labels, centers, n_iter, inertia, margin, strict."""
-    Zk = np.asarray(Zk, dtype=np.float64)
-    C = np.array(init, dtype=np.float64).reshape(k, Zk.shape[1])
+def kmeans(Zk, k, init, max_iter=300, tol=1e-4, dtype=np.float64):
+    """Lloyd from the initial centres `init` [k][D'].  Returns a dict: labels, centers, n_iter, inertia, margin, strict.
+    dtype np.longdouble: the same steps in extended precision (inertia is then a longdouble scalar)."""
+    Zk = np.asarray(Zk, dtype=dtype)
+    C = np.array(init, dtype=dtype).reshape(k, Zk.shape[1])
     n = Zk.shape[0]
     tol_abs = tol * np.mean(np.var(Zk, axis=0))
     old = np.full(n, -1)
@@ -106,7 +111,7 @@ def kmeans(Zk, k, init, max_iter=300, tol=1e-4):
             cnt[e] = 1
             cnt[labels[far]] -= 1
         new = np.where(cnt[:, None] > 0, sums / np.maximum(cnt, 1)[:, None], C)
-        shift = float(((new - C) ** 2).sum())
+        shift = ((new - C) ** 2).sum()
         C = new
         n_iter = it + 1
         if np.array_equal(labels, old):
@@ -118,7 +123,8 @@ def kmeans(Zk, k, init, max_iter=300, tol=1e-4):
     if not strict:
         labels, _, m = _assign(Zk, C)
         margin = min(margin, m)
-    inertia = float(((Zk - C[labels]) ** 2).sum())
+    inertia = ((Zk - C[labels]) ** 2).sum()
+    inertia = float(inertia) if dtype == np.float64 else inertia
     return {"labels": labels.astype(np.int64), "centers": C, "n_iter": n_iter, "inertia": inertia, "margin": margin,
             "strict": strict}
 
@@ -238,3 +244,140 @@ def diarize(X, n_speakers, init_centers=None, random_state=None):
     states, margins, cls = smooth(out["Z"], last)
     out.update({"hmm_states": states, "hmm_margin": float(margins.min()), "cls": cls})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# restatements in a chosen precision (np.longdouble: the reference of the tolerance tests; NumPy alone) and the designed
+# inputs of the edge suite (tests/test_diar_edges_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def standardize_p(X, dtype=np.longdouble):
+    """(mean, var, scale, constant, bound) of X [D][N]: standardize()'s steps in `dtype`."""
+    X = np.asarray(X, dtype=dtype)
+    n = X.shape[1]
+    mean = X.sum(axis=1) / n
+    dev = X - mean[:, None]
+    var = ((dev ** 2).sum(axis=1) - dev.sum(axis=1) ** 2 / n) / n
+    eps = dtype(np.finfo(np.float64).eps)
+    bound = n * eps * var + (n * mean * eps) ** 2
+    constant = var <= bound
+    return mean, var, np.where(constant, dtype(1), np.sqrt(var)), constant, bound
+
+
+def pair_sums_p(Zk, labels, k, dtype=np.longdouble):
+    """S [k][k] in `dtype`: the sum of |z_i - z_j| over i in c, j in c2 (difference form)."""
+    Z = np.asarray(Zk, dtype=dtype)
+    S = np.zeros((k, k), dtype=dtype)
+    for i in range(Z.shape[0]):
+        d = np.sqrt(((Z - Z[i]) ** 2).sum(axis=1))
+        np.add.at(S[labels[i]], labels, d)
+    return S
+
+
+def dim_distances_p(Z, select=None, dtype=np.longdouble):
+    """(column sums [D], mean over the D (D - 1) / 2 pairs) of the Euclidean distances between the FEATURE ROWS of
+    Z [N][D] over the windows `select` (a boolean mask; None: all)."""
+    Z = np.asarray(Z, dtype=dtype)
+    if select is not None:
+        Z = Z[select]
+    D = Z.shape[1]
+    M = np.sqrt(((Z.T[:, None, :] - Z.T[None, :, :]) ** 2).sum(axis=2)) if Z.shape[0] else np.zeros((D, D), dtype=dtype)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return M.sum(axis=0), np.triu(M, 1).sum() / (dtype(0.5) * D * (D - 1))
+
+
+PAIR_KS = (2, 3, 5, 8, 9, 16, 31, 32)
+
+
+def hand_labels(n, ks=PAIR_KS):
+    """labels [len(ks)][n] for one pair-sum launch over several k: a running pattern, then per k > 2 the last cluster EMPTY,
+    cluster 1 a SINGLE window (n - 1, in the last tile) and -- for k >= 5 -- cluster 2 the eleven windows 3..13 alone (wholly
+    inside the first 128-window tile)."""
+    out = np.empty((len(ks), n), dtype=np.int32)
+    t = np.arange(n)
+    for i, k in enumerate(ks):
+        lab = (t * 7 + i + t // 5) % k
+        if k > 2:
+            lab[lab == k - 1] = 0
+        lab[lab == 1] = 0
+        lab[n - 1] = 1
+        if k >= 5:
+            lab[lab == 2] = 3
+            lab[3:14] = 2
+        out[i] = lab
+    return out
+
+
+def scaler_rows(n, seed=9):
+    """(X [7][n], expected constant flags): benign; offset 1e8 with unit noise; offset 1e6 with 1e-3 noise; nearly constant
+    1 + 1e-9 noise (NOT constant by scikit-learn's bound); 1e6 + 1e-9 noise (constant by the bound: its variance is below
+    (n mean eps)^2); exactly constant 2.5; exactly constant 0."""
+    rng = np.random.default_rng(seed)
+    g = rng.standard_normal((7, n))
+    X = np.stack([g[0] * 2.0 - 1.0, 1e8 + g[1], 1e6 + 1e-3 * g[2], 1.0 + 1e-9 * g[3], 1e6 + 1e-9 * g[4], np.full(n, 2.5),
+                  np.zeros(n)])
+    return np.ascontiguousarray(X), np.array([False, False, False, False, True, True, True])
+
+
+def equidistant_case(lead=0):
+    """(Zk [N][3], init [2 + lead][3]): 192 windows at (-2, 0), 256 at (2, 0) and 64 at (0, 4), which are exactly
+    equidistant (d^2 = 20) from the centres (-2, 0) and (2, 0): they belong to the lower index.  Everything is a small
+    dyadic number and the cluster sizes are powers of two, so every distance, sum, centre and the inertia is exact in FP64
+    (FP64 and longdouble restatements agree bit for bit, asserted on the CPU).  lead: that many extra centres at
+    (-50 - 10 i, 0), each with 256 windows on it, in front: the tie is then between clusters lead and lead + 1.
+    The windows are shuffled; N = 512 + 256 lead spans several assign workgroups."""
+    pts = [(-2.0, 0.0)] * 192 + [(2.0, 0.0)] * 256 + [(0.0, 4.0)] * 64
+    init = [(-2.0, 0.0), (2.0, 0.0)]
+    for i in range(lead):
+        pts += [(-50.0 - 10 * i, 0.0)] * 256
+        init.insert(i, (-50.0 - 10 * i, 0.0))
+    Z = np.zeros((len(pts), 3))
+    Z[:, :2] = np.array(pts)
+    Z = Z[np.random.default_rng(3).permutation(len(pts))]
+    C = np.zeros((len(init), 3))
+    C[:, :2] = np.array(init)
+    return np.ascontiguousarray(Z), C
+
+
+FAR_TIES = {5: (0.0, 6.0), 6: (0.0, -6.0), 133: (-6.0, 0.0), 262: (0.0, 6.0)}
+
+
+def two_empty_case():
+    """(Zk [320][2], init [4][2]): centres 2 and 3 attract no window, so both are relocated in iteration 1, to the farthest
+    windows.  Four windows tie for the farthest (d^2 = 36 from centre 0) at indices 5, 6, 133 and 262 -- three different
+    points, so the order of the relocations shows in the centres: cluster 2 must take window 5 and cluster 3 window 6.
+    Cluster 0 keeps 128 windows after giving two away, so its centre is dyadic; run with max_iter = 1."""
+    Z = np.zeros((320, 2))
+    Z[:, 0] = 8.0                                                 # cluster 1: all on its centre
+    ordinary = [i for i in range(0, 320, 2) if i not in FAR_TIES][:126]     # cluster 0: 126 ordinary windows + the four
+    Z[ordinary] = 0.0
+    Z[ordinary[:26], 0] = 1.0
+    for i, p in FAR_TIES.items():
+        Z[i] = p
+    init = np.array([[0.0, 0.0], [8.0, 0.0], [1000.0, 1000.0], [-1000.0, 1000.0]])
+    return Z, init
+
+
+def near_duplicate_case(n=200, d=9, seed=8):
+    """(X [d][n], labels [n]): cluster 2 is 40 windows within 1e-9 of one another (in the last tile, across the tile edge
+    when n > 128), clusters 0 and 1 ordinary windows."""
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((d, n)) * 1.5
+    labels = (np.arange(n) % 2).astype(np.int32)
+    dup = np.arange(110, 150)
+    X[:, dup] = X[:, 110:111] + 1e-9 * rng.standard_normal((d, 40))
+    labels[dup] = 2
+    return np.ascontiguousarray(X), labels
+
+
+def stage_case(seed=31):
+    """(X [17][257], initial centres [3][kept dims]) for the stage dictionary of diarize_clusters_device: three planted
+    speakers, the centres three windows of the standardised, filtered matrix."""
+    rng = np.random.default_rng(seed)
+    means = rng.standard_normal((3, 17)) * 4.0
+    path = rng.integers(3, size=257)
+    X = np.ascontiguousarray((means[path] + rng.standard_normal((257, 17))).T * rng.uniform(0.5, 20.0, 17)[:, None])
+    Z = standardize(X)[0]
+    colsum, _ = dim_distances_p(Z, dtype=np.float64)
+    kept = np.nonzero(colsum < 1.1 * colsum.mean())[0]
+    first = [int(np.flatnonzero(path == c)[0]) for c in range(3)]
+    return X, np.ascontiguousarray(Z[first][:, kept])

@@ -194,3 +194,133 @@ def tie_rows(model, n, rng, X=None):
         for i in rng.choice(idx, min(len(idx), 3 * model.n_dims), replace=False):
             X[r, feat[i]] = thr[i]
     return X
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# np.longdouble links of the boosted models, and designed inputs for the edge suite (tests/test_forest_edges_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def boosted_proba_ld(raw):
+    """Rule 4's probabilities from FP64 raw scores [n][n_outputs], evaluated in np.longdouble."""
+    r = np.asarray(raw, dtype=np.longdouble)
+    with np.errstate(over="ignore", under="ignore"):
+        if r.shape[1] == 1:
+            e = 1 / (1 + np.exp(-r[:, 0]))
+            return np.stack([1 - e, e], axis=1)
+        z = np.exp(r - r.max(axis=1, keepdims=True))
+        return z / z.sum(axis=1, keepdims=True)
+
+
+F32_MAX = float(np.finfo(np.float32).max)
+F32_TINY = float(np.nextafter(np.float32(0), np.float32(1)))          # the smallest float32 subnormal
+BENIGN = -1.0                                                         # left of every boundary threshold below
+
+
+def _f32_up(x):
+    return float(np.nextafter(np.float32(x), np.float32(np.inf)))
+
+
+def _f32_down(x):
+    return float(np.nextafter(np.float32(x), np.float32(-np.inf)))
+
+
+def boundaries():
+    """[(name, threshold, missing_go_to_left, FP64 probe values)]: the places where a split decision turns."""
+    eq = float(np.float32(0.3))
+    a = float(np.float32(1.7))
+    b = _f32_up(a)
+    sub = float(np.float32(1e-40))
+    half_way = 2.0 ** 128 - 2.0 ** 103                                # FLT_MAX + half a float32 ulp: rounds to inf
+    return [
+        ("equal_f32", eq, 0, [eq, _f32_up(eq), _f32_down(eq)]),
+        # the FP64 value is right of the threshold, its float32 rounding left of it -- and the other way round
+        ("rounds_down_across", a + 0.25 * (b - a), 1, [a + 0.4 * (b - a), a + 0.6 * (b - a)]),
+        ("rounds_up_across", a + 0.75 * (b - a), 0, [a + 0.6 * (b - a), a + 0.4 * (b - a)]),
+        ("zero", 0.0, 1, [-0.0, 0.0, F32_TINY, -F32_TINY, 0.4 * F32_TINY, 0.6 * F32_TINY]),
+        ("negative_zero_threshold", -0.0, 0, [0.0, -0.0, F32_TINY]),
+        ("subnormal", sub, 1, [sub, _f32_up(sub), _f32_down(sub)]),
+        ("flt_max", F32_MAX, 0, [F32_MAX, float(np.nextafter(half_way, 0.0)), half_way, -half_way]),
+        ("below_flt_max", _f32_down(F32_MAX), 1, [F32_MAX, _f32_down(F32_MAX), -F32_MAX]),
+        ("nan_goes_left", 0.5, 1, [np.nan, 1.0]),
+        ("nan_goes_right", 0.5, 0, [np.nan, 0.0]),
+    ]
+
+
+def boundary_side(x, thr, miss):
+    """True: left.  scikit-learn's rule, rule 1 and 2 above, with NumPy float32 casts."""
+    with np.errstate(over="ignore"):
+        x32 = np.float64(x).astype(np.float32)
+    return bool(miss) if np.isnan(x32) else bool(np.float64(x32) <= thr)
+
+
+def boundary_rows():
+    """(X [n][n_dims] FP64, want_right [n][n_dims] bool): one row per probe, the other features at BENIGN, then one row
+    per probe position with every feature at a probe."""
+    B = boundaries()
+    rows = []
+    for f, (_, _, _, probes) in enumerate(B):
+        for p in probes:
+            r = np.full(len(B), BENIGN)
+            r[f] = p
+            rows.append(r)
+    for j in range(max(len(b[3]) for b in B)):
+        rows.append(np.array([b[3][j % len(b[3])] for b in B]))
+    X = np.array(rows)
+    right = np.array([[not boundary_side(x, B[f][1], B[f][2]) for f, x in enumerate(r)] for r in X])
+    return X, right
+
+
+def boundary_model(kind, n_classes=3, reverse=False):
+    """One stump per boundary, feature f = boundary f.  The right leaf of tree t is worth 2^-(t+1) (in the last class of an
+    averaged forest, in the raw score of a two-class boosted model, learning rate 1, init 0): the score is the bit mask of
+    the trees that went right, and every partial sum is exact."""
+    from pyaudioanalysis_amd.audioTrainTest import ForestArrays
+    B = boundaries()
+    order = list(range(len(B)))[::-1] if reverse else list(range(len(B)))
+    n = 3 * len(B)
+    cl, cr = -np.ones(n, dtype=np.int64), -np.ones(n, dtype=np.int64)
+    feature, thr = np.full(n, -2, dtype=np.int64), np.full(n, -2.0)
+    miss = np.zeros(n, dtype=np.uint8)
+    boosted = kind == "boosted"
+    value = np.zeros(n) if boosted else np.zeros((n, n_classes))
+    for t, f in enumerate(order):
+        cl[3 * t], cr[3 * t] = 1, 2
+        feature[3 * t], thr[3 * t], miss[3 * t] = f, B[f][1], B[f][2]
+        w = 2.0 ** -(t + 1)
+        if boosted:
+            value[3 * t + 2] = w
+        else:
+            value[3 * t + 1, 0] = 1.0
+            value[3 * t + 2, 0], value[3 * t + 2, n_classes - 1] = 1.0 - w, w
+    classes = np.arange(2 if boosted else n_classes, dtype=np.float64)
+    return ForestArrays(kind, np.arange(0, n + 1, 3), cl, cr, feature, thr, miss, value, classes, len(B),
+                        1.0 if boosted else 0.0, np.zeros(1) if boosted else None), order
+
+
+def boundary_mask(right, order):
+    """The exact score of boundary_model for the decisions `right` [n][n_dims]."""
+    return np.array([sum(2.0 ** -(t + 1) for t, f in enumerate(order) if r[f]) for r in right])
+
+
+def score_model(scores, learning_rate=1.0, init=None):
+    """A boosted model of one stage whose raw score for the row x = (i,) is init + learning_rate * scores[i]: per output a
+    chain over feature 0 with thresholds i + 0.5.  scores [n_rows][n_outputs]; one output is the two-class model."""
+    from pyaudioanalysis_amd.audioTrainTest import ForestArrays
+    S = np.atleast_2d(np.asarray(scores, dtype=np.float64))
+    n_rows, K = S.shape
+    depth = n_rows - 1
+    parts = []
+    for k in range(K):
+        n = 2 * depth + 1
+        cl, cr = -np.ones(n, dtype=np.int64), -np.ones(n, dtype=np.int64)
+        feature, thr, value = np.full(n, -2, dtype=np.int64), np.full(n, -2.0), np.zeros(n)
+        for i in range(depth):
+            cl[2 * i], cr[2 * i], feature[2 * i], thr[2 * i] = 2 * i + 1, 2 * i + 2, 0, i + 0.5
+            value[2 * i + 1] = S[i, k]
+        value[2 * depth] = S[depth, k]
+        parts.append((cl, cr, feature, thr, value))
+    offsets = np.concatenate([[0], np.cumsum([len(p[0]) for p in parts])])
+    cat = [np.concatenate([p[i] for p in parts]) for i in range(5)]
+    n_classes = 2 if K == 1 else K
+    init = np.zeros(K) if init is None else np.asarray(init, dtype=np.float64)
+    return ForestArrays("boosted", offsets, cat[0], cat[1], cat[2], cat[3], np.zeros(offsets[-1], dtype=np.uint8), cat[4],
+                        np.arange(n_classes, dtype=np.float64), 1, learning_rate, init)

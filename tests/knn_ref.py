@@ -28,7 +28,8 @@ def squared_distances(features, X):
     """[n_vec][n_train] sum_d (t_d - x_d)^2 of X [n_vec][n_dims] to features [n_train][n_dims]."""
     T = np.asarray(features, dtype=np.float64)
     X = np.atleast_2d(np.asarray(X, dtype=np.float64))
-    return np.stack([np.sum((T - x) ** 2, axis=1) for x in X])
+    with np.errstate(over="ignore"):            # a squared difference beyond DBL_MAX is inf, as on the device
+        return np.stack([np.sum((T - x) ** 2, axis=1) for x in X])
 
 
 def classify(features, labels, k, X):
@@ -65,3 +66,145 @@ def ambiguous(dist, labels, k):
     pos[order] = np.arange(order.shape[0])
     inside, outside = near & (pos < k), near & (pos >= k)
     return bool(inside.any() and outside.any() and np.unique(lab[near]).shape[0] > 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# seeded models of the GPU suite (tests/test_knn_gpu.py); kept here so that the CPU suite can bound their ambiguity
+# ---------------------------------------------------------------------------------------------------------------------
+AMBIGUOUS_CAP = 0.01            # share of a case's vectors that the restatement check may set aside as ambiguous
+
+# the shipped models too large for a golden file, as seeded models of exactly their shape:
+# name: (n_train, n_dims, n_classes, k, duplicated rows)
+SHAPES = {"knn_sm_shape": (2422, 136, 2, 5, 0), "knn_speaker_10_shape": (1294, 136, 10, 9, 0),
+          "knn_movie8class_shape": (3040, 136, 8, 9, 4)}
+
+EDGES = {
+    # name: (n_train, n_dims, n_classes, k, n_vec, ld)
+    "k1": (300, 20, 3, 1, 65, None),
+    "k32": (500, 33, 5, 32, 47, None),
+    "k32_fewer_rows": (20, 9, 3, 32, 17, None),
+    "c64": (900, 40, 64, 7, 100, None),
+    "d256": (300, 256, 4, 5, 33, None),
+    "d1": (200, 1, 3, 6, 50, None),
+    "single_query": (200, 136, 2, 5, 1, None),
+    "nvec_odd_ld": (400, 17, 4, 9, 37, 53),
+    "nvec_3001": (700, 136, 6, 5, 3001, None),
+}
+
+
+def seeded(n_train, n_dims, n_classes, k, seed, duplicates=0):
+    rng = np.random.default_rng(seed)
+    centres = rng.standard_normal((n_classes, n_dims)) * 1.5
+    labels = rng.integers(0, n_classes, n_train).astype(np.float64)
+    labels[:n_classes] = np.arange(n_classes)                     # every class present: n_classes distinct labels
+    F = centres[labels.astype(int)] + rng.standard_normal((n_train, n_dims))
+    for j in range(duplicates):                                   # duplicated rows with other labels (knn_movie8class)
+        F[n_train - 1 - j] = F[3 * j + 1]
+        labels[n_train - 1 - j] = (labels[3 * j + 1] + 1) % n_classes
+    return F, labels, k
+
+
+def shape_case(name):
+    """(F, labels, k, feats [n_dims][n_vec], mean, std) of a SHAPES entry."""
+    n_train, n_dims, n_classes, k, dup = SHAPES[name]
+    F, labels, k = seeded(n_train, n_dims, n_classes, k, 3, dup)
+    rng = np.random.default_rng(4)
+    n_vec = 203
+    mean, std = rng.normal(0, 2, n_dims), rng.uniform(0.5, 3.0, n_dims)
+    W = F[rng.integers(0, n_train, n_vec)] + 0.8 * rng.standard_normal((n_vec, n_dims))
+    if dup:
+        W[:dup] = F[[3 * j + 1 for j in range(dup)]]               # queries on the duplicated rows
+    return F, labels, k, (W * std + mean).T, mean, std
+
+
+def edge_case(name):
+    """(F, labels, k, feats [n_dims][n_vec], mean, std) of an EDGES entry."""
+    n_train, n_dims, n_classes, k, n_vec, ld = EDGES[name]
+    F, labels, k = seeded(n_train, n_dims, min(n_classes, n_train), k, 20 + len(name))
+    rng = np.random.default_rng(21)
+    mean, std = rng.normal(0, 1, n_dims), rng.uniform(0.5, 2.0, n_dims)
+    W = F[rng.integers(0, n_train, n_vec)] + 0.5 * rng.standard_normal((n_vec, n_dims))
+    return F, labels, k, (W * std + mean).T, mean, std
+
+
+def ambiguous_vectors(features, labels, k, X):
+    with np.errstate(invalid="ignore"):
+        D = np.sqrt(squared_distances(features, X))
+    return np.array([ambiguous(d, labels, k) for d in D])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# integer cases: every squared distance is an exact integer in FP64 whatever the order of the sum, so ascending
+# (d^2, index) is a total order and labels, P and the neighbour list are compared exactly with no vector set aside
+# ---------------------------------------------------------------------------------------------------------------------
+INT_N_TRAIN = (1, 2, 7, 8, 9, 15, 16, 17, 31, 33)
+INT_K = (1, 2, 8, 9, 31, 32)
+INT_DIMS = (1, 7, 8, 9, 255, 256)
+INT_CLASSES = (1, 2, 8, 9, 63, 64)
+INT_N_VEC = (1, 15, 16, 17)
+
+
+def integer_labels(n_train, n_classes, rng):
+    """n_train labels with exactly min(n_classes, n_train) distinct values, so that the model has that many classes.  Only
+    the even class indices are used as labels; the other distinct values are c + 0.5, which vote for no class: every odd
+    class has no training row."""
+    c = min(n_classes, n_train)
+    values = np.array([float(v) if v % 2 == 0 else v - 0.5 for v in range(c)])
+    labels = values[rng.integers(0, c, n_train)]
+    labels[:c] = values
+    return labels
+
+
+def integer_case(n_train, n_dims, n_classes, n_vec, seed, span=1):
+    """(F, labels, X [n_vec][n_dims]): integer training rows and queries in -span..span (mean 0 and std 1 leave them as
+    they are)."""
+    rng = np.random.default_rng(seed)
+    F = rng.integers(-span, span + 1, (n_train, n_dims)).astype(np.float64)
+    X = rng.integers(-span, span + 1, (n_vec, n_dims)).astype(np.float64)
+    return F, integer_labels(n_train, n_classes, rng), X
+
+
+def integer_grid():
+    """(n_train, k, n_dims, n_classes, n_vec) for every n_train x k of the lists, the other three cycling through theirs."""
+    out = []
+    for i, n_train in enumerate(INT_N_TRAIN):
+        for j, k in enumerate(INT_K):
+            c = i * len(INT_K) + j
+            out.append((n_train, k, INT_DIMS[c % 6], INT_CLASSES[(c // 2) % 6], INT_N_VEC[(c // 3) % 4]))
+    return out
+
+
+def tie_kinds(features, labels, k, X):
+    """Counts, over the queries, of the kinds of exact ties the (d^2, index) order has to resolve: 'kth' rows at the k-th
+    distance on both sides of the k boundary; 'lanes' equal-distance rows among the first k + 1 whose indices differ mod 8
+    (different lists of the kernel's eight-list merge); 'tiles' such rows in different 16-row tiles; 'votes' two classes
+    with the same, largest vote count."""
+    lab, n_classes = label_indices(labels)
+    D = squared_distances(features, X)
+    out = {"kth": 0, "lanes": 0, "tiles": 0, "votes": 0}
+    rows = np.arange(D.shape[1])
+    for v in range(D.shape[0]):
+        order = np.lexsort((rows, D[v]))
+        if order.shape[0] > k and D[v, order[k - 1]] == D[v, order[k]]:
+            out["kth"] += 1
+        head = order[:k + 1]
+        same = D[v, head][:, None] == D[v, head][None, :]
+        np.fill_diagonal(same, False)
+        out["lanes"] += bool((same & (head[:, None] % 8 != head[None, :] % 8)).any())
+        out["tiles"] += bool((same & (head[:, None] // 16 != head[None, :] // 16)).any())
+        votes = np.bincount(lab[order[:k]][lab[order[:k]] >= 0], minlength=n_classes)
+        out["votes"] += bool(votes.max() > 0 and np.count_nonzero(votes == votes.max()) > 1)
+    return out
+
+
+def overflow_case():
+    """(F, labels, k, X): queries of +-1e154 in dim 0, training rows of +-1e154 there and small integers elsewhere: the
+    squared distance to a row of the other sign is 4e308 = inf, to a row of the same sign a small exact integer."""
+    rng = np.random.default_rng(77)
+    n_train, n_dims = 40, 9
+    F = rng.integers(-1, 2, (n_train, n_dims)).astype(np.float64)
+    F[:, 0] = np.where(np.arange(n_train) % 3 == 0, 1e154, -1e154)      # 14 rows at +, 26 at -
+    X = rng.integers(-1, 2, (6, n_dims)).astype(np.float64)
+    X[:, 0] = [1e154, -1e154, 1e154, -1e154, 1e154, -1e154]
+    labels = (np.arange(n_train) % 4).astype(np.float64)
+    return F, labels, 32, X

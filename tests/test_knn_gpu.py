@@ -29,9 +29,7 @@ def _by_case(case):
     return [f for f in golden_files("knn") if str(np.load(f, allow_pickle=False)["case"]) == case]
 
 
-def _ambiguous(features, labels, k, X):
-    D = np.sqrt(knn_ref.squared_distances(features, X))
-    return np.array([knn_ref.ambiguous(d, labels, k) for d in D])
+_ambiguous = knn_ref.ambiguous_vectors
 
 
 def _neighbours_agree(nb, want, features, X, exact):
@@ -174,18 +172,6 @@ def test_file_classification_batch_equals_single_calls(gpu_lib):
         assert cid == ids[i] and np.array_equal(p, proba[i]), i
 
 
-def _seeded(n_train, n_dims, n_classes, k, seed, duplicates=0):
-    rng = np.random.default_rng(seed)
-    centres = rng.standard_normal((n_classes, n_dims)) * 1.5
-    labels = rng.integers(0, n_classes, n_train).astype(np.float64)
-    labels[:n_classes] = np.arange(n_classes)                     # every class present: n_classes distinct labels
-    F = centres[labels.astype(int)] + rng.standard_normal((n_train, n_dims))
-    for j in range(duplicates):                                   # duplicated rows with other labels (knn_movie8class)
-        F[n_train - 1 - j] = F[3 * j + 1]
-        labels[n_train - 1 - j] = (labels[3 * j + 1] + 1) % n_classes
-    return F, labels, k
-
-
 def _check_against_restatement(F, labels, k, feats, mean, std, what, ld=None):
     X = (feats.T - mean) / std
     model = audioTrainTest.knn_model(audioTrainTest.Knn(F, labels, k))
@@ -203,6 +189,8 @@ def _check_against_restatement(F, labels, k, feats, mean, std, what, ld=None):
                                                   nb.ctypes.data_as(_ffi.c_i32p)))
     want, wP, wnb = knn_ref.classify(F, labels, k, X)
     amb = _ambiguous(F, labels, k, X)
+    # the vectors set aside are capped: a stated share, which knn_ref alone keeps on the CPU (test_model_edges_ref_cpu.py)
+    assert int(amb.sum()) <= knn_ref.AMBIGUOUS_CAP * X.shape[0], (what, int(amb.sum()), X.shape[0])
     ok = ~amb
     assert np.array_equal(got[ok], want[ok]) and np.array_equal(P[ok], wP[ok])
     _neighbours_agree(nb[ok], wnb[ok], F, X[ok], exact=False)
@@ -210,52 +198,24 @@ def _check_against_restatement(F, labels, k, feats, mean, std, what, ld=None):
     return got, P
 
 
-# the shipped models too large for a golden file, as seeded models of exactly their shape
-SHAPES = {"knn_sm_shape": (2422, 136, 2, 5, 0), "knn_speaker_10_shape": (1294, 136, 10, 9, 0),
-          "knn_movie8class_shape": (3040, 136, 8, 9, 4)}
-
-
-@pytest.mark.parametrize("name", sorted(SHAPES))
+@pytest.mark.parametrize("name", sorted(knn_ref.SHAPES))
 def test_knn_kernel_matches_restatement_on_shipped_shapes(gpu_lib, name):
-    n_train, n_dims, n_classes, k, dup = SHAPES[name]
-    F, labels, k = _seeded(n_train, n_dims, n_classes, k, 3, dup)
-    rng = np.random.default_rng(4)
-    n_vec = 203
-    mean, std = rng.normal(0, 2, n_dims), rng.uniform(0.5, 3.0, n_dims)
-    W = F[rng.integers(0, n_train, n_vec)] + 0.8 * rng.standard_normal((n_vec, n_dims))
-    if dup:
-        W[:dup] = F[[3 * j + 1 for j in range(dup)]]               # queries on the duplicated rows
-    _check_against_restatement(F, labels, k, (W * std + mean).T, mean, std, name)
+    F, labels, k, feats, mean, std = knn_ref.shape_case(name)
+    _check_against_restatement(F, labels, k, feats, mean, std, name)
 
 
-EDGES = {
-    # name: (n_train, n_dims, n_classes, k, n_vec, ld)
-    "k1": (300, 20, 3, 1, 65, None),
-    "k32": (500, 33, 5, 32, 47, None),
-    "k32_fewer_rows": (20, 9, 3, 32, 17, None),
-    "c64": (900, 40, 64, 7, 100, None),
-    "d256": (300, 256, 4, 5, 33, None),
-    "d1": (200, 1, 3, 6, 50, None),
-    "single_query": (200, 136, 2, 5, 1, None),
-    "nvec_odd_ld": (400, 17, 4, 9, 37, 53),
-    "nvec_3001": (700, 136, 6, 5, 3001, None),
-}
-
-
-@pytest.mark.parametrize("name", sorted(EDGES))
+@pytest.mark.parametrize("name", sorted(knn_ref.EDGES))
 def test_knn_kernel_edges(gpu_lib, name):
-    n_train, n_dims, n_classes, k, n_vec, ld = EDGES[name]
-    F, labels, k = _seeded(n_train, n_dims, min(n_classes, n_train), k, 20 + len(name))
-    rng = np.random.default_rng(21)
-    mean, std = rng.normal(0, 1, n_dims), rng.uniform(0.5, 2.0, n_dims)
-    W = F[rng.integers(0, n_train, n_vec)] + 0.5 * rng.standard_normal((n_vec, n_dims))
-    got, P = _check_against_restatement(F, labels, k, (W * std + mean).T, mean, std, name, ld=ld)
+    n_train, n_dims, n_classes, k, n_vec, ld = knn_ref.EDGES[name]
+    F, labels, k, feats, mean, std = knn_ref.edge_case(name)
+    got, P = _check_against_restatement(F, labels, k, feats, mean, std, name, ld=ld)
     assert P.shape == (n_vec, n_classes)
 
 
 def test_nan_query_returns(gpu_lib):
-    """A zero std makes a query NaN: documented answer P = 0, label 0, no neighbours."""
-    F, labels, k = _seeded(100, 5, 3, 4, 9)
+    """A zero std makes a query NaN: documented answer P = 0, label 0, no neighbours.  The two columns next to it are
+    (2 - 1) / 0 = inf: every squared distance is inf, so the neighbours are the first k rows in index order."""
+    F, labels, k = knn_ref.seeded(100, 5, 3, 4, 9)
     model = audioTrainTest.knn_model(audioTrainTest.Knn(F, labels, k))
     feats = np.ones((5, 3))
     std = np.ones(5)
@@ -265,6 +225,12 @@ def test_nan_query_returns(gpu_lib):
     got, P, nb = model.predict(feats, np.ones(5), std, neighbors=True)
     assert got[1] == 0 and np.all(P[1] == 0) and np.all(nb[1] == -1)
     assert got.shape == (3,) and P.shape == (3, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        X = (feats.T - np.ones(5)) / std
+    want, wP, wnb = knn_ref.classify(F, labels, k, X[[0, 2]])
+    assert np.array_equal(wnb, np.tile(np.arange(k), (2, 1)))
+    for col, w in zip((0, 2), range(2)):
+        assert got[col] == want[w] and np.array_equal(P[col], wP[w]) and np.array_equal(nb[col], wnb[w]), col
 
 
 def test_one_hour_clip_through_the_device_path(gpu_lib):
