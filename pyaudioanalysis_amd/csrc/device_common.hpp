@@ -290,6 +290,12 @@ __device__ __forceinline__ double wscan_incl(double v) {
     v += dpp_mov_rows<0x143, 0xC>(v);
     return v;
 }
+// hand a group's value to the group after it: rows 1..3 receive lane 15 of the row before (row_bcast15), row 0 keeps `first`
+__device__ __forceinline__ double rows_from_prev(double v, double first) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(first), __double2loint(v), 0x142, 0xE, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(first), __double2hiint(v), 0x142, 0xE, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
 
 // ---- FP64 helpers of the feature stages: hardware seeds (v_rsq_f64 / v_rcp_f64) + Newton steps instead of libm's
 // general-purpose sequences (which also handle sub-normals, infinities and the IEEE division corner cases)

@@ -588,6 +588,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     double hold[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};    // ... and the row's last seven values / deltas, waiting for
     double holdd[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // their 64-byte chunk (store_row_chunked)
     bool first_quad = true;          // the run's first iteration (its first HALO frames belong to the run before when r0 > 0)
+    double rX_carry = 0.0;           // 1 / (sum X + 400 eps) of the quad's last frame, for the flux of the next quad's first
     int n_done = 0;                  // quads of this run whose FFT stages are complete (pacing)
 
     // software prefetch of the next quad's samples (NPRE x 16 B per lane) into registers
@@ -841,20 +842,22 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // X^2 is accumulated in five 5-bin chunks: their sum is the lane total (roll-off scan), and cut at the lane's
         // 40-bin block boundary they give the spectral-entropy block energies (:85-107) without a second sweep.
         // sum(m^2 X) (spread, below) rides along: m^2 is a compile-time constant
-        double sXa = 0.0, sXb = 0.0, sMa = 0.0, sMb = 0.0, sQa = 0.0, sQb = 0.0, sVa = 0.0, sVb = 0.0, mx = 0.0;
+        double sXa = 0.0, sXb = 0.0, sMa = 0.0, sMb = 0.0, sQa = 0.0, sQb = 0.0, mx = 0.0;
         double c5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int m = 0; m < 24; m += 2) {
             const double X0 = Xc[m], X1 = Xc[m + 1];
             sXa += X0; sXb += X1;
-            sVa += Xv[m]; sVb += Xv[m + 1];
             sMa = fma((double)m, X0, sMa); sMb = fma((double)(m + 1), X1, sMb);
             sQa = fma((double)(m * m), X0, sQa); sQb = fma((double)((m + 1) * (m + 1)), X1, sQb);
             c5[m / 5] = fma(X0, X0, c5[m / 5]); c5[(m + 1) / 5] = fma(X1, X1, c5[(m + 1) / 5]);
             mx = fmax(mx, fmax(X0, X1));
         }
-        sXa += Xc[24]; sVa += Xv[24]; sMa = fma(24.0, Xc[24], sMa); sQa = fma(576.0, Xc[24], sQa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = fmax(mx, Xc[24]);
-        const double cs = ((c5[0] + c5[1]) + (c5[2] + c5[3])) + c5[4];
+        sXa += Xc[24]; sMa = fma(24.0, Xc[24], sMa); sQa = fma(576.0, Xc[24], sQa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = fmax(mx, Xc[24]);
+        // the lane's energy as the running sum of its chunks: the prefixes pc[1..4] serve the roll-off below, which so uses
+        // the SAME sums as cs, the scan and the total sP (the energy up to a chunk's end is one and the same number everywhere)
+        const double pc2 = c5[0] + c5[1], pc3 = pc2 + c5[2], pc4 = pc3 + c5[3];
+        const double cs = pc4 + c5[4];
         // Lane i holds bins [25 i, 25 i + 25); block b holds bins [40 b, 40 b + 40).  The first kcut chunks of the lane
         // lie in block floor(25 i / 40), the rest in the next one; the pattern repeats every 8 lanes (200 bins):
         // kcut = 5 3 5 1 4 5 2 5.  "Home" lanes (i & 7 in {0,2,4,5,7}) are the first lane of a block: block energy =
@@ -877,12 +880,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         double sX = sXa + sXb;
         const double sXl = sX, sMl = sMa + sMb;        // the lane's own sum X, sum m X (spread)
         double sIX = f0 * fma(base_k, sX, sMl);
-        double sXp = sVa + sVb;
-        sX = group_sum(sX); sXp = group_sum(sXp);
+        sX = group_sum(sX);
         sIX = group_sum(sIX); mx = group_max(mx);
         // np.sum(X + eps) (:118-119) = sum X + 400 eps up to rounding
         const double sXe = sX + (double)NF * kEps;
-        sXp += (double)NF * kEps;
         const double run_incl = group_scan_incl(cs);
         const double sP = dpp_bcast15(run_incl);            // total = inclusive scan at lane 15
 
@@ -905,7 +906,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         const double den = sX * r + kEps;
         const double rden = fast_div(1.0, den);
         const double cen = (sIX * r) * rden;
-        const double rX = fast_div(1.0, sXe), rXp = fast_div(1.0, sXp);
+        // flux scales: 1 / np.sum(X + eps) of this frame and of the one before.  The latter IS the rX of frame t - 1 (same
+        // bins, same per-lane order, same group_sum: the same bits), so it is handed on instead of summed again: inside the
+        // quad from the group before, into group 0 from the last group of the iteration before.  A run's first quad has no
+        // such iteration: its group 0 is frame 0 (previous spectrum = itself, so rXp = rX) or a halo frame that is not stored
+        const double rX = fast_div(1.0, sXe);
+        double rXp = rows_from_prev(rX, rX_carry);
+        if (first_quad) rXp = (g == 0) ? rX : rXp;
+        rX_carry = readlane63(rX);
         // spread: sum (ind - C)^2 X / max = f0^2/max * sum ((k+1) - C/f0)^2 X; over the lane's bins k + 1 = base_k + m:
         // sum (cb + m)^2 X = cb (cb sum X + 2 sum m X) + sum m^2 X from the sums of sweep A (|cb + m| < 400, so the terms
         // exceed the result by at most 400^2 / (smallest (cb + m)^2) where that bin dominates: far below T_ROW_SPREAD)
@@ -927,17 +935,31 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         sFl = group_sum(sFl);
         const double spread = fast_sqrt(sSp * rden);
 
-        // roll-off (:127-140): first k with cumsum(X^2)[k] + eps > 0.9 sum(X^2).  The running energy never decreases, so the
-        // first bin that qualifies is the number of bins that do not (one compare and one add-with-carry per bin)
-        int below = 0;
+        // roll-off (:127-140): first k with cumsum(X^2)[k] + eps > 0.9 sum(X^2), in two levels.  The running energy is
+        // defined as [energy before the lane (scan)] + [the lane's whole chunks before the bin (pc)] + [the squares inside the
+        // bin's chunk, added in order]; it never decreases along the chunk ends, so the chunk that holds the crossing is the
+        // number of chunk ends that do not qualify (five compares; the lane's last end is the scan value itself, whose last
+        // is sP) and only that chunk's five bins are scanned.  Registers are chosen by selects on the compare masks: a
+        // dynamically indexed array would go to scratch.  (A crossing the chunk ends place in a chunk whose in-order sums
+        // all miss it by a rounding lands on the chunk's last bin.)
+        int below;
         {
             const double thr = 0.90 * sP;
-            double run = run_incl - cs;
+            const double base = run_incl - cs;
+            const double s1 = base + c5[0], s2 = base + pc2, s3 = base + pc3, s4 = base + pc4;
+            const bool n0 = !(s1 + kEps > thr), n1 = !(s2 + kEps > thr), n2 = !(s3 + kEps > thr), n3 = !(s4 + kEps > thr);
+            const bool n4 = !(run_incl + kEps > thr);
+            const int nb = (int)n0 + (int)n1 + (int)n2 + (int)n3 + (int)n4;          // chunks that end below the threshold
+            const unsigned long long m1 = __ballot(nb >= 1), m2 = __ballot(nb >= 2), m3 = __ballot(nb >= 3), m4 = __ballot(nb >= 4);
+            double run = sel64(m4, s4, sel64(m3, s3, sel64(m2, s2, sel64(m1, s1, base))));
+            int in = 0;
 #pragma unroll
-            for (int m = 0; m < 25; ++m) {
-                run = fma(Xc[m], Xc[m], run);
-                below += (run + kEps > thr) ? 0 : 1;
+            for (int u = 0; u < 5; ++u) {
+                const double x = sel64(m4, Xc[20 + u], sel64(m3, Xc[15 + u], sel64(m2, Xc[10 + u], sel64(m1, Xc[5 + u], Xc[u]))));
+                run = fma(x, x, run);
+                in += (run + kEps > thr) ? 0 : 1;
             }
+            below = (nb >= 5) ? 25 : 5 * nb + min(in, 4);
         }
         const int first = group_min_i((below < 25) ? 25 * i + below : 0x7fffffff);
 
