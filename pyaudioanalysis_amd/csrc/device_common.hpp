@@ -390,6 +390,16 @@ template <> __device__ __forceinline__ double load_sample<stereo16>(const stereo
 }
 template <typename T> __host__ __device__ constexpr double sample_scale() { return 1.0 / 32768.0; }
 template <> __host__ __device__ constexpr double sample_scale<stereo16>() { return 1.0 / 65536.0; }
+// host: the plan's sample_kind (0 int16, 1 float64, 2 interleaved stereo int16) as the kernels' sample type -- calls
+// f(SampleTag<T>()); a generic lambda reads T back with PAA_SAMPLE_T(tag)
+template <typename T> struct SampleTag { typedef T type; };
+#define PAA_SAMPLE_T(tag) typename decltype(tag)::type
+template <typename F>
+inline auto with_sample_type(int sample_kind, F &&f) {
+    if (sample_kind == 0) return f(SampleTag<int16_t>());
+    if (sample_kind == 2) return f(SampleTag<stereo16>());
+    return f(SampleTag<double>());
+}
 
 // Sign codes: only sums of |s_n - s_{n-1}| are ever used, so a sample's sign is kept as a small non-negative code whose
 // differences are the sign differences (up to the factor `sh` applied once to the wave total).

@@ -1,6 +1,5 @@
 // Speaker diarization (kernels_diar.hpp: standardisation, feature-row distances, k-means, cluster-pair distance sums) -- own
 // translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <cstdlib>
 #include <cstring>
 

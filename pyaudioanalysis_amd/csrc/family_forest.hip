@@ -1,6 +1,5 @@
 // Tree-ensemble classification (kernels_forest.hpp: audioTrainTest.classifier_wrapper for the "randomforest", "extratrees"
 // and "gradientboosting" models) -- own translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <cstdlib>
 #include <cstring>
 

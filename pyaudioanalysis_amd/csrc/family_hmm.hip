@@ -1,6 +1,5 @@
 // Gaussian HMM segmentation (kernels_hmm.hpp: emission log-likelihoods, Viterbi by segments, training statistics) -- own
 // translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <cstdlib>
 #include <cstring>
 

@@ -1,6 +1,5 @@
 // k-nearest-neighbour classification (kernels_knn.hpp: audioTrainTest.Knn.classify for the shipped knn_* models) -- own
 // translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <cstdlib>
 #include <cstring>
 

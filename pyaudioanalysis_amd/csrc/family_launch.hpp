@@ -1,8 +1,9 @@
 // Launch entry points of the feature-kernel families.  Every family is its own translation unit (family_<name>.hip: its
-// kernels are instantiated there and nowhere else, so the families compile in parallel); the host side of the library
-// (paa_lib.hip and the lib_*.hpp units it is made of) sees only these functions and the families' host-side layout /
-// selection code.  All of them queue ONE kernel on `stream` and return 0, or -1 when the launch failed (hipGetLastError
-// has the reason).  sample_kind: 0 int16, 1 float64, 2 interleaved stereo int16 (summed in the kernels' loads).
+// kernels AND the host ladder that picks an instance are there and nowhere else, so the families compile in parallel); the
+// host side of the library (paa_lib.hip and the lib_*.hpp units it is made of) sees only these functions and the families'
+// host-side layout / selection code in the kernel headers.  All of them queue ONE kernel on `stream` and return 0, or -1 when
+// the launch failed (hipGetLastError has the reason).  The one-wave families (fast, ct, tri, mix, blu, generic) take their
+// layout and one TileArgs record, and launch through tile_launch below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,36 @@
 #include "kernels_blu.hpp"
 
 namespace paa {
+// what every launch of a one-wave family over a tile list needs (lib_dispatch.hpp: tile_execute fills it from the plan)
+struct TileArgs {
+    const PlanDev &P;
+    const unsigned char *blob;       // the family's device tables
+    const void *d_packed;            // the samples; sample_kind: 0 int16, 1 float64, 2 interleaved stereo int16 (summed in the kernels' loads)
+    int sample_kind;
+    const ClipDev *clips;
+    const ClipNorm *norms;
+    const Tile *tiles;
+    long long n_tiles;
+    double *d_out;
+    hipStream_t stream;
+};
+// the launch of every one-wave family: `waves` tiles per workgroup, one wave each.  `attr` is the cache of THIS kernel
+// instance (a static of the caller, which is a template over the instance); the attribute is raised to exactly `lds`
+// bytes, again after paa_shutdown -> paa_init (LdsAttrCache's generation)
+template <typename L, typename T>
+int tile_launch(void (*kernel)(PlanDev, L, const unsigned char *, const T *, const ClipDev *, const ClipNorm *, const Tile *, int, double *),
+                LdsAttrCache &attr, int waves, size_t lds, const L &layout, const TileArgs &a) {
+    if (!attr.covers(lds)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return -1;
+        attr.set(lds);
+    }
+    const unsigned grid = (unsigned)((a.n_tiles + waves - 1) / waves);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, a.stream, a.P, layout, a.blob, (const T *)a.d_packed, a.clips, a.norms,
+                       a.tiles, (int)a.n_tiles, a.d_out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 namespace wgr { struct WgrTab; }
 namespace svc {
 constexpr int kMaxClasses = 16;
@@ -93,32 +124,21 @@ constexpr int kIntsPerK = hmm::kMaxStates + 1;      // cluster sizes and the num
 }  // namespace diar
 namespace launch {
 
-// kernels_fast.hpp: window 800, step 400 / 800, int16
-int fast(const FastLaunch &fl, const PlanDev &P, const FastTables &ft, const void *d_packed, const ClipDev *clips,
-         const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out, hipStream_t stream);
+// kernels_fast.hpp: window 800, step 400 / 800, int16 (a.blob: FastTables::d_blob)
+int fast(const FastLaunch &fl, const TileArgs &a);
 // kernels_ct.hpp: windows 2 RA RB (800, 640, 400, 320)
-int ct(const ct::CtLaunch &cl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-       const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out, hipStream_t stream);
+int ct(const ct::CtLaunch &cl, const TileArgs &a);
 // kernels_tri.hpp: three-pass register FFT (2400, 2205, 1764, 1920, 1600, 1200, 1102 features, 551; 1024, 2048, 512); three units
-int tri(const tri::TriLaunch &tl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-        const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out, hipStream_t stream);
-int tri_part_a(const tri::TriLaunch &tl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-               const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-               hipStream_t stream);
-int tri_part_b(const tri::TriLaunch &tl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-               const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-               hipStream_t stream);
-int tri_part_c(const tri::TriLaunch &tl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-               const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-               hipStream_t stream);
+int tri(const tri::TriLaunch &tl, const TileArgs &a);
+int tri_part_a(const tri::TriLaunch &tl, const TileArgs &a);
+int tri_part_b(const tri::TriLaunch &tl, const TileArgs &a);
+int tri_part_c(const tri::TriLaunch &tl, const TileArgs &a);
 // kernels_mix.hpp: in-place mixed-radix transform (every other length made of 2, 3, 5, 7, 11, 13)
-int mix(const mix::MixLayout &ml, size_t lds, int sample_kind, const PlanDev &P, const unsigned char *blob,
-        const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-        hipStream_t stream);
+int mix(const mix::MixLayout &ml, const TileArgs &a);
 // kernels_blu.hpp: Bluestein convolution on power-of-two transforms (lengths with a prime factor above 13)
-int blu(const blu::BluLayout &bl, size_t lds, int sample_kind, const PlanDev &P, const unsigned char *blob,
-        const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-        hipStream_t stream);
+int blu(const blu::BluLayout &bl, const TileArgs &a);
+// kernels_generic.hpp: Stockham passes in LDS (what is left)
+int generic(const GenLayout &gl, const TileArgs &a);
 // kernels_wgr.hpp: workgroup-wide three-pass register transform with fused features (16 000- / 8 000-sample windows); `runs`:
 // runs of consecutive frames, one workgroup walks runs b, b + grid, ...
 int wgr(int shape_id, int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
@@ -133,11 +153,6 @@ int wgs(int r0, int q, int sample_kind, const PlanDev &P, const void *d_packed, 
 // ... and the features of those frames from the unit-major rows (one workgroup per frame)
 int wgs_feat(int r0, int q, const PlanDev &P, const wg::FrameRef *frames, int n_frames, const ClipDev *clips, const double *spec,
              const double *tfeat, const double *psum, double *d_out, hipStream_t stream);
-// kernels_generic.hpp: Stockham passes in LDS (what is left)
-int generic(const GenLayout &gl, size_t lds, int sample_kind, const PlanDev &P, const unsigned char *blob,
-            const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles,
-            double *d_out, hipStream_t stream);
-
 // kernels_svc.hpp: multi-class probabilistic SVC over the columns of feats [n_dims][ld] (two kernels: the per-class sums go to
 // `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,

@@ -1,6 +1,5 @@
 // The multi-class probabilistic SVC (kernels_svc.hpp: audioTrainTest.classifier_wrapper for the shipped SVM models) -- own
 // translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <cstdlib>
 #include <cstring>
 

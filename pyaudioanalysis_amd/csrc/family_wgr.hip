@@ -1,6 +1,5 @@
 // The workgroup-wide three-pass register transform with fused features (kernels_wgr.hpp: 16 000- and 8 000-sample windows) -- own
 // translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -21,9 +20,9 @@ static int wgr_modes(int mode, const PlanDev &P, const void *d_packed, const Cli
 template <typename SH>
 static int wgr_kinds(int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
                      const Tile *runs, long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream) {
-    if (sample_kind == 0) return wgr_modes<SH, int16_t>(mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
-    if (sample_kind == 2) return wgr_modes<SH, stereo16>(mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
-    return wgr_modes<SH, double>(mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
+    return with_sample_type(sample_kind, [&](auto tag) {
+        return wgr_modes<SH, PAA_SAMPLE_T(tag)>(mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
+    });
 }
 int wgr(int shape_id, int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
         const Tile *runs, long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream) {

@@ -1,6 +1,5 @@
 // The real-input split of the long even windows on three register passes per sub-transform (kernels_wgs.hpp: 12 / 6 x 3675 samples = 44 100 /
 // 22 050, 12 / 8 / 6 x 4000 = 48 000 / 32 000 / 24 000) -- own translation unit, see family_launch.hpp.
-#define PAA_NO_HOST_LAUNCHERS
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -33,9 +32,9 @@ template <int R0, typename SH>
 static int wgs_kinds(int sample_kind, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
                      const wg::FrameRef *tasks, int n_tasks, int *counter, int num_cu, double *spec, double *tfeat, double *psum,
                      double *d_out, hipStream_t stream) {
-    if (sample_kind == 0) return wgs_one<int16_t, R0, SH>(P, d_packed, clips, norms, tasks, n_tasks, counter, num_cu, spec, tfeat, psum, d_out, stream);
-    if (sample_kind == 2) return wgs_one<stereo16, R0, SH>(P, d_packed, clips, norms, tasks, n_tasks, counter, num_cu, spec, tfeat, psum, d_out, stream);
-    return wgs_one<double, R0, SH>(P, d_packed, clips, norms, tasks, n_tasks, counter, num_cu, spec, tfeat, psum, d_out, stream);
+    return with_sample_type(sample_kind, [&](auto tag) {
+        return wgs_one<PAA_SAMPLE_T(tag), R0, SH>(P, d_packed, clips, norms, tasks, n_tasks, counter, num_cu, spec, tfeat, psum, d_out, stream);
+    });
 }
 #define PAA_WGS_ARGS sample_kind, P, d_packed, clips, norms, tasks, n_tasks, counter, num_cu, spec, tfeat, psum, d_out, stream
 int wgs(int r0, int q, int sample_kind, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,

@@ -729,7 +729,7 @@ struct CtLaunch {
     int shape = -1;                 // 0: 25 x 16 (W 800), 1: 20 x 16 (W 640), 2: 10 x 16 (W 320), 3: 25 x 8 (W 400)
     int waves = 8;
     size_t lds = 0;
-    const char *name = "";
+    const char *name = "";          // the kernel name behind the mode's prefix (lib_dispatch.hpp: mode_kernel_name)
     TabLayout layout;
 };
 
@@ -828,15 +828,13 @@ typedef Shape<10, 16> S320;
 typedef Shape<25, 8> S400;
 
 // returns 1 when a register-FFT instance exists for this window (fills cl and the table blob), 0 otherwise
-inline int ct_select(int window, int mode, double fs, const FftPlan &fft, const MelTable *mel, const ChromaTable *chroma,
+inline int ct_select(int window, double fs, const FftPlan &fft, const MelTable *mel, const ChromaTable *chroma,
                      CtLaunch &cl, std::vector<unsigned char> &blob) {
     const int sh = ct_shape_of(window);
     if (sh < 0 || !fft.even) return 0;
     cl.shape = sh;
-    static const char *names[3][4] = {{"st_ct_25x16", "st_ct_20x16", "st_ct_10x16", "st_ct_25x8"},
-                                      {"spectrogram_ct_25x16", "spectrogram_ct_20x16", "spectrogram_ct_10x16", "spectrogram_ct_25x8"},
-                                      {"chromagram_ct_25x16", "chromagram_ct_20x16", "chromagram_ct_10x16", "chromagram_ct_25x8"}};
-    cl.name = names[mode][sh];
+    static const char *names[4] = {"ct_25x16", "ct_20x16", "ct_10x16", "ct_25x8"};
+    cl.name = names[sh];
     switch (sh) {
         case 0: ct_fill<S800>(fft, mel, chroma, fs, cl, blob); break;
         case 1: ct_fill<S640>(fft, mel, chroma, fs, cl, blob); break;
@@ -846,60 +844,6 @@ inline int ct_select(int window, int mode, double fs, const FftPlan &fft, const 
     if (cl.lds > 160 * 1024) return 0;
     return 1;
 }
-
-#if !defined(PAA_NO_HOST_LAUNCHERS) || defined(PAA_LAUNCH_CT)      // (kernels are instantiated only in family_ct*.hip)
-template <typename SH, typename T, int MODE, int DELTAS, int NW>
-inline int ct_launch_one(const CtLaunch &cl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                         const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                         hipStream_t stream) {
-    static LdsAttrCache attr;
-    if (!attr.covers(cl.lds)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&st_ct_kernel<SH, T, MODE, DELTAS, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl.lds) != hipSuccess) return -1;
-        attr.set(cl.lds);
-    }
-    const unsigned grid = (unsigned)((n_tiles + NW - 1) / NW);
-    hipLaunchKernelGGL((st_ct_kernel<SH, T, MODE, DELTAS, NW>), dim3(grid), dim3(64 * NW), cl.lds, stream, P, cl.layout, blob,
-                       (const T *)d_packed, clips, norms, tiles, (int)n_tiles, d_out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <typename SH, typename T>
-inline int ct_launch_mode(const CtLaunch &cl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                          const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                          hipStream_t stream) {
-#define PAA_CT_GO(MODE, DELTAS)                                                                                          \
-    return ct_launch_one<SH, T, MODE, DELTAS, 8>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (P.mode == 1) { PAA_CT_GO(1, 0) }
-    if (P.mode == 2) { PAA_CT_GO(2, 0) }
-    if (P.deltas) { PAA_CT_GO(0, 1) }
-    PAA_CT_GO(0, 0)
-#undef PAA_CT_GO
-}
-
-template <typename T>
-inline int ct_launch_shape(const CtLaunch &cl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                           const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                           hipStream_t stream) {
-    switch (cl.shape) {
-        case 0: return ct_launch_mode<S800, T>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-        case 1: return ct_launch_mode<S640, T>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-        case 2: return ct_launch_mode<S320, T>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-        case 3: return ct_launch_mode<S400, T>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-        default: return -1;
-    }
-}
-
-// sample_kind 0: int16, 1: float64, 2: interleaved stereo int16 (summed in the loads)
-inline int ct_launch(const CtLaunch &cl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                     const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                     hipStream_t stream) {
-    if (sample_kind == 0) return ct_launch_shape<int16_t>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (sample_kind == 2) return ct_launch_shape<stereo16>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    return ct_launch_shape<double>(cl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-}
-
-#endif  // PAA_NO_HOST_LAUNCHERS
 
 }  // namespace ct
 }  // namespace paa

@@ -1193,49 +1193,4 @@ inline int fast_select(int window, int step, int sample_kind, double fs, FastTab
     return 1;
 }
 
-#if !defined(PAA_NO_HOST_LAUNCHERS) || defined(PAA_LAUNCH_FAST)      // (kernels are instantiated only in family_fast*.hip)
-template <int S, int DELTAS, int FIXED, int NW>
-inline int fast_launch_one(const FastLaunch &fl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                           const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles,
-                           double *d_out, hipStream_t stream) {
-    static LdsAttrCache attr;
-    if (!attr.covers(fl.lds)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&f800::st_fast_800_kernel<S, DELTAS, FIXED, NW>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl.lds) != hipSuccess) return -1;
-        attr.set(fl.lds);
-    }
-    const unsigned grid = (unsigned)((n_tiles + NW - 1) / NW);
-    hipLaunchKernelGGL((f800::st_fast_800_kernel<S, DELTAS, FIXED, NW>), dim3(grid), dim3(64 * NW), fl.lds, stream,
-                       P, fl.layout, blob, (const int16_t *)d_packed, clips, norms, tiles, (int)n_tiles, d_out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-template <int S, int NW>
-inline int fast_launch_step(const FastLaunch &fl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                            const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles,
-                            double *d_out, hipStream_t stream) {
-    if (fl.layout.fixed_lists)
-        return P.deltas ? fast_launch_one<S, 1, 1, NW>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream)
-                        : fast_launch_one<S, 0, 1, NW>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    return P.deltas ? fast_launch_one<S, 1, 0, NW>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream)
-                    : fast_launch_one<S, 0, 0, NW>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-}
-
-inline int fast_launch(const FastLaunch &fl, const PlanDev &P, const FastTables &ft, const void *d_packed,
-                       const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles,
-                       double *d_out, hipStream_t stream) {
-    if (!ft.d_blob) return -1;
-    const unsigned char *blob = reinterpret_cast<const unsigned char *>(ft.d_blob);
-    if (fl.variant == 800 && fl.waves_per_cu == 8)
-        return fast_launch_step<400, 8>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (fl.variant == 1600 && fl.waves_per_cu == 8)
-        return fast_launch_step<800, 8>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-#ifdef PAA_EXPERIMENTS      // the one-wave-per-SIMD instances (NW = 4, ~340 registers) are the A/B baseline of scripts/ab_waves.sh
-    if (fl.variant == 800) return fast_launch_step<400, 4>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (fl.variant == 1600) return fast_launch_step<800, 4>(fl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-#endif
-    return -1;
-}
-
-#endif  // PAA_NO_HOST_LAUNCHERS
 }  // namespace paa

@@ -59,22 +59,15 @@ inline int launch_chroma_tail(const PlanDev &P, int sample_kind, const void *d_s
     } else {
         spill = nullptr;
     }
-    if (lds > 64 * 1024) {
-        const void *fn = sample_kind == 0 ? reinterpret_cast<const void *>(&chroma_tail_kernel<int16_t>)
-                       : sample_kind == 2 ? reinterpret_cast<const void *>(&chroma_tail_kernel<stereo16>)
-                                          : reinterpret_cast<const void *>(&chroma_tail_kernel<double>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    }
-    if (sample_kind == 0)
-        hipLaunchKernelGGL(chroma_tail_kernel<int16_t>, dim3(count), dim3(256), lds, stream, P, (const int16_t *)d_sig,
-                           pos0, n_total, norms, d_out, spill);
-    else if (sample_kind == 2)        // interleaved stereo int16, summed in the loads (fused stereo_to_mono)
-        hipLaunchKernelGGL(chroma_tail_kernel<stereo16>, dim3(count), dim3(256), lds, stream, P, (const stereo16 *)d_sig,
-                           pos0, n_total, norms, d_out, spill);
-    else
-        hipLaunchKernelGGL(chroma_tail_kernel<double>, dim3(count), dim3(256), lds, stream, P, (const double *)d_sig,
-                           pos0, n_total, norms, d_out, spill);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return with_sample_type(sample_kind, [&](auto tag) {
+        typedef PAA_SAMPLE_T(tag) T;          // (stereo16: interleaved int16, summed in the loads -- fused stereo_to_mono)
+        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&chroma_tail_kernel<T>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return -1;
+        hipLaunchKernelGGL(chroma_tail_kernel<T>, dim3(count), dim3(256), lds, stream, P, (const T *)d_sig, pos0, n_total, norms, d_out,
+                           spill);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }
 
 }  // namespace paa

@@ -1528,7 +1528,7 @@ struct TriLaunch {
     int shape = -1;                 // index into the shape list above
     int waves = 0;
     size_t lds = 0;
-    const char *name = "";
+    const char *name = "";          // the kernel name behind the mode's prefix (lib_dispatch.hpp: mode_kernel_name)
     TriLayout layout;
 };
 
@@ -1736,16 +1736,9 @@ inline int tri_select(int window, int mode, double fs, const MelTable *mel, cons
     const int sh = tri_shape_of(window);
     if (sh < 0) return 0;
     tl.shape = sh;
-    static const char *names[3][12] = {
-        {"st_tri_20x20x3", "st_tri_r21x21x5", "st_tri_21x21x2", "st_tri_20x16x3", "st_tri_20x20x2", "st_tri_20x10x3", "st_tri_r29x19",
-         "st_tri_r19x29x2", "st_tri_8x8x8", "st_tri_16x16x4", "st_tri_4x8x8", "st_tri_4x4x8"},
-        {"spectrogram_tri_20x20x3", "spectrogram_tri_r21x21x5", "spectrogram_tri_21x21x2", "spectrogram_tri_20x16x3",
-         "spectrogram_tri_20x20x2", "spectrogram_tri_20x10x3", "spectrogram_tri_r29x19", "spectrogram_tri_r19x29x2",
-         "spectrogram_tri_8x8x8", "spectrogram_tri_16x16x4", "spectrogram_tri_4x8x8", "spectrogram_tri_4x4x8"},
-        {"chromagram_tri_20x20x3", "chromagram_tri_r21x21x5", "chromagram_tri_21x21x2", "chromagram_tri_20x16x3",
-         "chromagram_tri_20x20x2", "chromagram_tri_20x10x3", "chromagram_tri_r29x19", "chromagram_tri_r19x29x2",
-         "chromagram_tri_8x8x8", "chromagram_tri_16x16x4", "chromagram_tri_4x8x8", "chromagram_tri_4x4x8"}};
-    tl.name = names[mode][sh];
+    static const char *names[12] = {"tri_20x20x3", "tri_r21x21x5", "tri_21x21x2", "tri_20x16x3", "tri_20x20x2", "tri_20x10x3",
+                                    "tri_r29x19", "tri_r19x29x2", "tri_8x8x8", "tri_16x16x4", "tri_4x8x8", "tri_4x4x8"};
+    tl.name = names[sh];
     switch (sh) {
 #define PAA_TRI_FILL(ID, SH) case ID: tri_fill<SH>(fs, mode, mel, chroma, tl, blob); break;
         PAA_TRI_SHAPES(PAA_TRI_FILL)
@@ -1755,59 +1748,6 @@ inline int tri_select(int window, int mode, double fs, const MelTable *mel, cons
     if (tl.lds > 160 * 1024) return 0;
     return 1;
 }
-
-#if !defined(PAA_NO_HOST_LAUNCHERS) || defined(PAA_LAUNCH_TRI)      // (kernels are instantiated only in family_tri*.hip)
-template <typename SH, typename T, int MODE, int DELTAS>
-static inline int tri_launch_one(const TriLaunch &tl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                          const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                          hipStream_t stream) {
-    static LdsAttrCache attr;
-    if (!attr.covers(tl.lds)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&st_tri_kernel<SH, T, MODE, DELTAS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl.lds) != hipSuccess) return -1;
-        attr.set(tl.lds);
-    }
-    const int nwm = tl.waves;           // (<= the shape's maximum, which is what __launch_bounds__ promises)
-    const unsigned grid = (unsigned)((n_tiles + nwm - 1) / nwm);
-    hipLaunchKernelGGL((st_tri_kernel<SH, T, MODE, DELTAS>), dim3(grid), dim3(64 * nwm), tl.lds, stream, P, tl.layout, blob,
-                       (const T *)d_packed, clips, norms, tiles, (int)n_tiles, d_out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-template <typename SH, typename T>
-static inline int tri_launch_mode(const TriLaunch &tl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                           const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                           hipStream_t stream) {
-    if (P.mode == 1) return tri_launch_one<SH, T, 1, 0>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (P.mode == 2) return tri_launch_one<SH, T, 2, 0>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (P.deltas) return tri_launch_one<SH, T, 0, 1>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    return tri_launch_one<SH, T, 0, 0>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-}
-// (internal linkage: the two units that instantiate these launchers name different shapes in PAA_TRI_SHAPES_HERE)
-template <typename T>
-static inline int tri_launch_shape(const TriLaunch &tl, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                            const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                            hipStream_t stream) {
-    // (the shapes are spread over two translation units: PAA_TRI_SHAPES_HERE names the ones this unit instantiates)
-#ifndef PAA_TRI_SHAPES_HERE
-#define PAA_TRI_SHAPES_HERE(X) PAA_TRI_SHAPES(X)
-#endif
-    switch (tl.shape) {
-#define PAA_TRI_GO(ID, SH) case ID: return tri_launch_mode<SH, T>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-        PAA_TRI_SHAPES_HERE(PAA_TRI_GO)
-#undef PAA_TRI_GO
-        default: return -1;
-    }
-}
-// sample_kind 0: int16, 1: float64, 2: interleaved stereo int16 (summed in the loads)
-static inline int tri_launch(const TriLaunch &tl, int sample_kind, const PlanDev &P, const unsigned char *blob, const void *d_packed,
-                      const ClipDev *clips, const ClipNorm *norms, const Tile *tiles, long long n_tiles, double *d_out,
-                      hipStream_t stream) {
-    if (sample_kind == 0) return tri_launch_shape<int16_t>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    if (sample_kind == 2) return tri_launch_shape<stereo16>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-    return tri_launch_shape<double>(tl, P, blob, d_packed, clips, norms, tiles, n_tiles, d_out, stream);
-}
-
-#endif  // PAA_NO_HOST_LAUNCHERS
 
 }  // namespace tri
 }  // namespace paa

@@ -86,13 +86,14 @@ static int tile_work(FamilyCtx &c, std::vector<Tile> &tiles) {
     return PAA_OK;
 }
 // one launch of a one-wave family over a range of tiles
-typedef int (*TileLaunch)(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s);
+typedef int (*TileLaunch)(const paa_plan *p, const TileArgs &a);
 template <TileLaunch Launch>
 static int tile_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles) {
     if (n_tiles == 0) return PAA_OK;
     ProfScope prof_scope;
     { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-    if (Launch(p, d_packed, d_out, tiles, n_tiles, cs()))
+    const TileArgs a{p->P, p->fam.d_blob, d_packed, p->sample_kind, p->d_clips, p->d_norms, tiles, n_tiles, d_out, cs()};
+    if (Launch(p, a))
         return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
     return PAA_OK;
 }
@@ -117,14 +118,16 @@ static void fam_fast_rule(FamilyCtx &c, RunRule &r) {
     r.fill_wg_runs = fl.waves_per_cu;
     if (const char *rc_env = experiment_env("PAA_RUN_CAP")) r.run = std::max(16, atoi(rc_env) / 4 * 4);      // A/B experiments only
 }
-static int fam_fast_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::fast(p->fam.fl, p->P, p->tab->fast, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
+static int fam_fast_launch(const paa_plan *p, const TileArgs &a) {
+    TileArgs af = a;          // (its tables belong to the table set, not to the choice)
+    af.blob = reinterpret_cast<const unsigned char *>(p->tab->fast.d_blob);
+    return launch::fast(p->fam.fl, af);
 }
 
 // ---- kernels_ct.hpp: windows 2 RA RB (800, 640, 400, 320), any step / sample type / mode
 static int fam_ct_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
-    if (g_force_generic || !ct::ct_select(c.window, c.mode, c.fs, c.tab->fft, c.mel(), c.chroma(), f.cl, blob)) return 0;
-    f.lds = f.cl.lds; f.kernel_name = f.cl.name;
+    if (g_force_generic || !ct::ct_select(c.window, c.fs, c.tab->fft, c.mel(), c.chroma(), f.cl, blob)) return 0;
+    f.lds = f.cl.lds; f.kernel_name = mode_kernel_name(c.mode, f.cl.name);
     return 1;
 }
 static void fam_ct_rule(FamilyCtx &c, RunRule &r) {
@@ -135,15 +138,13 @@ static void fam_ct_rule(FamilyCtx &c, RunRule &r) {
     r.run = choose_run_cap(c.p->clips, 4, 16, 256, 0, c.p->fam.cl.waves, c.num_cu(), r.halo_inside);
     r.fill_wg_runs = c.p->fam.cl.waves;          // (one workgroup per CU; A/B scripts/rounds/r05/gpu_r05aj.sh: -0.4 ... -2.0 % on the feature shapes)
 }
-static int fam_ct_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::ct(p->fam.cl, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
-}
+static int fam_ct_launch(const paa_plan *p, const TileArgs &a) { return launch::ct(p->fam.cl, a); }
 
 // ---- kernels_tri.hpp: three-pass register FFT -- the reference's default 50 ms windows at 48 / 44.1 kHz (2400, 2205), the
 // 40 ms ones (1920, 1764), 1600, 1200, config 5's feature matrix (1102) and the odd 551 (50 ms at 11.025 kHz)
 static int fam_tri_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
     if (g_force_generic || !tri::tri_select(c.window, c.mode, c.fs, c.mel(), c.chroma(), f.trl, blob)) return 0;
-    f.lds = f.trl.lds; f.kernel_name = f.trl.name;
+    f.lds = f.trl.lds; f.kernel_name = mode_kernel_name(c.mode, f.trl.name);
     return 1;
 }
 static void fam_tri_rule(FamilyCtx &c, RunRule &r) {
@@ -153,9 +154,7 @@ static void fam_tri_rule(FamilyCtx &c, RunRule &r) {
     // (balanced runs -- RunRule::fill_wg_runs = trl.waves -- were A/B-ed here too, scripts/rounds/r05/gpu_r05ad.sh: 3072 runs of 19 / 20
     // frames instead of 3000 of 20 for config 5 changed nothing beyond the noise, 0.3202 / 0.3184 ms: the equal runs stay)
 }
-static int fam_tri_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::tri(p->fam.trl, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
-}
+static int fam_tri_launch(const paa_plan *p, const TileArgs &a) { return launch::tri(p->fam.trl, a); }
 
 // ---- kernels_mix.hpp: in-place mixed-radix transform for every other length made of 2, 3, 5, 7, 11, 13
 static int fam_mix_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
@@ -170,9 +169,7 @@ static void fam_mix_rule(FamilyCtx &c, RunRule &r) {
     r.quantum = 4;
     r.run = two_round_run(c.total_frames, c.p->fam.ml.waves, c.num_cu());
 }
-static int fam_mix_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::mix(p->fam.ml, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
-}
+static int fam_mix_launch(const paa_plan *p, const TileArgs &a) { return launch::mix(p->fam.ml, a); }
 
 // ---- kernels_blu.hpp: lengths with a prime factor above 13 (661, 1103, 736 ...): Bluestein's convolution on power-of-two transforms
 static int fam_blu_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsigned char> &blob) {
@@ -187,9 +184,7 @@ static void fam_blu_rule(FamilyCtx &c, RunRule &r) {
     r.quantum = 4;
     r.run = two_round_run(c.total_frames, c.p->fam.bl.waves, c.num_cu());
 }
-static int fam_blu_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::blu(p->fam.bl, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
-}
+static int fam_blu_launch(const paa_plan *p, const TileArgs &a) { return launch::blu(p->fam.bl, a); }
 
 // ---- kernels_generic.hpp: Stockham passes in LDS (what no other one-wave family takes: tiny windows, prime factors above 13
 // beyond 2730 samples), as long as the layout fits 160 KB of LDS
@@ -204,9 +199,7 @@ static void fam_generic_rule(FamilyCtx &c, RunRule &r) {
     r.quantum = 4;
     r.run = two_round_run(c.total_frames, c.p->fam.gl.waves, c.num_cu());
 }
-static int fam_generic_launch(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n, hipStream_t s) {
-    return launch::generic(p->fam.gl, p->fam.lds, p->sample_kind, p->P, p->fam.d_blob, d_packed, p->d_clips, p->d_norms, tiles, n, d_out, s);
-}
+static int fam_generic_launch(const paa_plan *p, const TileArgs &a) { return launch::generic(p->fam.gl, a); }
 
 // ---- windows beyond the LDS envelope of the one-wave kernels --------------------------------------------------------------------
 // kernels_wgr.hpp: the 1 s windows of music_thumbnailing at 16 / 8 kHz -- one fused launch, the transform in registers; its table
@@ -323,8 +316,7 @@ static int wg_build_work(paa_plan *p, int wgs_r0) {
 static int fam_wgs_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, wgs::wgs_select(c.window).r0); }
 static int fam_wg_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, 0); }
 static int run_wg_any(paa_plan *p, const void *d_packed, double *d_out, const wgs::Sel &sel) {
-    return p->sample_kind == 0 ? run_wg<int16_t>(p, d_packed, d_out, sel)
-         : p->sample_kind == 2 ? run_wg<stereo16>(p, d_packed, d_out, sel) : run_wg<double>(p, d_packed, d_out, sel);
+    return with_sample_type(p->sample_kind, [&](auto tag) { return run_wg<PAA_SAMPLE_T(tag)>(p, d_packed, d_out, sel); });
 }
 static int fam_wgs_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
     return run_wg_any(p, d_packed, d_out, wgs::wgs_select(p->P.W));
@@ -340,8 +332,7 @@ static int fam_hbm_select(const FamilyCtx &, FamilyChoice &f, std::vector<unsign
 }
 static int no_work(FamilyCtx &, std::vector<Tile> &) { return PAA_OK; }
 static int fam_hbm_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
-    return p->sample_kind == 0 ? run_big<int16_t>(p, d_packed, d_out)
-         : p->sample_kind == 2 ? run_big<stereo16>(p, d_packed, d_out) : run_big<double>(p, d_packed, d_out);
+    return with_sample_type(p->sample_kind, [&](auto tag) { return run_big<PAA_SAMPLE_T(tag)>(p, d_packed, d_out); });
 }
 
 // in choice order; ranged / norms_inline: the one-wave families only

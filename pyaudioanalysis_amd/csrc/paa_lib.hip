@@ -23,7 +23,6 @@
 #include "../../include/paa_hip.h"
 // the kernels of the feature families are instantiated in their own translation units (family_*.hip); this unit sees their
 // host-side layout / selection code and the launch entry points of family_launch.hpp
-#define PAA_NO_HOST_LAUNCHERS
 #include "family_launch.hpp"
 #include "kernels_aux.hpp"
 #include "kernels_big.hpp"
