@@ -386,6 +386,25 @@ int paa_diar_dev_kmeans_f64(const double *d_z, int n_dims, int64_t ld, int64_t n
 int paa_diar_dev_pair_sums_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *d_labels,
                                const int32_t *ks, int nk, double *sums);
 
+/* ---- the LDA step of speaker diarization (audioSegmentation.py:880-934, lda_dim > 0) ------------------------------------------
+ * The O(n) parts of scikit-learn's LinearDiscriminantAnalysis (svd solver) on a device matrix, feature-major [n_dims][ld]
+ * (n_dims 1..256), window t in column t.  Classes are CONTIGUOUS runs of windows: class c = windows run_offsets[c] ..
+ * run_offsets[c + 1] - 1 (host array of n_classes + 1 entries, 0 = first < ... < last = n_vec).  The small results are host
+ * arrays and every call is synchronous; the two symmetric eigenproblems between the calls (at most 256 x 256) are the caller's.
+ * class_stats: means [n_classes][n_dims] and within_std [n_dims], the population deviation of the windows about their class
+ * means over all windows (two passes: means, then deviations), zero replaced by 1 (a NaN stays a NaN).
+ * within_gram: gram [n_dims][n_dims] = Xs^T Xs of Xs = sqrt(fac) (x - mean of its class) / within_std, centred and scaled while
+ * it is loaded; the upper triangle is computed (FP64 matrix cores) in partials of 1024 windows that are added in window order,
+ * the lower triangle is its mirror image.  No floating-point atomics: two runs give identical bits.
+ * project: d_y [n_out][ld_y], y[j][t] = sum_d (x[d][t] - xbar[d]) scalings[d][j] (scalings [n_dims][n_out], 1 <= n_out <=
+ * n_dims), d ascending.                                                                                                   */
+int paa_lda_dev_class_stats_f64(const double *d_x, int n_dims, int64_t ld, int64_t n_vec, const int64_t *run_offsets,
+                                int64_t n_classes, double *means, double *within_std);
+int paa_lda_dev_within_gram_f64(const double *d_x, int n_dims, int64_t ld, int64_t n_vec, const int64_t *run_offsets,
+                                int64_t n_classes, const double *means, const double *within_std, double fac, double *gram);
+int paa_lda_dev_project_f64(const double *d_x, int n_dims, int64_t ld, int64_t n_vec, const double *xbar, const double *scalings,
+                            int n_out, double *d_y, int64_t ld_y);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------------- */
 #define PAA_COMM_ID_BYTES 128
 int paa_comm_unique_id(void *id_out /* PAA_COMM_ID_BYTES, rank 0 only */);

@@ -16,7 +16,10 @@ audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744
 hmm_segmentation, :287-492) runs on the GPU as well: class GaussianHmm stands in for hmmlearn's GaussianHMM (hmmlearn is not
 needed, also not to read a model file the reference wrote).  Speaker diarization (speaker_diarization, diarize_features,
 evaluate_speaker_diarization, speaker_diarization_evaluation, :251-284, :815-1090) runs its standardisation, k-means sweep and
-silhouettes on the GPU as well; its LDA branch (lda_dim > 0) is not ported.
+silhouettes on the GPU as well.  Its LDA branch (lda_dim > 0, :880-934) has entry points of its own -- speaker_diarization_lda,
+speaker_diarization_lda_signal, lda_fit_device / lda_transform_device / lda_fit_transform: class statistics, within-class
+Gram matrix and projection on the GPU, two eigenproblems of at most 256 x 256 with numpy.linalg.eigh on the host;
+speaker_diarization(lda_dim > 0) itself refuses and names them.
 """
 import contextlib
 import ctypes as C
@@ -788,12 +791,13 @@ def hmm_segmentation(audio_file, hmm_model_name, plot_results=False, gt_file="")
 
 
 # ---------------------------------------------------------------------------------------------------------
-# speaker diarization (reference :251-284, :815-1090; the LDA branch is not ported)
+# speaker diarization (reference :251-284, :815-1090; the LDA branch follows in a section of its own)
 # ---------------------------------------------------------------------------------------------------------
 DIAR_MODELS_ENV = "PAA_DIAR_MODELS"                  # directory that holds the two speaker SVM files
 DIAR_MODEL_FILES = ("svm_rbf_speaker_10", "svm_rbf_speaker_male_female")
 _DIAR_MAX_K = 32
 _DIAR_MAX_DIMS = 256
+_LDA_ELSEWHERE = "the LDA branch (lda_dim > 0) lives in speaker_diarization_lda / speaker_diarization_lda_signal"
 
 
 def evaluate_speaker_diarization(labels, labels_gt):
@@ -853,11 +857,7 @@ def _diar_silhouette(n, k, labels, a_mean, pair_sum):
     return a, b, sil
 
 
-def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, init_centers=None, max_iter=300, tol=1e-4):
-    """Steps 3-6 of diarize_features on a device-resident matrix (DeviceBuffer of [n_dims][n] doubles).  Returns (details, d_z):
-    the details dict of diarize_features without the HMM entries, and the DeviceBuffer of the standardised, UNFILTERED
-    matrix [n_dims][n] (the caller frees it)."""
-    lib = _ffi.lib()
+def _diar_check_sweep(n_dims, n, n_speakers):
     ks = list(range(2, 10)) if n_speakers <= 0 else [int(n_speakers)]
     if n < 1 or n_dims < 1 or n_dims > _DIAR_MAX_DIMS:
         raise ValueError("feature matrix of %d dims x %d windows: 1..%d dims and at least one window" % (n_dims, n, _DIAR_MAX_DIMS))
@@ -865,23 +865,15 @@ def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, in
         raise ValueError("%d speakers: 1..%d clusters are supported" % (ks[0], _DIAR_MAX_K))
     if n < max(ks):
         raise ValueError("%d windows are fewer than %d clusters" % (n, max(ks)))
+    return ks
+
+
+def _diar_sweep_device(d_zk, dims, n, ks, tol_abs, random_state, init_centers, max_iter):
+    """k-means for every k of `ks` and the silhouettes (steps 5-6) on the device matrix d_zk [dims][n], as it stands: the
+    per-k entries, scores and imax of the details dict."""
+    lib = _ffi.lib()
     bufs = []
-    d_z = _ffi.DeviceBuffer(n_dims * n * 8)
     try:
-        stats = np.empty((3, n_dims))
-        _ffi.check(lib.paa_diar_dev_standardize_f64(d_m.ptr, n_dims, n, n, d_z.ptr, _ffi.as_f64p(stats)))
-        colsum, pmean = np.empty(n_dims), np.empty(1)
-        _ffi.check(lib.paa_diar_dev_dim_distances_f64(d_z.ptr, n_dims, n, n, None, None, 0, _ffi.as_f64p(colsum), _ffi.as_f64p(pmean)))
-        kept = np.nonzero(colsum < 1.1 * np.mean(colsum))[0]
-        if kept.shape[0] < 1:
-            raise ValueError("no feature dimension passes the reference's distance filter (a single dimension never does)")
-        dims = int(kept.shape[0])
-        rows = np.ascontiguousarray(kept, dtype=np.int32)
-        d_zk = _ffi.DeviceBuffer(dims * n * 8)
-        bufs.append(d_zk)
-        _ffi.check(lib.paa_diar_dev_select_rows_f64(d_z.ptr, n_dims, n, n, rows.ctypes.data_as(_ffi.c_i32p), dims, d_zk.ptr))
-        # tol of scikit-learn: 1e-4 * mean(var(Zk, axis=0)); a standardised row has variance var / scale^2
-        tol_abs = tol * float(np.mean(stats[1, kept] / stats[2, kept] ** 2))
         rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
         nk = len(ks)
         centers = np.zeros((nk, _DIAR_MAX_K, dims))
@@ -908,8 +900,8 @@ def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, in
                                                       _ffi.as_f64p(a_mean)))
         pair = np.empty((nk, _DIAR_MAX_K, _DIAR_MAX_K))
         _ffi.check(lib.paa_diar_dev_pair_sums_f64(d_zk.ptr, dims, n, n, d_labels.ptr, ks_p, nk, _ffi.as_f64p(pair)))
-        details = {"kept_dims": kept, "dim_colsum": colsum, "mean": stats[0], "var": stats[1], "scale": stats[2], "ks": ks,
-                   "labels": {}, "centers": {}, "n_iter": {}, "inertia": {}, "sil_a": {}, "sil_b": {}, "sil": {}, "pair_sums": {}}
+        details = {"ks": ks, "labels": {}, "centers": {}, "n_iter": {}, "inertia": {}, "sil_a": {}, "sil_b": {}, "sil": {},
+                   "pair_sums": {}}
         scores = []
         for i, k in enumerate(ks):
             a, b, sil = _diar_silhouette(n, k, labels[i], a_mean[i], pair[i])
@@ -922,6 +914,37 @@ def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, in
             scores.append(np.mean(sil))
         details["scores"] = np.array(scores)
         details["imax"] = int(np.argmax(scores))
+        return details
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, init_centers=None, max_iter=300, tol=1e-4):
+    """Steps 3-6 of diarize_features on a device-resident matrix (DeviceBuffer of [n_dims][n] doubles).  Returns (details, d_z):
+    the details dict of diarize_features without the HMM entries, and the DeviceBuffer of the standardised, UNFILTERED
+    matrix [n_dims][n] (the caller frees it)."""
+    lib = _ffi.lib()
+    ks = _diar_check_sweep(n_dims, n, n_speakers)
+    bufs = []
+    d_z = _ffi.DeviceBuffer(n_dims * n * 8)
+    try:
+        stats = np.empty((3, n_dims))
+        _ffi.check(lib.paa_diar_dev_standardize_f64(d_m.ptr, n_dims, n, n, d_z.ptr, _ffi.as_f64p(stats)))
+        colsum, pmean = np.empty(n_dims), np.empty(1)
+        _ffi.check(lib.paa_diar_dev_dim_distances_f64(d_z.ptr, n_dims, n, n, None, None, 0, _ffi.as_f64p(colsum), _ffi.as_f64p(pmean)))
+        kept = np.nonzero(colsum < 1.1 * np.mean(colsum))[0]
+        if kept.shape[0] < 1:
+            raise ValueError("no feature dimension passes the reference's distance filter (a single dimension never does)")
+        dims = int(kept.shape[0])
+        rows = np.ascontiguousarray(kept, dtype=np.int32)
+        d_zk = _ffi.DeviceBuffer(dims * n * 8)
+        bufs.append(d_zk)
+        _ffi.check(lib.paa_diar_dev_select_rows_f64(d_z.ptr, n_dims, n, n, rows.ctypes.data_as(_ffi.c_i32p), dims, d_zk.ptr))
+        # tol of scikit-learn: 1e-4 * mean(var(Zk, axis=0)); a standardised row has variance var / scale^2
+        tol_abs = tol * float(np.mean(stats[1, kept] / stats[2, kept] ** 2))
+        details = {"kept_dims": kept, "dim_colsum": colsum, "mean": stats[0], "var": stats[1], "scale": stats[2]}
+        details.update(_diar_sweep_device(d_zk, dims, n, ks, tol_abs, random_state, init_centers, max_iter))
     except BaseException:
         d_z.free()
         raise
@@ -929,6 +952,30 @@ def diarize_clusters_device(d_m, n_dims, n, n_speakers, *, random_state=None, in
         for b in bufs:
             b.free()
     return details, d_z
+
+
+def cluster_prepared_device(d_y, n_dims, n, n_speakers, *, random_state=None, init_centers=None, max_iter=300, tol=1e-4):
+    """Steps 5-6 on an already prepared device matrix (DeviceBuffer of [n_dims][n] doubles, e.g. the LDA projection): the
+    k-means sweep and the silhouettes on the matrix as it stands -- no standardisation, no dimension filter.  The k-means
+    tolerance is scikit-learn's tol * mean(var(Y, axis = 0)).  Returns the per-k details of diarize_clusters_device (ks, labels,
+    centers, n_iter, inertia, sil_a, sil_b, sil, pair_sums, scores, imax) and "var"."""
+    ks = _diar_check_sweep(n_dims, n, n_speakers)
+    d_tmp = _ffi.DeviceBuffer(n_dims * n * 8)               # the standardised copy is not wanted, its statistics are
+    try:
+        stats = np.empty((3, n_dims))
+        _ffi.check(_ffi.lib().paa_diar_dev_standardize_f64(d_y.ptr, n_dims, n, n, d_tmp.ptr, _ffi.as_f64p(stats)))
+    finally:
+        d_tmp.free()
+    details = _diar_sweep_device(d_y, n_dims, n, ks, tol * float(np.mean(stats[1])), random_state, init_centers, max_iter)
+    details["var"] = stats[1]
+    return details
+
+
+def median_filter5(labels):
+    """scipy.signal.medfilt(labels, 5) as float64: the 5-tap median with zero-padded edges (reference :1012)."""
+    x = np.asarray(labels, dtype=np.float64)
+    padded = np.concatenate((np.zeros(2), x, np.zeros(2)))
+    return np.median(np.stack([padded[i:i + x.shape[0]] for i in range(5)]), axis=0)
 
 
 def _diarize_device(d_m, n_dims, n, n_speakers, random_state, init_centers, return_details):
@@ -940,8 +987,7 @@ def _diarize_device(d_m, n_dims, n, n_speakers, random_state, init_centers, retu
         _, states = GaussianHmm(priors, trans, means, cov).predict_device(d_z, n, n)
     finally:
         d_z.free()
-    padded = np.concatenate((np.zeros(2), states.astype(np.float64), np.zeros(2)))
-    cls = np.median(np.stack([padded[i:i + n] for i in range(5)]), axis=0)        # scipy.signal.medfilt(states, 5)
+    cls = median_filter5(states)
     if return_details:
         details["hmm_states"] = states
         return cls, details
@@ -1010,7 +1056,7 @@ def speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window=1.0
     matrix never leaves the device.  models: see speaker_diarization."""
     from . import audioTrainTest
     if lda_dim > 0:
-        raise NotImplementedError("the LDA branch of speaker_diarization (lda_dim > 0) is not ported")
+        raise NotImplementedError(_LDA_ELSEWHERE)
     loaded = _diar_models(models, models_dir)
     svcs = [(audioTrainTest.svc_model(m[0]), np.asarray(m[1], dtype=np.float64), np.asarray(m[2], dtype=np.float64)) for m in loaded]
     st = round(sampling_rate * 0.05)
@@ -1049,8 +1095,8 @@ def _plot_diarization(cls, n_classes, duration, mid_step, flags_gt, purities, n_
 
 def speaker_diarization(filename, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=0, plot_res=False, *,
                         models=None, models_dir=None, random_state=None, init_centers=None):
-    """Speaker diarization of a WAV file (reference :815-1056, lda_dim = 0 only): returns (cls, purity_cluster_m,
-    purity_speaker_m) -- the label of every mid-term window (float64) and, when <filename>.segments exists next to the file,
+    """Speaker diarization of a WAV file (reference :815-1056, lda_dim = 0; lda_dim > 0: speaker_diarization_lda): returns
+    (cls, purity_cluster_m, purity_speaker_m) -- the label of every mid-term window (float64) and, when <filename>.segments exists next to the file,
     the cluster and speaker purity against it (printed as the reference prints them), else -1, -1.
 
     n_speakers <= 0 sweeps k = 2..9.  As in the reference the returned labels come from the k-means of the LAST k tried,
@@ -1059,9 +1105,8 @@ def speaker_diarization(filename, n_speakers, mid_window=1.0, mid_step=0.1, shor
     reads svm_rbf_speaker_10 and svm_rbf_speaker_male_female (and their MEANS files) from models_dir or the directory
     named by the environment variable PAA_DIAR_MODELS -- FileNotFoundError says what is missing.  random_state seeds the
     k-means++ initialisation (the reference leaves it unseeded); init_centers {k: [k][kept dims]} replaces it."""
-    import os
     if lda_dim > 0:
-        raise NotImplementedError("the LDA branch of speaker_diarization (lda_dim > 0) is not ported")
+        raise NotImplementedError(_LDA_ELSEWHERE)
     loaded = _diar_models(models, models_dir)
     sampling_rate, signal = audioBasicIO.read_audio_file(filename)
     signal = audioBasicIO.stereo_to_mono(signal)
@@ -1069,6 +1114,13 @@ def speaker_diarization(filename, n_speakers, mid_window=1.0, mid_step=0.1, shor
     cls, details = speaker_diarization_signal(signal, sampling_rate, n_speakers, mid_window, mid_step, short_window, lda_dim,
                                               models=loaded, random_state=random_state, init_centers=init_centers,
                                               return_details=True)
+    return _score_diarization(filename, cls, details, mid_step, duration, n_speakers, plot_res)
+
+
+def _score_diarization(filename, cls, details, mid_step, duration, n_speakers, plot_res):
+    """(cls, cluster purity, speaker purity) against <filename>.segments when it exists (printed as the reference prints
+    them), else -1, -1; the plot on request (reference :1014-1056)."""
+    import os
     purities = (-1, -1)
     flags_gt = None
     gt_file = filename.replace('.wav', '.segments')
@@ -1084,8 +1136,9 @@ def speaker_diarization(filename, n_speakers, mid_window=1.0, mid_step=0.1, shor
 
 
 def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, models_dir=None, random_state=None):
-    """Prints the purities of every WAV file of a folder for every LDA dimension of the list (reference :1059-1090; only 0 is
-    supported): the number of speakers comes from the file's .segments ground truth (-1: unknown)."""
+    """Prints the purities of every WAV file of a folder for every LDA dimension of the list (reference :1059-1090): the
+    number of speakers comes from the file's .segments ground truth (-1: unknown).  Dimension 0 runs speaker_diarization,
+    a dimension above 0 speaker_diarization_lda, both with the reference's settings (2.0 / 0.2 / 0.05 s)."""
     import glob
     import os
     wav_files = sorted(glob.glob(os.path.join(folder_name, '*.wav')))
@@ -1101,5 +1154,226 @@ def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, 
     for dim in lda_dimensions:
         print("LDA = {0:d}".format(dim))
         for i, wav_file in enumerate(wav_files):
-            speaker_diarization(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
-                                random_state=random_state)
+            if dim > 0:
+                speaker_diarization_lda(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
+                                        random_state=random_state)
+            else:
+                speaker_diarization(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
+                                    random_state=random_state)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the LDA branch of speaker diarization (reference :880-934, :1001, :1012)
+# ---------------------------------------------------------------------------------------------------------
+LDA_TOL = 1e-4                                       # scikit-learn's LinearDiscriminantAnalysis(tol=1e-4)
+
+
+def lda_window_labels(n_windows, short_window):
+    """The class of every step-1 window as the reference computes it (:925-929): int(i * short_window / (1.0 / short_window)),
+    in that floating-point form.  Labels never decrease."""
+    lda_step_ratio = 1.0 / short_window
+    return (np.arange(int(n_windows)) * short_window / lda_step_ratio).astype(np.int64)
+
+
+def _lda_runs(labels, n):
+    """Run boundaries [C + 1] of non-decreasing labels [n]."""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.shape[0] != n:
+        raise ValueError("labels must hold one entry per window (%d)" % n)
+    if n > 1 and np.any(labels[1:] < labels[:-1]):
+        raise ValueError("labels decrease: only contiguous classes (non-decreasing labels, one run of windows per class) are "
+                         "supported")
+    starts = np.flatnonzero(np.concatenate(([True], labels[1:] != labels[:-1]))) if n else np.zeros(0, dtype=np.int64)
+    return np.ascontiguousarray(np.concatenate((starts, [n])), dtype=np.int64)
+
+
+def _lda_check(n_dims, n, offsets, n_components):
+    n_classes = offsets.shape[0] - 1
+    if n_dims < 1 or n_dims > _DIAR_MAX_DIMS or n < 1:
+        raise ValueError("feature matrix of %d dims x %d windows: 1..%d dims and at least one window" % (n_dims, n, _DIAR_MAX_DIMS))
+    if n_components < 1:
+        raise ValueError("n_components must be at least 1")
+    if n_components > min(n_dims, n_classes - 1):
+        raise ValueError("n_components cannot be larger than min(n_features, n_classes - 1).")     # scikit-learn's message
+    if n <= n_classes:
+        raise ValueError("The number of samples must be more than the number of classes.")
+
+
+def _eigh_desc(A):
+    """Singular values and right singular vectors of a matrix from its Gram matrix A: sqrt of the eigenvalues (negative ones
+    clamped to 0) in descending order, eigenvectors in the columns."""
+    lam, V = np.linalg.eigh(A)
+    order = np.argsort(lam)[::-1]
+    return np.sqrt(np.maximum(lam[order], 0.0)), V[:, order]
+
+
+def _margins(S, rank, threshold):
+    kept = float(S[rank - 1] / threshold) if rank > 0 else 0.0
+    dropped = float(threshold / S[rank]) if rank < S.shape[0] and S[rank] > 0 else np.inf
+    return kept, dropped
+
+
+def lda_fit_device(d_x, n_dims, ld, n, labels, n_components, tol=LDA_TOL):
+    """LinearDiscriminantAnalysis(n_components, solver="svd", tol).fit of scikit-learn on a device matrix (DeviceBuffer of
+    [n_dims][ld] doubles, window t in column t) with non-decreasing labels [n].  Class means, pooled within-class deviation
+    and the Gram matrix G = Xs^T Xs of the centred, scaled windows come from the device (paa_lda_dev_*); the singular values
+    and right singular vectors of Xs are those of G's eigen-decomposition (numpy.linalg.eigh, at most 256 x 256), and the
+    same again for the Gram matrix of the weighted class means in the whitened space -- host work that does not grow with
+    the number of windows.  Every column of scalings gets its largest-magnitude entry positive (an SVD leaves the sign
+    open).  Returns a dict: xbar, means, priors, std, scalings [n_dims][min(n_components, rank2)], scalings_all, S, rank,
+    S2, rank2, rank_margin / rank2_margin (kept / threshold, threshold / dropped), gram, offsets."""
+    lib = _ffi.lib()
+    offsets = _lda_runs(labels, n)
+    _lda_check(n_dims, n, offsets, n_components)
+    if ld < n:
+        raise ValueError("bad feature matrix: %d vectors, ld %d" % (n, ld))
+    n_classes = offsets.shape[0] - 1
+    means, std = np.empty((n_classes, n_dims)), np.empty(n_dims)
+    _ffi.check(lib.paa_lda_dev_class_stats_f64(d_x.ptr, n_dims, ld, n, _ffi.as_i64p(offsets), n_classes, _ffi.as_f64p(means),
+                                               _ffi.as_f64p(std)))
+    priors = np.diff(offsets) / float(n)
+    xbar = priors @ means
+    fac = 1.0 / (n - n_classes)
+    G = np.empty((n_dims, n_dims))
+    _ffi.check(lib.paa_lda_dev_within_gram_f64(d_x.ptr, n_dims, ld, n, _ffi.as_i64p(offsets), n_classes, _ffi.as_f64p(means),
+                                               _ffi.as_f64p(std), fac, _ffi.as_f64p(G)))
+    S, V = _eigh_desc(G)
+    rank = int(np.sum(S > tol))
+    if rank < 1:
+        raise ValueError("the within-class scatter has no singular value above tol = %g" % tol)
+    scalings = (V[:, :rank] / std[:, None]) / S[:rank]
+    fac2 = 1.0 / (n_classes - 1)                                                  # _lda_check: at least two classes
+    W = ((np.sqrt((n * priors) * fac2)) * (means - xbar).T).T @ scalings          # [C][rank]: the weighted class means
+    S2, V2 = _eigh_desc(W.T @ W)
+    rank2 = int(np.sum(S2 > tol * S2[0]))
+    full = scalings @ V2[:, :rank2]
+    top = np.argmax(np.abs(full), axis=0)
+    full = full * np.where(full[top, np.arange(full.shape[1])] < 0, -1.0, 1.0)
+    return {"xbar": xbar, "means": means, "priors": priors, "std": std, "gram": G, "offsets": offsets,
+            "scalings": np.ascontiguousarray(full[:, :n_components]), "scalings_all": full, "S": S, "rank": rank, "S2": S2,
+            "rank2": rank2, "rank_margin": _margins(S, rank, tol), "rank2_margin": _margins(S2, rank2, tol * S2[0]),
+            "n_dims": n_dims, "tol": tol}
+
+
+def lda_transform_device(model, d_x, n_dims, ld, n, d_y=None, ld_y=None):
+    """(x - xbar) @ scalings of a fitted model for every window of a device matrix [n_dims][ld]: returns (d_y, n_out), the
+    DeviceBuffer [n_out][ld_y] (made here when d_y is None, with ld_y = n; the caller frees it) -- the layout the
+    clustering kernels read."""
+    if n_dims != model["n_dims"]:
+        raise ValueError("feature vectors have %d dims, the model %d" % (n_dims, model["n_dims"]))
+    S = np.ascontiguousarray(model["scalings"], dtype=np.float64)
+    n_out = S.shape[1]
+    ld_y = n if ld_y is None else int(ld_y)
+    if n < 1 or ld < n or ld_y < n:
+        raise ValueError("bad feature matrix: %d vectors, ld %d, output ld %d" % (n, ld, ld_y))
+    own = d_y is None
+    if own:
+        d_y = _ffi.DeviceBuffer(n_out * ld_y * 8)
+    try:
+        xbar = np.ascontiguousarray(model["xbar"], dtype=np.float64)
+        _ffi.check(_ffi.lib().paa_lda_dev_project_f64(d_x.ptr, n_dims, ld, n, _ffi.as_f64p(xbar), _ffi.as_f64p(S), n_out, d_y.ptr,
+                                                      ld_y))
+    except BaseException:
+        if own:
+            d_y.free()
+        raise
+    return d_y, n_out
+
+
+def lda_fit_transform(X, labels, n_components, *, tol=LDA_TOL, return_model=False):
+    """LinearDiscriminantAnalysis(n_components).fit_transform(X, labels) for X (n_windows x n_dims) on the host, as
+    scikit-learn takes it; the result is (n_windows x n_components), columns signed as lda_fit_device says.  ValueError --
+    before any device work -- when n_components > min(n_dims, n_classes - 1) (scikit-learn's message), when there are not
+    more windows than classes (scikit-learn divides by zero there), and when labels decrease: only contiguous classes are
+    supported, which is what the reference's label formula produces."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError("X must be a (n_windows x n_dims) matrix")
+    n, n_dims = X.shape
+    _lda_check(n_dims, n, _lda_runs(labels, n), n_components)
+    d_x = _ffi.DeviceBuffer.from_host(np.ascontiguousarray(X.T))
+    try:
+        model = lda_fit_device(d_x, n_dims, n, n, labels, n_components, tol)
+        d_y, n_out = lda_transform_device(model, d_x, n_dims, n, n)
+        try:
+            Y = d_y.to_host(np.float64, n_out * n).reshape(n_out, n).T.copy()
+        finally:
+            d_y.free()
+    finally:
+        d_x.free()
+    return (Y, model) if return_model else Y
+
+
+def speaker_diarization_lda_signal(signal, sampling_rate, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=35,
+                                   *, models=None, models_dir=None, random_state=None, init_centers=None, return_details=False):
+    """The LDA branch of speaker_diarization (reference :880-934, lda_dim > 0) on an array, resident on the device:
+
+      mid-term statistics of the 68 short-term rows over int(round(mid_window / short_window)) frames at a step of ONE
+      frame (one window per short-term frame, the last ones shorter); the probabilities of the two speaker SVMs + 1e-4
+      below them; StandardScaler over the windows; labels int(i * short_window / (1.0 / short_window)); scikit-learn's
+      LinearDiscriminantAnalysis(n_components=lda_dim).fit_transform (lda_fit_device); k-means for k = 2..9 (or
+      n_speakers) and the silhouettes on the projection as it stands (cluster_prepared_device: no second
+      standardisation, no dimension filter); a 5-tap median filter (zero-padded) over the labels of the LAST k tried.
+
+    As in the reference the short-term window and step are round(fs * 0.05) whatever short_window says: short_window only
+    enters the window ratio and the labels.  There is no HMM smoothing in this branch, mid_step is not used, and the result
+    has one label per SHORT-TERM FRAME.  lda_dim > min(148, classes - 1) raises ValueError as scikit-learn does
+    (lda_dim = 35 needs 36 classes).  init_centers: {k: [k][lda_dim]}.  With return_details: the dict of
+    cluster_prepared_device plus "lda" (the model of lda_fit_device) and "lda_labels"."""
+    from . import audioTrainTest
+    if lda_dim <= 0:
+        raise ValueError("lda_dim must be positive here: speaker_diarization_signal is the lda_dim = 0 form")
+    loaded = _diar_models(models, models_dir)
+    svcs = [(audioTrainTest.svc_model(m[0]), np.asarray(m[1], dtype=np.float64), np.asarray(m[2], dtype=np.float64)) for m in loaded]
+    st = round(sampling_rate * 0.05)
+    window_ratio = int(round(mid_window / short_window))
+    if window_ratio < 1:
+        raise ValueError("mid_window / short_window rounds to 0")
+    rows, extra = 2 * 68, sum(len(s[0].classes) for s in svcs)
+    n_dims = rows + extra
+    lib = _ffi.lib()
+    with _mid_term_on_device(audioBasicIO.stereo_to_mono(signal), sampling_rate, window_ratio * st / float(sampling_rate),
+                             st / float(sampling_rate), st, st, extra) as (d_all, T):
+        labels = lda_window_labels(T, short_window)
+        _lda_check(n_dims, T, _lda_runs(labels, T), lda_dim)
+        at = rows                                   # the probability rows go below the statistics
+        for model, mean, std in svcs:
+            _, proba = model.predict_device(d_all, T, T, mean, std)
+            block = np.ascontiguousarray(proba.T + 1e-4)
+            _ffi.check(lib.paa_memcpy_h2d(C.c_void_p(d_all.ptr.value + at * T * 8), block.ctypes.data_as(C.c_void_p), block.nbytes))
+            at += block.shape[0]
+        d_z = _ffi.DeviceBuffer(n_dims * T * 8)
+        d_y = None
+        try:
+            stats = np.empty((3, n_dims))
+            _ffi.check(lib.paa_diar_dev_standardize_f64(d_all.ptr, n_dims, T, T, d_z.ptr, _ffi.as_f64p(stats)))
+            lda = lda_fit_device(d_z, n_dims, T, T, labels, lda_dim)
+            d_y, n_out = lda_transform_device(lda, d_z, n_dims, T, T)
+            details = cluster_prepared_device(d_y, n_out, T, n_speakers, random_state=random_state, init_centers=init_centers)
+        finally:
+            d_z.free()
+            if d_y is not None:
+                d_y.free()
+    cls = median_filter5(details["labels"][details["ks"][-1]])              # the reference filters the LAST k's labels
+    if return_details:
+        details["lda"] = lda
+        details["lda_labels"] = labels
+        return cls, details
+    return cls
+
+
+def speaker_diarization_lda(filename, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=35, plot_res=False, *,
+                            models=None, models_dir=None, random_state=None, init_centers=None):
+    """speaker_diarization(filename, ..., lda_dim > 0) of the reference: returns (cls, purity_cluster_m, purity_speaker_m) --
+    one label per short-term frame (float64, see speaker_diarization_lda_signal) and the purities against
+    <filename>.segments when it exists, else -1, -1.  As in the reference the ground truth is sampled -- and the plot's time
+    axis drawn -- at mid_step although the labels step by 0.05 s.  models, random_state, init_centers: see
+    speaker_diarization."""
+    loaded = _diar_models(models, models_dir)
+    sampling_rate, signal = audioBasicIO.read_audio_file(filename)
+    signal = audioBasicIO.stereo_to_mono(signal)
+    duration = len(signal) / sampling_rate
+    cls, details = speaker_diarization_lda_signal(signal, sampling_rate, n_speakers, mid_window, mid_step, short_window, lda_dim,
+                                                  models=loaded, random_state=random_state, init_centers=init_centers,
+                                                  return_details=True)
+    return _score_diarization(filename, cls, details, mid_step, duration, n_speakers, plot_res)

@@ -204,6 +204,18 @@ long long diar_pair_tiles(long long n);
 long long diar_pair_chunks(long long n);
 int diar_pair_sums(const double *d_Zk, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk,
                    const int *d_binoff, int nbins, double *d_partial, double *d_stage, double *d_S, hipStream_t stream);
+// kernels_lda.hpp (the LDA step of speaker diarization); classes are the runs off[c] .. off[c + 1] - 1 of windows (off [C + 1] on
+// the device).  means [C][D] and std [D] (pooled within-class deviation, zeros replaced by 1); dev and sq [C][D] are scratch
+int lda_class_stats(const double *d_X, long long ld, long long n, int D, const long long *d_off, long long C, double *d_means,
+                    double *d_dev, double *d_sq, double *d_std, hipStream_t stream);
+// G [D][D] = Xs^T Xs of Xs = (X - class mean) * rscale, in lda_gram_chunks(n) partials [D][D] each (scratch) added in chunk
+// order; cls [n] is scratch
+long long lda_gram_chunks(long long n);
+int lda_within_gram(const double *d_X, long long ld, long long n, int D, const long long *d_off, long long C, const double *d_means,
+                    const double *d_rscale, int *d_cls, double *d_partial, double *d_G, hipStream_t stream);
+// Y [n_out][ldy] = ((X - xbar)^T S)^T, S [D][n_out]
+int lda_project(const double *d_X, long long ld, long long n, int D, const double *d_xbar, const double *d_S, int n_out, double *d_Y,
+                long long ldy, hipStream_t stream);
 
 // timing builds (-DPAA_F800_TIMING / _TRACE): per-unit readers of the kernels' phase-cycle counters (kernels_fast.hpp:
 // PAA_PHASE_READER); no-ops otherwise

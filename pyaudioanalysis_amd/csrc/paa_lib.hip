@@ -547,6 +547,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_forest.hpp"
 #include "lib_hmm.hpp"
 #include "lib_diar.hpp"
+#include "lib_lda.hpp"
 
 // ------------------------------------------------------------------------------------------
 // RCCL gather (one process per GPU; librccl is loaded lazily so CPU-only hosts can load us)
