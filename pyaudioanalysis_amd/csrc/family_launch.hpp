@@ -3,7 +3,9 @@
 // host side of the library (paa_lib.hip and the lib_*.hpp units it is made of) sees only these functions and the families'
 // host-side layout / selection code in the kernel headers.  All of them queue ONE kernel on `stream` and return 0, or -1 when
 // the launch failed (hipGetLastError has the reason).  The one-wave families (fast, ct, tri, mix, blu, generic) take their
-// layout and one TileArgs record, and launch through tile_launch below.
+// layout and one TileArgs record, and launch through tile_launch below; the workgroup-wide ones (wgr, wgs here, the wg kernels
+// of lib_plan.hpp) take one WgArgs record plus what is their own, and launch through wg_launch.  Both helpers keep ONE rule
+// for kernels with more than 64 KB of LDS: one LdsAttrCache per kernel instance, raised to exactly the bytes launched.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,6 +44,35 @@ int tile_launch(void (*kernel)(PlanDev, L, const unsigned char *, const T *, con
     const unsigned grid = (unsigned)((a.n_tiles + waves - 1) / waves);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, a.stream, a.P, layout, a.blob, (const T *)a.d_packed, a.clips, a.norms,
                        a.tiles, (int)a.n_tiles, a.d_out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// what every launch of a workgroup-wide family needs (lib_dispatch.hpp: wg_args fills it from the plan)
+struct WgArgs {
+    const PlanDev &P;
+    const void *d_packed;            // the samples, as TileArgs::d_packed
+    int sample_kind;
+    const ClipDev *clips;
+    const ClipNorm *norms;
+    double *d_out;
+    int num_cu;
+    hipStream_t stream;
+};
+// the scratch rows of a chunk of frames between a spectrum kernel and its feature kernel (lib_plan.hpp: wg_scratch): Nf magnitudes
+// and 3 time-domain partials per row; psum: kernels_wgs.hpp's partial sums, 4 doubles per row and unit
+struct WgScratch {
+    double *spec, *tfeat, *psum;
+};
+// the launch of every workgroup-wide kernel, under tile_launch's rule for `attr`
+template <typename... Params, typename... Args>
+int wg_launch(void (*kernel)(Params...), LdsAttrCache &attr, unsigned grid, unsigned threads, size_t lds, hipStream_t stream,
+              const Args &...args) {
+    if (!attr.covers(lds)) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return -1;
+        attr.set(lds);
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, stream, args...);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -141,18 +172,14 @@ int blu(const blu::BluLayout &bl, const TileArgs &a);
 int generic(const GenLayout &gl, const TileArgs &a);
 // kernels_wgr.hpp: workgroup-wide three-pass register transform with fused features (16 000- / 8 000-sample windows); `runs`:
 // runs of consecutive frames, one workgroup walks runs b, b + grid, ...
-int wgr(int shape_id, int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
-        const Tile *runs, long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream);
+int wgr(int shape_id, int mode, const Tile *runs, long long n_runs, const wgr::WgrTab *d_tab, const WgArgs &a);
 // kernels_wgs.hpp: real-input split of the long even windows r0 x q samples (12 / 6 x 3675: 44 100, 22 050; 12 / 8 / 6 x 4000: 48 000, 32 000, 24 000),
 // three register passes per sub-transform; `tasks`: (frame, task type) records handed out through `counter` (zero at the first launch; the kernel
-// leaves it at zero); magnitudes go to the frames' UNIT-MAJOR rows of `spec` (spectrogram plans: d_out, natural order), the time-domain partials of
-// a frame to `tfeat`, the units' sum X / sum (k + 1) X / max X to `psum` (4 doubles per row and unit, r0 / 2 units)
-int wgs(int r0, int q, int sample_kind, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
-        const wg::FrameRef *tasks, int n_tasks, int *counter, int num_cu, double *spec, double *tfeat, double *psum, double *d_out,
-        hipStream_t stream);
+// leaves it at zero); magnitudes go to the frames' UNIT-MAJOR rows of s.spec (spectrogram plans: d_out, natural order), the time-domain partials of
+// a frame to s.tfeat, the units' sum X / sum (k + 1) X / max X to s.psum (r0 / 2 units)
+int wgs(int r0, int q, const wg::FrameRef *tasks, int n_tasks, int *counter, const WgScratch &s, const WgArgs &a);
 // ... and the features of those frames from the unit-major rows (one workgroup per frame)
-int wgs_feat(int r0, int q, const PlanDev &P, const wg::FrameRef *frames, int n_frames, const ClipDev *clips, const double *spec,
-             const double *tfeat, const double *psum, double *d_out, hipStream_t stream);
+int wgs_feat(int r0, int q, const wg::FrameRef *frames, int n_frames, const WgScratch &s, const WgArgs &a);
 // kernels_svc.hpp: multi-class probabilistic SVC over the columns of feats [n_dims][ld] (two kernels: the per-class sums go to
 // `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,

@@ -10,24 +10,25 @@
 namespace paa {
 namespace launch {
 
-template <typename SH, typename T>
-static int wgr_modes(int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *runs,
-                     long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream) {
-    if (mode == 0) return wgr::wgr_launch_one<SH, T, 0>(P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
-    if (mode == 1) return wgr::wgr_launch_one<SH, T, 1>(P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
-    return wgr::wgr_launch_one<SH, T, 2>(P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
+template <typename SH, typename T, int MODE>
+static int wgr_one(const Tile *runs, long long n_runs, const wgr::WgrTab *d_tab, const WgArgs &a) {
+    static LdsAttrCache attr;
+    const unsigned grid = (unsigned)std::min<long long>(n_runs, a.num_cu);
+    return wg_launch(&wgr::wgr_kernel<SH, T, MODE>, attr, grid, SH::NT, (size_t)SH::LDS_BYTES, a.stream, a.P, (const T *)a.d_packed, a.clips,
+                     a.norms, runs, (int)n_runs, d_tab, a.d_out);
 }
 template <typename SH>
-static int wgr_kinds(int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
-                     const Tile *runs, long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream) {
-    return with_sample_type(sample_kind, [&](auto tag) {
-        return wgr_modes<SH, PAA_SAMPLE_T(tag)>(mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
+static int wgr_shape(int mode, const Tile *runs, long long n_runs, const wgr::WgrTab *d_tab, const WgArgs &a) {
+    return with_sample_type(a.sample_kind, [&](auto tag) {
+        typedef PAA_SAMPLE_T(tag) T;
+        if (mode == 0) return wgr_one<SH, T, 0>(runs, n_runs, d_tab, a);
+        if (mode == 1) return wgr_one<SH, T, 1>(runs, n_runs, d_tab, a);
+        return wgr_one<SH, T, 2>(runs, n_runs, d_tab, a);
     });
 }
-int wgr(int shape_id, int sample_kind, int mode, const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms,
-        const Tile *runs, long long n_runs, int num_cu, const wgr::WgrTab *d_tab, double *d_out, hipStream_t stream) {
-    if (shape_id == 1) return wgr_kinds<wgr::S16000>(sample_kind, mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
-    if (shape_id == 2) return wgr_kinds<wgr::S8000>(sample_kind, mode, P, d_packed, clips, norms, runs, n_runs, num_cu, d_tab, d_out, stream);
+int wgr(int shape_id, int mode, const Tile *runs, long long n_runs, const wgr::WgrTab *d_tab, const WgArgs &a) {
+    if (shape_id == 1) return wgr_shape<wgr::S16000>(mode, runs, n_runs, d_tab, a);
+    if (shape_id == 2) return wgr_shape<wgr::S8000>(mode, runs, n_runs, d_tab, a);
     return -1;
 }
 

@@ -751,20 +751,5 @@ inline void wgr_build_runs(const std::vector<ClipDev> &clips, int num_cu, std::v
     }
 }
 
-template <typename SH, typename T, int MODE>
-inline int wgr_launch_one(const PlanDev &P, const void *d_packed, const ClipDev *clips, const ClipNorm *norms, const Tile *runs,
-                          long long n_runs, int num_cu, const WgrTab *d_tab, double *d_out, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&wgr_kernel<SH, T, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                SH::LDS_BYTES) != hipSuccess) return -1;
-        attr_set = true;
-    }
-    const unsigned grid = (unsigned)std::min<long long>(n_runs, num_cu);
-    hipLaunchKernelGGL((wgr_kernel<SH, T, MODE>), dim3(grid), dim3(SH::NT), (size_t)SH::LDS_BYTES, stream, P, (const T *)d_packed, clips,
-                       norms, runs, (int)n_runs, d_tab, d_out);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 }  // namespace wgr
 }  // namespace paa

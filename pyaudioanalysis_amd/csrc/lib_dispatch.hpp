@@ -93,9 +93,7 @@ static int tile_execute(paa_plan *p, const void *d_packed, double *d_out, const 
     ProfScope prof_scope;
     { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
     const TileArgs a{p->P, p->fam.d_blob, d_packed, p->sample_kind, p->d_clips, p->d_norms, tiles, n_tiles, d_out, cs()};
-    if (Launch(p, a))
-        return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
-    return PAA_OK;
+    return Launch(p, a) ? launch_failed(p) : PAA_OK;
 }
 
 // ---- kernels_fast.hpp: int16, window 800, step 400 / 800, features only
@@ -315,14 +313,23 @@ static int wg_build_work(paa_plan *p, int wgs_r0) {
 }
 static int fam_wgs_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, wgs::wgs_select(c.window).r0); }
 static int fam_wg_work(FamilyCtx &c, std::vector<Tile> &) { return wg_build_work(c.p, 0); }
-static int run_wg_any(paa_plan *p, const void *d_packed, double *d_out, const wgs::Sel &sel) {
-    return with_sample_type(p->sample_kind, [&](auto tag) { return run_wg<PAA_SAMPLE_T(tag)>(p, d_packed, d_out, sel); });
+// one WgArgs per execute of a workgroup-wide family
+static WgArgs wg_args(const paa_plan *p, const void *d_packed, double *d_out) {
+    return WgArgs{p->P, d_packed, p->sample_kind, p->d_clips, p->d_norms, d_out, g_num_cu, cs()};
+}
+static int fam_wgr_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *runs, long long n_runs) {
+    return run_wgr(p, wg_args(p, d_packed, d_out), runs, n_runs);
 }
 static int fam_wgs_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
-    return run_wg_any(p, d_packed, d_out, wgs::wgs_select(p->P.W));
+    return run_wgs(p, wg_args(p, d_packed, d_out), wgs::wgs_select(p->P.W));
 }
 static int fam_wg_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *, long long) {
-    return run_wg_any(p, d_packed, d_out, wgs::Sel{0, 0});
+    const WgArgs a = wg_args(p, d_packed, d_out);
+    return with_sample_type(p->sample_kind, [&](auto tag) {
+        typedef PAA_SAMPLE_T(tag) T;
+        wg_kernel_order<T>();
+        return p->fam.wl.r0 ? run_wg_split<T>(p, a) : run_wg_lds<T>(p, a);
+    });
 }
 
 // kernels_big.hpp: chunked Stockham passes through HBM scratch (what nothing else takes; no CPU fallback)
@@ -343,7 +350,7 @@ static const Family kFamilies[] = {
     {"mix", fam_mix_select, tile_work<fam_mix_rule>, tile_execute<fam_mix_launch>, true, true},
     {"blu", fam_blu_select, tile_work<fam_blu_rule>, tile_execute<fam_blu_launch>, true, true},
     {"generic", fam_generic_select, tile_work<fam_generic_rule>, tile_execute<fam_generic_launch>, true, true},
-    {"wgr", fam_wgr_select, fam_wgr_work, run_wgr, false, false},
+    {"wgr", fam_wgr_select, fam_wgr_work, fam_wgr_execute, false, false},
     {"wgs", fam_wgs_select, fam_wgs_work, fam_wgs_execute, false, false},
     {"wg", fam_wg_select, fam_wg_work, fam_wg_execute, false, false},
     {"hbm", fam_hbm_select, no_work, fam_hbm_execute, false, false},

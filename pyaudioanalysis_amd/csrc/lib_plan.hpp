@@ -137,7 +137,8 @@ struct FamilyChoice {
     mix::MixLayout ml;               // kernels_mix.hpp
     blu::BluLayout bl;               // kernels_blu.hpp
     GenLayout gl;                    // kernels_generic.hpp
-    wg::WgLayout wl;                 // kernels_wg.hpp / kernels_wgs.hpp
+    wg::WgLayout wl;                 // kernels_wg.hpp: r0 = 0 runs on run_wg_lds, r0 > 0 on run_wg_split (kernels_wgs.hpp: r0 > 0 is its select's
+                                     // condition; its own (r0, q) come from wgs_select)
     size_t lds = 0;
     std::string kernel_name;
     unsigned char *d_blob = nullptr;       // the entry's device tables (ct, tri, mix, blu, generic: LDS + global tables; wgr: WgrTab;
@@ -164,7 +165,7 @@ struct paa_plan {
     FamilyChoice fam;                // the kernel that runs the plan (lib_dispatch.hpp)
     bool blob_cached = false;        // fam.d_blob belongs to the table set's cached FamilyChoice (not freed with the plan)
     void *d_block = nullptr;         // the plan's one device block: d_clips, d_tiles, d_chunks, d_norms, d_psum / pmin / pmax point into it
-    void *d_big = nullptr;           // scratch of the big-window paths (run_wg, run_big)
+    void *d_big = nullptr;           // scratch of the big-window paths (grow_big; wg_scratch carves it for run_wg_lds / run_wg_split / run_wgs, run_big for itself)
     size_t big_bytes = 0;
     std::vector<wg::FrameRef> wg_frames;              // every frame of the plan, chunk after chunk (a chunk's rows fit the scratch)
     std::vector<std::pair<long long, long long>> wg_chunks;     // [first, last) into wg_frames
@@ -232,6 +233,23 @@ static int launch_stats(paa_plan *p, const void *d_packed) {
     return PAA_OK;
 }
 
+// the scratch of the big-window paths: p->d_big holds at least `need` bytes; *fresh: the block is a new one (its contents are
+// undefined).  A plan whose allocation failed is left without a block, big_bytes = 0: its next execute allocates again
+static int grow_big(paa_plan *p, size_t need, bool *fresh) {
+    *fresh = false;
+    if (need <= p->big_bytes) return PAA_OK;
+    if (p->d_big) {
+        HIP_TRY(hipStreamSynchronize(cs()));          // (kernels of the last execute may still use the old block)
+        (void)hipFree(p->d_big);
+        p->d_big = nullptr;
+        p->big_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&p->d_big, need));
+    p->big_bytes = need;
+    *fresh = true;
+    return PAA_OK;
+}
+
 // windows beyond the LDS envelope: chunked Stockham passes through HBM scratch (kernels_big.hpp)
 template <typename T>
 static int run_big(paa_plan *p, const void *d_packed, double *d_out) {
@@ -243,11 +261,8 @@ static int run_big(paa_plan *p, const void *d_packed, double *d_out) {
     long long C = (long long)std::max<size_t>(1, ((size_t)1 << 30) / per_frame);
     C = std::min<long long>(std::min<long long>(C, 65535), std::max<long long>(maxT, 1));
     const size_t need = (size_t)C * Nc * 32 + (size_t)(C + 1) * Nf * 8 + (size_t)C * 24 + 256;
-    if (need > p->big_bytes) {
-        if (p->d_big) { HIP_TRY(hipStreamSynchronize(cs())); (void)hipFree(p->d_big); p->d_big = nullptr; }
-        HIP_TRY(hipMalloc(&p->d_big, need));
-        p->big_bytes = need;
-    }
+    bool fresh;
+    { const int rc_g = grow_big(p, need, &fresh); if (rc_g) return rc_g; }
     double2 *bufA = reinterpret_cast<double2 *>(p->d_big);
     double2 *bufB = bufA + C * Nc;
     double *spec = reinterpret_cast<double *>(bufB + C * Nc);
@@ -312,10 +327,20 @@ struct ProfScope {
         HIP_TRY(hipEventRecord(start, cs()));
         return PAA_OK;
     }
-    ~ProfScope() { if (stop) (void)hipEventRecord(stop, cs()); }
+    // closes the bracket here, behind the launches queued so far (else: where the scope ends)
+    void end() {
+        if (stop) (void)hipEventRecord(stop, cs());
+        stop = nullptr;
+    }
+    ~ProfScope() { end(); }
 };
 
-// the delta rows of every clip of a features plan with deltas (kernels_wg.hpp: wg_delta_kernel), behind run_wg / run_wgr
+// a launch helper of family_launch.hpp returned -1 for the plan's kernel (`of`: which of its kernels, if not the first)
+static int launch_failed(const paa_plan *p, const char *of = "") {
+    return fail(PAA_ERR_HIP, "launch of %s%s failed: %s", of, p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+}
+
+// the delta rows of every clip of a features plan with deltas (kernels_wg.hpp: wg_delta_kernel), behind every workgroup-wide path
 static int launch_wg_deltas(paa_plan *p, double *d_out) {
     if (p->P.mode != 0 || !p->P.deltas) return PAA_OK;
     long long maxT = 0;
@@ -333,112 +358,144 @@ static int launch_wg_deltas(paa_plan *p, double *d_out) {
     return PAA_OK;
 }
 
-// windows beyond the one-wave kernels whose transform fits one workgroup's LDS (kernels_wg.hpp; ws.r0 > 0: the split runs on
-// kernels_wgs.hpp, r0 x q samples): per chunk of frames one launch for the spectra of ALL its frames and one for their
-// features, then one for the delta rows of all clips
+// ---- windows beyond the one-wave kernels whose transform fits one workgroup's LDS: per chunk of frames (lib_dispatch.hpp:
+// wg_build_work) one launch for the spectra of ALL its frames and one for their features, then one for the delta rows of all
+// clips.  Three paths, one function each: run_wg_lds (kernels_wg.hpp, the whole transform in LDS), run_wg_split (kernels_wg.hpp,
+// r0 sub-transforms) and run_wgs (kernels_wgs.hpp, the register split of r0 x q samples)
+// p->d_big of the three: [spec: Nf doubles per row | tfeat: 3 per row | psum: psum_row per row | the split transforms' task
+// counters: 256 bytes], a row per frame of the plan's largest chunk
+struct WgBig {
+    WgScratch s;
+    int *counters;
+    bool fresh;          // the block is a new one: nothing in it is zero
+};
+static int wg_scratch(paa_plan *p, size_t psum_row, WgBig &b) {
+    const size_t rows = (size_t)p->wg_rows;
+    const size_t o_tfeat = rows * (size_t)p->P.Nf, o_psum = o_tfeat + 3 * rows, o_counters = o_psum + psum_row * rows;      // in doubles
+    const int rc = grow_big(p, o_counters * 8 + 256, &b.fresh);
+    if (rc) return rc;
+    double *base = reinterpret_cast<double *>(p->d_big);
+    b.s = WgScratch{base, base + o_tfeat, base + o_psum};
+    b.counters = reinterpret_cast<int *>(base + o_counters);
+    return PAA_OK;
+}
+// chunk ci of the plan's frame list and -- split transforms -- of its task list, on the device
+struct WgChunk {
+    const wg::FrameRef *frames, *tasks;
+    int n, nt;
+};
+static WgChunk wg_chunk(const paa_plan *p, size_t ci) {
+    const auto &ch = p->wg_chunks[ci];
+    const auto tc = ci < p->wg_task_chunks.size() ? p->wg_task_chunks[ci] : std::pair<long long, long long>(0, 0);
+    return WgChunk{p->d_wg_frames + ch.first, p->d_wg_tasks + tc.first, (int)(ch.second - ch.first), (int)(tc.second - tc.first)};
+}
+
+// A code object holds its kernels in the order of their first use in the translation unit, and that order is part of the device code
+// the GPU runs validated (scripts/device_code_hash.py, tests/test_abi_cpu.py::test_device_code_is_the_validated_one): kernels_wg.hpp's
+// instances of one sample type are first named here, before the launchers below (fam_wg_execute)
 template <typename T>
-static int run_wg(paa_plan *p, const void *d_packed, double *d_out, const wgs::Sel &ws) {
-    const PlanDev &P = p->P;
-    const wg::WgLayout &wl = p->fam.wl;
-    const unsigned short *d_perm = reinterpret_cast<const unsigned short *>(p->fam.d_blob);
-    const size_t psum_row = ws.r0 ? (size_t)(ws.r0 / 2) * 4 : 0;                            // kernels_wgs.hpp: the units' partial sums of a row
-    const size_t need = (size_t)p->wg_rows * ((size_t)P.Nf * 8 + 24 + psum_row * 8) + 256;       // (+ the task counter of the split transform)
-    bool fresh = false;
-    if (need > p->big_bytes) {
-        if (p->d_big) { HIP_TRY(hipStreamSynchronize(cs())); (void)hipFree(p->d_big); p->d_big = nullptr; p->big_bytes = 0; }
-        HIP_TRY(hipMalloc(&p->d_big, need));
-        p->big_bytes = need;
-        fresh = true;
-    }
-    double *spec = reinterpret_cast<double *>(p->d_big);
-    double *tfeat = spec + (size_t)p->wg_rows * P.Nf;
-    double *psum = tfeat + 3 * (size_t)p->wg_rows;
-    int *task_counter = reinterpret_cast<int *>(psum + psum_row * (size_t)p->wg_rows);
-    // (kernels_wgs.hpp: one counter per XCD segment + the workgroups that are done; its last workgroup leaves them at zero)
-    if (fresh && ws.r0) HIP_TRY(hipMemsetAsync(task_counter, 0, 16 * sizeof(int), cs()));
+static void wg_kernel_order() {
+    const void *const order[] = {(const void *)&wg::wg_spectrum_kernel<T, 512>, (const void *)&wg::wg_spectrum_kernel<T, 768>,
+                                 (const void *)&wg::wg_split_kernel<T, 512>, (const void *)&wg::wg_split_kernel<T, 768>,
+                                 (const void *)&wg::wg_feat_kernel<true>, (const void *)&wg::wg_time_kernel<T>,
+                                 (const void *)&wg::wg_feat_kernel<false>};
+    (void)order;
+}
+// kernels_wg.hpp's kernels, one launcher (and one LDS attribute) per instance
+template <typename T, int NT>
+static int wg_spectrum(const paa_plan *p, const WgArgs &a, const WgChunk &c, const WgScratch &s) {
     static LdsAttrCache attr;
-    if (!attr.covers((size_t)wl.lds_bytes)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_spectrum_kernel<T, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_spectrum_kernel<T, 768>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_split_kernel<T, 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_split_kernel<T, 768>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, wl.lds_bytes));
-        attr.set((size_t)wl.lds_bytes);
-    }
-    static LdsAttrCache attr_feat;
-    if (!attr_feat.covers((size_t)wl.feat_lds_bytes)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&wg::wg_feat_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    wl.feat_lds_bytes));
-        attr_feat.set((size_t)wl.feat_lds_bytes);
-    }
+    const wg::WgLayout &wl = p->fam.wl;
+    // persistent workgroups: as many as the LDS footprint lets the chip hold at once, each walks frames b, b + grid, ...
+    const unsigned per_cu = (unsigned)std::max<size_t>(1, ((size_t)160 * 1024) / (size_t)wl.lds_bytes);
+    const unsigned grid = std::min<unsigned>((unsigned)c.n, (unsigned)a.num_cu * std::min<unsigned>(per_cu, NT == 768 ? 2u : 4u));
+    return wg_launch(&wg::wg_spectrum_kernel<T, NT>, attr, grid, NT, (size_t)wl.lds_bytes, a.stream, a.P, wl,
+                     reinterpret_cast<const unsigned short *>(p->fam.d_blob), (const T *)a.d_packed, a.clips, a.norms, c.frames, c.n, s.spec,
+                     s.tfeat, a.d_out);
+}
+template <typename T, int NT>
+static int wg_split(const paa_plan *p, const WgArgs &a, const WgChunk &c, int *counter, const WgScratch &s) {
+    static LdsAttrCache attr;
+    const wg::WgLayout &wl = p->fam.wl;
+    // persistent workgroups over (frame, sub-transform pair) tasks, one per CU
+    const unsigned grid = std::min<unsigned>((unsigned)c.nt, (unsigned)a.num_cu);
+    return wg_launch(&wg::wg_split_kernel<T, NT>, attr, grid, NT, (size_t)wl.lds_bytes, a.stream, a.P, wl,
+                     reinterpret_cast<const unsigned short *>(p->fam.d_blob), (const T *)a.d_packed, a.clips, a.norms, c.tasks, c.nt, counter,
+                     s.spec, a.d_out);
+}
+template <bool STAGED>          // (wl.feat_staged)
+static int wg_feat(const paa_plan *p, const WgArgs &a, const WgChunk &c, const WgScratch &s) {
+    static LdsAttrCache attr;
+    return wg_launch(&wg::wg_feat_kernel<STAGED>, attr, (unsigned)c.n, wg::kFeatThreads, (size_t)p->fam.wl.feat_lds_bytes, a.stream, a.P,
+                     c.frames, a.clips, s.spec, s.tfeat, a.d_out);
+}
+
+// (in all three, bench.py's event pairs bracket the spectrum kernel: the dominant one of the path)
+template <typename T>
+static int run_wg_lds(paa_plan *p, const WgArgs &a) {
+    WgBig b;
+    { const int rc_b = wg_scratch(p, 0, b); if (rc_b) return rc_b; }
     for (size_t ci = 0; ci < p->wg_chunks.size(); ++ci) {
-        const auto &ch = p->wg_chunks[ci];
-        const unsigned n = (unsigned)(ch.second - ch.first);
-        const wg::FrameRef *fr = p->d_wg_frames + ch.first;
-        ProfScope prof_scope;          // (bench.py's event pairs bracket the spectrum kernel: the dominant one of this path)
+        const WgChunk c = wg_chunk(p, ci);
+        ProfScope prof_scope;
         { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-        if (wl.r0) {
-            // split transforms: persistent workgroups over (frame, sub-transform pair) tasks, one per CU
-            const auto &tc = p->wg_task_chunks[ci];
-            const unsigned nt = (unsigned)(tc.second - tc.first);
-            const wg::FrameRef *tk = p->d_wg_tasks + tc.first;
-            const unsigned grid = std::min<unsigned>(nt, (unsigned)g_num_cu);
-            if (!ws.r0) HIP_TRY(hipMemsetAsync(task_counter, 0, sizeof(int), cs()));
-            if (ws.r0) {
-                if (launch::wgs(ws.r0, ws.q, p->sample_kind, P, d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, g_num_cu, spec, tfeat, psum, d_out, cs()))
-                    return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
-            } else if (wl.threads == 768)
-                hipLaunchKernelGGL((wg::wg_split_kernel<T, 768>), dim3(grid), dim3(768), (size_t)wl.lds_bytes, cs(), P, wl,
-                                   d_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
-            else
-                hipLaunchKernelGGL((wg::wg_split_kernel<T, 512>), dim3(grid), dim3(512), (size_t)wl.lds_bytes, cs(), P, wl,
-                                   d_perm, (const T *)d_packed, p->d_clips, p->d_norms, tk, (int)nt, task_counter, spec, d_out);
-            if (prof_scope.stop) { (void)hipEventRecord(prof_scope.stop, cs()); prof_scope.stop = nullptr; }
-            if (P.mode == 0 && !ws.r0)          // (kernels_wgs.hpp forms the time-domain features in its {1, 2} tasks)
-                hipLaunchKernelGGL((wg::wg_time_kernel<T>), dim3(n), dim3(64 * wg::kTimeWaves), 0, cs(), P, (const T *)d_packed, p->d_clips, p->d_norms,
-                                   fr, tfeat);
-        } else {
-        // persistent workgroups: as many as the LDS footprint lets the chip hold at once, each walks frames b, b + grid, ...
-        const unsigned per_cu = (unsigned)std::max<size_t>(1, ((size_t)160 * 1024) / (size_t)wl.lds_bytes);
-        const unsigned grid = std::min<unsigned>(n, (unsigned)g_num_cu * std::min<unsigned>(per_cu, wl.threads == 768 ? 2u : 4u));
-        if (wl.threads == 768)
-            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 768>), dim3(grid), dim3(768), (size_t)wl.lds_bytes, cs(), P, wl,
-                               d_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
-        else
-            hipLaunchKernelGGL((wg::wg_spectrum_kernel<T, 512>), dim3(grid), dim3(512), (size_t)wl.lds_bytes, cs(), P, wl,
-                               d_perm, (const T *)d_packed, p->d_clips, p->d_norms, fr, (int)n, spec, tfeat, d_out);
-        if (prof_scope.stop) { (void)hipEventRecord(prof_scope.stop, cs()); prof_scope.stop = nullptr; }
-        }
-        if (P.mode != 1 && ws.r0) {
-            if (launch::wgs_feat(ws.r0, ws.q, P, fr, (int)n, p->d_clips, spec, tfeat, psum, d_out, cs()))
-                return fail(PAA_ERR_HIP, "launch of the feature kernel of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
-        } else if (P.mode != 1) {
-            if (wl.feat_staged)
-                hipLaunchKernelGGL(wg::wg_feat_kernel<true>, dim3(n), dim3(wg::kFeatThreads), (size_t)wl.feat_lds_bytes, cs(), P, fr,
-                                   p->d_clips, spec, tfeat, d_out);
-            else
-                hipLaunchKernelGGL(wg::wg_feat_kernel<false>, dim3(n), dim3(wg::kFeatThreads), (size_t)wl.feat_lds_bytes, cs(), P, fr,
-                                   p->d_clips, spec, tfeat, d_out);
-        }
-        HIP_TRY(hipGetLastError());
+        if (p->fam.wl.threads == 768 ? wg_spectrum<T, 768>(p, a, c, b.s) : wg_spectrum<T, 512>(p, a, c, b.s)) return launch_failed(p);
+        prof_scope.end();
+        if (a.P.mode != 1 && (p->fam.wl.feat_staged ? wg_feat<true>(p, a, c, b.s) : wg_feat<false>(p, a, c, b.s)))
+            return launch_failed(p, "the feature kernel of ");
     }
-    return launch_wg_deltas(p, d_out);
+    return launch_wg_deltas(p, a.d_out);
+}
+
+template <typename T>
+static int run_wg_split(paa_plan *p, const WgArgs &a) {
+    WgBig b;
+    { const int rc_b = wg_scratch(p, 0, b); if (rc_b) return rc_b; }
+    for (size_t ci = 0; ci < p->wg_chunks.size(); ++ci) {
+        const WgChunk c = wg_chunk(p, ci);
+        ProfScope prof_scope;
+        { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
+        HIP_TRY(hipMemsetAsync(b.counters, 0, sizeof(int), a.stream));
+        if (p->fam.wl.threads == 768 ? wg_split<T, 768>(p, a, c, b.counters, b.s) : wg_split<T, 512>(p, a, c, b.counters, b.s))
+            return launch_failed(p);
+        prof_scope.end();
+        if (a.P.mode == 0) {
+            hipLaunchKernelGGL((wg::wg_time_kernel<T>), dim3((unsigned)c.n), dim3(64 * wg::kTimeWaves), 0, a.stream, a.P, (const T *)a.d_packed,
+                               a.clips, a.norms, c.frames, b.s.tfeat);
+            HIP_TRY(hipGetLastError());
+        }
+        if (a.P.mode != 1 && (p->fam.wl.feat_staged ? wg_feat<true>(p, a, c, b.s) : wg_feat<false>(p, a, c, b.s)))
+            return launch_failed(p, "the feature kernel of ");
+    }
+    return launch_wg_deltas(p, a.d_out);
+}
+
+static int run_wgs(paa_plan *p, const WgArgs &a, const wgs::Sel &ws) {
+    WgBig b;
+    { const int rc_b = wg_scratch(p, (size_t)(ws.r0 / 2) * 4, b); if (rc_b) return rc_b; }
+    // (kernels_wgs.hpp: one counter per XCD segment + the workgroups that are done; its last workgroup leaves them at zero)
+    if (b.fresh) HIP_TRY(hipMemsetAsync(b.counters, 0, 16 * sizeof(int), a.stream));
+    for (size_t ci = 0; ci < p->wg_chunks.size(); ++ci) {
+        const WgChunk c = wg_chunk(p, ci);
+        ProfScope prof_scope;
+        { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
+        if (launch::wgs(ws.r0, ws.q, c.tasks, c.nt, b.counters, b.s, a)) return launch_failed(p);
+        prof_scope.end();
+        // (the time-domain features are formed in the kernel's {1, 2} tasks)
+        if (a.P.mode != 1 && launch::wgs_feat(ws.r0, ws.q, c.frames, c.n, b.s, a)) return launch_failed(p, "the feature kernel of ");
+    }
+    return launch_wg_deltas(p, a.d_out);
 }
 
 // the fused three-pass kernel (kernels_wgr.hpp): ONE launch for all frames of all clips, then the delta rows
-static int run_wgr(paa_plan *p, const void *d_packed, double *d_out, const Tile *runs, long long n_runs) {
-    const PlanDev &P = p->P;
+static int run_wgr(paa_plan *p, const WgArgs &a, const Tile *runs, long long n_runs) {
     if (n_runs > 0) {
         ProfScope prof_scope;
         { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
-        if (launch::wgr(wgr::wgr_shape_id(P.W), p->sample_kind, P.mode, P, d_packed, p->d_clips, p->d_norms, runs, n_runs, g_num_cu,
-                        reinterpret_cast<const wgr::WgrTab *>(p->fam.d_blob), d_out, cs()))
-            return fail(PAA_ERR_HIP, "launch of %s failed: %s", p->fam.kernel_name.c_str(), hipGetErrorString(hipGetLastError()));
+        if (launch::wgr(wgr::wgr_shape_id(a.P.W), a.P.mode, runs, n_runs, reinterpret_cast<const wgr::WgrTab *>(p->fam.d_blob), a))
+            return launch_failed(p);
     }
-    return launch_wg_deltas(p, d_out);
+    return launch_wg_deltas(p, a.d_out);
 }
 
 #include "lib_dispatch.hpp"
