@@ -274,6 +274,36 @@ int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dim
                             const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                             int32_t *d_neighbors);
 
+/* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
+ * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as
+ * train_svm_regression makes them, audioTrainTest.py:222-226) for many feature vectors and many models at once: what
+ * file_regression (audioTrainTest.py:1099-1151) asks for once per model_name_* model -- one per target value, each with
+ * its own MEANS file -- and evaluate_regression (:774-855) once per test vector of each of its n_exp models per parameter
+ * value.  A handle is a BANK of n_models models that share n_dims: model m owns the support vectors sv_offsets[m] ..
+ * sv_offsets[m + 1] - 1 of support_vectors [total_sv][n_dims] and dual_coef [total_sv] (scikit-learn's _dual_coef_[0]),
+ * rho[m] (= -_intercept_), kernel_type[m] 0 (LINEAR) or 2 (RBF, with gamma[m] = _gamma) and its own standardisation
+ * mean[m][n_dims] / std[m][n_dims].  A model with no support vectors is legal (scikit-learn makes one when epsilon exceeds
+ * the label spread): it predicts -rho.  1 <= n_models <= 4096, 1 <= n_dims <= 256, offsets from 0 and not decreasing,
+ * gamma > 0 for RBF: anything else returns PAA_ERR_ARG, before any device work.  support_vectors / dual_coef may be NULL
+ * only when total_sv is 0.
+ * feats is feature-major [n_dims][ld], vector v in column v.  out[m][v] = sum_s dual_coef[s] K(sv_s, (x_v - mean_m) / std_m)
+ * - rho_m with the support vectors added in the model's order (libsvm's svm_predict_values); a value does not depend on the
+ * vector's place in the batch, on n_vec, on ld or on the other models of the bank.  Non-finite inputs are NOT validated
+ * (as in paa_svc_*): they propagate by IEEE rules.                                                                   */
+int paa_svr_create(int n_models, const int64_t *sv_offsets, const double *support_vectors, const double *dual_coef,
+                   const double *rho, const int32_t *kernel_type, const double *gamma, const double *mean, const double *std,
+                   int n_dims, void **out_handle);
+int paa_svr_destroy(void *handle);
+int paa_svr_num_models(const void *handle);
+/* host buffers in and out (synchronous): out [n_models][n_vec] */
+int paa_svr_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, double *out);
+/* device buffers in and out (the resident mid-term matrix of a plan, paa_plan_mid_execute), asynchronous on the library
+ * stream: d_out [n_models][ld_out], ld_out >= n_vec                                                                    */
+int paa_svr_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec, double *d_out,
+                            int64_t ld_out);
+/* tests: out4 = windows per workgroup, models per workgroup, support vectors per LDS tile, lanes per window group */
+int paa_debug_svr_geometry(int32_t *out4);
+
 /* ---- audioTrainTest.classifier_wrapper for the tree ensembles (audioTrainTest.py:84-93) -------------------------------
  * scikit-learn's RandomForestClassifier / ExtraTreesClassifier (kind PAA_FOREST_AVERAGED) and GradientBoostingClassifier
  * (kind PAA_FOREST_BOOSTED) over many feature vectors at once, as mid_term_file_classification (audioSegmentation.py:583-594)
@@ -293,6 +323,12 @@ int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dim
  * division by n_trees; boosted: the raw scores before the link).                                                        */
 #define PAA_FOREST_AVERAGED 0
 #define PAA_FOREST_BOOSTED  1
+/* scikit-learn's RandomForestRegressor (audioTrainTest.regression_wrapper, audioTrainTest.py:96-111, as
+ * train_random_forest_regression makes it, :229-233): an averaged forest with ONE output.  value [nodes], n_classes must be
+ * 1 (for this kind and only for it), learning_rate and init are not read.  proba [n_vec][1] receives the prediction
+ * (0.0 + v_0 + v_1 + ... in tree order, divided by n_trees: RandomForestRegressor.predict with n_jobs=None, bit for bit),
+ * raw [n_vec][1] the sum before the division, label_index 0 (-1: a value of x is infinite in float32).                */
+#define PAA_FOREST_REGRESSOR 2
 int paa_forest_create(int kind, int n_trees, const int64_t *node_offsets, const int64_t *children_left,
                       const int64_t *children_right, const int64_t *feature, const double *threshold,
                       const uint8_t *missing_go_to_left, const double *value, int n_classes, int n_dims, double learning_rate,

@@ -12,7 +12,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpaa_hip.so")
-SOURCES = ["paa_lib.hip", "family_fast.hip", "family_ct.hip", "family_tri_a.hip", "family_tri_b.hip", "family_tri_c.hip", "family_reg_mix_generic.hip", "family_blu.hip", "family_wgr.hip", "family_wgs.hip", "family_svc.hip", "family_knn.hip", "family_forest.hip", "family_hmm.hip", "family_diar.hip", "family_lda.hip"]
+SOURCES = ["paa_lib.hip", "family_fast.hip", "family_ct.hip", "family_tri_a.hip", "family_tri_b.hip", "family_tri_c.hip", "family_reg_mix_generic.hip", "family_blu.hip", "family_wgr.hip", "family_wgs.hip", "family_svc.hip", "family_svr.hip", "family_knn.hip", "family_forest.hip", "family_hmm.hip", "family_diar.hip", "family_lda.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "paa_hip.h")]
 # -disable-machine-licm: the feature kernels' loop bodies are thousands of instructions long; hoisting every FP64 literal
 # and per-lane LDS address out of them creates >100 loop-invariant registers that then spill (AGPR copies at one wave per
@@ -24,12 +24,13 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-std=c++17", "-fPIC", "-mllvm", "-disabl
 #   1920 / 2205 / 1102 +2.5 %; the power-of-two three-pass unit was 1.5 % slower with it and keeps the default;
 # * -amdgpu-load-store-vectorizer=0 on top (no <2 x double> LDS loads, i.e. no ds_read2_b64 from the IR either): the headline kernel
 #   0.2477 ms; every other family lost (Bluestein -19 %: its global loads are no longer merged), so only family_fast.hip has it.
+MAX_JOBS = 16      # compile jobs at a time: a host may report many more CPUs than a command is given
 NO_LSO = ["-Xclang", "-target-feature", "-Xclang", "-load-store-opt"]
 UNIT_FLAGS = {
     "family_fast.hip": NO_LSO + ["-mllvm", "-amdgpu-load-store-vectorizer=0"],
     "family_ct.hip": NO_LSO, "family_tri_a.hip": NO_LSO, "family_tri_b.hip": NO_LSO, "family_reg_mix_generic.hip": NO_LSO,
     "family_blu.hip": NO_LSO,
-}   # family_wgr / wgs / svc / knn / forest / hmm / diar / lda.hip keep the default flags
+}   # family_wgr / wgs / svc / svr / knn / forest / hmm / diar / lda.hip keep the default flags
 
 
 def hipcc_path():
@@ -52,7 +53,7 @@ def build_to(lib, extra_flags=(), opt="-O3", verbose=False, jobs=None):
     """Compile every translation unit (in parallel) and link them into `lib`.  extra_flags go to compile AND link."""
     hipcc = hipcc_path()
     extra = list(extra_flags) + os.environ.get("PAA_HIPCC_FLAGS", "").split()
-    jobs = jobs or min(len(SOURCES), os.cpu_count() or 1)
+    jobs = min(jobs or len(SOURCES), os.cpu_count() or 1, MAX_JOBS)
     with tempfile.TemporaryDirectory(prefix="paa_build_") as tmp:
         def compile_one(src):
             obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")

@@ -102,6 +102,13 @@ _SIGNATURES = {
     "paa_svc_predict_f64": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int64, C.c_int64, c_f64p, c_f64p, c_i32p, c_f64p]),
     "paa_svc_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "paa_svr_create": (C.c_int, [C.c_int, c_i64p, c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int,
+                                 C.POINTER(C.c_void_p)]),
+    "paa_svr_destroy": (C.c_int, [C.c_void_p]),
+    "paa_svr_num_models": (C.c_int, [C.c_void_p]),
+    "paa_svr_predict_f64": (C.c_int, [C.c_void_p, c_f64p, C.c_int, C.c_int64, C.c_int64, c_f64p]),
+    "paa_svr_dev_predict_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "paa_debug_svr_geometry": (C.c_int, [c_i32p]),
     "paa_knn_create": (C.c_int, [c_f64p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "paa_knn_destroy": (C.c_int, [C.c_void_p]),
     "paa_knn_num_classes": (C.c_int, [C.c_void_p]),

@@ -449,6 +449,27 @@ def mid_term_labels(signal, sampling_rate, classifier, mean, std, mt_win, mid_st
     return model.labels(idx), np.max(proba, axis=1)
 
 
+def mid_term_regression_signal(signal, sampling_rate, models, means, stds, model_type, mt_win, mid_step, st_win, st_step):
+    """The regression values of every mid-term window of a mono signal -- a target such as arousal along a recording:
+    [n_models][n_windows].  An addition without a counterpart in the reference (which regresses whole files only,
+    audioTrainTest.file_regression): the mid-term matrix stays in HBM and goes straight into the SVR bank kernel (one
+    launch for all models and windows) or, for "randomforest", into one traversal / reduction pair per forest.  means /
+    stds: one row per model, or one vector shared by all."""
+    from . import audioTrainTest
+    if model_type not in audioTrainTest._REGRESSION_TYPES:
+        raise NotImplementedError("regression model type %r: the GPU path serves 'svm', 'svm_rbf' and 'randomforest'" % (model_type,))
+    mid = _mid_term_on_device(signal, sampling_rate, mt_win, mid_step, round(sampling_rate * st_win), round(sampling_rate * st_step))
+    if model_type in audioTrainTest._SVM_TYPES:
+        bank = audioTrainTest.svr_bank(models, means, stds)
+        with mid as (d_mid, M):
+            return bank.predict_device(d_mid, M, M)
+    forests = [audioTrainTest._forest_regressor(m) for m in models]
+    means = audioTrainTest._stats_rows(means, len(forests), forests[0].n_dims, "means")
+    stds = audioTrainTest._stats_rows(stds, len(forests), forests[0].n_dims, "stds")
+    with mid as (d_mid, M):
+        return np.stack([f.predict_device(d_mid, M, M, means[i], stds[i])[1][:, 0] for i, f in enumerate(forests)])
+
+
 def mid_term_classification(signal, sampling_rate, classifier, mean, std, class_names, mt_win, mid_step, st_win, st_step,
                             compute_beat=False, plot_results=False, gt_file="", model_type=None):
     """mid_term_file_classification on a signal and a loaded SVM, kNN or tree-ensemble model (reference :518-604 from

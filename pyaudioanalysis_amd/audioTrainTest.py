@@ -1,4 +1,5 @@
-"""Drop-in for the classification half of pyAudioAnalysis.audioTrainTest (reference: pyAudioAnalysis/audioTrainTest.py).
+"""Drop-in for the classification and regression halves of pyAudioAnalysis.audioTrainTest (reference:
+pyAudioAnalysis/audioTrainTest.py).
 
     load_model(model_name, is_regression=False)                  audioTrainTest.py:523-553
     classifier_wrapper(classifier, classifier_type, test_sample) audioTrainTest.py:52-94
@@ -6,6 +7,13 @@
     file_classification_batch(files, model_name, model_type)     many files: one mid-term plan, one classifier launch
     Knn(features, labels, neighbors), load_model_knn(name)       audioTrainTest.py:33-49, :492-520
     forest_model(classifier), forest_predict(...), ForestArrays   the tree ensembles of classifier_wrapper (:84-93)
+    regression_wrapper(model, model_type, test_sample)            audioTrainTest.py:96-111
+    train_svm_regression, train_random_forest_regression          audioTrainTest.py:222-233
+    feature_extraction_train_regression(...)                      audioTrainTest.py:370-489
+    evaluate_regression(features, labels, n_exp, method, params)  audioTrainTest.py:774-855
+    file_regression(input_file, model_name, model_type)           audioTrainTest.py:1099-1151
+    file_regression_batch(files, model_name, model_type)          many files: one mid-term plan, one regression launch
+    regress(models, model_type, feats, means, stds), SvrBank, SvrArrays   every model on every vector in one launch
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -20,6 +28,13 @@ GradientBoostingClassifier, as the reference's trainers make them) predict() and
 bit-identical to scikit-learn; only the trees' tree_ arrays, classes_ and (boosted) learning_rate / init_ are read, so a
 model given as arrays (ForestArrays) works without scikit-learn.  Unpickling an SVM or tree-ensemble model needs
 scikit-learn exactly where the reference needs it (load_model).  Training stays with scikit-learn.
+Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
+SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
+value of evaluate_regression -- scores every vector in one launch (kernels_svr.hpp through paa_svr_*: libsvm's decision value
+in the model's support-vector order, each model after its own standardisation); a forest regressor is the averaged forest
+with one output (paa_forest_create kind 2), bit-identical to RandomForestRegressor.predict.  Only the fitted arrays are read
+(SVR: support_vectors_, _dual_coef_, _intercept_, _gamma, kernel), so SvrArrays / ForestArrays(kind="regressor") work
+without scikit-learn; the fits of the trainers and of evaluate_regression are scikit-learn's and dominate their run time.
 """
 import ctypes as C
 import os
@@ -34,6 +49,8 @@ from . import _ffi, audioBasicIO
 _SVM_TYPES = ("svm", "svm_rbf")
 _FOREST_TYPES = ("randomforest", "extratrees", "gradientboosting")
 _KERNEL_TYPES = {"linear": 0, "rbf": 2}          # libsvm's LINEAR / RBF
+_FOREST_KINDS = {"averaged": 0, "boosted": 1, "regressor": 2}      # PAA_FOREST_AVERAGED / _BOOSTED / _REGRESSOR
+_REGRESSION_TYPES = ("svm", "svm_rbf", "randomforest")
 
 
 class SvcArrays:
@@ -301,14 +318,15 @@ class ForestArrays:
     """A fitted tree ensemble given as plain arrays (e.g. from an .npz), so that no scikit-learn is needed: kind "averaged"
     (RandomForestClassifier / ExtraTreesClassifier: value [nodes][n_classes], the class fractions of tree_.value) or
     "boosted" (GradientBoostingClassifier: value [nodes], trees stage-major, n_outputs = 1 for two classes, else
-    n_classes; init [n_outputs] the constant initial raw score).  Trees are concatenated: tree t owns nodes
+    n_classes; init [n_outputs] the constant initial raw score) or "regressor" (RandomForestRegressor: value [nodes], one
+    output, classes ignored).  Trees are concatenated: tree t owns nodes
     node_offsets[t] .. node_offsets[t + 1] - 1, and its children_left / children_right / feature index are local to it, in
     scikit-learn's tree_ arrays' terms (-1 children: a leaf)."""
 
     def __init__(self, kind, node_offsets, children_left, children_right, feature, threshold, missing_go_to_left, value,
                  classes, n_dims, learning_rate=0.0, init=None):
-        if kind not in ("averaged", "boosted"):
-            raise ValueError("tree ensemble kind %r: 'averaged' or 'boosted'" % (kind,))
+        if kind not in _FOREST_KINDS:
+            raise ValueError("tree ensemble kind %r: 'averaged', 'boosted' or 'regressor'" % (kind,))
         self.kind = kind
         self.node_offsets = np.ascontiguousarray(node_offsets, dtype=np.int64)
         self.children_left = np.ascontiguousarray(children_left, dtype=np.int64)
@@ -319,7 +337,7 @@ class ForestArrays:
         self.missing_go_to_left = np.ascontiguousarray(np.zeros(n) if missing_go_to_left is None else missing_go_to_left,
                                                        dtype=np.uint8)
         self.value = np.ascontiguousarray(value, dtype=np.float64)
-        self.classes_ = np.asarray(classes)
+        self.classes_ = np.zeros(1) if kind == "regressor" else np.asarray(classes)      # a regressor: one output
         self.n_dims = int(n_dims)
         self.learning_rate = float(learning_rate)
         self.init = None if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(-1)
@@ -346,10 +364,16 @@ def _tree_arrays(trees, width):
 
 def forest_arrays(classifier):
     """ForestArrays of a fitted RandomForestClassifier, ExtraTreesClassifier or GradientBoostingClassifier (only its
-    estimators_' tree_ arrays, classes_, n_features_in_ and, boosted, learning_rate and init_ are read)."""
+    estimators_' tree_ arrays, classes_, n_features_in_ and, boosted, learning_rate and init_ are read), or of a fitted
+    RandomForestRegressor (estimators_ and no classes_; one output)."""
     if isinstance(classifier, ForestArrays):
         return classifier
     est = classifier.estimators_
+    if not hasattr(classifier, "classes_"):
+        if getattr(classifier, "n_outputs_", 1) != 1:
+            raise NotImplementedError("multi-output forests are not served by the GPU path")
+        arrays = _tree_arrays(list(est), 1)
+        return ForestArrays("regressor", *arrays[:6], arrays[6][:, 0], None, int(classifier.n_features_in_))
     classes = np.asarray(classifier.classes_)
     n_dims = int(classifier.n_features_in_)
     if isinstance(est, np.ndarray) and est.ndim == 2:                 # GradientBoostingClassifier: [n_stages][n_outputs]
@@ -381,9 +405,10 @@ class ForestModel(_DeviceModel):
         self.n_outputs = a.n_outputs
         self.n_dims = a.n_dims
         self.boosted = a.kind == "boosted"
+        self.regressor = a.kind == "regressor"
         n_trees = a.node_offsets.shape[0] - 1
         n_nodes = a.threshold.shape[0]
-        width = 1 if self.boosted else self.n_classes
+        width = 1 if self.boosted or self.regressor else self.n_classes
         for name in ("children_left", "children_right", "feature", "missing_go_to_left"):
             if getattr(a, name).shape != (n_nodes,):
                 raise ValueError("tree ensemble: %s has shape %s for %d nodes" % (name, getattr(a, name).shape, n_nodes))
@@ -397,7 +422,7 @@ class ForestModel(_DeviceModel):
                 None if init is None else init.shape[0], self.n_outputs))
         ptr = lambda x: x.ctypes.data_as(C.c_void_p)                       # noqa: E731
         handle = C.c_void_p()
-        _ffi.check(_ffi.lib().paa_forest_create(1 if self.boosted else 0, n_trees, ptr(a.node_offsets), ptr(a.children_left),
+        _ffi.check(_ffi.lib().paa_forest_create(_FOREST_KINDS[a.kind], n_trees, ptr(a.node_offsets), ptr(a.children_left),
                                                 ptr(a.children_right), ptr(a.feature), _ffi.as_f64p(a.threshold),
                                                 ptr(a.missing_go_to_left), _ffi.as_f64p(a.value), self.n_classes, self.n_dims,
                                                 a.learning_rate, _ffi.as_f64p(np.ascontiguousarray(init)), C.byref(handle)))
@@ -418,9 +443,13 @@ class ForestModel(_DeviceModel):
 
 
 def is_forest(classifier):
-    """A tree ensemble: ForestArrays / ForestModel, or a fitted scikit-learn ensemble (estimators_ and classes_)."""
-    return isinstance(classifier, (ForestArrays, ForestModel)) or (hasattr(classifier, "estimators_") and
-                                                                   hasattr(classifier, "classes_"))
+    """A tree-ensemble CLASSIFIER: ForestArrays / ForestModel, or a fitted scikit-learn ensemble (estimators_ and
+    classes_); a regressor (no classes_, kind "regressor") is not one."""
+    if isinstance(classifier, ForestArrays):
+        return classifier.kind != "regressor"
+    if isinstance(classifier, ForestModel):
+        return not classifier.regressor
+    return hasattr(classifier, "estimators_") and hasattr(classifier, "classes_")
 
 
 def forest_model(classifier):
@@ -575,4 +604,407 @@ def file_classification_batch(files, model_name, model_type):
                                                  short_window, short_step, compute_beat, model_type)
         for j, (i, _) in enumerate(members):
             out[i] = (ids[j], proba[j], classes)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# regression (reference :96-111, :222-233, :370-489, :774-855, :1099-1151)
+# ---------------------------------------------------------------------------------------------------------
+class SvrArrays:
+    """A fitted epsilon-SVR given by its arrays in scikit-learn's attribute names (e.g. from an .npz): support_vectors
+    [n_sv][n_dims] (n_sv = 0 is legal: the model predicts its intercept), dual_coef the PRIVATE _dual_coef_ [1][n_sv],
+    intercept the PRIVATE _intercept_ (libsvm's -rho), gamma the fitted _gamma, kernel 'linear' or 'rbf'."""
+
+    def __init__(self, support_vectors, dual_coef, intercept, gamma, kernel):
+        self.kernel = _svr_kernel(kernel)
+        self.support_vectors_ = np.asarray(support_vectors, dtype=np.float64)
+        self._dual_coef_ = np.asarray(dual_coef, dtype=np.float64).reshape(1, -1)
+        self._intercept_ = np.asarray(intercept, dtype=np.float64).reshape(-1)
+        self._gamma = float(gamma)
+
+
+def _svr_kernel(kernel):
+    kernel = str(kernel)
+    if kernel not in _KERNEL_TYPES:
+        raise NotImplementedError("SVR kernel %r: the GPU path serves 'rbf' and 'linear' models" % (kernel,))
+    return kernel
+
+
+def _stats_rows(stats, n_models, n_dims, what):
+    """[n_models][n_dims] from one vector (shared by every model) or one row per model."""
+    a = np.asarray(stats, dtype=np.float64)
+    if a.ndim == 1 or (a.ndim == 2 and a.shape[0] == 1 and n_models != 1):
+        a = np.broadcast_to(a.reshape(1, -1), (n_models, a.size))
+    if a.shape != (n_models, n_dims):
+        raise ValueError("%s of shape %s for %d models of %d dims" % (what, a.shape, n_models, n_dims))
+    return np.ascontiguousarray(a)
+
+
+class SvrBank:
+    """A bank of fitted SVR models (sklearn.svm.SVR or SvrArrays) that share n_dims, on the device (paa_svr_create), each
+    with its own standardisation: means / stds are one row per model, or one vector shared by all of them."""
+
+    def __init__(self, models, means, stds):
+        models = list(models)
+        if not models:
+            raise ValueError("an SVR bank needs at least one model")
+        svs, coefs, rho, kernels, gammas = [], [], [], [], []
+        for m in models:
+            kernel = _svr_kernel(getattr(m, "kernel", ""))
+            sv = np.asarray(m.support_vectors_, dtype=np.float64)
+            coef = np.asarray(m._dual_coef_, dtype=np.float64).reshape(-1)
+            icpt = np.asarray(m._intercept_, dtype=np.float64).reshape(-1)
+            if sv.ndim != 2 or coef.shape[0] != sv.shape[0] or icpt.shape[0] != 1:
+                raise ValueError("not a fitted SVR: inconsistent arrays")
+            svs.append(sv)
+            coefs.append(coef)
+            rho.append(-icpt[0])
+            kernels.append(_KERNEL_TYPES[kernel])
+            gammas.append(float(m._gamma) if kernel == "rbf" else 0.0)
+        self.n_models = len(models)
+        self.n_dims = int(svs[0].shape[1])
+        if any(sv.shape[1] != self.n_dims for sv in svs):
+            raise ValueError("the models of an SVR bank must share the number of dims")
+        self.means = _stats_rows(means, self.n_models, self.n_dims, "means")
+        self.stds = _stats_rows(stds, self.n_models, self.n_dims, "stds")
+        offsets = np.concatenate([[0], np.cumsum([sv.shape[0] for sv in svs])]).astype(np.int64)
+        sv = np.ascontiguousarray(np.concatenate(svs, axis=0))
+        coef = np.ascontiguousarray(np.concatenate(coefs))
+        handle = C.c_void_p()
+        _ffi.check(_ffi.lib().paa_svr_create(
+            self.n_models, _ffi.as_i64p(offsets), _ffi.as_f64p(sv) if sv.size else None, _ffi.as_f64p(coef) if coef.size else None,
+            _ffi.as_f64p(np.array(rho, dtype=np.float64)), np.array(kernels, dtype=np.int32).ctypes.data_as(_ffi.c_i32p),
+            _ffi.as_f64p(np.array(gammas, dtype=np.float64)), _ffi.as_f64p(self.means), _ffi.as_f64p(self.stds), self.n_dims,
+            C.byref(handle)))
+        self.handle = handle
+        self._finalizer = weakref.finalize(self, _ffi.lib().paa_svr_destroy, handle)
+
+    def predict(self, feats):
+        """feats [n_dims][n_vec] (feature-major) -> [n_models][n_vec]: model m's prediction of (feats[:, v] - means[m]) / stds[m]."""
+        F = np.ascontiguousarray(feats, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.n_dims or F.shape[1] < 1:
+            raise ValueError("feature matrix of shape %s for a model of %d dims" % (F.shape, self.n_dims))
+        n = F.shape[1]
+        out = np.empty((self.n_models, n), dtype=np.float64)
+        _ffi.check(_ffi.lib().paa_svr_predict_f64(self.handle, _ffi.as_f64p(F), self.n_dims, n, n, _ffi.as_f64p(out)))
+        return out
+
+    def predict_device(self, d_feats, ld, n_vec, d_out=None, ld_out=None):
+        """The same on a device-resident matrix (a DeviceBuffer holding [n_dims][ld] doubles).  With d_out (a DeviceBuffer
+        of [n_models][ld_out] doubles) the predictions stay on the device and None is returned."""
+        if d_out is not None:
+            _ffi.check(_ffi.lib().paa_svr_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, d_out.ptr,
+                                                          n_vec if ld_out is None else ld_out))
+            return None
+        buf = _ffi.DeviceBuffer(8 * n_vec * self.n_models)
+        try:
+            _ffi.check(_ffi.lib().paa_svr_dev_predict_f64(self.handle, d_feats.ptr, self.n_dims, ld, n_vec, buf.ptr, n_vec))
+            return buf.to_host(np.float64, n_vec * self.n_models).reshape(self.n_models, n_vec)
+        finally:
+            buf.free()
+
+
+def svr_bank(models, means, stds):
+    """The device bank of (models, means, stds).  A bank of ONE model is kept while the model lives, like the classifiers'
+    device models (and uploaded again when it is asked for with another mean / std)."""
+    if isinstance(models, SvrBank):
+        return models
+    models = list(models)
+    if len(models) != 1:
+        return SvrBank(models, means, stds)
+    cache = _uploaded.setdefault(SvrBank, weakref.WeakKeyDictionary())
+    try:
+        b = cache.get(models[0])
+    except TypeError:
+        b = None
+    if b is not None:
+        same = b.means.shape[1] == np.size(means) == np.size(stds) and \
+            np.array_equal(b.means[0], np.asarray(means, dtype=np.float64).reshape(-1)) and \
+            np.array_equal(b.stds[0], np.asarray(stds, dtype=np.float64).reshape(-1))
+        if same:
+            return b
+    b = SvrBank(models, means, stds)
+    try:
+        cache[models[0]] = b
+    except TypeError:
+        pass
+    return b
+
+
+def regress(models, model_type, feats, means, stds):
+    """regression_wrapper for every model of `models` on every column of feats [n_dims][n_vec], model m after
+    (x - means[m]) / stds[m] (one mean / std vector: shared by all): [n_models][n_vec].  "svm" / "svm_rbf": ONE launch
+    for the whole bank; "randomforest": one traversal / reduction pair per forest."""
+    if model_type in _SVM_TYPES:
+        return svr_bank(models, means, stds).predict(feats)
+    if model_type != "randomforest":
+        raise NotImplementedError("regression model type %r: the GPU path serves 'svm', 'svm_rbf' and 'randomforest'" % (model_type,))
+    models = list(models)
+    F = np.ascontiguousarray(feats, dtype=np.float64)
+    means = _stats_rows(means, len(models), F.shape[0], "means")
+    stds = _stats_rows(stds, len(models), F.shape[0], "stds")
+    out = np.empty((len(models), F.shape[1]), dtype=np.float64)
+    for i, m in enumerate(models):
+        out[i] = _forest_regressor(m).predict(F, means[i], stds[i])[1][:, 0]
+    return out
+
+
+def _forest_regressor(model):
+    fm = forest_model(model)
+    if not fm.regressor:
+        raise ValueError("a tree-ensemble classifier cannot regress")
+    return fm
+
+
+def regression_wrapper(model, model_type, test_sample):
+    """The regression result of one feature vector (reference :96-111): "svm" / "svm_rbf" / "randomforest" give the
+    model's predict() as a scalar, computed on the GPU; any other type gives None, as the reference falls through."""
+    if model_type not in _REGRESSION_TYPES:
+        return None
+    x = np.asarray(test_sample, dtype=np.float64).reshape(-1, 1)
+    return regress([model], model_type, x, np.zeros(x.shape[0]), np.ones(x.shape[0]))[0, 0]       # (x - 0) / 1 == x
+
+
+def train_svm_regression(features, labels, c_param, kernel='linear'):
+    """(fitted sklearn.svm.SVR, mean absolute training error) (reference :222-226): scikit-learn fits, the training
+    error comes from the device prediction."""
+    import sklearn.svm
+    svm = sklearn.svm.SVR(C=c_param, kernel=kernel)
+    svm.fit(features, labels)
+    X = np.asarray(features, dtype=np.float64)
+    pred = regress([svm], "svm", X.T, np.zeros(X.shape[1]), np.ones(X.shape[1]))[0]
+    return svm, np.mean(np.abs(pred - labels))
+
+
+def train_random_forest_regression(features, labels, n_estimators):
+    """(fitted RandomForestRegressor, mean absolute training error) (reference :229-233), as train_svm_regression."""
+    import sklearn.ensemble
+    rf = sklearn.ensemble.RandomForestRegressor(n_estimators=n_estimators)
+    rf.fit(features, labels)
+    X = np.asarray(features, dtype=np.float64)
+    pred = regress([rf], "randomforest", X.T, np.zeros(X.shape[1]), np.ones(X.shape[1]))[0]
+    return rf, np.mean(np.abs(pred - labels))
+
+
+def _fit_regressor(features, labels, method_name, param):
+    import sklearn.ensemble
+    import sklearn.svm
+    if method_name == "randomforest":
+        model = sklearn.ensemble.RandomForestRegressor(n_estimators=param)
+    else:
+        model = sklearn.svm.SVR(C=param, kernel="rbf" if method_name == "svm_rbf" else "linear")
+    model.fit(features, labels)
+    return model
+
+
+def evaluate_regression(features, labels, n_exp, method_name, params):
+    """Picks the parameter value with the lowest cross-validated squared error (reference :774-855): for every value,
+    n_exp random 90 / 10 splits of the standardised samples.  np.random.permutation is consumed and the models are
+    fitted in the reference's order (RandomForestRegressor draws from the same global state), by scikit-learn; the
+    predictions are deferred: per parameter value the n_exp models x ALL samples go out in one bank launch ("randomforest":
+    one traversal per forest), and the test and training errors are picked out on the host with the stored permutations.
+    Prints the reference's table; returns (best parameter, its error, its baseline error).  The fits dominate the run
+    time: the launch removes the per-vector predict loop and nothing else."""
+    if method_name not in _REGRESSION_TYPES:
+        raise NotImplementedError("regression method %r: 'svm', 'svm_rbf' or 'randomforest'" % (method_name,))
+    from sklearn.preprocessing import StandardScaler
+    features_norm = StandardScaler().fit_transform(features)
+    labels = np.asarray(labels)
+    n_samples = labels.shape[0]
+    n_train = int(round(0.9 * n_samples))
+    zeros, ones = np.zeros(features_norm.shape[1]), np.ones(features_norm.shape[1])
+    all_samples = np.ascontiguousarray(features_norm.T)
+    errors_all, er_train_all, er_base_all = [], [], []
+    for param in params:
+        perms, models = [], []
+        for _ in range(n_exp):
+            perm = np.random.permutation(range(n_samples))
+            models.append(_fit_regressor(features_norm[perm[:n_train]], [labels[i] for i in perm[:n_train]], method_name, param))
+            perms.append(perm)
+        pred = regress(models, method_name, all_samples, zeros, ones)           # [n_exp][n_samples]
+        errors, errors_train, errors_base = [], [], []
+        for e, perm in enumerate(perms):
+            train, test = perm[:n_train], perm[n_train:]
+            baseline = np.mean([labels[i] for i in train])
+            errors.append(np.array([(pred[e, i] - labels[i]) * (pred[e, i] - labels[i]) for i in test]).mean())
+            errors_base.append(np.array([(baseline - labels[i]) * (baseline - labels[i]) for i in test]).mean())
+            errors_train.append(np.mean(np.abs(pred[e, train] - labels[train])))
+        errors_all.append(np.array(errors).mean())
+        er_train_all.append(np.array(errors_train).mean())
+        er_base_all.append(np.array(errors_base).mean())
+    best = int(np.argmin(errors_all))
+    print("{0:s}\t\t{1:s}\t\t{2:s}\t\t{3:s}".format("Param", "MSE", "T-MSE", "R-MSE"))
+    for i in range(len(errors_all)):
+        print("{0:.4f}\t\t{1:.2f}\t\t{2:.2f}\t\t{3:.2f}".format(params[i], errors_all[i], er_train_all[i], er_base_all[i]), end="")
+        print("\t\t best" if i == best else "")
+    return params[best], errors_all[best], er_base_all[best]
+
+
+def save_parameters(path, *parameters):
+    """The MEANS file of a model: the parameters pickled one after the other (reference :364-367)."""
+    with open(path, "wb") as fo:
+        for p in parameters:
+            cPickle.dump(p, fo, protocol=cPickle.HIGHEST_PROTOCOL)
+
+
+def feature_extraction_train_regression(folder_name, mid_window, mid_step, short_window, short_step, model_type, model_name,
+                                        compute_beat=False):
+    """Trains one regression model per CSV file of a folder of audio files (reference :370-489): every `<task>.csv` pairs
+    file names with target values; features come from multiple_directory_feature_extraction (GPU), the parameter from
+    evaluate_regression, the final fit from scikit-learn; `model_name_<task>` and `model_name_<task>MEANS` are written as
+    the reference writes them.  Returns (errors, baseline errors, best parameters)."""
+    import csv
+    import glob
+    import ntpath
+    from sklearn.preprocessing import StandardScaler
+    features, _, filenames = aF.multiple_directory_feature_extraction([folder_name], mid_window, mid_step, short_window,
+                                                                      short_step, compute_beat=compute_beat)
+    features = features[0]
+    filenames = [ntpath.basename(f) for f in filenames[0]]
+    task_features, task_labels, task_names = [], [], []
+    for path in glob.glob(folder_name + os.sep + "*.csv"):
+        rows, values = [], []
+        with open(path, "rt") as fo:
+            for row in csv.reader(fo, delimiter=",", quotechar="|"):
+                if len(row) != 2:
+                    print("Warning: Row with unknown format in regression file")
+                elif row[0] in filenames:
+                    values.append(float(row[1]))
+                    rows.append(features[filenames.index(row[0]), :])
+                else:
+                    print("Warning: {} not found in list of files.".format(row[0]))
+        task_features.append(np.array(rows))
+        task_labels.append(np.array(values))
+        task_names.append(ntpath.basename(path).replace(".csv", ""))
+        if len(features) == 0:
+            print("ERROR: No data found in any input folder!")
+            return
+    if model_type in _SVM_TYPES:
+        model_params = np.array([0.001, 0.005, 0.01, 0.05, 0.1, 0.25, 0.5, 1.0, 5.0, 10.0])
+    elif model_type == "randomforest":
+        model_params = np.array([5, 10, 25, 50, 100])
+    errors, errors_base, best_params = [], [], []
+    for X, y, name in zip(task_features, task_labels, task_names):
+        print("Regression task " + name)
+        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params)
+        errors.append(error)
+        errors_base.append(base_error)
+        best_params.append(best)
+        print("Selected params: {0:.5f}".format(best))
+        scaler = StandardScaler()
+        X_norm = scaler.fit_transform(X)
+        if model_type in _REGRESSION_TYPES:
+            model = _fit_regressor(X_norm, y, model_type, best)
+            with open(model_name + "_" + name, "wb") as fo:
+                cPickle.dump(model, fo)
+            save_parameters(model_name + "_" + name + "MEANS", scaler.mean_.tolist(), scaler.scale_.tolist(), mid_window,
+                            mid_step, short_window, short_step, compute_beat)
+    return errors, errors_base, best_params
+
+
+def file_regression_signals(signals, sampling_rate, models, means, stds, mid_window, mid_step, short_window, short_step,
+                            compute_beat, model_type="svm_rbf"):
+    """file_regression for many mono signals of one sampling rate and loaded models: the clips go through ONE batched
+    mid-term (+ beat) plan, the long-term vectors through ONE regression launch (regress).  There is no short-file clamp
+    of mid_window here (reference :1127-1131, unlike file_classification).  Returns [n_signals][n_models]."""
+    models = list(models)
+    if len(signals) == 0:
+        return np.zeros((0, len(models)))
+    fs = sampling_rate
+    vectors = [None] * len(signals)
+    by_kind = {}
+    for i, s in enumerate(signals):
+        by_kind.setdefault(np.asarray(s).dtype == np.int16, []).append(i)
+    for _, members in by_kind.items():
+        mids, beats = aF.mid_and_beat_batch([signals[i] for i in members], fs, mid_window * fs, mid_step * fs,
+                                            round(fs * short_window), round(fs * short_step),
+                                            beat_window_seconds=short_step if compute_beat else None)
+        for j, i in enumerate(members):
+            v = mids[j].mean(axis=1)
+            if compute_beat:
+                v = np.append(v, beats[j, 0])
+                v = np.append(v, beats[j, 1])
+            vectors[i] = v
+    return np.ascontiguousarray(regress(models, model_type, np.stack(vectors, axis=1), means, stds).T)
+
+
+def file_regression_signal(signal, sampling_rate, models, means, stds, mid_window, mid_step, short_window, short_step,
+                           compute_beat, model_type="svm_rbf"):
+    """file_regression on a mono signal and loaded models: the regression results [n_models] (a batch of one clip)."""
+    return file_regression_signals([signal], sampling_rate, models, means, stds, mid_window, mid_step, short_window,
+                                   short_step, compute_beat, model_type)[0]
+
+
+def _regression_models(model_name):
+    """file_regression's model files (reference :1106-1114): every model_name_* that is no MEANS file, and the task names
+    (the text after the last underscore)."""
+    import glob
+    paths = [r for r in glob.glob(model_name + "_*") if r[-5::] != "MEANS"]
+    return paths, [r[r.rfind("_") + 1::] for r in paths]
+
+
+def _load_regression_models(paths):
+    """(models, means, stds, window parameters of the FIRST model) or None when a model file is missing."""
+    models, means, stds = [], [], []
+    params = load_model(paths[0], True)[3:]
+    for r in paths:
+        if not os.path.isfile(r):
+            print("fileClassification: input model_name not found!")
+            return None
+        model, mean, std = load_model(r, True)[:3]
+        models.append(model)
+        means.append(mean)
+        stds.append(std)
+    return models, np.array(means), np.array(stds), params
+
+
+def file_regression(input_file, model_name, model_type):
+    """(regression results, task names) of one audio file for every model model_name_<task> (reference :1099-1151); the
+    reference's error return (-1, -1, -1) for a missing file or model."""
+    if not os.path.isfile(input_file):
+        print("fileClassification: wav file not found!")
+        return -1, -1, -1
+    paths, names = _regression_models(model_name)
+    if model_type not in _REGRESSION_TYPES:
+        raise NotImplementedError("regression model type %r: the GPU path serves 'svm', 'svm_rbf' and 'randomforest'" % (model_type,))
+    loaded = _load_regression_models(paths)
+    if loaded is None:
+        return -1, -1, -1
+    models, means, stds, (mid_window, mid_step, short_window, short_step, compute_beat) = loaded
+    sampling_rate, signal = audioBasicIO.read_audio_file(input_file)
+    signal = audioBasicIO.stereo_to_mono(signal)
+    R = file_regression_signal(signal, sampling_rate, models, means, stds, mid_window, mid_step, short_window, short_step,
+                               compute_beat, model_type)
+    return list(R), names
+
+
+def file_regression_batch(files, model_name, model_type):
+    """file_regression over many files with one set of models: a list of (results, task names) per file, equal to one-file
+    calls.  Files are grouped by sampling rate; each group is one batched mid-term plan and one regression launch.
+    Missing / unreadable files give the reference's (-1, -1, -1)."""
+    out = [(-1, -1, -1)] * len(files)
+    present = [i for i, f in enumerate(files) if os.path.isfile(f)]
+    for i in range(len(files)):
+        if i not in present:
+            print("fileClassification: wav file not found!")
+    if not present:
+        return out
+    if model_type not in _REGRESSION_TYPES:
+        raise NotImplementedError("regression model type %r: the GPU path serves 'svm', 'svm_rbf' and 'randomforest'" % (model_type,))
+    paths, names = _regression_models(model_name)
+    loaded = _load_regression_models(paths)
+    if loaded is None:
+        return out
+    models, means, stds, (mid_window, mid_step, short_window, short_step, compute_beat) = loaded
+    groups = {}
+    for i in present:
+        fs, sig = audioBasicIO.read_audio_file(files[i])
+        if fs == 0:
+            continue
+        groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
+    for fs, members in groups.items():
+        R = file_regression_signals([s for _, s in members], fs, models, means, stds, mid_window, mid_step, short_window,
+                                    short_step, compute_beat, model_type)
+        for j, (i, _) in enumerate(members):
+            out[i] = (list(R[j]), names)
     return out

@@ -12,7 +12,7 @@ namespace launch {
 int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean,
            const double *d_scale, int *d_leaves, int *d_label, double *d_raw, double *d_proba, hipStream_t stream) {
     using namespace paa::forest;
-    if (m.n_trees < 1 || m.n_classes < 2 || m.n_classes > kMaxClasses || m.n_dims < 1 || m.n_dims > kMaxDims ||
+    if (m.n_trees < 1 || m.n_classes < 1 || m.n_classes > kMaxClasses || m.n_dims < 1 || m.n_dims > kMaxDims ||
         m.n_outputs < 1 || (m.boosted && m.n_trees % m.n_outputs) || n_vec < 1)
         return -1;
     const size_t lds = (size_t)m.n_dims * kWin * sizeof(float);

@@ -91,6 +91,30 @@ struct SvcDev {
     double gamma;
 };
 }  // namespace svc
+namespace svr {
+constexpr int kMaxModels = 4096;
+constexpr int kMaxDims = 256;
+// kernels_svr.hpp: a group of kGroupLanes lanes owns kWinPerGroup windows; a workgroup stages tiles of kTile support vectors
+// and walks kModelChunk models, one after the other
+constexpr int kGroupLanes = 8;
+constexpr int kWinPerGroup = 2;
+constexpr int kThreads = 128;
+constexpr int kWinPerBlock = kThreads / kGroupLanes * kWinPerGroup;   // 32
+constexpr int kTile = 16;
+constexpr int kModelChunk = 4;
+// one uploaded bank of epsilon-SVR models that share n_dims (libsvm's svm_model as scikit-learn holds it): device pointers
+struct SvrDev {
+    const double *sv;         // [total_sv][n_dims] support vectors, model after model
+    const double *coef;       // [total_sv] sv_coef (scikit-learn's _dual_coef_[0])
+    const long long *sv_off;  // [n_models + 1] model m owns support vectors sv_off[m] .. sv_off[m + 1] - 1 (none: legal)
+    const double *rho;        // [n_models] (= -_intercept_)
+    const double *gamma;      // [n_models]
+    const int *rbf;           // [n_models] 1: RBF, 0: linear
+    const int *same_prev;     // [n_models] 1: mean / std of model m equal those of model m - 1 bit for bit
+    const double *mean, *scale;   // [n_models][n_dims] every model's own standardisation
+    int n_models, n_dims;
+};
+}  // namespace svr
 namespace knn {
 constexpr int kMaxK = 32;
 constexpr int kMaxClasses = 64;
@@ -184,6 +208,10 @@ int wgs_feat(int r0, int q, const wg::FrameRef *frames, int n_frames, const WgSc
 // `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
         double *d_sums, int *d_label, double *d_proba, hipStream_t stream);
+// kernels_svr.hpp: a bank of epsilon-SVR models over the columns of feats [n_dims][ld] (one kernel): out [n_models][ld_out], every
+// model's prediction of every column after that model's own (x - mean) / std
+int svr(const svr::SvrDev &m, const double *d_feats, long long ld, long long n_vec, double *d_out, long long ld_out,
+        hipStream_t stream);
 // kernels_knn.hpp: k-nearest-neighbour classification of the columns of feats [n_dims][ld] (one kernel: labels [n_vec],
 // P [n_vec][n_classes] and, when d_neighbors is not null, the k neighbour indices [n_vec][k] in ascending (d^2, index))
 int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,

@@ -1,6 +1,7 @@
 // The tree ensembles of audioTrainTest.classifier_wrapper (audioTrainTest.py:84-93) -- scikit-learn's RandomForestClassifier,
-// ExtraTreesClassifier (averaged forests) and GradientBoostingClassifier (boosted sums) -- behind a handle, host-buffer and
-// device-buffer predict calls.  Kernels: kernels_forest.hpp (family_forest.hip).
+// ExtraTreesClassifier (averaged forests) and GradientBoostingClassifier (boosted sums) -- and the RandomForestRegressor of
+// regression_wrapper (:96-111; an averaged forest with one output, its prediction in the width-1 proba) -- behind a handle,
+// host-buffer and device-buffer predict calls.  Kernels: kernels_forest.hpp (family_forest.hip).
 // paa_forest_create takes scikit-learn's raw per-tree arrays, validates every index before anything reaches the device, and
 // re-lays each tree in preorder (left child = next node, 16-byte nodes, leaf values in their own array).
 #pragma once
@@ -20,9 +21,12 @@ extern "C" int paa_forest_create(int kind, int n_trees, const int64_t *node_offs
     *out_handle = nullptr;
     if (!node_offsets || !children_left || !children_right || !feature || !threshold || !value)
         return fail(PAA_ERR_ARG, "null argument");
-    if (kind != PAA_FOREST_AVERAGED && kind != PAA_FOREST_BOOSTED) return fail(PAA_ERR_ARG, "ensemble kind %d", kind);
-    if (n_classes < 2 || n_classes > forest::kMaxClasses)
-        return fail(PAA_ERR_ARG, "%d classes: 2..%d are supported", n_classes, forest::kMaxClasses);
+    if (kind != PAA_FOREST_AVERAGED && kind != PAA_FOREST_BOOSTED && kind != PAA_FOREST_REGRESSOR)
+        return fail(PAA_ERR_ARG, "ensemble kind %d", kind);
+    // a regressor is an averaged forest with ONE output (RandomForestRegressor, audioTrainTest.py:229-233): value [nodes]
+    if (kind == PAA_FOREST_REGRESSOR ? n_classes != 1 : (n_classes < 2 || n_classes > forest::kMaxClasses))
+        return kind == PAA_FOREST_REGRESSOR ? fail(PAA_ERR_ARG, "a regressor has one output, not %d", n_classes)
+                                            : fail(PAA_ERR_ARG, "%d classes: 2..%d are supported", n_classes, forest::kMaxClasses);
     if (n_dims < 1 || n_dims > forest::kMaxDims)
         return fail(PAA_ERR_ARG, "%d feature dimensions: 1..%d are supported", n_dims, forest::kMaxDims);
     if (n_trees < 1 || n_trees > kForestMaxTrees) return fail(PAA_ERR_ARG, "%d trees: 1..%d are supported", n_trees, kForestMaxTrees);
