@@ -141,9 +141,10 @@ class _DeviceModel:
 _uploaded = {}          # model class -> WeakKeyDictionary: classifier -> its device model
 
 
-def _device_model(cls, classifier):
+def _device_model(cls, classifier, make=None, still_valid=None):
     """The device copy of a classifier (uploaded at the first use, kept while the classifier lives; an object that cannot
-    be weakly referenced or hashed is uploaded at every call)."""
+    be weakly referenced or hashed is uploaded at every call).  make(classifier) builds it where cls(classifier) does
+    not; a kept copy for which still_valid(copy) is false is replaced."""
     if isinstance(classifier, cls):
         return classifier
     cache = _uploaded.setdefault(cls, weakref.WeakKeyDictionary())
@@ -151,8 +152,8 @@ def _device_model(cls, classifier):
         m = cache.get(classifier)
     except TypeError:
         m = None
-    if m is None:
-        m = cls(classifier)
+    if m is None or (still_valid is not None and not still_valid(m)):
+        m = (make or cls)(classifier)
         try:
             cache[classifier] = m
         except TypeError:
@@ -519,6 +520,31 @@ def _long_term_vector(signal, sampling_rate, mid_window, mid_step, short_window,
     return mid_features
 
 
+def _long_term_vectors(signals, fs, mid_window, mid_step, short_window, short_step, compute_beat, clamp_short):
+    """The long-term vectors [n_dims][n_signals] of many mono signals of one sampling rate: the clips go through ONE batched
+    mid-term (+ beat) plan per sample type.  clamp_short: clips shorter than mid_window take file_classification's clamp
+    (a window of their own length) through the single-clip path."""
+    vectors = [None] * len(signals)
+    by_kind = {}
+    for i, s in enumerate(signals):
+        if not clamp_short or s.shape[0] / float(fs) >= mid_window:
+            by_kind.setdefault(np.asarray(s).dtype == np.int16, []).append(i)
+    for _, members in by_kind.items():
+        mids, beats = aF.mid_and_beat_batch([signals[i] for i in members], fs, mid_window * fs, mid_step * fs,
+                                            round(fs * short_window), round(fs * short_step),
+                                            beat_window_seconds=short_step if compute_beat else None)
+        for j, i in enumerate(members):
+            v = mids[j].mean(axis=1)
+            if compute_beat:
+                v = np.append(v, beats[j, 0])
+                v = np.append(v, beats[j, 1])
+            vectors[i] = v
+    for i, v in enumerate(vectors):
+        if v is None:
+            vectors[i] = _long_term_vector(signals[i], fs, mid_window, mid_step, short_window, short_step, compute_beat)
+    return np.stack(vectors, axis=1)
+
+
 def file_classification_signal(signal, sampling_rate, classifier, mean, std, mid_window, mid_step, short_window,
                                short_step, compute_beat, model_type="svm_rbf"):
     """file_classification on a mono signal and a loaded model: (class id, probabilities)."""
@@ -555,27 +581,20 @@ def file_classification_signals(signals, sampling_rate, classifier, mean, std, m
     Returns (class ids [n], probabilities [n][k])."""
     if len(signals) == 0:
         return np.array([]), np.zeros((0, 0))
-    fs = sampling_rate
-    vectors = [None] * len(signals)
-    regular = [i for i, s in enumerate(signals) if s.shape[0] / float(fs) >= mid_window]
-    by_kind = {}
-    for i in regular:
-        by_kind.setdefault(np.asarray(signals[i]).dtype == np.int16, []).append(i)
-    for _, members in by_kind.items():
-        mids, beats = aF.mid_and_beat_batch([signals[i] for i in members], fs, mid_window * fs, mid_step * fs,
-                                            round(fs * short_window), round(fs * short_step),
-                                            beat_window_seconds=short_step if compute_beat else None)
-        for j, i in enumerate(members):
-            v = mids[j].mean(axis=1)
-            if compute_beat:
-                v = np.append(v, beats[j, 0])
-                v = np.append(v, beats[j, 1])
-            vectors[i] = v
-    for i, v in enumerate(vectors):
-        if v is None:
-            vectors[i] = _long_term_vector(signals[i], fs, mid_window, mid_step, short_window, short_step, compute_beat)
-    feats = np.stack(vectors, axis=1)
+    feats = _long_term_vectors(signals, sampling_rate, mid_window, mid_step, short_window, short_step, compute_beat, True)
     return predict(classifier, model_type, feats, mean, std)
+
+
+def _read_by_sampling_rate(files, indices):
+    """{sampling rate: [(index, mono signal), ...]} of files[i] for i in `indices`, taken one by one (a generator may
+    announce the files it leaves out between the reads); unreadable files are left out."""
+    groups = {}
+    for i in indices:
+        fs, sig = audioBasicIO.read_audio_file(files[i])
+        if fs == 0:
+            continue
+        groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
+    return groups
 
 
 def file_classification_batch(files, model_name, model_type):
@@ -590,16 +609,14 @@ def file_classification_batch(files, model_name, model_type):
     classifier, mean, std, classes, mid_window, mid_step, short_window, short_step, compute_beat = \
         _load(model_name, model_type)
     out = [(-1, -1, -1)] * len(files)
-    groups = {}
-    for i, f in enumerate(files):
-        if isinstance(f, str) and not os.path.isfile(f):
-            print("fileClassification: wav file not found!")
-            continue
-        fs, sig = audioBasicIO.read_audio_file(f)
-        if fs == 0:
-            continue
-        groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
-    for fs, members in groups.items():
+
+    def present():
+        for i, f in enumerate(files):
+            if isinstance(f, str) and not os.path.isfile(f):
+                print("fileClassification: wav file not found!")
+            else:
+                yield i
+    for fs, members in _read_by_sampling_rate(files, present()).items():
         ids, proba = file_classification_signals([s for _, s in members], fs, classifier, mean, std, mid_window, mid_step,
                                                  short_window, short_step, compute_beat, model_type)
         for j, (i, _) in enumerate(members):
@@ -712,23 +729,12 @@ def svr_bank(models, means, stds):
     models = list(models)
     if len(models) != 1:
         return SvrBank(models, means, stds)
-    cache = _uploaded.setdefault(SvrBank, weakref.WeakKeyDictionary())
-    try:
-        b = cache.get(models[0])
-    except TypeError:
-        b = None
-    if b is not None:
-        same = b.means.shape[1] == np.size(means) == np.size(stds) and \
+
+    def same_stats(b):
+        return b.means.shape[1] == np.size(means) == np.size(stds) and \
             np.array_equal(b.means[0], np.asarray(means, dtype=np.float64).reshape(-1)) and \
             np.array_equal(b.stds[0], np.asarray(stds, dtype=np.float64).reshape(-1))
-        if same:
-            return b
-    b = SvrBank(models, means, stds)
-    try:
-        cache[models[0]] = b
-    except TypeError:
-        pass
-    return b
+    return _device_model(SvrBank, models[0], lambda m: SvrBank([m], means, stds), same_stats)
 
 
 def regress(models, model_type, feats, means, stds):
@@ -910,22 +916,8 @@ def file_regression_signals(signals, sampling_rate, models, means, stds, mid_win
     models = list(models)
     if len(signals) == 0:
         return np.zeros((0, len(models)))
-    fs = sampling_rate
-    vectors = [None] * len(signals)
-    by_kind = {}
-    for i, s in enumerate(signals):
-        by_kind.setdefault(np.asarray(s).dtype == np.int16, []).append(i)
-    for _, members in by_kind.items():
-        mids, beats = aF.mid_and_beat_batch([signals[i] for i in members], fs, mid_window * fs, mid_step * fs,
-                                            round(fs * short_window), round(fs * short_step),
-                                            beat_window_seconds=short_step if compute_beat else None)
-        for j, i in enumerate(members):
-            v = mids[j].mean(axis=1)
-            if compute_beat:
-                v = np.append(v, beats[j, 0])
-                v = np.append(v, beats[j, 1])
-            vectors[i] = v
-    return np.ascontiguousarray(regress(models, model_type, np.stack(vectors, axis=1), means, stds).T)
+    feats = _long_term_vectors(signals, sampling_rate, mid_window, mid_step, short_window, short_step, compute_beat, False)
+    return np.ascontiguousarray(regress(models, model_type, feats, means, stds).T)
 
 
 def file_regression_signal(signal, sampling_rate, models, means, stds, mid_window, mid_step, short_window, short_step,
@@ -996,13 +988,7 @@ def file_regression_batch(files, model_name, model_type):
     if loaded is None:
         return out
     models, means, stds, (mid_window, mid_step, short_window, short_step, compute_beat) = loaded
-    groups = {}
-    for i in present:
-        fs, sig = audioBasicIO.read_audio_file(files[i])
-        if fs == 0:
-            continue
-        groups.setdefault(fs, []).append((i, audioBasicIO.stereo_to_mono(sig)))
-    for fs, members in groups.items():
+    for fs, members in _read_by_sampling_rate(files, present).items():
         R = file_regression_signals([s for _, s in members], fs, models, means, stds, mid_window, mid_step, short_window,
                                     short_step, compute_beat, model_type)
         for j, (i, _) in enumerate(members):

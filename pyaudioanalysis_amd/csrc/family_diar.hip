@@ -1,9 +1,9 @@
 // Speaker diarization (kernels_diar.hpp: standardisation, feature-row distances, k-means, cluster-pair distance sums) -- own
-// translation unit, see family_launch.hpp.
+// translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_diar.hpp"
 
 namespace paa {

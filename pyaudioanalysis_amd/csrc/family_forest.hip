@@ -1,9 +1,9 @@
 // Tree-ensemble classification (kernels_forest.hpp: audioTrainTest.classifier_wrapper for the "randomforest", "extratrees"
-// and "gradientboosting" models) -- own translation unit, see family_launch.hpp.
+// and "gradientboosting" models) -- own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_forest.hpp"
 
 namespace paa {

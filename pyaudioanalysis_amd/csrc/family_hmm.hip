@@ -1,9 +1,9 @@
 // Gaussian HMM segmentation (kernels_hmm.hpp: emission log-likelihoods, Viterbi by segments, training statistics) -- own
-// translation unit, see family_launch.hpp.
+// translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_hmm.hpp"
 
 namespace paa {

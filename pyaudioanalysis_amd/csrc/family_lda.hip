@@ -1,9 +1,9 @@
 // Linear discriminant analysis of speaker diarization (kernels_lda.hpp: class statistics, within-class Gram matrix,
-// projection) -- own translation unit, see family_launch.hpp.
+// projection) -- own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_lda.hpp"
 
 namespace paa {

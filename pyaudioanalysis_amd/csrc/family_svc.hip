@@ -1,9 +1,9 @@
 // The multi-class probabilistic SVC (kernels_svc.hpp: audioTrainTest.classifier_wrapper for the shipped SVM models) -- own
-// translation unit, see family_launch.hpp.
+// translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_svc.hpp"
 
 namespace paa {
@@ -18,14 +18,6 @@ static int svc_proba(const svc::SvcDev &m, long long n_vec, const double *d_sums
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <int K>
-static int svc_proba_k(int k, const svc::SvcDev &m, long long n_vec, const double *d_sums, int *d_label, double *d_proba,
-                       hipStream_t stream) {
-    if (k == K) return svc_proba<K>(m, n_vec, d_sums, d_label, d_proba, stream);
-    if constexpr (K < svc::kMaxClasses) return svc_proba_k<K + 1>(k, m, n_vec, d_sums, d_label, d_proba, stream);
-    return -1;
-}
-
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
         double *d_sums, int *d_label, double *d_proba, hipStream_t stream) {
     if (m.k < 2 || m.k > svc::kMaxClasses || m.n_dims < 1 || m.n_dims > svc::kMaxDims || n_vec < 1) return -1;
@@ -33,7 +25,7 @@ int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_v
     hipLaunchKernelGGL(svc::svc_class_sums_kernel, dim3((unsigned)blocks), dim3(svc::kThreads), 0, stream, m, d_feats, ld, n_vec,
                        d_mean, d_scale, d_sums);
     if (hipGetLastError() != hipSuccess) return -1;
-    return svc_proba_k<2>(m.k, m, n_vec, d_sums, d_label, d_proba, stream);
+    return dispatch_int<2, svc::kMaxClasses>(m.k, [&](auto K) { return svc_proba<K()>(m, n_vec, d_sums, d_label, d_proba, stream); });
 }
 
 }  // namespace launch

@@ -1,9 +1,9 @@
 // The bank of epsilon-SVR models (kernels_svr.hpp: audioTrainTest.regression_wrapper for the "svm" / "svm_rbf" models) --
-// own translation unit, see family_launch.hpp.
+// own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_svr.hpp"
 
 namespace paa {
@@ -19,6 +19,13 @@ int svr(const svr::SvrDev &m, const double *d_feats, long long ld, long long n_v
     hipLaunchKernelGGL(svr::svr_bank_kernel, dim3((unsigned)xblocks, (unsigned)yblocks), dim3(svr::kThreads), 0, stream, m, d_feats,
                        ld, n_vec, d_out, ld_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+void svr_geometry(int out4[4]) {
+    out4[0] = svr::kWinPerBlock;
+    out4[1] = svr::kModelChunk;
+    out4[2] = svr::kTile;
+    out4[3] = svr::kGroupLanes;
 }
 
 }  // namespace launch

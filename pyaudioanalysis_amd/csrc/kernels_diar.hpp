@@ -24,7 +24,7 @@
 //    store P[c][c2] + P[c2][c].  pair_reduce_kernel adds the tiles' partials in tile order (two stages).
 #pragma once
 #include "device_common.hpp"
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace diar {

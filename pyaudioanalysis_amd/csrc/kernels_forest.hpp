@@ -23,7 +23,7 @@
 // walk ends after at most the tree's node count; every index was validated before the upload.
 #pragma once
 #include "device_common.hpp"
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace forest {

@@ -26,7 +26,7 @@
 //    deviation of every feature row, two-pass about the mean as np.std does.
 #pragma once
 #include "device_common.hpp"
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace hmm {

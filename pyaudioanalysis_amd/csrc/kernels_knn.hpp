@@ -6,10 +6,8 @@
 // Here the ranking is by squared distance in the difference form sum_d (t_d - x_d)^2 (no sqrt, no |x|^2 + |t|^2 - 2 x.t
 // expansion, whose cancellation reorders close neighbours), ties broken by the training index: the order is ascending
 // (d^2, index).  The reference's argsort leaves the order of equal distances undefined.
-// One kernel per k (a template parameter, 1..kMaxK):
-//  * a group of kGroupLanes lanes owns ONE query; lane l holds dims l, l + 8, ... (standardised on load, zero beyond
-//    n_dims) in registers;
-//  * tiles of kTile training rows (zero-padded to 8 M dims) are staged in LDS, one read of a tile per workgroup;
+// One kernel per k (a template parameter, 1..kMaxK), on the lane split of kernels_kv.hpp with ONE query per group and the
+// training rows as rows:
 //  * per step of 8 rows each lane forms its partial squared distances to all 8, and a three-stage reduce-scatter (xor 4,
 //    2, 1: 7 shuffles) leaves lane l with the full d^2 of row base + l;
 //  * lane l keeps a sorted list of its K best (d^2, index) in registers for the rows = l mod 8; after warm-up a row costs
@@ -18,16 +16,18 @@
 //    classes l, l + 8, ...), P = count / K and the first maximum are written.
 // NaN distances (a NaN query, i.e. a zero std) are never inserted: such a query gets P = 0, label 0 and no neighbours (-1).
 #pragma once
-#include "device_common.hpp"
-#include "family_launch.hpp"
+#include "kernels_kv.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace knn {
 
-constexpr int kGroupLanes = 8;
-constexpr int kThreads = kQueriesPerBlock * kGroupLanes;            // 128
-constexpr int kTile = 16;                                           // training rows per LDS tile (a multiple of 8)
-constexpr int kMaxM = kMaxDims / kGroupLanes;                       // 32 dims per lane
+using kv::kGroupLanes;
+using kv::kMaxM;
+using kv::kThreads;
+using kv::kTile;
+static_assert(kMaxDims <= kv::kMaxDims && kQueriesPerBlock * kGroupLanes == kThreads && kTile % kGroupLanes == 0,
+              "one query per group; a tile is whole steps of 8 rows");
 constexpr int kClassSlots = kMaxClasses / kGroupLanes;              // 8 classes per lane
 
 // (d, i) before (e, j) in ascending (d^2, index) order; an index < 0 is an empty slot, after every real entry
@@ -60,10 +60,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(KnnDev m, const double *_
 
     for (int base = 0; base < m.n_train; base += kTile) {
         __syncthreads();
-        for (int i = tid; i < kTile * pitch; i += kThreads) {
-            const int s = base + i / pitch, d = i % pitch;
-            tile[i] = (s < m.n_train && d < m.n_dims) ? m.train[(long long)s * m.n_dims + d] : 0.0;
-        }
+        kv::stage_rows(tile, m.train, base, m.n_train, m.n_dims, pitch, tid);
         __syncthreads();
         const int cnt = min(kTile, m.n_train - base);
         for (int r = 0; r < cnt; r += kGroupLanes) {

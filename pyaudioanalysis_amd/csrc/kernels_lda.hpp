@@ -19,7 +19,7 @@
 //  * project_kernel: Y[j][t] = sum_d (X[d][t] - xbar[d]) S[d][j], d ascending; thread per window, kProjOut outputs each.
 #pragma once
 #include "device_common.hpp"
-#include "family_launch.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace lda {

@@ -14,31 +14,24 @@
 // partial sums A[c][r] = sum_{s in c} sv_coef[r][s] K_s; svc_proba_kernel (one thread per window) forms dec_ij = A[i][j-1] +
 // A[j][i] - rho, the votes and the probabilities.
 #pragma once
-#include "device_common.hpp"
-#include "family_launch.hpp"
+#include "kernels_kv.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace svc {
 
 // ---- kernel values and per-class sums ---------------------------------------------------------------------------------
-// A group of kGroupLanes lanes owns kWinPerGroup windows; lane l holds dims l, l + 8, l + 16, ... of both (standardised on
-// load, zero beyond n_dims) in registers.  Workgroups stage tiles of kTile support vectors (zero-padded to 8 M dims) and
-// their dual coefficients in LDS: one read of a tile per workgroup.  Per support vector a lane forms its partial squared
-// distance (or dot product), three xor shuffles give every lane of the group the full sum, and lane l accumulates rows l
-// and l + 8 of sv_coef for the current class; at the end of a class's range the rows are written to A.
-constexpr int kGroupLanes = 8;
+// The lane split of kernels_kv.hpp with kWinPerGroup windows per group and the support vectors as rows; the tile's dual
+// coefficients are staged beside it.  Lane l accumulates rows l and l + 8 of sv_coef for the current class; at the end of a
+// class's range the rows are written to A.
+using kv::group_sum;
+using kv::kGroupLanes;
+using kv::kMaxM;
+using kv::kThreads;
+using kv::kTile;
 constexpr int kWinPerGroup = 2;
-constexpr int kThreads = 128;
 constexpr int kWinPerBlock = kThreads / kGroupLanes * kWinPerGroup;   // 32
-constexpr int kTile = 16;
-constexpr int kMaxM = kMaxDims / kGroupLanes;                         // 32 dims per lane
-
-__device__ __forceinline__ double group_sum(double v) {
-    v += __shfl_xor(v, 1, kGroupLanes);
-    v += __shfl_xor(v, 2, kGroupLanes);
-    v += __shfl_xor(v, 4, kGroupLanes);
-    return v;
-}
+static_assert(kMaxDims <= kv::kMaxDims && kMaxClasses - 1 <= 2 * kGroupLanes, "the model limits fit the lane split");
 
 __global__ __launch_bounds__(kThreads) void svc_class_sums_kernel(SvcDev m, const double *__restrict__ feats, long long ld,
                                                                   long long n_vec, const double *__restrict__ mean,
@@ -77,10 +70,7 @@ __global__ __launch_bounds__(kThreads) void svc_class_sums_kernel(SvcDev m, cons
     while (cls < k && m.class_end[cls] == 0) flush();          // classes without support vectors
     for (int base = 0; base < m.n_sv; base += kTile) {
         __syncthreads();
-        for (int i = tid; i < kTile * pitch; i += kThreads) {
-            const int s = base + i / pitch, d = i % pitch;
-            tile[i] = (s < m.n_sv && d < m.n_dims) ? m.sv[(long long)s * m.n_dims + d] : 0.0;
-        }
+        kv::stage_rows(tile, m.sv, base, m.n_sv, m.n_dims, pitch, tid);
         for (int i = tid; i < rows * kTile; i += kThreads) {
             const int r = i / kTile, s = base + i % kTile;
             coef[i] = s < m.n_sv ? m.coef[(long long)r * m.n_sv + s] : 0.0;

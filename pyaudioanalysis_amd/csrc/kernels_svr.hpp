@@ -5,11 +5,9 @@
 // (sklearn/svm/src/libsvm/svm.cpp, a third-party dependency of the reference; its published algorithm is restated here and
 // the GPU tests compare with the installed scikit-learn):
 //   out[m][v] = sum_s coef[s] K(sv_s, (x_v - mean_m) / std_m) - rho_m,   s over model m's support vectors IN THEIR ORDER,
-// K the dense k_function: RBF exp(-gamma sum_d (s_d - x_d)^2) in the difference form, linear sum_d s_d x_d -- as in
-// svc_class_sums_kernel (kernels_svc.hpp), whose lane split this kernel keeps: a group of kGroupLanes lanes owns
-// kWinPerGroup windows, lane l holds dims l, l + 8, ... of both in registers, tiles of kTile support vectors are staged in
-// LDS once per workgroup and used for all of its kWinPerBlock windows, three xor shuffles complete a kernel value.
-// What differs is the shape of the work: the grid is window tiles x chunks of kModelChunk models; a workgroup walks the
+// K the dense k_function: RBF exp(-gamma sum_d (s_d - x_d)^2) in the difference form, linear sum_d s_d x_d -- on the lane
+// split of kernels_kv.hpp with kWinPerGroup windows per group and the support vectors as rows.
+// Its own is the shape of the work: the grid is window tiles x chunks of kModelChunk models; a workgroup walks the
 // models of its chunk one after the other, forms the standardised vectors on the load path once per model (the models of a bank keep
 // their own mean / std) and keeps the registers when a model's mean / std equal its predecessor's bit for bit (same_prev,
 // set by the host: the evaluate_regression case).  One coefficient per support vector, one running sum per window: every
@@ -17,21 +15,21 @@
 // the window's place in the batch, nor on n_vec, ld, the chunking or the other models of the bank.  A model without support
 // vectors gives 0 - rho.  Non-finite inputs are not validated (as in the SVC kernel): they propagate by IEEE rules.
 #pragma once
-#include "device_common.hpp"
-#include "family_launch.hpp"
+#include "kernels_kv.hpp"
+#include "model_launch.hpp"
 
 namespace paa {
 namespace svr {
 
-// kGroupLanes, kWinPerGroup, kThreads, kWinPerBlock, kTile, kModelChunk: family_launch.hpp
-constexpr int kMaxM = kMaxDims / kGroupLanes;                         // 32 dims per lane
-
-__device__ __forceinline__ double group_sum(double v) {
-    v += __shfl_xor(v, 1, kGroupLanes);
-    v += __shfl_xor(v, 2, kGroupLanes);
-    v += __shfl_xor(v, 4, kGroupLanes);
-    return v;
-}
+using kv::group_sum;
+using kv::kGroupLanes;
+using kv::kMaxM;
+using kv::kThreads;
+using kv::kTile;
+constexpr int kWinPerGroup = 2;
+constexpr int kWinPerBlock = kThreads / kGroupLanes * kWinPerGroup;   // 32
+constexpr int kModelChunk = 4;
+static_assert(kMaxDims <= kv::kMaxDims, "the model limit fits the lane split");
 
 __global__ __launch_bounds__(kThreads) void svr_bank_kernel(SvrDev m, const double *__restrict__ feats, long long ld,
                                                             long long n_vec, double *__restrict__ out,
@@ -61,11 +59,7 @@ __global__ __launch_bounds__(kThreads) void svr_bank_kernel(SvrDev m, const doub
         double acc[kWinPerGroup] = {0.0, 0.0};
         for (long long base = s_begin; base < s_end; base += kTile) {
             __syncthreads();
-            for (int i = tid; i < kTile * pitch; i += kThreads) {
-                const long long s = base + i / pitch;
-                const int d = i % pitch;
-                tile[i] = (s < s_end && d < m.n_dims) ? m.sv[s * m.n_dims + d] : 0.0;
-            }
+            kv::stage_rows(tile, m.sv, base, s_end, m.n_dims, pitch, tid);
             if (tid < kTile) coef[tid] = base + tid < s_end ? m.coef[base + tid] : 0.0;
             __syncthreads();
             const int cnt = (int)min((long long)kTile, s_end - base);

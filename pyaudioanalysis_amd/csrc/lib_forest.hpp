@@ -121,10 +121,6 @@ extern "C" int paa_forest_num_classes(const void *handle) {
     return handle ? ((const PaaForest *)handle)->dev.n_classes : fail(PAA_ERR_ARG, "null handle");
 }
 
-static int forest_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    return check_model_matrix(handle ? &((const PaaForest *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec, 0);
-}
-
 static size_t forest_leaf_bytes(const forest::ForestDev &m, int64_t n_vec) {
     return (size_t)m.n_trees * (size_t)std::min<int64_t>(n_vec, forest::kChunk) * sizeof(int);
 }
@@ -132,7 +128,7 @@ static size_t forest_leaf_bytes(const forest::ForestDev &m, int64_t n_vec) {
 extern "C" int paa_forest_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                                           const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                                           double *d_raw) {
-    int rc = forest_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaForest>(handle, n_dims, ld, n_vec, 0);
     if (rc) return rc;
     if (!d_feats || !d_mean || !d_std || !d_label_index || !d_proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
@@ -151,7 +147,7 @@ extern "C" int paa_forest_dev_predict_f64(const void *handle, const double *d_fe
 
 extern "C" int paa_forest_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec,
                                       const double *mean, const double *std, int32_t *label_index, double *proba, double *raw) {
-    int rc = forest_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaForest>(handle, n_dims, ld, n_vec, 0);
     if (rc) return rc;
     if (!feats || !mean || !std || !label_index || !proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;

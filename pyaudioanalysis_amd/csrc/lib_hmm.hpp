@@ -83,9 +83,7 @@ extern "C" int paa_hmm_num_states(const void *handle) {
     return handle ? ((const PaaHmm *)handle)->dev.n_states : fail(PAA_ERR_ARG, "null handle");
 }
 
-static int hmm_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    return check_model_matrix(handle ? &((const PaaHmm *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec, 0x7fffffffLL);
-}
+constexpr int64_t kHmmMaxVec = 0x7fffffffLL;
 
 static int hmm_check_offsets(const int64_t *offsets, int64_t n_seq, int64_t n_vec) {
     if (!offsets) return fail(PAA_ERR_ARG, "null offsets");
@@ -142,7 +140,7 @@ static int hmm_decode_core(PaaHmm *h, const double *d_feats, int64_t ld, int64_t
 
 static int hmm_dev_decode(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                           const int64_t *offsets, int64_t n_seq, int32_t *d_states, double *d_logprob, int64_t block_rows) {
-    int rc = hmm_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaHmm>(handle, n_dims, ld, n_vec, kHmmMaxVec);
     if (rc) return rc;
     if ((rc = hmm_check_offsets(offsets, n_seq, n_vec))) return rc;
     if (!d_feats || !d_states || !d_logprob) return fail(PAA_ERR_ARG, "null buffer");
@@ -164,7 +162,7 @@ extern "C" int paa_debug_hmm_dev_decode_f64(const void *handle, const double *d_
 
 extern "C" int paa_hmm_dev_loglik_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                                       double *d_loglik) {
-    int rc = hmm_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaHmm>(handle, n_dims, ld, n_vec, kHmmMaxVec);
     if (rc) return rc;
     if (!d_feats || !d_loglik) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
@@ -175,7 +173,7 @@ extern "C" int paa_hmm_dev_loglik_f64(const void *handle, const double *d_feats,
 
 extern "C" int paa_hmm_decode_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec,
                                   const int64_t *offsets, int64_t n_seq, int32_t *states, double *logprob) {
-    int rc = hmm_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaHmm>(handle, n_dims, ld, n_vec, kHmmMaxVec);
     if (rc) return rc;
     if ((rc = hmm_check_offsets(offsets, n_seq, n_vec))) return rc;
     if (!feats || !states || !logprob) return fail(PAA_ERR_ARG, "null buffer");

@@ -38,15 +38,12 @@ extern "C" int paa_knn_num_classes(const void *handle) {
     return handle ? ((const PaaKnn *)handle)->dev.n_classes : fail(PAA_ERR_ARG, "null handle");
 }
 
-static int knn_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    return check_model_matrix(handle ? &((const PaaKnn *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec,
-                              0x7fffffffLL * knn::kQueriesPerBlock);      // grid limit
-}
+constexpr int64_t kKnnMaxVec = 0x7fffffffLL * knn::kQueriesPerBlock;      // grid limit
 
 extern "C" int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                                        const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                                        int32_t *d_neighbors) {
-    int rc = knn_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaKnn>(handle, n_dims, ld, n_vec, kKnnMaxVec);
     if (rc) return rc;
     if (!d_feats || !d_mean || !d_std || !d_label_index || !d_proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
@@ -58,7 +55,7 @@ extern "C" int paa_knn_dev_predict_f64(const void *handle, const double *d_feats
 extern "C" int paa_knn_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec,
                                    const double *mean, const double *std, int32_t *label_index, double *proba,
                                    int32_t *neighbors) {
-    int rc = knn_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaKnn>(handle, n_dims, ld, n_vec, kKnnMaxVec);
     if (rc) return rc;
     if (!feats || !mean || !std || !label_index || !proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;

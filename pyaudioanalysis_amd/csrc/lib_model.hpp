@@ -11,17 +11,19 @@ static inline size_t up256(size_t bytes) { return (bytes + 255) / 256 * 256; }
         if (call) return fail(PAA_ERR_HIP, what " launch failed: %s", hipGetErrorString(hipGetLastError()));     \
     } while (0)
 
-// A feature matrix [n_dims][ld] with n_vec columns in use.  model_dims: where the n_dims of the model behind the handle is
-// found (nullptr: a null handle), or check_matrix for an entry point without a model; max_vec: the family's grid limit
-// (0: none).  Runs before ensure_init(): an argument error is reported on a host without a device too.
+// A feature matrix [n_dims][ld] with n_vec columns in use: model_check<Handle> against the n_dims of the model behind the
+// handle (PaaSvc, PaaSvr, PaaKnn, PaaForest, PaaHmm), or check_matrix for an entry point without a model; max_vec: the
+// family's grid limit (0: none).  Runs before ensure_init(): an argument error is reported on a host without a device too.
 static int check_matrix(int64_t ld, int64_t n_vec, int64_t max_vec) {
     if (n_vec < 1 || ld < n_vec) return fail(PAA_ERR_ARG, "bad feature matrix: %lld vectors, ld %lld", (long long)n_vec, (long long)ld);
     if (max_vec && n_vec > max_vec) return fail(PAA_ERR_ARG, "too many vectors");
     return PAA_OK;
 }
-static int check_model_matrix(const int *model_dims, int n_dims, int64_t ld, int64_t n_vec, int64_t max_vec) {
-    if (!model_dims) return fail(PAA_ERR_ARG, "null handle");
-    if (n_dims != *model_dims) return fail(PAA_ERR_ARG, "feature vectors have %d dims, the model %d", n_dims, *model_dims);
+template <typename Handle>
+static int model_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec, int64_t max_vec) {
+    if (!handle) return fail(PAA_ERR_ARG, "null handle");
+    const int model_dims = ((const Handle *)handle)->dev.n_dims;
+    if (n_dims != model_dims) return fail(PAA_ERR_ARG, "feature vectors have %d dims, the model %d", n_dims, model_dims);
     return check_matrix(ld, n_vec, max_vec);
 }
 

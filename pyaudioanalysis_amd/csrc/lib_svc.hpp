@@ -56,14 +56,11 @@ extern "C" int paa_svc_num_classes(const void *handle) {
     return handle ? ((const PaaSvc *)handle)->dev.k : fail(PAA_ERR_ARG, "null handle");
 }
 
-static int svc_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    return check_model_matrix(handle ? &((const PaaSvc *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec,
-                              0x7fffffffLL * 16);      // grid limit of both kernels
-}
+constexpr int64_t kSvcMaxVec = 0x7fffffffLL * 16;      // grid limit of both kernels
 
 extern "C" int paa_svc_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                                        const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba) {
-    int rc = svc_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaSvc>(handle, n_dims, ld, n_vec, kSvcMaxVec);
     if (rc) return rc;
     if (!d_feats || !d_mean || !d_std || !d_label_index || !d_proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;
@@ -80,7 +77,7 @@ extern "C" int paa_svc_dev_predict_f64(const void *handle, const double *d_feats
 
 extern "C" int paa_svc_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec,
                                    const double *mean, const double *std, int32_t *label_index, double *proba) {
-    int rc = svc_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaSvc>(handle, n_dims, ld, n_vec, kSvcMaxVec);
     if (rc) return rc;
     if (!feats || !mean || !std || !label_index || !proba) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;

@@ -72,21 +72,15 @@ extern "C" int paa_svr_num_models(const void *handle) {
 // windows per workgroup, models per workgroup, support vectors per LDS tile, lanes per window group (for the edge tests)
 extern "C" int paa_debug_svr_geometry(int32_t *out4) {
     if (!out4) return fail(PAA_ERR_ARG, "null");
-    out4[0] = svr::kWinPerBlock;
-    out4[1] = svr::kModelChunk;
-    out4[2] = svr::kTile;
-    out4[3] = svr::kGroupLanes;
+    launch::svr_geometry(out4);
     return PAA_OK;
 }
 
-static int svr_check(const void *handle, int n_dims, int64_t ld, int64_t n_vec) {
-    return check_model_matrix(handle ? &((const PaaSvr *)handle)->dev.n_dims : nullptr, n_dims, ld, n_vec,
-                              0x7fffffffLL * 16);      // grid limit
-}
+constexpr int64_t kSvrMaxVec = 0x7fffffffLL * 16;      // grid limit
 
 extern "C" int paa_svr_dev_predict_f64(const void *handle, const double *d_feats, int n_dims, int64_t ld, int64_t n_vec,
                                        double *d_out, int64_t ld_out) {
-    int rc = svr_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaSvr>(handle, n_dims, ld, n_vec, kSvrMaxVec);
     if (rc) return rc;
     if (ld_out < n_vec) return fail(PAA_ERR_ARG, "output rows of %lld for %lld vectors", (long long)ld_out, (long long)n_vec);
     if (!d_feats || !d_out) return fail(PAA_ERR_ARG, "null buffer");
@@ -96,7 +90,7 @@ extern "C" int paa_svr_dev_predict_f64(const void *handle, const double *d_feats
 }
 
 extern "C" int paa_svr_predict_f64(const void *handle, const double *feats, int n_dims, int64_t ld, int64_t n_vec, double *out) {
-    int rc = svr_check(handle, n_dims, ld, n_vec);
+    int rc = model_check<PaaSvr>(handle, n_dims, ld, n_vec, kSvrMaxVec);
     if (rc) return rc;
     if (!feats || !out) return fail(PAA_ERR_ARG, "null buffer");
     if ((rc = ensure_init())) return rc;

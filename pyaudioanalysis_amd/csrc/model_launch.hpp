@@ -1,0 +1,187 @@
+// Limits, device records and launch entry points of the model families (svc, svr, knn, forest, hmm, diar, lda).  Every family
+// is its own translation unit (family_<name>.hip: its kernels and the host code that picks an instance are there and
+// nowhere else); the host side of the library (the lib_*.hpp units of paa_lib.hip) sees only what is here.  Every launch::
+// function queues its kernels on `stream` and returns 0, or -1 when a launch failed (hipGetLastError has the reason).
+// No device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+#include <utility>
+
+namespace paa {
+namespace svc {
+constexpr int kMaxClasses = 16;
+constexpr int kMaxDims = 256;
+// one uploaded model (libsvm's svm_model as scikit-learn holds it): device pointers
+struct SvcDev {
+    const double *sv;         // [n_sv][n_dims] support vectors, grouped by class
+    const double *coef;       // [k - 1][n_sv] sv_coef (scikit-learn's _dual_coef_)
+    const int *class_end;     // [k] end of class c's range of support vectors (cumulative n_support)
+    const double *rho;        // [k (k - 1) / 2] (= -_intercept_)
+    const double *prob_a, *prob_b;
+    int n_sv, n_dims, k, rbf;
+    double gamma;
+};
+}  // namespace svc
+namespace svr {
+constexpr int kMaxModels = 4096;
+constexpr int kMaxDims = 256;
+// one uploaded bank of epsilon-SVR models that share n_dims (libsvm's svm_model as scikit-learn holds it): device pointers
+struct SvrDev {
+    const double *sv;         // [total_sv][n_dims] support vectors, model after model
+    const double *coef;       // [total_sv] sv_coef (scikit-learn's _dual_coef_[0])
+    const long long *sv_off;  // [n_models + 1] model m owns support vectors sv_off[m] .. sv_off[m + 1] - 1 (none: legal)
+    const double *rho;        // [n_models] (= -_intercept_)
+    const double *gamma;      // [n_models]
+    const int *rbf;           // [n_models] 1: RBF, 0: linear
+    const int *same_prev;     // [n_models] 1: mean / std of model m equal those of model m - 1 bit for bit
+    const double *mean, *scale;   // [n_models][n_dims] every model's own standardisation
+    int n_models, n_dims;
+};
+}  // namespace svr
+namespace knn {
+constexpr int kMaxK = 32;
+constexpr int kMaxClasses = 64;
+constexpr int kMaxDims = 256;
+constexpr int kQueriesPerBlock = 16;      // kernels_knn.hpp: one query per group of lanes
+// one uploaded kNN model (audioTrainTest.Knn): device pointers
+struct KnnDev {
+    const double *train;      // [n_train][n_dims] training vectors
+    const int *labels;        // [n_train] class index of every row (a value outside 0..n_classes-1 votes for no class)
+    int n_train, n_dims, n_classes, k;
+};
+}  // namespace knn
+namespace forest {
+constexpr int kMaxClasses = 64;
+constexpr int kMaxDims = 256;
+constexpr int kWin = 64;                  // kernels_forest.hpp: windows per traversal workgroup, one per lane
+constexpr int kChunk = 32768;             // windows per traversal / reduction pass (bounds the leaf-slot scratch)
+// a packed tree node (preorder: the left child of node i is node i + 1): 16 bytes, one load per visited node
+constexpr int kFeatureMask = 0xffff, kMissingLeft = 1 << 16, kLeaf = 1 << 17;
+struct Node {
+    double threshold;         // go left when (double)x32[feature] <= threshold
+    int meta;                 // feature | kMissingLeft (NaN goes left) | kLeaf
+    int next;                 // internal: the right child's node index; leaf: its leaf slot (row of leaf_values)
+};
+// one uploaded tree ensemble (scikit-learn's RandomForest / ExtraTrees / GradientBoosting classifiers): device pointers
+struct ForestDev {
+    const Node *nodes;        // every tree's nodes, tree after tree, each in preorder
+    const int *roots;         // [n_trees] node index of every root
+    const double *leaf_values;    // [n_leaves][n_outputs] averaged forest: class fractions; boosted: [n_leaves] values
+    const double *init;       // [n_outputs] boosted: the constant initial raw score
+    int n_trees, n_dims, n_classes, n_outputs, boosted;
+    double learning_rate;
+};
+}  // namespace forest
+namespace hmm {
+constexpr int kMaxStates = 32;
+constexpr int kMaxDims = 256;
+constexpr int kBlockRows = 256;           // rows per segment of a long sequence (kernels_hmm.hpp); shorter sequences are one segment
+// one uploaded Gaussian HMM (diagonal): device pointers; kp = n_states rounded up to a power of two (>= 2), padded
+// states have log-probability -inf
+struct HmmDev {
+    const double *mu, *inv;   // [n_dims][kp] means and 1 / covars_ (the reference's covars_ hold standard deviations)
+    const double *cst;        // [kp] n_dims log(2 pi) + sum_d log covars_[k][d]
+    const double *logpi;      // [kp] log startprob
+    const double *logA;       // [kp][kp] log transmat
+    int n_states, n_dims, kp;
+};
+// rows r0 .. r1 - 1 of the stacked sequences; first / last: the segment begins / ends its sequence
+struct Segment {
+    long long r0, r1;
+    int first, last;
+};
+}  // namespace hmm
+namespace diar {
+// k-means of one k of a sweep (kernels_diar.hpp): written by finish_kernel, polled by the host after every iteration
+struct KmState {
+    int done, strict, n_iter, n_empty;
+    double shift;
+};
+constexpr int kMaxPoints = 8;                         // candidate windows per sqdist_points_kernel launch
+constexpr int kIntsPerK = hmm::kMaxStates + 1;      // cluster sizes and the number of changed labels of one assignment
+}  // namespace diar
+
+// f(std::integral_constant<int, v>) for Lo <= v <= Hi, one instance per value; -1 outside the range
+template <int Lo, int Hi, typename F>
+int dispatch_int(int v, F &&f) {
+    if (v == Lo) return f(std::integral_constant<int, Lo>{});
+    if constexpr (Lo < Hi) return dispatch_int<Lo + 1, Hi>(v, std::forward<F>(f));
+    return -1;
+}
+
+namespace launch {
+
+// kernels_svc.hpp: multi-class probabilistic SVC over the columns of feats [n_dims][ld] (two kernels: the per-class sums go to
+// `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
+int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
+        double *d_sums, int *d_label, double *d_proba, hipStream_t stream);
+// kernels_svr.hpp: a bank of epsilon-SVR models over the columns of feats [n_dims][ld] (one kernel): out [n_models][ld_out], every
+// model's prediction of every column after that model's own (x - mean) / std
+int svr(const svr::SvrDev &m, const double *d_feats, long long ld, long long n_vec, double *d_out, long long ld_out,
+        hipStream_t stream);
+// ... and its geometry, for tests that aim at its edges: windows per workgroup, models per workgroup, support vectors per tile, lanes per group
+void svr_geometry(int out4[4]);
+// kernels_knn.hpp: k-nearest-neighbour classification of the columns of feats [n_dims][ld] (one kernel: labels [n_vec],
+// P [n_vec][n_classes] and, when d_neighbors is not null, the k neighbour indices [n_vec][k] in ascending (d^2, index))
+int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
+        int *d_label, double *d_proba, int *d_neighbors, hipStream_t stream);
+// kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
+// two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
+// infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the
+// probabilities proba [n_vec][n_classes])
+int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean,
+           const double *d_scale, int *d_leaves, int *d_label, double *d_raw, double *d_proba, hipStream_t stream);
+// kernels_hmm.hpp: frame log-likelihoods loglik [n_vec][n_states] of the columns of feats [n_dims][ld] (one kernel)
+int hmm_emission(const hmm::HmmDev &m, const double *d_feats, long long ld, long long n_vec, double *d_loglik, hipStream_t stream);
+// ... and Viterbi over n_seq sequences cut into n_seg segments (segment s of sequence q: seq_seg[q] <= s < seq_seg[q + 1]):
+// states [rows] and logprob [n_seq].  multi: some sequence has more than one segment (two more kernels: M [n_seg][kp][kp],
+// V [n_seg][kp]); Vout [n_seg][kp], psi [rows][kp] bytes, emap [n_seg][kp] bytes, seg_end [n_seg] are scratch
+int hmm_decode(const hmm::HmmDev &m, const double *d_loglik, const hmm::Segment *d_segs, long long n_seg,
+               const long long *d_seq_seg, long long n_seq, int multi, double *d_M, double *d_V, double *d_Vout,
+               unsigned char *d_psi, unsigned char *d_emap, int *d_seg_end, int *d_states, double *d_logprob, hipStream_t stream);
+// ... and the training statistics of labelled windows: counts [K + K K] (zero on entry: class counts, transition counts),
+// means / stds [K][n_dims] (two kernels)
+int hmm_stats(const double *d_feats, long long ld, long long n_vec, const int *d_labels, int n_states, int n_dims,
+              int *d_counts, double *d_means, double *d_stds, hipStream_t stream);
+// kernels_diar.hpp (speaker diarization); every matrix feature-major [n_dims][ld].  Z = StandardScaler of M, stats [3][n_dims]
+int diar_standardize(const double *d_M, long long ldm, long long n, int n_dims, double *d_Z, long long ldz, double *d_stats,
+                     hipStream_t stream);
+// out [n_rows][ldo] = the rows `d_rows` of Z
+int diar_select_rows(const double *d_Z, long long ldz, long long n, const int *d_rows, int n_rows, double *d_out, long long ldo,
+                     hipStream_t stream);
+// distances between feature rows over the windows labelled c of sweep entry kidx (d_labels [nk][n]; null: all windows, nk =
+// kmax = 1): dist [nk][kmax][D][D] (scratch), colsum [nk][kmax][D], pmean [nk][kmax]
+int diar_dim_distances(const double *d_Z, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk, int kmax,
+                       double *d_dist, double *d_colsum, double *d_pmean, hipStream_t stream);
+// one Lloyd iteration of every unfinished k (ints [nk][33] is zeroed here), and the last pass (labels, d2, inertia [nk])
+int diar_kmeans_step(const double *d_Zk, long long ld, long long n, int D, const int *d_ks, int nk, int kmax, double *d_centers,
+                     diar::KmState *d_state, int *d_labels, double *d_d2, int *d_ints, double *d_sums, double tol, int max_iter,
+                     hipStream_t stream);
+int diar_kmeans_last(const double *d_Zk, long long ld, long long n, int D, const int *d_ks, int nk, int kmax, const double *d_centers,
+                     const diar::KmState *d_state, int *d_labels, double *d_d2, double *d_inertia, hipStream_t stream);
+int diar_sqdist_points(const double *d_Zk, long long ld, long long n, int D, const long long *d_idx, int n_pts, double *d_out,
+                       hipStream_t stream);
+int diar_get_points(const double *d_Zk, long long ld, int D, const long long *d_idx, int n_pts, double *d_out, hipStream_t stream);
+// cluster-pair distance sums of every k of a sweep in one pass: S [binoff[nk]] (per k: [K][K]); partial and stage are scratch
+// of diar_pair_tiles(n) * nbins and diar_pair_chunks(n) * nbins doubles
+long long diar_pair_tiles(long long n);
+long long diar_pair_chunks(long long n);
+int diar_pair_sums(const double *d_Zk, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk,
+                   const int *d_binoff, int nbins, double *d_partial, double *d_stage, double *d_S, hipStream_t stream);
+// kernels_lda.hpp (the LDA step of speaker diarization); classes are the runs off[c] .. off[c + 1] - 1 of windows (off [C + 1] on
+// the device).  means [C][D] and std [D] (pooled within-class deviation, zeros replaced by 1); dev and sq [C][D] are scratch
+int lda_class_stats(const double *d_X, long long ld, long long n, int D, const long long *d_off, long long C, double *d_means,
+                    double *d_dev, double *d_sq, double *d_std, hipStream_t stream);
+// G [D][D] = Xs^T Xs of Xs = (X - class mean) * rscale, in lda_gram_chunks(n) partials [D][D] each (scratch) added in chunk
+// order; cls [n] is scratch
+long long lda_gram_chunks(long long n);
+int lda_within_gram(const double *d_X, long long ld, long long n, int D, const long long *d_off, long long C, const double *d_means,
+                    const double *d_rscale, int *d_cls, double *d_partial, double *d_G, hipStream_t stream);
+// Y [n_out][ldy] = ((X - xbar)^T S)^T, S [D][n_out]
+int lda_project(const double *d_X, long long ld, long long n, int D, const double *d_xbar, const double *d_S, int n_out, double *d_Y,
+                long long ldy, hipStream_t stream);
+
+}  // namespace launch
+}  // namespace paa

@@ -24,6 +24,7 @@
 // the kernels of the feature families are instantiated in their own translation units (family_*.hip); this unit sees their
 // host-side layout / selection code and the launch entry points of family_launch.hpp
 #include "family_launch.hpp"
+#include "model_launch.hpp"
 #include "kernels_aux.hpp"
 #include "kernels_big.hpp"
 #include "kernels_wg.hpp"
