@@ -274,6 +274,45 @@ int paa_knn_dev_predict_f64(const void *handle, const double *d_feats, int n_dim
                             const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                             int32_t *d_neighbors);
 
+/* ---- the kNN half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700) ----------------------------------------
+ * evaluate_classifier draws len(params) x n_exp random splits of one sample matrix and, for "knn", runs Knn.classify
+ * (:33-49) once per test vector of every split after a StandardScaler fitted on that split's training rows (:652-680).  Here
+ * every split is a JOB of two index lists over ONE sample matrix, and all jobs run in one launch; X is uploaded once per call.
+ *   X [n_samples][n_dims]    every sample, row-major (1 <= n_dims <= 256, 1 <= n_samples < 2^31)
+ *   labels [n_samples]       the class INDEX of every sample; -1 (any value outside 0..n_classes[j]-1) votes for no class
+ *   n_jobs >= 1              number of jobs
+ *   train_off [n_jobs + 1], train_idx [train_off[n_jobs]]   job j trains on the samples train_idx[train_off[j] .. train_off[j+1]-1],
+ *                            in that order (the rows of the reference's X_train); at least one per job
+ *   test_off [n_jobs + 1], test_idx [test_off[n_jobs]]      ... and classifies the samples test_idx[test_off[j] .. test_off[j+1]-1];
+ *                            an empty test list is legal.  Offsets begin at 0 and do not decrease; indices are 0..n_samples-1;
+ *                            lists may repeat and overlap
+ *   mean, std [n_jobs][n_dims]   job j's standardisation: every training and test row is (x - mean_j) / std_j, IEEE division,
+ *                            element by element BEFORE the difference is taken (StandardScaler.transform, :658, :676)
+ *   k [n_jobs]               1 <= k[j] <= 32 (Knn.neighbors of the split)
+ *   n_classes [n_jobs]       1 <= n_classes[j] <= max_classes <= 64: the number of distinct training labels of the split
+ *                            (Knn.classify :40 counts them per split: a class absent from it shrinks n_classes, and rows labelled
+ *                            >= n_classes[j] vote for no class)
+ * Neighbours are ranked in ascending (d^2, position in the job's train list), d^2 = sum_d (t_d - x_d)^2 of the standardised
+ * rows: the tie rule is the row index into the reference's X_train, NOT the sample index.  The first k[j] of that order vote.
+ * Outputs hold Q = test_off[n_jobs] rows, in job order then test-list order:
+ *   label_out [Q]            the first class < n_classes[j] with the most votes
+ *   proba_out [Q][max_classes]   (may be NULL) votes(c) / k[j], also when the job has fewer than k[j] rows; 0 at c >= n_classes[j]
+ *   neighbors_out [Q][K]     (may be NULL) the neighbours' train-list positions in that order, -1 past k[j] or past the train list;
+ *                            K = the smallest of 1, 2, 4, 8, 16, 32 that is >= max_j k[j] (the kernel instance the sweep runs at)
+ * A query with NaN distances (std 0 where x == mean) gets no neighbours: P = 0, label 0; other jobs are unaffected.
+ * PAA_ERR_ARG, with a message and before the device is touched: a null pointer (other than the two optional outputs), offsets
+ * that do not begin at 0 or decrease, an index outside 0..n_samples-1, k / classes / dims outside the limits above, an empty
+ * train list, Q > 2^31 - 1.  Q == 0 returns PAA_OK and writes nothing.  Synchronous, host buffers in and out.
+ * Of evaluate_classifier's six classifier types only "knn" is served here; the five scikit-learn types keep scikit-learn's
+ * fits and gain only one paa_svc_* / paa_forest_* launch per fitted model in place of the per-vector predict loop, and SMOTE
+ * resampling (smote=True, :653-656) is refused by the Python layer: its rows are no rows of X.                           */
+int paa_knn_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                       const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                       const double *mean, const double *std, const int32_t *k, const int32_t *n_classes, int max_classes,
+                       int32_t *label_out, double *proba_out, int32_t *neighbors_out);
+/* tests: out10 = queries per workgroup, training rows per LDS tile, rows per step, the number of K instances, the instances */
+int paa_debug_knn_split_geometry(int32_t *out10);
+
 /* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
  * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as
  * train_svm_regression makes them, audioTrainTest.py:222-226) for many feature vectors and many models at once: what

@@ -14,6 +14,11 @@ pyAudioAnalysis/audioTrainTest.py).
     file_regression(input_file, model_name, model_type)           audioTrainTest.py:1099-1151
     file_regression_batch(files, model_name, model_type)          many files: one mid-term plan, one regression launch
     regress(models, model_type, feats, means, stds), SvrBank, SvrArrays   every model on every vector in one launch
+    train_knn, train_svm, train_random_forest, train_gradient_boosting, train_extra_trees   audioTrainTest.py:117-219
+    features_to_matrix, group_split, print_confusion_matrix       audioTrainTest.py:887-911, :556-573, :858-884
+    evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, ...)   audioTrainTest.py:576-771
+    extract_features_and_train(paths, ..., classifier_type, model_name, ...)                   audioTrainTest.py:236-361
+    knn_split_predict(X, labels, jobs, proba=False, neighbors=False)   every kNN split of a sweep in one launch
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -27,7 +32,10 @@ GradientBoostingClassifier, as the reference's trainers make them) predict() and
 (kernels_forest.hpp through paa_forest_*): every tree walked for every vector, the leaf values summed in tree order,
 bit-identical to scikit-learn; only the trees' tree_ arrays, classes_ and (boosted) learning_rate / init_ are read, so a
 model given as arrays (ForestArrays) works without scikit-learn.  Unpickling an SVM or tree-ensemble model needs
-scikit-learn exactly where the reference needs it (load_model).  Training stays with scikit-learn.
+scikit-learn exactly where the reference needs it (load_model).  Training stays with scikit-learn: evaluate_classifier / extract_features_and_train tune and train all six
+types; for "knn", which has no fit, the whole split sweep of evaluate_classifier is ONE launch over index lists into one
+resident sample matrix (knn_split_kernel through paa_knn_splits_f64); the five scikit-learn types gain only the removal of
+the per-vector predict loop.  smote / use_smote are refused (NotImplementedError).
 Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
 SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
 value of evaluate_regression -- scores every vector in one launch (kernels_svr.hpp through paa_svr_*: libsvm's decision value
@@ -753,6 +761,354 @@ def regress(models, model_type, feats, means, stds):
     for i, m in enumerate(models):
         out[i] = _forest_regressor(m).predict(F, means[i], stds[i])[1][:, 0]
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# training and tuning of classifiers (reference :117-219, :236-361, :556-771, :858-911)
+# ---------------------------------------------------------------------------------------------------------------------
+_CLASSIFIER_TYPES = _SVM_TYPES + ("knn",) + _FOREST_TYPES
+
+
+def train_knn(features, labels, neighbors):
+    """This package's Knn over the given rows (reference :117-129): a kNN has no fit."""
+    return Knn(features, labels, neighbors)
+
+
+def train_svm(features, labels, c_param, kernel='linear'):
+    """A fitted sklearn.svm.SVC(probability=True, gamma='auto') (reference :132-155); scikit-learn fits."""
+    import sklearn.svm
+    svm = sklearn.svm.SVC(C=c_param, kernel=kernel, probability=True, gamma='auto')
+    svm.fit(features, labels)
+    return svm
+
+
+def train_random_forest(features, labels, n_estimators):
+    """A fitted RandomForestClassifier (reference :158-178); scikit-learn fits."""
+    import sklearn.ensemble
+    rf = sklearn.ensemble.RandomForestClassifier(n_estimators=n_estimators)
+    rf.fit(features, labels)
+    return rf
+
+
+def train_gradient_boosting(features, labels, n_estimators):
+    """A fitted GradientBoostingClassifier (reference :181-199); scikit-learn fits."""
+    import sklearn.ensemble
+    gb = sklearn.ensemble.GradientBoostingClassifier(n_estimators=n_estimators)
+    gb.fit(features, labels)
+    return gb
+
+
+def train_extra_trees(features, labels, n_estimators):
+    """A fitted ExtraTreesClassifier (reference :202-219); scikit-learn fits."""
+    import sklearn.ensemble
+    et = sklearn.ensemble.ExtraTreesClassifier(n_estimators=n_estimators)
+    et.fit(features, labels)
+    return et
+
+
+def _train_classifier(features, labels, classifier_name, param):
+    if classifier_name in _SVM_TYPES:
+        return train_svm(features, labels, param, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
+    return {"knn": train_knn, "randomforest": train_random_forest, "gradientboosting": train_gradient_boosting,
+            "extratrees": train_extra_trees}[classifier_name](features, labels, param)
+
+
+def features_to_matrix(features):
+    """(the feature matrices of a list stacked, the class index of every row as floats) (reference :887-911).  As in the
+    reference a list of ONE matrix gives that matrix itself and labels of shape [n][1], an empty list two empty arrays."""
+    if len(features) == 0:
+        return np.array([]), np.array([])
+    if len(features) == 1:
+        return features[0], np.zeros((len(features[0]), 1))
+    return np.vstack(list(features)), np.concatenate([i * np.ones(len(f)) for i, f in enumerate(features)])
+
+
+def group_split(X, y, train_indeces, test_indeces, split_id):
+    """(X_train, X_test, y_train, y_test) of split `split_id` of two lists of index lists (reference :556-573)."""
+    train_index, test_index = train_indeces[split_id], test_indeces[split_id]
+    return X[train_index], X[test_index], y[train_index], y[test_index]
+
+
+def print_confusion_matrix(cm, class_names):
+    """Prints a confusion matrix in per cent of all samples (reference :858-884)."""
+    if cm.shape[0] != len(class_names):
+        print("printConfusionMatrix: Wrong argument sizes\n")
+        return
+    short = [c[0:3] if len(c) > 4 else c for c in class_names]
+    print("".join("\t{0:s}".format(c) for c in short))
+    total = np.sum(cm)
+    for i, c in enumerate(short):
+        print("{0:s}".format(c) + "".join("\t{0:.2f}".format(100.0 * cm[i][j] / total) for j in range(len(class_names))))
+
+
+def knn_split_geometry():
+    """(queries per workgroup, training rows per LDS tile, rows per step, the K instances) of the split-sweep kernel."""
+    geo = np.zeros(10, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_debug_knn_split_geometry(geo.ctypes.data_as(_ffi.c_i32p)))
+    return int(geo[0]), int(geo[1]), int(geo[2]), tuple(int(v) for v in geo[4:4 + geo[3]])
+
+
+class KnnSplitResult:
+    """What knn_split_predict returns: label [Q] (int64 class indices), proba [Q][max_classes] or None, neighbors
+    [Q][k_launch] or None (train-list positions, -1 past a job's k or train list), test_off [n_jobs + 1] (job j owns the rows
+    test_off[j] .. test_off[j + 1] - 1), n_classes [n_jobs] and k [n_jobs]."""
+
+    def __init__(self, label, proba, neighbors, test_off, n_classes, k):
+        self.label, self.proba, self.neighbors, self.test_off, self.n_classes, self.k = label, proba, neighbors, test_off, n_classes, k
+
+    def job(self, j):
+        """(labels, P [n_test][n_classes_j] or None, neighbours [n_test][k_j] or None) of job j."""
+        a, b = int(self.test_off[j]), int(self.test_off[j + 1])
+        return (self.label[a:b], None if self.proba is None else self.proba[a:b, :self.n_classes[j]],
+                None if self.neighbors is None else self.neighbors[a:b, :self.k[j]])
+
+
+def _index_list(idx, what, j):
+    a = np.asarray(idx)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError("job %d: the %s list must be a one-dimensional array of integers" % (j, what))
+    if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+        raise ValueError("job %d: a %s index does not fit 32 bits" % (j, what))
+    return a.astype(np.int32)
+
+
+def knn_split_predict(X, labels, jobs, proba=False, neighbors=False):
+    """Knn.classify for every job of a sweep over ONE sample matrix, in one launch (paa_knn_splits_f64, knn_split_kernel).
+    X [n_samples][n_dims]; labels [n_samples]; a job is (train_idx, test_idx, mean, scale, k): the rows X[train_idx]
+    standardised as (x - mean) / scale are the model, in that order, the rows X[test_idx] the queries.  n_classes of a
+    job is the number of distinct labels of ITS training rows, as KnnModel counts it (the reference's Knn.classify :40):
+    a class absent from a split shrinks it, and rows labelled >= n_classes then vote for no class, like labels that
+    are no integers >= 0.  Neighbours rank in ascending (squared distance, position in train_idx).  Returns a KnnSplitResult."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    raw = np.asarray(labels).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or raw.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
+    jobs = list(jobs)
+    if not jobs:
+        raise ValueError("no jobs")
+    n_samples, n_dims = X.shape
+    lab = np.full(n_samples, -1, dtype=np.int32)
+    if raw.dtype.kind in "biuf":
+        v = raw.astype(np.float64)
+        ok = (v == np.floor(v)) & (v >= 0) & (v < 2**31)
+        lab[ok] = v[ok].astype(np.int32)
+    train, test, means, scales, ks, ncls = [], [], [], [], [], []
+    for j, job in enumerate(jobs):
+        if len(job) != 5:
+            raise ValueError("job %d: (train_idx, test_idx, mean, scale, k) expected" % j)
+        tr, te = _index_list(job[0], "train", j), _index_list(job[1], "test", j)
+        mean, scale = _stats(job[2], job[3], n_dims)
+        train.append(tr)
+        test.append(te)
+        means.append(mean)
+        scales.append(scale)
+        ks.append(int(job[4]))
+        inside = tr[(tr >= 0) & (tr < n_samples)]               # an index outside the matrix is the library's error to report
+        ncls.append(max(int(np.unique(raw[inside]).shape[0]), 1))
+    train_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in train])]).astype(np.int64)
+    test_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in test])]).astype(np.int64)
+    train_idx = np.ascontiguousarray(np.concatenate(train), dtype=np.int32)
+    test_idx = np.ascontiguousarray(np.concatenate(test), dtype=np.int32)
+    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
+    k, n_classes = np.array(ks, dtype=np.int32), np.array(ncls, dtype=np.int32)
+    max_classes = int(n_classes.max())
+    instances = knn_split_geometry()[3]
+    k_launch = min([K for K in instances if K >= int(k.max())], default=instances[-1])
+    Q = int(test_off[-1])
+    label = np.zeros(Q, dtype=np.int32)
+    P = np.zeros((Q, max_classes), dtype=np.float64) if proba else None
+    nb = np.full((Q, k_launch), -1, dtype=np.int32) if neighbors else None
+    _ffi.check(_ffi.lib().paa_knn_splits_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, lab.ctypes.data_as(_ffi.c_i32p), len(jobs), train_off.ctypes.data_as(_ffi.c_i64p),
+        train_idx.ctypes.data_as(_ffi.c_i32p), test_off.ctypes.data_as(_ffi.c_i64p), test_idx.ctypes.data_as(_ffi.c_i32p),
+        _ffi.as_f64p(mean), _ffi.as_f64p(scale), k.ctypes.data_as(_ffi.c_i32p), n_classes.ctypes.data_as(_ffi.c_i32p), max_classes,
+        label.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(P) if proba else None, nb.ctypes.data_as(_ffi.c_i32p) if neighbors else None))
+    return KnnSplitResult(label.astype(np.int64), P, nb, test_off, n_classes, k)
+
+
+def _draw_split(n_samples, train_percentage):
+    """One random split as (train indices, test indices): train_test_split over the sample indices consumes NumPy's
+    global state exactly as the reference's train_test_split(X, y, ...) (:648-649) does, and X[train], X[test], y[test]
+    are its arrays in its row order."""
+    from sklearn.model_selection import train_test_split
+    return train_test_split(np.arange(n_samples), test_size=1 - train_percentage)
+
+
+def evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
+                        train_percentage=0.90, smote=False):
+    """Picks the classifier parameter with the best cross-validated accuracy (parameter_mode 0) or macro F1 (1)
+    (reference :576-771): for every value, n_exp random splits (n_exp = -1: int(50000 / n_samples) + 1), each with its own
+    StandardScaler; with list_of_ids the n_exp GroupShuffleSplit(train_size=.8) splits are drawn once and shared by every value.
+    "knn": a kNN has no fit, and nothing but the splits draws from NumPy's global state, so ALL splits are drawn up front in
+    the reference's order (parameter-major), a scaler is fitted per split on the host and ONE knn_split_predict launch
+    classifies every test vector of the sweep against index lists over the one resident sample matrix.
+    The five scikit-learn types: per (value, experiment) split -> scaler -> scikit-learn fit in the reference's order (the
+    fits draw from the same global state); the test rows of each fitted model are scored by the device models in one
+    launch per model (predict).  The fits dominate: the launch removes the per-vector predict loop and nothing else.
+    Confusion matrices, the missing-class repair, precision / recall / F1 / accuracy, the printed table and the return value
+    (params[first arg-max]) are the reference's, on the host.  smote=True raises NotImplementedError."""
+    return evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids, n_exp,
+                                    train_percentage, smote)[0]
+
+
+def evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
+                             train_percentage=0.90, smote=False):
+    """evaluate_classifier, returning (the chosen parameter, the confusion matrix of every parameter value, the predictions
+    [parameter][experiment] of every split's test rows)."""
+    if smote:
+        raise NotImplementedError("smote=True: imbalanced-learn's SMOTE makes training rows that are no rows of the sample "
+                                  "matrix; this package does not resample")
+    if classifier_name not in _CLASSIFIER_TYPES:
+        raise NotImplementedError("classifier %r: one of %s" % (classifier_name, ", ".join(_CLASSIFIER_TYPES)))
+    import sklearn.metrics
+    from sklearn.preprocessing import StandardScaler
+    X, y = features_to_matrix(features)
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 2 or len(class_names) != len(features):
+        raise ValueError("%d feature matrices stacked to shape %s for %d class names" % (len(features), X.shape, len(class_names)))
+    n_classes = len(features)
+    n_samples_total = X.shape[0]
+    if n_exp == -1:
+        n_exp = int(50000 / n_samples_total) + 1
+    if list_of_ids:
+        from sklearn.model_selection import GroupShuffleSplit
+        shared = [(tr, te) for tr, te in GroupShuffleSplit(n_splits=n_exp, train_size=.8).split(X, y, list_of_ids)]
+
+    # splits (and, but for kNN, fits) in the reference's order; predictions [parameter][experiment]
+    splits, predictions = [], []
+    for C_param in params:
+        splits.append([])
+        predictions.append([])
+        for e in range(n_exp):
+            print("Param = {0:.5f} - classifier Evaluation Experiment {1:d} of {2:d}".format(C_param, e + 1, n_exp))
+            train_idx, test_idx = shared[e] if list_of_ids else _draw_split(n_samples_total, train_percentage)
+            scaler = StandardScaler().fit(X[train_idx])
+            splits[-1].append((train_idx, test_idx, scaler.mean_, scaler.scale_))
+            if classifier_name != "knn":
+                classifier = _train_classifier(scaler.transform(X[train_idx]), y[train_idx], classifier_name, C_param)
+                predictions[-1].append(list(predict(classifier, classifier_name, X[test_idx].T, scaler.mean_, scaler.scale_)[0])
+                                       if len(test_idx) else [])
+    if classifier_name == "knn":
+        jobs = [(tr, te, mean, scale, int(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
+        res = knn_split_predict(X, y, jobs)
+        predictions = [[list(res.job(i * n_exp + e)[0]) for e in range(n_exp)] for i in range(len(splits))]
+
+    ac_all, f1_all, f1_std_all, pre_all, rec_all, f1_classes_all, cms_all = [], [], [], [], [], [], []
+    y_flat = np.asarray(y).reshape(-1)
+    for row, preds in zip(splits, predictions):
+        cm = np.zeros((n_classes, n_classes))
+        f1_per_exp = []
+        for (train_idx, test_idx, _, _), y_pred in zip(row, preds):
+            y_test = y[test_idx]
+            cmt = sklearn.metrics.confusion_matrix(y_test, y_pred)
+            f1_per_exp.append(sklearn.metrics.f1_score(y_test, y_pred, average='macro'))
+            if cmt.size != cm.size:             # a class in neither the test labels nor the predictions: its row and column
+                missing = set(y_flat).difference(set(y_test.tolist() + y_pred))
+                missing = [int(c) for c in list(missing)]
+                for c in missing:
+                    cmt = np.insert(cmt, c, 0, axis=0)
+                for c in missing:
+                    cmt = np.insert(cmt, c, 0, axis=1)
+            cm = cm + cmt
+        cm = cm + 0.0000000010
+        rec = np.array([cm[c, c] / np.sum(cm[c, :]) for c in range(cm.shape[0])])
+        pre = np.array([cm[c, c] / np.sum(cm[:, c]) for c in range(cm.shape[0])])
+        f1 = 2 * rec * pre / (rec + pre)
+        pre_all.append(pre)
+        rec_all.append(rec)
+        f1_classes_all.append(f1)
+        ac_all.append(np.sum(np.diagonal(cm)) / np.sum(cm))
+        cms_all.append(cm)
+        f1_all.append(np.mean(f1))
+        f1_std_all.append(np.std(f1_per_exp))
+
+    print("\t\t", end="")
+    for i, c in enumerate(class_names):
+        print("{0:s}\t\t".format(c) if i == len(class_names) - 1 else "{0:s}\t\t\t".format(c), end="")
+    print("OVERALL")
+    print("\tC" + "\tPRE\tREC\tf1" * len(class_names) + "\t{0:s}\t{1:s}".format("ACC", "f1"))
+    best_ac_ind = np.argmax(ac_all)
+    best_f1_ind = np.argmax(f1_all)
+    for i in range(len(pre_all)):
+        line = "\t{0:.3f}".format(params[i])
+        for c in range(len(pre_all[i])):
+            line += "\t{0:.1f}\t{1:.1f}\t{2:.1f}".format(100.0 * pre_all[i][c], 100.0 * rec_all[i][c], 100.0 * f1_classes_all[i][c])
+        line += "\t{0:.1f}\t{1:.1f}".format(100.0 * ac_all[i], 100.0 * f1_all[i])
+        if i == best_f1_ind:
+            line += "\t best f1"
+        if i == best_ac_ind:
+            line += "\t best Acc"
+        print(line)
+    if parameter_mode == 0:
+        print("Confusion Matrix:")
+        print_confusion_matrix(cms_all[best_ac_ind], class_names)
+        return params[best_ac_ind], cms_all, predictions
+    elif parameter_mode == 1:
+        print("Confusion Matrix:")
+        print_confusion_matrix(cms_all[best_f1_ind], class_names)
+        print(f"Best macro f1 {100 * f1_all[best_f1_ind]:.1f}")
+        print(f"Best macro f1 std {100 * f1_std_all[best_f1_ind]:.1f}")
+        return params[best_f1_ind], cms_all, predictions
+    return None, cms_all, predictions
+
+
+def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
+                               compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False):
+    """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
+    :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
+    evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
+    reference's format -- "knn": eleven pickles in model_name (load_model_knn); otherwise the pickled classifier in model_name
+    and model_name + "MEANS" (load_model).  use_smote=True raises NotImplementedError."""
+    if use_smote:
+        raise NotImplementedError("use_smote=True: this package does not resample (see evaluate_classifier)")
+    from sklearn.preprocessing import StandardScaler
+    features, class_names, file_names = aF.multiple_directory_feature_extraction(paths, mid_window, mid_step, short_window,
+                                                                                 short_step, compute_beat=compute_beat)
+    file_names = [name for names in file_names for name in names]
+    list_of_ids = [dict_of_ids[name] for name in file_names] if dict_of_ids else None
+    if len(features) == 0:
+        print("trainSVM_feature ERROR: No data found in any input folder!")
+        return
+    for i, feat in enumerate(features):
+        if len(feat) == 0:
+            print("trainSVM_feature ERROR: " + paths[i] + " folder is empty or non-existing!")
+            return
+    if classifier_type in _SVM_TYPES:
+        classifier_par = np.array([0.001, 0.01, 0.5, 1.0, 5.0, 10.0, 20.0])
+    elif classifier_type == "knn":
+        classifier_par = np.array([1, 3, 5, 7, 9, 11, 13, 15])
+    elif classifier_type in _FOREST_TYPES:
+        classifier_par = np.array([10, 25, 50, 100, 200, 500])
+    else:
+        raise NotImplementedError("classifier %r: one of %s" % (classifier_type, ", ".join(_CLASSIFIER_TYPES)))
+    kept = []
+    for feat in features:
+        if feat.ndim == 1:                      # a class of one sample
+            feat = feat.reshape((1, feat.shape[0]))
+        rows = []
+        for row in feat:
+            if np.isnan(row).any() or np.isinf(row).any():
+                print("NaN Found! Feature vector not used for training")
+            else:
+                rows.append(row.tolist())
+        kept.append(np.array(rows))
+    features = kept
+    best_param = evaluate_classifier(features, class_names, classifier_type, classifier_par, 1, list_of_ids, n_exp=-1,
+                                     train_percentage=train_percentage, smote=use_smote)
+    print("Selected params: {0:.5f}".format(best_param))
+    features, labels = features_to_matrix(features)
+    scaler = StandardScaler()
+    features = scaler.fit_transform(features)
+    mean = scaler.mean_.tolist()
+    std = scaler.scale_.tolist()
+    if classifier_type == "knn":
+        save_parameters(model_name, features.tolist(), labels.tolist(), mean, std, class_names, best_param, mid_window, mid_step,
+                        short_window, short_step, compute_beat)
+    else:
+        classifier = _train_classifier(features, labels, classifier_type, best_param)
+        with open(model_name, "wb") as fid:
+            cPickle.dump(classifier, fid)
+        save_parameters(model_name + "MEANS", mean, std, class_names, mid_window, mid_step, short_window, short_step, compute_beat)
 
 
 def _forest_regressor(model):

@@ -30,5 +30,45 @@ int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_v
     });
 }
 
+template <int K>
+static int knn_split_at(const knn::KnnSplitDev &m, long long n_blocks, int *d_label, double *d_proba, int *d_neighbors,
+                        hipStream_t stream) {
+    const int pitch = (m.n_dims + knn::kGroupLanes - 1) / knn::kGroupLanes * knn::kGroupLanes;
+    const size_t lds = (size_t)knn::kTile * pitch * sizeof(double);
+    hipLaunchKernelGGL(knn::knn_split_kernel<K>, dim3((unsigned)n_blocks), dim3(knn::kThreads), lds, stream, m, d_label, d_proba,
+                       d_neighbors);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int knn_split_k_launch(int k_max) {
+    for (int K : knn::kSplitKs)
+        if (k_max >= 1 && k_max <= K) return K;
+    return 0;
+}
+
+int knn_split(const knn::KnnSplitDev &m, long long n_blocks, int k_max, int *d_label, double *d_proba, int *d_neighbors,
+              hipStream_t stream) {
+    if (m.n_dims < 1 || m.n_dims > knn::kMaxDims || m.max_classes < 1 || m.max_classes > knn::kMaxClasses || n_blocks < 1 ||
+        n_blocks > 0x7fffffffLL)
+        return -1;
+    switch (knn_split_k_launch(k_max)) {
+    case 1: return knn_split_at<1>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    case 2: return knn_split_at<2>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    case 4: return knn_split_at<4>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    case 8: return knn_split_at<8>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    case 16: return knn_split_at<16>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    case 32: return knn_split_at<32>(m, n_blocks, d_label, d_proba, d_neighbors, stream);
+    }
+    return -1;
+}
+
+void knn_split_geometry(int out10[10]) {
+    out10[0] = knn::kQueriesPerBlock;
+    out10[1] = knn::kTile;
+    out10[2] = knn::kGroupLanes;
+    out10[3] = (int)(sizeof(knn::kSplitKs) / sizeof(knn::kSplitKs[0]));
+    for (int i = 0; i < 6; ++i) out10[4 + i] = knn::kSplitKs[i];
+}
+
 }  // namespace launch
 }  // namespace paa

@@ -51,6 +51,23 @@ struct KnnDev {
     const int *labels;        // [n_train] class index of every row (a value outside 0..n_classes-1 votes for no class)
     int n_train, n_dims, n_classes, k;
 };
+// a sweep of kNN jobs over ONE sample matrix (audioTrainTest.evaluate_classifier's splits): job j trains on the rows
+// train_idx[train_off[j] .. train_off[j + 1] - 1] of X and classifies the rows test_idx[test_off[j] .. test_off[j + 1] - 1], both
+// after its own (x - mean_j) / scale_j, with its own k_j and n_classes_j.  Device pointers
+struct SplitBlock {
+    int job, first;           // a workgroup's job and the position in that job's test list of its first query
+};
+struct KnnSplitDev {
+    const double *X;          // [n_samples][n_dims] every sample, row-major
+    const int *labels;        // [n_samples] class index of every sample (a value outside 0..n_classes_j-1 votes for no class)
+    const long long *train_off, *test_off;    // [n_jobs + 1], from 0
+    const int *train_idx, *test_idx;          // sample indices, job after job
+    const double *mean, *scale;               // [n_jobs][n_dims]
+    const int *k, *n_classes;                 // [n_jobs]
+    const SplitBlock *blocks;                 // [n_blocks] host-built grid
+    int n_dims, max_classes;
+};
+constexpr int kSplitKs[] = {1, 2, 4, 8, 16, 32};      // the instances of knn_split_kernel: a sweep runs at the smallest >= its largest k
 }  // namespace knn
 namespace forest {
 constexpr int kMaxClasses = 64;
@@ -127,6 +144,16 @@ void svr_geometry(int out4[4]);
 // P [n_vec][n_classes] and, when d_neighbors is not null, the k neighbour indices [n_vec][k] in ascending (d^2, index))
 int knn(const knn::KnnDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
         int *d_label, double *d_proba, int *d_neighbors, hipStream_t stream);
+// kernels_knn.hpp: a sweep of kNN jobs over one sample matrix (one kernel, n_blocks workgroups of the host-built table
+// m.blocks; k_max: the largest k of the sweep): labels [Q], P [Q][max_classes] when d_proba is not null (zeros at and beyond a
+// job's n_classes), the neighbours' train-list positions [Q][k_launch] when d_neighbors is not null (-1 past a job's k or
+// train list), Q test vectors in job order then test-list order, in ascending (d^2, train-list position)
+int knn_split(const knn::KnnSplitDev &m, long long n_blocks, int k_max, int *d_label, double *d_proba, int *d_neighbors,
+              hipStream_t stream);
+// ... the instance a sweep with that largest k runs at (0: none), and the geometry for tests that aim at its edges: queries per
+// workgroup, training rows per LDS tile, rows per step (= lanes per query), the number of K instances and the instances
+int knn_split_k_launch(int k_max);
+void knn_split_geometry(int out10[10]);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
 // two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
 // infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the

@@ -6,6 +6,8 @@
     python scripts/bench_classify.py                       # GPU: SVC and kNN kernel rates per shipped model, 1 h clip end
                                                            # to end
     python scripts/bench_classify.py --forest              # GPU: tree-ensemble rates per model shape, 1 h clip end to end
+    python scripts/bench_classify.py --train               # GPU: evaluate_classifier("knn"), the split sweep in one launch against
+                                                           # the per-split loop of paa_knn_create / predict / destroy (DESIGN K14)
     python scripts/bench_classify.py --reference-loop DIR  # host: the reference's per-window loops (SVM: scikit-learn;
                                                            # kNN: NumPy + SciPy) (DIR = pyAudioAnalysis/data/models)
 
@@ -344,6 +346,103 @@ def diar(args):
     return out
 
 
+def train(args):
+    """evaluate_classifier("knn") at 5 000 x 136, 8 classes, k = 1 .. 15, n_exp = -1 (11 experiments: 88 splits), 90 % training:
+    (a) paa_knn_splits_f64 alone on the 88 jobs (one upload of X, one launch); (b) the same jobs as a loop of paa_knn_create +
+    paa_knn_predict_f64 + paa_knn_destroy over host-standardised training rows (what the library could do before); (c)
+    evaluate_classifier host to host; and one scikit-learn type with the share of its fits.  Wall time around the synchronous
+    calls (copies included), the events of paa_timer_* beside it; medians of --train-reps warm calls."""
+    import contextlib
+    import ctypes as C
+    import io
+    import train_ref
+    from sklearn.preprocessing import StandardScaler
+    from pyaudioanalysis_amd import _ffi, audioTrainTest
+    _ffi.init(0)
+    lib = _ffi.lib()
+    feats = train_ref.bench_features()
+    names = ["c%d" % c for c in range(len(feats))]
+    X, y = train_ref.features_to_matrix(feats)
+    X = np.ascontiguousarray(X)
+    n_samples, n_dims = X.shape
+    params = np.array(train_ref.KNN_PARAMS)
+    n_exp = int(50000 / n_samples) + 1
+    np.random.seed(7)
+    jobs = []
+    for k in params:
+        for _ in range(n_exp):
+            tr, te = audioTrainTest._draw_split(n_samples, 0.9)
+            sc = StandardScaler().fit(X[tr])
+            jobs.append((tr, te, sc.mean_, sc.scale_, int(k)))
+    qpb, tile, step, instances = audioTrainTest.knn_split_geometry()
+    out = {"what": "evaluate_classifier('knn'): the split sweep (scripts/bench_classify.py --train)", "samples": n_samples, "dims": n_dims,
+           "classes": len(feats), "params": params.tolist(), "n_exp": n_exp, "jobs": len(jobs), "train_percentage": 0.9,
+           "queries": int(sum(len(j[1]) for j in jobs)), "train_rows_per_job": int(len(jobs[0][0])),
+           "k_instance": int(min(K for K in instances if K >= params.max())),
+           "grid_workgroups": int(sum((len(j[1]) + qpb - 1) // qpb for j in jobs)), "threads_per_workgroup": 128,
+           "library": os.environ.get("PAA_HIP_LIBRARY", "default"), "reps": args.train_reps}
+    out["fp64_flop"] = 3.0 * sum(len(j[0]) * len(j[1]) for j in jobs) * n_dims
+    out["bytes_uploaded_sweep"] = int(X.nbytes + 4 * sum(len(j[0]) + len(j[1]) for j in jobs) + 16 * n_dims * len(jobs))
+    out["bytes_uploaded_loop"] = int(sum(8 * n_dims * (len(j[0]) + len(j[1])) + 4 * len(j[0]) for j in jobs))
+
+    def both(fn):
+        return {"wall_s": median_time(fn, args.train_reps), "events_s": event_time(fn, args.train_reps)}
+
+    # (a) the new entry alone
+    res = audioTrainTest.knn_split_predict(X, y, jobs)
+    out["a_split_sweep"] = both(lambda: audioTrainTest.knn_split_predict(X, y, jobs))
+    out["a_split_sweep"]["note"] = "knn_split_predict: the index lists are concatenated on the host inside the timed call"
+
+    # (b) the loop the library could run before: one uploaded model per split
+    lab32 = y.astype(np.int32)
+    models = [(np.ascontiguousarray((X[tr] - mean) / scale), np.ascontiguousarray(lab32[tr]), np.ascontiguousarray(X[te].T), mean, scale, k,
+               int(np.unique(y[tr]).shape[0])) for tr, te, mean, scale, k in jobs]
+    loop_labels = []
+
+    def loop():
+        loop_labels.clear()
+        for T, lab, Q, mean, scale, k, n_classes in models:
+            h = C.c_void_p()
+            _ffi.check(lib.paa_knn_create(_ffi.as_f64p(T), lab.ctypes.data_as(_ffi.c_i32p), T.shape[0], n_dims, n_classes, k, C.byref(h)))
+            idx = np.empty(Q.shape[1], dtype=np.int32)
+            P = np.empty((Q.shape[1], n_classes))
+            _ffi.check(lib.paa_knn_predict_f64(h, _ffi.as_f64p(Q), n_dims, Q.shape[1], Q.shape[1], _ffi.as_f64p(mean), _ffi.as_f64p(scale),
+                                               idx.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(P), None))
+            _ffi.check(lib.paa_knn_destroy(h))
+            loop_labels.append(idx)
+    out["b_model_loop"] = both(loop)
+    out["same_labels"] = bool(np.array_equal(np.concatenate(loop_labels), res.label))
+    out["loop_over_sweep"] = out["b_model_loop"]["wall_s"] / out["a_split_sweep"]["wall_s"]
+
+    # (c) evaluate_classifier host to host
+    def evaluate(kind, p, n):
+        np.random.seed(7)
+        with contextlib.redirect_stdout(io.StringIO()):
+            return audioTrainTest.evaluate_classifier(feats, names, kind, p, 1, None, n_exp=n, train_percentage=0.9)
+    out["c_evaluate_classifier_knn"] = {"wall_s": median_time(lambda: evaluate("knn", params, -1), args.train_reps), "best": int(evaluate("knn", params, -1))}
+
+    # one scikit-learn type: where its time goes
+    fit_s = [0.0]
+    real = audioTrainTest._train_classifier
+
+    def timed_fit(*a):
+        t0 = time.perf_counter()
+        m = real(*a)
+        fit_s[0] += time.perf_counter() - t0
+        return m
+    audioTrainTest._train_classifier = timed_fit
+    try:
+        evaluate("randomforest", np.array([25, 100]), 2)
+        fit_s[0] = 0.0
+        t0 = time.perf_counter()
+        evaluate("randomforest", np.array([25, 100]), 2)
+        total = time.perf_counter() - t0
+    finally:
+        audioTrainTest._train_classifier = real
+    out["randomforest_25_100_n_exp_2"] = {"wall_s": total, "fits_s": fit_s[0], "fits_share": fit_s[0] / total}
+    return out
+
+
 def reference_loop(args):
     import pickle
     import warnings
@@ -391,11 +490,13 @@ def main():
     ap.add_argument("--forest", action="store_true", help="the tree-ensemble shapes only")
     ap.add_argument("--hmm", action="store_true", help="the HMM segmenter only")
     ap.add_argument("--diar", action="store_true", help="speaker diarization only")
+    ap.add_argument("--train", action="store_true", help="evaluate_classifier('knn'): the split sweep in one launch")
+    ap.add_argument("--train-reps", type=int, default=10)
     ap.add_argument("--diar-windows", type=int, default=36000)
     ap.add_argument("--diar-reference-windows", type=int, default=6000)
     args = ap.parse_args()
     print(json.dumps(reference_loop(args) if args.reference_loop else forest(args) if args.forest else
-                     hmm(args) if args.hmm else diar(args) if args.diar else gpu(args)))
+                     hmm(args) if args.hmm else diar(args) if args.diar else train(args) if args.train else gpu(args)))
 
 
 if __name__ == "__main__":
