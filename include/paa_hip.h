@@ -501,6 +501,12 @@ int paa_comm_barrier(void);
 int paa_debug_mel_bank(double fs, int num_fft, double *out_dense);
 int paa_debug_dct(double *out_13x40);
 int paa_debug_chroma(double fs, int num_fft, int capacity, int32_t *src, double *weight, int32_t *slot);
+/* the clip constants of a plan (csrc/device_common.hpp: ClipNorm): runs the plan's statistics kernel and clip_params_kernel on
+ * d_packed -- also for plans whose feature kernel folds the partials itself -- and waits.  out[0..9] = {samples per statistics
+ * chunk, CUs of the device, clips, statistics chunks, norms_inline, sample kind, 0, 0, 0, 0}; then ten doubles per clip: mean, inv,
+ * mu, delta_mu, m_int, zb, mu_whole, dc_shift, stat_first, stat_count.  capacity (doubles) >= 10 (clips + 1).  A later
+ * paa_plan_execute of the plan computes what it would have computed without this call; needs a device                       */
+int paa_debug_plan_clip_norms(paa_plan_t *plan, const void *d_packed, double *out, int64_t capacity);
 /* per-phase cycle totals of the fast kernel (diagnostic builds with -DPAA_F800_TIMING; zeros otherwise) */
 int paa_debug_wave_trace(uint64_t *out, int max_waves);
 int paa_debug_lane_peak(void);     /* most host-buffer calls in flight at once since the last query */

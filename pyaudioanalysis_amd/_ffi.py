@@ -163,6 +163,7 @@ _SIGNATURES = {
     "paa_debug_mel_bank": (C.c_int, [C.c_double, C.c_int, c_f64p]),
     "paa_debug_dct": (C.c_int, [c_f64p]),
     "paa_debug_chroma": (C.c_int, [C.c_double, C.c_int, C.c_int, c_i32p, c_f64p, c_i32p]),
+    "paa_debug_plan_clip_norms": (C.c_int, [C.c_void_p, C.c_void_p, c_f64p, C.c_int64]),
     "paa_debug_phase_cycles": (C.c_int, [C.POINTER(C.c_uint64)]),
     "paa_debug_wave_trace": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "paa_debug_lane_peak": (C.c_int, []),

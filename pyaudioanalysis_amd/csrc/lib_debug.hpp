@@ -48,6 +48,34 @@ extern "C" int paa_debug_wave_trace(uint64_t *out, int max_waves) {
 #endif
 }
 
+// The clip constants of a plan as clip_params_kernel forms them: the plan's statistics kernel, then clip_params_kernel for the
+// plan's sample type -- also for the plans whose feature kernel folds the partials itself (norms_inline) -- on the caller's lane
+// stream, then a wait.  out[0..9] = {stat_chunk, num_cu, clips, statistics chunks, norms_inline, sample kind, 0, 0, 0, 0}, then one
+// row of ten doubles per clip: mean, inv, mu, delta_mu, m_int, zb, mu_whole, dc_shift, stat_first, stat_count.  Nothing a later
+// paa_plan_execute reads is left changed: it forms the partials (and, where its kernel reads them, the constants) again.
+extern "C" int paa_debug_plan_clip_norms(paa_plan_t *plan, const void *d_packed, double *out, int64_t capacity) {
+    if (!plan || !d_packed || !out) return fail(PAA_ERR_ARG, "null plan / buffer");
+    if (capacity < 10 * (plan->n_clips + 1))
+        return fail(PAA_ERR_ARG, "capacity %lld < %lld doubles", (long long)capacity, 10LL * (plan->n_clips + 1));
+    { const int rc_init = ensure_init(); if (rc_init) return rc_init; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    const int rc = launch_stats(plan, d_packed, true);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(cs()));
+    std::vector<ClipNorm> nm((size_t)plan->n_clips);
+    HIP_TRY(hipMemcpy(nm.data(), plan->d_norms, nm.size() * sizeof(ClipNorm), hipMemcpyDeviceToHost));
+    const double head[10] = {(double)plan->stat_chunk, (double)g_num_cu, (double)plan->n_clips, (double)plan->n_chunks,
+                             (double)plan->P.norms_inline, (double)plan->sample_kind, 0.0, 0.0, 0.0, 0.0};
+    std::copy(head, head + 10, out);
+    for (long long c = 0; c < plan->n_clips; ++c) {
+        const ClipNorm &n = nm[(size_t)c];
+        const double row[10] = {n.mean, n.inv, n.mu, n.delta_mu, (double)n.m_int, (double)n.zb, (double)n.mu_whole, n.dc_shift,
+                                (double)plan->clips[c].stat_first, (double)plan->clips[c].stat_count};
+        std::copy(row, row + 10, out + 10 * (c + 1));
+    }
+    return PAA_OK;
+}
+
 extern "C" int paa_debug_mel_bank(double fs, int num_fft, double *out_dense) {
     if (!out_dense || num_fft < 1) return fail(PAA_ERR_ARG, "bad argument");
     MelTable t;

@@ -201,7 +201,8 @@ static void plan_free_synced(paa_plan *p) {
     plan_free(p);
 }
 
-static int launch_stats(paa_plan *p, const void *d_packed) {
+// force_params: clip_params_kernel runs whatever norms_inline says (paa_debug_plan_clip_norms reads its output)
+static int launch_stats(paa_plan *p, const void *d_packed, bool force_params = false) {
     if (p->n_chunks > 0) {
         if (p->sample_kind == 0)
             hipLaunchKernelGGL(clip_stats_i16_kernel, dim3((unsigned)p->n_chunks), dim3(256), 0, cs(),
@@ -217,7 +218,7 @@ static int launch_stats(paa_plan *p, const void *d_packed) {
                                (double *)p->d_pmax);
     }
     const unsigned gb = (unsigned)p->n_clips;
-    if (p->P.norms_inline) {
+    if (p->P.norms_inline && !force_params) {
         HIP_TRY(hipGetLastError());
         return PAA_OK;
     }
