@@ -313,6 +313,61 @@ int paa_knn_splits_f64(const double *X, int64_t n_samples, int n_dims, const int
 /* tests: out10 = queries per workgroup, training rows per LDS tile, rows per step, the number of K instances, the instances */
 int paa_debug_knn_split_geometry(int32_t *out10);
 
+/* ---- the SVM half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700 with train_svm :132-155) ---------------------
+ * For "svm" / "svm_rbf" evaluate_classifier fits sklearn.svm.SVC(C, kernel, probability=True, gamma='auto') once per split and reads
+ * only the vote labels of predict(); libsvm fits every pair of classes (svm.cpp: svm_train -> svm_train_one -> solve_c_svc ->
+ * Solver::Solve), and with probability=True five more times per pair for Platt's cross-validation, which the sweep never reads.
+ * Here a TASK is one binary C-SVC dual problem over rows of ONE resident sample matrix, one workgroup solves one task with
+ * libsvm's Solver without shrinking in FP64 throughout (libsvm keeps its kernel cache in float32, so agreement with scikit-learn is
+ * bounded by the stopping tolerance, not bit-exact), and all tasks of a call run side by side.
+ *
+ * paa_smo_tasks_f64 -- the solver alone (Solver::Solve, select_working_set, calculate_rho):
+ *   X [n_samples][n_dims]    every sample, row-major (1 <= n_dims <= 256, 1 <= n_samples < 2^31)
+ *   task_off [n_tasks + 1], task_idx / task_sign [task_off[n_tasks]]   task t owns the rows task_idx[task_off[t] .. task_off[t+1]-1]
+ *                            of X with the signs task_sign[..] (+1: the first class of the pair, -1: the second); 1..8192 rows
+ *   mean, std [n_tasks][n_dims]   task t's standardisation, (x - mean_t) / std_t with an IEEE division on the load path
+ *   C, gamma [n_tasks]       C > 0; gamma > 0 is read for kernel_type 2 only
+ *   kernel_type              0: K = z_t . z_s;  2: K = exp(-gamma |z_t - z_s|^2)  (libsvm's LINEAR / RBF)
+ *   eps > 0                  stop when Gmax + Gmax2 < eps (SVC's tol);  max_iter >= 1 (libsvm's floor is 10^7)
+ *   iters_per_launch         iterations a task may run in one kernel launch (0: the default, 1024); the state lives in device
+ *                            memory between launches, the host compacts the unfinished tasks and launches again.  No launch is
+ *                            unbounded, and every output is bit-identical for any value, for a task alone or in any batch
+ * Outputs: alpha_y [task_off[n_tasks]] = alpha_t y_t; per task rho, iterations, gap (the last Gmax + Gmax2; 0 when an index set was
+ * empty) and status (2: converged, 3: max_iter reached -- outputs are those of the last iterate, finite); n_launches may be NULL.
+ * The decision value of a standardised z is sum_t alpha_t y_t K(z_t, z) - rho; positive votes for the first class.
+ *
+ * paa_svc_fit_splits_f64 -- the sweep, in the job form of paa_knn_splits_f64 (labels, train_off / train_idx, test_off / test_idx,
+ * mean / std [n_jobs][n_dims]) plus C, gamma [n_jobs].  The host builds job j's tasks from the classes PRESENT in its training
+ * list in ascending order: per pair (a, b), a < b, row-major, the rows of a in train-list order, then those of b.  Every test
+ * row gets the decision value of each pair over the task's rows with alpha != 0, libsvm's vote (dec > 0: a, else b) and the
+ * first class with the most votes.
+ *   label_out [Q]            the class INDEX (a value of `labels`), Q = test_off[n_jobs] rows in job order then test-list order
+ *   dec_out [Q][max_pairs]   (may be NULL) the decision values, zeros past a job's pairs; max_pairs >= every job's pair count
+ *   task_iterations, task_status, task_n_sv [n_tasks]   (each may be NULL) per task in job order then pair order; n_tasks must then
+ *                            equal the number of tasks the jobs make;  n_launches (may be NULL)
+ * PAA_ERR_ARG, with a message and before the device is touched: a null pointer (other than the optional outputs), offsets that do
+ * not begin at 0 or decrease, an index outside 0..n_samples-1, a sign other than +-1, a negative training label, n_dims < 1,
+ * C <= 0, gamma <= 0 (RBF), eps <= 0, kernel_type other than 0 / 2, max_iter < 1, an empty task, a job whose training list holds
+ * fewer than two classes.  PAA_ERR_UNSUPPORTED, likewise before the device is touched: n_dims > 256 (PAA_SMO_MAX_DIMS), a task of
+ * more than 8192 rows (PAA_SMO_MAX_ROWS), a job with more than 64 classes.  An empty test list is legal.  Synchronous, host
+ * buffers in and out.  Not served: Platt probabilities (probability=True's second half), a model file, SVR.              */
+#define PAA_SMO_MAX_ROWS 8192
+#define PAA_SMO_MAX_DIMS 256
+#define PAA_SMO_CONVERGED 2
+#define PAA_SMO_NOT_CONVERGED 3
+int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
+                      const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std, const double *C,
+                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch, double *alpha_y,
+                      double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_launches);
+int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                           const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                           const double *mean, const double *std, const double *C, const double *gamma, int kernel_type,
+                           double eps, int max_iter, int iters_per_launch, int32_t *label_out, double *dec_out, int max_pairs,
+                           int n_tasks, int32_t *task_iterations, int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches);
+/* tests: out6 = threads per workgroup, lane groups, rows per task, test rows per scoring workgroup, default iterations per
+ * launch, dims                                                                                                        */
+int paa_debug_smo_geometry(int32_t *out6);
+
 /* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
  * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as
  * train_svm_regression makes them, audioTrainTest.py:222-226) for many feature vectors and many models at once: what

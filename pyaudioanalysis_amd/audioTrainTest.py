@@ -19,6 +19,7 @@ pyAudioAnalysis/audioTrainTest.py).
     evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, ...)   audioTrainTest.py:576-771
     extract_features_and_train(paths, ..., classifier_type, model_name, ...)                   audioTrainTest.py:236-361
     knn_split_predict(X, labels, jobs, proba=False, neighbors=False)   every kNN split of a sweep in one launch
+    svm_split_fit_predict(X, labels, jobs, kernel, ...), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -35,7 +36,10 @@ model given as arrays (ForestArrays) works without scikit-learn.  Unpickling an 
 scikit-learn exactly where the reference needs it (load_model).  Training stays with scikit-learn: evaluate_classifier / extract_features_and_train tune and train all six
 types; for "knn", which has no fit, the whole split sweep of evaluate_classifier is ONE launch over index lists into one
 resident sample matrix (knn_split_kernel through paa_knn_splits_f64); the five scikit-learn types gain only the removal of
-the per-vector predict loop.  smote / use_smote are refused (NotImplementedError).
+the per-vector predict loop -- by default.  With svm_fit="device" evaluate_classifier fits "svm" / "svm_rbf" on the GPU too:
+every pair of classes of every split is a binary C-SVC problem of smo_kernel (libsvm's solver without shrinking, FP64; no Platt
+cross-validation, whose probabilities the sweep never reads), all of them side by side (paa_svc_fit_splits_f64); the final
+fit of extract_features_and_train and its model file stay scikit-learn's.  smote / use_smote are refused (NotImplementedError).
 Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
 SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
 value of evaluate_regression -- scores every vector in one launch (kernels_svr.hpp through paa_svr_*: libsvm's decision value
@@ -926,6 +930,165 @@ def knn_split_predict(X, labels, jobs, proba=False, neighbors=False):
     return KnnSplitResult(label.astype(np.int64), P, nb, test_off, n_classes, k)
 
 
+def smo_geometry():
+    """(threads per workgroup, lane groups, rows per task, test rows per scoring workgroup, default iterations per launch,
+    dims) of the SMO solver and its scoring kernel (kernels_smo.hpp)."""
+    geo = np.zeros(6, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_debug_smo_geometry(geo.ctypes.data_as(_ffi.c_i32p)))
+    return tuple(int(v) for v in geo)
+
+
+SMO_CONVERGED, SMO_NOT_CONVERGED = 2, 3          # PAA_SMO_CONVERGED / PAA_SMO_NOT_CONVERGED
+
+
+def _warn_not_converged(status, max_iter):
+    """scikit-learn's warning for a libsvm fit that stopped at max_iter (its ConvergenceWarning when it is installed)."""
+    n = int(np.count_nonzero(np.asarray(status) == SMO_NOT_CONVERGED))
+    if not n:
+        return
+    import warnings
+    try:
+        from sklearn.exceptions import ConvergenceWarning as category
+    except ImportError:
+        category = UserWarning
+    warnings.warn("Solver terminated early (max_iter=%d) in %d of %d binary problems.  Consider pre-processing your data with "
+                  "StandardScaler or MinMaxScaler." % (max_iter, n, len(status)), category, stacklevel=3)
+
+
+class SmoResult:
+    """What smo_solve returns: alpha_y (a list of one array per task, alpha_t y_t in the task's row order), rho, iterations,
+    gap and status per task (SMO_CONVERGED / SMO_NOT_CONVERGED) and the number of kernel launches."""
+
+    def __init__(self, alpha_y, rho, iterations, gap, status, n_launches):
+        self.alpha_y, self.rho, self.iterations, self.gap, self.status, self.n_launches = alpha_y, rho, iterations, gap, status, n_launches
+
+
+def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0):
+    """Binary C-SVC dual problems over ONE sample matrix, all solved side by side (paa_smo_tasks_f64, smo_kernel: libsvm's
+    Solver without shrinking, FP64).  X [n_samples][n_dims]; a task is (rows, signs, mean, scale, C, gamma): the rows X[rows]
+    standardised as (x - mean) / scale, signs +1 (the first class) or -1, gamma read for kernel="rbf" only (None: 1 / n_dims).
+    iters_per_launch bounds one kernel launch (0: the library's default); results do not depend on it.  A task that stops at
+    max_iter has the status SMO_NOT_CONVERGED and a warning is issued, as scikit-learn does.  Returns an SmoResult."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    tasks = list(tasks)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("sample matrix of shape %s" % (X.shape,))
+    if not tasks:
+        raise ValueError("no tasks")
+    if kernel not in _KERNEL_TYPES:
+        raise NotImplementedError("SVM kernel %r: the GPU solver serves 'rbf' and 'linear'" % (kernel,))
+    n_samples, n_dims = X.shape
+    rows, signs, means, scales, Cs, gammas = [], [], [], [], [], []
+    for t, task in enumerate(tasks):
+        if len(task) != 6:
+            raise ValueError("task %d: (rows, signs, mean, scale, C, gamma) expected" % t)
+        r = _index_list(task[0], "row", t)
+        sg = np.asarray(task[1], dtype=np.float64).reshape(-1)
+        if sg.shape[0] != r.shape[0]:
+            raise ValueError("task %d: %d rows and %d signs" % (t, r.shape[0], sg.shape[0]))
+        mean, scale = _stats(task[2], task[3], n_dims)
+        rows.append(r)
+        signs.append(np.where(sg == 1, 1, np.where(sg == -1, -1, 0)).astype(np.int8))
+        means.append(mean)
+        scales.append(scale)
+        Cs.append(float(task[4]))
+        gammas.append(1.0 / n_dims if task[5] is None else float(task[5]))
+    off = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int64)
+    idx = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32)
+    sign = np.ascontiguousarray(np.concatenate(signs), dtype=np.int8)
+    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
+    C_arr, g_arr = np.array(Cs, dtype=np.float64), np.array(gammas, dtype=np.float64)
+    n_tasks, total = len(tasks), int(off[-1])
+    alpha_y, rho, gap = np.zeros(total), np.zeros(n_tasks), np.zeros(n_tasks)
+    iterations, status, launches = np.zeros(n_tasks, dtype=np.int32), np.zeros(n_tasks, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_smo_tasks_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, n_tasks, off.ctypes.data_as(_ffi.c_i64p), idx.ctypes.data_as(_ffi.c_i32p),
+        sign.ctypes.data_as(C.POINTER(C.c_int8)), _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr),
+        _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
+        iterations.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(gap), status.ctypes.data_as(_ffi.c_i32p),
+        launches.ctypes.data_as(_ffi.c_i32p)))
+    _warn_not_converged(status, int(max_iter))
+    return SmoResult([alpha_y[off[t]:off[t + 1]] for t in range(n_tasks)], rho, iterations, gap, status, int(launches[0]))
+
+
+class SvmSplitResult:
+    """What svm_split_fit_predict returns: label [Q] (class values as in `labels`), decision [Q][max_pairs] or None (zeros past
+    a job's pairs), test_off [n_jobs + 1], classes (per job the classes present in its training list, ascending), task_off
+    [n_jobs + 1] (job j owns the tasks task_off[j] .. task_off[j + 1] - 1, its pairs (a, b), a < b, row-major) and per task
+    iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel."""
+
+    def __init__(self, label, decision, test_off, classes, task_off, iterations, status, n_sv, n_launches):
+        self.label, self.decision, self.test_off, self.classes, self.task_off = label, decision, test_off, classes, task_off
+        self.iterations, self.status, self.n_sv, self.n_launches = iterations, status, n_sv, n_launches
+
+    def job(self, j):
+        """(labels, decision values [n_test][pairs_j] or None, iterations [pairs_j], status [pairs_j], n_sv [pairs_j]) of job j."""
+        a, b = int(self.test_off[j]), int(self.test_off[j + 1])
+        t0, t1 = int(self.task_off[j]), int(self.task_off[j + 1])
+        return (self.label[a:b], None if self.decision is None else self.decision[a:b, :t1 - t0], self.iterations[t0:t1],
+                self.status[t0:t1], self.n_sv[t0:t1])
+
+
+def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, decision=False, max_iter=10**7, iters_per_launch=0):
+    """SVC(C, kernel, gamma).fit(train).predict(test) for every job of a sweep over ONE sample matrix (paa_svc_fit_splits_f64:
+    every pair of the classes present in a job's training list is a binary problem of smo_kernel, all of them side by side;
+    then libsvm's one-against-one vote of every test row).  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the
+    training rows); a job is (train_idx, test_idx, mean, scale, C).  gamma=None is 1 / n_dims, the reference's gamma='auto'.
+    No probabilities are fitted: the sweep reads vote labels only.  Returns an SvmSplitResult."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    raw = np.asarray(labels).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or raw.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
+    jobs = list(jobs)
+    if not jobs:
+        raise ValueError("no jobs")
+    if kernel not in _KERNEL_TYPES:
+        raise NotImplementedError("SVM kernel %r: the GPU solver serves 'rbf' and 'linear'" % (kernel,))
+    n_samples, n_dims = X.shape
+    lab = np.full(n_samples, -1, dtype=np.int32)
+    if raw.dtype.kind in "biuf":
+        v = raw.astype(np.float64)
+        ok = (v == np.floor(v)) & (v >= 0) & (v < 2**31)
+        lab[ok] = v[ok].astype(np.int32)
+    train, test, means, scales, Cs, classes = [], [], [], [], [], []
+    for j, job in enumerate(jobs):
+        if len(job) != 5:
+            raise ValueError("job %d: (train_idx, test_idx, mean, scale, C) expected" % j)
+        tr, te = _index_list(job[0], "train", j), _index_list(job[1], "test", j)
+        mean, scale = _stats(job[2], job[3], n_dims)
+        train.append(tr)
+        test.append(te)
+        means.append(mean)
+        scales.append(scale)
+        Cs.append(float(job[4]))
+        inside = tr[(tr >= 0) & (tr < n_samples)]               # an index outside the matrix is the library's error to report
+        classes.append(np.unique(lab[inside]))
+    train_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in train])]).astype(np.int64)
+    test_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in test])]).astype(np.int64)
+    train_idx = np.ascontiguousarray(np.concatenate(train), dtype=np.int32)
+    test_idx = np.ascontiguousarray(np.concatenate(test), dtype=np.int32)
+    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
+    C_arr = np.array(Cs, dtype=np.float64)
+    g_arr = np.full(len(jobs), 1.0 / n_dims if gamma is None else float(gamma), dtype=np.float64)
+    pairs = [len(c) * (len(c) - 1) // 2 for c in classes]
+    task_off = np.concatenate([[0], np.cumsum(pairs)]).astype(np.int64)
+    n_tasks, max_pairs, Q = int(task_off[-1]), max(max(pairs), 1), int(test_off[-1])
+    label = np.zeros(Q, dtype=np.int32)
+    dec = np.zeros((Q, max_pairs), dtype=np.float64) if decision else None
+    iterations, status, n_sv = (np.zeros(max(n_tasks, 1), dtype=np.int32) for _ in range(3))
+    launches = np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_svc_fit_splits_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, lab.ctypes.data_as(_ffi.c_i32p), len(jobs), train_off.ctypes.data_as(_ffi.c_i64p),
+        train_idx.ctypes.data_as(_ffi.c_i32p), test_off.ctypes.data_as(_ffi.c_i64p), test_idx.ctypes.data_as(_ffi.c_i32p),
+        _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
+        int(max_iter), int(iters_per_launch), label.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(dec) if decision else None, max_pairs,
+        n_tasks, iterations.ctypes.data_as(_ffi.c_i32p), status.ctypes.data_as(_ffi.c_i32p), n_sv.ctypes.data_as(_ffi.c_i32p),
+        launches.ctypes.data_as(_ffi.c_i32p)))
+    iterations, status, n_sv = iterations[:n_tasks], status[:n_tasks], n_sv[:n_tasks]
+    _warn_not_converged(status, int(max_iter))
+    return SvmSplitResult(label.astype(np.int64), dec, test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
+
+
 def _draw_split(n_samples, train_percentage):
     """One random split as (train indices, test indices): train_test_split over the sample indices consumes NumPy's
     global state exactly as the reference's train_test_split(X, y, ...) (:648-649) does, and X[train], X[test], y[test]
@@ -935,7 +1098,7 @@ def _draw_split(n_samples, train_percentage):
 
 
 def evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                        train_percentage=0.90, smote=False):
+                        train_percentage=0.90, smote=False, *, svm_fit="sklearn"):
     """Picks the classifier parameter with the best cross-validated accuracy (parameter_mode 0) or macro F1 (1)
     (reference :576-771): for every value, n_exp random splits (n_exp = -1: int(50000 / n_samples) + 1), each with its own
     StandardScaler; with list_of_ids the n_exp GroupShuffleSplit(train_size=.8) splits are drawn once and shared by every value.
@@ -946,15 +1109,25 @@ def evaluate_classifier(features, class_names, classifier_name, params, paramete
     fits draw from the same global state); the test rows of each fitted model are scored by the device models in one
     launch per model (predict).  The fits dominate: the launch removes the per-vector predict loop and nothing else.
     Confusion matrices, the missing-class repair, precision / recall / F1 / accuracy, the printed table and the return value
-    (params[first arg-max]) are the reference's, on the host.  smote=True raises NotImplementedError."""
+    (params[first arg-max]) are the reference's, on the host.  smote=True raises NotImplementedError.
+    svm_fit="device" (keyword only; "svm" / "svm_rbf", any other type raises ValueError): as for kNN, ALL splits are drawn up
+    front in parameter-major order, a scaler is fitted per split on the host and ONE svm_split_fit_predict call fits every
+    pair of classes of every split on the GPU (libsvm's solver, no Platt cross-validation: the sweep reads vote labels only)
+    and classifies every test row.  The one visible difference to the default: scikit-learn's probabilistic fits draw a libsvm
+    seed from NumPy's global state between the splits, the device mode consumes that state for the splits only, so for one seed
+    the two modes see different splits.  svm_fit="sklearn" (the default) is the behaviour described above, untouched."""
     return evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids, n_exp,
-                                    train_percentage, smote)[0]
+                                    train_percentage, smote, svm_fit=svm_fit)[0]
 
 
 def evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                             train_percentage=0.90, smote=False):
+                             train_percentage=0.90, smote=False, *, svm_fit="sklearn"):
     """evaluate_classifier, returning (the chosen parameter, the confusion matrix of every parameter value, the predictions
     [parameter][experiment] of every split's test rows)."""
+    if svm_fit not in ("sklearn", "device"):
+        raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
+    if svm_fit == "device" and classifier_name not in _SVM_TYPES:
+        raise ValueError("svm_fit='device' serves the classifier types %s, not %r" % (" and ".join(_SVM_TYPES), classifier_name))
     if smote:
         raise NotImplementedError("smote=True: imbalanced-learn's SMOTE makes training rows that are no rows of the sample "
                                   "matrix; this package does not resample")
@@ -984,7 +1157,7 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
             train_idx, test_idx = shared[e] if list_of_ids else _draw_split(n_samples_total, train_percentage)
             scaler = StandardScaler().fit(X[train_idx])
             splits[-1].append((train_idx, test_idx, scaler.mean_, scaler.scale_))
-            if classifier_name != "knn":
+            if classifier_name != "knn" and svm_fit != "device":
                 classifier = _train_classifier(scaler.transform(X[train_idx]), y[train_idx], classifier_name, C_param)
                 predictions[-1].append(list(predict(classifier, classifier_name, X[test_idx].T, scaler.mean_, scaler.scale_)[0])
                                        if len(test_idx) else [])
@@ -992,6 +1165,10 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
         jobs = [(tr, te, mean, scale, int(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
         res = knn_split_predict(X, y, jobs)
         predictions = [[list(res.job(i * n_exp + e)[0]) for e in range(n_exp)] for i in range(len(splits))]
+    elif svm_fit == "device":
+        jobs = [(tr, te, mean, scale, float(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
+        res = svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
+        predictions = [[[y.dtype.type(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
 
     ac_all, f1_all, f1_std_all, pre_all, rec_all, f1_classes_all, cms_all = [], [], [], [], [], [], []
     y_flat = np.asarray(y).reshape(-1)
@@ -1053,12 +1230,16 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
 
 
 def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
-                               compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False):
+                               compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn"):
     """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
     :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
     evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
     reference's format -- "knn": eleven pickles in model_name (load_model_knn); otherwise the pickled classifier in model_name
-    and model_name + "MEANS" (load_model).  use_smote=True raises NotImplementedError."""
+    and model_name + "MEANS" (load_model).  use_smote=True raises NotImplementedError.  svm_fit (keyword only) goes to the tuning
+    step, evaluate_classifier, and nowhere else: the final fit and the model file stay scikit-learn's, because the file format
+    is a pickled SVC."""
+    if svm_fit not in ("sklearn", "device") or (svm_fit == "device" and classifier_type not in _SVM_TYPES):
+        raise ValueError("svm_fit=%r with the classifier type %r" % (svm_fit, classifier_type))
     if use_smote:
         raise NotImplementedError("use_smote=True: this package does not resample (see evaluate_classifier)")
     from sklearn.preprocessing import StandardScaler
@@ -1094,7 +1275,7 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
         kept.append(np.array(rows))
     features = kept
     best_param = evaluate_classifier(features, class_names, classifier_type, classifier_par, 1, list_of_ids, n_exp=-1,
-                                     train_percentage=train_percentage, smote=use_smote)
+                                     train_percentage=train_percentage, smote=use_smote, svm_fit=svm_fit)
     print("Selected params: {0:.5f}".format(best_param))
     features, labels = features_to_matrix(features)
     scaler = StandardScaler()

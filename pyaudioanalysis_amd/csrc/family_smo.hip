@@ -1,0 +1,43 @@
+// The batched SMO solver and the one-against-one vote of the SVM split sweep (kernels_smo.hpp: the SVM fits of
+// audioTrainTest.evaluate_classifier) -- own translation unit, see model_launch.hpp.
+#include "model_launch.hpp"
+#include "kernels_smo.hpp"
+
+namespace paa {
+namespace launch {
+
+static int raise_lds(const void *kernel, size_t lds) {
+    if (lds <= 32 * 1024) return 0;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -1;
+}
+
+int smo_step(const smo::SmoDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream) {
+    if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > smo::kMaxRows) return -2;
+    if (n_live < 1 || budget < 1) return -1;
+    const int pitch = (m.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
+    const size_t lds = ((size_t)4 * pitch + n_max) * sizeof(double);
+    if (raise_lds(reinterpret_cast<const void *>(&smo::smo_kernel), lds)) return -1;
+    hipLaunchKernelGGL(smo::smo_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), lds, stream, m, d_live, budget);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double *d_dec, hipStream_t stream) {
+    if (f.n_dims < 1 || f.n_dims > smo::kMaxDims || n_blocks < 1 || n_blocks > 0x7fffffffLL) return -1;
+    const int pitch = (f.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
+    const size_t lds = ((size_t)smo::kTile * pitch + smo::kTile) * sizeof(double);
+    if (raise_lds(reinterpret_cast<const void *>(&smo::svc_pairs_kernel), lds)) return -1;
+    hipLaunchKernelGGL(smo::svc_pairs_kernel, dim3((unsigned)n_blocks), dim3(smo::kThreads), lds, stream, f, d_label, d_dec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+void smo_geometry(int out6[6]) {
+    out6[0] = smo::kThreads;
+    out6[1] = smo::kGroups;
+    out6[2] = smo::kMaxRows;
+    out6[3] = smo::kQueriesPerBlock;
+    out6[4] = smo::kDefaultItersPerLaunch;
+    out6[5] = smo::kMaxDims;
+}
+
+}  // namespace launch
+}  // namespace paa

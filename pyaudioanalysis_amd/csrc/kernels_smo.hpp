@@ -1,0 +1,328 @@
+// The SVM fits of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700 with train_svm :132-155) as a batch of binary
+// C-SVC dual problems: libsvm's Solver (svm.cpp: Solve, select_working_set, calculate_rho) without shrinking, FP64 throughout,
+// one workgroup per TASK, and the one-against-one vote of svm_predict over the fitted tasks.
+// A task is a list of rows of the resident sample matrix X, a sign per row, the mean / scale of its job (rows are
+// standardised on the load path, (x - mean) / scale with an IEEE division, as in knn_split_kernel), C and gamma.
+//
+// smo_kernel: the lane split of kernels_kv.hpp -- a group of 8 lanes owns the rows g, g + 32, g + 64, ... of the task and
+// lane l the dims l, l + 8, ... of a row; three xor shuffles give every lane of the group the kernel value, so all eight
+// lanes carry the same scalars and lane 0 stores.  Per iteration:
+//   1. every group scans its rows for max v over I_up (v = -y G) and max -v over I_low; the workgroup reduces (value, index)
+//      pairs with "greater value, then greater index" -- exact, associative and commutative, so the order of the reduction
+//      cannot matter and no lane's timing does;
+//   2. z_i is staged in LDS, every group forms K_it for its rows (kept in LDS: the gradient update needs it again), and in
+//      the same pass the second-order objective -b^2 / eta of its rows; the workgroup reduces to j (least value, then
+//      greatest index);
+//   3. every thread computes the two-variable update from the same values, z_j is staged, every group forms K_jt and
+//      updates G_t of its rows.
+// alpha, G and K_tt live in device memory between launches; a launch runs at most `budget` iterations of a task and an
+// iteration reads nothing but (alpha, G): the result is bit-identical for any budget, alone or in any batch.
+// At a stop (converged or max_iter) the workgroup writes rho, the gap, alpha_t y_t and the number of support vectors; the
+// sum behind rho adds the groups' partial sums (each in row order) in group order.
+//
+// svc_pairs_kernel: one group per test row of a job (32 rows per workgroup); per pair of the job the task's rows go through
+// LDS tiles, standardised once per tile, and the rows with alpha != 0 add alpha_t y_t K(z_t, z) in train-list order.
+#pragma once
+#include "kernels_kv.hpp"
+#include "model_launch.hpp"
+
+namespace paa {
+namespace smo {
+
+using kv::kGroupLanes;
+using kv::kMaxM;
+using kv::kTile;
+static_assert(kMaxDims <= kv::kMaxDims && kThreads % 64 == 0 && kGroups * kGroupLanes == kThreads, "groups of 8 lanes");
+constexpr int kWaves = kThreads / 64;
+constexpr double kTau = 1e-12;
+constexpr int kClassSlots = kMaxClasses / kGroupLanes;
+
+// (a, i) replaces (b, j) when a is greater, or equal with a greater index; an index < 0 is "none"
+__device__ __forceinline__ void take_max(double &b, int &j, double a, int i) {
+    if (i >= 0 && (j < 0 || a > b || (a == b && i > j))) { b = a; j = i; }
+}
+__device__ __forceinline__ void wave_max(double &v, int &i) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        take_max(v, i, ov, oi);
+    }
+}
+// the workgroup's (greatest value, then greatest index); red_v / red_i [kWaves] in LDS.  Every thread returns the same pair
+__device__ __forceinline__ void block_max(double &v, int &i, double *red_v, int *red_i, int tid) {
+    wave_max(v, i);
+    __syncthreads();                                    // the previous use of red_* is over
+    if (tid % 64 == 0) { red_v[tid / 64] = v; red_i[tid / 64] = i; }
+    __syncthreads();
+    v = red_v[0];
+    i = red_i[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) take_max(v, i, red_v[w], red_i[w]);
+}
+
+// zs [pitch] = row `s` of X standardised, zero beyond n_dims (the whole workgroup; the caller synchronises)
+__device__ __forceinline__ void stage_point(double *zs, const double *X, int s, int n_dims, const double *mean, const double *scale,
+                                            int pitch, int tid) {
+    for (int d = tid; d < pitch; d += kThreads) zs[d] = d < n_dims ? (X[(long long)s * n_dims + d] - mean[d]) / scale[d] : 0.0;
+}
+
+// K(z_t, z) of row `s` of X against the staged point zs, for the calling group (every lane gets the value)
+__device__ __forceinline__ double kernel_value(const double *__restrict__ X, int s, const double *zs, const double *mean,
+                                               const double *scale, int n_dims, int M, int lane, bool rbf, double gamma) {
+    const double *__restrict__ x = X + (long long)s * n_dims;
+    double acc = 0.0;
+    for (int i = 0; i < M; ++i) {
+        const int d = lane + kGroupLanes * i;
+        const double z = d < n_dims ? (x[d] - mean[d]) / scale[d] : 0.0;
+        if (rbf) {
+            const double df = z - zs[d];
+            acc = fma(df, df, acc);
+        } else {
+            acc = fma(z, zs[d], acc);
+        }
+    }
+    acc = kv::group_sum(acc);
+    return rbf ? exp(-gamma * acc) : acc;
+}
+
+__global__ __launch_bounds__(kThreads) void smo_kernel(SmoDev m, const int *__restrict__ live, int budget) {
+    extern __shared__ double lds[];                     // mean [pitch] | scale [pitch] | zi [pitch] | zj [pitch] | Ki [n_max]
+    __shared__ double red_v[kWaves];
+    __shared__ int red_i[kWaves];
+    __shared__ double red_sum[kGroups], red_ub[kGroups], red_lb[kGroups];
+    __shared__ int red_free[kGroups], red_sv[kGroups];
+    const int tid = threadIdx.x, lane = tid % kGroupLanes, group = tid / kGroupLanes;
+    const int task = live[blockIdx.x];
+    const SmoTask T = m.tasks[task];
+    const int n = T.n, n_dims = m.n_dims;
+    const int M = (n_dims + kGroupLanes - 1) / kGroupLanes, pitch = M * kGroupLanes;
+    double *s_mean = lds, *s_scale = lds + pitch, *zi = lds + 2 * pitch, *zj = lds + 3 * pitch, *Ki = lds + 4 * pitch;
+    const int *__restrict__ idx = m.idx + T.off;
+    const signed char *__restrict__ sign = m.sign + T.off;
+    double *alpha = m.alpha + T.off, *G = m.G + T.off, *QD = m.QD + T.off;
+    const bool rbf = m.rbf != 0;
+    const double C = T.C, gamma = T.gamma;
+    for (int d = tid; d < pitch; d += kThreads) {
+        s_mean[d] = d < n_dims ? m.mean[(long long)T.stat * n_dims + d] : 0.0;
+        s_scale[d] = d < n_dims ? m.scale[(long long)T.stat * n_dims + d] : 1.0;
+    }
+    __syncthreads();
+    int iter = m.iter[task];
+    if (m.status[task] == kFresh) {                     // alpha = 0, G = -1, K_tt once per task
+        for (int t = group; t < n; t += kGroups) {
+            const double *__restrict__ x = m.X + (long long)idx[t] * n_dims;
+            double acc = 0.0;
+            if (!rbf)
+                for (int i = 0; i < M; ++i) {
+                    const int d = lane + kGroupLanes * i;
+                    const double z = d < n_dims ? (x[d] - s_mean[d]) / s_scale[d] : 0.0;
+                    acc = fma(z, z, acc);
+                }
+            acc = kv::group_sum(acc);
+            if (lane == 0) {
+                QD[t] = rbf ? 1.0 : acc;                // exp(-gamma * 0)
+                alpha[t] = 0.0;
+                G[t] = -1.0;
+            }
+        }
+        iter = 0;
+        __syncthreads();
+    }
+
+    int status = kRunning;
+    double gmax = 0.0, gmax2 = 0.0;
+    bool both = false;                                  // I_up and I_low are not empty: the gap is a number
+    for (int done = 0;; ++done) {
+        // 1. i: the greatest v over I_up (ties: the greatest index); Gmax2 over I_low
+        double bv = 0.0, b2 = 0.0;
+        int bi = -1, b2i = -1;
+        for (int t = group; t < n; t += kGroups) {
+            const double a = alpha[t], v = sign[t] > 0 ? -G[t] : G[t];
+            const bool pos = sign[t] > 0;
+            if (pos ? a < C : a > 0.0) take_max(bv, bi, v, t);
+            if (pos ? a > 0.0 : a < C) take_max(b2, b2i, -v, t);
+        }
+        block_max(bv, bi, red_v, red_i, tid);
+        block_max(b2, b2i, red_v, red_i, tid);
+        gmax = bv;
+        gmax2 = b2;
+        const int i = bi;
+        both = bi >= 0 && b2i >= 0;
+        if (i < 0 || b2i < 0 || !(gmax + gmax2 >= m.eps)) { status = kConverged; break; }
+        if (iter >= m.max_iter) { status = kNotConverged; break; }
+        if (done >= budget) break;
+
+        // 2. K_it for every row, and j: the least -b^2 / eta over I_low with b > 0 (ties: the greatest index)
+        stage_point(zi, m.X, idx[i], n_dims, s_mean, s_scale, pitch, tid);
+        __syncthreads();
+        const double qd_i = QD[i];
+        double jv = 0.0;
+        int ji = -1;
+        for (int t = group; t < n; t += kGroups) {
+            const double k = kernel_value(m.X, idx[t], zi, s_mean, s_scale, n_dims, M, lane, rbf, gamma);
+            if (lane == 0) Ki[t] = k;
+            const double a = alpha[t], v = sign[t] > 0 ? -G[t] : G[t];
+            const bool pos = sign[t] > 0;
+            const double b = gmax - v;
+            if ((pos ? a > 0.0 : a < C) && b > 0.0) {
+                double eta = qd_i + QD[t] - 2.0 * k;
+                if (!(eta > 0.0)) eta = kTau;
+                take_max(jv, ji, (b * b) / eta, t);       // the greatest b^2 / eta is the least -b^2 / eta
+            }
+        }
+        block_max(jv, ji, red_v, red_i, tid);           // (its barriers also publish Ki)
+        const int j = ji;
+        if (j < 0) { status = kConverged; break; }
+
+        // 3. the two-variable update (every thread, from the same values), then G
+        const double yi = sign[i], yj = sign[j], ai = alpha[i], aj = alpha[j];
+        double eta = qd_i + QD[j] - 2.0 * Ki[j];
+        if (!(eta > 0.0)) eta = kTau;
+        double ni, nj;
+        if (yi != yj) {
+            const double delta = (-G[i] - G[j]) / eta, d = ai - aj;
+            ni = ai + delta;
+            nj = aj + delta;
+            if (d > 0.0) { if (nj < 0.0) { nj = 0.0; ni = d; } }
+            else { if (ni < 0.0) { ni = 0.0; nj = -d; } }
+            if (d > 0.0) { if (ni > C) { ni = C; nj = C - d; } }
+            else { if (nj > C) { nj = C; ni = C + d; } }
+        } else {
+            const double delta = (G[i] - G[j]) / eta, s = ai + aj;
+            ni = ai - delta;
+            nj = aj + delta;
+            if (s > C) { if (ni > C) { ni = C; nj = s - C; } }
+            else { if (nj < 0.0) { nj = 0.0; ni = s; } }
+            if (s > C) { if (nj > C) { nj = C; ni = s - C; } }
+            else { if (ni < 0.0) { ni = 0.0; nj = s; } }
+        }
+        const double ci = yi * (ni - ai), cj = yj * (nj - aj);
+        stage_point(zj, m.X, idx[j], n_dims, s_mean, s_scale, pitch, tid);
+        __syncthreads();                                // every thread has read alpha and G of i and j
+        for (int t = group; t < n; t += kGroups) {
+            const double k = kernel_value(m.X, idx[t], zj, s_mean, s_scale, n_dims, M, lane, rbf, gamma);
+            if (lane == 0) G[t] += (double)sign[t] * (Ki[t] * ci + k * cj);
+        }
+        if (tid == 0) { alpha[i] = ni; alpha[j] = nj; }
+        ++iter;
+        __syncthreads();                                // G and alpha of this iteration before the next scan
+    }
+
+    if (status == kRunning) {
+        if (tid == 0) { m.iter[task] = iter; m.status[task] = kRunning; }
+        return;
+    }
+    // rho (calculate_rho), alpha_t y_t and the support-vector count
+    double sum = 0.0, ub = __builtin_inf(), lb = -__builtin_inf();
+    int n_free = 0, n_sv = 0;
+    for (int t = group; t < n; t += kGroups) {
+        const double a = alpha[t], y = sign[t], yG = y * G[t];
+        if (a > 0.0 && a < C) { sum += yG; ++n_free; }
+        else if ((a >= C) == (y < 0.0)) ub = fmin(ub, yG);          // {alpha = C, y = -1} and {alpha = 0, y = +1}
+        else lb = fmax(lb, yG);
+        n_sv += a != 0.0;
+        if (lane == 0) m.alpha_y[T.off + t] = a * y;
+    }
+    if (lane == 0) { red_sum[group] = sum; red_ub[group] = ub; red_lb[group] = lb; red_free[group] = n_free; red_sv[group] = n_sv; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int g = 1; g < kGroups; ++g) {
+            sum += red_sum[g];
+            ub = fmin(ub, red_ub[g]);
+            lb = fmax(lb, red_lb[g]);
+            n_free += red_free[g];
+            n_sv += red_sv[g];
+        }
+        m.rho[task] = n_free > 0 ? sum / (double)n_free : (ub + lb) / 2.0;
+        m.gap[task] = both ? gmax + gmax2 : 0.0;
+        m.n_sv[task] = n_sv;
+        m.iter[task] = iter;
+        m.status[task] = status;
+    }
+}
+
+// The one-against-one vote over the fitted tasks of a sweep (svm_predict, svm.cpp): workgroup b serves the test rows
+// blocks[b].first .. + 31 of job blocks[b].job, one per group.  Per pair p = (a, b), a < b over the job's k present classes,
+// dec = sum over the task's rows with alpha != 0, in the task's row order, of alpha_t y_t K(z_t, z) - rho; dec > 0 votes for a,
+// otherwise b; the label is the first class with the most votes (its position among the job's classes).  dec_out
+// [Q][max_pairs] may be null.
+__global__ __launch_bounds__(kThreads) void svc_pairs_kernel(SvcFitDev f, int *__restrict__ label, double *__restrict__ dec_out) {
+    extern __shared__ double lds[];                     // tile [kTile][pitch] | ay [kTile]
+    const int tid = threadIdx.x, lane = tid % kGroupLanes, group = tid / kGroupLanes;
+    const int n_dims = f.n_dims, M = (n_dims + kGroupLanes - 1) / kGroupLanes, pitch = M * kGroupLanes;
+    double *tile = lds, *ay = lds + kTile * pitch;
+    const knn::SplitBlock blk = f.blocks[blockIdx.x];
+    const long long q0 = f.test_off[blk.job];
+    const int n_test = (int)(f.test_off[blk.job + 1] - q0), k = f.job_k[blk.job], task0 = f.job_task[blk.job];
+    const double *__restrict__ mean = f.mean + (long long)blk.job * n_dims;
+    const double *__restrict__ scale = f.scale + (long long)blk.job * n_dims;
+    const int qi = blk.first + group;
+    const bool live = qi < n_test;
+    const long long q = q0 + qi;
+    const double *__restrict__ xrow = f.X + (long long)(live ? f.test_idx[q] : 0) * n_dims;
+    const bool rbf = f.rbf != 0;
+    double x[kMaxM];
+#pragma unroll
+    for (int i = 0; i < kMaxM; ++i) {
+        const int d = lane + kGroupLanes * i;
+        x[i] = (i < M && d < n_dims && live) ? (xrow[d] - mean[d]) / scale[d] : 0.0;
+    }
+    int votes[kClassSlots];
+#pragma unroll
+    for (int s = 0; s < kClassSlots; ++s) votes[s] = 0;
+    int p = 0;
+    for (int a = 0; a < k; ++a) {
+        for (int b = a + 1; b < k; ++b, ++p) {
+            const SmoTask T = f.tasks[task0 + p];
+            const int *__restrict__ idx = f.idx + T.off;
+            const double *__restrict__ alpha_y = f.alpha_y + T.off;
+            double dec = 0.0;
+            for (int base = 0; base < T.n; base += kTile) {
+                __syncthreads();
+                for (int e = tid; e < kTile * pitch; e += kThreads) {
+                    const int s = base + e / pitch, d = e % pitch;
+                    tile[e] = (s < T.n && d < n_dims) ? (f.X[(long long)idx[s] * n_dims + d] - mean[d]) / scale[d] : 0.0;
+                }
+                if (tid < kTile) ay[tid] = base + tid < T.n ? alpha_y[base + tid] : 0.0;
+                __syncthreads();
+                for (int r = 0; r < kTile; ++r) {
+                    const double c = ay[r];
+                    if (c == 0.0) continue;             // not a support vector (the same for the whole workgroup)
+                    const double *t = tile + r * pitch + lane;
+                    double acc = 0.0;
+#pragma unroll
+                    for (int i = 0; i < kMaxM; ++i) {
+                        if (i < M) {
+                            if (rbf) {
+                                const double df = t[kGroupLanes * i] - x[i];
+                                acc = fma(df, df, acc);
+                            } else {
+                                acc = fma(t[kGroupLanes * i], x[i], acc);
+                            }
+                        }
+                    }
+                    acc = kv::group_sum(acc);
+                    dec = fma(c, rbf ? exp(-T.gamma * acc) : acc, dec);
+                }
+            }
+            dec -= f.rho[task0 + p];
+            const int w = dec > 0.0 ? a : b;
+#pragma unroll
+            for (int s = 0; s < kClassSlots; ++s) votes[s] += w == lane + kGroupLanes * s;
+            if (dec_out && live && lane == 0) dec_out[q * f.max_pairs + p] = dec;
+        }
+    }
+    int key = -1;                                       // votes * 128 + (127 - class): the most votes, then the lowest class
+#pragma unroll
+    for (int s = 0; s < kClassSlots; ++s) {
+        const int c = lane + kGroupLanes * s;
+        if (c < k) key = max(key, votes[s] * 128 + (127 - c));
+    }
+#pragma unroll
+    for (int o = 1; o < kGroupLanes; o <<= 1) key = max(key, __shfl_xor(key, o, kGroupLanes));
+    if (live && lane == 0) label[q] = 127 - key % 128;
+}
+
+}  // namespace smo
+}  // namespace paa

@@ -1,0 +1,267 @@
+// The SVM fits of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700 with train_svm :132-155) on the device: a batch
+// of binary C-SVC dual problems (tasks) over ONE uploaded sample matrix, solved by relaunching smo_kernel until every task has
+// stopped, and the split sweep built on it (pair tasks per job, then the one-against-one vote of every test row).
+// Kernels: kernels_smo.hpp (family_smo.hip).
+#pragma once
+
+// the limits, for callers and tests: threads per workgroup, groups, rows per task, test rows per scoring workgroup, the default
+// iterations per launch, dims
+extern "C" int paa_debug_smo_geometry(int32_t *out6) {
+    if (!out6) return fail(PAA_ERR_ARG, "null");
+    launch::smo_geometry(out6);
+    return PAA_OK;
+}
+
+// what both entry points ask of the solver's parameters
+static int smo_params_check(int n_dims, int kernel_type, double eps, int max_iter, int iters_per_launch) {
+    if (n_dims < 1) return fail(PAA_ERR_ARG, "%d feature dimensions", n_dims);
+    if (n_dims > smo::kMaxDims) return fail(PAA_ERR_UNSUPPORTED, "%d feature dimensions: at most %d are supported", n_dims, smo::kMaxDims);
+    if (kernel_type != 0 && kernel_type != 2) return fail(PAA_ERR_ARG, "kernel type %d: 0 (linear) and 2 (RBF) are supported", kernel_type);
+    if (!(eps > 0.0)) return fail(PAA_ERR_ARG, "eps = %g: a positive tolerance is needed", eps);
+    if (max_iter < 1) return fail(PAA_ERR_ARG, "max_iter = %d", max_iter);
+    if (iters_per_launch < 0) return fail(PAA_ERR_ARG, "iters_per_launch = %d (0: the default, %d)", iters_per_launch, smo::kDefaultItersPerLaunch);
+    return PAA_OK;
+}
+static int smo_task_check(int t, int64_t n, double C, double gamma, int kernel_type) {
+    if (n < 1) return fail(PAA_ERR_ARG, "task %d: no rows", t);
+    if (n > smo::kMaxRows) return fail(PAA_ERR_UNSUPPORTED, "task %d: %lld rows: at most %d per task are supported", t, (long long)n, smo::kMaxRows);
+    if (!(C > 0.0) || !std::isfinite(C)) return fail(PAA_ERR_ARG, "task %d: C = %g", t, C);
+    if (kernel_type == 2 && (!(gamma > 0.0) || !std::isfinite(gamma))) return fail(PAA_ERR_ARG, "task %d: gamma = %g", t, gamma);
+    return PAA_OK;
+}
+
+// The state of a batch on the device, freed on return: alpha | G | QD | alpha_y [rows]; rho | gap [tasks]; iter | status | n_sv |
+// live [tasks]
+struct SmoState {
+    DevBlock block;
+    int *live = nullptr;
+};
+static int smo_state_alloc(SmoState &s, smo::SmoDev &m, size_t rows, size_t n_tasks) {
+    const size_t b_rows = up256(rows * 8), b_task8 = up256(n_tasks * 8), b_task4 = up256(n_tasks * 4);
+    HIP_TRY(hipMalloc(&s.block.p, 4 * b_rows + 2 * b_task8 + 4 * b_task4));
+    char *p = (char *)s.block.p;
+    m.alpha = (double *)p;      p += b_rows;
+    m.G = (double *)p;          p += b_rows;
+    m.QD = (double *)p;         p += b_rows;
+    m.alpha_y = (double *)p;    p += b_rows;
+    m.rho = (double *)p;        p += b_task8;
+    m.gap = (double *)p;        p += b_task8;
+    m.iter = (int *)p;          p += b_task4;
+    m.status = (int *)p;        p += b_task4;
+    m.n_sv = (int *)p;          p += b_task4;
+    s.live = (int *)p;
+    HIP_TRY(hipMemsetAsync(m.iter, 0, 2 * b_task4, cs()));       // iteration 0, status kFresh
+    return PAA_OK;
+}
+
+// Runs every task to its stop: a launch gives each unfinished task at most `budget` iterations, the host reads the status
+// words, compacts the unfinished tasks and launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
+static int smo_run(const smo::SmoDev &m, const SmoState &s, const std::vector<smo::SmoTask> &tasks, int budget, std::vector<int> &status,
+                   int *n_launches) {
+    const int n_tasks = (int)tasks.size();
+    std::vector<int> live(n_tasks);
+    for (int t = 0; t < n_tasks; ++t) live[t] = t;
+    status.assign(n_tasks, smo::kFresh);
+    const long long launch_cap = (long long)m.max_iter / budget + 2;     // every launch advances every live task by `budget`
+    long long launches = 0;
+    while (!live.empty()) {
+        if (launches++ >= launch_cap) return fail(PAA_ERR_HIP, "the solver made no progress in %lld launches", launch_cap);
+        int n_max = 0;
+        for (int t : live) n_max = std::max(n_max, tasks[t].n);
+        HIP_TRY(hipMemcpyAsync(s.live, live.data(), live.size() * 4, hipMemcpyHostToDevice, cs()));
+        LAUNCH_TRY("SMO", launch::smo_step(m, s.live, (int)live.size(), n_max, budget, cs()));
+        HIP_TRY(hipMemcpyAsync(status.data(), m.status, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+        HIP_TRY(hipStreamSynchronize(cs()));
+        size_t kept = 0;
+        for (int t : live)
+            if (status[t] < smo::kConverged) live[kept++] = t;
+        live.resize(kept);
+    }
+    if (n_launches) *n_launches = (int)launches;
+    return PAA_OK;
+}
+
+// The solver alone (libsvm's Solver::Solve for C-SVC, svm.cpp, as svm_train_one runs it under SVC.fit): see paa_hip.h
+extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
+                                 const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
+                                 const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                 int iters_per_launch, double *alpha_y, double *rho, int32_t *iterations, double *gap,
+                                 int32_t *status, int32_t *n_launches) {
+    if (!X || !task_off || !task_idx || !task_sign || !mean || !std || !C || !gamma || !alpha_y || !rho || !iterations || !gap || !status)
+        return fail(PAA_ERR_ARG, "null argument");
+    if (n_samples < 1 || n_samples > 0x7fffffffLL) return fail(PAA_ERR_ARG, "%lld samples", (long long)n_samples);
+    int rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
+    if ((rc = split_offsets_check(task_off, n_tasks, "task"))) return rc;
+    const int64_t rows = task_off[n_tasks];
+    std::vector<smo::SmoTask> tasks(n_tasks);
+    for (int t = 0; t < n_tasks; ++t) {
+        if ((rc = smo_task_check(t, task_off[t + 1] - task_off[t], C[t], gamma[t], kernel_type))) return rc;
+        tasks[t] = {(long long)task_off[t], (int)(task_off[t + 1] - task_off[t]), t, C[t], gamma[t]};
+    }
+    for (int64_t i = 0; i < rows; ++i) {
+        if (task_idx[i] < 0 || task_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "row index %d of %lld samples", task_idx[i], (long long)n_samples);
+        if (task_sign[i] != 1 && task_sign[i] != -1) return fail(PAA_ERR_ARG, "sign %d of row %lld: +1 or -1", (int)task_sign[i], (long long)i);
+    }
+    if ((rc = ensure_init())) return rc;
+    const size_t sb = (size_t)n_tasks * n_dims * 8;
+    DevBlock block;
+    BlockPart parts[] = {{tasks.data(), tasks.size() * sizeof(smo::SmoTask), 8}, {mean, sb, 8}, {std, sb, 8},
+                         {task_idx, (size_t)rows * 4, 4}, {task_sign, (size_t)rows, 1}};
+    if ((rc = block_upload(block, parts, 5, "the SMO tasks"))) return rc;
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    smo::SmoDev m{};
+    m.X = st.feats;
+    m.tasks = (const smo::SmoTask *)parts[0].dev;
+    m.mean = (const double *)parts[1].dev;
+    m.scale = (const double *)parts[2].dev;
+    m.idx = (const int *)parts[3].dev;
+    m.sign = (const signed char *)parts[4].dev;
+    m.n_dims = n_dims;
+    m.rbf = kernel_type == 2;
+    m.max_iter = max_iter;
+    m.eps = eps;
+    SmoState s;
+    if ((rc = smo_state_alloc(s, m, (size_t)rows, (size_t)n_tasks))) return rc;
+    std::vector<int> st_words;
+    if ((rc = smo_run(m, s, tasks, iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch, st_words, n_launches))) return rc;
+    HIP_TRY(hipMemcpyAsync(alpha_y, m.alpha_y, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(rho, m.rho, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(gap, m.gap, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(iterations, m.iter, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipStreamSynchronize(cs()));
+    std::copy(st_words.begin(), st_words.end(), status);
+    return PAA_OK;
+}
+
+// The SVM half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700): every split a job, every pair of the classes
+// present in its training list a task; see paa_hip.h
+extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                      const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                      const int32_t *test_idx, const double *mean, const double *std, const double *C,
+                                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                      int32_t *label_out, double *dec_out, int max_pairs, int n_tasks, int32_t *task_iterations,
+                                      int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches) {
+    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !label_out)
+        return fail(PAA_ERR_ARG, "null argument");
+    if (n_samples < 1 || n_samples > 0x7fffffffLL) return fail(PAA_ERR_ARG, "%lld samples", (long long)n_samples);
+    int rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if (n_jobs < 1) return fail(PAA_ERR_ARG, "no jobs");
+    if ((rc = split_offsets_check(train_off, n_jobs, "train"))) return rc;
+    if ((rc = split_offsets_check(test_off, n_jobs, "test"))) return rc;
+    const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
+    if (n_q > kKnnSplitMaxQ) return fail(PAA_ERR_ARG, "too many test vectors");
+    for (int64_t i = 0; i < n_t; ++i) {
+        if (train_idx[i] < 0 || train_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "train index %d of %lld samples", train_idx[i], (long long)n_samples);
+        if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
+    }
+    for (int64_t i = 0; i < n_q; ++i)
+        if (test_idx[i] < 0 || test_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "test index %d of %lld samples", test_idx[i], (long long)n_samples);
+    // the pair tasks: per job the classes present in its training list, ascending; per pair (a, b), a < b, the rows of a in
+    // train-list order, then those of b
+    std::vector<smo::SmoTask> tasks;
+    std::vector<int> idx, job_task(n_jobs + 1, 0), job_k(n_jobs), job_class;     // job_class: every job's classes, job after job
+    std::vector<signed char> sign;
+    std::vector<size_t> job_class_off(n_jobs + 1, 0);
+    std::vector<knn::SplitBlock> blocks;
+    int pairs_max = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t *tr = train_idx + train_off[j];
+        const int64_t n_train = train_off[j + 1] - train_off[j];
+        std::vector<int> classes;
+        for (int64_t i = 0; i < n_train; ++i) classes.push_back(labels[tr[i]]);
+        std::sort(classes.begin(), classes.end());
+        classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+        const int k = (int)classes.size();
+        if (k < 2) return fail(PAA_ERR_ARG, "job %d: %d class(es) in its training list: an SVM needs two", j, k);
+        if (k > smo::kMaxClasses) return fail(PAA_ERR_UNSUPPORTED, "job %d: %d classes: at most %d are supported", j, k, smo::kMaxClasses);
+        std::vector<std::vector<int>> rows(k);
+        for (int64_t i = 0; i < n_train; ++i)
+            rows[std::lower_bound(classes.begin(), classes.end(), labels[tr[i]]) - classes.begin()].push_back(tr[i]);
+        for (int a = 0; a < k; ++a)
+            for (int b = a + 1; b < k; ++b) {
+                const int64_t n = (int64_t)rows[a].size() + (int64_t)rows[b].size();
+                if ((rc = smo_task_check((int)tasks.size(), n, C[j], gamma[j], kernel_type))) return rc;
+                tasks.push_back({(long long)idx.size(), (int)n, j, C[j], gamma[j]});
+                idx.insert(idx.end(), rows[a].begin(), rows[a].end());
+                idx.insert(idx.end(), rows[b].begin(), rows[b].end());
+                sign.insert(sign.end(), rows[a].size(), (signed char)1);
+                sign.insert(sign.end(), rows[b].size(), (signed char)-1);
+            }
+        if (tasks.size() > 0x3fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
+        job_k[j] = k;
+        job_task[j + 1] = (int)tasks.size();
+        job_class.insert(job_class.end(), classes.begin(), classes.end());
+        job_class_off[j + 1] = job_class.size();
+        pairs_max = std::max(pairs_max, k * (k - 1) / 2);
+        for (int64_t first = 0; first < test_off[j + 1] - test_off[j]; first += smo::kQueriesPerBlock) blocks.push_back({j, (int)first});
+    }
+    if (dec_out && max_pairs < pairs_max) return fail(PAA_ERR_ARG, "max_pairs = %d, a job has %d pairs", max_pairs, pairs_max);
+    if ((task_iterations || task_status || task_n_sv) && n_tasks != (int)tasks.size())
+        return fail(PAA_ERR_ARG, "n_tasks = %d, the jobs make %d tasks", n_tasks, (int)tasks.size());
+    if (!dec_out) max_pairs = pairs_max;
+    if ((rc = ensure_init())) return rc;
+    const size_t sb = (size_t)n_jobs * n_dims * 8, rows = idx.size(), nt = tasks.size();
+    knn::SplitBlock none{0, 0};
+    DevBlock block;
+    BlockPart parts[] = {{tasks.data(), nt * sizeof(smo::SmoTask), 8},
+                         {mean, sb, 8},
+                         {std, sb, 8},
+                         {test_off, (size_t)(n_jobs + 1) * 8, 8},
+                         {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
+                         {idx.data(), rows * 4, 4},
+                         {n_q ? test_idx : idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
+                         {job_task.data(), (size_t)(n_jobs + 1) * 4, 4},
+                         {job_k.data(), (size_t)n_jobs * 4, 4},
+                         {sign.data(), rows, 1}};
+    if ((rc = block_upload(block, parts, 10, "the SVM split jobs"))) return rc;
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0,
+                    {{n_q ? label_out : nullptr, (size_t)n_q * 4}, {n_q ? dec_out : nullptr, (size_t)n_q * max_pairs * 8}})))
+        return rc;
+    smo::SmoDev m{};
+    m.X = st.feats;
+    m.tasks = (const smo::SmoTask *)parts[0].dev;
+    m.mean = (const double *)parts[1].dev;
+    m.scale = (const double *)parts[2].dev;
+    m.idx = (const int *)parts[5].dev;
+    m.sign = (const signed char *)parts[9].dev;
+    m.n_dims = n_dims;
+    m.rbf = kernel_type == 2;
+    m.max_iter = max_iter;
+    m.eps = eps;
+    SmoState s;
+    if ((rc = smo_state_alloc(s, m, rows, nt))) return rc;
+    std::vector<int> st_words;
+    if ((rc = smo_run(m, s, tasks, iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch, st_words, n_launches))) return rc;
+    if (task_iterations) HIP_TRY(hipMemcpyAsync(task_iterations, m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
+    if (task_n_sv) HIP_TRY(hipMemcpyAsync(task_n_sv, m.n_sv, nt * 4, hipMemcpyDeviceToHost, cs()));
+    if (task_status) std::copy(st_words.begin(), st_words.end(), task_status);
+    if (n_q) {
+        smo::SvcFitDev f{};
+        f.X = st.feats;
+        f.test_off = (const long long *)parts[3].dev;
+        f.blocks = (const knn::SplitBlock *)parts[4].dev;
+        f.test_idx = (const int *)parts[6].dev;
+        f.job_task = (const int *)parts[7].dev;
+        f.job_k = (const int *)parts[8].dev;
+        f.mean = m.mean;
+        f.scale = m.scale;
+        f.tasks = m.tasks;
+        f.idx = m.idx;
+        f.alpha_y = m.alpha_y;
+        f.rho = m.rho;
+        f.n_dims = n_dims;
+        f.rbf = m.rbf;
+        f.max_pairs = max_pairs;
+        if (st.out[1]) HIP_TRY(hipMemsetAsync(st.out[1], 0, (size_t)n_q * max_pairs * 8, cs()));     // zeros past a job's pairs
+        LAUNCH_TRY("SVM vote", launch::svc_pairs(f, (long long)blocks.size(), (int32_t *)st.out[0], (double *)st.out[1], cs()));
+    }
+    if ((rc = finish(st))) return rc;
+    for (int j = 0; j < n_jobs; ++j)                  // a label is the position among the job's classes: back to class indices
+        for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) label_out[q] = job_class[job_class_off[j] + label_out[q]];
+    return PAA_OK;
+}

@@ -1,4 +1,4 @@
-// Limits, device records and launch entry points of the model families (svc, svr, knn, forest, hmm, diar, lda).  Every family
+// Limits, device records and launch entry points of the model families (svc, svr, knn, smo, forest, hmm, diar, lda).  Every family
 // is its own translation unit (family_<name>.hip: its kernels and the host code that picks an instance are there and
 // nowhere else); the host side of the library (the lib_*.hpp units of paa_lib.hip) sees only what is here.  Every launch::
 // function queues its kernels on `stream` and returns 0, or -1 when a launch failed (hipGetLastError has the reason).
@@ -69,6 +69,51 @@ struct KnnSplitDev {
 };
 constexpr int kSplitKs[] = {1, 2, 4, 8, 16, 32};      // the instances of knn_split_kernel: a sweep runs at the smallest >= its largest k
 }  // namespace knn
+namespace smo {
+constexpr int kThreads = 256;             // kernels_smo.hpp: one workgroup per task, 32 groups of 8 lanes
+constexpr int kGroups = 32;
+constexpr int kMaxRows = 8192;            // rows of a task: its kernel row K_it stays in LDS (64 KB)
+constexpr int kMaxDims = 256;
+constexpr int kMaxClasses = 64;           // classes present in one job of a sweep
+constexpr int kQueriesPerBlock = 32;      // svc_pairs_kernel: one test row per group
+constexpr int kDefaultItersPerLaunch = 1024;
+enum Status { kFresh = 0, kRunning = 1, kConverged = 2, kNotConverged = 3 };
+// one binary C-SVC dual problem over rows of the resident sample matrix
+struct SmoTask {
+    long long off;            // its rows are idx[off .. off + n - 1], with sign[off ..]
+    int n, stat;              // stat: the row of mean / scale it standardises with
+    double C, gamma;
+};
+// a batch of tasks and their state: device pointers
+struct SmoDev {
+    const double *X;          // [n_samples][n_dims]
+    const int *idx;           // sample index of every row of every task
+    const signed char *sign;  // +1: the first class of the pair, -1: the second
+    const SmoTask *tasks;
+    const double *mean, *scale;   // [..][n_dims]
+    double *alpha, *G, *QD;   // state per row: alpha, the gradient, K_tt
+    double *alpha_y;          // out per row, written at a task's stop: alpha_t y_t
+    int *iter, *status;       // state per task (status: Status)
+    double *rho, *gap;        // out per task
+    int *n_sv;                // out per task: rows with alpha != 0
+    int n_dims, rbf, max_iter;
+    double eps;
+};
+// the fitted tasks of a split sweep and its test lists (job j owns the tasks job_task[j] .. job_task[j + 1] - 1, the pairs
+// (a, b), a < b, of its job_k[j] present classes in row-major order): device pointers
+struct SvcFitDev {
+    const double *X;
+    const long long *test_off;
+    const int *test_idx;
+    const knn::SplitBlock *blocks;
+    const int *job_task, *job_k;
+    const double *mean, *scale;   // [n_jobs][n_dims]
+    const SmoTask *tasks;
+    const int *idx;
+    const double *alpha_y, *rho;
+    int n_dims, rbf, max_pairs;
+};
+}  // namespace smo
 namespace forest {
 constexpr int kMaxClasses = 64;
 constexpr int kMaxDims = 256;
@@ -154,6 +199,15 @@ int knn_split(const knn::KnnSplitDev &m, long long n_blocks, int k_max, int *d_l
 // workgroup, training rows per LDS tile, rows per step (= lanes per query), the number of K instances and the instances
 int knn_split_k_launch(int k_max);
 void knn_split_geometry(int out10[10]);
+// kernels_smo.hpp: at most `budget` SMO iterations of each of the n_live tasks d_live [n_live] of the batch m (one workgroup
+// each; n_max: the longest of them, which sizes the LDS); -2 when n_max or n_dims exceeds the limits
+int smo_step(const smo::SmoDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
+// ... and the one-against-one vote over fitted tasks: labels [Q] (position among the job's classes) and, when d_dec is not null,
+// decision values [Q][max_pairs]
+int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double *d_dec, hipStream_t stream);
+// ... the geometry for tests that aim at its edges: threads per workgroup, groups, the row limit, test rows per scoring
+// workgroup, the default iterations per launch, the dims limit
+void smo_geometry(int out6[6]);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
 // two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
 // infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the
