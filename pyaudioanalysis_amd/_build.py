@@ -12,11 +12,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpaa_hip.so")
-SOURCES = ["paa_lib.hip", "family_fast.hip", "family_ct.hip", "family_tri_a.hip", "family_tri_b.hip", "family_tri_c.hip", "family_reg_mix_generic.hip", "family_blu.hip", "family_wgr.hip", "family_wgs.hip", "family_svc.hip", "family_svr.hip", "family_knn.hip", "family_forest.hip", "family_hmm.hip", "family_diar.hip", "family_lda.hip"]
-# the batched SMO solver of the SVM split sweep (kernels_smo.hpp), default flags.  A list of its own: tests/test_regress_cpu.py
-# pins len(SOURCES); every unit of ALL_SOURCES is compiled and linked alike
-SOLVER_SOURCES = ["family_smo.hip"]
-ALL_SOURCES = SOURCES + SOLVER_SOURCES
+SOURCES = ["paa_lib.hip", "family_fast.hip", "family_ct.hip", "family_tri_a.hip", "family_tri_b.hip", "family_tri_c.hip", "family_reg_mix_generic.hip", "family_blu.hip", "family_wgr.hip", "family_wgs.hip", "family_svc.hip", "family_svr.hip", "family_knn.hip", "family_forest.hip", "family_hmm.hip", "family_diar.hip", "family_lda.hip", "family_smo.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "paa_hip.h")]
 # -disable-machine-licm: the feature kernels' loop bodies are thousands of instructions long; hoisting every FP64 literal
 # and per-lane LDS address out of them creates >100 loop-invariant registers that then spill (AGPR copies at one wave per
@@ -49,7 +45,7 @@ def is_stale(lib=None):
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, s) for s in ALL_SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -57,7 +53,7 @@ def build_to(lib, extra_flags=(), opt="-O3", verbose=False, jobs=None):
     """Compile every translation unit (in parallel) and link them into `lib`.  extra_flags go to compile AND link."""
     hipcc = hipcc_path()
     extra = list(extra_flags) + os.environ.get("PAA_HIPCC_FLAGS", "").split()
-    jobs = min(jobs or len(ALL_SOURCES), os.cpu_count() or 1, MAX_JOBS)
+    jobs = min(jobs or len(SOURCES), os.cpu_count() or 1, MAX_JOBS)
     with tempfile.TemporaryDirectory(prefix="paa_build_") as tmp:
         def compile_one(src):
             obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
@@ -69,7 +65,7 @@ def build_to(lib, extra_flags=(), opt="-O3", verbose=False, jobs=None):
                 raise RuntimeError("hipcc failed on %s:\n%s%s" % (src, res.stdout, res.stderr))
             return obj
         with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as pool:
-            objs = list(pool.map(compile_one, ALL_SOURCES))
+            objs = list(pool.map(compile_one, SOURCES))
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [f for f in extra if f.startswith("-fsanitize") or f == "-g"] \
             + objs + ["-o", lib + ".tmp", "-ldl"]
         if verbose:

@@ -276,6 +276,10 @@ def as_f64p(a):
     return a.ctypes.data_as(c_f64p)
 
 
+def as_i32p(a):
+    return a.ctypes.data_as(c_i32p)
+
+
 def as_i64p(a):
     return a.ctypes.data_as(c_i64p)
 

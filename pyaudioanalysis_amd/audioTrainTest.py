@@ -48,6 +48,7 @@ with one output (paa_forest_create kind 2), bit-identical to RandomForestRegress
 (SVR: support_vectors_, _dual_coef_, _intercept_, _gamma, kernel), so SvrArrays / ForestArrays(kind="regressor") work
 without scikit-learn; the fits of the trainers and of evaluate_regression are scikit-learn's and dominate their run time.
 """
+import collections
 import ctypes as C
 import os
 import pickle as cPickle
@@ -87,6 +88,17 @@ def _stats(mean, std, n_dims):
     if mean.shape[0] != n_dims or std.shape[0] != n_dims:
         raise ValueError("mean / std of %d / %d values for a model of %d dims" % (mean.shape[0], std.shape[0], n_dims))
     return mean, std
+
+
+def _class_indices(raw, bound=2**31):
+    """Raw labels [n] as int32 class indices: an integer-valued label in 0 .. bound - 1 is its own index, every other label
+    (fractional, negative, too large, no number) is -1 and counts for no class."""
+    labels = np.full(raw.shape[0], -1, dtype=np.int32)
+    if raw.dtype.kind in "biuf":
+        v = raw.astype(np.float64)
+        ok = (v == np.floor(v)) & (v >= 0) & (v < bound)
+        labels[ok] = v[ok].astype(np.int32)
+    return labels
 
 
 class _DeviceModel:
@@ -229,15 +241,11 @@ class KnnModel(_DeviceModel):
         if train.ndim != 2 or raw.shape[0] != train.shape[0]:
             raise ValueError("kNN model: features %s and %d labels" % (train.shape, raw.shape[0]))
         self.n_classes = int(np.unique(raw).shape[0])
-        labels = np.full(raw.shape[0], -1, dtype=np.int32)
-        if raw.dtype.kind in "biuf":
-            v = raw.astype(np.float64)
-            ok = (v == np.floor(v)) & (v >= 0) & (v < self.n_classes)
-            labels[ok] = v[ok].astype(np.int32)
+        labels = _class_indices(raw, self.n_classes)
         self.k = int(classifier.neighbors)
         self.n_dims = train.shape[1]
         handle = C.c_void_p()
-        _ffi.check(_ffi.lib().paa_knn_create(_ffi.as_f64p(train), labels.ctypes.data_as(_ffi.c_i32p), train.shape[0], self.n_dims,
+        _ffi.check(_ffi.lib().paa_knn_create(_ffi.as_f64p(train), _ffi.as_i32p(labels), train.shape[0], self.n_dims,
                                              self.n_classes, self.k, C.byref(handle)))
         self._adopt(handle)
 
@@ -852,7 +860,13 @@ def knn_split_geometry():
     return int(geo[0]), int(geo[1]), int(geo[2]), tuple(int(v) for v in geo[4:4 + geo[3]])
 
 
-class KnnSplitResult:
+class _SplitResult:
+    def _rows(self, j):
+        """job j's rows of every output that has one row per test vector: test_off[j] .. test_off[j + 1] - 1"""
+        return slice(int(self.test_off[j]), int(self.test_off[j + 1]))
+
+
+class KnnSplitResult(_SplitResult):
     """What knn_split_predict returns: label [Q] (int64 class indices), proba [Q][max_classes] or None, neighbors
     [Q][k_launch] or None (train-list positions, -1 past a job's k or train list), test_off [n_jobs + 1] (job j owns the rows
     test_off[j] .. test_off[j + 1] - 1), n_classes [n_jobs] and k [n_jobs]."""
@@ -862,9 +876,9 @@ class KnnSplitResult:
 
     def job(self, j):
         """(labels, P [n_test][n_classes_j] or None, neighbours [n_test][k_j] or None) of job j."""
-        a, b = int(self.test_off[j]), int(self.test_off[j + 1])
-        return (self.label[a:b], None if self.proba is None else self.proba[a:b, :self.n_classes[j]],
-                None if self.neighbors is None else self.neighbors[a:b, :self.k[j]])
+        r = self._rows(j)
+        return (self.label[r], None if self.proba is None else self.proba[r, :self.n_classes[j]],
+                None if self.neighbors is None else self.neighbors[r, :self.k[j]])
 
 
 def _index_list(idx, what, j):
@@ -876,13 +890,28 @@ def _index_list(idx, what, j):
     return a.astype(np.int32)
 
 
-def knn_split_predict(X, labels, jobs, proba=False, neighbors=False):
-    """Knn.classify for every job of a sweep over ONE sample matrix, in one launch (paa_knn_splits_f64, knn_split_kernel).
-    X [n_samples][n_dims]; labels [n_samples]; a job is (train_idx, test_idx, mean, scale, k): the rows X[train_idx]
-    standardised as (x - mean) / scale are the model, in that order, the rows X[test_idx] the queries.  n_classes of a
-    job is the number of distinct labels of ITS training rows, as KnnModel counts it (the reference's Knn.classify :40):
-    a class absent from a split shrinks it, and rows labelled >= n_classes then vote for no class, like labels that
-    are no integers >= 0.  Neighbours rank in ascending (squared distance, position in train_idx).  Returns a KnnSplitResult."""
+def _offsets(counts):
+    """[0, counts[0], counts[0] + counts[1], ...] as int64: list j of a concatenation owns offsets[j] .. offsets[j + 1] - 1."""
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
+def _packed(lists, dtype):       # (the lists as one contiguous array of dtype, their offsets)
+    return np.ascontiguousarray(np.concatenate(lists), dtype=dtype), _offsets([a.shape[0] for a in lists])
+
+
+def _check_kernel(kernel):
+    if kernel not in _KERNEL_TYPES:
+        raise NotImplementedError("SVM kernel %r: the GPU solver serves 'rbf' and 'linear'" % (kernel,))
+
+
+_Jobs = collections.namedtuple("_Jobs", "X raw labels train_idx train_off test_idx test_off mean scale last inside")
+
+
+def _pack_jobs(X, labels, jobs, last, convert, kernel=None):
+    """The jobs (train_idx, test_idx, mean, scale, <last>) of a sweep over ONE sample matrix, checked and packed for the library:
+    X [n_samples][n_dims] as float64, the raw labels and their int32 class indices, the train and test lists concatenated with
+    their offsets [n_jobs + 1], mean / scale [n_jobs][n_dims], per job convert(<last>) and the training rows inside the
+    matrix (an index outside is the library's error to report).  kernel: an SVM sweep's, refused before any job is read."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     raw = np.asarray(labels).reshape(-1)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or raw.shape[0] != X.shape[0]:
@@ -890,44 +919,49 @@ def knn_split_predict(X, labels, jobs, proba=False, neighbors=False):
     jobs = list(jobs)
     if not jobs:
         raise ValueError("no jobs")
+    if kernel is not None:
+        _check_kernel(kernel)
     n_samples, n_dims = X.shape
-    lab = np.full(n_samples, -1, dtype=np.int32)
-    if raw.dtype.kind in "biuf":
-        v = raw.astype(np.float64)
-        ok = (v == np.floor(v)) & (v >= 0) & (v < 2**31)
-        lab[ok] = v[ok].astype(np.int32)
-    train, test, means, scales, ks, ncls = [], [], [], [], [], []
+    train, test, means, scales, lasts, inside = [], [], [], [], [], []
     for j, job in enumerate(jobs):
         if len(job) != 5:
-            raise ValueError("job %d: (train_idx, test_idx, mean, scale, k) expected" % j)
+            raise ValueError("job %d: (train_idx, test_idx, mean, scale, %s) expected" % (j, last))
         tr, te = _index_list(job[0], "train", j), _index_list(job[1], "test", j)
         mean, scale = _stats(job[2], job[3], n_dims)
         train.append(tr)
         test.append(te)
         means.append(mean)
         scales.append(scale)
-        ks.append(int(job[4]))
-        inside = tr[(tr >= 0) & (tr < n_samples)]               # an index outside the matrix is the library's error to report
-        ncls.append(max(int(np.unique(raw[inside]).shape[0]), 1))
-    train_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in train])]).astype(np.int64)
-    test_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in test])]).astype(np.int64)
-    train_idx = np.ascontiguousarray(np.concatenate(train), dtype=np.int32)
-    test_idx = np.ascontiguousarray(np.concatenate(test), dtype=np.int32)
-    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
-    k, n_classes = np.array(ks, dtype=np.int32), np.array(ncls, dtype=np.int32)
+        lasts.append(convert(job[4]))
+        inside.append(tr[(tr >= 0) & (tr < n_samples)])
+    return _Jobs(X, raw, _class_indices(raw), *_packed(train, np.int32), *_packed(test, np.int32), np.stack(means), np.stack(scales), lasts,
+                 inside)
+
+
+def knn_split_predict(X, labels, jobs, proba=False, neighbors=False):
+    """Knn.classify for every job of a sweep over ONE sample matrix, in one launch (paa_knn_splits_f64, knn_split_kernel).
+    X [n_samples][n_dims]; labels [n_samples]; a job is (train_idx, test_idx, mean, scale, k): the rows X[train_idx]
+    standardised as (x - mean) / scale are the model, in that order, the rows X[test_idx] the queries.  n_classes of a
+    job is the number of distinct labels of ITS training rows, as KnnModel counts it (the reference's Knn.classify :40):
+    a class absent from a split shrinks it, and rows labelled >= n_classes then vote for no class, like labels that
+    are no integers >= 0.  Neighbours rank in ascending (squared distance, position in train_idx).  Returns a KnnSplitResult."""
+    p = _pack_jobs(X, labels, jobs, "k", int)
+    n_samples, n_dims = p.X.shape
+    k = np.array(p.last, dtype=np.int32)
+    n_classes = np.array([max(int(np.unique(p.raw[rows]).shape[0]), 1) for rows in p.inside], dtype=np.int32)
     max_classes = int(n_classes.max())
     instances = knn_split_geometry()[3]
     k_launch = min([K for K in instances if K >= int(k.max())], default=instances[-1])
-    Q = int(test_off[-1])
+    Q = int(p.test_off[-1])
     label = np.zeros(Q, dtype=np.int32)
     P = np.zeros((Q, max_classes), dtype=np.float64) if proba else None
     nb = np.full((Q, k_launch), -1, dtype=np.int32) if neighbors else None
     _ffi.check(_ffi.lib().paa_knn_splits_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, lab.ctypes.data_as(_ffi.c_i32p), len(jobs), train_off.ctypes.data_as(_ffi.c_i64p),
-        train_idx.ctypes.data_as(_ffi.c_i32p), test_off.ctypes.data_as(_ffi.c_i64p), test_idx.ctypes.data_as(_ffi.c_i32p),
-        _ffi.as_f64p(mean), _ffi.as_f64p(scale), k.ctypes.data_as(_ffi.c_i32p), n_classes.ctypes.data_as(_ffi.c_i32p), max_classes,
-        label.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(P) if proba else None, nb.ctypes.data_as(_ffi.c_i32p) if neighbors else None))
-    return KnnSplitResult(label.astype(np.int64), P, nb, test_off, n_classes, k)
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(k), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(k),
+        _ffi.as_i32p(n_classes), max_classes, _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None,
+        _ffi.as_i32p(nb) if neighbors else None))
+    return KnnSplitResult(label.astype(np.int64), P, nb, p.test_off, n_classes, k)
 
 
 def smo_geometry():
@@ -975,8 +1009,7 @@ def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_lau
         raise ValueError("sample matrix of shape %s" % (X.shape,))
     if not tasks:
         raise ValueError("no tasks")
-    if kernel not in _KERNEL_TYPES:
-        raise NotImplementedError("SVM kernel %r: the GPU solver serves 'rbf' and 'linear'" % (kernel,))
+    _check_kernel(kernel)
     n_samples, n_dims = X.shape
     rows, signs, means, scales, Cs, gammas = [], [], [], [], [], []
     for t, task in enumerate(tasks):
@@ -993,25 +1026,23 @@ def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_lau
         scales.append(scale)
         Cs.append(float(task[4]))
         gammas.append(1.0 / n_dims if task[5] is None else float(task[5]))
-    off = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int64)
-    idx = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32)
+    idx, off = _packed(rows, np.int32)
     sign = np.ascontiguousarray(np.concatenate(signs), dtype=np.int8)
-    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
+    mean, scale = np.stack(means), np.stack(scales)
     C_arr, g_arr = np.array(Cs, dtype=np.float64), np.array(gammas, dtype=np.float64)
     n_tasks, total = len(tasks), int(off[-1])
     alpha_y, rho, gap = np.zeros(total), np.zeros(n_tasks), np.zeros(n_tasks)
     iterations, status, launches = np.zeros(n_tasks, dtype=np.int32), np.zeros(n_tasks, dtype=np.int32), np.zeros(1, dtype=np.int32)
     _ffi.check(_ffi.lib().paa_smo_tasks_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, n_tasks, off.ctypes.data_as(_ffi.c_i64p), idx.ctypes.data_as(_ffi.c_i32p),
-        sign.ctypes.data_as(C.POINTER(C.c_int8)), _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr),
-        _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
-        iterations.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(gap), status.ctypes.data_as(_ffi.c_i32p),
-        launches.ctypes.data_as(_ffi.c_i32p)))
+        _ffi.as_f64p(X), n_samples, n_dims, n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), sign.ctypes.data_as(C.POINTER(C.c_int8)),
+        _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
+        int(max_iter), int(iters_per_launch), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
+        _ffi.as_i32p(status), _ffi.as_i32p(launches)))
     _warn_not_converged(status, int(max_iter))
     return SmoResult([alpha_y[off[t]:off[t + 1]] for t in range(n_tasks)], rho, iterations, gap, status, int(launches[0]))
 
 
-class SvmSplitResult:
+class SvmSplitResult(_SplitResult):
     """What svm_split_fit_predict returns: label [Q] (class values as in `labels`), decision [Q][max_pairs] or None (zeros past
     a job's pairs), test_off [n_jobs + 1], classes (per job the classes present in its training list, ascending), task_off
     [n_jobs + 1] (job j owns the tasks task_off[j] .. task_off[j + 1] - 1, its pairs (a, b), a < b, row-major) and per task
@@ -1023,9 +1054,9 @@ class SvmSplitResult:
 
     def job(self, j):
         """(labels, decision values [n_test][pairs_j] or None, iterations [pairs_j], status [pairs_j], n_sv [pairs_j]) of job j."""
-        a, b = int(self.test_off[j]), int(self.test_off[j + 1])
+        r = self._rows(j)
         t0, t1 = int(self.task_off[j]), int(self.task_off[j + 1])
-        return (self.label[a:b], None if self.decision is None else self.decision[a:b, :t1 - t0], self.iterations[t0:t1],
+        return (self.label[r], None if self.decision is None else self.decision[r, :t1 - t0], self.iterations[t0:t1],
                 self.status[t0:t1], self.n_sv[t0:t1])
 
 
@@ -1035,58 +1066,27 @@ def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3
     then libsvm's one-against-one vote of every test row).  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the
     training rows); a job is (train_idx, test_idx, mean, scale, C).  gamma=None is 1 / n_dims, the reference's gamma='auto'.
     No probabilities are fitted: the sweep reads vote labels only.  Returns an SvmSplitResult."""
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    raw = np.asarray(labels).reshape(-1)
-    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1 or raw.shape[0] != X.shape[0]:
-        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
-    jobs = list(jobs)
-    if not jobs:
-        raise ValueError("no jobs")
-    if kernel not in _KERNEL_TYPES:
-        raise NotImplementedError("SVM kernel %r: the GPU solver serves 'rbf' and 'linear'" % (kernel,))
-    n_samples, n_dims = X.shape
-    lab = np.full(n_samples, -1, dtype=np.int32)
-    if raw.dtype.kind in "biuf":
-        v = raw.astype(np.float64)
-        ok = (v == np.floor(v)) & (v >= 0) & (v < 2**31)
-        lab[ok] = v[ok].astype(np.int32)
-    train, test, means, scales, Cs, classes = [], [], [], [], [], []
-    for j, job in enumerate(jobs):
-        if len(job) != 5:
-            raise ValueError("job %d: (train_idx, test_idx, mean, scale, C) expected" % j)
-        tr, te = _index_list(job[0], "train", j), _index_list(job[1], "test", j)
-        mean, scale = _stats(job[2], job[3], n_dims)
-        train.append(tr)
-        test.append(te)
-        means.append(mean)
-        scales.append(scale)
-        Cs.append(float(job[4]))
-        inside = tr[(tr >= 0) & (tr < n_samples)]               # an index outside the matrix is the library's error to report
-        classes.append(np.unique(lab[inside]))
-    train_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in train])]).astype(np.int64)
-    test_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in test])]).astype(np.int64)
-    train_idx = np.ascontiguousarray(np.concatenate(train), dtype=np.int32)
-    test_idx = np.ascontiguousarray(np.concatenate(test), dtype=np.int32)
-    mean, scale = np.ascontiguousarray(np.stack(means)), np.ascontiguousarray(np.stack(scales))
-    C_arr = np.array(Cs, dtype=np.float64)
-    g_arr = np.full(len(jobs), 1.0 / n_dims if gamma is None else float(gamma), dtype=np.float64)
+    p = _pack_jobs(X, labels, jobs, "C", float, kernel)
+    n_samples, n_dims = p.X.shape
+    classes = [np.unique(p.labels[rows]) for rows in p.inside]
+    C_arr = np.array(p.last, dtype=np.float64)
+    g_arr = np.full(len(classes), 1.0 / n_dims if gamma is None else float(gamma), dtype=np.float64)
     pairs = [len(c) * (len(c) - 1) // 2 for c in classes]
-    task_off = np.concatenate([[0], np.cumsum(pairs)]).astype(np.int64)
-    n_tasks, max_pairs, Q = int(task_off[-1]), max(max(pairs), 1), int(test_off[-1])
+    task_off = _offsets(pairs)
+    n_tasks, max_pairs, Q = int(task_off[-1]), max(max(pairs), 1), int(p.test_off[-1])
     label = np.zeros(Q, dtype=np.int32)
     dec = np.zeros((Q, max_pairs), dtype=np.float64) if decision else None
     iterations, status, n_sv = (np.zeros(max(n_tasks, 1), dtype=np.int32) for _ in range(3))
     launches = np.zeros(1, dtype=np.int32)
     _ffi.check(_ffi.lib().paa_svc_fit_splits_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, lab.ctypes.data_as(_ffi.c_i32p), len(jobs), train_off.ctypes.data_as(_ffi.c_i64p),
-        train_idx.ctypes.data_as(_ffi.c_i32p), test_off.ctypes.data_as(_ffi.c_i64p), test_idx.ctypes.data_as(_ffi.c_i32p),
-        _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
-        int(max_iter), int(iters_per_launch), label.ctypes.data_as(_ffi.c_i32p), _ffi.as_f64p(dec) if decision else None, max_pairs,
-        n_tasks, iterations.ctypes.data_as(_ffi.c_i32p), status.ctypes.data_as(_ffi.c_i32p), n_sv.ctypes.data_as(_ffi.c_i32p),
-        launches.ctypes.data_as(_ffi.c_i32p)))
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(classes), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
+        _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch), _ffi.as_i32p(label),
+        _ffi.as_f64p(dec) if decision else None, max_pairs, n_tasks, _ffi.as_i32p(iterations), _ffi.as_i32p(status), _ffi.as_i32p(n_sv),
+        _ffi.as_i32p(launches)))
     iterations, status, n_sv = iterations[:n_tasks], status[:n_tasks], n_sv[:n_tasks]
     _warn_not_converged(status, int(max_iter))
-    return SvmSplitResult(label.astype(np.int64), dec, test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
+    return SvmSplitResult(label.astype(np.int64), dec, p.test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
 
 
 def _draw_split(n_samples, train_percentage):
@@ -1161,14 +1161,13 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
                 classifier = _train_classifier(scaler.transform(X[train_idx]), y[train_idx], classifier_name, C_param)
                 predictions[-1].append(list(predict(classifier, classifier_name, X[test_idx].T, scaler.mean_, scaler.scale_)[0])
                                        if len(test_idx) else [])
-    if classifier_name == "knn":
-        jobs = [(tr, te, mean, scale, int(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
-        res = knn_split_predict(X, y, jobs)
-        predictions = [[list(res.job(i * n_exp + e)[0]) for e in range(n_exp)] for i in range(len(splits))]
-    elif svm_fit == "device":
-        jobs = [(tr, te, mean, scale, float(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
-        res = svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
-        predictions = [[[y.dtype.type(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
+    if classifier_name == "knn" or svm_fit == "device":       # one sweep over every split
+        knn, cast = classifier_name == "knn", int if classifier_name == "knn" else float
+        jobs = [(tr, te, mean, scale, cast(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
+        res = knn_split_predict(X, y, jobs) if knn else \
+            svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
+        as_label = (lambda v: v) if knn else y.dtype.type      # kNN: the result's int64 as it is
+        predictions = [[[as_label(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
 
     ac_all, f1_all, f1_std_all, pre_all, rec_all, f1_classes_all, cms_all = [], [], [], [], [], [], []
     y_flat = np.asarray(y).reshape(-1)

@@ -76,17 +76,6 @@ extern "C" int paa_debug_knn_split_geometry(int32_t *out10) {
     return PAA_OK;
 }
 
-constexpr int64_t kKnnSplitMaxQ = 0x7fffffffLL;        // a test vector's place in the outputs is an int32 on the host side of the table
-
-// offsets [n_jobs + 1] from 0 and not decreasing, no list longer than an int
-static int split_offsets_check(const int64_t *off, int n_jobs, const char *what) {
-    if (off[0] != 0) return fail(PAA_ERR_ARG, "%s offsets begin at %lld, not 0", what, (long long)off[0]);
-    for (int j = 0; j < n_jobs; ++j)
-        if (off[j + 1] < off[j] || off[j + 1] - off[j] > 0x7fffffffLL)
-            return fail(PAA_ERR_ARG, "%s offsets of job %d: %lld .. %lld", what, j, (long long)off[j], (long long)off[j + 1]);
-    return PAA_OK;
-}
-
 // The kNN half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700): every (parameter value, experiment) split as a
 // job of index lists over ONE uploaded sample matrix, all jobs in one launch (knn_split_kernel).
 extern "C" int paa_knn_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
@@ -96,33 +85,26 @@ extern "C" int paa_knn_splits_f64(const double *X, int64_t n_samples, int n_dims
                                   int32_t *neighbors_out) {
     if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !k || !n_classes || !label_out)
         return fail(PAA_ERR_ARG, "null argument");
-    if (n_samples < 1 || n_samples > 0x7fffffffLL) return fail(PAA_ERR_ARG, "%lld samples", (long long)n_samples);
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
     if (n_dims < 1 || n_dims > knn::kMaxDims) return fail(PAA_ERR_ARG, "%d feature dimensions: 1..%d are supported", n_dims, knn::kMaxDims);
     if (max_classes < 1 || max_classes > knn::kMaxClasses)
         return fail(PAA_ERR_ARG, "%d classes: 1..%d are supported", max_classes, knn::kMaxClasses);
-    if (n_jobs < 1) return fail(PAA_ERR_ARG, "no jobs");
-    int rc;
-    if ((rc = split_offsets_check(train_off, n_jobs, "train"))) return rc;
-    if ((rc = split_offsets_check(test_off, n_jobs, "test"))) return rc;
+    if ((rc = sweep_jobs_check(n_jobs, train_off, test_off))) return rc;
     const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
-    if (n_q > kKnnSplitMaxQ) return fail(PAA_ERR_ARG, "too many test vectors");
     int k_max = 0;
-    std::vector<knn::SplitBlock> blocks;
     for (int j = 0; j < n_jobs; ++j) {
         if (k[j] < 1 || k[j] > knn::kMaxK) return fail(PAA_ERR_ARG, "job %d: k = %d neighbours: 1..%d are supported", j, k[j], knn::kMaxK);
         if (n_classes[j] < 1 || n_classes[j] > max_classes)
             return fail(PAA_ERR_ARG, "job %d: %d classes: 1..%d (max_classes)", j, n_classes[j], max_classes);
         if (train_off[j + 1] == train_off[j]) return fail(PAA_ERR_ARG, "job %d: no training vectors", j);
         k_max = std::max(k_max, (int)k[j]);
-        for (int64_t first = 0; first < test_off[j + 1] - test_off[j]; first += knn::kQueriesPerBlock)
-            blocks.push_back({j, (int)first});
     }
-    for (int64_t i = 0; i < n_t; ++i)
-        if (train_idx[i] < 0 || train_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "train index %d of %lld samples", train_idx[i], (long long)n_samples);
-    for (int64_t i = 0; i < n_q; ++i)
-        if (test_idx[i] < 0 || test_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "test index %d of %lld samples", test_idx[i], (long long)n_samples);
+    if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
+    if ((rc = sweep_index_check(test_idx, n_q, n_samples, "test"))) return rc;
     if (n_q == 0) return PAA_OK;                      // every test list empty: nothing to classify
     if ((rc = ensure_init())) return rc;
+    const std::vector<knn::SplitBlock> blocks = sweep_blocks(test_off, n_jobs, knn::kQueriesPerBlock);
     const int k_launch = launch::knn_split_k_launch(k_max);
     const size_t sb = (size_t)n_jobs * n_dims * 8;
     DevBlock block;                                   // the job tables: freed on return

@@ -54,10 +54,14 @@ static int smo_state_alloc(SmoState &s, smo::SmoDev &m, size_t rows, size_t n_ta
     return PAA_OK;
 }
 
-// Runs every task to its stop: a launch gives each unfinished task at most `budget` iterations, the host reads the status
-// words, compacts the unfinished tasks and launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
-static int smo_run(const smo::SmoDev &m, const SmoState &s, const std::vector<smo::SmoTask> &tasks, int budget, std::vector<int> &status,
-                   int *n_launches) {
+// Solves a batch: allocates its state into s and m, then runs every task to its stop: a launch gives each unfinished task at
+// most `budget` iterations (iters_per_launch, 0: the default), the host reads the status words, compacts the unfinished tasks
+// and launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
+static int smo_solve_batch(smo::SmoDev &m, SmoState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, int iters_per_launch,
+                           std::vector<int> &status, int *n_launches) {
+    int rc;
+    if ((rc = smo_state_alloc(s, m, rows, tasks.size()))) return rc;
+    const int budget = iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch;
     const int n_tasks = (int)tasks.size();
     std::vector<int> live(n_tasks);
     for (int t = 0; t < n_tasks; ++t) live[t] = t;
@@ -81,6 +85,23 @@ static int smo_run(const smo::SmoDev &m, const SmoState &s, const std::vector<sm
     return PAA_OK;
 }
 
+// the solver's view of an uploaded batch: the staged matrix, the uploaded tasks | mean | scale | idx | sign and the parameters
+static smo::SmoDev smo_dev(const double *X, const BlockPart &tasks, const BlockPart &mean, const BlockPart &scale, const BlockPart &idx,
+                           const BlockPart &sign, int n_dims, int kernel_type, double eps, int max_iter) {
+    smo::SmoDev m{};
+    m.X = X;
+    m.tasks = (const smo::SmoTask *)tasks.dev;
+    m.mean = (const double *)mean.dev;
+    m.scale = (const double *)scale.dev;
+    m.idx = (const int *)idx.dev;
+    m.sign = (const signed char *)sign.dev;
+    m.n_dims = n_dims;
+    m.rbf = kernel_type == 2;
+    m.max_iter = max_iter;
+    m.eps = eps;
+    return m;
+}
+
 // The solver alone (libsvm's Solver::Solve for C-SVC, svm.cpp, as svm_train_one runs it under SVC.fit): see paa_hip.h
 extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
                                  const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
@@ -89,21 +110,20 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
                                  int32_t *status, int32_t *n_launches) {
     if (!X || !task_off || !task_idx || !task_sign || !mean || !std || !C || !gamma || !alpha_y || !rho || !iterations || !gap || !status)
         return fail(PAA_ERR_ARG, "null argument");
-    if (n_samples < 1 || n_samples > 0x7fffffffLL) return fail(PAA_ERR_ARG, "%lld samples", (long long)n_samples);
     int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
     if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
     if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
-    if ((rc = split_offsets_check(task_off, n_tasks, "task"))) return rc;
+    if ((rc = sweep_offsets_check(task_off, n_tasks, "task"))) return rc;
     const int64_t rows = task_off[n_tasks];
     std::vector<smo::SmoTask> tasks(n_tasks);
     for (int t = 0; t < n_tasks; ++t) {
         if ((rc = smo_task_check(t, task_off[t + 1] - task_off[t], C[t], gamma[t], kernel_type))) return rc;
         tasks[t] = {(long long)task_off[t], (int)(task_off[t + 1] - task_off[t]), t, C[t], gamma[t]};
     }
-    for (int64_t i = 0; i < rows; ++i) {
-        if (task_idx[i] < 0 || task_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "row index %d of %lld samples", task_idx[i], (long long)n_samples);
+    if ((rc = sweep_index_check(task_idx, rows, n_samples, "row"))) return rc;
+    for (int64_t i = 0; i < rows; ++i)
         if (task_sign[i] != 1 && task_sign[i] != -1) return fail(PAA_ERR_ARG, "sign %d of row %lld: +1 or -1", (int)task_sign[i], (long long)i);
-    }
     if ((rc = ensure_init())) return rc;
     const size_t sb = (size_t)n_tasks * n_dims * 8;
     DevBlock block;
@@ -112,21 +132,10 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     if ((rc = block_upload(block, parts, 5, "the SMO tasks"))) return rc;
     Staged st;                                        // X goes up once, through the lane's scratch
     if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
-    smo::SmoDev m{};
-    m.X = st.feats;
-    m.tasks = (const smo::SmoTask *)parts[0].dev;
-    m.mean = (const double *)parts[1].dev;
-    m.scale = (const double *)parts[2].dev;
-    m.idx = (const int *)parts[3].dev;
-    m.sign = (const signed char *)parts[4].dev;
-    m.n_dims = n_dims;
-    m.rbf = kernel_type == 2;
-    m.max_iter = max_iter;
-    m.eps = eps;
+    smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], n_dims, kernel_type, eps, max_iter);
     SmoState s;
-    if ((rc = smo_state_alloc(s, m, (size_t)rows, (size_t)n_tasks))) return rc;
     std::vector<int> st_words;
-    if ((rc = smo_run(m, s, tasks, iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch, st_words, n_launches))) return rc;
+    if ((rc = smo_solve_batch(m, s, tasks, (size_t)rows, iters_per_launch, st_words, n_launches))) return rc;
     HIP_TRY(hipMemcpyAsync(alpha_y, m.alpha_y, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(rho, m.rho, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(gap, m.gap, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
@@ -136,38 +145,20 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     return PAA_OK;
 }
 
-// The SVM half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700): every split a job, every pair of the classes
-// present in its training list a task; see paa_hip.h
-extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
-                                      const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
-                                      const int32_t *test_idx, const double *mean, const double *std, const double *C,
-                                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
-                                      int32_t *label_out, double *dec_out, int max_pairs, int n_tasks, int32_t *task_iterations,
-                                      int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches) {
-    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !label_out)
-        return fail(PAA_ERR_ARG, "null argument");
-    if (n_samples < 1 || n_samples > 0x7fffffffLL) return fail(PAA_ERR_ARG, "%lld samples", (long long)n_samples);
-    int rc;
-    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
-    if (n_jobs < 1) return fail(PAA_ERR_ARG, "no jobs");
-    if ((rc = split_offsets_check(train_off, n_jobs, "train"))) return rc;
-    if ((rc = split_offsets_check(test_off, n_jobs, "test"))) return rc;
-    const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
-    if (n_q > kKnnSplitMaxQ) return fail(PAA_ERR_ARG, "too many test vectors");
-    for (int64_t i = 0; i < n_t; ++i) {
-        if (train_idx[i] < 0 || train_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "train index %d of %lld samples", train_idx[i], (long long)n_samples);
-        if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
-    }
-    for (int64_t i = 0; i < n_q; ++i)
-        if (test_idx[i] < 0 || test_idx[i] >= n_samples) return fail(PAA_ERR_ARG, "test index %d of %lld samples", test_idx[i], (long long)n_samples);
-    // the pair tasks: per job the classes present in its training list, ascending; per pair (a, b), a < b, the rows of a in
-    // train-list order, then those of b
+// The pair tasks of a split sweep: per job the classes present in its training list, ascending; per pair (a, b), a < b, one task
+// over the rows of a in train-list order (sign +1), then those of b (sign -1)
+struct PairTasks {
     std::vector<smo::SmoTask> tasks;
-    std::vector<int> idx, job_task(n_jobs + 1, 0), job_k(n_jobs), job_class;     // job_class: every job's classes, job after job
+    std::vector<int> idx, job_task, job_k, job_class;     // job_task [n_jobs + 1]; job_class: every job's classes, job after job
     std::vector<signed char> sign;
-    std::vector<size_t> job_class_off(n_jobs + 1, 0);
-    std::vector<knn::SplitBlock> blocks;
+    std::vector<size_t> job_class_off;                    // [n_jobs + 1] into job_class
     int pairs_max = 0;
+};
+static int svc_pair_tasks(PairTasks &p, const int32_t *labels, int n_jobs, const int64_t *train_off, const int32_t *train_idx,
+                          const double *C, const double *gamma, int kernel_type) {
+    p.job_task.assign(n_jobs + 1, 0);
+    p.job_k.assign(n_jobs, 0);
+    p.job_class_off.assign(n_jobs + 1, 0);
     for (int j = 0; j < n_jobs; ++j) {
         const int32_t *tr = train_idx + train_off[j];
         const int64_t n_train = train_off[j + 1] - train_off[j];
@@ -184,62 +175,81 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
         for (int a = 0; a < k; ++a)
             for (int b = a + 1; b < k; ++b) {
                 const int64_t n = (int64_t)rows[a].size() + (int64_t)rows[b].size();
-                if ((rc = smo_task_check((int)tasks.size(), n, C[j], gamma[j], kernel_type))) return rc;
-                tasks.push_back({(long long)idx.size(), (int)n, j, C[j], gamma[j]});
-                idx.insert(idx.end(), rows[a].begin(), rows[a].end());
-                idx.insert(idx.end(), rows[b].begin(), rows[b].end());
-                sign.insert(sign.end(), rows[a].size(), (signed char)1);
-                sign.insert(sign.end(), rows[b].size(), (signed char)-1);
+                int rc;
+                if ((rc = smo_task_check((int)p.tasks.size(), n, C[j], gamma[j], kernel_type))) return rc;
+                p.tasks.push_back({(long long)p.idx.size(), (int)n, j, C[j], gamma[j]});
+                p.idx.insert(p.idx.end(), rows[a].begin(), rows[a].end());
+                p.idx.insert(p.idx.end(), rows[b].begin(), rows[b].end());
+                p.sign.insert(p.sign.end(), rows[a].size(), (signed char)1);
+                p.sign.insert(p.sign.end(), rows[b].size(), (signed char)-1);
             }
-        if (tasks.size() > 0x3fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
-        job_k[j] = k;
-        job_task[j + 1] = (int)tasks.size();
-        job_class.insert(job_class.end(), classes.begin(), classes.end());
-        job_class_off[j + 1] = job_class.size();
-        pairs_max = std::max(pairs_max, k * (k - 1) / 2);
-        for (int64_t first = 0; first < test_off[j + 1] - test_off[j]; first += smo::kQueriesPerBlock) blocks.push_back({j, (int)first});
+        if (p.tasks.size() > 0x3fffffffULL) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
+        p.job_k[j] = k;
+        p.job_task[j + 1] = (int)p.tasks.size();
+        p.job_class.insert(p.job_class.end(), classes.begin(), classes.end());
+        p.job_class_off[j + 1] = p.job_class.size();
+        p.pairs_max = std::max(p.pairs_max, k * (k - 1) / 2);
     }
-    if (dec_out && max_pairs < pairs_max) return fail(PAA_ERR_ARG, "max_pairs = %d, a job has %d pairs", max_pairs, pairs_max);
-    if ((task_iterations || task_status || task_n_sv) && n_tasks != (int)tasks.size())
-        return fail(PAA_ERR_ARG, "n_tasks = %d, the jobs make %d tasks", n_tasks, (int)tasks.size());
-    if (!dec_out) max_pairs = pairs_max;
+    return PAA_OK;
+}
+
+// The SVM half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700): every split a job, every pair of the classes
+// present in its training list a task; see paa_hip.h
+extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                      const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                      const int32_t *test_idx, const double *mean, const double *std, const double *C,
+                                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                      int32_t *label_out, double *dec_out, int max_pairs, int n_tasks, int32_t *task_iterations,
+                                      int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches) {
+    // check
+    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !label_out)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if ((rc = sweep_jobs_check(n_jobs, train_off, test_off))) return rc;
+    const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
+    if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
+    for (int64_t i = 0; i < n_t; ++i)
+        if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
+    if ((rc = sweep_index_check(test_idx, n_q, n_samples, "test"))) return rc;
+    // the pair tasks
+    PairTasks p;
+    if ((rc = svc_pair_tasks(p, labels, n_jobs, train_off, train_idx, C, gamma, kernel_type))) return rc;
+    if (dec_out && max_pairs < p.pairs_max) return fail(PAA_ERR_ARG, "max_pairs = %d, a job has %d pairs", max_pairs, p.pairs_max);
+    if ((task_iterations || task_status || task_n_sv) && n_tasks != (int)p.tasks.size())
+        return fail(PAA_ERR_ARG, "n_tasks = %d, the jobs make %d tasks", n_tasks, (int)p.tasks.size());
+    if (!dec_out) max_pairs = p.pairs_max;
     if ((rc = ensure_init())) return rc;
-    const size_t sb = (size_t)n_jobs * n_dims * 8, rows = idx.size(), nt = tasks.size();
-    knn::SplitBlock none{0, 0};
+    // upload
+    const std::vector<knn::SplitBlock> blocks = sweep_blocks(test_off, n_jobs, smo::kQueriesPerBlock);
+    const size_t sb = (size_t)n_jobs * n_dims * 8, rows = p.idx.size(), nt = p.tasks.size();
+    const knn::SplitBlock none{0, 0};
     DevBlock block;
-    BlockPart parts[] = {{tasks.data(), nt * sizeof(smo::SmoTask), 8},
+    BlockPart parts[] = {{p.tasks.data(), nt * sizeof(smo::SmoTask), 8},
                          {mean, sb, 8},
                          {std, sb, 8},
                          {test_off, (size_t)(n_jobs + 1) * 8, 8},
                          {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
-                         {idx.data(), rows * 4, 4},
-                         {n_q ? test_idx : idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
-                         {job_task.data(), (size_t)(n_jobs + 1) * 4, 4},
-                         {job_k.data(), (size_t)n_jobs * 4, 4},
-                         {sign.data(), rows, 1}};
+                         {p.idx.data(), rows * 4, 4},
+                         {n_q ? test_idx : p.idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
+                         {p.job_task.data(), (size_t)(n_jobs + 1) * 4, 4},
+                         {p.job_k.data(), (size_t)n_jobs * 4, 4},
+                         {p.sign.data(), rows, 1}};
     if ((rc = block_upload(block, parts, 10, "the SVM split jobs"))) return rc;
     Staged st;                                        // X goes up once, through the lane's scratch
     if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0,
                     {{n_q ? label_out : nullptr, (size_t)n_q * 4}, {n_q ? dec_out : nullptr, (size_t)n_q * max_pairs * 8}})))
         return rc;
-    smo::SmoDev m{};
-    m.X = st.feats;
-    m.tasks = (const smo::SmoTask *)parts[0].dev;
-    m.mean = (const double *)parts[1].dev;
-    m.scale = (const double *)parts[2].dev;
-    m.idx = (const int *)parts[5].dev;
-    m.sign = (const signed char *)parts[9].dev;
-    m.n_dims = n_dims;
-    m.rbf = kernel_type == 2;
-    m.max_iter = max_iter;
-    m.eps = eps;
+    // solve the batch
+    smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[5], parts[9], n_dims, kernel_type, eps, max_iter);
     SmoState s;
-    if ((rc = smo_state_alloc(s, m, rows, nt))) return rc;
     std::vector<int> st_words;
-    if ((rc = smo_run(m, s, tasks, iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch, st_words, n_launches))) return rc;
+    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches))) return rc;
     if (task_iterations) HIP_TRY(hipMemcpyAsync(task_iterations, m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
     if (task_n_sv) HIP_TRY(hipMemcpyAsync(task_n_sv, m.n_sv, nt * 4, hipMemcpyDeviceToHost, cs()));
     if (task_status) std::copy(st_words.begin(), st_words.end(), task_status);
+    // vote
     if (n_q) {
         smo::SvcFitDev f{};
         f.X = st.feats;
@@ -261,7 +271,8 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
         LAUNCH_TRY("SVM vote", launch::svc_pairs(f, (long long)blocks.size(), (int32_t *)st.out[0], (double *)st.out[1], cs()));
     }
     if ((rc = finish(st))) return rc;
-    for (int j = 0; j < n_jobs; ++j)                  // a label is the position among the job's classes: back to class indices
-        for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) label_out[q] = job_class[job_class_off[j] + label_out[q]];
+    // a label is the position among the job's classes: back to class indices
+    for (int j = 0; j < n_jobs; ++j)
+        for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) label_out[q] = p.job_class[p.job_class_off[j] + label_out[q]];
     return PAA_OK;
 }

@@ -265,3 +265,34 @@ def test_evaluate_classifier_default_mode_is_the_parents(gpu_lib):
         assert ret == want_ret and text == want_text
         assert np.array_equal(np.array(cms), want_cms)
         assert np.array_equal(np.concatenate([p for row in preds for p in row]), np.concatenate(want_preds))
+
+
+@pytest.mark.parametrize("kernel", ["linear", "rbf"])
+def test_solver_alone_against_the_sweep(gpu_lib, kernel):
+    """Every pair task of a two-job sweep, solved by smo_solve on the rows the sweep builds for it (class a's rows in train-list
+    order, then class b's, signs +1 / -1): the iterations and status the sweep reports, and the sweep's decision values against
+    alpha_y / rho of the solver alone, recomputed on the host as test_decision_values_against_scikit_learns_golden does, within
+    that golden case's tol_dec.  The smo_binary golden's matrix, splits and statistics under three classes (class 1 split in two)."""
+    g = train_ref.load_golden("smo_binary")
+    X, tr, te = g["X"], g["train_idx"], g["test_idx"]
+    lab = np.where((g["labels"] == 1) & (np.arange(X.shape[0]) % 2 == 1), 2, g["labels"])
+    cases = [(p, job) for p, name, job, eps in binary_cases(g) if name == kernel and eps == EPS and job[4] >= 1.0]
+    assert len(cases) == 2
+    sweep = audioTrainTest.svm_split_fit_predict(X, lab, [job for p, job in cases], kernel=kernel, eps=EPS, decision=True)
+    assert [c.tolist() for c in sweep.classes] == [[0, 1, 2]] * 2 and sweep.task_off.tolist() == [0, 3, 6]
+    for j, (p, job) in enumerate(cases):
+        pairs = [(a, b) for a in range(3) for b in range(a + 1, 3)]
+        tasks = [(np.concatenate([tr[lab[tr] == a], tr[lab[tr] == b]]),
+                  np.concatenate([np.ones(np.count_nonzero(lab[tr] == a)), -np.ones(np.count_nonzero(lab[tr] == b))]),
+                  job[2], job[3], job[4], None) for a, b in pairs]
+        alone = audioTrainTest.smo_solve(X, tasks, kernel=kernel, eps=EPS)
+        labels, dec, its, status, n_sv = sweep.job(j)
+        assert np.array_equal(alone.iterations, its) and np.array_equal(alone.status, status)
+        assert np.array_equal([np.count_nonzero(a) for a in alone.alpha_y], n_sv)
+        Zq = (X[te] - job[2]) / job[3]
+        for t, task in enumerate(tasks):
+            sv = alone.alpha_y[t] != 0
+            host = smo_ref.gram(Zq, kernel, 1.0 / X.shape[1], ((X[task[0]] - job[2]) / job[3])[sv]) @ alone.alpha_y[t][sv] - alone.rho[t]
+            dist = np.max(np.abs(dec[:, t] - host)) / np.max(np.abs(host))
+            print("%s job %d pair %s: distance %.3g, tol_dec %.3g, iterations %d" % (kernel, j, pairs[t], dist, float(g[p + "tol_dec"]), its[t]))
+            assert dist <= float(g[p + "tol_dec"]), (p, t)

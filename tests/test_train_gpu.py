@@ -302,3 +302,37 @@ def test_extract_features_and_train_svm(gpu_lib, tmp_path):
     assert len(loaded) == 9 and loaded[3] == ["tones", "bursts"] and loaded[1].shape == (136,)
     class_id, P, names = audioTrainTest.file_classification(os.path.join(str(tmp_path), "tones/t03.wav"), model, "svm")
     assert names == ["tones", "bursts"] and P.shape == (2,) and class_id in (0.0, 1.0)
+
+
+def test_one_job_list_through_both_sweeps(gpu_lib):
+    """The same (train_idx, test_idx, mean, scale) jobs through knn_split_predict and svm_split_fit_predict: 3 classes x 12 rows x
+    5 dims of small integers; an empty test list, 17 test rows (one past the 16 queries of a kNN workgroup), 33 (one past the 32
+    rows of an SVM vote workgroup) and a training list without class 2.  Both results carve the test rows up alike, and each
+    job's slice equals, bit for bit, what the same function returns for that job alone."""
+    rng = np.random.default_rng(77)
+    y = np.repeat(np.arange(3), 12)
+    X = (rng.integers(-3, 4, (36, 5)) + 2 * y[:, None]).astype(np.float64)
+    perm = rng.permutation(36)
+    lists = [(perm[:30], perm[:0]), (perm[5:], perm[:17]), (perm, perm[:33]), (np.flatnonzero(y < 2)[::-1], perm[20:])]
+    stats = [(np.zeros(5), np.ones(5)), (np.arange(5.0), np.full(5, 2.0)), (np.ones(5), np.full(5, 0.5)), (-np.ones(5), np.ones(5))]
+    ks, Cs = (1, 3, 32, 4), (0.5, 1.0, 20.0, 1.0)
+    n_test = [0, 17, 33, 16]
+    knn_jobs = [l + s + (k,) for l, s, k in zip(lists, stats, ks)]
+    svm_jobs = [l + s + (C,) for l, s, C in zip(lists, stats, Cs)]
+    knn = audioTrainTest.knn_split_predict(X, y, knn_jobs, proba=True, neighbors=True)
+    svm = audioTrainTest.svm_split_fit_predict(X, y, svm_jobs, decision=True)
+    want_off = np.concatenate([[0], np.cumsum(n_test)])
+    assert np.array_equal(knn.test_off, want_off) and np.array_equal(svm.test_off, want_off)
+    assert knn.test_off.dtype == svm.test_off.dtype == np.int64
+    assert knn.n_classes.tolist() == [3, 3, 3, 2] and [c.tolist() for c in svm.classes] == [[0, 1, 2]] * 3 + [[0, 1]]
+    assert svm.task_off.tolist() == [0, 3, 6, 9, 10] and svm.decision.shape == (66, 3) and knn.proba.shape == (66, 3)
+    for j in range(4):
+        k_got, s_got = knn.job(j), svm.job(j)
+        assert k_got[0].shape == s_got[0].shape == (n_test[j],)
+        assert k_got[1].shape == (n_test[j], knn.n_classes[j]) and k_got[2].shape == (n_test[j], ks[j])
+        assert s_got[1].shape == (n_test[j], len(svm.classes[j]) * (len(svm.classes[j]) - 1) // 2)
+        k_alone = audioTrainTest.knn_split_predict(X, y, [knn_jobs[j]], proba=True, neighbors=True).job(0)
+        s_alone = audioTrainTest.svm_split_fit_predict(X, y, [svm_jobs[j]], decision=True).job(0)
+        for got, want in zip(k_got + s_got, k_alone + s_alone):
+            assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), j
+    assert np.all(svm.status == audioTrainTest.SMO_CONVERGED) and np.all(np.isin(svm.job(3)[0], [0, 1]))
