@@ -57,8 +57,21 @@ def rho_of(alpha, G, y, C):
     return float((ub + lb) / 2)
 
 
-def solve(K, y, C, eps=1e-3, max_iter=10**7):
-    """(alpha, rho, iterations, gap, status) of min 1/2 a^T Q a - e^T a, 0 <= a <= C, y^T a = 0, Q = y y^T K."""
+def _margin(values):
+    """Best minus second-best of the candidate values of a selection: inf with one candidate, 0 for an exact tie."""
+    if values.shape[0] < 2:
+        return np.inf
+    top = np.partition(values, values.shape[0] - 2)[-2:]
+    return float(top[1] - top[0])
+
+
+def solve(K, y, C, eps=1e-3, max_iter=10**7, trace=None):
+    """(alpha, rho, iterations, gap, status) of min 1/2 a^T Q a - e^T a, 0 <= a <= C, y^T a = 0, Q = y y^T K.
+    trace: a list that receives one dict per iteration -- i, j; margin_i / margin_j, best minus second-best candidate value of
+    the two selections (v over I_up; b^2 / eta over the candidates of j); branches, the clips of the update that fired (A1..A4
+    for y_i != y_j, B1..B4 for equal signs, in the order of the ifs below: at most one of each if / elif pair); tau, whether
+    eta of the chosen pair was not positive; eta_rel = eta / (QD_i + QD_j); g_scale = max(1, max |G|) and gap = Gmax + Gmax2
+    of the state the iteration started from."""
     y = np.asarray(y, dtype=np.float64)
     n = y.shape[0]
     alpha, G, QD = np.zeros(n), -np.ones(n), np.diagonal(K).copy()
@@ -82,35 +95,55 @@ def solve(K, y, C, eps=1e-3, max_iter=10**7):
         obj = np.where(cand, -(b * b) / eta, np.inf)
         j = n - 1 - int(np.argmin(obj[::-1]))
         ai, aj = alpha[i], alpha[j]
+        fired = []
         if y[i] != y[j]:
             delta = (-G[i] - G[j]) / eta[j]
             d = ai - aj
             ni, nj = ai + delta, aj + delta
             if d > 0 and nj < 0:
                 nj, ni = 0.0, d
+                fired.append("A1")
             elif d <= 0 and ni < 0:
                 ni, nj = 0.0, -d
+                fired.append("A2")
             if d > 0 and ni > C:
                 ni, nj = C, C - d
+                fired.append("A3")
             elif d <= 0 and nj > C:
                 nj, ni = C, C + d
+                fired.append("A4")
         else:
             delta = (G[i] - G[j]) / eta[j]
             s = ai + aj
             ni, nj = ai - delta, aj + delta
             if s > C and ni > C:
                 ni, nj = C, s - C
+                fired.append("B1")
             elif s <= C and nj < 0:
                 nj, ni = 0.0, s
+                fired.append("B2")
             if s > C and nj > C:
                 nj, ni = C, s - C
+                fired.append("B3")
             elif s <= C and ni < 0:
                 ni, nj = 0.0, s
+                fired.append("B4")
+        if trace is not None:
+            raw = QD[i] + QD[j] - 2.0 * K[i, j]
+            trace.append(dict(i=i, j=j, margin_i=_margin(v[up]), margin_j=_margin(-obj[cand]), branches=tuple(fired), tau=not raw > 0,
+                              eta_rel=float(eta[j] / (QD[i] + QD[j])) if QD[i] + QD[j] > 0 else np.inf, g_scale=float(max(1.0, np.max(np.abs(G)))),
+                              gap=float(gmax + gmax2)))
         G += y * (y[i] * K[i] * (ni - ai) + y[j] * K[j] * (nj - aj))
         alpha[i], alpha[j] = ni, nj
         it += 1
     gap = gmax + gmax2 if np.isfinite(gmax) and np.isfinite(gmax2) else 0.0
     return alpha, rho_of(alpha, G, y, C), it, float(gap), status
+
+
+def solve_trace(K, y, C, eps=1e-3, max_iter=10**7):
+    """solve() and the list of its iterations (see solve)."""
+    trace = []
+    return solve(K, y, C, eps, max_iter, trace), trace
 
 
 def gradient(K, y, alpha):
