@@ -229,6 +229,33 @@ __device__ __forceinline__ int group_min_i(int v) {
     v = min(v, dpp_mov_i<PAA_DPP_RM>(v));
     return v;
 }
+// lane N of the 16-lane row in every lane of the row: row_newbcast:N (gfx90a and later), two moves
+template <int N>
+__device__ __forceinline__ double group_bcast(double v) { return dpp_mov<0x150 + N>(v); }
+// per-lane choice between two doubles (two v_cndmask_b32)
+__device__ __forceinline__ double pick(bool take_a, double a, double b) {
+    return __hiloint2double(take_a ? __double2hiint(a) : __double2hiint(b), take_a ? __double2loint(a) : __double2loint(b));
+}
+// Four group sums whose totals only one lane each reads, in one butterfly: the totals of p, q, r, s land in lanes 13, 12, 15, 14
+// of the row; every lane ends with some total or other.  Seven additions less than four group_sum calls, and each total has
+// group_sum's bits.  group_sum at lane L is a tree over fixed lanes (its dependency cone): at level 1 (after the X1 step) it
+// reads 8 lanes, one of each pair; at level 2 four, one of each quad; at level 3 two.  The cones of lanes 15, 14, 13, 12 are
+// disjoint at every level -- level 1: lanes {0 2 5 7 8 10 13 15} for 15 and 13, the other eight for 14 and 12; level 2:
+// {0 7 8 15}, {1 6 9 14}, {2 5 10 13}, {3 4 11 12} -- so each lane carries, with the very same DPP steps (X1, X2, half mirror,
+// mirror), only the quantity whose cone it lies in and hands its partner the other one.  Every addition has the operands the
+// full butterfly has at that lane.  r_l1 is r AFTER its level-1 step (the caller forms it in every lane: the one quantity here
+// whose level 1 is an FMA, see the spread in kernels_fast.hpp), so lane 15's cone is reproduced operation by operation; p, q and
+// s are plain sums, whose totals are the same in every lane anyway (IEEE addition is commutative).
+__device__ __forceinline__ double group_sum4_to_lanes(double p, double q, double r_l1, double s, int i) {
+    const bool in_r = (((i >> 2) ^ i) & 1) == 0;              // lanes 0 2 5 7 8 10 13 15: p and r at level 1
+    const bool keep_b = (((i >> 2) ^ (i >> 1)) & 1) == 0;     // lanes 0 1 6 7 8 9 14 15: r and s from level 2 on
+    const double a = pick(in_r, p, q) + dpp_mov<PAA_DPP_X1>(pick(in_r, q, p));
+    const double b = pick(in_r, r_l1, s + dpp_mov<PAA_DPP_X1>(s));
+    double v = pick(keep_b, b, a) + dpp_mov<PAA_DPP_X2>(pick(keep_b, a, b));
+    v += dpp_mov<PAA_DPP_HM>(v);
+    v += dpp_mov<PAA_DPP_RM>(v);
+    return v;
+}
 // inclusive prefix sum over the 16-lane row: row_shr:n shifts zeros in (bound_ctrl)
 __device__ __forceinline__ double group_scan_incl(double v) {
     v += dpp_mov<0x111>(v);

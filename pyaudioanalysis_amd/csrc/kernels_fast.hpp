@@ -338,9 +338,14 @@ __device__ __forceinline__ void dft16_tw_pair(double2 *a, double2 *b, TwF tw) {
 }
 #define PAA_DFT16_POS(q) (4 * ((q) % 4) + (q) / 4)
 
-// value of lane 15 of the row in every lane (v_readlane-free: row_bcast is not available inside a row, so
-// take the maximum of a non-negative non-decreasing scan instead: the inclusive scan's largest entry)
-__device__ __forceinline__ double dpp_bcast15(double v) { return group_max(v); }
+// value of lane 15 of the row in every lane: row_newbcast:15, two moves.  (Until round 10 this was group_max of the
+// inclusive scan -- four v_max_f64 and eight moves -- which is the same number whenever the scan does not decrease towards
+// lane 15; the lanes' prefix sums are separate trees, so a frame whose top 25 bins hold less than a rounding of the total
+// energy could return lane 14's prefix instead.  Exactly periodic synthetic inputs can get there -- a bin-centred tone or a
+// square wave whose period divides the window leaves only round-off in bins 375 .. 399 -- a recorded signal with any noise
+// floor cannot.  Lane 15's own entry is the value the roll-off's last compare uses anyway, so it is the consistent one; the
+// "onebin" clip of tests/test_fast800_bits_gpu.py is such an input and gives the earlier build's bits.)
+__device__ __forceinline__ double dpp_bcast15(double v) { return group_bcast<15>(v); }
 
 // fast_sqrt / mag_sqrt / fast_div / fast_log2 / fast_log10: device_common.hpp (shared with the other feature kernels)
 
@@ -683,7 +688,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             if (G::PAD == 0 && ch == 0) sp = (s16x2){0, before_reg};
             else sp = __builtin_bit_cast(s16x2, reinterpret_cast<const int *>(raw + G::PAD + CHUNK * ch)[-1]);
             sp = __builtin_elementwise_min(__builtin_elementwise_max(__builtin_elementwise_sub_sat(sp, zc_b), zc_lo), zc_two);
-            double sx2 = 0.0;            // sum x^2 (exact: every term is an integer below 2^31, the sum below 2^53)
+            // sum x^2 as a 64-bit integer: a pair gives up to 2^31 (unsigned), the chunk's 20 pairs stay below 2^36; one
+            // v_lshl_add_u64 per pair instead of a conversion and an FP64 addition, and ONE exact conversion per chunk
+            unsigned long long sx2i = 0;
             int sx = 0;                  // sum x
             int zacc = 0, zfirst = 0;
 #pragma unroll
@@ -700,13 +707,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
                     if (v4 == 0 && h == 0) zfirst = abs((int)(sgw & 0xffffu) - (int)(shw & 0xffffu));
                     asm("v_sad_u16 %0, %1, %2, %0" : "+v"(zacc) : "v"(sgw), "v"(shw));
                     sp = sg;
-                    sx2 += (double)(unsigned)__builtin_amdgcn_sdot2(cur, cur, 0, false);     // 2^31 for (-32768, -32768)
+                    sx2i += (unsigned long long)(unsigned)__builtin_amdgcn_sdot2(cur, cur, 0, false);     // 2^31 for (-32768, -32768)
                     sx = __builtin_amdgcn_sdot2(cur, zc_one, sx, false);
                 }
             }
             // sum (x - m_int)^2 and sum (x - m_int) in exact integer arithmetic, then the residual mean as before:
             // sum y^2 over the chunk = (inv/2^15)^2 * sum (x' - delta)^2 with x' = x - m_int, |delta| <= 1/2
             const double mi = nm.mi;
+            const double sx2 = (double)sx2i;
             const double e2 = fma(mi, fma((double)CHUNK, mi, -2.0 * (double)sx), sx2);
             const int s1 = sx - CHUNK * m_int;
             const double e = y_scale2 * fma(delta_mu, fma(-2.0, (double)s1, nm.chunk_dmu), e2);
@@ -890,19 +898,19 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // energy entropy: 80-sample block i = chunks CPF g + 2 i, + 1 (:34-51)
         const double eblk = (i < 10) ? cE[CPF * g + 2 * i] + cE[CPF * g + 2 * i + 1] : 0.0;
         const double e_tot = group_sum(eblk);
-        double ent_f, ent_e;
-        {
-            const double sf = fast_div(pblk, sP + kEps), se = fast_div(eblk, e_tot + kEps);
-            ent_f = group_sum(home ? -(sf * fast_log2(sf + kEps)) : 0.0);
-            ent_e = group_sum((i < 10) ? -(se * fast_log2(se + kEps)) : 0.0);
-        }
+        // the entropies' quotients p = block / total: sf counts in the ten home lanes, se in lanes 0 .. 9.  Their logarithms
+        // ride in the mel stage's fast_log2 calls, and the sums of -p log2 p in the four-way reduction after it (below)
+        const double sf = fast_div(pblk, sP + kEps), se = fast_div(eblk, e_tot + kEps);
         // zero crossings: 20 chunks of the frame minus the pair that straddles the frame start (:22-26)
         int zc = cZ[CPF * g + i] + ((i < 4) ? cZ[CPF * g + 16 + i] : 0) - ((i == 0) ? cF[CPF * g] : 0);
         zc = group_sum_i(zc) << zc_shift;
 
         PAA_TICK(5)
         // centroid, spread, flux (:57-82, :110-124)
-        const double r = (mx == 0.0) ? 1.0 / kEps : fast_div(1.0, mx);
+        // 1 / max and 1 / np.sum(X + eps) (the flux scale, below) are independent per-frame scalars that all sixteen lanes
+        // hold alike: ONE fast_div forms both -- lane 15 divides by sXe, the others by mx -- and row broadcasts hand them out
+        const double rq = fast_div(1.0, pick(i == 15, sXe, mx));
+        const double r = (mx == 0.0) ? 1.0 / kEps : group_bcast<0>(rq);
         const double den = sX * r + kEps;
         const double rden = fast_div(1.0, den);
         const double cen = (sIX * r) * rden;
@@ -910,7 +918,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // bins, same per-lane order, same group_sum: the same bits), so it is handed on instead of summed again: inside the
         // quad from the group before, into group 0 from the last group of the iteration before.  A run's first quad has no
         // such iteration: its group 0 is frame 0 (previous spectrum = itself, so rXp = rX) or a halo frame that is not stored
-        const double rX = fast_div(1.0, sXe);
+        const double rX = group_bcast<15>(rq);
         double rXp = rows_from_prev(rX, rX_carry);
         if (first_quad) rXp = (g == 0) ? rX : rXp;
         rX_carry = readlane63(rX);
@@ -930,10 +938,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             sFa = fma(f0d, f0d, sFa);
         }
         const double sSl = fma(cb, fma(cb, sXl, 2.0 * sMl), sQa + sQb);
-        double sSp = sSl * (f0sq * r), sFl = sFa + sFb;
-        sSp = group_sum(sSp);
-        sFl = group_sum(sFl);
-        const double spread = fast_sqrt(sSp * rden);
+        // the lane's terms of the spread and flux sums; the sums themselves: the four-way reduction after the mel stage.
+        // Level 1 of the spread sum is formed here, in every lane, as the FMA it has always compiled to (own product folded
+        // into the addition of the neighbour's rounded product: the lanes of a pair do NOT hold the same bits after it).
+        const double sSk = f0sq * r;
+        double sFl_l = sFa + sFb;
+        double sS1 = fma(sSl, sSk, dpp_mov<PAA_DPP_X1>(sSl * sSk));
+        asm volatile("" : "+v"(sS1), "+v"(sFl_l));
 
         // roll-off (:127-140): first k with cumsum(X^2)[k] + eps > 0.9 sum(X^2), in two levels.  The running energy is
         // defined as [energy before the lane (scan)] + [the lane's whole chunks before the bin (pc)] + [the squares inside the
@@ -967,6 +978,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // MFCC (:236-254): per-lane padded mel lists (host-built): class 0 = filter i, class 1 = filter 16+i,
         // class 2 = one half of filter 32 + (i & 7); the halves meet through a row rotation by 8
         double *mg = msp + 40 * g;
+        // the four sums only the writer lanes read: lane 13 spectral entropy, lane 12 energy entropy, lane 15 spread sum (times 1 / den), lane 14 flux
+        double ent_t;
         {
             // a filter covers consecutive bins, so only its first bin is tabulated (k*[i]); weights are
             // zero-padded to the class length and the bin index is clamped into the spectrum
@@ -1008,8 +1021,20 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             acc2 += dpp_mov<0x128>(acc2);                    // row_ror:8
             mg[i] = fast_log10(acc0 + kEps);
             mg[16 + i] = fast_log10(acc1 + kEps);
-            const double l2 = fast_log10(acc2 + kEps);
-            if (i < 8) mg[32 + i] = l2;
+            // class 2 fills lanes 0 .. 7 only, and each entropy needs ten logarithms: 8 + 10 + 10 arguments share TWO calls.
+            //   call A: lanes 0 .. 7 acc2; home lanes 8 10 12 13 15 their sf; lane 9 its se; lane 11 the se of lane 8 (row_shr:3)
+            //   call B: home lanes 0 2 4 5 7 their sf; lanes 1 3 6 their se; lanes 8 .. 15 the se of lanes 0 .. 7 (row_ror:8)
+            // (lane 14 of call A and the non-home lanes 9 11 14 of call B carry an argument nobody reads.)  The logarithms of se
+            // come back to the lane of their se, so every term -p log2 p is formed in its own lane from the same operands.
+            const bool lo8 = i < 8;
+            const double argA = pick(lo8, acc2, pick(i == 9, se, pick(i == 11, dpp_mov<0x113>(se), sf)));
+            const double argB = pick(lo8, pick(home, sf, se), dpp_mov<0x128>(se));
+            const double lgA = fast_log2(argA + kEps), lgB = fast_log2(argB + kEps);
+            if (lo8) mg[32 + i] = lgA * 0.30102999566398119521;          // fast_log10
+            const double lsf = pick(lo8, lgB, lgA);
+            const double lse = pick(lo8, pick(home, dpp_mov<0x128>(lgB), lgB), pick(i == 9, lgA, dpp_mov<0x103>(lgA)));   // lane 8: row_shl:3
+            const double tot = group_sum4_to_lanes(home ? -(sf * lsf) : 0.0, (i < 10) ? -(se * lse) : 0.0, sS1, sFl_l, i);
+            ent_t = pick(i == 15, tot * rden, tot);              // lane 15: the spread's radicand
         }
         PAA_TICK(7)
         // chroma (:277-321): lane i < 12 = pitch class i, padded gather list in ascending slot order
@@ -1054,18 +1079,19 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         if (i == 15) {
             fg[0] = ((double)zc * 0.5) * (1.0 / (double)(W - 1));
             fg[1] = e_tot * (1.0 / (double)W);
-            fg[2] = ent_e;
             fg[3] = cen * r_half_fs;
-            fg[4] = spread * r_half_fs;
-            fg[5] = ent_f;
-            fg[6] = (t == 0) ? 0.0 : sFl;      // first frame: previous spectrum = itself (:624-625)
             fg[7] = (first == 0x7fffffff) ? 0.0 : (double)first * (1.0 / (double)NF);
         }
         {   // population std of the 12 chroma values (:667), by DPP inside the group
             const double m = group_sum((i < 12) ? chroma : 0.0) / 12.0;
             const double d = (i < 12) ? chroma - m : 0.0;
             const double var = group_sum(d * d) / 12.0;
-            if (i == 14) fg[33] = fast_sqrt(var);
+            // the spread's square root (lane 15) and the chroma deviation's (lane 14) in one call
+            const double sq = fast_sqrt(pick(i == 15, ent_t, var));
+            if (i == 14) fg[33] = sq;
+            // lanes 12 .. 15 hold the four sums (group_sum4_to_lanes): features 2, 5, 6, 4
+            const double wv = pick(i == 15, sq * r_half_fs, (i == 14 && t == 0) ? 0.0 : ent_t);     // first frame: previous spectrum = itself (:624-625)
+            if (i >= 12) fg[(0x4652 >> (4 * (i - 12))) & 7] = wv;
         }
         wsync();
 
