@@ -350,7 +350,7 @@ int paa_debug_knn_split_geometry(int32_t *out10);
  * C <= 0, gamma <= 0 (RBF), eps <= 0, kernel_type other than 0 / 2, max_iter < 1, an empty task, a job whose training list holds
  * fewer than two classes.  PAA_ERR_UNSUPPORTED, likewise before the device is touched: n_dims > 256 (PAA_SMO_MAX_DIMS), a task of
  * more than 8192 rows (PAA_SMO_MAX_ROWS), a job with more than 64 classes.  An empty test list is legal.  Synchronous, host
- * buffers in and out.  Not served: Platt probabilities (probability=True's second half), a model file, SVR.              */
+ * buffers in and out.  Not served: Platt probabilities (probability=True's second half), a model file.                   */
 #define PAA_SMO_MAX_ROWS 8192
 #define PAA_SMO_MAX_DIMS 256
 #define PAA_SMO_CONVERGED 2
@@ -367,6 +367,48 @@ int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const
 /* tests: out6 = threads per workgroup, lane groups, rows per task, test rows per scoring workgroup, default iterations per
  * launch, dims                                                                                                        */
 int paa_debug_smo_geometry(int32_t *out6);
+
+/* ---- the SVR half of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855 with train_svm_regression :222-226) -----------
+ * For "svm" / "svm_rbf" evaluate_regression fits sklearn.svm.SVR(C, kernel) (epsilon 0.1, gamma 'scale') once per split: libsvm's
+ * solve_epsilon_svr hands Solver::Solve a dual of 2 n variables over n rows -- variable v stands for row v mod n with the sign +1
+ * for v < n and -1 for v >= n, the linear term epsilon - y_t / epsilon + y_t, Q_uv = sign_u sign_v K(row u, row v).  Here a TASK is
+ * one such problem over rows of ONE resident sample matrix and its resident targets; one workgroup solves one task with libsvm's
+ * Solver without shrinking in FP64 throughout (the selections, TAU, the clip cases and calculate_rho of paa_smo_tasks_f64 over the
+ * indices 0 .. 2 n - 1; a kernel row is formed once per ROW and serves both of its variables), and all tasks of a call run side by
+ * side, relaunched as paa_smo_tasks_f64 relaunches (iters_per_launch; bit-identical outputs for any value, alone or in any batch).
+ *
+ * paa_svr_tasks_f64 -- the solver alone:
+ *   X [n_samples][n_dims], y [n_samples]   every sample, row-major, and its finite target (1 <= n_dims <= 256, 1 <= n_samples < 2^31)
+ *   task_off [n_tasks + 1], task_idx [task_off[n_tasks]]   task t owns the rows task_idx[task_off[t] .. task_off[t+1]-1]; 1..8192 rows
+ *   mean, std [n_tasks][n_dims]   task t's standardisation, (x - mean_t) / std_t with an IEEE division on the load path
+ *   C, gamma, epsilon [n_tasks]   C > 0; gamma > 0 is read for kernel_type 2 only; epsilon >= 0
+ *   kernel_type, eps, max_iter, iters_per_launch   as for paa_smo_tasks_f64
+ * Outputs: beta [task_off[n_tasks]] = alpha_t - alpha_{t+n}; per task rho, iterations, gap, status (PAA_SMO_CONVERGED /
+ * PAA_SMO_NOT_CONVERGED: outputs are those of the last iterate, finite) and n_sv (rows with beta != 0); train_pred
+ * [task_off[n_tasks]], the prediction of every row of the task, G_t - epsilon + y_t - rho from the gradient the solver holds;
+ * n_launches may be NULL.  The prediction for a standardised z is sum_t beta_t K(z_t, z) - rho.
+ *
+ * paa_svr_fit_splits_f64 -- the sweep, in the job form of paa_knn_splits_f64 (train_off / train_idx, test_off / test_idx, mean / std
+ * [n_jobs][n_dims]) plus y [n_samples] and C, gamma, epsilon [n_jobs].  Job j is ONE task over its training list in list order; its
+ * test rows are scored over the rows with beta != 0 in that order.
+ *   pred_out [Q]             the predictions, Q = test_off[n_jobs] rows in job order then test-list order
+ *   train_pred_out [train_off[n_jobs]]   (may be NULL) the training predictions of every job, as train_pred above
+ *   job_iterations, job_status, job_n_sv [n_jobs]   (each may be NULL);  n_launches (may be NULL)
+ * PAA_ERR_ARG, with a message and before the device is touched: a null pointer (other than the optional outputs), offsets that do
+ * not begin at 0 or decrease, an index outside 0..n_samples-1, a target that is not finite, n_dims < 1, C <= 0, gamma <= 0 (RBF),
+ * epsilon < 0, eps <= 0, kernel_type other than 0 / 2, max_iter < 1, an empty task or training list.  PAA_ERR_UNSUPPORTED, likewise
+ * before the device is touched: n_dims > 256 (PAA_SMO_MAX_DIMS), a task of more than 8192 rows (PAA_SMO_MAX_ROWS).  An empty test
+ * list is legal.  Synchronous, host buffers in and out.  Not served: nu-SVR, sample weights, a model file.              */
+int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                      const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                      const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
+                      double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
+                      int32_t *n_launches);
+int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
+                           const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                           const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type,
+                           double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
+                           int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches);
 
 /* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
  * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as

@@ -46,7 +46,11 @@ value of evaluate_regression -- scores every vector in one launch (kernels_svr.h
 in the model's support-vector order, each model after its own standardisation); a forest regressor is the averaged forest
 with one output (paa_forest_create kind 2), bit-identical to RandomForestRegressor.predict.  Only the fitted arrays are read
 (SVR: support_vectors_, _dual_coef_, _intercept_, _gamma, kernel), so SvrArrays / ForestArrays(kind="regressor") work
-without scikit-learn; the fits of the trainers and of evaluate_regression are scikit-learn's and dominate their run time.
+without scikit-learn; the fits of the trainers and of evaluate_regression are scikit-learn's and dominate their run time --
+by default.  With svm_fit="device" evaluate_regression fits "svm" / "svm_rbf" on the GPU too: every split of every parameter
+value is one epsilon-SVR problem of svr_smo_kernel (libsvm's solver without shrinking, FP64; a dual of 2 n variables over n
+rows whose kernel rows are formed once per row), all of them side by side, scored in the same call
+(paa_svr_fit_splits_f64); the final fit of feature_extraction_train_regression and its model file stay scikit-learn's.
 """
 import collections
 import ctypes as C
@@ -1089,6 +1093,122 @@ def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3
     return SvmSplitResult(label.astype(np.int64), dec, p.test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
 
 
+class SvrSolveResult:
+    """What svr_solve returns: beta and train_pred (lists of one array per task, in the task's row order: alpha_t - alpha_{t+n}
+    and the prediction of the row), rho, iterations, gap, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv (rows with
+    beta != 0) per task and the number of kernel launches."""
+
+    def __init__(self, beta, train_pred, rho, iterations, gap, status, n_sv, n_launches):
+        self.beta, self.train_pred, self.rho, self.iterations, self.gap = beta, train_pred, rho, iterations, gap
+        self.status, self.n_sv, self.n_launches = status, n_sv, n_launches
+
+
+def _targets(y, n_samples):
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+    if y.shape[0] != n_samples:
+        raise ValueError("%d targets for %d samples" % (y.shape[0], n_samples))
+    return y
+
+
+def svr_solve(X, y, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0):
+    """Epsilon-SVR dual problems over ONE sample matrix and its targets, all solved side by side (paa_svr_tasks_f64,
+    svr_smo_kernel: libsvm's solve_epsilon_svr over its Solver without shrinking, FP64).  X [n_samples][n_dims]; y [n_samples];
+    a task is (rows, mean, scale, C, gamma, epsilon): the rows X[rows] standardised as (x - mean) / scale with the targets
+    y[rows], gamma read for kernel="rbf" only (None: 1 / n_dims).  iters_per_launch bounds one kernel launch (0: the library's
+    default); results do not depend on it.  A task that stops at max_iter has the status SMO_NOT_CONVERGED and a warning is
+    issued, as scikit-learn does.  The prediction for a standardised z is sum_t beta_t K(z_t, z) - rho; train_pred holds it
+    for the task's own rows, read from the solver's gradient.  Returns an SvrSolveResult."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    tasks = list(tasks)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("sample matrix of shape %s" % (X.shape,))
+    if not tasks:
+        raise ValueError("no tasks")
+    _check_kernel(kernel)
+    n_samples, n_dims = X.shape
+    y = _targets(y, n_samples)
+    rows, means, scales, Cs, gammas, epsilons = [], [], [], [], [], []
+    for t, task in enumerate(tasks):
+        if len(task) != 6:
+            raise ValueError("task %d: (rows, mean, scale, C, gamma, epsilon) expected" % t)
+        rows.append(_index_list(task[0], "row", t))
+        mean, scale = _stats(task[1], task[2], n_dims)
+        means.append(mean)
+        scales.append(scale)
+        Cs.append(float(task[3]))
+        gammas.append(1.0 / n_dims if task[4] is None else float(task[4]))
+        epsilons.append(float(task[5]))
+    idx, off = _packed(rows, np.int32)
+    mean, scale = np.stack(means), np.stack(scales)
+    C_arr, g_arr, e_arr = (np.array(v, dtype=np.float64) for v in (Cs, gammas, epsilons))
+    n_tasks, total = len(tasks), int(off[-1])
+    beta, train_pred, rho, gap = np.zeros(total), np.zeros(total), np.zeros(n_tasks), np.zeros(n_tasks)
+    iterations, status, n_sv = (np.zeros(n_tasks, dtype=np.int32) for _ in range(3))
+    launches = np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_svr_tasks_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, _ffi.as_f64p(y), n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_f64p(mean),
+        _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps),
+        int(max_iter), int(iters_per_launch), _ffi.as_f64p(beta), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
+        _ffi.as_i32p(status), _ffi.as_i32p(n_sv), _ffi.as_f64p(train_pred), _ffi.as_i32p(launches)))
+    _warn_not_converged(status, int(max_iter))
+    per_task = lambda a: [a[off[t]:off[t + 1]] for t in range(n_tasks)]
+    return SvrSolveResult(per_task(beta), per_task(train_pred), rho, iterations, gap, status, n_sv, int(launches[0]))
+
+
+class SvrSplitResult(_SplitResult):
+    """What svr_split_fit_predict returns: pred [Q] (the test predictions), train_pred [T] or None (the training predictions,
+    job j owns train_off[j] .. train_off[j + 1] - 1), test_off / train_off [n_jobs + 1], gamma [n_jobs] (the values the fits ran
+    with) and per job iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel."""
+
+    def __init__(self, pred, train_pred, test_off, train_off, gamma, iterations, status, n_sv, n_launches):
+        self.pred, self.train_pred, self.test_off, self.train_off, self.gamma = pred, train_pred, test_off, train_off, gamma
+        self.iterations, self.status, self.n_sv, self.n_launches = iterations, status, n_sv, n_launches
+
+    def job(self, j):
+        """(test predictions, training predictions or None, iterations, status, n_sv) of job j."""
+        t0, t1 = int(self.train_off[j]), int(self.train_off[j + 1])
+        return (self.pred[self._rows(j)], None if self.train_pred is None else self.train_pred[t0:t1], int(self.iterations[j]),
+                int(self.status[j]), int(self.n_sv[j]))
+
+
+def svr_split_fit_predict(X, y, jobs, kernel="linear", gamma=None, epsilon=0.1, eps=1e-3, train_pred=False, max_iter=10**7,
+                          iters_per_launch=0):
+    """SVR(C, kernel, gamma, epsilon).fit(train).predict(test) for every job of a sweep over ONE sample matrix
+    (paa_svr_fit_splits_f64: every job is one epsilon-SVR problem of svr_smo_kernel, all of them side by side; then the test
+    rows of every job are scored).  X [n_samples][n_dims]; y [n_samples]; a job is (train_idx, test_idx, mean, scale, C).
+    gamma=None is scikit-learn's SVR default, 'scale': per job 1 / (n_dims * Z.var()) of its standardised training rows Z (1
+    when that variance is 0), formed with NumPy on the host.  train_pred=True also returns the predictions of every job's
+    training rows, which the solver reads from its final gradient: no training row is scored again.  Returns an
+    SvrSplitResult."""
+    p = _pack_jobs(X, y, jobs, "C", float, kernel)
+    n_samples, n_dims = p.X.shape
+    targets = _targets(p.raw, n_samples)
+    n_jobs = len(p.last)
+    C_arr = np.array(p.last, dtype=np.float64)
+    if gamma is None:
+        g_arr = np.ones(n_jobs)
+        for j, rows in enumerate(p.inside):
+            var = ((p.X[rows] - p.mean[j]) / p.scale[j]).var() if kernel == "rbf" and rows.shape[0] else 0.0
+            if var != 0:
+                g_arr[j] = 1.0 / (n_dims * var)
+    else:
+        g_arr = np.full(n_jobs, float(gamma), dtype=np.float64)
+    e_arr = np.full(n_jobs, float(epsilon), dtype=np.float64)
+    Q, T = int(p.test_off[-1]), int(p.train_off[-1])
+    pred = np.zeros(Q)
+    tp = np.zeros(T) if train_pred else None
+    iterations, status, n_sv = (np.zeros(n_jobs, dtype=np.int32) for _ in range(3))
+    launches = np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_svr_fit_splits_f64(
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_f64p(targets), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
+        _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch),
+        _ffi.as_f64p(pred), _ffi.as_f64p(tp) if train_pred else None, _ffi.as_i32p(iterations), _ffi.as_i32p(status),
+        _ffi.as_i32p(n_sv), _ffi.as_i32p(launches)))
+    _warn_not_converged(status, int(max_iter))
+    return SvrSplitResult(pred, tp, p.test_off, p.train_off, g_arr, iterations, status, n_sv, int(launches[0]))
+
+
 def _draw_split(n_samples, train_percentage):
     """One random split as (train indices, test indices): train_test_split over the sample indices consumes NumPy's
     global state exactly as the reference's train_test_split(X, y, ...) (:648-649) does, and X[train], X[test], y[test]
@@ -1339,16 +1459,30 @@ def _fit_regressor(features, labels, method_name, param):
     return model
 
 
-def evaluate_regression(features, labels, n_exp, method_name, params):
+def _check_svr_fit(svm_fit, method_name):
+    if svm_fit not in ("sklearn", "device"):
+        raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
+    if svm_fit == "device" and method_name not in _SVM_TYPES:
+        raise ValueError("svm_fit='device' serves the regression methods %s, not %r" % (" and ".join(_SVM_TYPES), method_name))
+
+
+def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit="sklearn"):
     """Picks the parameter value with the lowest cross-validated squared error (reference :774-855): for every value,
     n_exp random 90 / 10 splits of the standardised samples.  np.random.permutation is consumed and the models are
     fitted in the reference's order (RandomForestRegressor draws from the same global state), by scikit-learn; the
     predictions are deferred: per parameter value the n_exp models x ALL samples go out in one bank launch ("randomforest":
     one traversal per forest), and the test and training errors are picked out on the host with the stored permutations.
     Prints the reference's table; returns (best parameter, its error, its baseline error).  The fits dominate the run
-    time: the launch removes the per-vector predict loop and nothing else."""
+    time: the launch removes the per-vector predict loop and nothing else.
+    svm_fit="device" (keyword only; "svm" / "svm_rbf", "randomforest" raises ValueError): ALL len(params) x n_exp permutations
+    are drawn up front with np.random.permutation, in the reference's order (an SVR fit draws nothing, so both modes see the
+    same splits under one seed), and ONE sweep (svr_split_fit_predict: epsilon-SVR with scikit-learn's defaults epsilon 0.1,
+    gamma 'scale', tol 1e-3) fits and scores every split; the training errors come from the solver's gradient.  The errors,
+    the baseline, the table and the return value are formed as above.  svm_fit="sklearn" (the default) is the behaviour
+    described above, untouched."""
     if method_name not in _REGRESSION_TYPES:
         raise NotImplementedError("regression method %r: 'svm', 'svm_rbf' or 'randomforest'" % (method_name,))
+    _check_svr_fit(svm_fit, method_name)
     from sklearn.preprocessing import StandardScaler
     features_norm = StandardScaler().fit_transform(features)
     labels = np.asarray(labels)
@@ -1357,20 +1491,30 @@ def evaluate_regression(features, labels, n_exp, method_name, params):
     zeros, ones = np.zeros(features_norm.shape[1]), np.ones(features_norm.shape[1])
     all_samples = np.ascontiguousarray(features_norm.T)
     errors_all, er_train_all, er_base_all = [], [], []
-    for param in params:
-        perms, models = [], []
-        for _ in range(n_exp):
-            perm = np.random.permutation(range(n_samples))
-            models.append(_fit_regressor(features_norm[perm[:n_train]], [labels[i] for i in perm[:n_train]], method_name, param))
-            perms.append(perm)
-        pred = regress(models, method_name, all_samples, zeros, ones)           # [n_exp][n_samples]
+    if svm_fit == "device":                            # one sweep over every split of every parameter value
+        all_perms = [[np.random.permutation(range(n_samples)) for _ in range(n_exp)] for _ in params]
+        sweep = svr_split_fit_predict(features_norm, labels, [(perm[:n_train], perm[n_train:], zeros, ones, float(param))
+                                                              for param, perms in zip(params, all_perms) for perm in perms],
+                                      kernel="rbf" if method_name == "svm_rbf" else "linear", train_pred=True)
+    for p, param in enumerate(params):
+        if svm_fit == "device":
+            perms = all_perms[p]
+            picked = [sweep.job(p * n_exp + e)[:2] for e in range(n_exp)]          # (test, training) predictions per experiment
+        else:
+            perms, models = [], []
+            for _ in range(n_exp):
+                perm = np.random.permutation(range(n_samples))
+                models.append(_fit_regressor(features_norm[perm[:n_train]], [labels[i] for i in perm[:n_train]], method_name, param))
+                perms.append(perm)
+            pred = regress(models, method_name, all_samples, zeros, ones)           # [n_exp][n_samples]
+            picked = [(pred[e, perm[n_train:]], pred[e, perm[:n_train]]) for e, perm in enumerate(perms)]
         errors, errors_train, errors_base = [], [], []
-        for e, perm in enumerate(perms):
+        for (pred_test, pred_train), perm in zip(picked, perms):
             train, test = perm[:n_train], perm[n_train:]
             baseline = np.mean([labels[i] for i in train])
-            errors.append(np.array([(pred[e, i] - labels[i]) * (pred[e, i] - labels[i]) for i in test]).mean())
+            errors.append(np.array([(pred_test[k] - labels[i]) * (pred_test[k] - labels[i]) for k, i in enumerate(test)]).mean())
             errors_base.append(np.array([(baseline - labels[i]) * (baseline - labels[i]) for i in test]).mean())
-            errors_train.append(np.mean(np.abs(pred[e, train] - labels[train])))
+            errors_train.append(np.mean(np.abs(pred_train - labels[train])))
         errors_all.append(np.array(errors).mean())
         er_train_all.append(np.array(errors_train).mean())
         er_base_all.append(np.array(errors_base).mean())
@@ -1390,11 +1534,13 @@ def save_parameters(path, *parameters):
 
 
 def feature_extraction_train_regression(folder_name, mid_window, mid_step, short_window, short_step, model_type, model_name,
-                                        compute_beat=False):
+                                        compute_beat=False, *, svm_fit="sklearn"):
     """Trains one regression model per CSV file of a folder of audio files (reference :370-489): every `<task>.csv` pairs
     file names with target values; features come from multiple_directory_feature_extraction (GPU), the parameter from
     evaluate_regression, the final fit from scikit-learn; `model_name_<task>` and `model_name_<task>MEANS` are written as
-    the reference writes them.  Returns (errors, baseline errors, best parameters)."""
+    the reference writes them.  svm_fit (keyword only) goes to evaluate_regression: "device" tunes C on the GPU; the final fit
+    and the model file, a pickled SVR, stay scikit-learn's.  Returns (errors, baseline errors, best parameters)."""
+    _check_svr_fit(svm_fit, model_type)
     import csv
     import glob
     import ntpath
@@ -1428,7 +1574,7 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
     errors, errors_base, best_params = [], [], []
     for X, y, name in zip(task_features, task_labels, task_names):
         print("Regression task " + name)
-        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params)
+        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params, svm_fit=svm_fit)
         errors.append(error)
         errors_base.append(base_error)
         best_params.append(best)

@@ -1,10 +1,13 @@
-// The bank of epsilon-SVR models (kernels_svr.hpp: audioTrainTest.regression_wrapper for the "svm" / "svm_rbf" models) --
-// own translation unit, see model_launch.hpp.
+// The epsilon-SVR family: the bank of fitted models (kernels_svr.hpp: audioTrainTest.regression_wrapper for the "svm" / "svm_rbf"
+// models) and the batched solver that fits them in the SVR split sweep (kernels_svrfit.hpp: the SVR fits of
+// audioTrainTest.evaluate_regression; the sweep scores with svc_pairs_kernel of family_smo.hip) -- own translation unit, see
+// model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
 #include "model_launch.hpp"
 #include "kernels_svr.hpp"
+#include "kernels_svrfit.hpp"
 
 namespace paa {
 namespace launch {
@@ -18,6 +21,18 @@ int svr(const svr::SvrDev &m, const double *d_feats, long long ld, long long n_v
     const int yblocks = (m.n_models + svr::kModelChunk - 1) / svr::kModelChunk;
     hipLaunchKernelGGL(svr::svr_bank_kernel, dim3((unsigned)xblocks, (unsigned)yblocks), dim3(svr::kThreads), 0, stream, m, d_feats,
                        ld, n_vec, d_out, ld_out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream) {
+    if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > smo::kMaxRows) return -2;
+    if (n_live < 1 || budget < 1) return -1;
+    const int pitch = (m.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
+    const size_t lds = ((size_t)4 * pitch + n_max) * sizeof(double);
+    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&svrfit::svr_smo_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(svrfit::svr_smo_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), lds, stream, m, d_live, budget);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -54,27 +54,28 @@ static int smo_state_alloc(SmoState &s, smo::SmoDev &m, size_t rows, size_t n_ta
     return PAA_OK;
 }
 
-// Solves a batch: allocates its state into s and m, then runs every task to its stop: a launch gives each unfinished task at
-// most `budget` iterations (iters_per_launch, 0: the default), the host reads the status words, compacts the unfinished tasks
-// and launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
-static int smo_solve_batch(smo::SmoDev &m, SmoState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, int iters_per_launch,
-                           std::vector<int> &status, int *n_launches) {
-    int rc;
-    if ((rc = smo_state_alloc(s, m, rows, tasks.size()))) return rc;
+// The relaunch loop of a batch of solver tasks (smo_kernel; svr_smo_kernel of lib_svrfit.hpp): step(n_live, n_max, budget) gives
+// each of the n_live unfinished tasks listed in d_live (n_max: the longest of them) at most `budget` iterations
+// (iters_per_launch, 0: the default), the host reads the status words d_status [n_tasks], compacts the unfinished tasks and
+// launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
+template <typename Step>
+static int smo_relaunch(const std::vector<smo::SmoTask> &tasks, int max_iter, int iters_per_launch, int *d_live, const int *d_status,
+                        std::vector<int> &status, int *n_launches, Step step) {
     const int budget = iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch;
     const int n_tasks = (int)tasks.size();
     std::vector<int> live(n_tasks);
     for (int t = 0; t < n_tasks; ++t) live[t] = t;
     status.assign(n_tasks, smo::kFresh);
-    const long long launch_cap = (long long)m.max_iter / budget + 2;     // every launch advances every live task by `budget`
+    const long long launch_cap = (long long)max_iter / budget + 2;       // every launch advances every live task by `budget`
     long long launches = 0;
     while (!live.empty()) {
         if (launches++ >= launch_cap) return fail(PAA_ERR_HIP, "the solver made no progress in %lld launches", launch_cap);
         int n_max = 0;
         for (int t : live) n_max = std::max(n_max, tasks[t].n);
-        HIP_TRY(hipMemcpyAsync(s.live, live.data(), live.size() * 4, hipMemcpyHostToDevice, cs()));
-        LAUNCH_TRY("SMO", launch::smo_step(m, s.live, (int)live.size(), n_max, budget, cs()));
-        HIP_TRY(hipMemcpyAsync(status.data(), m.status, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+        HIP_TRY(hipMemcpyAsync(d_live, live.data(), live.size() * 4, hipMemcpyHostToDevice, cs()));
+        int rc;
+        if ((rc = step((int)live.size(), n_max, budget))) return rc;
+        HIP_TRY(hipMemcpyAsync(status.data(), d_status, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
         HIP_TRY(hipStreamSynchronize(cs()));
         size_t kept = 0;
         for (int t : live)
@@ -83,6 +84,17 @@ static int smo_solve_batch(smo::SmoDev &m, SmoState &s, const std::vector<smo::S
     }
     if (n_launches) *n_launches = (int)launches;
     return PAA_OK;
+}
+
+// Solves a batch: allocates its state into s and m, then runs every task to its stop (smo_relaunch)
+static int smo_solve_batch(smo::SmoDev &m, SmoState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, int iters_per_launch,
+                           std::vector<int> &status, int *n_launches) {
+    int rc;
+    if ((rc = smo_state_alloc(s, m, rows, tasks.size()))) return rc;
+    return smo_relaunch(tasks, m.max_iter, iters_per_launch, s.live, m.status, status, n_launches, [&](int n_live, int n_max, int budget) {
+        LAUNCH_TRY("SMO", launch::smo_step(m, s.live, n_live, n_max, budget, cs()));
+        return (int)PAA_OK;
+    });
 }
 
 // the solver's view of an uploaded batch: the staged matrix, the uploaded tasks | mean | scale | idx | sign and the parameters

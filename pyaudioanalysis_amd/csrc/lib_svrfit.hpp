@@ -1,0 +1,201 @@
+// The SVR fits of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855 with train_svm_regression :222-226) on the device:
+// a batch of epsilon-SVR dual problems (tasks) over ONE uploaded sample matrix and its targets, solved by relaunching
+// svr_smo_kernel until every task has stopped (smo_relaunch, lib_smo.hpp), and the split sweep built on it: one task per job,
+// then svc_pairs_kernel over the test rows, a job being one "pair" whose alpha_y is beta -- its decision value is the prediction.
+// Kernels: kernels_svrfit.hpp (family_svr.hip), kernels_smo.hpp (family_smo.hip).
+#pragma once
+
+// what a task adds to smo_task_check: the width of its tube
+static int svr_epsilon_check(int t, double epsilon) {
+    if (!(epsilon >= 0.0) || !std::isfinite(epsilon)) return fail(PAA_ERR_ARG, "task %d: epsilon = %g", t, epsilon);
+    return PAA_OK;
+}
+static int svr_targets_check(const double *y, int64_t n_samples) {
+    for (int64_t i = 0; i < n_samples; ++i)
+        if (!std::isfinite(y[i])) return fail(PAA_ERR_ARG, "the target of sample %lld is %g", (long long)i, y[i]);
+    return PAA_OK;
+}
+
+// The state of a batch on the device, freed on return: alpha | G [2 rows]; QD | beta | train_pred [rows]; rho | gap [tasks]; iter |
+// status | n_sv | live [tasks]; label [n_q] (what svc_pairs_kernel writes beside the decision values)
+struct SvrFitState {
+    DevBlock block;
+    int *live = nullptr, *label = nullptr;
+};
+static int svr_state_alloc(SvrFitState &s, svrfit::SvrDev &m, size_t rows, size_t n_tasks, size_t n_q) {
+    const size_t b_rows = up256(rows * 8), b_task8 = up256(n_tasks * 8), b_task4 = up256(n_tasks * 4);
+    HIP_TRY(hipMalloc(&s.block.p, 7 * b_rows + 2 * b_task8 + 4 * b_task4 + up256(n_q * 4)));
+    char *p = (char *)s.block.p;
+    m.alpha = (double *)p;      p += 2 * b_rows;
+    m.G = (double *)p;          p += 2 * b_rows;
+    m.QD = (double *)p;         p += b_rows;
+    m.beta = (double *)p;       p += b_rows;
+    m.train_pred = (double *)p; p += b_rows;
+    m.rho = (double *)p;        p += b_task8;
+    m.gap = (double *)p;        p += b_task8;
+    m.iter = (int *)p;          p += b_task4;
+    m.status = (int *)p;        p += b_task4;
+    m.n_sv = (int *)p;          p += b_task4;
+    s.live = (int *)p;          p += b_task4;
+    s.label = (int *)p;
+    HIP_TRY(hipMemsetAsync(m.iter, 0, 2 * b_task4, cs()));       // iteration 0, status kFresh
+    return PAA_OK;
+}
+
+// Solves a batch: allocates its state into s and m, then runs every task to its stop (smo_relaunch)
+static int svr_solve_batch(svrfit::SvrDev &m, SvrFitState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, size_t n_q,
+                           int iters_per_launch, std::vector<int> &status, int *n_launches) {
+    int rc;
+    if ((rc = svr_state_alloc(s, m, rows, tasks.size(), n_q))) return rc;
+    return smo_relaunch(tasks, m.max_iter, iters_per_launch, s.live, m.status, status, n_launches, [&](int n_live, int n_max, int budget) {
+        LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
+        return (int)PAA_OK;
+    });
+}
+
+// the solver's view of an uploaded batch: the staged matrix, the uploaded y | tasks | epsilon | mean | scale | idx and the parameters
+static svrfit::SvrDev svr_dev(const double *X, const BlockPart &y, const BlockPart &tasks, const BlockPart &epsilon, const BlockPart &mean,
+                              const BlockPart &scale, const BlockPart &idx, int n_dims, int kernel_type, double eps, int max_iter) {
+    svrfit::SvrDev m{};
+    m.X = X;
+    m.y = (const double *)y.dev;
+    m.tasks = (const smo::SmoTask *)tasks.dev;
+    m.epsilon = (const double *)epsilon.dev;
+    m.mean = (const double *)mean.dev;
+    m.scale = (const double *)scale.dev;
+    m.idx = (const int *)idx.dev;
+    m.n_dims = n_dims;
+    m.rbf = kernel_type == 2;
+    m.max_iter = max_iter;
+    m.eps = eps;
+    return m;
+}
+
+// the tasks of index lists list_off [n + 1]: task t is list t with the statistics row t; every check of a task
+static int svr_tasks(std::vector<smo::SmoTask> &tasks, int n, const int64_t *list_off, const double *C, const double *gamma,
+                     const double *epsilon, int kernel_type) {
+    tasks.resize(n);
+    for (int t = 0; t < n; ++t) {
+        int rc;
+        if ((rc = smo_task_check(t, list_off[t + 1] - list_off[t], C[t], gamma[t], kernel_type))) return rc;
+        if ((rc = svr_epsilon_check(t, epsilon[t]))) return rc;
+        tasks[t] = {(long long)list_off[t], (int)(list_off[t + 1] - list_off[t]), t, C[t], gamma[t]};
+    }
+    return PAA_OK;
+}
+
+// The solver alone (libsvm's solve_epsilon_svr over Solver::Solve, svm.cpp, as svm_train_one runs it under SVR.fit): see paa_hip.h
+extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                                 const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                                 const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
+                                 double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
+                                 int32_t *n_launches) {
+    if (!X || !y || !task_off || !task_idx || !mean || !std || !C || !gamma || !epsilon || !beta || !rho || !iterations || !gap || !status ||
+        !n_sv || !train_pred)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
+    if ((rc = sweep_offsets_check(task_off, n_tasks, "task"))) return rc;
+    const int64_t rows = task_off[n_tasks];
+    std::vector<smo::SmoTask> tasks;
+    if ((rc = svr_tasks(tasks, n_tasks, task_off, C, gamma, epsilon, kernel_type))) return rc;
+    if ((rc = sweep_index_check(task_idx, rows, n_samples, "row"))) return rc;
+    if ((rc = svr_targets_check(y, n_samples))) return rc;
+    if ((rc = ensure_init())) return rc;
+    const size_t sb = (size_t)n_tasks * n_dims * 8;
+    DevBlock block;
+    BlockPart parts[] = {{y, (size_t)n_samples * 8, 8}, {tasks.data(), tasks.size() * sizeof(smo::SmoTask), 8}, {epsilon, (size_t)n_tasks * 8, 8},
+                         {mean, sb, 8}, {std, sb, 8}, {task_idx, (size_t)rows * 4, 4}};
+    if ((rc = block_upload(block, parts, 6, "the SVR tasks"))) return rc;
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[5], n_dims, kernel_type, eps, max_iter);
+    SvrFitState s;
+    std::vector<int> st_words;
+    if ((rc = svr_solve_batch(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches))) return rc;
+    HIP_TRY(hipMemcpyAsync(beta, m.beta, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(train_pred, m.train_pred, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(rho, m.rho, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(gap, m.gap, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(iterations, m.iter, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(n_sv, m.n_sv, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipStreamSynchronize(cs()));
+    std::copy(st_words.begin(), st_words.end(), status);
+    return PAA_OK;
+}
+
+// The SVR half of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855): every split a job, every job one task over its
+// training list; see paa_hip.h
+extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
+                                      const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                                      const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type,
+                                      double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
+                                      int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches) {
+    // check
+    if (!X || !y || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !epsilon || !pred_out)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if ((rc = sweep_jobs_check(n_jobs, train_off, test_off))) return rc;
+    const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
+    if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
+    if ((rc = sweep_index_check(test_idx, n_q, n_samples, "test"))) return rc;
+    std::vector<smo::SmoTask> tasks;
+    if ((rc = svr_tasks(tasks, n_jobs, train_off, C, gamma, epsilon, kernel_type))) return rc;
+    if ((rc = svr_targets_check(y, n_samples))) return rc;
+    if ((rc = ensure_init())) return rc;
+    // upload: a job is the one pair of two "classes" for the scoring kernel, its task the job's own number
+    const std::vector<knn::SplitBlock> blocks = sweep_blocks(test_off, n_jobs, smo::kQueriesPerBlock);
+    std::vector<int> job_task(n_jobs + 1), job_k(n_jobs, 2);
+    for (int j = 0; j <= n_jobs; ++j) job_task[j] = j;
+    const size_t sb = (size_t)n_jobs * n_dims * 8;
+    const knn::SplitBlock none{0, 0};
+    DevBlock block;
+    BlockPart parts[] = {{y, (size_t)n_samples * 8, 8},
+                         {tasks.data(), tasks.size() * sizeof(smo::SmoTask), 8},
+                         {epsilon, (size_t)n_jobs * 8, 8},
+                         {mean, sb, 8},
+                         {std, sb, 8},
+                         {test_off, (size_t)(n_jobs + 1) * 8, 8},
+                         {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
+                         {train_idx, (size_t)n_t * 4, 4},
+                         {n_q ? test_idx : train_idx, (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
+                         {job_task.data(), (size_t)(n_jobs + 1) * 4, 4},
+                         {job_k.data(), (size_t)n_jobs * 4, 4}};
+    if ((rc = block_upload(block, parts, 11, "the SVR split jobs"))) return rc;
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {{n_q ? pred_out : nullptr, (size_t)n_q * 8}}))) return rc;
+    // solve the batch
+    svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[7], n_dims, kernel_type, eps, max_iter);
+    SvrFitState s;
+    std::vector<int> st_words;
+    if ((rc = svr_solve_batch(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches))) return rc;
+    if (job_iterations) HIP_TRY(hipMemcpyAsync(job_iterations, m.iter, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
+    if (job_n_sv) HIP_TRY(hipMemcpyAsync(job_n_sv, m.n_sv, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
+    if (train_pred_out) HIP_TRY(hipMemcpyAsync(train_pred_out, m.train_pred, (size_t)n_t * 8, hipMemcpyDeviceToHost, cs()));
+    if (job_status) std::copy(st_words.begin(), st_words.end(), job_status);
+    // score: the decision value of a job's one pair is sum_t beta_t K(z_t, z) - rho
+    if (n_q) {
+        smo::SvcFitDev f{};
+        f.X = st.feats;
+        f.test_off = (const long long *)parts[5].dev;
+        f.blocks = (const knn::SplitBlock *)parts[6].dev;
+        f.test_idx = (const int *)parts[8].dev;
+        f.job_task = (const int *)parts[9].dev;
+        f.job_k = (const int *)parts[10].dev;
+        f.mean = m.mean;
+        f.scale = m.scale;
+        f.tasks = m.tasks;
+        f.idx = m.idx;
+        f.alpha_y = m.beta;
+        f.rho = m.rho;
+        f.n_dims = n_dims;
+        f.rbf = m.rbf;
+        f.max_pairs = 1;
+        LAUNCH_TRY("SVR scoring", launch::svc_pairs(f, (long long)blocks.size(), s.label, (double *)st.out[0], cs()));
+    }
+    return finish(st);
+}

@@ -1,4 +1,4 @@
-// Limits, device records and launch entry points of the model families (svc, svr, knn, smo, forest, hmm, diar, lda).  Every family
+// Limits, device records and launch entry points of the model families (svc, svr with svrfit, knn, smo, forest, hmm, diar, lda).  Every family
 // is its own translation unit (family_<name>.hip: its kernels and the host code that picks an instance are there and
 // nowhere else); the host side of the library (the lib_*.hpp units of paa_lib.hip) sees only what is here.  Every launch::
 // function queues its kernels on `stream` and returns 0, or -1 when a launch failed (hipGetLastError has the reason).
@@ -114,6 +114,27 @@ struct SvcFitDev {
     int n_dims, rbf, max_pairs;
 };
 }  // namespace smo
+namespace svrfit {
+// a batch of epsilon-SVR dual problems and their state (kernels_svrfit.hpp): device pointers.  A task is an smo::SmoTask (its n rows
+// are idx[off ..]); its 2 n dual variables -- variable v stands for row v mod n, with the sign +1 for v < n and -1 for v >= n --
+// have their alpha and G at 2 off .. 2 off + 2 n - 1; K_tt, beta and the training predictions are per row, at off
+struct SvrDev {
+    const double *X;          // [n_samples][n_dims]
+    const double *y;          // [n_samples]: the targets
+    const int *idx;           // sample index of every row of every task
+    const smo::SmoTask *tasks;
+    const double *epsilon;    // [n_tasks]: the width of the tube
+    const double *mean, *scale;   // [..][n_dims]
+    double *alpha, *G;        // state per variable
+    double *QD;               // state per row: K_tt
+    double *beta, *train_pred;    // out per row, written at a task's stop: alpha_t - alpha_{t+n}; sum_s beta_s K_ts - rho
+    int *iter, *status;       // state per task (status: smo::Status)
+    double *rho, *gap;        // out per task
+    int *n_sv;                // out per task: rows with beta != 0
+    int n_dims, rbf, max_iter;
+    double eps;
+};
+}  // namespace svrfit
 namespace forest {
 constexpr int kMaxClasses = 64;
 constexpr int kMaxDims = 256;
@@ -208,6 +229,8 @@ int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double 
 // ... the geometry for tests that aim at its edges: threads per workgroup, groups, the row limit, test rows per scoring
 // workgroup, the default iterations per launch, the dims limit
 void smo_geometry(int out6[6]);
+// kernels_svrfit.hpp: smo_step for a batch of epsilon-SVR tasks (the limits are the SMO solver's)
+int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
 // two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
 // infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the

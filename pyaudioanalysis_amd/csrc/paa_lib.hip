@@ -548,6 +548,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_sweep.hpp"
 #include "lib_knn.hpp"
 #include "lib_smo.hpp"
+#include "lib_svrfit.hpp"
 #include "lib_forest.hpp"
 #include "lib_hmm.hpp"
 #include "lib_diar.hpp"
