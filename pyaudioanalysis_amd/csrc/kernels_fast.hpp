@@ -556,8 +556,32 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     PAA_T0()
     const Tile tl = tiles[tile_id];
     const ClipDev c = clips[tl.clip];
-    const ClipNorm nm = wave_clip_norm<int16_t>(P, c, norms, tl.clip, lane);      // (formed from the partials in this prologue)
     const int16_t *xc = sig + c.sample_off;
+    const int r0 = tl.t0, t_end = tl.t0 + tl.cnt;      // frames [r0, t_end) are this wave's to store
+    // a run that starts inside a clip begins its first quad HALO frames early: the spectrum of frame r0 - 1 (flux of the first stored
+    // frame) and, with deltas, the complete features of r0 - 1 (whose flux needs the spectrum of r0 - 2) come out of that quad, whose
+    // other frames are already the run's own -- until round 5 a whole halo quad ran first (one iteration of 19 for nothing)
+    constexpr int HALO = DELTAS ? 2 : 1;
+    int q0 = r0 >= HALO ? r0 - HALO : 0;
+    // software prefetch of a quad's samples (NPRE x 16 B per lane) into registers.  The first quad's is requested here, in
+    // front of the statistics partials (its address needs only the tile and the clip), so the two latencies run together
+    int4 pre[G::NPRE];
+#pragma unroll
+    for (int r = 0; r < G::NPRE; ++r) pre[r] = make_int4(0, 0, 0, 0);
+    bool pre_ok;
+#define PAA_F800_FETCH(q)                                                                              \
+    {                                                                                                  \
+        const long long base_ = (long long)(q) * S;                                                    \
+        const int16_t *src_ = xc + base_;                                                              \
+        pre_ok = ((reinterpret_cast<uintptr_t>(src_) & 15) == 0) && (c.n - base_ >= RAW_N);            \
+        if (pre_ok) {                                                                                  \
+            const int4 *s4_ = reinterpret_cast<const int4 *>(src_);                                    \
+            _Pragma("unroll") for (int r_ = 0; r_ < G::NPRE; ++r_)                                     \
+                if (lane + 64 * r_ < RAW_N / 8) pre[r_] = s4_[lane + 64 * r_];                         \
+        }                                                                                              \
+    }
+    PAA_F800_FETCH(q0)
+    const ClipNorm nm = wave_clip_norm<int16_t>(P, c, norms, tl.clip, lane);      // (formed from the partials in this prologue)
     const long long Tc = c.T;
     double *oc = out + c.out_off;
 
@@ -582,12 +606,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     const s16x2 zc_one = {1, 1};
     const int zc_shift = mu_whole ? 0 : 1;
 
-    const int r0 = tl.t0, t_end = tl.t0 + tl.cnt;      // frames [r0, t_end) are this wave's to store
-    // a run that starts inside a clip begins its first quad HALO frames early: the spectrum of frame r0 - 1 (flux of the first stored
-    // frame) and, with deltas, the complete features of r0 - 1 (whose flux needs the spectrum of r0 - 2) come out of that quad, whose
-    // other frames are already the run's own -- until round 5 a whole halo quad ran first (one iteration of 19 for nothing)
-    constexpr int HALO = DELTAS ? 2 : 1;
-    int q0 = r0 >= HALO ? r0 - HALO : 0;
     int slot0 = 2;                   // slots of a quad: slot0 .. slot0+3 (mod 5) after the rotation at the loop head; previous = slot0-1
     double vlast = 0.0;              // lane l < 34: feature l of the frame before this quad
     double hold[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};    // ... and the row's last seven values / deltas, waiting for
@@ -595,24 +613,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     bool first_quad = true;          // the run's first iteration (its first HALO frames belong to the run before when r0 > 0)
     double rX_carry = 0.0;           // 1 / (sum X + 400 eps) of the quad's last frame, for the flux of the next quad's first
     int n_done = 0;                  // quads of this run whose FFT stages are complete (pacing)
-
-    // software prefetch of the next quad's samples (NPRE x 16 B per lane) into registers
-    int4 pre[G::NPRE];
-#pragma unroll
-    for (int r = 0; r < G::NPRE; ++r) pre[r] = make_int4(0, 0, 0, 0);
-    bool pre_ok;
-#define PAA_F800_FETCH(q)                                                                              \
-    {                                                                                                  \
-        const long long base_ = (long long)(q) * S;                                                    \
-        const int16_t *src_ = xc + base_;                                                              \
-        pre_ok = ((reinterpret_cast<uintptr_t>(src_) & 15) == 0) && (c.n - base_ >= RAW_N);            \
-        if (pre_ok) {                                                                                  \
-            const int4 *s4_ = reinterpret_cast<const int4 *>(src_);                                    \
-            _Pragma("unroll") for (int r_ = 0; r_ < G::NPRE; ++r_)                                     \
-                if (lane + 64 * r_ < RAW_N / 8) pre[r_] = s4_[lane + 64 * r_];                         \
-        }                                                                                              \
-    }
-    if (NW == 4) PAA_F800_FETCH(q0)
 
     int16_t before_next = 0;         // lane 0: the sample just before the NEXT quad (saved while raw[] still holds it)
     int16_t before_reg = 0;          // lane 0: the sample just before THIS quad
@@ -657,9 +657,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             // instead of an exposed one per iteration)
             int16_t before = 0;
             if (lane == 0) before = (!first_quad) ? before_next : ((base > 0) ? src[-1] : src[0]);
-            // NW = 8: no register prefetch across the loop edge (16 live registers through every stage would cost more
-            // than the exposed load: the partner wave of the SIMD computes meanwhile)
-            if (NW != 4) PAA_F800_FETCH(q0)
+            // pre[] holds this quad's samples when pre_ok: NW = 4 requested them at the previous iteration's staging point
+            // (below), NW = 8 behind its pass 2 -- 16 to 28 live registers through the transforms would cost more than the
+            // load they hide, past them the register pressure is over its peak and the whole feature phase covers the
+            // latency (fetched here instead, the load stood exposed 18 times per run: the step was 2 % slower)
             if (pre_ok) {
                 int4 *d4 = reinterpret_cast<int4 *>(raw + G::PAD);
 #pragma unroll
@@ -833,6 +834,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         wsync();
         ++n_done;
         PAA_F800_PACE(-1)
+        // NW = 8: the next quad's samples travel while the feature phase runs (from here on pre_ok speaks of that quad)
+        if (NW != 4 && q0 + QUAD < t_end) PAA_F800_FETCH(q0 + QUAD)
 
         PAA_TICK(4)
         // ---------------- features: 16 lanes per frame (group g <-> frame q0 + g)
