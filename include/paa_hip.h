@@ -350,7 +350,39 @@ int paa_debug_knn_split_geometry(int32_t *out10);
  * C <= 0, gamma <= 0 (RBF), eps <= 0, kernel_type other than 0 / 2, max_iter < 1, an empty task, a job whose training list holds
  * fewer than two classes.  PAA_ERR_UNSUPPORTED, likewise before the device is touched: n_dims > 256 (PAA_SMO_MAX_DIMS), a task of
  * more than 8192 rows (PAA_SMO_MAX_ROWS), a job with more than 64 classes.  An empty test list is legal.  Synchronous, host
- * buffers in and out.  Not served: Platt probabilities (probability=True's second half), a model file.                   */
+ * buffers in and out.  The sweep fits no Platt probabilities (it reads vote labels only); paa_svc_fit_proba_f64 below fits them.
+ * Not served: a model file (the Python layer writes one from paa_svc_fit_proba_f64's outputs).
+ *
+ * paa_platt_sigmoid_f64 -- probability=True's sigmoid fit alone (svm.cpp: sigmoid_train), one workgroup per PROBLEM:
+ *   dec, sign [prob_off[n_problems]]   problem p owns dec[prob_off[p] .. prob_off[p+1]-1], the held-out decision values of one class
+ *                            pair, with the signs sign[..] (+1: the pair's first class, -1: the second); 1..8192 values
+ * Outputs per problem: A, B of P(first class | dec) = 1 / (1 + exp(A dec + B)); iterations (Newton iterations made); stop
+ * (PAA_PLATT_CONVERGED, PAA_PLATT_LINE_SEARCH_FAILED, PAA_PLATT_MAX_ITERATIONS: for the latter two libsvm prints a message and keeps
+ * the last A, B; so does this).  sigmoid_train operation for operation in FP64; only the order of its sums over the values
+ * differs (fixed by the problem's length alone), so the outputs are bit-identical for a problem alone or in any batch.
+ *
+ * paa_svc_fit_proba_f64 -- SVC(C, kernel, gamma, probability=True, random_state).fit for every job, in the job form of
+ * paa_svc_fit_splits_f64 without test lists, plus seed [n_jobs]: libsvm's random_seed, 0 <= seed < 2^31 (scikit-learn draws it as
+ * check_random_state(random_state).randint(np.iinfo('i').max)).  Per pair (a, b), a < b, of the classes present in a job, pair after
+ * pair in job order then row-major, with the pair's l rows in PAIR-ROW ORDER (the rows of a in train-list order, then those of b):
+ *   - the full fit is one task, as in paa_svc_fit_splits_f64;
+ *   - svm_binary_svc_probability's five folds: std::mt19937(seed), restarted for every pair; perm = 0..l-1 shuffled by
+ *     j = i + bounded(l - i), swap(perm[i], perm[j]), bounded(range) being Lemire's m = (uint64)r * range with rejection
+ *     (if (uint32)m < range, redraw while (uint32)m < (2^32 - range) % range), m >> 32; fold f holds out
+ *     perm[f l / 5 .. (f + 1) l / 5 - 1] and trains on the rest, one task whose rows go in permutation order, grouped by class, the
+ *     class seen first put first.  A fold whose training part lacks a class makes no task: its held-out values are +1 (only a),
+ *     -1 (only b) or 0 (neither);
+ *   - all tasks of all jobs are solved side by side, the held-out rows of every fold are scored by the sweep's scoring kernel,
+ *     and one launch of the sigmoid kernel fits every pair.
+ *   n_pairs, n_rows          must equal the number of pairs the jobs make and the sum of their l
+ *   alpha_y [n_rows]         alpha_t y_t of the full fits, pair after pair, each in pair-row order
+ *   rho, prob_a, prob_b [n_pairs], n_sv [n_pairs]   of the full fit / of the sigmoid (libsvm's rho, probA, probB)
+ *   task_iterations, task_status [n_pairs][6]   slot 0: the full fit, slots 1..5: the folds; status PAA_SMO_CONVERGED /
+ *                            PAA_SMO_NOT_CONVERGED, 0 with 0 iterations for a fold that made no task
+ *   sig_iterations, sig_stop [n_pairs]   as for paa_platt_sigmoid_f64
+ *   cv_dec [n_rows]          (may be NULL) the held-out decision values in pair-row order;  n_launches (may be NULL)
+ * Errors are those of paa_svc_fit_splits_f64, raised before the device is touched, plus PAA_ERR_ARG for a seed outside 0..2^31-1.
+ * Synchronous, host buffers in and out.  Not served: class weights, shrinking.                                           */
 #define PAA_SMO_MAX_ROWS 8192
 #define PAA_SMO_MAX_DIMS 256
 #define PAA_SMO_CONVERGED 2
@@ -364,6 +396,17 @@ int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const
                            const double *mean, const double *std, const double *C, const double *gamma, int kernel_type,
                            double eps, int max_iter, int iters_per_launch, int32_t *label_out, double *dec_out, int max_pairs,
                            int n_tasks, int32_t *task_iterations, int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches);
+#define PAA_PLATT_CONVERGED 0
+#define PAA_PLATT_LINE_SEARCH_FAILED 1
+#define PAA_PLATT_MAX_ITERATIONS 2
+int paa_platt_sigmoid_f64(const double *dec, const int8_t *sign, int n_problems, const int64_t *prob_off, double *A, double *B,
+                          int32_t *iterations, int32_t *stop);
+int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                          const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std, const double *C,
+                          const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch, const int64_t *seed,
+                          int n_pairs, int64_t n_rows, double *alpha_y, double *rho, double *prob_a, double *prob_b, int32_t *n_sv,
+                          int32_t *task_iterations, int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
+                          int32_t *n_launches);
 /* tests: out6 = threads per workgroup, lane groups, rows per task, test rows per scoring workgroup, default iterations per
  * launch, dims                                                                                                        */
 int paa_debug_smo_geometry(int32_t *out6);

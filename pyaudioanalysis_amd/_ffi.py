@@ -124,6 +124,10 @@ _SIGNATURES = {
     "paa_svc_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
                                          c_f64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_i32p, c_f64p, C.c_int, C.c_int, c_i32p,
                                          c_i32p, c_i32p, c_i32p]),
+    "paa_platt_sigmoid_f64": (C.c_int, [c_f64p, C.POINTER(C.c_int8), C.c_int, c_i64p, c_f64p, c_f64p, c_i32p, c_i32p]),
+    "paa_svc_fit_proba_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p,
+                                        C.c_int, C.c_double, C.c_int, C.c_int, c_i64p, C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p,
+                                        c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p]),
     "paa_debug_smo_geometry": (C.c_int, [c_i32p]),
     "paa_svr_tasks_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p,
                                     C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p, c_i32p]),

@@ -12,7 +12,8 @@ SVM probability of silence_removal); there is no CPU fallback for those.  `music
 features and the similarity matrix in HBM: only the filtered matrix it returns comes back to the host.
 `silence_removal` trains its two-class SVM exactly where the reference does -- with scikit-learn (:739,
 audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744-748) by one kernel over all frames
-(svm_onset_probability).  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
+(svm_onset_probability); with svm_fit="device" the SVM is trained on the GPU instead (audioTrainTest.train_svm_device: the full
+fit, libsvm's five cross-validation fits and the sigmoid fit) and scikit-learn is not needed.  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
 hmm_segmentation, :287-492) runs on the GPU as well: class GaussianHmm stands in for hmmlearn's GaussianHMM (hmmlearn is not
 needed, also not to read a model file the reference wrote).  Speaker diarization (speaker_diarization, diarize_features,
 evaluate_speaker_diarization, speaker_diarization_evaluation, :251-284, :815-1090) runs its standardisation, k-means sweep and
@@ -223,18 +224,39 @@ def _plot_segments(signal, sampling_rate, prob, st_step, seg_limits):
     plt.show()
 
 
-def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, weight=0.5, plot=False):
+def _train_onset_svm_device(low_energy, high_energy, random_state):
+    """_train_onset_svm without scikit-learn: StandardScaler's mean_ / scale_ (a constant feature keeps scale 1), applied on the
+    load path of audioTrainTest.train_svm_device's fits (C = 1, linear, gamma='auto', probability=True)."""
+    from . import audioTrainTest as aT
+    features = np.vstack([low_energy, high_energy])
+    labels = np.append(np.zeros(low_energy.shape[0]), np.ones(high_energy.shape[0]))
+    mean = features.mean(axis=0)
+    scale = np.sqrt(features.var(axis=0))
+    scale[scale < 10 * np.finfo(np.float64).eps] = 1.0                                     # sklearn's _handle_zeros_in_scale
+    return aT._train_svm_device(features, labels, 1.0, 'linear', random_state, mean, scale), mean, scale
+
+
+def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, weight=0.5, plot=False, *, svm_fit="sklearn",
+                    random_state=None):
     """Event detection (silence removal), reference :672-815.  Returns the list of [start, end] segments in seconds.
 
     signal, sampling_rate: the audio; st_win, st_step: short-term window and step in SECONDS; smooth_window: length of
     the probability smoothing in seconds; weight in (0, 1): the higher, the stricter (values outside are pulled to
-    0.01 / 0.99, :697-700)."""
+    0.01 / 0.99, :697-700).  svm_fit (keyword only): "sklearn" (the default) trains the onset SVM with scikit-learn; "device"
+    trains it on the GPU (audioTrainTest.train_svm_device: the full fit, libsvm's five cross-validation fits and the sigmoid
+    fit) and needs no scikit-learn; random_state is read by that mode alone (None: one draw from NumPy's global state, as
+    scikit-learn's fit makes).  Any other value of svm_fit raises ValueError."""
+    if svm_fit not in ("sklearn", "device"):
+        raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
     from . import ShortTermFeatures as stf
     weight = min(max(weight, 0.01), 0.99) if not 0 < weight < 1 else weight
     mono = audioBasicIO.stereo_to_mono(signal)
     st_feats, _ = stf.feature_extraction(mono, sampling_rate, st_win * sampling_rate, st_step * sampling_rate)   # :707-710
     quiet, loud = _energy_extremes(st_feats)
-    svm, mean, std = _train_onset_svm(quiet.T, loud.T)                                     # :730-739, scikit-learn
+    if svm_fit == "device":
+        svm, mean, std = _train_onset_svm_device(quiet.T, loud.T, random_state)
+    else:
+        svm, mean, std = _train_onset_svm(quiet.T, loud.T)                                 # :730-739, scikit-learn
     # onset probability of every frame in one kernel (replaces the predict_proba loop :741-748), then smoothing (:751)
     prob = smooth_moving_avg(svm_onset_probability(st_feats, mean, std, svm), smooth_window / st_step)
     active = np.flatnonzero(prob > _onset_threshold(prob, weight))                         # :761

@@ -20,6 +20,8 @@ pyAudioAnalysis/audioTrainTest.py).
     extract_features_and_train(paths, ..., classifier_type, model_name, ...)                   audioTrainTest.py:236-361
     knn_split_predict(X, labels, jobs, proba=False, neighbors=False)   every kNN split of a sweep in one launch
     svm_split_fit_predict(X, labels, jobs, kernel, ...), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
+    train_svm_device(features, labels, c_param, kernel, random_state=None), to_sklearn_svc(model)   SVC(probability=True).fit on the GPU
+    svc_fit_proba(X, labels, jobs, kernel, ...), platt_sigmoid(dec, signs, offsets)   its stages: fits, folds and sigmoids; the sigmoid alone
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -39,7 +41,11 @@ resident sample matrix (knn_split_kernel through paa_knn_splits_f64); the five s
 the per-vector predict loop -- by default.  With svm_fit="device" evaluate_classifier fits "svm" / "svm_rbf" on the GPU too:
 every pair of classes of every split is a binary C-SVC problem of smo_kernel (libsvm's solver without shrinking, FP64; no Platt
 cross-validation, whose probabilities the sweep never reads), all of them side by side (paa_svc_fit_splits_f64); the final
-fit of extract_features_and_train and its model file stay scikit-learn's.  smote / use_smote are refused (NotImplementedError).
+fit of extract_features_and_train and its model file are scikit-learn's by default.  train_svm_device is train_svm on the GPU,
+Platt probabilities included (paa_svc_fit_proba_f64: per pair the full fit and libsvm's five cross-validation fits for
+scikit-learn's seed as smo_kernel tasks, the held-out rows scored by svc_pairs_kernel, probA_ / probB_ by platt_sigmoid_kernel);
+to_sklearn_svc makes a real SVC of its result, which extract_features_and_train(final_fit="device") pickles as the model file.
+smote / use_smote are refused (NotImplementedError).
 Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
 SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
 value of evaluate_regression -- scores every vector in one launch (kernels_svr.hpp through paa_svr_*: libsvm's decision value
@@ -977,6 +983,7 @@ def smo_geometry():
 
 
 SMO_CONVERGED, SMO_NOT_CONVERGED = 2, 3          # PAA_SMO_CONVERGED / PAA_SMO_NOT_CONVERGED
+SMO_MAX_ROWS = 8192                              # PAA_SMO_MAX_ROWS
 
 
 def _warn_not_converged(status, max_iter):
@@ -1091,6 +1098,217 @@ def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3
     iterations, status, n_sv = iterations[:n_tasks], status[:n_tasks], n_sv[:n_tasks]
     _warn_not_converged(status, int(max_iter))
     return SvmSplitResult(label.astype(np.int64), dec, p.test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
+
+
+PLATT_CONVERGED, PLATT_LINE_SEARCH_FAILED, PLATT_MAX_ITERATIONS = 0, 1, 2      # PAA_PLATT_*
+
+
+def _signs(signs, n, what):
+    sg = np.asarray(signs, dtype=np.float64).reshape(-1)
+    if sg.shape[0] != n:
+        raise ValueError("%s: %d values and %d signs" % (what, n, sg.shape[0]))
+    return np.ascontiguousarray(np.where(sg == 1, 1, np.where(sg == -1, -1, 0)), dtype=np.int8)
+
+
+class PlattResult:
+    """What platt_sigmoid returns, per problem: A, B, iterations (Newton iterations) and stop (PLATT_CONVERGED,
+    PLATT_LINE_SEARCH_FAILED, PLATT_MAX_ITERATIONS)."""
+
+    def __init__(self, A, B, iterations, stop):
+        self.A, self.B, self.iterations, self.stop = A, B, iterations, stop
+
+
+def platt_sigmoid(dec, signs, offsets):
+    """libsvm's sigmoid_train for a batch of problems in one launch (paa_platt_sigmoid_f64, platt_sigmoid_kernel): problem p owns
+    the decision values dec[offsets[p] : offsets[p + 1]] with the signs signs[..] (+1: the pair's first class, -1: the second);
+    P(first class | dec) = 1 / (1 + exp(A dec + B)).  Returns a PlattResult."""
+    dec = np.ascontiguousarray(np.asarray(dec, dtype=np.float64).reshape(-1))
+    off = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
+    if off.shape[0] < 2:
+        raise ValueError("no problems")
+    if dec.shape[0] != off[-1]:
+        raise ValueError("%d decision values for offsets that end at %d" % (dec.shape[0], off[-1]))
+    sign = _signs(signs, dec.shape[0], "platt_sigmoid")
+    n = off.shape[0] - 1
+    A, B = np.zeros(n), np.zeros(n)
+    iterations, stop = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_platt_sigmoid_f64(_ffi.as_f64p(dec), sign.ctypes.data_as(C.POINTER(C.c_int8)), n, _ffi.as_i64p(off),
+                                                _ffi.as_f64p(A), _ffi.as_f64p(B), _ffi.as_i32p(iterations), _ffi.as_i32p(stop)))
+    return PlattResult(A, B, iterations, stop)
+
+
+class SvcProbaResult:
+    """What svc_fit_proba returns.  classes: per job the classes present in its training list, ascending; pair_off [n_jobs + 1]:
+    job j owns the pairs pair_off[j] .. pair_off[j + 1] - 1, its pairs (a, b), a < b, row-major.  Per pair: rows (the sample
+    indices in pair-row order: the rows of a in train-list order, then those of b), signs (+1 / -1), alpha_y (the full fit's
+    alpha_t y_t over those rows), rho, prob_a, prob_b, n_sv, iterations / status [6] (slot 0: the full fit, 1..5: the folds;
+    status 0: the fold made no task), sigmoid_iterations, sigmoid_stop (PLATT_*) and cv_dec (the held-out decision values over
+    the rows, or None); n_launches of the solver kernel."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _seeds(seeds, n_jobs):
+    s = np.asarray(seeds)
+    if s.dtype.kind not in "iu" or s.ndim > 1 or (s.ndim == 1 and s.shape[0] != n_jobs):
+        raise ValueError("seeds: one integer, or one per job")
+    s = np.ascontiguousarray(np.broadcast_to(s.astype(np.int64), (n_jobs,)))
+    if (s < 0).any() or (s > np.iinfo(np.int32).max).any():
+        raise ValueError("seeds: libsvm's random_seed is in 0 .. 2^31 - 1")
+    return s
+
+
+def svc_fit_proba(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, seeds=0, return_cv=False, max_iter=10**7, iters_per_launch=0):
+    """SVC(C, kernel, gamma, probability=True).fit(train) for every job over ONE sample matrix (paa_svc_fit_proba_f64): per pair
+    of the classes present in a job the full fit and the fits of libsvm's five cross-validation folds are binary problems of
+    smo_kernel, all of them side by side; svc_pairs_kernel scores every fold's held-out rows; one platt_sigmoid_kernel launch
+    fits probA / probB of every pair.  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the training rows); a job is
+    (train_idx, mean, scale, C).  seeds: libsvm's random_seed of every job (what scikit-learn draws from random_state), one int
+    for all jobs or one per job; the folds are libsvm's for that seed.  gamma=None is 1 / n_dims.  Returns an SvcProbaResult."""
+    jobs = list(jobs)
+    for j, job in enumerate(jobs):
+        if len(job) != 4:
+            raise ValueError("job %d: (train_idx, mean, scale, C) expected" % j)
+    no_test = np.zeros(0, dtype=np.int32)
+    p = _pack_jobs(X, labels, [(job[0], no_test, job[1], job[2], job[3]) for job in jobs], "C", float, kernel)
+    n_samples, n_dims = p.X.shape
+    seed = _seeds(seeds, len(jobs))
+    classes = [np.unique(p.labels[rows]) for rows in p.inside]
+    rows, signs = [], []
+    for tr, cl in zip(p.inside, classes):
+        lab = p.labels[tr]
+        for a in range(len(cl)):
+            for b in range(a + 1, len(cl)):
+                ra, rb = tr[lab == cl[a]], tr[lab == cl[b]]
+                rows.append(np.concatenate([ra, rb]))
+                signs.append(np.concatenate([np.ones(len(ra), dtype=np.int8), -np.ones(len(rb), dtype=np.int8)]))
+    pair_off = _offsets([len(c) * (len(c) - 1) // 2 for c in classes])
+    row_off = _offsets([len(r) for r in rows])
+    n_pairs, n_rows = len(rows), int(row_off[-1])
+    C_arr = np.array(p.last, dtype=np.float64)
+    g_arr = np.full(len(jobs), 1.0 / n_dims if gamma is None else float(gamma), dtype=np.float64)
+    m = max(n_pairs, 1)
+    alpha_y, cv = np.zeros(max(n_rows, 1)), np.zeros(max(n_rows, 1)) if return_cv else None
+    rho, prob_a, prob_b = np.zeros(m), np.zeros(m), np.zeros(m)
+    n_sv, sig_it, sig_stop = (np.zeros(m, dtype=np.int32) for _ in range(3))
+    iterations, status = np.zeros((m, 6), dtype=np.int32), np.zeros((m, 6), dtype=np.int32)
+    launches = np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_svc_fit_proba_f64(
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(jobs), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
+        int(max_iter), int(iters_per_launch), _ffi.as_i64p(seed), n_pairs, n_rows, _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
+        _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b), _ffi.as_i32p(n_sv), _ffi.as_i32p(iterations), _ffi.as_i32p(status),
+        _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(cv) if return_cv else None, _ffi.as_i32p(launches)))
+    _warn_not_converged(status[:n_pairs].reshape(-1), int(max_iter))
+    per_pair = lambda a: [a[row_off[t]:row_off[t + 1]] for t in range(n_pairs)]
+    return SvcProbaResult(classes=classes, pair_off=pair_off, rows=rows, signs=signs, alpha_y=per_pair(alpha_y), rho=rho[:n_pairs],
+                          prob_a=prob_a[:n_pairs], prob_b=prob_b[:n_pairs], n_sv=n_sv[:n_pairs], iterations=iterations[:n_pairs],
+                          status=status[:n_pairs], sigmoid_iterations=sig_it[:n_pairs], sigmoid_stop=sig_stop[:n_pairs],
+                          cv_dec=per_pair(cv) if return_cv else None, n_launches=int(launches[0]))
+
+
+class DeviceSvc:
+    """What train_svm_device returns: a fitted probabilistic SVC given by its arrays in scikit-learn's attribute names and
+    conventions (support_, support_vectors_, n_support_, dual_coef_ / _dual_coef_, intercept_ / _intercept_, probA_, probB_,
+    classes_, kernel, _gamma, C; shape_fit_ for to_sklearn_svc).  svc_model, svm_predict, classifier_wrapper, device_model and
+    audioSegmentation.svm_onset_probability read it as they read an sklearn.svm.SVC."""
+    probability = True
+    gamma = "auto"
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _libsvm_seed(random_state):
+    """libsvm's random_seed as scikit-learn draws it: check_random_state(random_state).randint(np.iinfo('i').max) -- None is ONE
+    draw from NumPy's global state, an int a fresh RandomState, a RandomState itself."""
+    if random_state is None:
+        return int(np.random.randint(np.iinfo('i').max))
+    if isinstance(random_state, np.random.RandomState):
+        return int(random_state.randint(np.iinfo('i').max))
+    return int(np.random.RandomState(random_state).randint(np.iinfo('i').max))
+
+
+def _train_svm_device(features, labels, c_param, kernel, random_state, mean, scale):
+    """train_svm_device over the rows (features - mean) / scale, standardised on the load path."""
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    raw = np.asarray(labels).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
+    _check_kernel(kernel)
+    classes, y = np.unique(raw, return_inverse=True)
+    k = classes.shape[0]
+    if k < 2:
+        raise ValueError("The number of classes has to be greater than one; got %d class" % k)
+    counts = np.bincount(y, minlength=k)
+    top = int(np.sort(counts)[-2:].sum())
+    if top > SMO_MAX_ROWS:
+        raise NotImplementedError("a pair of classes has %d rows: the GPU solver serves at most %d rows per pair" % (top, SMO_MAX_ROWS))
+    seed = _libsvm_seed(random_state)
+    n, n_dims = X.shape
+    res = svc_fit_proba(X, y.astype(np.int32), [(np.arange(n), mean, scale, float(c_param))], kernel=kernel, seeds=seed)
+    # libsvm's model: the support vectors are the union over the pairs, grouped by class ascending, in sample order within a class
+    coef = np.zeros((k - 1, n))
+    is_sv = np.zeros(n, dtype=bool)
+    t = 0
+    for a in range(k):
+        for b in range(a + 1, k):
+            rows, ay = res.rows[t], res.alpha_y[t]
+            in_a = y[rows] == a
+            coef[b - 1, rows[in_a]] = ay[in_a]           # class a's coefficients against b: row b - 1
+            coef[a, rows[~in_a]] = ay[~in_a]             # class b's against a: row a
+            is_sv[rows[ay != 0]] = True
+            t += 1
+    support = np.flatnonzero(is_sv)
+    support = support[np.argsort(y[support], kind="stable")].astype(np.int32)
+    dual = np.ascontiguousarray(coef[:, support])
+    intercept = -res.rho
+    flip = -1.0 if k == 2 else 1.0                       # scikit-learn publishes the two-class model negated
+    n_support = np.bincount(y[support], minlength=k).astype(np.int32)
+    return DeviceSvc(support_=support, support_vectors_=np.ascontiguousarray((X[support] - mean) / scale),
+                     n_support_=n_support, _n_support=n_support.copy(), _dual_coef_=dual, dual_coef_=flip * dual, _intercept_=intercept, intercept_=flip * intercept,
+                     probA_=res.prob_a.copy(), probB_=res.prob_b.copy(), _probA=res.prob_a.copy(), _probB=res.prob_b.copy(),
+                     classes_=classes, kernel=kernel, _gamma=1.0 / n_dims, C=float(c_param), shape_fit_=X.shape, fit_status_=0,
+                     n_features_in_=n_dims, random_seed=seed, fit_result=res)
+
+
+def train_svm_device(features, labels, c_param, kernel='linear', *, random_state=None):
+    """train_svm on the GPU: SVC(C=c_param, kernel=kernel, probability=True, gamma='auto', random_state=random_state).fit(features,
+    labels) by svc_fit_proba -- every pair's full fit, libsvm's five cross-validation fits per pair for that seed and the
+    sigmoid fits.  Returns a DeviceSvc.  random_state=None draws the seed from NumPy's global state exactly as scikit-learn
+    does (one randint), an int goes through np.random.RandomState.  A pair of classes above 8192 rows raises
+    NotImplementedError; there is no CPU fallback.  Agreement with scikit-learn is bounded by libsvm's stopping tolerance (its
+    kernel cache is float32), not bit-exact."""
+    n_dims = np.asarray(features).shape[1] if np.asarray(features).ndim == 2 else 0
+    return _train_svm_device(features, labels, c_param, kernel, random_state, np.zeros(n_dims), np.ones(n_dims))
+
+
+def to_sklearn_svc(model):
+    """A real sklearn.svm.SVC with the fitted attributes of a DeviceSvc (or of anything that carries them): it predicts as
+    scikit-learn predicts from those arrays and pickles as the reference's model files do.  Needs scikit-learn."""
+    import sklearn.svm
+    svc = sklearn.svm.SVC(C=float(model.C), kernel=model.kernel, probability=True, gamma='auto')
+    n_support = np.asarray(model.n_support_, dtype=np.int32)
+    k = n_support.shape[0]
+    svc.support_ = np.asarray(model.support_, dtype=np.int32)
+    svc.support_vectors_ = np.ascontiguousarray(model.support_vectors_, dtype=np.float64)
+    svc._n_support = n_support
+    svc._dual_coef_ = np.ascontiguousarray(model._dual_coef_, dtype=np.float64)
+    svc._intercept_ = np.ascontiguousarray(model._intercept_, dtype=np.float64)
+    flip = -1.0 if k == 2 else 1.0
+    svc.dual_coef_ = flip * svc._dual_coef_
+    svc.intercept_ = flip * svc._intercept_
+    svc._probA = np.ascontiguousarray(model.probA_, dtype=np.float64)
+    svc._probB = np.ascontiguousarray(model.probB_, dtype=np.float64)
+    svc.classes_ = np.asarray(model.classes_)
+    svc._gamma = float(model._gamma)
+    svc._sparse = False
+    svc.shape_fit_ = tuple(model.shape_fit_)
+    svc.fit_status_ = 0
+    svc.class_weight_ = np.ones(k)
+    svc.n_features_in_ = int(svc.support_vectors_.shape[1])
+    return svc
 
 
 class SvrSolveResult:
@@ -1349,16 +1567,21 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
 
 
 def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
-                               compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn"):
+                               compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn",
+                               final_fit="sklearn"):
     """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
     :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
     evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
     reference's format -- "knn": eleven pickles in model_name (load_model_knn); otherwise the pickled classifier in model_name
     and model_name + "MEANS" (load_model).  use_smote=True raises NotImplementedError.  svm_fit (keyword only) goes to the tuning
-    step, evaluate_classifier, and nowhere else: the final fit and the model file stay scikit-learn's, because the file format
-    is a pickled SVC."""
+    step, evaluate_classifier, and nowhere else.  final_fit (keyword only): "sklearn" (the default) fits the final model with
+    scikit-learn; "device" ("svm" / "svm_rbf" only, any other type raises ValueError before any work) fits it with
+    train_svm_device and writes the model file in the reference's format, a pickled sklearn.svm.SVC, through to_sklearn_svc --
+    the MEANS file is the same."""
     if svm_fit not in ("sklearn", "device") or (svm_fit == "device" and classifier_type not in _SVM_TYPES):
         raise ValueError("svm_fit=%r with the classifier type %r" % (svm_fit, classifier_type))
+    if final_fit not in ("sklearn", "device") or (final_fit == "device" and classifier_type not in _SVM_TYPES):
+        raise ValueError("final_fit=%r with the classifier type %r" % (final_fit, classifier_type))
     if use_smote:
         raise NotImplementedError("use_smote=True: this package does not resample (see evaluate_classifier)")
     from sklearn.preprocessing import StandardScaler
@@ -1405,7 +1628,11 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
         save_parameters(model_name, features.tolist(), labels.tolist(), mean, std, class_names, best_param, mid_window, mid_step,
                         short_window, short_step, compute_beat)
     else:
-        classifier = _train_classifier(features, labels, classifier_type, best_param)
+        if final_fit == "device":
+            classifier = to_sklearn_svc(train_svm_device(features, labels, best_param,
+                                                         kernel="rbf" if classifier_type == "svm_rbf" else "linear"))
+        else:
+            classifier = _train_classifier(features, labels, classifier_type, best_param)
         with open(model_name, "wb") as fid:
             cPickle.dump(classifier, fid)
         save_parameters(model_name + "MEANS", mean, std, class_names, mid_window, mid_step, short_window, short_step, compute_beat)

@@ -1,7 +1,9 @@
 // The batched SMO solver and the one-against-one vote of the SVM split sweep (kernels_smo.hpp: the SVM fits of
-// audioTrainTest.evaluate_classifier) -- own translation unit, see model_launch.hpp.
+// audioTrainTest.evaluate_classifier) and the sigmoid fit of probabilistic SVMs (kernels_platt.hpp) -- own translation unit,
+// see model_launch.hpp.
 #include "model_launch.hpp"
 #include "kernels_smo.hpp"
+#include "kernels_platt.hpp"
 
 namespace paa {
 namespace launch {
@@ -27,6 +29,15 @@ int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double 
     const size_t lds = ((size_t)smo::kTile * pitch + smo::kTile) * sizeof(double);
     if (raise_lds(reinterpret_cast<const void *>(&smo::svc_pairs_kernel), lds)) return -1;
     hipLaunchKernelGGL(smo::svc_pairs_kernel, dim3((unsigned)n_blocks), dim3(smo::kThreads), lds, stream, f, d_label, d_dec);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int platt_sigmoid(const platt::PlattDev &p, int n_problems, int l_max, hipStream_t stream) {
+    if (l_max < 1 || l_max > platt::kMaxRows) return -2;
+    if (n_problems < 1) return -1;
+    const size_t lds = ((size_t)l_max * 9 + 7) / 8 * 8;
+    if (raise_lds(reinterpret_cast<const void *>(&platt::platt_sigmoid_kernel), lds)) return -1;
+    hipLaunchKernelGGL(platt::platt_sigmoid_kernel, dim3((unsigned)n_problems), dim3(platt::kThreads), lds, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -288,3 +288,262 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
         for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) label_out[q] = p.job_class[p.job_class_off[j] + label_out[q]];
     return PAA_OK;
 }
+
+// ---- probability=True's second half (svm.cpp: svm_binary_svc_probability, sigmoid_train) ----------------------------------------
+
+// Fits the n problems dec / sign / off (device arrays) with one launch of platt_sigmoid_kernel; the outputs go to host arrays
+static int platt_run(const double *d_dec, const signed char *d_sign, const long long *d_off, int n, int l_max, double *A, double *B,
+                     int32_t *iterations, int32_t *stop) {
+    const size_t b8 = up256((size_t)n * 8), b4 = up256((size_t)n * 4);
+    DevBlock out;
+    HIP_TRY(hipMalloc(&out.p, 2 * b8 + 2 * b4));
+    platt::PlattDev p{};
+    p.dec = d_dec;
+    p.sign = d_sign;
+    p.off = d_off;
+    p.A = (double *)out.p;
+    p.B = (double *)((char *)out.p + b8);
+    p.iter = (int *)((char *)out.p + 2 * b8);
+    p.stop = (int *)((char *)out.p + 2 * b8 + b4);
+    LAUNCH_TRY("sigmoid fit", launch::platt_sigmoid(p, n, l_max, cs()));
+    HIP_TRY(hipMemcpyAsync(A, p.A, (size_t)n * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(B, p.B, (size_t)n * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(iterations, p.iter, (size_t)n * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(stop, p.stop, (size_t)n * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipStreamSynchronize(cs()));
+    return PAA_OK;
+}
+
+// the problems of a sigmoid launch: offsets from 0, 1 .. platt::kMaxRows values each; l_max: the longest
+static int platt_offsets_check(const int64_t *off, int n, int *l_max) {
+    int rc;
+    if ((rc = sweep_offsets_check(off, n, "problem"))) return rc;
+    *l_max = 0;
+    for (int p = 0; p < n; ++p) {
+        const int64_t l = off[p + 1] - off[p];
+        if (l < 1) return fail(PAA_ERR_ARG, "problem %d: no values", p);
+        if (l > platt::kMaxRows) return fail(PAA_ERR_UNSUPPORTED, "problem %d: %lld values: at most %d per problem are supported", p, (long long)l, platt::kMaxRows);
+        *l_max = std::max(*l_max, (int)l);
+    }
+    return PAA_OK;
+}
+
+// The sigmoid fit alone: see paa_hip.h
+extern "C" int paa_platt_sigmoid_f64(const double *dec, const int8_t *sign, int n_problems, const int64_t *prob_off, double *A, double *B,
+                                     int32_t *iterations, int32_t *stop) {
+    if (!dec || !sign || !prob_off || !A || !B || !iterations || !stop) return fail(PAA_ERR_ARG, "null argument");
+    if (n_problems < 1) return fail(PAA_ERR_ARG, "no problems");
+    int rc, l_max;
+    if ((rc = platt_offsets_check(prob_off, n_problems, &l_max))) return rc;
+    const int64_t total = prob_off[n_problems];
+    for (int64_t i = 0; i < total; ++i)
+        if (sign[i] != 1 && sign[i] != -1) return fail(PAA_ERR_ARG, "sign %d of value %lld: +1 or -1", (int)sign[i], (long long)i);
+    if ((rc = ensure_init())) return rc;
+    LaneGuard lane;       // own stream for this call (see Lane)
+    DevBlock block;
+    BlockPart parts[] = {{dec, (size_t)total * 8, 8}, {prob_off, (size_t)(n_problems + 1) * 8, 8}, {sign, (size_t)total, 1}};
+    if ((rc = block_upload(block, parts, 3, "the sigmoid problems"))) return rc;
+    return platt_run((const double *)parts[0].dev, (const signed char *)parts[2].dev, (const long long *)parts[1].dev, n_problems, l_max,
+                     A, B, iterations, stop);
+}
+
+// libsvm's bounded draw (scikit-learn's newrand.h: Lemire's method with rejection over std::mt19937)
+static uint32_t platt_bounded(std::mt19937 &gen, uint32_t range) {
+    uint64_t m = (uint64_t)(uint32_t)gen() * range;
+    uint32_t low = (uint32_t)m;
+    if (low < range) {
+        const uint32_t t = (uint32_t)(0u - range) % range;
+        while (low < t) {
+            m = (uint64_t)(uint32_t)gen() * range;
+            low = (uint32_t)m;
+        }
+    }
+    return (uint32_t)(m >> 32);
+}
+
+// The folds of svm_binary_svc_probability over the pair tasks p (svc_pair_tasks): per pair the permutation of its rows from the
+// job's seed; per fold with both classes in its training part one task appended to p (rows in permutation order, grouped by
+// class, the class seen first put first) and, when it holds rows out, one scoring job.  cv [rows of the pairs] receives the
+// constants of the folds that make no task; where [Q] is the place in cv of every scored row, fold_task [pairs][5] the task of a
+// fold (-1: none)
+struct PlattFolds {
+    std::vector<int64_t> test_off{0};     // [n_score + 1]
+    std::vector<int> test_idx, job_task, job_stat;      // held-out sample rows; per scoring job its task and its job
+    std::vector<int64_t> where;
+    std::vector<int> fold_task;
+};
+static int platt_folds(PlattFolds &f, PairTasks &p, const int64_t *seed, std::vector<double> &cv, int kernel_type) {
+    const int n_pairs = (int)p.tasks.size();
+    f.fold_task.assign((size_t)n_pairs * 5, -1);
+    std::vector<int> perm, first, second;
+    for (int t = 0; t < n_pairs; ++t) {
+        const smo::SmoTask T = p.tasks[t];
+        const int l = T.n;
+        std::mt19937 gen((uint32_t)seed[T.stat]);
+        perm.resize(l);
+        for (int i = 0; i < l; ++i) perm[i] = i;
+        for (int i = 0; i < l; ++i) std::swap(perm[i], perm[i + (int)platt_bounded(gen, (uint32_t)(l - i))]);
+        for (int fold = 0; fold < 5; ++fold) {
+            const int begin = (int)((int64_t)fold * l / 5), end = (int)((int64_t)(fold + 1) * l / 5);
+            first.clear();
+            second.clear();
+            int lead = 0;                                 // the sign of the class seen first
+            for (int k = 0; k < l; ++k) {
+                if (k >= begin && k < end) continue;
+                const int s = p.sign[T.off + perm[k]];
+                if (!lead) lead = s;
+                (s == lead ? first : second).push_back(perm[k]);
+            }
+            if (second.empty()) {                         // one class or none: no fit
+                for (int k = begin; k < end; ++k) cv[T.off + perm[k]] = (double)lead;
+                continue;
+            }
+            int rc;
+            const int64_t n = (int64_t)first.size() + (int64_t)second.size();
+            if ((rc = smo_task_check((int)p.tasks.size(), n, T.C, T.gamma, kernel_type))) return rc;
+            f.fold_task[(size_t)t * 5 + fold] = (int)p.tasks.size();
+            p.tasks.push_back({(long long)p.idx.size(), (int)n, T.stat, T.C, T.gamma});
+            for (const std::vector<int> *rows : {&first, &second})
+                for (int r : *rows) {
+                    const int sample = p.idx[T.off + r];
+                    const signed char sg = p.sign[T.off + r];
+                    p.idx.push_back(sample);
+                    p.sign.push_back(sg);
+                }
+            if (end > begin) {
+                f.job_task.push_back(f.fold_task[(size_t)t * 5 + fold]);
+                f.job_stat.push_back(T.stat);
+                for (int k = begin; k < end; ++k) {
+                    f.test_idx.push_back(p.idx[T.off + perm[k]]);
+                    f.where.push_back(T.off + perm[k]);
+                }
+                f.test_off.push_back((int64_t)f.test_idx.size());
+            }
+        }
+    }
+    return PAA_OK;
+}
+
+// SVC(probability=True).fit for every job: the full fits, Platt's folds and the sigmoid fits; see paa_hip.h
+extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                     const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
+                                     const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                     int iters_per_launch, const int64_t *seed, int n_pairs, int64_t n_rows, double *alpha_y,
+                                     double *rho, double *prob_a, double *prob_b, int32_t *n_sv, int32_t *task_iterations,
+                                     int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
+                                     int32_t *n_launches) {
+    // check
+    if (!X || !labels || !train_off || !train_idx || !mean || !std || !C || !gamma || !seed || !alpha_y || !rho || !prob_a || !prob_b ||
+        !n_sv || !task_iterations || !task_status || !sig_iterations || !sig_stop)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, eps, max_iter, iters_per_launch))) return rc;
+    if (n_jobs < 1) return fail(PAA_ERR_ARG, "no jobs");
+    if ((rc = sweep_offsets_check(train_off, n_jobs, "train"))) return rc;
+    const int64_t n_t = train_off[n_jobs];
+    if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
+    for (int64_t i = 0; i < n_t; ++i)
+        if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
+    for (int j = 0; j < n_jobs; ++j)
+        if (seed[j] < 0 || seed[j] > 0x7fffffffLL) return fail(PAA_ERR_ARG, "job %d: seed %lld: libsvm's random_seed is in 0 .. 2^31 - 1", j, (long long)seed[j]);
+    // the tasks: the full fit of every pair, then the folds
+    PairTasks p;
+    if ((rc = svc_pair_tasks(p, labels, n_jobs, train_off, train_idx, C, gamma, kernel_type))) return rc;
+    const size_t np = p.tasks.size(), rows_full = p.idx.size();
+    if (n_pairs != (int)np || n_rows != (int64_t)rows_full)
+        return fail(PAA_ERR_ARG, "n_pairs = %d, n_rows = %lld: the jobs make %d pairs of %lld rows", n_pairs, (long long)n_rows, (int)np, (long long)rows_full);
+    std::vector<int64_t> prob_off(np + 1, 0);
+    int l_max = 0;
+    for (size_t t = 0; t < np; ++t) {
+        prob_off[t + 1] = prob_off[t] + p.tasks[t].n;
+        l_max = std::max(l_max, p.tasks[t].n);
+    }
+    std::vector<double> cv(rows_full, 0.0);
+    PlattFolds f;
+    if ((rc = platt_folds(f, p, seed, cv, kernel_type))) return rc;
+    if (p.tasks.size() > 0x3fffffffULL || f.test_idx.size() > (size_t)kSweepMaxQ) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
+    if ((rc = ensure_init())) return rc;
+    // upload: a fold with held-out rows is a scoring job of one pair, standardised as its job
+    const int n_score = (int)f.job_task.size();
+    const int64_t n_q = f.test_off[n_score];
+    const std::vector<knn::SplitBlock> blocks = sweep_blocks(f.test_off.data(), n_score, smo::kQueriesPerBlock);
+    std::vector<double> s_mean((size_t)std::max(n_score, 1) * n_dims, 0.0), s_std((size_t)std::max(n_score, 1) * n_dims, 1.0);
+    for (int s = 0; s < n_score; ++s) {
+        std::copy(mean + (size_t)f.job_stat[s] * n_dims, mean + (size_t)(f.job_stat[s] + 1) * n_dims, s_mean.begin() + (size_t)s * n_dims);
+        std::copy(std + (size_t)f.job_stat[s] * n_dims, std + (size_t)(f.job_stat[s] + 1) * n_dims, s_std.begin() + (size_t)s * n_dims);
+    }
+    std::vector<int> job_k((size_t)std::max(n_score, 1), 2);
+    f.job_task.push_back((int)p.tasks.size());
+    const size_t sb = (size_t)n_jobs * n_dims * 8, rows = p.idx.size(), nt = p.tasks.size();
+    const knn::SplitBlock none{0, 0};
+    DevBlock block;
+    BlockPart parts[] = {{p.tasks.data(), nt * sizeof(smo::SmoTask), 8},
+                         {mean, sb, 8},
+                         {std, sb, 8},
+                         {s_mean.data(), s_mean.size() * 8, 8},
+                         {s_std.data(), s_std.size() * 8, 8},
+                         {f.test_off.data(), (size_t)(n_score + 1) * 8, 8},
+                         {prob_off.data(), (np + 1) * 8, 8},
+                         {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
+                         {p.idx.data(), rows * 4, 4},
+                         {n_q ? f.test_idx.data() : p.idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
+                         {f.job_task.data(), (size_t)(n_score + 1) * 4, 4},
+                         {job_k.data(), job_k.size() * 4, 4},
+                         {p.sign.data(), rows, 1}};
+    if ((rc = block_upload(block, parts, 13, "the probabilistic SVM jobs"))) return rc;
+    std::vector<int32_t> q_label((size_t)n_q);
+    std::vector<double> q_dec((size_t)n_q);
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0,
+                    {{n_q ? q_label.data() : nullptr, (size_t)n_q * 4}, {n_q ? q_dec.data() : nullptr, (size_t)n_q * 8}})))
+        return rc;
+    // solve the batch
+    smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[8], parts[12], n_dims, kernel_type, eps, max_iter);
+    SmoState s;
+    std::vector<int> st_words;
+    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches))) return rc;
+    std::vector<int32_t> iters(nt);
+    HIP_TRY(hipMemcpyAsync(iters.data(), m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(alpha_y, m.alpha_y, rows_full * 8, hipMemcpyDeviceToHost, cs()));      // the full fits come first
+    HIP_TRY(hipMemcpyAsync(rho, m.rho, np * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(n_sv, m.n_sv, np * 4, hipMemcpyDeviceToHost, cs()));
+    // score the held-out rows of every fold
+    if (n_q) {
+        smo::SvcFitDev v{};
+        v.X = st.feats;
+        v.test_off = (const long long *)parts[5].dev;
+        v.blocks = (const knn::SplitBlock *)parts[7].dev;
+        v.test_idx = (const int *)parts[9].dev;
+        v.job_task = (const int *)parts[10].dev;
+        v.job_k = (const int *)parts[11].dev;
+        v.mean = (const double *)parts[3].dev;
+        v.scale = (const double *)parts[4].dev;
+        v.tasks = m.tasks;
+        v.idx = m.idx;
+        v.alpha_y = m.alpha_y;
+        v.rho = m.rho;
+        v.n_dims = n_dims;
+        v.rbf = m.rbf;
+        v.max_pairs = 1;
+        LAUNCH_TRY("fold scoring", launch::svc_pairs(v, (long long)blocks.size(), (int32_t *)st.out[0], (double *)st.out[1], cs()));
+    }
+    if ((rc = finish(st))) return rc;
+    for (int64_t q = 0; q < n_q; ++q) cv[f.where[q]] = q_dec[q];
+    for (size_t t = 0; t < np; ++t) {
+        task_iterations[t * 6] = iters[t];
+        task_status[t * 6] = st_words[t];
+        for (int fold = 0; fold < 5; ++fold) {
+            const int ft = f.fold_task[t * 5 + fold];
+            task_iterations[t * 6 + 1 + fold] = ft < 0 ? 0 : iters[ft];
+            task_status[t * 6 + 1 + fold] = ft < 0 ? 0 : st_words[ft];
+        }
+    }
+    if (cv_dec) std::copy(cv.begin(), cv.end(), cv_dec);
+    // the sigmoid of every pair: its held-out values in pair-row order with the signs of its full task
+    DevBlock d_cv;
+    BlockPart cv_part[] = {{cv.data(), rows_full * 8, 8}};
+    if ((rc = block_upload(d_cv, cv_part, 1, "the held-out decision values"))) return rc;
+    return platt_run((const double *)cv_part[0].dev, m.sign, (const long long *)parts[6].dev, (int)np, l_max, prob_a, prob_b,
+                     sig_iterations, sig_stop);
+}

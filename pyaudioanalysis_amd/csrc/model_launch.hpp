@@ -114,6 +114,22 @@ struct SvcFitDev {
     int n_dims, rbf, max_pairs;
 };
 }  // namespace smo
+namespace platt {
+constexpr int kThreads = 256;             // kernels_platt.hpp: one workgroup per problem (the held-out values of one class pair)
+constexpr int kMaxRows = smo::kMaxRows;   // values of a problem: they stay in LDS with their signs (72 KB)
+constexpr int kMaxIter = 100;             // sigmoid_train's constants (svm.cpp)
+constexpr int kMaxHalvings = 34;          // step 1, 1/2, ... 2^-33: the steps >= kMinStep
+constexpr double kMinStep = 1e-10, kSigma = 1e-12, kEps = 1e-5;
+enum Stop { kConverged = 0, kLineSearchFailed = 1, kMaxIterations = 2 };
+// a batch of sigmoid fits: device pointers.  Problem p owns dec / sign [off[p] .. off[p + 1] - 1]
+struct PlattDev {
+    const double *dec;
+    const signed char *sign;  // +1: the pair's first class, -1: the second
+    const long long *off;     // [n_problems + 1]
+    double *A, *B;            // out per problem
+    int *iter, *stop;         // out per problem: Newton iterations; Stop
+};
+}  // namespace platt
 namespace svrfit {
 // a batch of epsilon-SVR dual problems and their state (kernels_svrfit.hpp): device pointers.  A task is an smo::SmoTask (its n rows
 // are idx[off ..]); its 2 n dual variables -- variable v stands for row v mod n, with the sign +1 for v < n and -1 for v >= n --
@@ -229,6 +245,9 @@ int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double 
 // ... the geometry for tests that aim at its edges: threads per workgroup, groups, the row limit, test rows per scoring
 // workgroup, the default iterations per launch, the dims limit
 void smo_geometry(int out6[6]);
+// kernels_platt.hpp: libsvm's sigmoid_train for each of the n_problems problems of p (one workgroup each; l_max: the longest
+// of them, which sizes the LDS); -2 when l_max exceeds platt::kMaxRows
+int platt_sigmoid(const platt::PlattDev &p, int n_problems, int l_max, hipStream_t stream);
 // kernels_svrfit.hpp: smo_step for a batch of epsilon-SVR tasks (the limits are the SMO solver's)
 int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows

@@ -15,6 +15,7 @@
 #include <memory>
 #include <condition_variable>
 #include <mutex>
+#include <random>
 #include <string>
 #include <tuple>
 #include <utility>
