@@ -523,6 +523,66 @@ int paa_forest_dev_predict_f64(const void *handle, const double *d_feats, int n_
                                const double *d_mean, const double *d_std, int32_t *d_label_index, double *d_proba,
                                double *d_raw);
 
+/* ---- fitting the tree ensembles: audioTrainTest.train_random_forest / train_extra_trees (audioTrainTest.py:158-178, :202-219) and the
+ * forest half of evaluate_classifier (:631-700) -------------------------------------------------------------------------------------
+ * A TREE is scikit-learn 1.7.2's DecisionTreeClassifier / ExtraTreeClassifier as its forests fit it: DepthFirstTreeBuilder, Gini,
+ * BestSplitter (splitter 0, "randomforest") or RandomSplitter (splitter 1, "extratrees"), max_features = max(1, int(sqrt(n_dims))),
+ * min_samples_split 2, min_samples_leaf 1, no depth limit, integer sample weights (a forest's bootstrap counts; 0: the row is out
+ * of the bag).  One workgroup builds one tree, all trees of a call side by side, over index lists into ONE resident sample matrix.
+ * The builder is restated operation for operation (the float32 input (float)((x - mean) / std), the rand_r xorshift, the
+ * Fisher-Yates feature draw with its constant-feature bookkeeping, the 1e-7 candidate rule, the proxy improvement, the thresholds,
+ * the leaf rules, the preorder numbering), so every array equals scikit-learn's bit for bit, for a tree alone or at any place of
+ * any batch.
+ *
+ * paa_tree_fit_tasks_f64 -- the trees alone:
+ *   X [n_samples][n_dims]    every sample, row-major (1 <= n_dims <= 256, 1 <= n_samples < 2^31)
+ *   job_off [n_jobs + 1], job_idx / job_label [job_off[n_jobs]]   job j owns the rows job_idx[job_off[j] .. job_off[j+1]-1] of X with
+ *                            the class indices job_label[..] in 0 .. job_k[j] - 1; 1..8192 rows (PAA_TREE_MAX_ROWS), 1..64 classes
+ *   mean, std [n_jobs][n_dims]   job j's standardisation
+ *   task_job, task_seed [n_tasks]   tree t is fitted on job task_job[t] with the rand_r state task_seed[t] (0 .. 2^32 - 1; scikit-learn
+ *                            draws it as RandomState(random_state).randint(0, 2^31 - 1))
+ *   task_weight              tree after tree, one weight in 0 .. 8191 per row of the tree's job; one of them must be positive
+ *   total_nodes, total_values   the room of the outputs: tree t owns cap_t = 2 (rows of positive weight) - 1 node slots, behind those
+ *                            of the trees before it, and cap_t * job_k values likewise
+ * Outputs: job_flags [n_jobs] (1: a standardised value is infinite in float32, 2: one is NaN; when any is set NOTHING is fitted and
+ * the other outputs are untouched); node_count [n_tasks]; per node slot children_left, children_right (-1: a leaf; tree-local),
+ * feature (-2: a leaf), threshold (-2.0), impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left and value
+ * [job_k] = the class fractions, as tree_.value holds them.
+ *
+ * paa_forest_fit_splits_f64 -- the sweep, in the job form of paa_knn_splits_f64 (labels, train_off / train_idx, test_off / test_idx,
+ * mean / std [n_jobs][n_dims]) plus n_estimators [n_jobs].  Job j's class indices are re-encoded to the classes PRESENT in its
+ * training list, ascending (scikit-learn's np.unique).  Its trees t = sum of n_estimators before j .. take tree_seed [t] and, when
+ * tree_weight is not NULL, the weights tree_weight [tree after tree, one per training row of the tree's job] (NULL: every row 1, an
+ * ExtraTreesClassifier).  The trees are fitted in chunks of whole jobs within 1 GiB of device scratch, every test row is scored on
+ * the device by the kernels of paa_forest_predict_f64 (sum over the trees in tree order, divided by n_estimators, first arg-max);
+ * no tree crosses to the host.
+ *   label_out [Q]            the class INDEX (a value of `labels`); -1: a test value is infinite in float32
+ *   proba [Q][max_classes]   (may be NULL) column c: the job's c-th present class; zeros past a job's classes
+ *   job_flags [n_jobs]       as above; when any is set the call stops there and label_out / proba are not valid
+ *   n_chunks                 (may be NULL)
+ * PAA_ERR_ARG, with a message and before the device is touched: a null pointer (other than the optional ones), offsets that do not
+ * begin at 0 or decrease, an index outside 0..n_samples-1, a class index outside its range, an empty job, a weight outside 0..8191, a
+ * tree without a positive weight, a seed outside 0..2^32-1, n_estimators < 1, totals that differ from what the tasks make.
+ * PAA_ERR_UNSUPPORTED, likewise: n_dims > 256, a job of more than 8192 rows or 64 classes.  Synchronous, host buffers in and out.
+ * Not served: other criteria, depth or leaf-size limits, class weights, missing values, gradient boosting, regressors.       */
+#define PAA_TREE_MAX_ROWS 8192
+#define PAA_TREE_MAX_WEIGHT 8191
+#define PAA_TREE_BEST 0
+#define PAA_TREE_RANDOM 1
+int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off, const int32_t *job_idx,
+                           const int32_t *job_label, const int32_t *job_k, const double *mean, const double *std, int n_tasks,
+                           const int32_t *task_job, const int64_t *task_seed, const int32_t *task_weight, int splitter,
+                           int64_t total_nodes, int64_t total_values, int32_t *job_flags, int32_t *node_count, int32_t *children_left,
+                           int32_t *children_right, int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                           double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value);
+int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                              const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                              const double *mean, const double *std, const int32_t *n_estimators, int splitter,
+                              const int64_t *tree_seed, const int32_t *tree_weight, int32_t *label_out, double *proba, int max_classes,
+                              int32_t *job_flags, int32_t *n_chunks);
+/* tests: out6 = threads per workgroup, rows per job, classes, dims, the largest weight, MiB of scratch per chunk */
+int paa_debug_tree_fit_geometry(int32_t *out6);
+
 /* ---- audioSegmentation.hmm_segmentation / train_hmm_compute_statistics (audioSegmentation.py:287-492) -------------------
  * Gaussian hidden Markov models with one diagonal Gaussian per state, as the reference trains them and hmmlearn's
  * GaussianHMM.predict decodes them.  The model: startprob [K], transmat [K][K], means [K][n_dims], covars [K][n_dims] --

@@ -22,6 +22,8 @@ pyAudioAnalysis/audioTrainTest.py).
     svm_split_fit_predict(X, labels, jobs, kernel, ...), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
     train_svm_device(features, labels, c_param, kernel, random_state=None), to_sklearn_svc(model)   SVC(probability=True).fit on the GPU
     svc_fit_proba(X, labels, jobs, kernel, ...), platt_sigmoid(dec, signs, offsets)   its stages: fits, folds and sigmoids; the sigmoid alone
+    forest_split_fit_predict(X, labels, jobs, kind, proba=False), tree_fit(X, tasks, splitter)   every forest fit of a sweep side by side on the GPU
+    train_forest_device(features, labels, n_estimators, kind, random_state=None), to_sklearn_forest(arrays, kind)   the forests' fit on the GPU
 
 For the model types "svm" / "svm_rbf" (the shipped SVC(probability=True) models of data/models) predict() and
 predict_proba() run on the GPU (kernels_svc.hpp through paa_svc_*): libsvm's decision values, votes, Platt sigmoids and
@@ -45,6 +47,11 @@ fit of extract_features_and_train and its model file are scikit-learn's by defau
 Platt probabilities included (paa_svc_fit_proba_f64: per pair the full fit and libsvm's five cross-validation fits for
 scikit-learn's seed as smo_kernel tasks, the held-out rows scored by svc_pairs_kernel, probA_ / probB_ by platt_sigmoid_kernel);
 to_sklearn_svc makes a real SVC of its result, which extract_features_and_train(final_fit="device") pickles as the model file.
+With forest_fit="device" "randomforest" / "extratrees" are fitted on the GPU too: one workgroup per tree builds scikit-learn's
+depth-first Gini tree bit for bit (tree_fit_kernel through paa_tree_fit_tasks_f64 / paa_forest_fit_splits_f64; the host draws the
+tree seeds, rand_r seeds and bootstrap counts NumPy draws for scikit-learn), the sweep scores every test row with the predict
+kernels, train_forest_device is the final fit and to_sklearn_forest makes the model file's RandomForestClassifier /
+ExtraTreesClassifier.
 smote / use_smote are refused (NotImplementedError).
 Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
 SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
@@ -1427,6 +1434,298 @@ def svr_split_fit_predict(X, y, jobs, kernel="linear", gamma=None, epsilon=0.1, 
     return SvrSplitResult(pred, tp, p.test_off, p.train_off, g_arr, iterations, status, n_sv, int(launches[0]))
 
 
+TREE_MAX_ROWS = 8192                             # PAA_TREE_MAX_ROWS: rows of one tree's training list
+TREE_MAX_WEIGHT = 8191                           # PAA_TREE_MAX_WEIGHT
+RAND_R_MAX = 2147483647                          # scikit-learn's RAND_R_MAX: a splitter's rand_r seed is randint(0, RAND_R_MAX)
+_TREE_SPLITTERS = {"best": 0, "random": 1}       # PAA_TREE_BEST / PAA_TREE_RANDOM
+_FOREST_FIT_KINDS = {"randomforest": "best", "extratrees": "random"}
+_TREE_RS = np.random.RandomState(0)              # tree_inputs' own generator, re-seeded per tree; never NumPy's global state
+_TREE_FIELDS = ("children_left", "children_right", "feature", "threshold", "impurity", "n_node_samples", "weighted_n_node_samples",
+                "missing_go_to_left", "value")
+
+
+def tree_fit_geometry():
+    """(threads per workgroup, rows per tree, classes, dims, the largest weight, MiB of device scratch per chunk of a sweep) of
+    the tree builder (kernels_treefit.hpp)."""
+    geo = np.zeros(6, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_debug_tree_fit_geometry(geo.ctypes.data_as(_ffi.c_i32p)))
+    return tuple(int(v) for v in geo)
+
+
+def _raise_tree_flags(flags):
+    """scikit-learn's input validation of the standardised float32 training rows, for the whole call: NaN before infinity."""
+    flags = np.asarray(flags)
+    if np.any(flags & 2):
+        raise ValueError("Input X contains NaN.")
+    if np.any(flags & 1):
+        raise ValueError("Input X contains infinity or a value too large for dtype('float32').")
+
+
+def _check_tree_rows(n, what):
+    if n > TREE_MAX_ROWS:
+        raise NotImplementedError("%s has %d training rows: the GPU tree builder serves at most %d rows per tree" % (what, n, TREE_MAX_ROWS))
+
+
+def _splitter_of(kind):
+    if kind in _TREE_SPLITTERS:
+        return kind
+    if kind not in _FOREST_FIT_KINDS:
+        raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees' (splitters 'best' / 'random')" % (kind,))
+    return _FOREST_FIT_KINDS[kind]
+
+
+def forest_tree_seeds(random_state, n_estimators):
+    """Per tree the random_state a scikit-learn forest gives its estimators: check_random_state(random_state), then ONE
+    randint(np.iinfo(np.int32).max) per tree, in order (None: NumPy's global state, an int: a fresh RandomState)."""
+    if random_state is None:
+        rs = np.random.mtrand._rand
+    elif isinstance(random_state, np.random.RandomState):
+        rs = random_state
+    else:
+        rs = _TREE_RS
+        rs.seed(random_state)
+    return [int(v) for v in rs.randint(np.iinfo(np.int32).max, size=int(n_estimators))] if int(n_estimators) > 0 else []
+
+
+def tree_inputs(seed, n_rows, bootstrap):
+    """What NumPy draws for ONE tree of a forest whose estimator has random_state=seed: (the splitter's rand_r seed,
+    RandomState(seed).randint(0, RAND_R_MAX); the in-bag counts of a bootstrap, np.bincount of
+    RandomState(seed).randint(0, n, n, dtype=np.int32), or None).  Both are first draws of their own RandomState(seed)."""
+    _TREE_RS.seed(seed)                           # re-seeding one RandomState gives RandomState(seed)'s stream at a twentieth of the cost
+    rand_r = int(_TREE_RS.randint(0, RAND_R_MAX))
+    if not bootstrap:
+        return rand_r, None
+    _TREE_RS.seed(seed)
+    picks = _TREE_RS.randint(0, n_rows, n_rows, dtype=np.int32)
+    return rand_r, np.bincount(picks, minlength=n_rows).astype(np.int32)
+
+
+class TreeFitResult:
+    """What tree_fit returns: trees, one dict per task with scikit-learn's tree_ arrays (children_left, children_right, feature,
+    threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value [nodes][n_classes]), and classes, per
+    task the classes present among its rows, ascending."""
+
+    def __init__(self, trees, classes):
+        self.trees, self.classes = trees, classes
+
+
+def tree_fit(X, tasks, splitter):
+    """Decision trees over ONE sample matrix, all built side by side (paa_tree_fit_tasks_f64, tree_fit_kernel: scikit-learn
+    1.7.2's DepthFirstTreeBuilder with Gini, max_features='sqrt', no depth limit, bit for bit).  X [n_samples][n_dims]; a task is
+    (rows, y, weights, seed, mean, scale): the rows X[rows] standardised as float32((x - mean) / scale), their labels y
+    (re-encoded to the classes present, as np.unique does), integer weights (0: out of the bag; None: all 1) and the
+    splitter's rand_r seed.  splitter: 'best' (DecisionTreeClassifier, 'randomforest') or 'random' (ExtraTreeClassifier,
+    'extratrees').  Tasks that pass the SAME rows, y, mean and scale objects share one float32 copy on the device.  More than
+    8192 rows in a task raise NotImplementedError, NaN / infinity scikit-learn's ValueError.  Returns a TreeFitResult."""
+    splitter = _splitter_of(splitter)
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    tasks = list(tasks)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("sample matrix of shape %s" % (X.shape,))
+    if not tasks:
+        raise ValueError("no tasks")
+    n_samples, n_dims = X.shape
+    job_of, rows_l, label_l, k_l, means, scales, classes_l = {}, [], [], [], [], [], []
+    task_job, seeds, weights = [], [], []
+    for t, task in enumerate(tasks):
+        if len(task) != 6:
+            raise ValueError("task %d: (rows, y, weights, seed, mean, scale) expected" % t)
+        key = tuple(id(task[i]) for i in (0, 1, 4, 5))
+        if key not in job_of:
+            r = _index_list(task[0], "row", t)
+            y = np.asarray(task[1]).reshape(-1)
+            if y.shape[0] != r.shape[0]:
+                raise ValueError("task %d: %d rows and %d labels" % (t, r.shape[0], y.shape[0]))
+            _check_tree_rows(r.shape[0], "task %d" % t)
+            mean, scale = _stats(task[4], task[5], n_dims)
+            classes, idx = np.unique(y, return_inverse=True) if y.shape[0] else (y, y)
+            job_of[key] = len(rows_l)
+            rows_l.append(r)
+            label_l.append(idx.astype(np.int32).reshape(-1))
+            k_l.append(int(classes.shape[0]))
+            classes_l.append(classes)
+            means.append(mean)
+            scales.append(scale)
+        j = job_of[key]
+        n = rows_l[j].shape[0]
+        w = np.ones(n, dtype=np.int64) if task[2] is None else np.asarray(task[2]).reshape(-1)
+        if w.shape[0] != n or (w.size and w.dtype.kind not in "iub"):
+            raise ValueError("task %d: %d rows and weights of shape %s, dtype %s (integers expected)" % (t, n, w.shape, w.dtype))
+        task_job.append(j)
+        seeds.append(int(task[3]))
+        weights.append(np.clip(w.astype(np.int64), -1, TREE_MAX_WEIGHT + 1).astype(np.int32))
+    idx, off = _packed(rows_l, np.int32)
+    label = np.ascontiguousarray(np.concatenate(label_l), dtype=np.int32)
+    k = np.array(k_l, dtype=np.int32)
+    mean, scale = np.stack(means), np.stack(scales)
+    task_job = np.array(task_job, dtype=np.int32)
+    seed = np.array(seeds, dtype=np.int64)
+    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32)
+    caps = np.array([max(2 * int(np.count_nonzero(w)) - 1, 0) for w in weights], dtype=np.int64)
+    node_off = _offsets(caps)
+    val_off = _offsets(caps * k[task_job])
+    total_nodes, total_values, n_tasks = int(node_off[-1]), int(val_off[-1]), len(tasks)
+    i32 = lambda: np.zeros(max(total_nodes, 1), dtype=np.int32)          # noqa: E731
+    f64 = lambda: np.zeros(max(total_nodes, 1), dtype=np.float64)        # noqa: E731
+    out = {"children_left": i32(), "children_right": i32(), "feature": i32(), "threshold": f64(), "impurity": f64(),
+           "n_node_samples": i32(), "weighted_n_node_samples": f64(), "missing_go_to_left": np.zeros(max(total_nodes, 1), dtype=np.uint8)}
+    value = np.zeros(max(total_values, 1), dtype=np.float64)
+    flags, count = np.zeros(len(rows_l), dtype=np.int32), np.zeros(n_tasks, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_tree_fit_tasks_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, len(rows_l), _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_i32p(label), _ffi.as_i32p(k),
+        _ffi.as_f64p(mean), _ffi.as_f64p(scale), n_tasks, _ffi.as_i32p(task_job), _ffi.as_i64p(seed), _ffi.as_i32p(weight),
+        _TREE_SPLITTERS[splitter], total_nodes, total_values, _ffi.as_i32p(flags), _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
+        _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
+        _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
+        out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(value)))
+    _raise_tree_flags(flags)
+    trees = []
+    for t in range(n_tasks):
+        a, n_nodes, kt = int(node_off[t]), int(count[t]), int(k[task_job[t]])
+        tree = {name: arr[a:a + n_nodes].astype(np.int64) if arr.dtype == np.int32 else arr[a:a + n_nodes].copy() for name, arr in out.items()}
+        tree["value"] = value[int(val_off[t]):int(val_off[t]) + n_nodes * kt].reshape(n_nodes, kt).copy()
+        trees.append(tree)
+    return TreeFitResult(trees, [classes_l[j] for j in task_job])
+
+
+class ForestSplitResult(_SplitResult):
+    """What forest_split_fit_predict returns: label [Q] (class values as in `labels`), proba [Q][max_classes] or None (column c:
+    the job's c-th present class; zeros past a job's classes), test_off [n_jobs + 1], classes (per job the classes present in its
+    training list, ascending), n_estimators [n_jobs] and the number of chunks the trees were fitted in."""
+
+    def __init__(self, label, proba, test_off, classes, n_estimators, n_chunks):
+        self.label, self.proba, self.test_off, self.classes, self.n_estimators, self.n_chunks = label, proba, test_off, classes, n_estimators, n_chunks
+
+    def job(self, j):
+        """(labels, probabilities [n_test][classes present in job j] or None) of job j."""
+        r = self._rows(j)
+        return self.label[r], None if self.proba is None else self.proba[r, :len(self.classes[j])]
+
+
+def forest_split_fit_predict(X, labels, jobs, kind, proba=False):
+    """RandomForestClassifier / ExtraTreesClassifier(n_estimators, random_state=seed).fit(train).predict(test) for every job of a
+    sweep over ONE sample matrix (paa_forest_fit_splits_f64: one workgroup per tree, the trees of all jobs side by side in chunks of
+    bounded device scratch; every test row is scored on the device by the traversal and reduction kernels of forest_predict, no
+    tree crosses to the host).  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the training rows); a job is
+    (train_idx, test_idx, mean, scale, (n_estimators, seed)); kind 'randomforest' (bootstrap) or 'extratrees'.  The host does what
+    NumPy does for scikit-learn: per job forest_tree_seeds(seed, n_estimators), per tree tree_inputs.  Labels and probabilities
+    equal scikit-learn's for the same seeds bit for bit.  A training list above 8192 rows raises NotImplementedError before the
+    device is touched; NaN / infinity raise scikit-learn's ValueError.  Returns a ForestSplitResult."""
+    if kind not in _FOREST_FIT_KINDS:
+        raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
+    p = _pack_jobs(X, labels, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
+    n_samples, n_dims = p.X.shape
+    n_jobs = len(p.last)
+    counts = np.diff(p.train_off)
+    for j in range(n_jobs):
+        _check_tree_rows(int(counts[j]), "job %d" % j)
+    classes = [np.unique(p.labels[rows]) for rows in p.inside]
+    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
+    bootstrap = kind == "randomforest"
+    seeds, weights = [], []
+    for j in range(n_jobs):
+        for s in forest_tree_seeds(p.last[j][1], n_est[j]):
+            rand_r, w = tree_inputs(s, int(counts[j]), bootstrap and counts[j] > 0)
+            seeds.append(rand_r)
+            if w is not None:
+                weights.append(w)
+    seed = np.array(seeds, dtype=np.int64)
+    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32) if weights else None
+    Q, max_classes = int(p.test_off[-1]), max(max(len(c) for c in classes), 1)
+    label = np.zeros(Q, dtype=np.int32)
+    P = np.zeros((Q, max_classes), dtype=np.float64) if proba else None
+    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_forest_fit_splits_f64(
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
+        _TREE_SPLITTERS[_FOREST_FIT_KINDS[kind]], _ffi.as_i64p(seed), _ffi.as_i32p(weight) if weight is not None else None,
+        _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None, max_classes, _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
+    _raise_tree_flags(flags)
+    ForestModel._raise_invalid(label)
+    return ForestSplitResult(label.astype(np.int64), P, p.test_off, classes, n_est, int(chunks[0]))
+
+
+def train_forest_device(features, labels, n_estimators, kind="randomforest", *, random_state=None):
+    """train_random_forest / train_extra_trees on the GPU: RandomForestClassifier / ExtraTreesClassifier(n_estimators,
+    random_state=random_state).fit(features, labels) by tree_fit -- per tree the seed scikit-learn's forest draws
+    (forest_tree_seeds; None: from NumPy's global state exactly as scikit-learn does), the splitter's rand_r seed and, for
+    'randomforest', the bootstrap counts (tree_inputs).  Returns a ForestArrays of kind "averaged" whose arrays equal those of
+    scikit-learn's estimators_ bit for bit (it also carries impurity, n_node_samples and weighted_n_node_samples, for
+    to_sklearn_forest), so forest_model, forest_predict, classifier_wrapper and device_model take it.  More than 8192 rows raise
+    NotImplementedError before the device is touched; there is no CPU fallback."""
+    if kind not in _FOREST_FIT_KINDS:
+        raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    raw = np.asarray(labels).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
+    if int(n_estimators) < 1:
+        raise ValueError("n_estimators = %r" % (n_estimators,))
+    n, n_dims = X.shape
+    _check_tree_rows(n, "the training set")
+    rows, mean, scale = np.arange(n), np.zeros(n_dims), np.ones(n_dims)
+    tasks = []
+    for s in forest_tree_seeds(random_state, n_estimators):
+        rand_r, w = tree_inputs(s, n, kind == "randomforest")
+        tasks.append((rows, raw, w, rand_r, mean, scale))
+    res = tree_fit(X, tasks, kind)
+    cat = lambda name: np.concatenate([t[name] for t in res.trees])        # noqa: E731
+    arrays = ForestArrays("averaged", _offsets([t["feature"].shape[0] for t in res.trees]), cat("children_left"), cat("children_right"),
+                          cat("feature"), cat("threshold"), cat("missing_go_to_left"), cat("value"), res.classes[0], n_dims)
+    arrays.impurity, arrays.n_node_samples, arrays.weighted_n_node_samples = cat("impurity"), cat("n_node_samples"), cat("weighted_n_node_samples")
+    return arrays
+
+
+def to_sklearn_forest(arrays, kind):
+    """A real fitted sklearn.ensemble.RandomForestClassifier ('randomforest') / ExtraTreesClassifier ('extratrees') with the trees of
+    a ForestArrays of kind "averaged" (every Tree is built through __setstate__): it predicts as scikit-learn predicts from those
+    arrays and pickles as the reference's model files do.  impurity, n_node_samples and weighted_n_node_samples are those of
+    train_forest_device when the arrays carry them, zeros otherwise (prediction reads none of them).  Needs scikit-learn."""
+    import sklearn.ensemble
+    from sklearn.tree._tree import NODE_DTYPE, Tree
+    if kind not in _FOREST_FIT_KINDS:
+        raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
+    a = forest_arrays(arrays)
+    if a.kind != "averaged":
+        raise ValueError("a tree ensemble of kind %r: 'averaged' expected" % (a.kind,))
+    n_trees, k = a.node_offsets.shape[0] - 1, a.n_classes
+    cls = sklearn.ensemble.RandomForestClassifier if kind == "randomforest" else sklearn.ensemble.ExtraTreesClassifier
+    forest = cls(n_estimators=n_trees)
+    forest._validate_estimator()
+    forest.classes_ = np.asarray(a.classes_)
+    forest.n_classes_ = k
+    forest.n_features_in_ = a.n_dims
+    forest.n_outputs_ = 1
+    value = a.value.reshape(-1, k)
+    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
+    forest.estimators_ = []
+    for t in range(n_trees):
+        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
+        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
+        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
+        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
+        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
+        for name in extra:
+            if extra[name] is not None:
+                nodes[name] = extra[name][lo:hi]
+        depth, level = 0, np.zeros(1, dtype=np.int64)          # the tree's depth, level by level
+        while True:
+            below = np.concatenate([nodes["left_child"][level], nodes["right_child"][level]])
+            level = below[below >= 0]
+            if not level.size:
+                break
+            depth += 1
+        tree = Tree(a.n_dims, np.array([k], dtype=np.intp), 1)
+        tree.__setstate__({"max_depth": depth, "node_count": hi - lo, "nodes": nodes,
+                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, k))})
+        est = forest._make_estimator(append=False)
+        est.tree_ = tree
+        est.classes_, est.n_classes_ = forest.classes_, k
+        est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, max(1, int(np.sqrt(a.n_dims)))
+        forest.estimators_.append(est)
+    return forest
+
+
 def _draw_split(n_samples, train_percentage):
     """One random split as (train indices, test indices): train_test_split over the sample indices consumes NumPy's
     global state exactly as the reference's train_test_split(X, y, ...) (:648-649) does, and X[train], X[test], y[test]
@@ -1436,7 +1735,7 @@ def _draw_split(n_samples, train_percentage):
 
 
 def evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                        train_percentage=0.90, smote=False, *, svm_fit="sklearn"):
+                        train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn"):
     """Picks the classifier parameter with the best cross-validated accuracy (parameter_mode 0) or macro F1 (1)
     (reference :576-771): for every value, n_exp random splits (n_exp = -1: int(50000 / n_samples) + 1), each with its own
     StandardScaler; with list_of_ids the n_exp GroupShuffleSplit(train_size=.8) splits are drawn once and shared by every value.
@@ -1453,19 +1752,30 @@ def evaluate_classifier(features, class_names, classifier_name, params, paramete
     pair of classes of every split on the GPU (libsvm's solver, no Platt cross-validation: the sweep reads vote labels only)
     and classifies every test row.  The one visible difference to the default: scikit-learn's probabilistic fits draw a libsvm
     seed from NumPy's global state between the splits, the device mode consumes that state for the splits only, so for one seed
-    the two modes see different splits.  svm_fit="sklearn" (the default) is the behaviour described above, untouched."""
+    the two modes see different splits.  svm_fit="sklearn" (the default) is the behaviour described above, untouched.
+    forest_fit="device" (keyword only; "randomforest" / "extratrees", any other type raises ValueError before any work): the same
+    path -- ALL splits are drawn up front in parameter-major order, then ONE seed per split is drawn from NumPy's global state in
+    job order (np.random.randint(np.iinfo(np.int32).max)), and ONE forest_split_fit_predict call fits the n_estimators trees of
+    every split on the GPU and classifies every test row there.  Every split's predictions are those of scikit-learn's forest
+    with random_state=<that seed> on the same split, bit for bit.  The one visible difference to the default: scikit-learn's
+    fits draw their tree seeds from the global state between the splits, so for one np.random.seed the two modes see different
+    splits.  A split above 8192 training rows raises NotImplementedError.  forest_fit="sklearn" (the default): untouched."""
     return evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids, n_exp,
-                                    train_percentage, smote, svm_fit=svm_fit)[0]
+                                    train_percentage, smote, svm_fit=svm_fit, forest_fit=forest_fit)[0]
 
 
 def evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                             train_percentage=0.90, smote=False, *, svm_fit="sklearn"):
+                             train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn"):
     """evaluate_classifier, returning (the chosen parameter, the confusion matrix of every parameter value, the predictions
     [parameter][experiment] of every split's test rows)."""
     if svm_fit not in ("sklearn", "device"):
         raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
     if svm_fit == "device" and classifier_name not in _SVM_TYPES:
         raise ValueError("svm_fit='device' serves the classifier types %s, not %r" % (" and ".join(_SVM_TYPES), classifier_name))
+    if forest_fit not in ("sklearn", "device"):
+        raise ValueError("forest_fit=%r: 'sklearn' or 'device'" % (forest_fit,))
+    if forest_fit == "device" and classifier_name not in _FOREST_FIT_KINDS:
+        raise ValueError("forest_fit='device' serves the classifier types %s, not %r" % (" and ".join(_FOREST_FIT_KINDS), classifier_name))
     if smote:
         raise NotImplementedError("smote=True: imbalanced-learn's SMOTE makes training rows that are no rows of the sample "
                                   "matrix; this package does not resample")
@@ -1495,14 +1805,16 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
             train_idx, test_idx = shared[e] if list_of_ids else _draw_split(n_samples_total, train_percentage)
             scaler = StandardScaler().fit(X[train_idx])
             splits[-1].append((train_idx, test_idx, scaler.mean_, scaler.scale_))
-            if classifier_name != "knn" and svm_fit != "device":
+            if classifier_name != "knn" and svm_fit != "device" and forest_fit != "device":
                 classifier = _train_classifier(scaler.transform(X[train_idx]), y[train_idx], classifier_name, C_param)
                 predictions[-1].append(list(predict(classifier, classifier_name, X[test_idx].T, scaler.mean_, scaler.scale_)[0])
                                        if len(test_idx) else [])
-    if classifier_name == "knn" or svm_fit == "device":       # one sweep over every split
+    if classifier_name == "knn" or svm_fit == "device" or forest_fit == "device":       # one sweep over every split
         knn, cast = classifier_name == "knn", int if classifier_name == "knn" else float
+        if forest_fit == "device":                            # (n_estimators, the forest's seed): one draw per job, in job order
+            cast = lambda v: (int(v), int(np.random.randint(np.iinfo(np.int32).max)))      # noqa: E731
         jobs = [(tr, te, mean, scale, cast(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
-        res = knn_split_predict(X, y, jobs) if knn else \
+        res = knn_split_predict(X, y, jobs) if knn else forest_split_fit_predict(X, y, jobs, classifier_name) if forest_fit == "device" else \
             svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
         as_label = (lambda v: v) if knn else y.dtype.type      # kNN: the result's int64 as it is
         predictions = [[[as_label(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
@@ -1568,7 +1880,7 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
 
 def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
                                compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn",
-                               final_fit="sklearn"):
+                               final_fit="sklearn", forest_fit="sklearn"):
     """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
     :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
     evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
@@ -1577,7 +1889,11 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     step, evaluate_classifier, and nowhere else.  final_fit (keyword only): "sklearn" (the default) fits the final model with
     scikit-learn; "device" ("svm" / "svm_rbf" only, any other type raises ValueError before any work) fits it with
     train_svm_device and writes the model file in the reference's format, a pickled sklearn.svm.SVC, through to_sklearn_svc --
-    the MEANS file is the same."""
+    the MEANS file is the same.  forest_fit (keyword only): "device" ("randomforest" / "extratrees" only, any other type raises
+    ValueError before any work) tunes n_estimators with evaluate_classifier(forest_fit="device") AND makes the final fit with
+    train_forest_device; the model file is a pickled RandomForestClassifier / ExtraTreesClassifier made by to_sklearn_forest."""
+    if forest_fit not in ("sklearn", "device") or (forest_fit == "device" and classifier_type not in _FOREST_FIT_KINDS):
+        raise ValueError("forest_fit=%r with the classifier type %r" % (forest_fit, classifier_type))
     if svm_fit not in ("sklearn", "device") or (svm_fit == "device" and classifier_type not in _SVM_TYPES):
         raise ValueError("svm_fit=%r with the classifier type %r" % (svm_fit, classifier_type))
     if final_fit not in ("sklearn", "device") or (final_fit == "device" and classifier_type not in _SVM_TYPES):
@@ -1617,7 +1933,8 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
         kept.append(np.array(rows))
     features = kept
     best_param = evaluate_classifier(features, class_names, classifier_type, classifier_par, 1, list_of_ids, n_exp=-1,
-                                     train_percentage=train_percentage, smote=use_smote, svm_fit=svm_fit)
+                                     train_percentage=train_percentage, smote=use_smote, svm_fit=svm_fit,
+                                     forest_fit=forest_fit)
     print("Selected params: {0:.5f}".format(best_param))
     features, labels = features_to_matrix(features)
     scaler = StandardScaler()
@@ -1631,6 +1948,8 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
         if final_fit == "device":
             classifier = to_sklearn_svc(train_svm_device(features, labels, best_param,
                                                          kernel="rbf" if classifier_type == "svm_rbf" else "linear"))
+        elif forest_fit == "device":
+            classifier = to_sklearn_forest(train_forest_device(features, labels, int(best_param), kind=classifier_type), classifier_type)
         else:
             classifier = _train_classifier(features, labels, classifier_type, best_param)
         with open(model_name, "wb") as fid:

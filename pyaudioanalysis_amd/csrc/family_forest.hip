@@ -1,10 +1,12 @@
 // Tree-ensemble classification (kernels_forest.hpp: audioTrainTest.classifier_wrapper for the "randomforest", "extratrees"
-// and "gradientboosting" models) -- own translation unit, see model_launch.hpp.
+// and "gradientboosting" models) and the fit of the first two (kernels_treefit.hpp: audioTrainTest.train_random_forest /
+// train_extra_trees and the forest half of evaluate_classifier) -- own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
 #include "model_launch.hpp"
 #include "kernels_forest.hpp"
+#include "kernels_treefit.hpp"
 
 namespace paa {
 namespace launch {
@@ -33,6 +35,59 @@ int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long
         if (hipGetLastError() != hipSuccess) return -1;
     }
     return 0;
+}
+
+int tree_prep(const treefit::TreeDev &m, int n_jobs, int n_max, hipStream_t stream) {
+    using namespace paa::treefit;
+    if (n_jobs < 1 || n_jobs > 65535 || n_max < 1 || n_max > kMaxRows || m.n_dims < 1 || m.n_dims > kMaxDims) return -1;
+    if (hipMemsetAsync(m.flags, 0, (size_t)n_jobs * sizeof(int), stream) != hipSuccess) return -1;
+    const long long elems = (long long)n_max * m.n_dims;
+    hipLaunchKernelGGL(tree_prep_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads), (unsigned)n_jobs), dim3(kThreads), 0,
+                       stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int k_max, hipStream_t stream) {
+    using namespace paa::treefit;
+    if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows || k_max < 1 || k_max > kMaxClasses) return -2;
+    if (n_tasks < 1 || (splitter != kBest && splitter != kRandom)) return -1;
+    // LDS: the sort words (best: a power of two of 64-bit words; random: the partition's 32-bit buffer) | the rows | best: the class
+    // histogram, 256 columns (128 above 32 classes, which keeps the largest launch below the CU's 160 KB) | the feature arrays
+    int p2 = 2;
+    while (p2 < inbag_max) p2 <<= 1;
+    m.lds_keys = splitter == kBest ? p2 : (inbag_max + 1) / 2;
+    m.lds_rows = (inbag_max + 1) / 2 * 2;
+    m.hist_cols = k_max > 32 ? 128 : 256;
+    const size_t hist = splitter == kBest ? (size_t)k_max * (m.hist_cols + 1) * sizeof(int) : 0;
+    m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4 + hist);
+    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
+    if (lds > 152 * 1024) return -2;
+    const void *kernel = splitter == kBest ? reinterpret_cast<const void *>(&tree_fit_kernel<kBest>)
+                                           : reinterpret_cast<const void *>(&tree_fit_kernel<kRandom>);
+    if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+    if (splitter == kBest)
+        hipLaunchKernelGGL(tree_fit_kernel<kBest>, dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    else
+        hipLaunchKernelGGL(tree_fit_kernel<kRandom>, dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int tree_gather(const double *d_X, int n_dims, const int *d_rows, long long n_rows, double *d_out, long long ld, hipStream_t stream) {
+    using namespace paa::treefit;
+    if (n_rows < 1 || n_dims < 1 || ld < n_rows) return -1;
+    const long long elems = n_rows * n_dims;
+    hipLaunchKernelGGL(tree_gather_kernel, dim3((unsigned)((elems + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_X, n_dims,
+                       d_rows, n_rows, d_out, ld);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+void tree_fit_geometry(int out6[6]) {
+    out6[0] = treefit::kThreads;
+    out6[1] = treefit::kMaxRows;
+    out6[2] = treefit::kMaxClasses;
+    out6[3] = treefit::kMaxDims;
+    out6[4] = treefit::kMaxWeight;
+    out6[5] = (int)(treefit::kChunkBytes >> 20);
 }
 
 }  // namespace launch

@@ -1,0 +1,385 @@
+// Fitting random forests and extra trees on the device (audioTrainTest.train_random_forest / train_extra_trees and the forest half
+// of evaluate_classifier, audioTrainTest.py:158-219, :631-700): a batch of trees over index lists into ONE uploaded sample matrix,
+// one workgroup per tree (paa_tree_fit_tasks_f64: the trees come back as scikit-learn's arrays), and the split sweep built on it
+// (paa_forest_fit_splits_f64: the trees are fitted in chunks of bounded device scratch, every test row is scored by the
+// traversal and reduction kernels of the predict path, no tree crosses to the host).  Kernels: kernels_treefit.hpp and
+// kernels_forest.hpp (family_forest.hip).
+#pragma once
+
+// the limits, for callers and tests: threads per workgroup, rows per job, classes, dims, the largest weight, MiB per chunk
+extern "C" int paa_debug_tree_fit_geometry(int32_t *out6) {
+    if (!out6) return fail(PAA_ERR_ARG, "null");
+    launch::tree_fit_geometry(out6);
+    return PAA_OK;
+}
+
+static int tree_params_check(int n_dims, int splitter) {
+    if (n_dims < 1) return fail(PAA_ERR_ARG, "%d feature dimensions", n_dims);
+    if (n_dims > treefit::kMaxDims) return fail(PAA_ERR_UNSUPPORTED, "%d feature dimensions: at most %d are supported", n_dims, treefit::kMaxDims);
+    if (splitter != treefit::kBest && splitter != treefit::kRandom)
+        return fail(PAA_ERR_ARG, "splitter %d: 0 (best, random forests) and 1 (random, extra trees) are supported", splitter);
+    return PAA_OK;
+}
+static int tree_job_check(int j, int64_t n, int k) {
+    if (n < 1) return fail(PAA_ERR_ARG, "job %d: no training rows", j);
+    if (n > treefit::kMaxRows) return fail(PAA_ERR_UNSUPPORTED, "job %d: %lld training rows: at most %d per tree are supported", j, (long long)n, treefit::kMaxRows);
+    if (k < 1) return fail(PAA_ERR_ARG, "job %d: %d classes", j, k);
+    if (k > treefit::kMaxClasses) return fail(PAA_ERR_UNSUPPORTED, "job %d: %d classes: at most %d are supported", j, k, treefit::kMaxClasses);
+    return PAA_OK;
+}
+static int tree_seed_check(int t, int64_t seed) {
+    if (seed < 0 || seed > 0xffffffffLL) return fail(PAA_ERR_ARG, "tree %d: seed %lld: a rand_r state is in 0 .. 2^32 - 1", t, (long long)seed);
+    return PAA_OK;
+}
+// the weights of one tree over its job's n rows: 0 .. kMaxWeight, one of them positive; *in_bag: the rows with a positive weight
+static int tree_weight_check(int t, const int32_t *w, int64_t n, int *in_bag) {
+    int bag = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (w[i] < 0 || w[i] > treefit::kMaxWeight) return fail(PAA_ERR_ARG, "tree %d: weight %d of row %lld: 0 .. %d", t, w[i], (long long)i, treefit::kMaxWeight);
+        bag += w[i] != 0;
+    }
+    if (!bag) return fail(PAA_ERR_ARG, "tree %d: every row has the weight 0", t);
+    *in_bag = bag;
+    return PAA_OK;
+}
+
+// One batch of trees on the device.  The caller fills jobs (off, n, k, stat; x_off is set here) and tasks (job, seed, w_off,
+// cap = 2 in-bag rows - 1, node_rel; node_off / val_off are set here), uploads X and names the host arrays; run() allocates,
+// makes the float32 copies, reads the flags back and, when no job is flagged, fits every tree
+struct TreeBatch {
+    std::vector<treefit::TreeJob> jobs;
+    std::vector<treefit::TreeTask> tasks;
+    std::vector<int> flags;                   // per job, after run()
+    int64_t total_nodes = 0, total_values = 0;
+    int inbag_max = 0, k_max = 0, n_max = 0;
+    bool any_flag = false;
+    DevBlock in, work;
+    treefit::TreeDev dev{};
+    // the offsets of the outputs: tree after tree, cap nodes and cap * k values each
+    void layout() {
+        int64_t x_off = 0;
+        for (auto &j : jobs) {
+            j.x_off = x_off;
+            x_off += (int64_t)j.n * dev.n_dims;
+            n_max = std::max(n_max, j.n);
+            k_max = std::max(k_max, j.k);
+        }
+        x_words = x_off;
+        total_nodes = total_values = 0;
+        for (auto &t : tasks) {
+            t.node_off = total_nodes;
+            t.val_off = total_values;
+            total_nodes += t.cap;
+            total_values += (int64_t)t.cap * jobs[t.job].k;
+            inbag_max = std::max(inbag_max, (t.cap + 1) / 2);
+        }
+    }
+    int64_t x_words = 0;
+    // device bytes of a batch with these totals (the sweep cuts its chunks by it)
+    static size_t bytes(int64_t x_words, int64_t weights, int64_t nodes, int64_t values, bool arrays) {
+        return (size_t)x_words * 4 + (size_t)weights * 4 + (size_t)nodes * (sizeof(treefit::StackRec) + sizeof(forest::Node) + (arrays ? 41 : 0)) +
+               (size_t)values * 8;
+    }
+    int run(const double *d_X, const int32_t *idx, const int32_t *label, int64_t rows, const int32_t *weight, int64_t n_weights,
+            const double *mean, const double *std, int n_stats, int splitter, bool arrays) {
+        const size_t sb = (size_t)n_stats * dev.n_dims * 8;
+        const int32_t none = 0;
+        BlockPart parts[] = {{jobs.data(), jobs.size() * sizeof(treefit::TreeJob), 8},
+                             {tasks.data(), tasks.size() * sizeof(treefit::TreeTask), 8},
+                             {mean, sb, 8},
+                             {std, sb, 8},
+                             {idx, (size_t)rows * 4, 4},
+                             {label, (size_t)rows * 4, 4},
+                             {n_weights ? weight : &none, (size_t)std::max<int64_t>(n_weights, 1) * 4, 4}};
+        int rc;
+        if ((rc = block_upload(in, parts, 7, "the tree tasks"))) return rc;
+        const size_t n_t = tasks.size(), n_j = jobs.size(), tn = (size_t)total_nodes;
+        const size_t b_x = up256((size_t)x_words * 4), b_flags = up256(n_j * 4), b_stack = up256(tn * sizeof(treefit::StackRec)),
+                     b_nodes = up256(tn * sizeof(forest::Node)), b_val = up256((size_t)total_values * 8), b_cnt = up256(n_t * 4),
+                     b_i = up256(tn * 4), b_d = up256(tn * 8), b_u = up256(tn);
+        HIP_TRY(hipMalloc(&work.p, b_x + b_flags + b_stack + b_nodes + b_val + b_cnt + (arrays ? 4 * b_i + 3 * b_d + b_u : 0)));
+        char *p = (char *)work.p;
+        dev.X = d_X;
+        dev.jobs = (const treefit::TreeJob *)parts[0].dev;
+        dev.tasks = (const treefit::TreeTask *)parts[1].dev;
+        dev.mean = (const double *)parts[2].dev;
+        dev.scale = (const double *)parts[3].dev;
+        dev.idx = (const int *)parts[4].dev;
+        dev.label = (const int *)parts[5].dev;
+        dev.weight = (const int *)parts[6].dev;
+        dev.x32 = (float *)p;                   p += b_x;
+        dev.flags = (int *)p;                   p += b_flags;
+        dev.stack = (treefit::StackRec *)p;     p += b_stack;
+        dev.nodes = (forest::Node *)p;          p += b_nodes;
+        dev.value = (double *)p;                p += b_val;
+        dev.node_count = (int *)p;              p += b_cnt;
+        if (arrays) {
+            dev.children_left = (int *)p;       p += b_i;
+            dev.children_right = (int *)p;      p += b_i;
+            dev.feature = (int *)p;             p += b_i;
+            dev.n_node_samples = (int *)p;      p += b_i;
+            dev.threshold = (double *)p;        p += b_d;
+            dev.impurity = (double *)p;         p += b_d;
+            dev.weighted_n_node_samples = (double *)p;      p += b_d;
+            dev.missing_go_to_left = (unsigned char *)p;
+        }
+        dev.max_features = std::max(1, (int)std::sqrt((double)dev.n_dims));
+        LAUNCH_TRY("tree input", launch::tree_prep(dev, (int)n_j, n_max, cs()));
+        flags.assign(n_j, 0);
+        HIP_TRY(hipMemcpyAsync(flags.data(), dev.flags, n_j * 4, hipMemcpyDeviceToHost, cs()));
+        HIP_TRY(hipStreamSynchronize(cs()));
+        for (int f : flags) any_flag |= f != 0;
+        if (any_flag) return PAA_OK;              // a NaN or an infinity: nothing is fitted, the caller reports it
+        const int lrc = launch::tree_fit(dev, (int)n_t, splitter, inbag_max, k_max, cs());
+        if (lrc == -2) return fail(PAA_ERR_UNSUPPORTED, "the trees exceed the kernel's limits");
+        if (lrc) return fail(PAA_ERR_HIP, "tree fit launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return PAA_OK;
+    }
+};
+
+// The trees alone: see paa_hip.h
+extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
+                                      const int32_t *job_idx, const int32_t *job_label, const int32_t *job_k, const double *mean,
+                                      const double *std, int n_tasks, const int32_t *task_job, const int64_t *task_seed,
+                                      const int32_t *task_weight, int splitter, int64_t total_nodes, int64_t total_values,
+                                      int32_t *job_flags, int32_t *node_count, int32_t *children_left, int32_t *children_right,
+                                      int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                                      double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value) {
+    if (!X || !job_off || !job_idx || !job_label || !job_k || !mean || !std || !task_job || !task_seed || !task_weight || !job_flags ||
+        !node_count || !children_left || !children_right || !feature || !threshold || !impurity || !n_node_samples ||
+        !weighted_n_node_samples || !missing_go_to_left || !value)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = tree_params_check(n_dims, splitter))) return rc;
+    if (n_jobs < 1 || n_jobs > 65535) return fail(PAA_ERR_ARG, "%d jobs: 1 .. 65535", n_jobs);
+    if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
+    if ((rc = sweep_offsets_check(job_off, n_jobs, "job"))) return rc;
+    const int64_t rows = job_off[n_jobs];
+    TreeBatch b;
+    b.dev.n_dims = n_dims;
+    b.jobs.resize(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t n = job_off[j + 1] - job_off[j];
+        if ((rc = tree_job_check(j, n, job_k[j]))) return rc;
+        b.jobs[j] = {(long long)job_off[j], 0, (int)n, job_k[j], j, 0};
+        for (int64_t i = job_off[j]; i < job_off[j + 1]; ++i)
+            if (job_label[i] < 0 || job_label[i] >= job_k[j])
+                return fail(PAA_ERR_ARG, "job %d: class index %d of row %lld: 0 .. %d", j, job_label[i], (long long)(i - job_off[j]), job_k[j] - 1);
+    }
+    if ((rc = sweep_index_check(job_idx, rows, n_samples, "row"))) return rc;
+    b.tasks.resize(n_tasks);
+    int64_t w_off = 0;
+    for (int t = 0; t < n_tasks; ++t) {
+        if (task_job[t] < 0 || task_job[t] >= n_jobs) return fail(PAA_ERR_ARG, "task %d: job %d of %d", t, task_job[t], n_jobs);
+        if ((rc = tree_seed_check(t, task_seed[t]))) return rc;
+        const int n = b.jobs[task_job[t]].n;
+        int bag;
+        if ((rc = tree_weight_check(t, task_weight + w_off, n, &bag))) return rc;
+        b.tasks[t] = {(long long)w_off, 0, 0, task_job[t], 2 * bag - 1, 0, (unsigned)task_seed[t]};
+        w_off += n;
+    }
+    b.layout();
+    if (total_nodes != b.total_nodes || total_values != b.total_values)
+        return fail(PAA_ERR_ARG, "total_nodes = %lld, total_values = %lld: the tasks make %lld nodes and %lld values", (long long)total_nodes,
+                    (long long)total_values, (long long)b.total_nodes, (long long)b.total_values);
+    if (b.total_nodes > 0x7fffffffLL) return fail(PAA_ERR_UNSUPPORTED, "too many nodes");
+    if ((rc = ensure_init())) return rc;
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    if ((rc = b.run(st.feats, job_idx, job_label, rows, task_weight, w_off, mean, std, n_jobs, splitter, true))) return rc;
+    std::copy(b.flags.begin(), b.flags.end(), job_flags);
+    if (b.any_flag) return PAA_OK;
+    const size_t tn = (size_t)b.total_nodes;
+    const treefit::TreeDev &m = b.dev;
+    HIP_TRY(hipMemcpyAsync(node_count, m.node_count, (size_t)n_tasks * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(children_left, m.children_left, tn * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(children_right, m.children_right, tn * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(feature, m.feature, tn * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(n_node_samples, m.n_node_samples, tn * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(threshold, m.threshold, tn * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(impurity, m.impurity, tn * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(weighted_n_node_samples, m.weighted_n_node_samples, tn * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(missing_go_to_left, m.missing_go_to_left, tn, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(value, m.value, (size_t)b.total_values * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipStreamSynchronize(cs()));
+    return PAA_OK;
+}
+
+// The forest half of audioTrainTest.evaluate_classifier: every split a job of n_estimators trees; see paa_hip.h
+extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                         const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                         const int32_t *test_idx, const double *mean, const double *std, const int32_t *n_estimators,
+                                         int splitter, const int64_t *tree_seed, const int32_t *tree_weight, int32_t *label_out,
+                                         double *proba, int max_classes, int32_t *job_flags, int32_t *n_chunks) {
+    // check
+    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !n_estimators || !tree_seed || !label_out ||
+        !job_flags)
+        return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = tree_params_check(n_dims, splitter))) return rc;
+    if ((rc = sweep_jobs_check(n_jobs, train_off, test_off))) return rc;
+    const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
+    if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
+    for (int64_t i = 0; i < n_t; ++i)
+        if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
+    if ((rc = sweep_index_check(test_idx, n_q, n_samples, "test"))) return rc;
+    // per job the classes present in its training list, ascending, and every row's place among them
+    std::vector<int> row_label((size_t)n_t), job_class;
+    std::vector<size_t> job_class_off(n_jobs + 1, 0);
+    std::vector<int64_t> first_tree(n_jobs + 1, 0), first_weight(n_jobs + 1, 0);
+    std::vector<treefit::TreeJob> jobs(n_jobs);
+    int k_all = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t *tr = train_idx + train_off[j];
+        const int64_t n = train_off[j + 1] - train_off[j];
+        std::vector<int> classes;
+        for (int64_t i = 0; i < n; ++i) classes.push_back(labels[tr[i]]);
+        std::sort(classes.begin(), classes.end());
+        classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+        if ((rc = tree_job_check(j, n, (int)classes.size()))) return rc;
+        if (n_estimators[j] < 1 || n_estimators[j] > kForestMaxTrees)
+            return fail(PAA_ERR_ARG, "job %d: %d trees: 1..%d are supported", j, n_estimators[j], kForestMaxTrees);
+        for (int64_t i = 0; i < n; ++i)
+            row_label[train_off[j] + i] = (int)(std::lower_bound(classes.begin(), classes.end(), labels[tr[i]]) - classes.begin());
+        jobs[j] = {(long long)train_off[j], 0, (int)n, (int)classes.size(), j, 0};
+        k_all = std::max(k_all, (int)classes.size());
+        job_class.insert(job_class.end(), classes.begin(), classes.end());
+        job_class_off[j + 1] = job_class.size();
+        first_tree[j + 1] = first_tree[j] + n_estimators[j];
+        first_weight[j + 1] = first_weight[j] + (tree_weight ? (int64_t)n_estimators[j] * n : 0);
+    }
+    if (proba && max_classes < k_all) return fail(PAA_ERR_ARG, "max_classes = %d, a job has %d classes", max_classes, k_all);
+    std::vector<int> caps((size_t)first_tree[n_jobs]);
+    for (int j = 0; j < n_jobs; ++j)
+        for (int e = 0; e < n_estimators[j]; ++e) {
+            const int64_t t = first_tree[j] + e;
+            if ((rc = tree_seed_check((int)t, tree_seed[t]))) return rc;
+            int bag = jobs[j].n;
+            if (tree_weight && (rc = tree_weight_check((int)t, tree_weight + first_weight[j] + (int64_t)e * jobs[j].n, jobs[j].n, &bag))) return rc;
+            caps[t] = 2 * bag - 1;
+        }
+    if ((rc = ensure_init())) return rc;
+    std::fill(job_flags, job_flags + n_jobs, 0);
+    if (proba) std::fill(proba, proba + (size_t)n_q * max_classes, 0.0);      // zeros past a job's classes
+    Staged st;                                        // X goes up once, through the lane's scratch
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    // chunks of whole jobs within the scratch bound
+    int chunks = 0;
+    std::vector<int32_t> h_label;
+    std::vector<double> h_proba;
+    for (int j0 = 0; j0 < n_jobs;) {
+        int j1 = j0;
+        int64_t xw = 0, ww = 0, nodes = 0, values = 0;
+        while (j1 < n_jobs) {
+            int64_t jn = 0;
+            for (int64_t t = first_tree[j1]; t < first_tree[j1 + 1]; ++t) jn += caps[t];
+            const int64_t xw2 = xw + (int64_t)jobs[j1].n * n_dims, ww2 = ww + first_weight[j1 + 1] - first_weight[j1], nodes2 = nodes + jn,
+                          values2 = values + jn * jobs[j1].k;
+            if (j1 > j0 && (TreeBatch::bytes(xw2, ww2, nodes2, values2, false) > (size_t)treefit::kChunkBytes || nodes2 > 0x7fffffffLL)) break;
+            xw = xw2, ww = ww2, nodes = nodes2, values = values2;
+            ++j1;
+        }
+        if (nodes > 0x7fffffffLL) return fail(PAA_ERR_UNSUPPORTED, "job %d: too many nodes", j0);
+        ++chunks;
+        TreeBatch b;
+        b.dev.n_dims = n_dims;
+        std::vector<int> roots;
+        std::vector<int64_t> job_node(j1 - j0 + 1, 0), job_val(j1 - j0 + 1, 0);
+        for (int j = j0; j < j1; ++j) {
+            treefit::TreeJob job = jobs[j];
+            job.off -= train_off[j0];
+            job.stat = j - j0;
+            b.jobs.push_back(job);
+            int64_t jn = 0;
+            for (int e = 0; e < n_estimators[j]; ++e) {
+                const int64_t t = first_tree[j] + e;
+                const long long w_off = tree_weight ? (long long)(first_weight[j] - first_weight[j0] + (int64_t)e * job.n) : -1;
+                b.tasks.push_back({w_off, 0, 0, j - j0, caps[t], (int)jn, (unsigned)tree_seed[t]});
+                roots.push_back((int)jn);
+                jn += caps[t];
+            }
+            job_node[j - j0 + 1] = job_node[j - j0] + jn;
+            job_val[j - j0 + 1] = job_val[j - j0] + jn * job.k;
+        }
+        b.layout();
+        if ((rc = b.run(st.feats, train_idx + train_off[j0], row_label.data() + train_off[j0], train_off[j1] - train_off[j0],
+                        tree_weight ? tree_weight + first_weight[j0] : nullptr, first_weight[j1] - first_weight[j0],
+                        mean + (size_t)j0 * n_dims, std + (size_t)j0 * n_dims, j1 - j0, splitter, false)))
+            return rc;
+        for (int j = j0; j < j1; ++j) job_flags[j] = b.flags[j - j0];
+        if (b.any_flag) break;                            // a NaN or an infinity in a training row: the caller reports it
+        // score every job's test rows with its trees: the traversal and reduction kernels of the predict path
+        int64_t q_max = 0, leaf_max = 0, q_chunk = test_off[j1] - test_off[j0];
+        for (int j = j0; j < j1; ++j) {
+            const int64_t q = test_off[j + 1] - test_off[j];
+            q_max = std::max(q_max, q);
+            leaf_max = std::max(leaf_max, (int64_t)n_estimators[j] * std::min<int64_t>(q, forest::kChunk));
+        }
+        if (q_chunk) {
+            DevBlock score;
+            const size_t b_roots = up256(roots.size() * 4), b_test = up256((size_t)q_chunk * 4), b_feats = up256((size_t)q_max * n_dims * 8),
+                         b_leaves = up256((size_t)leaf_max * 4), b_raw = up256((size_t)q_max * k_all * 8), b_label = up256((size_t)q_chunk * 4),
+                         b_proba = up256((size_t)q_chunk * k_all * 8);
+            HIP_TRY(hipMalloc(&score.p, b_roots + b_test + b_feats + b_leaves + b_raw + b_label + b_proba));
+            char *p = (char *)score.p;
+            int *d_roots = (int *)p;            p += b_roots;
+            int *d_test = (int *)p;             p += b_test;
+            double *d_feats = (double *)p;      p += b_feats;
+            int *d_leaves = (int *)p;           p += b_leaves;
+            double *d_raw = (double *)p;        p += b_raw;
+            int *d_label = (int *)p;            p += b_label;
+            double *d_proba = (double *)p;
+            HIP_TRY(hipMemcpyAsync(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, cs()));
+            HIP_TRY(hipMemcpyAsync(d_test, test_idx + test_off[j0], (size_t)q_chunk * 4, hipMemcpyHostToDevice, cs()));
+            int64_t p_off = 0;
+            std::vector<int64_t> job_p(j1 - j0 + 1, 0);
+            for (int j = j0; j < j1; ++j) {
+                const int64_t q = test_off[j + 1] - test_off[j], q0 = test_off[j] - test_off[j0];
+                job_p[j - j0] = p_off;
+                if (q) {
+                    const treefit::TreeJob &job = b.jobs[j - j0];
+                    LAUNCH_TRY("test row gather", launch::tree_gather(st.feats, n_dims, d_test + q0, q, d_feats, q, cs()));
+                    forest::ForestDev f{};
+                    f.nodes = b.dev.nodes + job_node[j - j0];
+                    f.roots = d_roots + (first_tree[j] - first_tree[j0]);
+                    f.leaf_values = b.dev.value + job_val[j - j0];
+                    f.init = nullptr;
+                    f.n_trees = n_estimators[j];
+                    f.n_dims = n_dims;
+                    f.n_classes = f.n_outputs = job.k;
+                    f.boosted = 0;
+                    f.learning_rate = 0.0;
+                    LAUNCH_TRY("tree-ensemble", launch::forest(f, d_feats, (long long)q, (long long)q, b.dev.mean + (size_t)(j - j0) * n_dims,
+                                                               b.dev.scale + (size_t)(j - j0) * n_dims, d_leaves, d_label + q0, d_raw,
+                                                               d_proba + p_off, cs()));
+                    p_off += q * job.k;
+                }
+            }
+            job_p[j1 - j0] = p_off;
+            h_label.resize((size_t)q_chunk);
+            h_proba.resize((size_t)p_off);
+            HIP_TRY(hipMemcpyAsync(h_label.data(), d_label, (size_t)q_chunk * 4, hipMemcpyDeviceToHost, cs()));
+            if (proba && p_off) HIP_TRY(hipMemcpyAsync(h_proba.data(), d_proba, (size_t)p_off * 8, hipMemcpyDeviceToHost, cs()));
+            HIP_TRY(hipStreamSynchronize(cs()));
+            // a label is the position among the job's classes (-1: a test value is infinite in float32): back to class indices
+            for (int j = j0; j < j1; ++j) {
+                const int k = b.jobs[j - j0].k;
+                for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) {
+                    const int l = h_label[(size_t)(q - test_off[j0])];
+                    label_out[q] = l < 0 ? l : job_class[job_class_off[j] + l];
+                    if (proba) {
+                        const double *row = h_proba.data() + job_p[j - j0] + (q - test_off[j]) * k;
+                        for (int c = 0; c < k; ++c) proba[(size_t)q * max_classes + c] = row[c];
+                    }
+                }
+            }
+        } else {
+            HIP_TRY(hipStreamSynchronize(cs()));
+        }
+        j0 = j1;
+    }
+    if (n_chunks) *n_chunks = chunks;
+    return PAA_OK;
+}

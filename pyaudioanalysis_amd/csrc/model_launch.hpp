@@ -173,6 +173,56 @@ struct ForestDev {
     double learning_rate;
 };
 }  // namespace forest
+namespace treefit {
+constexpr int kThreads = 256;             // kernels_treefit.hpp: one workgroup per tree
+constexpr int kMaxRows = 8192;            // rows of a job's training list: a row's place, class and weight share one 32-bit word
+constexpr int kMaxClasses = forest::kMaxClasses;
+constexpr int kMaxDims = forest::kMaxDims;
+constexpr int kMaxWeight = 8191;          // a row's integer weight (0: out of the bag)
+constexpr long long kChunkBytes = 1LL << 30;      // device scratch of one chunk of a sweep's trees (a job is never cut)
+enum Splitter { kBest = 0, kRandom = 1 };
+// a job: the rows idx[off .. off + n - 1] of the sample matrix, their class indices label[off ..] in 0 .. k - 1, standardised
+// with row `stat` of mean / scale; its float32 copy x32[x_off ..] is feature-major [n_dims][n]
+struct TreeJob {
+    long long off, x_off;
+    int n, k, stat, pad;
+};
+// a tree: its job, the rand_r seed, the weights weight[w_off .. w_off + n - 1] of the job's rows (w_off < 0: every row 1) and
+// its place in the outputs: nodes at node_off (room for cap = 2 in-bag rows - 1), values at val_off; the packed nodes count
+// from node_rel (the tree's first node among the nodes of its job's trees)
+struct TreeTask {
+    long long w_off, node_off, val_off;
+    int job, cap, node_rel;
+    unsigned seed;
+};
+// a pending right child of the depth-first build
+struct StackRec {
+    int start, end, parent, n_known;
+    double impurity;
+};
+// a batch of trees: device pointers.  The scikit-learn arrays (children_left .. missing) may be null: the sweep keeps the packed
+// nodes and the values only
+struct TreeDev {
+    const double *X;          // [n_samples][n_dims]
+    const int *idx, *label;   // per job row
+    const TreeJob *jobs;
+    const TreeTask *tasks;
+    const int *weight;
+    const double *mean, *scale;   // [..][n_dims]
+    float *x32;               // prep: every job's standardised float32 rows
+    int *flags;               // prep, per job: 1: a value is infinite in float32, 2: a value is NaN
+    StackRec *stack;          // [total cap]
+    forest::Node *nodes;      // out [total cap]: forest_traverse_kernel's layout
+    double *value;            // out: per node the class fractions, [cap][k of the job] per tree
+    int *node_count;          // out per task
+    int *children_left, *children_right, *feature, *n_node_samples;
+    double *threshold, *impurity, *weighted_n_node_samples;
+    unsigned char *missing_go_to_left;
+    int n_dims, max_features;
+    int lds_keys, lds_rows, hist_cols, lds_feat;      // LDS geometry of the launch: 8-byte sort words, row words, columns of the class
+                                                      // histogram, byte offset of the feature arrays
+};
+}  // namespace treefit
 namespace hmm {
 constexpr int kMaxStates = 32;
 constexpr int kMaxDims = 256;
@@ -256,6 +306,15 @@ int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_m
 // probabilities proba [n_vec][n_classes])
 int forest(const forest::ForestDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean,
            const double *d_scale, int *d_leaves, int *d_label, double *d_raw, double *d_proba, hipStream_t stream);
+// kernels_treefit.hpp: the float32 copies of n_jobs jobs (n_max: the longest of them) and their flags (zeroed here)
+int tree_prep(const treefit::TreeDev &m, int n_jobs, int n_max, hipStream_t stream);
+// ... one workgroup per task builds its tree (splitter: treefit::Splitter; inbag_max: the most in-bag rows of a task, k_max the
+// most classes of a job; they size the LDS and are written into m); -2 when a limit is exceeded
+int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int k_max, hipStream_t stream);
+// ... out [n_dims][ld] = the rows d_rows [n_rows] of X [..][n_dims], feature-major as the traversal kernel reads them
+int tree_gather(const double *d_X, int n_dims, const int *d_rows, long long n_rows, double *d_out, long long ld, hipStream_t stream);
+// ... threads per workgroup, the row limit, the class limit, the dims limit, the weight limit, the chunk size in MiB
+void tree_fit_geometry(int out6[6]);
 // kernels_hmm.hpp: frame log-likelihoods loglik [n_vec][n_states] of the columns of feats [n_dims][ld] (one kernel)
 int hmm_emission(const hmm::HmmDev &m, const double *d_feats, long long ld, long long n_vec, double *d_loglik, hipStream_t stream);
 // ... and Viterbi over n_seq sequences cut into n_seg segments (segment s of sequence q: seq_seg[q] <= s < seq_seg[q + 1]):
