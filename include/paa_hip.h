@@ -564,7 +564,7 @@ int paa_forest_dev_predict_f64(const void *handle, const double *d_feats, int n_
  * begin at 0 or decrease, an index outside 0..n_samples-1, a class index outside its range, an empty job, a weight outside 0..8191, a
  * tree without a positive weight, a seed outside 0..2^32-1, n_estimators < 1, totals that differ from what the tasks make.
  * PAA_ERR_UNSUPPORTED, likewise: n_dims > 256, a job of more than 8192 rows or 64 classes.  Synchronous, host buffers in and out.
- * Not served: other criteria, depth or leaf-size limits, class weights, missing values, gradient boosting, regressors.       */
+ * Not served: other criteria, depth or leaf-size limits, class weights, missing values, gradient boosting (regressors: below). */
 #define PAA_TREE_MAX_ROWS 8192
 #define PAA_TREE_MAX_WEIGHT 8191
 #define PAA_TREE_BEST 0
@@ -582,6 +582,40 @@ int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, co
                               int32_t *job_flags, int32_t *n_chunks);
 /* tests: out6 = threads per workgroup, rows per job, classes, dims, the largest weight, MiB of scratch per chunk */
 int paa_debug_tree_fit_geometry(int32_t *out6);
+
+/* ---- fitting the forest regressor: audioTrainTest.train_random_forest_regression (audioTrainTest.py:229-233) and the "randomforest"
+ * sweep of evaluate_regression (:774-855) ---------------------------------------------------------------------------------------------
+ * A regression TREE is scikit-learn 1.7.2's DecisionTreeRegressor as RandomForestRegressor(n_estimators) fits it: the same builder
+ * and BestSplitter as above with the squared-error criterion (RegressionCriterion / MSE), max_features = n_dims, one output.  The
+ * floating-point sums of a node (sum w y, sum (w y) y, the prefix sums of the candidate scan) are formed in a FIXED order that
+ * depends only on the node's rows and the sorted order (kernels_treefit.hpp writes it down; no float atomics), so a tree is
+ * bit-identical run to run, alone or anywhere in a batch.  When targets and weights make every such sum exact in FP64 (e.g. targets
+ * that are multiples of 1/8 with |y| <= 1024 and a total weight <= 8192) every array equals scikit-learn's bit for bit; otherwise
+ * scikit-learn's own summation order (its introsort and in-place partition) is NOT reproduced: the sums may differ in the last
+ * places and a tie that rounding breaks may fall the other way -- a valid CART tree, not scikit-learn's bits.
+ *
+ * paa_tree_fit_reg_tasks_f64 -- the trees alone: the arguments of paa_tree_fit_tasks_f64 with job_target [job_off[n_jobs]] (finite
+ * doubles, one per job row) in place of job_label / job_k and without `splitter`; value [total_nodes] holds the node's weighted mean
+ * target, so total_values == total_nodes.
+ *
+ * paa_forest_reg_fit_splits_f64 -- the sweep: the arguments of paa_forest_fit_splits_f64 with targets [n_samples] in place of labels
+ * and without `splitter`; tree_weight NULL: every row 1 (no bootstrap).  Same chunking; the trees of a chunk are scored by the
+ * kernels of paa_forest_predict_f64 as the averaged forest with one output.
+ *   pred [Q]                 the prediction of every test row (sum over the trees in tree order / n_estimators)
+ *   train_pred [T]           (may be NULL) the prediction of every job's own training rows, T = train_off[n_jobs]
+ *   job_flags [n_jobs]       as above; 1 is also set when a TEST value of the job is infinite in float32; when any is set pred /
+ *                            train_pred are not valid
+ * Errors as above; PAA_ERR_ARG also for a target (of a job row / a training row) that is not finite.                             */
+int paa_tree_fit_reg_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off, const int32_t *job_idx,
+                               const double *job_target, const double *mean, const double *std, int n_tasks, const int32_t *task_job,
+                               const int64_t *task_seed, const int32_t *task_weight, int64_t total_nodes, int64_t total_values,
+                               int32_t *job_flags, int32_t *node_count, int32_t *children_left, int32_t *children_right,
+                               int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                               double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value);
+int paa_forest_reg_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *targets, int n_jobs,
+                                  const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                                  const double *mean, const double *std, const int32_t *n_estimators, const int64_t *tree_seed,
+                                  const int32_t *tree_weight, double *pred, double *train_pred, int32_t *job_flags, int32_t *n_chunks);
 
 /* ---- audioSegmentation.hmm_segmentation / train_hmm_compute_statistics (audioSegmentation.py:287-492) -------------------
  * Gaussian hidden Markov models with one diagonal Gaussian per state, as the reference trains them and hmmlearn's

@@ -148,6 +148,11 @@ _SIGNATURES = {
     "paa_forest_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
                                             c_i32p, C.c_int, c_i64p, c_i32p, c_i32p, c_f64p, C.c_int, c_i32p, c_i32p]),
     "paa_debug_tree_fit_geometry": (C.c_int, [c_i32p]),
+    "paa_tree_fit_reg_tasks_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int, c_i32p,
+                                             c_i64p, c_i32p, C.c_int64, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_f64p,
+                                             c_i32p, c_f64p, C.POINTER(C.c_uint8), c_f64p]),
+    "paa_forest_reg_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
+                                                c_i32p, c_i64p, c_i32p, c_f64p, c_f64p, c_i32p, c_i32p]),
     "paa_hmm_create": (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "paa_hmm_destroy": (C.c_int, [C.c_void_p]),
     "paa_hmm_num_states": (C.c_int, [C.c_void_p]),

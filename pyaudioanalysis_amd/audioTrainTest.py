@@ -64,6 +64,11 @@ by default.  With svm_fit="device" evaluate_regression fits "svm" / "svm_rbf" on
 value is one epsilon-SVR problem of svr_smo_kernel (libsvm's solver without shrinking, FP64; a dual of 2 n variables over n
 rows whose kernel rows are formed once per row), all of them side by side, scored in the same call
 (paa_svr_fit_splits_f64); the final fit of feature_extraction_train_regression and its model file stay scikit-learn's.
+With forest_fit="device" evaluate_regression fits "randomforest" on the GPU: one workgroup per tree builds scikit-learn's
+squared-error regression tree (the MSE instance of tree_fit_kernel through paa_tree_fit_reg_tasks_f64 /
+paa_forest_reg_fit_splits_f64), every floating-point sum in a fixed order -- scikit-learn's bits when the targets make the sums
+exact, a valid CART tree otherwise (tree_fit_regression); train_random_forest_regression_device is the final fit and
+to_sklearn_forest_regressor makes the model file's RandomForestRegressor.
 """
 import collections
 import ctypes as C
@@ -1466,6 +1471,15 @@ def _check_tree_rows(n, what):
         raise NotImplementedError("%s has %d training rows: the GPU tree builder serves at most %d rows per tree" % (what, n, TREE_MAX_ROWS))
 
 
+def _check_targets(y):
+    """scikit-learn's validation of regression targets: NaN before infinity."""
+    y = np.asarray(y, dtype=np.float64)
+    if np.isnan(y).any():
+        raise ValueError("Input y contains NaN.")
+    if np.isinf(y).any():
+        raise ValueError("Input y contains infinity or a value too large for dtype('float64').")
+
+
 def _splitter_of(kind):
     if kind in _TREE_SPLITTERS:
         return kind
@@ -1517,7 +1531,24 @@ def tree_fit(X, tasks, splitter):
     splitter's rand_r seed.  splitter: 'best' (DecisionTreeClassifier, 'randomforest') or 'random' (ExtraTreeClassifier,
     'extratrees').  Tasks that pass the SAME rows, y, mean and scale objects share one float32 copy on the device.  More than
     8192 rows in a task raise NotImplementedError, NaN / infinity scikit-learn's ValueError.  Returns a TreeFitResult."""
-    splitter = _splitter_of(splitter)
+    return _tree_fit(X, tasks, _splitter_of(splitter))
+
+
+def tree_fit_regression(X, tasks):
+    """Regression trees over ONE sample matrix, all built side by side (paa_tree_fit_reg_tasks_f64, the squared-error instance of
+    tree_fit_kernel: scikit-learn 1.7.2's DecisionTreeRegressor as a RandomForestRegressor fits it -- best splitter, every feature,
+    no depth limit).  X and the tasks (rows, y, weights, seed, mean, scale) are tree_fit's, y being float targets.  The kernel forms
+    every floating-point sum in a fixed order, so a tree is bit-identical run to run, alone or in any batch; when targets and weights
+    make the sums exact in FP64 (e.g. multiples of 1/8 within +-1024 and a total weight <= 8192) every array equals scikit-learn's bit
+    for bit, otherwise it is a valid CART tree whose sums may differ from scikit-learn's in the last places.
+    NaN / infinity in y raise scikit-learn's ValueError and more than 8192 rows NotImplementedError, before the library is asked.
+    Returns a TreeFitResult with value [nodes][1] and classes None."""
+    return _tree_fit(X, tasks, None)
+
+
+def _tree_fit(X, tasks, splitter):
+    """tree_fit (splitter 'best' / 'random') and tree_fit_regression (splitter None)."""
+    regression = splitter is None
     X = np.ascontiguousarray(X, dtype=np.float64)
     tasks = list(tasks)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
@@ -1538,11 +1569,15 @@ def tree_fit(X, tasks, splitter):
                 raise ValueError("task %d: %d rows and %d labels" % (t, r.shape[0], y.shape[0]))
             _check_tree_rows(r.shape[0], "task %d" % t)
             mean, scale = _stats(task[4], task[5], n_dims)
-            classes, idx = np.unique(y, return_inverse=True) if y.shape[0] else (y, y)
+            if regression:
+                _check_targets(y)
+                classes, idx = None, np.asarray(y, dtype=np.float64)
+            else:
+                classes, idx = np.unique(y, return_inverse=True) if y.shape[0] else (y, y)
             job_of[key] = len(rows_l)
             rows_l.append(r)
-            label_l.append(idx.astype(np.int32).reshape(-1))
-            k_l.append(int(classes.shape[0]))
+            label_l.append(idx.astype(np.float64 if regression else np.int32).reshape(-1))
+            k_l.append(1 if regression else int(classes.shape[0]))
             classes_l.append(classes)
             means.append(mean)
             scales.append(scale)
@@ -1555,7 +1590,7 @@ def tree_fit(X, tasks, splitter):
         seeds.append(int(task[3]))
         weights.append(np.clip(w.astype(np.int64), -1, TREE_MAX_WEIGHT + 1).astype(np.int32))
     idx, off = _packed(rows_l, np.int32)
-    label = np.ascontiguousarray(np.concatenate(label_l), dtype=np.int32)
+    label = np.ascontiguousarray(np.concatenate(label_l), dtype=np.float64 if regression else np.int32)
     k = np.array(k_l, dtype=np.int32)
     mean, scale = np.stack(means), np.stack(scales)
     task_job = np.array(task_job, dtype=np.int32)
@@ -1571,13 +1606,16 @@ def tree_fit(X, tasks, splitter):
            "n_node_samples": i32(), "weighted_n_node_samples": f64(), "missing_go_to_left": np.zeros(max(total_nodes, 1), dtype=np.uint8)}
     value = np.zeros(max(total_values, 1), dtype=np.float64)
     flags, count = np.zeros(len(rows_l), dtype=np.int32), np.zeros(n_tasks, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_tree_fit_tasks_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, len(rows_l), _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_i32p(label), _ffi.as_i32p(k),
-        _ffi.as_f64p(mean), _ffi.as_f64p(scale), n_tasks, _ffi.as_i32p(task_job), _ffi.as_i64p(seed), _ffi.as_i32p(weight),
-        _TREE_SPLITTERS[splitter], total_nodes, total_values, _ffi.as_i32p(flags), _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
-        _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
-        _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
-        out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(value)))
+    head = (_ffi.as_f64p(X), n_samples, n_dims, len(rows_l), _ffi.as_i64p(off), _ffi.as_i32p(idx))
+    middle = (_ffi.as_f64p(mean), _ffi.as_f64p(scale), n_tasks, _ffi.as_i32p(task_job), _ffi.as_i64p(seed), _ffi.as_i32p(weight))
+    tail = (total_nodes, total_values, _ffi.as_i32p(flags), _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
+            _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
+            _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
+            out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(value))
+    if regression:
+        _ffi.check(_ffi.lib().paa_tree_fit_reg_tasks_f64(*head, _ffi.as_f64p(label), *middle, *tail))
+    else:
+        _ffi.check(_ffi.lib().paa_tree_fit_tasks_f64(*head, _ffi.as_i32p(label), _ffi.as_i32p(k), *middle, _TREE_SPLITTERS[splitter], *tail))
     _raise_tree_flags(flags)
     trees = []
     for t in range(n_tasks):
@@ -1585,7 +1623,7 @@ def tree_fit(X, tasks, splitter):
         tree = {name: arr[a:a + n_nodes].astype(np.int64) if arr.dtype == np.int32 else arr[a:a + n_nodes].copy() for name, arr in out.items()}
         tree["value"] = value[int(val_off[t]):int(val_off[t]) + n_nodes * kt].reshape(n_nodes, kt).copy()
         trees.append(tree)
-    return TreeFitResult(trees, [classes_l[j] for j in task_job])
+    return TreeFitResult(trees, None if regression else [classes_l[j] for j in task_job])
 
 
 class ForestSplitResult(_SplitResult):
@@ -1676,6 +1714,17 @@ def train_forest_device(features, labels, n_estimators, kind="randomforest", *, 
     return arrays
 
 
+def _tree_depth(left, right):
+    """The depth of a tree given by its children arrays, level by level."""
+    depth, level = 0, np.zeros(1, dtype=np.int64)
+    while True:
+        below = np.concatenate([left[level], right[level]])
+        level = below[below >= 0]
+        if not level.size:
+            return depth
+        depth += 1
+
+
 def to_sklearn_forest(arrays, kind):
     """A real fitted sklearn.ensemble.RandomForestClassifier ('randomforest') / ExtraTreesClassifier ('extratrees') with the trees of
     a ForestArrays of kind "averaged" (every Tree is built through __setstate__): it predicts as scikit-learn predicts from those
@@ -1708,20 +1757,136 @@ def to_sklearn_forest(arrays, kind):
         for name in extra:
             if extra[name] is not None:
                 nodes[name] = extra[name][lo:hi]
-        depth, level = 0, np.zeros(1, dtype=np.int64)          # the tree's depth, level by level
-        while True:
-            below = np.concatenate([nodes["left_child"][level], nodes["right_child"][level]])
-            level = below[below >= 0]
-            if not level.size:
-                break
-            depth += 1
         tree = Tree(a.n_dims, np.array([k], dtype=np.intp), 1)
-        tree.__setstate__({"max_depth": depth, "node_count": hi - lo, "nodes": nodes,
+        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
                            "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, k))})
         est = forest._make_estimator(append=False)
         est.tree_ = tree
         est.classes_, est.n_classes_ = forest.classes_, k
         est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, max(1, int(np.sqrt(a.n_dims)))
+        forest.estimators_.append(est)
+    return forest
+
+
+class ForestRegressionSplitResult(_SplitResult):
+    """What forest_regression_split_fit_predict returns: pred [Q] (the test predictions), train_pred [T] or None (the predictions of
+    every job's own training rows, job j owns train_off[j] .. train_off[j + 1] - 1), test_off / train_off [n_jobs + 1],
+    n_estimators [n_jobs] and the number of chunks the trees were fitted in."""
+
+    def __init__(self, pred, train_pred, test_off, train_off, n_estimators, n_chunks):
+        self.pred, self.train_pred, self.test_off, self.train_off = pred, train_pred, test_off, train_off
+        self.n_estimators, self.n_chunks = n_estimators, n_chunks
+
+    def job(self, j):
+        """(test predictions, training predictions or None) of job j."""
+        t0, t1 = int(self.train_off[j]), int(self.train_off[j + 1])
+        return self.pred[self._rows(j)], None if self.train_pred is None else self.train_pred[t0:t1]
+
+
+def forest_regression_split_fit_predict(X, y, jobs, train_pred=False):
+    """RandomForestRegressor(n_estimators, random_state=seed).fit(train).predict(test) for every job of a sweep over ONE sample
+    matrix (paa_forest_reg_fit_splits_f64: one workgroup per tree, chunks of bounded device scratch, every test row -- with
+    train_pred=True every job's training rows too -- scored on the device as the averaged forest with one output; no tree crosses to
+    the host).  X [n_samples][n_dims]; y [n_samples] float targets; a job is (train_idx, test_idx, mean, scale, (n_estimators,
+    seed)).  The host draws exactly what it draws for the classifier: per job forest_tree_seeds(seed, n_estimators), per tree
+    tree_inputs(..., bootstrap=True).  Predictions equal scikit-learn's bit for bit when the targets make the trees' sums exact (see
+    tree_fit_regression); otherwise they are those of valid CART trees.  NaN / infinity in y raise scikit-learn's ValueError and a
+    training list above 8192 rows NotImplementedError, before the library is asked.  Returns a ForestRegressionSplitResult."""
+    p = _pack_jobs(X, y, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
+    n_samples, n_dims = p.X.shape
+    targets = _targets(p.raw, n_samples)
+    _check_targets(targets)
+    n_jobs = len(p.last)
+    counts = np.diff(p.train_off)
+    for j in range(n_jobs):
+        _check_tree_rows(int(counts[j]), "job %d" % j)
+    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
+    seeds, weights = [], []
+    for j in range(n_jobs):
+        for s in forest_tree_seeds(p.last[j][1], n_est[j]):
+            rand_r, w = tree_inputs(s, int(counts[j]), counts[j] > 0)
+            seeds.append(rand_r)
+            if w is not None:
+                weights.append(w)
+    seed = np.array(seeds, dtype=np.int64)
+    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32) if weights else None
+    Q, T = int(p.test_off[-1]), int(p.train_off[-1])
+    pred = np.zeros(Q)
+    tp = np.zeros(T) if train_pred else None
+    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_forest_reg_fit_splits_f64(
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_f64p(targets), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
+        _ffi.as_i64p(seed), _ffi.as_i32p(weight) if weight is not None else None, _ffi.as_f64p(pred),
+        _ffi.as_f64p(tp) if train_pred else None, _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
+    _raise_tree_flags(flags)
+    return ForestRegressionSplitResult(pred, tp, p.test_off, p.train_off, n_est, int(chunks[0]))
+
+
+def train_random_forest_regression_device(features, labels, n_estimators, *, random_state=None):
+    """train_random_forest_regression on the GPU: RandomForestRegressor(n_estimators, random_state=random_state).fit(features,
+    labels) by tree_fit_regression -- per tree the seed scikit-learn's forest draws (forest_tree_seeds; None: from NumPy's global
+    state exactly as scikit-learn does), the splitter's rand_r seed and the bootstrap counts (tree_inputs).  Returns (a ForestArrays
+    of kind "regressor", which forest_model, regress and regression_wrapper take and which carries impurity, n_node_samples and
+    weighted_n_node_samples for to_sklearn_forest_regressor; the mean absolute training error, from the device prediction).  The
+    arrays equal those of scikit-learn's estimators_ bit for bit when the targets make the trees' sums exact (tree_fit_regression).
+    More than 8192 rows raise NotImplementedError before the device is touched; there is no CPU fallback."""
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    y = np.asarray(labels, dtype=np.float64).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or y.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d targets" % (X.shape, y.shape[0]))
+    if int(n_estimators) < 1:
+        raise ValueError("n_estimators = %r" % (n_estimators,))
+    _check_targets(y)
+    n, n_dims = X.shape
+    _check_tree_rows(n, "the training set")
+    rows, mean, scale = np.arange(n), np.zeros(n_dims), np.ones(n_dims)
+    tasks = []
+    for s in forest_tree_seeds(random_state, n_estimators):
+        rand_r, w = tree_inputs(s, n, True)
+        tasks.append((rows, y, w, rand_r, mean, scale))
+    res = tree_fit_regression(X, tasks)
+    cat = lambda name: np.concatenate([t[name] for t in res.trees])        # noqa: E731
+    arrays = ForestArrays("regressor", _offsets([t["feature"].shape[0] for t in res.trees]), cat("children_left"), cat("children_right"),
+                          cat("feature"), cat("threshold"), cat("missing_go_to_left"), cat("value")[:, 0], None, n_dims)
+    arrays.impurity, arrays.n_node_samples, arrays.weighted_n_node_samples = cat("impurity"), cat("n_node_samples"), cat("weighted_n_node_samples")
+    pred = regress([arrays], "randomforest", X.T, mean, scale)[0]
+    return arrays, np.mean(np.abs(pred - y))
+
+
+def to_sklearn_forest_regressor(arrays):
+    """A real fitted sklearn.ensemble.RandomForestRegressor with the trees of a ForestArrays of kind "regressor" (every Tree is built
+    through __setstate__): it predicts as scikit-learn predicts from those arrays and pickles as the reference's regression model
+    files do.  impurity, n_node_samples and weighted_n_node_samples are those of train_random_forest_regression_device when the
+    arrays carry them, zeros otherwise (prediction reads none of them).  Needs scikit-learn."""
+    import sklearn.ensemble
+    from sklearn.tree._tree import NODE_DTYPE, Tree
+    a = forest_arrays(arrays)
+    if a.kind != "regressor":
+        raise ValueError("a tree ensemble of kind %r: 'regressor' expected" % (a.kind,))
+    n_trees = a.node_offsets.shape[0] - 1
+    forest = sklearn.ensemble.RandomForestRegressor(n_estimators=n_trees)
+    forest._validate_estimator()
+    forest.n_features_in_ = a.n_dims
+    forest.n_outputs_ = 1
+    value = a.value.reshape(-1)
+    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
+    forest.estimators_ = []
+    for t in range(n_trees):
+        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
+        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
+        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
+        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
+        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
+        for name in extra:
+            if extra[name] is not None:
+                nodes[name] = extra[name][lo:hi]
+        tree = Tree(a.n_dims, np.array([1], dtype=np.intp), 1)
+        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
+                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, 1))})
+        est = forest._make_estimator(append=False)
+        est.tree_ = tree
+        est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, a.n_dims
         forest.estimators_.append(est)
     return forest
 
@@ -2012,7 +2177,14 @@ def _check_svr_fit(svm_fit, method_name):
         raise ValueError("svm_fit='device' serves the regression methods %s, not %r" % (" and ".join(_SVM_TYPES), method_name))
 
 
-def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit="sklearn"):
+def _check_forest_regression_fit(forest_fit, method_name):
+    if forest_fit not in ("sklearn", "device"):
+        raise ValueError("forest_fit=%r: 'sklearn' or 'device'" % (forest_fit,))
+    if forest_fit == "device" and method_name != "randomforest":
+        raise ValueError("forest_fit='device' serves the regression method 'randomforest', not %r" % (method_name,))
+
+
+def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit="sklearn", forest_fit="sklearn"):
     """Picks the parameter value with the lowest cross-validated squared error (reference :774-855): for every value,
     n_exp random 90 / 10 splits of the standardised samples.  np.random.permutation is consumed and the models are
     fitted in the reference's order (RandomForestRegressor draws from the same global state), by scikit-learn; the
@@ -2025,10 +2197,17 @@ def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit
     same splits under one seed), and ONE sweep (svr_split_fit_predict: epsilon-SVR with scikit-learn's defaults epsilon 0.1,
     gamma 'scale', tol 1e-3) fits and scores every split; the training errors come from the solver's gradient.  The errors,
     the baseline, the table and the return value are formed as above.  svm_fit="sklearn" (the default) is the behaviour
-    described above, untouched."""
+    described above, untouched.
+    forest_fit="device" (keyword only; "randomforest", any other method raises ValueError): ALL len(params) x n_exp permutations
+    are drawn up front, in the reference's order, THEN one forest seed per split with np.random.randint(np.iinfo(np.int32).max), in
+    job order (the default mode interleaves every permutation with its forest's own draws, so the two modes see different splits
+    under one seed), and ONE sweep (forest_regression_split_fit_predict: RandomForestRegressor(n_estimators=param,
+    random_state=seed) per split, on the GPU) fits every forest and scores its test and training rows.  More than 8192 training
+    rows raise NotImplementedError.  The errors, the baseline, the table and the return value are formed as above."""
     if method_name not in _REGRESSION_TYPES:
         raise NotImplementedError("regression method %r: 'svm', 'svm_rbf' or 'randomforest'" % (method_name,))
     _check_svr_fit(svm_fit, method_name)
+    _check_forest_regression_fit(forest_fit, method_name)
     from sklearn.preprocessing import StandardScaler
     features_norm = StandardScaler().fit_transform(features)
     labels = np.asarray(labels)
@@ -2042,8 +2221,16 @@ def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit
         sweep = svr_split_fit_predict(features_norm, labels, [(perm[:n_train], perm[n_train:], zeros, ones, float(param))
                                                               for param, perms in zip(params, all_perms) for perm in perms],
                                       kernel="rbf" if method_name == "svm_rbf" else "linear", train_pred=True)
+    if forest_fit == "device":                         # likewise: every permutation, then every forest's seed, then one sweep
+        _check_targets(labels)
+        _check_tree_rows(n_train, "a training split")
+        all_perms = [[np.random.permutation(range(n_samples)) for _ in range(n_exp)] for _ in params]
+        seeds = [[int(np.random.randint(np.iinfo(np.int32).max)) for _ in range(n_exp)] for _ in params]
+        sweep = forest_regression_split_fit_predict(
+            features_norm, labels, [(perm[:n_train], perm[n_train:], zeros, ones, (int(param), seed))
+                                    for param, perms, srow in zip(params, all_perms, seeds) for perm, seed in zip(perms, srow)], train_pred=True)
     for p, param in enumerate(params):
-        if svm_fit == "device":
+        if svm_fit == "device" or forest_fit == "device":
             perms = all_perms[p]
             picked = [sweep.job(p * n_exp + e)[:2] for e in range(n_exp)]          # (test, training) predictions per experiment
         else:
@@ -2080,13 +2267,17 @@ def save_parameters(path, *parameters):
 
 
 def feature_extraction_train_regression(folder_name, mid_window, mid_step, short_window, short_step, model_type, model_name,
-                                        compute_beat=False, *, svm_fit="sklearn"):
+                                        compute_beat=False, *, svm_fit="sklearn", forest_fit="sklearn"):
     """Trains one regression model per CSV file of a folder of audio files (reference :370-489): every `<task>.csv` pairs
     file names with target values; features come from multiple_directory_feature_extraction (GPU), the parameter from
     evaluate_regression, the final fit from scikit-learn; `model_name_<task>` and `model_name_<task>MEANS` are written as
     the reference writes them.  svm_fit (keyword only) goes to evaluate_regression: "device" tunes C on the GPU; the final fit
-    and the model file, a pickled SVR, stay scikit-learn's.  Returns (errors, baseline errors, best parameters)."""
+    and the model file, a pickled SVR, stay scikit-learn's.  forest_fit (keyword only, "randomforest") goes to evaluate_regression
+    too; with "device" the final fit is train_random_forest_regression_device and the model file is the pickled
+    to_sklearn_forest_regressor of its arrays, a real RandomForestRegressor that load_model(..., is_regression=True) and
+    file_regression read unchanged.  Returns (errors, baseline errors, best parameters)."""
     _check_svr_fit(svm_fit, model_type)
+    _check_forest_regression_fit(forest_fit, model_type)
     import csv
     import glob
     import ntpath
@@ -2120,7 +2311,7 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
     errors, errors_base, best_params = [], [], []
     for X, y, name in zip(task_features, task_labels, task_names):
         print("Regression task " + name)
-        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params, svm_fit=svm_fit)
+        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params, svm_fit=svm_fit, forest_fit=forest_fit)
         errors.append(error)
         errors_base.append(base_error)
         best_params.append(best)
@@ -2128,7 +2319,10 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
         scaler = StandardScaler()
         X_norm = scaler.fit_transform(X)
         if model_type in _REGRESSION_TYPES:
-            model = _fit_regressor(X_norm, y, model_type, best)
+            if forest_fit == "device":
+                model = to_sklearn_forest_regressor(train_random_forest_regression_device(X_norm, y, int(best))[0])
+            else:
+                model = _fit_regressor(X_norm, y, model_type, best)
             with open(model_name + "_" + name, "wb") as fo:
                 cPickle.dump(model, fo)
             save_parameters(model_name + "_" + name + "MEANS", scaler.mean_.tolist(), scaler.scale_.tolist(), mid_window,

@@ -1,6 +1,7 @@
 // Tree-ensemble classification (kernels_forest.hpp: audioTrainTest.classifier_wrapper for the "randomforest", "extratrees"
 // and "gradientboosting" models) and the fit of the first two (kernels_treefit.hpp: audioTrainTest.train_random_forest /
-// train_extra_trees and the forest half of evaluate_classifier) -- own translation unit, see model_launch.hpp.
+// train_extra_trees and the forest half of evaluate_classifier) and of the forest regressor (train_random_forest_regression and
+// the "randomforest" sweep of evaluate_regression) -- own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
@@ -62,13 +63,34 @@ int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int 
     m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4 + hist);
     const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
     if (lds > 152 * 1024) return -2;
-    const void *kernel = splitter == kBest ? reinterpret_cast<const void *>(&tree_fit_kernel<kBest>)
-                                           : reinterpret_cast<const void *>(&tree_fit_kernel<kRandom>);
+    const void *kernel = splitter == kBest ? reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kGini>)
+                                           : reinterpret_cast<const void *>(&tree_fit_kernel<kRandom, kGini>);
     if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
     if (splitter == kBest)
-        hipLaunchKernelGGL(tree_fit_kernel<kBest>, dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+        hipLaunchKernelGGL((tree_fit_kernel<kBest, kGini>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
     else
-        hipLaunchKernelGGL(tree_fit_kernel<kRandom>, dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+        hipLaunchKernelGGL((tree_fit_kernel<kRandom, kGini>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int tree_fit_reg(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream) {
+    using namespace paa::treefit;
+    if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows) return -2;
+    if (n_tasks < 1 || !m.target) return -1;
+    // LDS: the sort words (a power of two of 64-bit words) | the rows | the feature arrays; the chunk sums of the candidate scan stay
+    // in registers (one chunk per thread), so there is no histogram: 96.5 KB at 8192 rows
+    int p2 = 2;
+    while (p2 < inbag_max) p2 <<= 1;
+    m.lds_keys = p2;
+    m.lds_rows = (inbag_max + 1) / 2 * 2;
+    m.hist_cols = kThreads;
+    m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4);
+    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
+    if (lds > 152 * 1024) return -2;
+    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kMse>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL((tree_fit_kernel<kBest, kMse>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

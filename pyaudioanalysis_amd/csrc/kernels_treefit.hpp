@@ -30,6 +30,31 @@
 // LDS; the stack of pending right children (its depth can reach the number of in-bag rows) and the outputs in global memory.
 // Thread 0 runs the builder's control flow (the draws, the bookkeeping, the node records) and publishes what the others need
 // through the control block; the data-parallel steps (class totals, gather, sort, scan, min / max, partition) use all threads.
+//
+// K19, the regressor (audioTrainTest.train_random_forest_regression and the "randomforest" sweep of evaluate_regression,
+// audioTrainTest.py:229-233, :774-855): CRIT = kMse restates RegressionCriterion / MSE of _criterion.pyx over the BestSplitter
+// with RandomForestRegressor's settings: max_features = n_dims (the draw loop ends when every non-constant feature was visited),
+// one output.  The row word's class field is 0; the targets are a per-job double list in global memory, read through the row
+// index of the word (sort words + row words + targets would fill the CU's 160 KB at 8192 rows, so they are not staged in LDS).
+//  * per node sum_total = sum w y, sq_sum_total = sum (w y) y, weighted_n = sum w; value = sum_total / weighted_n; the root's
+//    impurity is sq_sum_total / weighted_n - (sum_total / weighted_n)^2 (the square a plain product);
+//  * the proxy at position p of the sorted rows is sum_left sum_left / w_left + sum_right sum_right / w_right with sum_left the
+//    prefix of w y and sum_right = sum_total - sum_left; the first strict maximum wins;
+//  * after the final partition sq_sum_left = sum_left (w y) y, sq_sum_right = sq_sum_total - sq_sum_left, and each child's
+//    impurity is sq_sum / w - (sum / w)^2; improvement and the leaf rules are the classifier's.
+// THE ORDER OF EVERY FLOATING-POINT SUM IS FIXED and depends only on the node's rows and the sorted order; there is no float atomic:
+//  * a node's totals and the left child's sums: the node's rows (in the order the stable partitions left them) are cut into 256
+//    consecutive chunks of ceil(n / 256) rows; thread t adds chunk t serially from 0.0 in row order; the 256 partial sums are
+//    added by a xor butterfly within each wave (offsets 32, 16, .. 1) and the four wave sums as ((s0 + s1) + s2) + s3;
+//  * the prefix of w y left of a candidate: the sorted rows (64-bit sort words: value, then weight, then the row's place) are cut
+//    into the same 256 chunks; thread t adds chunk t serially; the chunk sums get an inclusive Hillis-Steele scan within each wave
+//    (offsets 1, 2, .. 32), a chunk's exclusive prefix is (sum of the earlier waves' totals, in wave order from 0.0) + (the scan
+//    value of the lane before, 0.0 for lane 0); from there thread t walks its chunk serially.
+// So a tree is bit-identical run to run, alone or anywhere in a batch.  When the targets and weights make every such sum exact
+// in FP64 (e.g. multiples of 2^-3, |y| <= 2^10, total weight <= 2^13: sum w y y needs 13 + 20 + 6 bits), the order is immaterial
+// and every array equals scikit-learn's bit for bit; otherwise the sums may differ from scikit-learn's (which follow its introsort
+// and in-place partition) in the last places, and a tie that rounding breaks may fall the other way: a valid CART tree, not
+// scikit-learn's bits.
 #pragma once
 #include "device_common.hpp"
 #include "model_launch.hpp"
@@ -129,8 +154,102 @@ __device__ __forceinline__ int block_scan_excl(int v, int *s_w, int &total) {
     return base + inc - v;
 }
 
-template <int SPLITTER>
+// best splitter: the first strict maximum of the columns' (proxy, position) in position order; thread 0 keeps it when it beats the
+// best of the features before, with the threshold between the two sorted values
+__device__ __forceinline__ void best_of_columns(double bv, int bp, double *red_v, int *red_p, const unsigned long long *keys, int f,
+                                                double &best_proxy, int &best_f, double &best_thr) {
+    const int tid = threadIdx.x;
+    red_v[tid] = bv;
+    red_p[tid] = bp;
+    __syncthreads();
+    if (tid < kWave) {
+        bv = red_v[4 * tid];
+        bp = red_p[4 * tid];
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+            if (red_v[4 * tid + q] > bv) {
+                bv = red_v[4 * tid + q];
+                bp = red_p[4 * tid + q];
+            }
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const double ov = __shfl_down(bv, o, kWave);
+            const int op = __shfl_down(bp, o, kWave);
+            if (tid + o < kWave && ov > bv) {
+                bv = ov;
+                bp = op;
+            }
+        }
+        if (tid == 0 && bv > best_proxy) {
+            best_proxy = bv;
+            best_f = f;
+            const double v0 = (double)value_of((unsigned)(keys[bp - 1] >> 32)), v1 = (double)value_of((unsigned)(keys[bp] >> 32));
+            best_thr = v0 / 2.0 + v1 / 2.0;
+            if (best_thr == v1 || best_thr == INFINITY || best_thr == -INFINITY) best_thr = v0;
+        }
+    }
+}
+
+// (MSE) the sums of a, b and c over the workgroup's threads, in every thread: a xor butterfly within each wave, then the waves in order
+__device__ __forceinline__ void block_sum3(double &a, double &b, double &c) {
+    __shared__ double s_d[3][kThreads / kWave];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        a = a + __shfl_xor(a, o, kWave);
+        b = b + __shfl_xor(b, o, kWave);
+        c = c + __shfl_xor(c, o, kWave);
+    }
+    if (lane == 0) {
+        s_d[0][wave] = a;
+        s_d[1][wave] = b;
+        s_d[2][wave] = c;
+    }
+    __syncthreads();
+    a = ((s_d[0][0] + s_d[0][1]) + s_d[0][2]) + s_d[0][3];
+    b = ((s_d[1][0] + s_d[1][1]) + s_d[1][2]) + s_d[1][3];
+    c = ((s_d[2][0] + s_d[2][1]) + s_d[2][2]) + s_d[2][3];
+    __syncthreads();
+}
+
+// (MSE) exclusive prefix of (v, w) over the workgroup's threads: Hillis-Steele within each wave, the earlier waves' totals in order
+__device__ __forceinline__ void block_scan_excl_d(double v, int w, double &ev, int &ew) {
+    __shared__ double s_v[kThreads / kWave];
+    __shared__ int s_n[kThreads / kWave];
+    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    double inc = v;
+    int winc = w;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const double u = __shfl_up(inc, o, kWave);
+        const int uw = __shfl_up(winc, o, kWave);
+        if (lane >= o) {
+            inc = u + inc;
+            winc += uw;
+        }
+    }
+    if (lane == kWave - 1) {
+        s_v[wave] = inc;
+        s_n[wave] = winc;
+    }
+    const double before = __shfl_up(inc, 1, kWave);
+    __syncthreads();
+    double base = 0.0;
+    int wbase = 0;
+#pragma unroll
+    for (int i = 0; i < kThreads / kWave - 1; ++i)
+        if (i < wave) {
+            base = base + s_v[i];
+            wbase += s_n[i];
+        }
+    __syncthreads();
+    ev = base + (lane ? before : 0.0);
+    ew = wbase + winc - w;
+}
+
+template <int SPLITTER, int CRIT>
 __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
+    static_assert(CRIT == kGini || SPLITTER == kBest, "the MSE criterion is built for the best splitter");
     extern __shared__ unsigned long long dyn[];
     __shared__ Control ctl;
     __shared__ int tot[kMaxClasses], left[kMaxClasses], s_w[kThreads / kWave], red_p[kThreads];
@@ -147,7 +266,8 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
     unsigned short *feat = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(dyn) + m.lds_feat);     // behind the histogram
     unsigned short *cons = feat + n_dims;
     const float *xj = m.x32 + job.x_off;
-    const int *lab = m.label + job.off;
+    const int *lab = CRIT == kGini ? m.label + job.off : nullptr;
+    const double *tgt = CRIT == kMse ? m.target + job.off : nullptr;
     const int *wt = task.w_off < 0 ? nullptr : m.weight + task.w_off;
 
     // the rows in the bag, in list order
@@ -159,7 +279,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
         int at = block_scan_excl(cnt, s_w, n_bag);
         for (int i = c0; i < c1; ++i) {
             const int w = wt ? wt[i] : 1;
-            if (w != 0) rows[at++] = row_word(w, lab[i], i);
+            if (w != 0) rows[at++] = row_word(w, CRIT == kGini ? lab[i] : 0, i);
         }
     }
     for (int d = tid; d < n_dims; d += kThreads) {
@@ -184,25 +304,54 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
 
     for (;;) {
         const int start = ctl.start, end = ctl.end, n_node = end - start, n_known = ctl.n_known, node = ctl.node;
-        // the class totals of the node
-        if (tid < K) tot[tid] = 0;
-        __syncthreads();
-        for (int i = start + tid; i < end; i += kThreads) atomicAdd(&tot[word_class(rows[i])], word_weight(rows[i]));
-        __syncthreads();
-        if (tid == 0) {
-            int w = 0;
-            for (int c = 0; c < K; ++c) w += tot[c];
-            if (first) {
-                impurity = gini_of(tot, 1, K, (double)w);
-                w_total = (double)w;
-                first = 0;
+        double sum_tot = 0.0, sq_tot = 0.0;                         // (MSE) the node's sum w y and sum (w y) y, in every thread
+        if constexpr (CRIT == kGini) {
+            // the class totals of the node
+            if (tid < K) tot[tid] = 0;
+            __syncthreads();
+            for (int i = start + tid; i < end; i += kThreads) atomicAdd(&tot[word_class(rows[i])], word_weight(rows[i]));
+            __syncthreads();
+            if (tid == 0) {
+                int w = 0;
+                for (int c = 0; c < K; ++c) w += tot[c];
+                if (first) {
+                    impurity = gini_of(tot, 1, K, (double)w);
+                    w_total = (double)w;
+                    first = 0;
+                }
+                ctl.w_node = w;
+                ctl.leaf = n_node < 2 || impurity <= DBL_EPSILON;
             }
-            ctl.w_node = w;
-            ctl.leaf = n_node < 2 || impurity <= DBL_EPSILON;
+            __syncthreads();
+        } else {
+            // RegressionCriterion.init: the node's totals, chunk-serial then the fixed-shape sum (see the header)
+            const int chunk = (n_node + kThreads - 1) / kThreads, c0 = min(n_node, tid * chunk), c1 = min(n_node, c0 + chunk);
+            double wn = 0.0;
+            for (int i = c0; i < c1; ++i) {
+                const unsigned w = rows[start + i];
+                const double y = tgt[word_row(w)], wy = (double)word_weight(w) * y;
+                sum_tot = sum_tot + wy;
+                sq_tot = sq_tot + wy * y;
+                wn = wn + (double)word_weight(w);                   // (integers below 2^26: exact)
+            }
+            block_sum3(sum_tot, sq_tot, wn);
+            if (tid == 0) {
+                if (first) {
+                    impurity = sq_tot / wn - (sum_tot / wn) * (sum_tot / wn);
+                    w_total = wn;
+                    first = 0;
+                }
+                ctl.w_node = (int)wn;
+                ctl.leaf = n_node < 2 || impurity <= DBL_EPSILON;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         const int w_node = ctl.w_node;
-        if (tid < K) m.value[task.val_off + (long long)node * K + tid] = (double)tot[tid] / (double)w_node;
+        if constexpr (CRIT == kGini) {
+            if (tid < K) m.value[task.val_off + (long long)node * K + tid] = (double)tot[tid] / (double)w_node;
+        } else {
+            if (tid == 0) m.value[task.val_off + node] = sum_tot / (double)w_node;
+        }
 
         // thread 0's split search state (Splitter.node_split)
         int f_i = n_dims, n_found = 0, n_drawn = 0, n_total = n_known, n_visited = 0, f_j = 0, best_f = -1;
@@ -303,7 +452,42 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                     __syncthreads();                                // (the control block is rewritten next)
                     continue;
                 }
-                if constexpr (SPLITTER == kBest) {
+                if constexpr (SPLITTER == kBest && CRIT == kMse) {
+                    // sum w y and the weight left of every candidate: per chunk of consecutive sorted rows, a prefix over the chunks,
+                    // then every thread walks its own chunk (see the header for the order)
+                    const int chunk = (n_node + kThreads - 1) / kThreads, c0 = min(n_node, tid * chunk), c1 = min(n_node, c0 + chunk);
+                    double ps = 0.0, sl;
+                    int pw = 0, wl;
+                    for (int p = c0; p < c1; ++p) {
+                        const unsigned w = (unsigned)keys[p];
+                        ps = ps + (double)word_weight(w) * tgt[word_row(w)];
+                        pw += word_weight(w);
+                    }
+                    block_scan_excl_d(ps, pw, sl, wl);
+                    double bv = -INFINITY;
+                    int bp = -1;
+                    if (c0 < c1) {
+                        float prev = c0 > 0 ? value_of((unsigned)(keys[c0 - 1] >> 32)) : 0.0f;
+                        for (int p = c0; p < c1; ++p) {
+                            const unsigned long long kw = keys[p];
+                            const float v = value_of((unsigned)(kw >> 32));
+                            if (p > 0 && !(v <= prev + kFeatureThreshold)) {
+                                const double dl = (double)wl, dr = (double)(w_node - wl), sr = sum_tot - sl;
+                                const double proxy = sl * sl / dl + sr * sr / dr;
+                                if (proxy > bv) {
+                                    bv = proxy;
+                                    bp = p;
+                                }
+                            }
+                            const unsigned w = (unsigned)kw;
+                            sl = sl + (double)word_weight(w) * tgt[word_row(w)];
+                            wl += word_weight(w);
+                            prev = v;
+                        }
+                    }
+                    best_of_columns(bv, bp, red_v, red_p, keys, f, best_proxy, best_f, best_thr);
+                    __syncthreads();                                // (the sort words and the control block are rewritten next)
+                } else if constexpr (SPLITTER == kBest) {
                     // class counts left of every candidate: per column of consecutive sorted rows, then a prefix over the columns
                     const int cols = m.hist_cols, chunk = (n_node + cols - 1) / cols;
                     const int c0 = min(n_node, tid * chunk), c1 = tid < cols ? min(n_node, c0 + chunk) : c0;
@@ -368,35 +552,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                             prev = v;
                         }
                     }
-                    red_v[tid] = bv;
-                    red_p[tid] = bp;
-                    __syncthreads();
-                    if (tid < kWave) {                              // the first strict maximum in position order
-                        bv = red_v[4 * tid];
-                        bp = red_p[4 * tid];
-#pragma unroll
-                        for (int q = 1; q < 4; ++q)
-                            if (red_v[4 * tid + q] > bv) {
-                                bv = red_v[4 * tid + q];
-                                bp = red_p[4 * tid + q];
-                            }
-#pragma unroll
-                        for (int o = 1; o < kWave; o <<= 1) {
-                            const double ov = __shfl_down(bv, o, kWave);
-                            const int op = __shfl_down(bp, o, kWave);
-                            if (tid + o < kWave && ov > bv) {
-                                bv = ov;
-                                bp = op;
-                            }
-                        }
-                        if (tid == 0 && bv > best_proxy) {
-                            best_proxy = bv;
-                            best_f = f;
-                            const double v0 = (double)value_of((unsigned)(keys[bp - 1] >> 32)), v1 = (double)value_of((unsigned)(keys[bp] >> 32));
-                            best_thr = v0 / 2.0 + v1 / 2.0;
-                            if (best_thr == v1 || best_thr == INFINITY || best_thr == -INFINITY) best_thr = v0;
-                        }
-                    }
+                    best_of_columns(bv, bp, red_v, red_p, keys, f, best_proxy, best_f, best_thr);
                     __syncthreads();                                // (the sort words and the control block are rewritten next)
                 } else {
                     __syncthreads();
@@ -445,8 +601,9 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                 const double thr = ctl.best_thr;
                 const float *xf = xj + (long long)best_f * n;
                 unsigned *tmp = reinterpret_cast<unsigned *>(keys);
-                if (tid < K) left[tid] = 0;
+                if (CRIT == kGini && tid < K) left[tid] = 0;
                 const int chunk = (n_node + kThreads - 1) / kThreads, c0 = min(n_node, tid * chunk), c1 = min(n_node, c0 + chunk);
+                double sum_l = 0.0, sq_l = 0.0, wn_l = 0.0;         // (MSE) the left child's sums, chunk-serial
                 int cnt = 0;
                 for (int i = c0; i < c1; ++i) cnt += (double)xf[word_row(rows[start + i])] <= thr;
                 int lpos = block_scan_excl(cnt, s_w, n_left);
@@ -455,16 +612,30 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                     const unsigned w = rows[start + i];
                     if ((double)xf[word_row(w)] <= thr) {
                         tmp[lpos++] = w;
-                        atomicAdd(&left[word_class(w)], word_weight(w));
+                        if constexpr (CRIT == kGini) {
+                            atomicAdd(&left[word_class(w)], word_weight(w));
+                        } else {
+                            const double y = tgt[word_row(w)], wy = (double)word_weight(w) * y;
+                            sum_l = sum_l + wy;
+                            sq_l = sq_l + wy * y;
+                            wn_l = wn_l + (double)word_weight(w);
+                        }
                     } else {
                         tmp[rpos++] = w;
                     }
                 }
                 __syncthreads();
                 for (int i = tid; i < n_node; i += kThreads) rows[start + i] = tmp[i];
+                if constexpr (CRIT == kMse) block_sum3(sum_l, sq_l, wn_l);
                 if (tid == 0) {
                     if (n_left < 1 || n_left >= n_node) {
                         leaf = 1;                                   // (cannot happen with finite values)
+                    } else if constexpr (CRIT == kMse) {           // MSE.children_impurity
+                        const double dl = wn_l, dn = (double)w_node, dr = dn - dl, sum_r = sum_tot - sum_l;
+                        imp_l = sq_l / dl - (sum_l / dl) * (sum_l / dl);
+                        imp_r = (sq_tot - sq_l) / dr - (sum_r / dr) * (sum_r / dr);
+                        const double improvement = (dn / w_total) * (impurity - (dr / dn * imp_r) - (dl / dn * imp_l));
+                        leaf = improvement + DBL_EPSILON < 0.0;
                     } else {
                         int wl = 0;
                         for (int c = 0; c < K; ++c) wl += left[c];

@@ -4,6 +4,10 @@
 // (paa_forest_fit_splits_f64: the trees are fitted in chunks of bounded device scratch, every test row is scored by the
 // traversal and reduction kernels of the predict path, no tree crosses to the host).  Kernels: kernels_treefit.hpp and
 // kernels_forest.hpp (family_forest.hip).
+// The regressor (train_random_forest_regression and the "randomforest" sweep of evaluate_regression, audioTrainTest.py:229-233,
+// :774-855) goes the same two ways with targets in place of labels (paa_tree_fit_reg_tasks_f64, paa_forest_reg_fit_splits_f64):
+// every job has ONE output, the trees are built by the squared-error instance of tree_fit_kernel with max_features = n_dims, and
+// the sweep scores them as the averaged forest with one output.
 #pragma once
 
 // the limits, for callers and tests: threads per workgroup, rows per job, classes, dims, the largest weight, MiB per chunk
@@ -27,6 +31,13 @@ static int tree_job_check(int j, int64_t n, int k) {
     if (k > treefit::kMaxClasses) return fail(PAA_ERR_UNSUPPORTED, "job %d: %d classes: at most %d are supported", j, k, treefit::kMaxClasses);
     return PAA_OK;
 }
+// the targets of the rows idx [n] (idx null: the list itself) are finite
+static int tree_target_check(const double *target, const int32_t *idx, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(target[idx ? idx[i] : i]))
+            return fail(PAA_ERR_ARG, "target %lld is not finite", (long long)(idx ? idx[i] : i));
+    return PAA_OK;
+}
 static int tree_seed_check(int t, int64_t seed) {
     if (seed < 0 || seed > 0xffffffffLL) return fail(PAA_ERR_ARG, "tree %d: seed %lld: a rand_r state is in 0 .. 2^32 - 1", t, (long long)seed);
     return PAA_OK;
@@ -45,7 +56,8 @@ static int tree_weight_check(int t, const int32_t *w, int64_t n, int *in_bag) {
 
 // One batch of trees on the device.  The caller fills jobs (off, n, k, stat; x_off is set here) and tasks (job, seed, w_off,
 // cap = 2 in-bag rows - 1, node_rel; node_off / val_off are set here), uploads X and names the host arrays; run() allocates,
-// makes the float32 copies, reads the flags back and, when no job is flagged, fits every tree
+// makes the float32 copies, reads the flags back and, when no job is flagged, fits every tree.  With `target` (per job row, in
+// place of `label`) the trees are regression trees: every job's k is 1, max_features is n_dims, the splitter the best one
 struct TreeBatch {
     std::vector<treefit::TreeJob> jobs;
     std::vector<treefit::TreeTask> tasks;
@@ -80,8 +92,8 @@ struct TreeBatch {
         return (size_t)x_words * 4 + (size_t)weights * 4 + (size_t)nodes * (sizeof(treefit::StackRec) + sizeof(forest::Node) + (arrays ? 41 : 0)) +
                (size_t)values * 8;
     }
-    int run(const double *d_X, const int32_t *idx, const int32_t *label, int64_t rows, const int32_t *weight, int64_t n_weights,
-            const double *mean, const double *std, int n_stats, int splitter, bool arrays) {
+    int run(const double *d_X, const int32_t *idx, const int32_t *label, const double *target, int64_t rows, const int32_t *weight,
+            int64_t n_weights, const double *mean, const double *std, int n_stats, int splitter, bool arrays) {
         const size_t sb = (size_t)n_stats * dev.n_dims * 8;
         const int32_t none = 0;
         BlockPart parts[] = {{jobs.data(), jobs.size() * sizeof(treefit::TreeJob), 8},
@@ -89,7 +101,7 @@ struct TreeBatch {
                              {mean, sb, 8},
                              {std, sb, 8},
                              {idx, (size_t)rows * 4, 4},
-                             {label, (size_t)rows * 4, 4},
+                             {target ? (const void *)target : (const void *)label, (size_t)rows * (target ? 8 : 4), (size_t)(target ? 8 : 4)},
                              {n_weights ? weight : &none, (size_t)std::max<int64_t>(n_weights, 1) * 4, 4}};
         int rc;
         if ((rc = block_upload(in, parts, 7, "the tree tasks"))) return rc;
@@ -105,7 +117,8 @@ struct TreeBatch {
         dev.mean = (const double *)parts[2].dev;
         dev.scale = (const double *)parts[3].dev;
         dev.idx = (const int *)parts[4].dev;
-        dev.label = (const int *)parts[5].dev;
+        dev.label = target ? nullptr : (const int *)parts[5].dev;
+        dev.target = target ? (const double *)parts[5].dev : nullptr;
         dev.weight = (const int *)parts[6].dev;
         dev.x32 = (float *)p;                   p += b_x;
         dev.flags = (int *)p;                   p += b_flags;
@@ -123,29 +136,30 @@ struct TreeBatch {
             dev.weighted_n_node_samples = (double *)p;      p += b_d;
             dev.missing_go_to_left = (unsigned char *)p;
         }
-        dev.max_features = std::max(1, (int)std::sqrt((double)dev.n_dims));
+        dev.max_features = target ? dev.n_dims : std::max(1, (int)std::sqrt((double)dev.n_dims));
         LAUNCH_TRY("tree input", launch::tree_prep(dev, (int)n_j, n_max, cs()));
         flags.assign(n_j, 0);
         HIP_TRY(hipMemcpyAsync(flags.data(), dev.flags, n_j * 4, hipMemcpyDeviceToHost, cs()));
         HIP_TRY(hipStreamSynchronize(cs()));
         for (int f : flags) any_flag |= f != 0;
         if (any_flag) return PAA_OK;              // a NaN or an infinity: nothing is fitted, the caller reports it
-        const int lrc = launch::tree_fit(dev, (int)n_t, splitter, inbag_max, k_max, cs());
+        const int lrc = target ? launch::tree_fit_reg(dev, (int)n_t, inbag_max, cs()) : launch::tree_fit(dev, (int)n_t, splitter, inbag_max, k_max, cs());
         if (lrc == -2) return fail(PAA_ERR_UNSUPPORTED, "the trees exceed the kernel's limits");
         if (lrc) return fail(PAA_ERR_HIP, "tree fit launch failed: %s", hipGetErrorString(hipGetLastError()));
         return PAA_OK;
     }
 };
 
-// The trees alone: see paa_hip.h
-extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
-                                      const int32_t *job_idx, const int32_t *job_label, const int32_t *job_k, const double *mean,
-                                      const double *std, int n_tasks, const int32_t *task_job, const int64_t *task_seed,
-                                      const int32_t *task_weight, int splitter, int64_t total_nodes, int64_t total_values,
-                                      int32_t *job_flags, int32_t *node_count, int32_t *children_left, int32_t *children_right,
-                                      int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
-                                      double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value) {
-    if (!X || !job_off || !job_idx || !job_label || !job_k || !mean || !std || !task_job || !task_seed || !task_weight || !job_flags ||
+// The trees alone, classification (job_label, job_k) or regression (job_target): see paa_hip.h
+static int tree_fit_tasks(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off, const int32_t *job_idx,
+                          const int32_t *job_label, const int32_t *job_k, const double *job_target, const double *mean,
+                          const double *std, int n_tasks, const int32_t *task_job, const int64_t *task_seed,
+                          const int32_t *task_weight, int splitter, int64_t total_nodes, int64_t total_values, int32_t *job_flags,
+                          int32_t *node_count, int32_t *children_left, int32_t *children_right, int32_t *feature, double *threshold,
+                          double *impurity, int32_t *n_node_samples, double *weighted_n_node_samples, uint8_t *missing_go_to_left,
+                          double *value) {
+    const bool reg = job_label == nullptr && job_k == nullptr;
+    if (!X || !job_off || !job_idx || (reg ? !job_target : (!job_label || !job_k)) || !mean || !std || !task_job || !task_seed || !task_weight || !job_flags ||
         !node_count || !children_left || !children_right || !feature || !threshold || !impurity || !n_node_samples ||
         !weighted_n_node_samples || !missing_go_to_left || !value)
         return fail(PAA_ERR_ARG, "null argument");
@@ -161,12 +175,14 @@ extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_
     b.jobs.resize(n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         const int64_t n = job_off[j + 1] - job_off[j];
-        if ((rc = tree_job_check(j, n, job_k[j]))) return rc;
-        b.jobs[j] = {(long long)job_off[j], 0, (int)n, job_k[j], j, 0};
-        for (int64_t i = job_off[j]; i < job_off[j + 1]; ++i)
-            if (job_label[i] < 0 || job_label[i] >= job_k[j])
-                return fail(PAA_ERR_ARG, "job %d: class index %d of row %lld: 0 .. %d", j, job_label[i], (long long)(i - job_off[j]), job_k[j] - 1);
+        const int k = reg ? 1 : job_k[j];
+        if ((rc = tree_job_check(j, n, k))) return rc;
+        b.jobs[j] = {(long long)job_off[j], 0, (int)n, k, j, 0};
+        for (int64_t i = job_off[j]; !reg && i < job_off[j + 1]; ++i)
+            if (job_label[i] < 0 || job_label[i] >= k)
+                return fail(PAA_ERR_ARG, "job %d: class index %d of row %lld: 0 .. %d", j, job_label[i], (long long)(i - job_off[j]), k - 1);
     }
+    if (reg && (rc = tree_target_check(job_target, nullptr, rows))) return rc;
     if ((rc = sweep_index_check(job_idx, rows, n_samples, "row"))) return rc;
     b.tasks.resize(n_tasks);
     int64_t w_off = 0;
@@ -187,7 +203,7 @@ extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_
     if ((rc = ensure_init())) return rc;
     Staged st;                                        // X goes up once, through the lane's scratch
     if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
-    if ((rc = b.run(st.feats, job_idx, job_label, rows, task_weight, w_off, mean, std, n_jobs, splitter, true))) return rc;
+    if ((rc = b.run(st.feats, job_idx, job_label, job_target, rows, task_weight, w_off, mean, std, n_jobs, splitter, true))) return rc;
     std::copy(b.flags.begin(), b.flags.end(), job_flags);
     if (b.any_flag) return PAA_OK;
     const size_t tn = (size_t)b.total_nodes;
@@ -205,16 +221,41 @@ extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_
     HIP_TRY(hipStreamSynchronize(cs()));
     return PAA_OK;
 }
+extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
+                                      const int32_t *job_idx, const int32_t *job_label, const int32_t *job_k, const double *mean,
+                                      const double *std, int n_tasks, const int32_t *task_job, const int64_t *task_seed,
+                                      const int32_t *task_weight, int splitter, int64_t total_nodes, int64_t total_values,
+                                      int32_t *job_flags, int32_t *node_count, int32_t *children_left, int32_t *children_right,
+                                      int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                                      double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value) {
+    if (!job_label || !job_k) return fail(PAA_ERR_ARG, "null argument");
+    return tree_fit_tasks(X, n_samples, n_dims, n_jobs, job_off, job_idx, job_label, job_k, nullptr, mean, std, n_tasks, task_job, task_seed,
+                          task_weight, splitter, total_nodes, total_values, job_flags, node_count, children_left, children_right, feature,
+                          threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value);
+}
+extern "C" int paa_tree_fit_reg_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
+                                          const int32_t *job_idx, const double *job_target, const double *mean, const double *std,
+                                          int n_tasks, const int32_t *task_job, const int64_t *task_seed, const int32_t *task_weight,
+                                          int64_t total_nodes, int64_t total_values, int32_t *job_flags, int32_t *node_count,
+                                          int32_t *children_left, int32_t *children_right, int32_t *feature, double *threshold,
+                                          double *impurity, int32_t *n_node_samples, double *weighted_n_node_samples,
+                                          uint8_t *missing_go_to_left, double *value) {
+    return tree_fit_tasks(X, n_samples, n_dims, n_jobs, job_off, job_idx, nullptr, nullptr, job_target, mean, std, n_tasks, task_job,
+                          task_seed, task_weight, treefit::kBest, total_nodes, total_values, job_flags, node_count, children_left,
+                          children_right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value);
+}
 
-// The forest half of audioTrainTest.evaluate_classifier: every split a job of n_estimators trees; see paa_hip.h
-extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
-                                         const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
-                                         const int32_t *test_idx, const double *mean, const double *std, const int32_t *n_estimators,
-                                         int splitter, const int64_t *tree_seed, const int32_t *tree_weight, int32_t *label_out,
-                                         double *proba, int max_classes, int32_t *job_flags, int32_t *n_chunks) {
+// The forest half of audioTrainTest.evaluate_classifier (labels; label_out, proba) and the "randomforest" sweep of evaluate_regression
+// (targets; pred, train_pred): every split a job of n_estimators trees; see paa_hip.h
+static int forest_fit_splits(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, const double *targets, int n_jobs,
+                             const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                             const double *mean, const double *std, const int32_t *n_estimators, int splitter, const int64_t *tree_seed,
+                             const int32_t *tree_weight, int32_t *label_out, double *proba, int max_classes, double *pred,
+                             double *train_pred, int32_t *job_flags, int32_t *n_chunks) {
     // check
-    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !n_estimators || !tree_seed || !label_out ||
-        !job_flags)
+    const bool reg = targets != nullptr;
+    if (!X || (reg ? !pred : (!labels || !label_out)) || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !n_estimators ||
+        !tree_seed || !job_flags)
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -222,11 +263,14 @@ extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int
     if ((rc = sweep_jobs_check(n_jobs, train_off, test_off))) return rc;
     const int64_t n_q = test_off[n_jobs], n_t = train_off[n_jobs];
     if ((rc = sweep_index_check(train_idx, n_t, n_samples, "train"))) return rc;
-    for (int64_t i = 0; i < n_t; ++i)
+    if (reg && (rc = tree_target_check(targets, train_idx, n_t))) return rc;
+    for (int64_t i = 0; !reg && i < n_t; ++i)
         if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
     if ((rc = sweep_index_check(test_idx, n_q, n_samples, "test"))) return rc;
     // per job the classes present in its training list, ascending, and every row's place among them
-    std::vector<int> row_label((size_t)n_t), job_class;
+    std::vector<int> row_label(reg ? 0 : (size_t)n_t), job_class;
+    std::vector<double> row_target(reg ? (size_t)n_t : 0);
+    for (int64_t i = 0; reg && i < n_t; ++i) row_target[i] = targets[train_idx[i]];
     std::vector<size_t> job_class_off(n_jobs + 1, 0);
     std::vector<int64_t> first_tree(n_jobs + 1, 0), first_weight(n_jobs + 1, 0);
     std::vector<treefit::TreeJob> jobs(n_jobs);
@@ -234,14 +278,14 @@ extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int
     for (int j = 0; j < n_jobs; ++j) {
         const int32_t *tr = train_idx + train_off[j];
         const int64_t n = train_off[j + 1] - train_off[j];
-        std::vector<int> classes;
-        for (int64_t i = 0; i < n; ++i) classes.push_back(labels[tr[i]]);
+        std::vector<int> classes(reg ? 1 : 0, 0);                 // a regression job: one output
+        for (int64_t i = 0; !reg && i < n; ++i) classes.push_back(labels[tr[i]]);
         std::sort(classes.begin(), classes.end());
         classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
         if ((rc = tree_job_check(j, n, (int)classes.size()))) return rc;
         if (n_estimators[j] < 1 || n_estimators[j] > kForestMaxTrees)
             return fail(PAA_ERR_ARG, "job %d: %d trees: 1..%d are supported", j, n_estimators[j], kForestMaxTrees);
-        for (int64_t i = 0; i < n; ++i)
+        for (int64_t i = 0; !reg && i < n; ++i)
             row_label[train_off[j] + i] = (int)(std::lower_bound(classes.begin(), classes.end(), labels[tr[i]]) - classes.begin());
         jobs[j] = {(long long)train_off[j], 0, (int)n, (int)classes.size(), j, 0};
         k_all = std::max(k_all, (int)classes.size());
@@ -304,24 +348,27 @@ extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int
             job_val[j - j0 + 1] = job_val[j - j0] + jn * job.k;
         }
         b.layout();
-        if ((rc = b.run(st.feats, train_idx + train_off[j0], row_label.data() + train_off[j0], train_off[j1] - train_off[j0],
+        if ((rc = b.run(st.feats, train_idx + train_off[j0], reg ? nullptr : row_label.data() + train_off[j0],
+                        reg ? row_target.data() + train_off[j0] : nullptr, train_off[j1] - train_off[j0],
                         tree_weight ? tree_weight + first_weight[j0] : nullptr, first_weight[j1] - first_weight[j0],
                         mean + (size_t)j0 * n_dims, std + (size_t)j0 * n_dims, j1 - j0, splitter, false)))
             return rc;
         for (int j = j0; j < j1; ++j) job_flags[j] = b.flags[j - j0];
         if (b.any_flag) break;                            // a NaN or an infinity in a training row: the caller reports it
-        // score every job's test rows with its trees: the traversal and reduction kernels of the predict path
-        int64_t q_max = 0, leaf_max = 0, q_chunk = test_off[j1] - test_off[j0];
+        // score every job's test rows with its trees: the traversal and reduction kernels of the predict path.  A regression sweep that
+        // wants them scores every job's training rows too (the chunk's uploaded train lists), behind the chunk's test rows
+        const int64_t q_chunk = test_off[j1] - test_off[j0], t_chunk = reg && train_pred ? train_off[j1] - train_off[j0] : 0;
+        int64_t q_max = 0, leaf_max = 0;
         for (int j = j0; j < j1; ++j) {
-            const int64_t q = test_off[j + 1] - test_off[j];
+            const int64_t q = std::max<int64_t>(test_off[j + 1] - test_off[j], t_chunk ? jobs[j].n : 0);
             q_max = std::max(q_max, q);
             leaf_max = std::max(leaf_max, (int64_t)n_estimators[j] * std::min<int64_t>(q, forest::kChunk));
         }
-        if (q_chunk) {
+        if (q_chunk + t_chunk) {
             DevBlock score;
             const size_t b_roots = up256(roots.size() * 4), b_test = up256((size_t)q_chunk * 4), b_feats = up256((size_t)q_max * n_dims * 8),
-                         b_leaves = up256((size_t)leaf_max * 4), b_raw = up256((size_t)q_max * k_all * 8), b_label = up256((size_t)q_chunk * 4),
-                         b_proba = up256((size_t)q_chunk * k_all * 8);
+                         b_leaves = up256((size_t)leaf_max * 4), b_raw = up256((size_t)q_max * k_all * 8),
+                         b_label = up256((size_t)(q_chunk + t_chunk) * 4), b_proba = up256((size_t)(q_chunk + t_chunk) * k_all * 8);
             HIP_TRY(hipMalloc(&score.p, b_roots + b_test + b_feats + b_leaves + b_raw + b_label + b_proba));
             char *p = (char *)score.p;
             int *d_roots = (int *)p;            p += b_roots;
@@ -332,48 +379,62 @@ extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int
             int *d_label = (int *)p;            p += b_label;
             double *d_proba = (double *)p;
             HIP_TRY(hipMemcpyAsync(d_roots, roots.data(), roots.size() * 4, hipMemcpyHostToDevice, cs()));
-            HIP_TRY(hipMemcpyAsync(d_test, test_idx + test_off[j0], (size_t)q_chunk * 4, hipMemcpyHostToDevice, cs()));
+            if (q_chunk) HIP_TRY(hipMemcpyAsync(d_test, test_idx + test_off[j0], (size_t)q_chunk * 4, hipMemcpyHostToDevice, cs()));
             int64_t p_off = 0;
             std::vector<int64_t> job_p(j1 - j0 + 1, 0);
+            // the rows d_rows [q] of job j: labels to d_label + at, probabilities (regression: predictions) to d_proba + at_p
+            auto score_rows = [&](int j, const int *d_rows, int64_t q, int64_t at, int64_t at_p) -> int {
+                const treefit::TreeJob &job = b.jobs[j - j0];
+                LAUNCH_TRY("scored row gather", launch::tree_gather(st.feats, n_dims, d_rows, q, d_feats, q, cs()));
+                forest::ForestDev f{};
+                f.nodes = b.dev.nodes + job_node[j - j0];
+                f.roots = d_roots + (first_tree[j] - first_tree[j0]);
+                f.leaf_values = b.dev.value + job_val[j - j0];
+                f.init = nullptr;
+                f.n_trees = n_estimators[j];
+                f.n_dims = n_dims;
+                f.n_classes = f.n_outputs = job.k;
+                f.boosted = 0;
+                f.learning_rate = 0.0;
+                LAUNCH_TRY("tree-ensemble", launch::forest(f, d_feats, (long long)q, (long long)q, b.dev.mean + (size_t)(j - j0) * n_dims,
+                                                           b.dev.scale + (size_t)(j - j0) * n_dims, d_leaves, d_label + at, d_raw,
+                                                           d_proba + at_p, cs()));
+                return PAA_OK;
+            };
             for (int j = j0; j < j1; ++j) {
                 const int64_t q = test_off[j + 1] - test_off[j], q0 = test_off[j] - test_off[j0];
                 job_p[j - j0] = p_off;
-                if (q) {
-                    const treefit::TreeJob &job = b.jobs[j - j0];
-                    LAUNCH_TRY("test row gather", launch::tree_gather(st.feats, n_dims, d_test + q0, q, d_feats, q, cs()));
-                    forest::ForestDev f{};
-                    f.nodes = b.dev.nodes + job_node[j - j0];
-                    f.roots = d_roots + (first_tree[j] - first_tree[j0]);
-                    f.leaf_values = b.dev.value + job_val[j - j0];
-                    f.init = nullptr;
-                    f.n_trees = n_estimators[j];
-                    f.n_dims = n_dims;
-                    f.n_classes = f.n_outputs = job.k;
-                    f.boosted = 0;
-                    f.learning_rate = 0.0;
-                    LAUNCH_TRY("tree-ensemble", launch::forest(f, d_feats, (long long)q, (long long)q, b.dev.mean + (size_t)(j - j0) * n_dims,
-                                                               b.dev.scale + (size_t)(j - j0) * n_dims, d_leaves, d_label + q0, d_raw,
-                                                               d_proba + p_off, cs()));
-                    p_off += q * job.k;
-                }
+                if (q && (rc = score_rows(j, d_test + q0, q, q0, p_off))) return rc;
+                p_off += q * b.jobs[j - j0].k;
             }
             job_p[j1 - j0] = p_off;
-            h_label.resize((size_t)q_chunk);
-            h_proba.resize((size_t)p_off);
-            HIP_TRY(hipMemcpyAsync(h_label.data(), d_label, (size_t)q_chunk * 4, hipMemcpyDeviceToHost, cs()));
-            if (proba && p_off) HIP_TRY(hipMemcpyAsync(h_proba.data(), d_proba, (size_t)p_off * 8, hipMemcpyDeviceToHost, cs()));
+            for (int j = j0; t_chunk && j < j1; ++j) {        // (regression: k is 1, so a row's prediction sits at the row's place)
+                const int64_t t0 = q_chunk + train_off[j] - train_off[j0];
+                if ((rc = score_rows(j, b.dev.idx + b.jobs[j - j0].off, b.jobs[j - j0].n, t0, t0))) return rc;
+            }
+            h_label.resize((size_t)(q_chunk + t_chunk));
+            h_proba.resize((size_t)(p_off + t_chunk));
+            HIP_TRY(hipMemcpyAsync(h_label.data(), d_label, (size_t)(q_chunk + t_chunk) * 4, hipMemcpyDeviceToHost, cs()));
+            if ((proba || reg) && p_off + t_chunk)
+                HIP_TRY(hipMemcpyAsync(h_proba.data(), d_proba, (size_t)(p_off + t_chunk) * 8, hipMemcpyDeviceToHost, cs()));
             HIP_TRY(hipStreamSynchronize(cs()));
-            // a label is the position among the job's classes (-1: a test value is infinite in float32): back to class indices
             for (int j = j0; j < j1; ++j) {
                 const int k = b.jobs[j - j0].k;
                 for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) {
                     const int l = h_label[(size_t)(q - test_off[j0])];
+                    if (reg) {                                    // the averaged forest's one output; -1: a test value is infinite in float32
+                        pred[q] = h_proba[(size_t)(q - test_off[j0])];
+                        if (l < 0) job_flags[j] |= 1;
+                        continue;
+                    }
+                    // a label is the position among the job's classes (-1: a test value is infinite in float32): back to class indices
                     label_out[q] = l < 0 ? l : job_class[job_class_off[j] + l];
                     if (proba) {
                         const double *row = h_proba.data() + job_p[j - j0] + (q - test_off[j]) * k;
                         for (int c = 0; c < k; ++c) proba[(size_t)q * max_classes + c] = row[c];
                     }
                 }
+                for (int64_t t = train_off[j]; t_chunk && t < train_off[j + 1]; ++t) train_pred[t] = h_proba[(size_t)(q_chunk + t - train_off[j0])];
             }
         } else {
             HIP_TRY(hipStreamSynchronize(cs()));
@@ -382,4 +443,22 @@ extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int
     }
     if (n_chunks) *n_chunks = chunks;
     return PAA_OK;
+}
+extern "C" int paa_forest_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                         const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                         const int32_t *test_idx, const double *mean, const double *std, const int32_t *n_estimators,
+                                         int splitter, const int64_t *tree_seed, const int32_t *tree_weight, int32_t *label_out,
+                                         double *proba, int max_classes, int32_t *job_flags, int32_t *n_chunks) {
+    if (!labels) return fail(PAA_ERR_ARG, "null argument");
+    return forest_fit_splits(X, n_samples, n_dims, labels, nullptr, n_jobs, train_off, train_idx, test_off, test_idx, mean, std, n_estimators,
+                             splitter, tree_seed, tree_weight, label_out, proba, max_classes, nullptr, nullptr, job_flags, n_chunks);
+}
+extern "C" int paa_forest_reg_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *targets, int n_jobs,
+                                             const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                             const int32_t *test_idx, const double *mean, const double *std,
+                                             const int32_t *n_estimators, const int64_t *tree_seed, const int32_t *tree_weight,
+                                             double *pred, double *train_pred, int32_t *job_flags, int32_t *n_chunks) {
+    if (!targets) return fail(PAA_ERR_ARG, "null argument");
+    return forest_fit_splits(X, n_samples, n_dims, nullptr, targets, n_jobs, train_off, train_idx, test_off, test_idx, mean, std,
+                             n_estimators, treefit::kBest, tree_seed, tree_weight, nullptr, nullptr, 0, pred, train_pred, job_flags, n_chunks);
 }

@@ -181,6 +181,7 @@ constexpr int kMaxDims = forest::kMaxDims;
 constexpr int kMaxWeight = 8191;          // a row's integer weight (0: out of the bag)
 constexpr long long kChunkBytes = 1LL << 30;      // device scratch of one chunk of a sweep's trees (a job is never cut)
 enum Splitter { kBest = 0, kRandom = 1 };
+enum Criterion { kGini = 0, kMse = 1 };   // classification; regression (squared error, one output, best splitter)
 // a job: the rows idx[off .. off + n - 1] of the sample matrix, their class indices label[off ..] in 0 .. k - 1, standardised
 // with row `stat` of mean / scale; its float32 copy x32[x_off ..] is feature-major [n_dims][n]
 struct TreeJob {
@@ -204,7 +205,8 @@ struct StackRec {
 // nodes and the values only
 struct TreeDev {
     const double *X;          // [n_samples][n_dims]
-    const int *idx, *label;   // per job row
+    const int *idx, *label;   // per job row (label: kGini)
+    const double *target;     // per job row (kMse; such a job has k = 1)
     const TreeJob *jobs;
     const TreeTask *tasks;
     const int *weight;
@@ -213,7 +215,7 @@ struct TreeDev {
     int *flags;               // prep, per job: 1: a value is infinite in float32, 2: a value is NaN
     StackRec *stack;          // [total cap]
     forest::Node *nodes;      // out [total cap]: forest_traverse_kernel's layout
-    double *value;            // out: per node the class fractions, [cap][k of the job] per tree
+    double *value;            // out: per node the class fractions, [cap][k of the job] per tree; kMse: the weighted mean, [cap]
     int *node_count;          // out per task
     int *children_left, *children_right, *feature, *n_node_samples;
     double *threshold, *impurity, *weighted_n_node_samples;
@@ -311,6 +313,8 @@ int tree_prep(const treefit::TreeDev &m, int n_jobs, int n_max, hipStream_t stre
 // ... one workgroup per task builds its tree (splitter: treefit::Splitter; inbag_max: the most in-bag rows of a task, k_max the
 // most classes of a job; they size the LDS and are written into m); -2 when a limit is exceeded
 int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int k_max, hipStream_t stream);
+// ... the same for regression trees (treefit::kMse over the best splitter; m.target in place of m.label, every job's k is 1)
+int tree_fit_reg(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream);
 // ... out [n_dims][ld] = the rows d_rows [n_rows] of X [..][n_dims], feature-major as the traversal kernel reads them
 int tree_gather(const double *d_X, int n_dims, const int *d_rows, long long n_rows, double *d_out, long long ld, hipStream_t stream);
 // ... threads per workgroup, the row limit, the class limit, the dims limit, the weight limit, the chunk size in MiB
