@@ -312,6 +312,25 @@ def limit_case(n=8192):
     return dict(X=X, y=y.astype(np.int64), w=np.ones(n, dtype=np.int32), mean=np.zeros(2), scale=np.ones(2), seed=20240229)
 
 
+def wide_limit_case(n_classes=64, n=8192):
+    """The classifier's largest launch: the row limit with 64 classes (128 histogram columns of 64 rows) or, with n_classes=32, the
+    same rows labelled y % 32 (the full 32 x 257 histogram, the column switch from below).  3 dims, every value a float32 multiple
+    of 1/64: columns 0 and 1 are the class's place on an 8 x 8 grid plus noise, column 2 is noise.  Weights: mostly 1, 400 rows 0,
+    300 rows 3, one row 8191 (the weight limit); every class keeps a weighted row.  scikit-learn 1.7.2 grows 8089 (best) and 12351
+    (random) nodes on the 64 classes."""
+    rs = np.random.RandomState(2025)
+    y = np.arange(n) % 64
+    rs.shuffle(y)
+    X = np.stack([y % 8 + 0.4 * rs.randn(n), y // 8 + 0.4 * rs.randn(n), rs.randn(n)], axis=1)
+    X = (np.round(X * 64) / 64).astype(np.float32).astype(np.float64)
+    w = np.ones(n, dtype=np.int32)
+    pick = rs.permutation(n)
+    w[pick[:400]], w[pick[400:700]], w[pick[700]] = 0, 3, 8191
+    y = (y % n_classes).astype(np.int64)
+    assert np.unique(y[w > 0]).shape[0] == n_classes
+    return dict(X=X, y=y, w=w, mean=np.zeros(3), scale=np.ones(3), seed=20250611)
+
+
 def sweep_case():
     """A sweep of 3 classes over 330 rows: n_estimators 1, 3, 10 x 2 experiments, plus one job whose training list lacks class 2.
     Returns (X, y, jobs) with jobs of (train_idx, test_idx, mean, scale, (n_estimators, seed))."""
@@ -339,3 +358,151 @@ def sklearn_forest(X, y, job, kind):
     m = cls(n_estimators=ne, random_state=seed).fit((X[tr] - mean) / scale, y[tr])
     Z = (X[te] - mean) / scale
     return m.predict(Z), m.predict_proba(Z), m
+
+
+def dims_and_weight_cases():
+    """The classifier's remaining edges, held by fit_tree (tests/test_treefit_scale_*.py): 255 and 256 dims (max_features 15 and 16;
+    256 is the dims limit, the two feature arrays full) and the weight limit 8191 among the weights 0, 1, 2."""
+    rs = np.random.RandomState(4711)
+    out = {}
+    for d in (255, 256):
+        y = np.arange(80) % 3
+        rs.shuffle(y)
+        X = np.round((rs.randn(80, d) + 0.6 * y[:, None] * rs.randn(1, d)) * 512) / 512
+        out["dims_%d" % d] = dict(X=X, y=y.astype(np.int64), w=np.ones(80, dtype=np.int32), mean=X.mean(0), scale=X.std(0),
+                                  seed=int(rs.randint(0, RAND_R_MAX)))
+    y = np.arange(100) % 3
+    rs.shuffle(y)
+    X = rs.randn(100, 4) + 0.6 * y[:, None] * rs.randn(1, 4)
+    w = np.array([0, 1, 2, 8191], dtype=np.int32)[rs.randint(0, 4, 100)]
+    first = [int(np.flatnonzero(y == c)[0]) for c in range(3)]
+    w[first] = np.maximum(w[first], 1)                                              # every class keeps a weighted row
+    assert np.unique(y[w > 0]).shape[0] == 3 and set(w.tolist()) == {0, 1, 2, 8191}
+    out["weights_0_1_2_8191"] = dict(X=X, y=y.astype(np.int64), w=w, mean=np.zeros(4), scale=np.ones(4), seed=int(rs.randint(0, RAND_R_MAX)))
+    return out
+
+
+def check_gini_tree(tree, x32, y, weight, n_classes):
+    """Walks a classification tree on the host and asserts what holds of EVERY tree the builder may return for these rows, whichever
+    features it drew: n_node_samples and weighted_n_node_samples are the true counts of the rows that reach the node; value is the
+    weighted class fraction of those rows (integer counts, one FP64 division: exact to the bit); impurity is the Gini of those counts
+    in class order; an internal node sends at least one row each way and its missing_go_to_left names the larger side; a leaf is pure
+    or unsplittable (fewer than 2 rows or every feature constant on them: with min_samples_leaf = 1 the draw goes on until it finds a
+    feature that is not constant, and a Gini split never has a negative improvement).  Returns the number of leaves."""
+    x32 = np.asarray(x32, dtype=np.float32)
+    y, weight = np.asarray(y).astype(np.int64), np.asarray(weight).astype(np.int64)
+    leaves, seen = 0, 0
+    stack = [(0, np.flatnonzero(weight != 0))]
+    while stack:
+        node, rows = stack.pop()
+        seen += 1
+        counts = np.bincount(y[rows], weights=weight[rows], minlength=n_classes).astype(np.int64)
+        w_node = int(counts.sum())
+        assert int(tree["n_node_samples"][node]) == rows.shape[0] and float(tree["weighted_n_node_samples"][node]) == float(w_node), node
+        assert np.array_equal(np.asarray(tree["value"][node]), counts.astype(np.float64) / np.float64(w_node)), node
+        assert float(tree["impurity"][node]) == float(_gini(counts, w_node)), node
+        left, right = int(tree["children_left"][node]), int(tree["children_right"][node])
+        if left < 0:
+            assert right < 0 and int(tree["feature"][node]) == -2 and float(tree["threshold"][node]) == -2.0, node
+            pure = np.count_nonzero(counts) == 1
+            splittable = rows.shape[0] >= 2 and bool(np.any(x32[rows].max(0) > x32[rows].min(0)))
+            assert pure or not splittable, node
+            leaves += 1
+            continue
+        assert left == node + 1 and right > left, node
+        go_left = x32[rows, int(tree["feature"][node])].astype(np.float64) <= float(tree["threshold"][node])
+        n_left = int(go_left.sum())
+        assert 1 <= n_left < rows.shape[0], node
+        assert int(tree["missing_go_to_left"][node]) == int(n_left > rows.shape[0] - n_left), node
+        stack.append((right, rows[~go_left]))
+        stack.append((left, rows[go_left]))
+    assert seen == np.asarray(tree["feature"]).shape[0]
+    return leaves
+
+
+def score_trees(trees, z32):
+    """What scikit-learn's forests compute from fitted trees for the float32 rows z32: per tree the leaf each row reaches
+    (x <= threshold goes left), the leaves' values summed in tree order and divided by the tree count.  Returns [rows][outputs]."""
+    z = np.asarray(z32, dtype=np.float32).astype(np.float64)
+    total = np.zeros((z.shape[0], np.asarray(trees[0]["value"]).shape[1]))
+    for t in trees:
+        feature, threshold = np.asarray(t["feature"]), np.asarray(t["threshold"])
+        left, right = np.asarray(t["children_left"]), np.asarray(t["children_right"])
+        node = np.zeros(z.shape[0], dtype=np.int64)
+        while True:
+            inner = np.flatnonzero(left[node] >= 0)
+            if not inner.size:
+                break
+            at = node[inner]
+            node[inner] = np.where(z[inner, feature[at]] <= threshold[at], left[at], right[at])
+        total += np.asarray(t["value"])[node]
+    return total / len(trees)
+
+
+def expected_chunks(jobs, kind, labels=None):
+    """The chunks a sweep must fit these jobs in, as lists of job numbers: the packing rule of lib_treefit.hpp restated.  A job takes
+    4 n n_dims bytes of float32 rows, 4 bytes per weight (one per row and tree with a bootstrap, none for extra trees), 40 bytes per
+    node of capacity (a stack record and a packed node) and 8 k bytes per node for the values (k: the classes present in the job's
+    training rows, 1 for the regressor); a tree's capacity is 2 (in-bag rows) - 1 nodes.  A job joins the current chunk unless it
+    is not the chunk's first and the sum would exceed 2^30 bytes.  kind: "randomforest", "extratrees" or "regressor"."""
+    chunks, used = [], 0
+    for j, (tr, _, mean, _, (n_estimators, seed)) in enumerate(jobs):
+        n, n_dims = len(tr), len(mean)
+        k = 1 if kind == "regressor" else int(np.unique(np.asarray(labels)[tr]).shape[0])
+        if kind == "extratrees":
+            weights, nodes = 0, n_estimators * (2 * n - 1)
+        else:
+            weights = n_estimators * n
+            nodes = sum(2 * int(np.count_nonzero(bootstrap_weights(s, n))) - 1 for s in forest_seeds(seed, n_estimators))
+        size = 4 * n * n_dims + 4 * weights + 40 * nodes + 8 * k * nodes
+        if chunks and used + size <= 2 ** 30:
+            chunks[-1].append(j)
+            used += size
+        else:
+            chunks.append([j])
+            used = size
+    return chunks
+
+
+CHUNK_TREES = {"randomforest": 64, "extratrees": 40}
+CHUNK_LAYOUT = [[0, 1], [2, 3, 4], [5, 6]]                 # what expected_chunks gives for chunk_sweep_case, either kind
+CHUNK_TINY, CHUNK_NO_TEST = 3, 5
+
+
+def _chunk_stats(j, Z):
+    """A big job's own mean and scale: one column is moved out to -2^(18 + j % 4), where float32 keeps 1/32 .. 1/4 of the 1/64 grid
+    the values lie on, so the float32 rows -- and with them the trees -- are those of THIS job's statistics and of no other's."""
+    mean, scale = Z.mean(0), Z.std(0) * (1.0 + j / 8.0)
+    mean[j % 3] = -float(2 ** (18 + j % 4))
+    return mean, scale
+
+
+def chunk_sweep_case(kind):
+    """A classifier sweep that needs three chunks of the real 1 GiB bound: the wide_limit_case rows plus 400 rows for the test lists;
+    seven jobs big, big, big, tiny, big, big, big.  A big job trains on its own permutation of the 8192 rows (64 classes) with its
+    own mean, scale and seed and has 50 test rows (job 5: none); the tiny job trains 3 trees on 5 rows of the classes 17 and 40 and
+    has 7 test rows.  Returns (X, y, jobs) with jobs of (train_idx, test_idx, mean, scale, (n_estimators, seed))."""
+    c = wide_limit_case()
+    rs = np.random.RandomState(606)
+    y2 = rs.randint(0, 64, 400)
+    X2 = np.round(np.stack([y2 % 8 + 0.4 * rs.randn(400), y2 // 8 + 0.4 * rs.randn(400), rs.randn(400)], axis=1) * 64) / 64
+    X, y = np.concatenate([c["X"], X2]), np.concatenate([c["y"], y2]).astype(np.float64)
+    n, jobs = c["X"].shape[0], []
+    for j in range(7):
+        seed = int(rs.randint(np.iinfo(np.int32).max))
+        if j == CHUNK_TINY:
+            tr = np.concatenate([np.flatnonzero(c["y"] == 17)[:3], np.flatnonzero(c["y"] == 40)[:2]])
+            jobs.append((tr, n + rs.permutation(400)[:7], np.zeros(3), np.ones(3), (3, seed)))
+            continue
+        tr = rs.permutation(n)
+        te = n + rs.permutation(400)[:0 if j == CHUNK_NO_TEST else 50]
+        jobs.append((tr, te) + _chunk_stats(j, X[tr]) + ((CHUNK_TREES[kind], seed),))
+    return X, y, jobs
+
+
+def job_tasks(y, job, bootstrap, forest_tree_seeds, tree_inputs):
+    """One job of a sweep as the tasks tree_fit / tree_fit_regression take: per tree the seed and the weights that
+    train_forest_device derives, through the two functions of audioTrainTest handed in."""
+    tr, _, mean, scale, (n_estimators, seed) = job
+    rows, labels = np.asarray(tr), np.asarray(y)[tr]
+    return [(rows, labels) + tree_inputs(s, rows.shape[0], bootstrap)[::-1] + (mean, scale) for s in forest_tree_seeds(seed, n_estimators)]

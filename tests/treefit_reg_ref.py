@@ -310,3 +310,35 @@ def check_cart_tree(tree, x32, y, weight, distinct=False):
         stack.append((int(tree["children_right"][node]), rows[~go_left]))
         stack.append((int(tree["children_left"][node]), rows[go_left]))
     return internal
+
+
+CHUNK_TREES = 700
+CHUNK_LAYOUT, CHUNK_TINY, CHUNK_NO_TEST = T.CHUNK_LAYOUT, T.CHUNK_TINY, T.CHUNK_NO_TEST
+
+
+def chunk_sweep_case():
+    """The regressor's sweep over three chunks of the real 1 GiB bound: the rows, lists, means and scales of
+    treefit_ref.chunk_sweep_case with 700 trees per big job (a tree of ~5180 in-bag rows takes ~0.53 MB of capacity, whatever its
+    depth).  The targets are the cell of the 8 x 8 grid the row lies in -- 64 levels a tree finds with a few exact cuts -- plus noise on
+    every 16th row, which the tree must then isolate: ~1/6 of the nodes of an unrestricted target, so that the ~10 000 trees of the test
+    stay within seconds.  Multiples of 1/8 within +-1024 and a bootstrap's total weight of 8192: every sum is exact."""
+    X, _, jobs = T.chunk_sweep_case("randomforest")
+    rs = np.random.RandomState(707)
+    cell = 8.0 * np.floor(np.clip(X[:, 0], 0, 7.5)) + np.floor(np.clip(X[:, 1], 0, 7.5))
+    y = eighths(cell + np.where(np.arange(X.shape[0]) % 16 == 0, 4.0 * rs.randn(X.shape[0]), 0.0))
+    jobs = [j[:4] + ((j[4][0] if i == CHUNK_TINY else CHUNK_TREES, j[4][1]),) for i, j in enumerate(jobs)]
+    for j in jobs:
+        assert_exact(y[j[0]], np.ones(len(j[0]), dtype=np.int64))
+    return X, y, jobs
+
+
+def many_test_rows_case():
+    """One job whose test list is longer than one traversal pass of the sweep's scoring (32 768 rows): 60 training rows, 3 trees,
+    32 769 + 5 test rows of a 33 000 x 3 matrix.  Returns (X, labels of 3 classes, exact targets, the job)."""
+    rs = np.random.RandomState(808)
+    X = np.round(rs.randn(33000, 3) * 64) / 64
+    labels = (np.arange(33000) % 3).astype(np.float64)
+    X[:, 0] += labels
+    y = eighths(3.0 * X[:, 0] - 2.0 * np.abs(X[:, 2]) + rs.randn(33000))
+    tr, te = np.arange(60), 60 + rs.permutation(32940)[:32769 + 5]
+    return X, labels, y, (tr, te, X[tr].mean(0), X[tr].std(0), (3, 90210))
