@@ -82,8 +82,10 @@ def solved(n_dims, kernel, iters_per_launch=0):
 
 
 def dual_state(beta, K, targets, C):
-    """(alpha [2 n], G [2 n]) of the returned beta: alpha_t = max(beta_t, 0), alpha_{t+n} = max(-beta_t, 0) -- libsvm never holds
-    both variables of a row above zero at a stop that the checks accept -- and the gradient recomputed from it."""
+    """(alpha [2 n], G [2 n]) of the returned beta: alpha_t = max(beta_t, 0), alpha_{t+n} = max(-beta_t, 0) -- for epsilon > 0
+    libsvm never holds both variables of a row above zero at a stop that the checks accept -- and the gradient recomputed from
+    it.  For epsilon > 0 ONLY: at epsilon = 0 the two variables of a row tie exactly, most states hold both above zero
+    (tests/test_svr_edges_ref_cpu.py) and this helper must not be used."""
     alpha = np.concatenate([np.maximum(beta, 0.0), np.maximum(-beta, 0.0)])
     return alpha, svr_fit_ref.gradient(K, targets, alpha, EPSILON)
 
