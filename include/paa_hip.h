@@ -617,6 +617,54 @@ int paa_forest_reg_fit_splits_f64(const double *X, int64_t n_samples, int n_dims
                                   const double *mean, const double *std, const int32_t *n_estimators, const int64_t *tree_seed,
                                   const int32_t *tree_weight, double *pred, double *train_pred, int32_t *job_flags, int32_t *n_chunks);
 
+/* ---- fitting gradient-boosting classifiers: audioTrainTest.train_gradient_boosting (audioTrainTest.py:181-199) and the
+ * "gradientboosting" sweep of evaluate_classifier (:631-700) ---------------------------------------------------------------------
+ * The model is scikit-learn 1.7.2's GradientBoostingClassifier(n_estimators) with its defaults: log-loss, subsample 1, the class
+ * priors as the initial raw score, and per stage one DecisionTreeRegressor(criterion="friedman_mse", max_depth) per class (one in
+ * all for two classes) on the negative gradients, whose leaves take one Newton step (_update_terminal_regions).  A stage's TREE is
+ * the regression tree above with FriedmanMSE's proxy and improvement and a depth limit (a node at max_depth is a leaf; the root has
+ * depth 0); its sums keep the fixed order, so a model is a function of its job alone: bit-identical run to run, alone or anywhere in
+ * a batch, in any chunking.  Where the residual sums are exact in FP64 (stage 0 of balanced jobs with 2, 4 or 8 classes) every tree
+ * array and leaf value equals scikit-learn's bit for bit; later stages sum rounded residuals and may differ in the last places.
+ *
+ * paa_tree_fit_boost_tasks_f64 -- the builder alone: the arguments of paa_tree_fit_reg_tasks_f64 and max_depth (>= 1) before
+ * total_nodes; value holds the node means (no leaf step).
+ *
+ * paa_boost_fit_splits_f64 -- the sweep: X, labels, the train / test lists, mean / std as paa_forest_fit_splits_f64; job j is fitted
+ * with n_estimators[j] stages on the classes present among its training rows (at least two, else PAA_ERR_ARG).
+ *   tree_seed                the rand_r seed of every tree, job after job, within a job stage-major then by class (one per stage for
+ *                            two classes)
+ *   init [n_jobs][max_classes]   the initial raw score of every job (its first k_out entries are read; k_out = 1 for two classes)
+ *   learning_rate, max_depth scikit-learn's 0.1 and 3
+ *   chunk_bytes              <= 0: the 1 GiB rule for the device scratch of one chunk of jobs (a job is never cut); > 0: a smaller
+ *                            bound (tests)
+ *   label_out [Q]            the class index of every test row (-1: a test value is infinite in float32, -2: it is NaN)
+ *   proba [Q][max_classes]   (may be NULL) predict_proba, zeros past a job's classes
+ *   train_score [sum of n_estimators]    (may be NULL) per job and stage the mean training loss, scikit-learn's train_score_
+ *   train_raw                (may be NULL) per job the raw predictions of its training rows after the last stage, [n][k_out]
+ *   train_resid              (may be NULL) per job the negative gradients its LAST stage's trees were fitted to, [n][k_out], as
+ *                            boost_gradient_kernel formed them from the raw predictions of the stage before (tests)
+ *   total_nodes              0: no trees are returned.  Else the sum over the trees of min(2 n - 1, 2^(max_depth + 1) - 1), and
+ *                            node_count .. value receive every tree's scikit-learn arrays in the order of tree_seed, each tree at
+ *                            the sum of the sizes before it (value: the Newton value at a leaf, the mean residual elsewhere)
+ *   job_flags, n_chunks      as paa_forest_fit_splits_f64
+ * Errors as above.                                                                                                                   */
+int paa_tree_fit_boost_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off, const int32_t *job_idx,
+                                 const double *job_target, const double *mean, const double *std, int n_tasks, const int32_t *task_job,
+                                 const int64_t *task_seed, const int32_t *task_weight, int max_depth, int64_t total_nodes,
+                                 int64_t total_values, int32_t *job_flags, int32_t *node_count, int32_t *children_left,
+                                 int32_t *children_right, int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                                 double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value);
+int paa_boost_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs, const int64_t *train_off,
+                             const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                             const double *std, const int32_t *n_estimators, const int64_t *tree_seed, const double *init,
+                             int max_classes, double learning_rate, int max_depth, int64_t chunk_bytes, int32_t *label_out,
+                             double *proba, double *train_score, double *train_raw, double *train_resid, int64_t total_nodes,
+                             int32_t *node_count,
+                             int32_t *children_left, int32_t *children_right, int32_t *feature, double *threshold, double *impurity,
+                             int32_t *n_node_samples, double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value,
+                             int32_t *job_flags, int32_t *n_chunks);
+
 /* ---- audioSegmentation.hmm_segmentation / train_hmm_compute_statistics (audioSegmentation.py:287-492) -------------------
  * Gaussian hidden Markov models with one diagonal Gaussian per state, as the reference trains them and hmmlearn's
  * GaussianHMM.predict decodes them.  The model: startprob [K], transmat [K][K], means [K][n_dims], covars [K][n_dims] --

@@ -153,6 +153,13 @@ _SIGNATURES = {
                                              c_i32p, c_f64p, C.POINTER(C.c_uint8), c_f64p]),
     "paa_forest_reg_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
                                                 c_i32p, c_i64p, c_i32p, c_f64p, c_f64p, c_i32p, c_i32p]),
+    "paa_tree_fit_boost_tasks_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int, c_i32p,
+                                               c_i64p, c_i32p, C.c_int, C.c_int64, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p,
+                                               c_f64p, c_i32p, c_f64p, C.POINTER(C.c_uint8), c_f64p]),
+    "paa_boost_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
+                                           c_i32p, c_i64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int64, c_i32p, c_f64p, c_f64p, c_f64p,
+                                           c_f64p, C.c_int64, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_f64p, c_i32p, c_f64p, C.POINTER(C.c_uint8),
+                                           c_f64p, c_i32p, c_i32p]),
     "paa_hmm_create": (C.c_int, [c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "paa_hmm_destroy": (C.c_int, [C.c_void_p]),
     "paa_hmm_num_states": (C.c_int, [C.c_void_p]),

@@ -52,6 +52,10 @@ depth-first Gini tree bit for bit (tree_fit_kernel through paa_tree_fit_tasks_f6
 tree seeds, rand_r seeds and bootstrap counts NumPy draws for scikit-learn), the sweep scores every test row with the predict
 kernels, train_forest_device is the final fit and to_sklearn_forest makes the model file's RandomForestClassifier /
 ExtraTreesClassifier.
+With boosting_fit="device" "gradientboosting" is fitted on the GPU as well: per stage one launch forms the negative gradients and the
+loss of the stage before (boost_gradient_kernel) and one builds the stage's depth-3 Friedman trees, one workgroup per (split, class),
+with the leaves' Newton steps (paa_boost_fit_splits_f64; boosting_split_fit_predict, train_gradient_boosting_device,
+to_sklearn_boosting, tree_fit_boosting).
 smote / use_smote are refused (NotImplementedError).
 Regression ("svm" / "svm_rbf": sklearn.svm.SVR; "randomforest": RandomForestRegressor) predicts on the GPU too: a BANK of
 SVR models -- file_regression's model_name_* models, each with its own MEANS file, or the n_exp models of one parameter
@@ -429,7 +433,10 @@ def forest_arrays(classifier):
             raise NotImplementedError("gradient boosting with init=%r: the GPU path serves the default prior and 'zero'"
                                       % (init_,))
         arrays = _tree_arrays([e for stage in est for e in stage], 1)
-        return ForestArrays("boosted", *arrays[:6], arrays[6][:, 0], classes, n_dims, classifier.learning_rate, init)
+        boosted = ForestArrays("boosted", *arrays[:6], arrays[6][:, 0], classes, n_dims, classifier.learning_rate, init)
+        if hasattr(init_, "class_prior_"):                            # (to_sklearn_boosting rebuilds init_ from it)
+            boosted.class_prior_ = np.asarray(init_.class_prior_, dtype=np.float64)
+        return boosted
     if getattr(classifier, "n_outputs_", 1) != 1:
         raise NotImplementedError("multi-output forests are not served by the GPU path")
     arrays = _tree_arrays(list(est), classes.shape[0])
@@ -1546,8 +1553,19 @@ def tree_fit_regression(X, tasks):
     return _tree_fit(X, tasks, None)
 
 
-def _tree_fit(X, tasks, splitter):
-    """tree_fit (splitter 'best' / 'random') and tree_fit_regression (splitter None)."""
+def tree_fit_boosting(X, tasks, max_depth=3):
+    """The regression trees of gradient-boosting stages over ONE sample matrix, all built side by side (paa_tree_fit_boost_tasks_f64,
+    the Friedman instance of tree_fit_kernel: scikit-learn 1.7.2's DecisionTreeRegressor(criterion="friedman_mse", max_depth) -- best
+    splitter, every feature, a node at max_depth is a leaf).  X and the tasks (rows, y, weights, seed, mean, scale) are
+    tree_fit_regression's, and so are the fixed summation order, the exactness rule (targets that are multiples of 1/8 within +-1024
+    give scikit-learn's arrays bit for bit), the refusals and the result: value [nodes][1] holds the node means (no leaf step)."""
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 1:
+        raise ValueError("max_depth = %r: an integer >= 1" % (max_depth,))
+    return _tree_fit(X, tasks, None, int(max_depth))
+
+
+def _tree_fit(X, tasks, splitter, max_depth=None):
+    """tree_fit (splitter 'best' / 'random'), tree_fit_regression (splitter None) and tree_fit_boosting (... with max_depth)."""
     regression = splitter is None
     X = np.ascontiguousarray(X, dtype=np.float64)
     tasks = list(tasks)
@@ -1612,7 +1630,9 @@ def _tree_fit(X, tasks, splitter):
             _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
             _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
             out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(value))
-    if regression:
+    if regression and max_depth is not None:
+        _ffi.check(_ffi.lib().paa_tree_fit_boost_tasks_f64(*head, _ffi.as_f64p(label), *middle, max_depth, *tail))
+    elif regression:
         _ffi.check(_ffi.lib().paa_tree_fit_reg_tasks_f64(*head, _ffi.as_f64p(label), *middle, *tail))
     else:
         _ffi.check(_ffi.lib().paa_tree_fit_tasks_f64(*head, _ffi.as_i32p(label), _ffi.as_i32p(k), *middle, _TREE_SPLITTERS[splitter], *tail))
@@ -1891,6 +1911,236 @@ def to_sklearn_forest_regressor(arrays):
     return forest
 
 
+BOOST_LEARNING_RATE, BOOST_MAX_DEPTH = 0.1, 3    # GradientBoostingClassifier's defaults, which train_gradient_boosting keeps
+
+
+def boosting_tree_seeds(random_state, n_trees):
+    """Per tree of a GradientBoostingClassifier the rand_r seed of its splitter: scikit-learn hands every tree of the ensemble the SAME
+    RandomState (check_random_state(random_state): None is NumPy's global state, an int a fresh RandomState), and every tree's
+    splitter draws ONE randint(0, RAND_R_MAX) from it, stage after stage and within a stage class after class."""
+    if random_state is None:
+        rs = np.random.mtrand._rand
+    elif isinstance(random_state, np.random.RandomState):
+        rs = random_state
+    else:
+        rs = _TREE_RS
+        rs.seed(random_state)
+    return [int(v) for v in rs.randint(0, RAND_R_MAX, size=int(n_trees))] if int(n_trees) > 0 else []
+
+
+def boosting_init(class_index, n_classes):
+    """The constant initial raw score of a GradientBoostingClassifier (init=None) on rows with the class indices class_index in
+    0 .. n_classes - 1: DummyClassifier(strategy="prior")'s class fractions, clipped to float32's eps, through the loss's link --
+    scikit-learn's own link objects, so the bits are its bits (8 balanced classes give -2.2e-16, not 0).  [1] for two classes."""
+    from sklearn._loss.link import LogitLink, MultinomialLogit
+    counts = np.bincount(np.asarray(class_index, dtype=np.int64), minlength=int(n_classes))
+    prior = counts / counts.sum()
+    eps = np.finfo(np.float32).eps
+    if n_classes == 2:
+        return np.asarray(LogitLink().link(np.clip(prior[1:2], eps, 1 - eps, dtype=np.float64)), dtype=np.float64).reshape(1)
+    return np.asarray(MultinomialLogit().link(np.clip(prior.reshape(1, -1), eps, 1 - eps, dtype=np.float64)), dtype=np.float64)[0]
+
+
+def _boost_tree_cap(n, max_depth):
+    return min(2 * n - 1, 2 ** (max_depth + 1) - 1)
+
+
+class BoostingSplitResult(_SplitResult):
+    """What boosting_split_fit_predict returns: label [Q] (class values as in `labels`), proba [Q][max_classes] or None (column c: the
+    job's c-th present class; zeros past a job's classes), test_off [n_jobs + 1], classes (per job the classes present in its training
+    list, ascending), n_estimators [n_jobs], the number of chunks the jobs were fitted in and, with train_score=True, per job
+    train_score (scikit-learn's train_score_ [n_estimators]), train_raw (the raw predictions of its training rows after the last
+    stage, [n][n_outputs]) and train_resid (the negative gradients its last stage's trees were fitted to, [n][n_outputs]), else None; models: per job a ForestArrays of kind "boosted" when the trees were asked for, else None."""
+
+    def __init__(self, label, proba, test_off, classes, n_estimators, n_chunks, train_score, train_raw, train_resid, models):
+        self.label, self.proba, self.test_off, self.classes, self.n_estimators, self.n_chunks = label, proba, test_off, classes, n_estimators, n_chunks
+        self.train_score, self.train_raw, self.train_resid, self.models = train_score, train_raw, train_resid, models
+
+    def job(self, j):
+        """(labels, probabilities [n_test][classes present in job j] or None) of job j."""
+        r = self._rows(j)
+        return self.label[r], None if self.proba is None else self.proba[r, :len(self.classes[j])]
+
+
+def boosting_split_fit_predict(X, labels, jobs, proba=False, train_score=False, *, trees=False, chunk_bytes=None):
+    """GradientBoostingClassifier(n_estimators, random_state=seed).fit(train).predict(test) for every job of a sweep over ONE sample
+    matrix (paa_boost_fit_splits_f64: per stage one gradient launch and one tree launch over all jobs that still have stages, one
+    workgroup per (job, class) tree, which also takes the leaves' Newton steps and updates the raw predictions; every test row is
+    scored on the device by the boosted path of forest_predict; no tree crosses to the host unless trees=True).  X [n_samples][n_dims];
+    labels [n_samples] (integers >= 0 on the training rows); a job is (train_idx, test_idx, mean, scale, (n_estimators, seed)).  The
+    host does what NumPy does for scikit-learn: per job boosting_tree_seeds(seed, stages x trees per stage) and boosting_init.  A
+    model is a function of its job alone (bit-identical alone, in any batch and chunking); stage 0 of a balanced job with 2, 4 or 8
+    classes equals scikit-learn's bit for bit, later stages are those of a valid boosted model whose sums may differ from
+    scikit-learn's in the last places.  A training list above 8192 rows raises NotImplementedError and one
+    that holds a single class scikit-learn's ValueError, before the library is asked; NaN / infinity raise scikit-learn's ValueError.
+    chunk_bytes (keyword only): a bound below the library's 1 GiB for the device scratch of one chunk of jobs (tests).  Returns a
+    BoostingSplitResult."""
+    p = _pack_jobs(X, labels, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
+    n_samples, n_dims = p.X.shape
+    n_jobs = len(p.last)
+    counts = np.diff(p.train_off)
+    for j in range(n_jobs):
+        _check_tree_rows(int(counts[j]), "job %d" % j)
+    classes = [np.unique(p.labels[rows]) for rows in p.inside]
+    for j in range(n_jobs):
+        if counts[j] > 0 and len(classes[j]) < 2:
+            raise ValueError("y contains %d class after sample_weight trimmed classes with zero weights, while a minimum of 2 classes "
+                             "are required." % len(classes[j]))
+    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
+    k_out = [1 if len(c) == 2 else len(c) for c in classes]
+    max_classes = max(max(len(c) for c in classes), 2)
+    init = np.zeros((n_jobs, max_classes), dtype=np.float64)
+    seeds = []
+    for j in range(n_jobs):
+        seeds += boosting_tree_seeds(p.last[j][1], int(n_est[j]) * k_out[j])
+        if len(classes[j]) >= 2:
+            init[j, :k_out[j]] = boosting_init(np.searchsorted(classes[j], p.labels[p.inside[j]]), len(classes[j]))
+    seed = np.array(seeds if seeds else [0], dtype=np.int64)
+    Q, T = int(p.test_off[-1]), int(p.train_off[-1])
+    label = np.zeros(Q, dtype=np.int32)
+    P = np.zeros((Q, max_classes), dtype=np.float64) if proba else None
+    score_off = _offsets(n_est)
+    raw_off = _offsets([int(counts[j]) * k_out[j] for j in range(n_jobs)])
+    score = np.zeros(max(int(score_off[-1]), 1)) if train_score else None
+    raw = np.zeros(max(int(raw_off[-1]), 1)) if train_score else None
+    resid = np.zeros(max(int(raw_off[-1]), 1)) if train_score else None
+    caps = np.repeat([_boost_tree_cap(int(counts[j]), BOOST_MAX_DEPTH) for j in range(n_jobs)],
+                     [int(n_est[j]) * k_out[j] for j in range(n_jobs)]).astype(np.int64) if trees else np.zeros(0, dtype=np.int64)
+    node_off = _offsets(caps)
+    total_nodes = int(node_off[-1]) if trees else 0
+    i32 = lambda n: np.zeros(max(n, 1), dtype=np.int32)          # noqa: E731
+    f64 = lambda n: np.zeros(max(n, 1), dtype=np.float64)        # noqa: E731
+    out = {"children_left": i32(total_nodes), "children_right": i32(total_nodes), "feature": i32(total_nodes), "threshold": f64(total_nodes),
+           "impurity": f64(total_nodes), "n_node_samples": i32(total_nodes), "weighted_n_node_samples": f64(total_nodes),
+           "missing_go_to_left": np.zeros(max(total_nodes, 1), dtype=np.uint8), "value": f64(total_nodes)}
+    count = i32(len(caps) if trees else 0)
+    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    _ffi.check(_ffi.lib().paa_boost_fit_splits_f64(
+        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
+        _ffi.as_i64p(seed), _ffi.as_f64p(init), max_classes, BOOST_LEARNING_RATE, BOOST_MAX_DEPTH, int(chunk_bytes or 0),
+        _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None, _ffi.as_f64p(score) if train_score else None,
+        _ffi.as_f64p(raw) if train_score else None, _ffi.as_f64p(resid) if train_score else None, total_nodes, _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
+        _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
+        _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
+        out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(out["value"]), _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
+    _raise_tree_flags(flags)
+    ForestModel._raise_invalid(label)
+    scores = [score[int(score_off[j]):int(score_off[j + 1])].copy() for j in range(n_jobs)] if train_score else None
+    raws = [raw[int(raw_off[j]):int(raw_off[j + 1])].reshape(int(counts[j]), k_out[j]).copy() for j in range(n_jobs)] if train_score else None
+    resids = [resid[int(raw_off[j]):int(raw_off[j + 1])].reshape(int(counts[j]), k_out[j]).copy() for j in range(n_jobs)] if train_score else None
+    models = None
+    if trees:
+        models, t0 = [], 0
+        for j in range(n_jobs):
+            n_trees = int(n_est[j]) * k_out[j]
+            cut = lambda name: np.concatenate([out[name][int(node_off[t]):int(node_off[t]) + int(count[t])] for t in range(t0, t0 + n_trees)])   # noqa: E731
+            m = ForestArrays("boosted", _offsets(count[t0:t0 + n_trees]), cut("children_left"), cut("children_right"), cut("feature"),
+                             cut("threshold"), cut("missing_go_to_left"), cut("value"), classes[j], n_dims, BOOST_LEARNING_RATE, init[j, :k_out[j]])
+            m.impurity, m.n_node_samples, m.weighted_n_node_samples = cut("impurity"), cut("n_node_samples").astype(np.int64), cut("weighted_n_node_samples")
+            m.max_depth = BOOST_MAX_DEPTH
+            cnt = np.bincount(np.searchsorted(classes[j], p.labels[p.inside[j]]), minlength=len(classes[j]))
+            m.class_prior_ = cnt / cnt.sum()
+            if train_score:
+                m.train_score_ = scores[j]
+            models.append(m)
+            t0 += n_trees
+    return BoostingSplitResult(label.astype(np.int64), P, p.test_off, classes, n_est, int(chunks[0]), scores, raws, resids, models)
+
+
+def train_gradient_boosting_device(features, labels, n_estimators, *, random_state=None):
+    """train_gradient_boosting on the GPU: GradientBoostingClassifier(n_estimators, random_state=random_state).fit(features, labels)
+    by boosting_split_fit_predict with one job over all rows (random_state None: the trees' seeds come from NumPy's global state
+    exactly as scikit-learn draws them).  Returns a ForestArrays of kind "boosted", which forest_model, forest_predict,
+    classifier_wrapper and device_model take, with train_score_ attached (and impurity, n_node_samples, weighted_n_node_samples for
+    to_sklearn_boosting).  More than 8192 rows raise NotImplementedError and a single class scikit-learn's ValueError before the
+    device is touched; there is no CPU fallback."""
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    raw = np.asarray(labels).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
+    if int(n_estimators) < 1:
+        raise ValueError("n_estimators = %r" % (n_estimators,))
+    n, n_dims = X.shape
+    _check_tree_rows(n, "the training set")
+    classes, idx = np.unique(raw, return_inverse=True)
+    job = (np.arange(n), np.zeros(0, dtype=np.int64), np.zeros(n_dims), np.ones(n_dims), (int(n_estimators), random_state))
+    res = boosting_split_fit_predict(X, idx.reshape(-1), [job], train_score=True, trees=True)
+    model = res.models[0]
+    model.classes_ = classes
+    return model
+
+
+def to_sklearn_boosting(arrays):
+    """A real fitted sklearn.ensemble.GradientBoostingClassifier with the trees of a ForestArrays of kind "boosted" (every Tree is
+    built through __setstate__): estimators_ [stages][trees per stage] of DecisionTreeRegressors, init_ (a DummyClassifier with the
+    class priors that give the arrays' initial raw score), classes_, n_trees_per_iteration_ and train_score_ (the arrays' when they
+    carry it, zeros otherwise).  It predicts as scikit-learn predicts from those arrays, pickles as the reference's model files do,
+    and load_model / classifier_wrapper read it unchanged.  Needs scikit-learn."""
+    import sklearn.ensemble
+    from sklearn.dummy import DummyClassifier
+    from sklearn.tree import DecisionTreeRegressor
+    from sklearn.tree._tree import NODE_DTYPE, Tree
+    a = forest_arrays(arrays)
+    if a.kind != "boosted":
+        raise ValueError("a tree ensemble of kind %r: 'boosted' expected" % (a.kind,))
+    n_trees, k, k_out = a.node_offsets.shape[0] - 1, a.n_classes, a.n_outputs
+    if k < 2 or n_trees < 1 or n_trees % k_out or a.init is None or a.init.shape[0] != k_out:
+        raise ValueError("boosted ensemble: %d trees for %d outputs of %d classes" % (n_trees, k_out, k))
+    n_stages = n_trees // k_out
+    max_depth = int(getattr(a, "max_depth", BOOST_MAX_DEPTH))
+    gb = sklearn.ensemble.GradientBoostingClassifier(n_estimators=n_stages, learning_rate=a.learning_rate, max_depth=max_depth)
+    gb.classes_ = np.asarray(a.classes_)
+    gb.n_classes_ = k
+    gb.n_features_in_ = a.n_dims
+    gb.n_trees_per_iteration_ = k_out
+    gb.n_estimators_ = n_stages
+    gb.max_features_ = a.n_dims
+    gb._loss = gb._get_loss(sample_weight=None)
+    # the priors whose link is the initial raw score: the fit's own when the arrays carry them, else softmax / expit of the score
+    # (the link's inverse); _raw_predict_init clips and links them
+    if getattr(a, "class_prior_", None) is not None:
+        prior = np.asarray(a.class_prior_, dtype=np.float64)
+    elif k_out == 1:
+        p1 = 1.0 / (1.0 + np.exp(-a.init[0]))
+        prior = np.array([1.0 - p1, p1])
+    else:
+        e = np.exp(a.init - np.max(a.init))
+        prior = e / e.sum()
+    init = DummyClassifier(strategy="prior")
+    init.classes_, init.n_classes_, init.class_prior_ = np.arange(k), k, prior
+    init.n_outputs_, init.sparse_output_, init._strategy, init.n_features_in_ = 1, False, "prior", a.n_dims
+    gb.init_ = init
+    gb.train_score_ = np.asarray(getattr(a, "train_score_", np.zeros(n_stages)), dtype=np.float64)
+    value = a.value.reshape(-1)
+    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
+    gb.estimators_ = np.empty((n_stages, k_out), dtype=object)
+    for t in range(n_trees):
+        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
+        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
+        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
+        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
+        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
+        for name in extra:
+            if extra[name] is not None:
+                nodes[name] = extra[name][lo:hi]
+        tree = Tree(a.n_dims, np.array([1], dtype=np.intp), 1)
+        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
+                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, 1))})
+        est = DecisionTreeRegressor(criterion="friedman_mse", max_depth=max_depth)
+        est.tree_ = tree
+        est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, a.n_dims
+        gb.estimators_[t // k_out, t % k_out] = est
+    return gb
+
+
+def _check_boosting_fit(boosting_fit, classifier_name):
+    if boosting_fit not in ("sklearn", "device"):
+        raise ValueError("boosting_fit=%r: 'sklearn' or 'device'" % (boosting_fit,))
+    if boosting_fit == "device" and classifier_name != "gradientboosting":
+        raise ValueError("boosting_fit='device' serves the classifier type 'gradientboosting', not %r" % (classifier_name,))
+
+
 def _draw_split(n_samples, train_percentage):
     """One random split as (train indices, test indices): train_test_split over the sample indices consumes NumPy's
     global state exactly as the reference's train_test_split(X, y, ...) (:648-649) does, and X[train], X[test], y[test]
@@ -1900,7 +2150,7 @@ def _draw_split(n_samples, train_percentage):
 
 
 def evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                        train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn"):
+                        train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
     """Picks the classifier parameter with the best cross-validated accuracy (parameter_mode 0) or macro F1 (1)
     (reference :576-771): for every value, n_exp random splits (n_exp = -1: int(50000 / n_samples) + 1), each with its own
     StandardScaler; with list_of_ids the n_exp GroupShuffleSplit(train_size=.8) splits are drawn once and shared by every value.
@@ -1924,13 +2174,19 @@ def evaluate_classifier(features, class_names, classifier_name, params, paramete
     every split on the GPU and classifies every test row there.  Every split's predictions are those of scikit-learn's forest
     with random_state=<that seed> on the same split, bit for bit.  The one visible difference to the default: scikit-learn's
     fits draw their tree seeds from the global state between the splits, so for one np.random.seed the two modes see different
-    splits.  A split above 8192 training rows raises NotImplementedError.  forest_fit="sklearn" (the default): untouched."""
+    splits.  A split above 8192 training rows raises NotImplementedError.  forest_fit="sklearn" (the default): untouched.
+    boosting_fit="device" (keyword only; "gradientboosting", any other type raises ValueError naming boosting_fit before any work):
+    the same path once more -- ALL splits up front in parameter-major order, then ONE seed per split in job order
+    (np.random.randint(np.iinfo(np.int32).max)), and ONE boosting_split_fit_predict call fits the n_estimators stages of every split
+    on the GPU and classifies every test row there.  Every split's model is a valid boosted model of scikit-learn's kind for
+    random_state=<that seed> (stage 0 of balanced 2-, 4- and 8-class splits bit for bit; see boosting_split_fit_predict).
+    boosting_fit="sklearn" (the default): untouched."""
     return evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids, n_exp,
-                                    train_percentage, smote, svm_fit=svm_fit, forest_fit=forest_fit)[0]
+                                    train_percentage, smote, svm_fit=svm_fit, forest_fit=forest_fit, boosting_fit=boosting_fit)[0]
 
 
 def evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                             train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn"):
+                             train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
     """evaluate_classifier, returning (the chosen parameter, the confusion matrix of every parameter value, the predictions
     [parameter][experiment] of every split's test rows)."""
     if svm_fit not in ("sklearn", "device"):
@@ -1941,6 +2197,7 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
         raise ValueError("forest_fit=%r: 'sklearn' or 'device'" % (forest_fit,))
     if forest_fit == "device" and classifier_name not in _FOREST_FIT_KINDS:
         raise ValueError("forest_fit='device' serves the classifier types %s, not %r" % (" and ".join(_FOREST_FIT_KINDS), classifier_name))
+    _check_boosting_fit(boosting_fit, classifier_name)
     if smote:
         raise NotImplementedError("smote=True: imbalanced-learn's SMOTE makes training rows that are no rows of the sample "
                                   "matrix; this package does not resample")
@@ -1970,16 +2227,17 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
             train_idx, test_idx = shared[e] if list_of_ids else _draw_split(n_samples_total, train_percentage)
             scaler = StandardScaler().fit(X[train_idx])
             splits[-1].append((train_idx, test_idx, scaler.mean_, scaler.scale_))
-            if classifier_name != "knn" and svm_fit != "device" and forest_fit != "device":
+            if classifier_name != "knn" and svm_fit != "device" and forest_fit != "device" and boosting_fit != "device":
                 classifier = _train_classifier(scaler.transform(X[train_idx]), y[train_idx], classifier_name, C_param)
                 predictions[-1].append(list(predict(classifier, classifier_name, X[test_idx].T, scaler.mean_, scaler.scale_)[0])
                                        if len(test_idx) else [])
-    if classifier_name == "knn" or svm_fit == "device" or forest_fit == "device":       # one sweep over every split
+    if classifier_name == "knn" or svm_fit == "device" or forest_fit == "device" or boosting_fit == "device":       # one sweep over every split
         knn, cast = classifier_name == "knn", int if classifier_name == "knn" else float
-        if forest_fit == "device":                            # (n_estimators, the forest's seed): one draw per job, in job order
+        if forest_fit == "device" or boosting_fit == "device":  # (n_estimators, the ensemble's seed): one draw per job, in job order
             cast = lambda v: (int(v), int(np.random.randint(np.iinfo(np.int32).max)))      # noqa: E731
         jobs = [(tr, te, mean, scale, cast(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
         res = knn_split_predict(X, y, jobs) if knn else forest_split_fit_predict(X, y, jobs, classifier_name) if forest_fit == "device" else \
+            boosting_split_fit_predict(X, y, jobs) if boosting_fit == "device" else \
             svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
         as_label = (lambda v: v) if knn else y.dtype.type      # kNN: the result's int64 as it is
         predictions = [[[as_label(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
@@ -2045,7 +2303,7 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
 
 def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
                                compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn",
-                               final_fit="sklearn", forest_fit="sklearn"):
+                               final_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
     """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
     :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
     evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
@@ -2056,7 +2314,11 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     train_svm_device and writes the model file in the reference's format, a pickled sklearn.svm.SVC, through to_sklearn_svc --
     the MEANS file is the same.  forest_fit (keyword only): "device" ("randomforest" / "extratrees" only, any other type raises
     ValueError before any work) tunes n_estimators with evaluate_classifier(forest_fit="device") AND makes the final fit with
-    train_forest_device; the model file is a pickled RandomForestClassifier / ExtraTreesClassifier made by to_sklearn_forest."""
+    train_forest_device; the model file is a pickled RandomForestClassifier / ExtraTreesClassifier made by to_sklearn_forest.
+    boosting_fit (keyword only): "device" ("gradientboosting" only, any other type raises ValueError before any work) tunes
+    n_estimators with evaluate_classifier(boosting_fit="device") AND makes the final fit with train_gradient_boosting_device; the model
+    file is a pickled GradientBoostingClassifier made by to_sklearn_boosting."""
+    _check_boosting_fit(boosting_fit, classifier_type)
     if forest_fit not in ("sklearn", "device") or (forest_fit == "device" and classifier_type not in _FOREST_FIT_KINDS):
         raise ValueError("forest_fit=%r with the classifier type %r" % (forest_fit, classifier_type))
     if svm_fit not in ("sklearn", "device") or (svm_fit == "device" and classifier_type not in _SVM_TYPES):
@@ -2099,7 +2361,7 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     features = kept
     best_param = evaluate_classifier(features, class_names, classifier_type, classifier_par, 1, list_of_ids, n_exp=-1,
                                      train_percentage=train_percentage, smote=use_smote, svm_fit=svm_fit,
-                                     forest_fit=forest_fit)
+                                     forest_fit=forest_fit, boosting_fit=boosting_fit)
     print("Selected params: {0:.5f}".format(best_param))
     features, labels = features_to_matrix(features)
     scaler = StandardScaler()
@@ -2115,6 +2377,8 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
                                                          kernel="rbf" if classifier_type == "svm_rbf" else "linear"))
         elif forest_fit == "device":
             classifier = to_sklearn_forest(train_forest_device(features, labels, int(best_param), kind=classifier_type), classifier_type)
+        elif boosting_fit == "device":
+            classifier = to_sklearn_boosting(train_gradient_boosting_device(features, labels, int(best_param)))
         else:
             classifier = _train_classifier(features, labels, classifier_type, best_param)
         with open(model_name, "wb") as fid:

@@ -1,13 +1,15 @@
 // Tree-ensemble classification (kernels_forest.hpp: audioTrainTest.classifier_wrapper for the "randomforest", "extratrees"
 // and "gradientboosting" models) and the fit of the first two (kernels_treefit.hpp: audioTrainTest.train_random_forest /
 // train_extra_trees and the forest half of evaluate_classifier) and of the forest regressor (train_random_forest_regression and
-// the "randomforest" sweep of evaluate_regression) -- own translation unit, see model_launch.hpp.
+// the "randomforest" sweep of evaluate_regression) and of the third (kernels_boost.hpp and the kFriedman instance of
+// tree_fit_kernel: train_gradient_boosting and the "gradientboosting" sweep) -- own translation unit, see model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
 #include "model_launch.hpp"
 #include "kernels_forest.hpp"
 #include "kernels_treefit.hpp"
+#include "kernels_boost.hpp"
 
 namespace paa {
 namespace launch {
@@ -91,6 +93,34 @@ int tree_fit_reg(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t st
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return -1;
     hipLaunchKernelGGL((tree_fit_kernel<kBest, kMse>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int tree_fit_boost(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream, bool configure) {
+    using namespace paa::treefit;
+    if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows) return -2;
+    if (n_tasks < 1 || !m.target || m.max_depth < 0 || (m.raw && (!m.boost || !m.label))) return -1;
+    // LDS: as the squared-error instance (96.5 KB at 8192 rows)
+    if (configure) {
+        int p2 = 2;
+        while (p2 < inbag_max) p2 <<= 1;
+        m.lds_keys = p2;
+        m.lds_rows = (inbag_max + 1) / 2 * 2;
+        m.hist_cols = kThreads;
+        m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4);
+    }
+    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
+    if (lds > 152 * 1024 || m.lds_rows < inbag_max) return -2;
+    if (configure && lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kFriedman>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL((tree_fit_kernel<kBest, kFriedman>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int boost_gradient(const boost::BoostDev &m, int n_jobs, int stage, hipStream_t stream) {
+    if (n_jobs < 1 || stage < 0) return -1;
+    hipLaunchKernelGGL(boost::boost_gradient_kernel, dim3((unsigned)n_jobs), dim3(boost::kThreads), 0, stream, m, stage);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -55,6 +55,23 @@
 // and every array equals scikit-learn's bit for bit; otherwise the sums may differ from scikit-learn's (which follow its introsort
 // and in-place partition) in the last places, and a tie that rounding breaks may fall the other way: a valid CART tree, not
 // scikit-learn's bits.
+//
+// K20, a boosting stage's tree (audioTrainTest.train_gradient_boosting and the "gradientboosting" sweep of evaluate_classifier,
+// audioTrainTest.py:181-199, :631-700): CRIT = kFriedman restates FriedmanMSE over MSE for GradientBoostingClassifier's
+// DecisionTreeRegressor(criterion="friedman_mse", max_depth = 3, max_features = None): the sums, the node value and every impurity are
+// kMse's, in kMse's fixed order; compile-time differences only:
+//  * the proxy at a candidate is diff diff / (w_left w_right) with diff = w_right sum_left - w_left sum_right, and the improvement
+//    of the chosen split diff diff / (w_left w_right weighted_n_node_samples) (never negative, so it closes no node);
+//  * a node is also a leaf when depth >= max_depth (the root has depth 0); the depth of a pending right child rides in the upper half of
+//    its stack record's parent word (a node id is below 2^15);
+//  * the leaf step (the sweep: TreeDev.raw and .boost set).  The targets of tree (job, class k) are the negative gradients r of that
+//    class at the start of the stage (kernels_boost.hpp), read per job row as kMse reads them.  When the builder closes a leaf, over
+//    the leaf's contiguous rows: num = (sum r) / n -- the node's sum_total, already formed in the fixed order -- times (K - 1) / K
+//    (one double, 1.0 for two classes); den = (sum p (1 - p)) / n with p = (y == k) - r, chunk-serial then the fixed-shape sum; value =
+//    0.0 when |den| < 1e-150, else num / den (_update_terminal_regions through np.average and _safe_divide); it replaces the leaf's
+//    mean, internal nodes keep theirs.  Then raw[row] += learning_rate * value for the leaf's rows: a row lies in exactly one leaf of
+//    the tree and the residuals were taken before the launch, so the update is in place and free of races.
+// The Gini and MSE instances keep their operations.
 #pragma once
 #include "device_common.hpp"
 #include "model_launch.hpp"
@@ -128,6 +145,7 @@ __device__ __forceinline__ double gini_of(const int *counts, int pitch, int K, d
 struct Control {
     int start, end, parent, is_left, n_known, node, leaf, done;
     int w_node, cur_f, n_found, best_f, n_left;
+    int closed;                                                     // (Friedman) the node just recorded is a leaf: read behind the loop's last barrier
     double best_thr, thr;
 };
 
@@ -249,7 +267,9 @@ __device__ __forceinline__ void block_scan_excl_d(double v, int w, double &ev, i
 
 template <int SPLITTER, int CRIT>
 __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
-    static_assert(CRIT == kGini || SPLITTER == kBest, "the MSE criterion is built for the best splitter");
+    static_assert(CRIT == kGini || SPLITTER == kBest, "the regression criteria are built for the best splitter");
+    constexpr bool kReg = CRIT != kGini;                            // real targets: the squared-error sums
+    constexpr bool kFried = CRIT == kFriedman;                      // ... with Friedman's proxy and improvement, a depth limit, the leaf step
     extern __shared__ unsigned long long dyn[];
     __shared__ Control ctl;
     __shared__ int tot[kMaxClasses], left[kMaxClasses], s_w[kThreads / kWave], red_p[kThreads];
@@ -266,8 +286,8 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
     unsigned short *feat = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(dyn) + m.lds_feat);     // behind the histogram
     unsigned short *cons = feat + n_dims;
     const float *xj = m.x32 + job.x_off;
-    const int *lab = CRIT == kGini ? m.label + job.off : nullptr;
-    const double *tgt = CRIT == kMse ? m.target + job.off : nullptr;
+    const int *lab = CRIT == kGini || (kFried && m.label) ? m.label + job.off : nullptr;
+    const double *tgt = !kReg ? nullptr : (kFried && m.boost) ? m.target + m.boost[blockIdx.x].off : m.target + job.off;
     const int *wt = task.w_off < 0 ? nullptr : m.weight + task.w_off;
 
     // the rows in the bag, in list order
@@ -288,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
     }
     // thread 0's builder state
     unsigned rng = task.seed;
-    int sp = 0, first = 1;
+    int sp = 0, first = 1, depth = 0;
     double impurity = 0.0, w_total = 0.0;
     StackRec *stack = m.stack + task.node_off;
     if (tid == 0) {
@@ -343,6 +363,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                 }
                 ctl.w_node = (int)wn;
                 ctl.leaf = n_node < 2 || impurity <= DBL_EPSILON;
+                if constexpr (kFried) ctl.leaf = ctl.leaf || depth >= m.max_depth;
             }
             __syncthreads();
         }
@@ -452,7 +473,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                     __syncthreads();                                // (the control block is rewritten next)
                     continue;
                 }
-                if constexpr (SPLITTER == kBest && CRIT == kMse) {
+                if constexpr (SPLITTER == kBest && kReg) {
                     // sum w y and the weight left of every candidate: per chunk of consecutive sorted rows, a prefix over the chunks,
                     // then every thread walks its own chunk (see the header for the order)
                     const int chunk = (n_node + kThreads - 1) / kThreads, c0 = min(n_node, tid * chunk), c1 = min(n_node, c0 + chunk);
@@ -473,7 +494,13 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                             const float v = value_of((unsigned)(kw >> 32));
                             if (p > 0 && !(v <= prev + kFeatureThreshold)) {
                                 const double dl = (double)wl, dr = (double)(w_node - wl), sr = sum_tot - sl;
-                                const double proxy = sl * sl / dl + sr * sr / dr;
+                                double proxy;
+                                if constexpr (kFried) {             // FriedmanMSE.proxy_impurity_improvement
+                                    const double diff = dr * sl - dl * sr;
+                                    proxy = diff * diff / (dl * dr);
+                                } else {
+                                    proxy = sl * sl / dl + sr * sr / dr;
+                                }
                                 if (proxy > bv) {
                                     bv = proxy;
                                     bp = p;
@@ -626,15 +653,21 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                 }
                 __syncthreads();
                 for (int i = tid; i < n_node; i += kThreads) rows[start + i] = tmp[i];
-                if constexpr (CRIT == kMse) block_sum3(sum_l, sq_l, wn_l);
+                if constexpr (kReg) block_sum3(sum_l, sq_l, wn_l);
                 if (tid == 0) {
                     if (n_left < 1 || n_left >= n_node) {
                         leaf = 1;                                   // (cannot happen with finite values)
-                    } else if constexpr (CRIT == kMse) {           // MSE.children_impurity
+                    } else if constexpr (kReg) {                   // MSE.children_impurity
                         const double dl = wn_l, dn = (double)w_node, dr = dn - dl, sum_r = sum_tot - sum_l;
                         imp_l = sq_l / dl - (sum_l / dl) * (sum_l / dl);
                         imp_r = (sq_tot - sq_l) / dr - (sum_r / dr) * (sum_r / dr);
-                        const double improvement = (dn / w_total) * (impurity - (dr / dn * imp_r) - (dl / dn * imp_l));
+                        double improvement;
+                        if constexpr (kFried) {                     // FriedmanMSE.impurity_improvement (one output)
+                            const double diff = dr * sum_l - dl * sum_r;
+                            improvement = diff * diff / (dl * dr * dn);
+                        } else {
+                            improvement = (dn / w_total) * (impurity - (dr / dn * imp_r) - (dl / dn * imp_l));
+                        }
                         leaf = improvement + DBL_EPSILON < 0.0;
                     } else {
                         int wl = 0;
@@ -681,7 +714,7 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
             if (!leaf) {
                 stack[sp].start = start + n_left;
                 stack[sp].end = end;
-                stack[sp].parent = node;
+                stack[sp].parent = kFried ? node | ((depth + 1) << 16) : node;     // (a node id is below 2^15)
                 stack[sp].n_known = n_total;
                 stack[sp].impurity = imp_r;
                 ++sp;
@@ -690,11 +723,13 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                 ctl.is_left = 1;
                 ctl.n_known = n_total;
                 impurity = imp_l;
+                ++depth;
             } else if (sp > 0) {
                 --sp;
                 ctl.start = stack[sp].start;
                 ctl.end = stack[sp].end;
-                ctl.parent = stack[sp].parent;
+                ctl.parent = kFried ? stack[sp].parent & 0xffff : stack[sp].parent;
+                depth = kFried ? stack[sp].parent >> 16 : 0;
                 ctl.is_left = 0;
                 ctl.n_known = stack[sp].n_known;
                 impurity = stack[sp].impurity;
@@ -703,8 +738,33 @@ __global__ __launch_bounds__(kThreads) void tree_fit_kernel(TreeDev m) {
                 m.node_count[blockIdx.x] = node + 1;
             }
             ctl.node = node + 1;
+            if constexpr (kFried) ctl.closed = leaf;                // (a field of its own: ctl.leaf is read by the other waves without a barrier after this)
         }
         __syncthreads();
+        if constexpr (kFried) {
+            // _update_terminal_regions of the closed leaf: one Newton step over its rows, then the raw predictions of those rows
+            if (m.raw != nullptr && ctl.closed) {                   // (written before the barrier above; next written after the leaf step's own barriers)
+                const BoostTask bt = m.boost[blockIdx.x];
+                const int chunk = (n_node + kThreads - 1) / kThreads, c0 = min(n_node, tid * chunk), c1 = min(n_node, c0 + chunk);
+                double den = 0.0, z0 = 0.0, z1 = 0.0;
+                for (int i = c0; i < c1; ++i) {
+                    const int r = word_row(rows[start + i]);
+                    const double p = (lab[r] == bt.cls ? 1.0 : 0.0) - tgt[r];
+                    den = den + p * (1.0 - p);
+                }
+                block_sum3(den, z0, z1);
+                double num = sum_tot / (double)n_node;
+                num = num * bt.factor;                              // (K - 1) / K; 1.0 for the two-class loss
+                den = den / (double)n_node;
+                const double value = fabs(den) < 1e-150 ? 0.0 : num / den;
+                const double step = m.learning_rate * value;
+                if (tid == 0) m.value[task.val_off + node] = value;
+                for (int i = start + tid; i < end; i += kThreads) {
+                    const long long at = bt.off + word_row(rows[i]);
+                    m.raw[at] = m.raw[at] + step;
+                }
+            }
+        }
         if (ctl.done) break;
     }
 }

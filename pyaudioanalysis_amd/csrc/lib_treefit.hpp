@@ -65,6 +65,7 @@ struct TreeBatch {
     int64_t total_nodes = 0, total_values = 0;
     int inbag_max = 0, k_max = 0, n_max = 0;
     bool any_flag = false;
+    int max_depth = -1;                       // >= 0 (with `target`): the trees of a boosting stage, Friedman's criterion under that depth
     DevBlock in, work;
     treefit::TreeDev dev{};
     // the offsets of the outputs: tree after tree, cap nodes and cap * k values each
@@ -143,7 +144,9 @@ struct TreeBatch {
         HIP_TRY(hipStreamSynchronize(cs()));
         for (int f : flags) any_flag |= f != 0;
         if (any_flag) return PAA_OK;              // a NaN or an infinity: nothing is fitted, the caller reports it
-        const int lrc = target ? launch::tree_fit_reg(dev, (int)n_t, inbag_max, cs()) : launch::tree_fit(dev, (int)n_t, splitter, inbag_max, k_max, cs());
+        dev.max_depth = max_depth;
+        const int lrc = target ? (max_depth >= 0 ? launch::tree_fit_boost(dev, (int)n_t, inbag_max, cs()) : launch::tree_fit_reg(dev, (int)n_t, inbag_max, cs()))
+                               : launch::tree_fit(dev, (int)n_t, splitter, inbag_max, k_max, cs());
         if (lrc == -2) return fail(PAA_ERR_UNSUPPORTED, "the trees exceed the kernel's limits");
         if (lrc) return fail(PAA_ERR_HIP, "tree fit launch failed: %s", hipGetErrorString(hipGetLastError()));
         return PAA_OK;
@@ -154,7 +157,7 @@ struct TreeBatch {
 static int tree_fit_tasks(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off, const int32_t *job_idx,
                           const int32_t *job_label, const int32_t *job_k, const double *job_target, const double *mean,
                           const double *std, int n_tasks, const int32_t *task_job, const int64_t *task_seed,
-                          const int32_t *task_weight, int splitter, int64_t total_nodes, int64_t total_values, int32_t *job_flags,
+                          const int32_t *task_weight, int splitter, int max_depth, int64_t total_nodes, int64_t total_values, int32_t *job_flags,
                           int32_t *node_count, int32_t *children_left, int32_t *children_right, int32_t *feature, double *threshold,
                           double *impurity, int32_t *n_node_samples, double *weighted_n_node_samples, uint8_t *missing_go_to_left,
                           double *value) {
@@ -172,6 +175,7 @@ static int tree_fit_tasks(const double *X, int64_t n_samples, int n_dims, int n_
     const int64_t rows = job_off[n_jobs];
     TreeBatch b;
     b.dev.n_dims = n_dims;
+    b.max_depth = max_depth;
     b.jobs.resize(n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         const int64_t n = job_off[j + 1] - job_off[j];
@@ -230,7 +234,7 @@ extern "C" int paa_tree_fit_tasks_f64(const double *X, int64_t n_samples, int n_
                                       double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value) {
     if (!job_label || !job_k) return fail(PAA_ERR_ARG, "null argument");
     return tree_fit_tasks(X, n_samples, n_dims, n_jobs, job_off, job_idx, job_label, job_k, nullptr, mean, std, n_tasks, task_job, task_seed,
-                          task_weight, splitter, total_nodes, total_values, job_flags, node_count, children_left, children_right, feature,
+                          task_weight, splitter, -1, total_nodes, total_values, job_flags, node_count, children_left, children_right, feature,
                           threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value);
 }
 extern "C" int paa_tree_fit_reg_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
@@ -241,7 +245,19 @@ extern "C" int paa_tree_fit_reg_tasks_f64(const double *X, int64_t n_samples, in
                                           double *impurity, int32_t *n_node_samples, double *weighted_n_node_samples,
                                           uint8_t *missing_go_to_left, double *value) {
     return tree_fit_tasks(X, n_samples, n_dims, n_jobs, job_off, job_idx, nullptr, nullptr, job_target, mean, std, n_tasks, task_job,
-                          task_seed, task_weight, treefit::kBest, total_nodes, total_values, job_flags, node_count, children_left,
+                          task_seed, task_weight, treefit::kBest, -1, total_nodes, total_values, job_flags, node_count, children_left,
+                          children_right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value);
+}
+extern "C" int paa_tree_fit_boost_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_jobs, const int64_t *job_off,
+                                            const int32_t *job_idx, const double *job_target, const double *mean, const double *std,
+                                            int n_tasks, const int32_t *task_job, const int64_t *task_seed, const int32_t *task_weight,
+                                            int max_depth, int64_t total_nodes, int64_t total_values, int32_t *job_flags,
+                                            int32_t *node_count, int32_t *children_left, int32_t *children_right, int32_t *feature,
+                                            double *threshold, double *impurity, int32_t *n_node_samples,
+                                            double *weighted_n_node_samples, uint8_t *missing_go_to_left, double *value) {
+    if (max_depth < 1 || max_depth > treefit::kMaxRows) return fail(PAA_ERR_ARG, "max_depth = %d: 1 .. %d", max_depth, treefit::kMaxRows);
+    return tree_fit_tasks(X, n_samples, n_dims, n_jobs, job_off, job_idx, nullptr, nullptr, job_target, mean, std, n_tasks, task_job,
+                          task_seed, task_weight, treefit::kBest, max_depth, total_nodes, total_values, job_flags, node_count, children_left,
                           children_right, feature, threshold, impurity, n_node_samples, weighted_n_node_samples, missing_go_to_left, value);
 }
 

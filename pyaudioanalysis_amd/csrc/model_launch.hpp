@@ -181,7 +181,8 @@ constexpr int kMaxDims = forest::kMaxDims;
 constexpr int kMaxWeight = 8191;          // a row's integer weight (0: out of the bag)
 constexpr long long kChunkBytes = 1LL << 30;      // device scratch of one chunk of a sweep's trees (a job is never cut)
 enum Splitter { kBest = 0, kRandom = 1 };
-enum Criterion { kGini = 0, kMse = 1 };   // classification; regression (squared error, one output, best splitter)
+enum Criterion { kGini = 0, kMse = 1, kFriedman = 2 };    // classification; regression (squared error, one output, best splitter);
+                                                          // a boosting stage's tree (Friedman's improvement over the squared-error sums, a depth limit)
 // a job: the rows idx[off .. off + n - 1] of the sample matrix, their class indices label[off ..] in 0 .. k - 1, standardised
 // with row `stat` of mean / scale; its float32 copy x32[x_off ..] is feature-major [n_dims][n]
 struct TreeJob {
@@ -200,6 +201,13 @@ struct TreeTask {
 struct StackRec {
     int start, end, parent, n_known;
     double impurity;
+};
+// a boosting stage's tree (kFriedman, the sweep): its residuals are target[off .. off + n - 1] and the raw predictions it steps
+// raw[off ..], by the job's rows; cls: the class whose tree it is (the two-class loss: 1); factor: (K - 1) / K, 1.0 for two classes
+struct BoostTask {
+    long long off;
+    double factor;
+    int cls, pad;
 };
 // a batch of trees: device pointers.  The scikit-learn arrays (children_left .. missing) may be null: the sweep keeps the packed
 // nodes and the values only
@@ -223,8 +231,29 @@ struct TreeDev {
     int n_dims, max_features;
     int lds_keys, lds_rows, hist_cols, lds_feat;      // LDS geometry of the launch: 8-byte sort words, row words, columns of the class
                                                       // histogram, byte offset of the feature arrays
+    // kFriedman: a node at max_depth is a leaf (the root has depth 0).  With boost / raw (the sweep; null: the builder alone) task t
+    // reads its targets through boost[t], and a closed leaf takes its Newton value and adds learning_rate * value to its rows of raw
+    int max_depth, pad;
+    const BoostTask *boost;
+    double *raw;
+    double learning_rate;
 };
 }  // namespace treefit
+namespace boost {
+constexpr int kThreads = 256;             // kernels_boost.hpp: one workgroup per job
+// a job of a boosting sweep: its rows' class indices label[off .. off + n - 1] in 0 .. k - 1, its raw predictions and residuals
+// [k_out][n] at r_off (k_out = 1 for two classes, else k), its initial raw score init[init_off ..], its losses loss[loss_off + stage]
+struct BoostJob {
+    long long off, r_off, loss_off, init_off;
+    int n, k, n_stages, pad;
+};
+struct BoostDev {
+    const BoostJob *jobs;
+    const int *label;
+    const double *init;
+    double *raw, *resid, *loss;
+};
+}  // namespace boost
 namespace hmm {
 constexpr int kMaxStates = 32;
 constexpr int kMaxDims = 256;
@@ -315,6 +344,13 @@ int tree_prep(const treefit::TreeDev &m, int n_jobs, int n_max, hipStream_t stre
 int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int k_max, hipStream_t stream);
 // ... the same for regression trees (treefit::kMse over the best splitter; m.target in place of m.label, every job's k is 1)
 int tree_fit_reg(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream);
+// ... the same for the trees of boosting stages (treefit::kFriedman over the best splitter, m.max_depth; tasks, boost records and
+// node counts are read from m's pointers as given, so a stage launches at its first task).  configure: size the LDS for inbag_max and
+// write the geometry into m; false for the later stages of a chunk, whose geometry m already holds
+int tree_fit_boost(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream, bool configure = true);
+// kernels_boost.hpp: for each of the first n_jobs jobs, at `stage`: the mean loss of the raw predictions (stage > 0: to loss[stage -
+// 1]) and, while stage < n_stages, the negative gradients of the stage's trees (stage 0 writes the initial raw predictions first)
+int boost_gradient(const boost::BoostDev &m, int n_jobs, int stage, hipStream_t stream);
 // ... out [n_dims][ld] = the rows d_rows [n_rows] of X [..][n_dims], feature-major as the traversal kernel reads them
 int tree_gather(const double *d_X, int n_dims, const int *d_rows, long long n_rows, double *d_out, long long ld, hipStream_t stream);
 // ... threads per workgroup, the row limit, the class limit, the dims limit, the weight limit, the chunk size in MiB
