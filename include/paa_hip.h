@@ -411,6 +411,55 @@ int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const 
  * launch, dims                                                                                                        */
 int paa_debug_smo_geometry(int32_t *out6);
 
+/* ---- silence removal of a batch of clips (audioSegmentation.py:672-815), on the device end to end ---------------------------------
+ * paa_silence_batch_i16 / _f64 -- the clips lie back to back in `packed` (clip c: samples offsets[c] .. offsets[c + 1] - 1), one
+ * sampling rate, window and step (in samples) for all.  Per chunk of whole clips (the device scratch of a chunk stays within 1 GiB,
+ * or within chunk_bytes when that is > 0 and smaller; nothing depends on the chunking):
+ *   1. the short-term matrices [68][T_c] of the batched plan, which stay in device memory;
+ *   2. per clip, tenth = T / 10: quiet_limit = mean of the tenth smallest energies (row 1) + 1e-15, loud_limit = mean of the tenth
+ *      largest without one instance of the maximum + 1e-15; the flags energy <= quiet_limit and energy >= loud_limit, their counts;
+ *   3. the training rows of every clip -- its quiet frames in frame order, then its loud frames in frame order -- in one matrix
+ *      [rows][68], with the clip's scaler: mean and sqrt(var) as NumPy's axis-0 reductions give them, a scale below 10 eps set to 1;
+ *   4. per clip SVC(C = 1, linear, probability = True).fit over its standardised rows (quiet: class 0) with libsvm's folds for
+ *      seeds[c], as paa_svc_fit_proba_f64 fits one job;
+ *   5. the onset probability of every frame (paa_svm_binary_proba_f64's arithmetic with the fit folded into one weight vector),
+ *      smoothed by a box of widths[c] frames over the sequence continued by point reflection (untouched for a width < 3);
+ *   6. threshold = ((1 - weights[c]) * lowest tenth).mean() + weights[c] * highest tenth.mean() of the smoothed values and the flags
+ *      prob > threshold.
+ * Errors name the clip: PAA_ERR_ARG for a clip of fewer than 20 frames or fewer than widths[c] (before any device work) and for an
+ * empty quiet or loud set, PAA_ERR_UNSUPPORTED for more than 8192 quiet + loud rows (both after step 2 of every chunk and before
+ * any fit).
+ * Outputs, host arrays.  Per frame, clip after clip: quiet, loud, active (0 / 1), raw (step 5 before smoothing), prob.  Per clip:
+ * limits [2], counts [2], mean / scale [68], rho, prob_a, prob_b, threshold, n_sv, iterations / status [6] (slot 0: the full fit,
+ * 1..5: the folds), sig_iterations, sig_stop.  Per training row, clip c's rows from row_cap_off[c] (room for min(2 T_c, 8192) rows
+ * is enough): src (the row's frame) and alpha_y.  stage_ms [6] (may be null; the stream is drained between the stages when it is
+ * not): milliseconds of features, selection, training sets, fits, probability with threshold, copy-back.
+ *
+ * paa_onset_training_sets_f64 -- steps 2 and 3 for short-term matrices in host memory, [n_dims][frames[c]] blocks back to back
+ * (frames[c] >= 20; row 1 is the energy).  src / X [rows][n_dims] receive the rows of all clips back to back (row_capacity: the
+ * room in rows; the sum of 2 frames[c] is always enough); a clip without rows has mean 0 and scale 1.
+ * paa_onset_activity_f64 -- steps 5 and 6 for such matrices and one linear model per clip: w / mean / scale [n_clips][n_dims],
+ * intercept, prob_a, prob_b [n_clips]; dec = <w, (x - mean) / scale> + intercept is scikit-learn's decision_function.            */
+int paa_silence_batch_i16(const int16_t *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                          const int32_t *widths, const double *weights, const int64_t *seeds, int64_t chunk_bytes,
+                          const int64_t *row_cap_off, uint8_t *quiet, uint8_t *loud, uint8_t *active, double *raw, double *prob,
+                          double *limits, int32_t *counts, double *mean, double *scale, int32_t *src, double *alpha_y, double *rho,
+                          double *prob_a, double *prob_b, double *threshold, int32_t *n_sv, int32_t *iterations, int32_t *status,
+                          int32_t *sig_iterations, int32_t *sig_stop, double *stage_ms);
+int paa_silence_batch_f64(const double *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                          const int32_t *widths, const double *weights, const int64_t *seeds, int64_t chunk_bytes,
+                          const int64_t *row_cap_off, uint8_t *quiet, uint8_t *loud, uint8_t *active, double *raw, double *prob,
+                          double *limits, int32_t *counts, double *mean, double *scale, int32_t *src, double *alpha_y, double *rho,
+                          double *prob_a, double *prob_b, double *threshold, int32_t *n_sv, int32_t *iterations, int32_t *status,
+                          int32_t *sig_iterations, int32_t *sig_stop, double *stage_ms);
+int paa_onset_training_sets_f64(const double *feats, const int32_t *frames, int n_clips, int n_dims, int64_t chunk_bytes,
+                                int64_t row_capacity, double *limits, int32_t *counts, uint8_t *quiet, uint8_t *loud, int32_t *src,
+                                double *X, double *mean, double *scale);
+int paa_onset_activity_f64(const double *feats, const int32_t *frames, int n_clips, int n_dims, const double *w,
+                           const double *intercept, const double *prob_a, const double *prob_b, const double *mean,
+                           const double *scale, const int32_t *widths, const double *weights, int64_t chunk_bytes, double *raw,
+                           double *prob, double *threshold, uint8_t *active);
+
 /* ---- the SVR half of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855 with train_svm_regression :222-226) -----------
  * For "svm" / "svm_rbf" evaluate_regression fits sklearn.svm.SVR(C, kernel) (epsilon 0.1, gamma 'scale') once per split: libsvm's
  * solve_epsilon_svr hands Solver::Solve a dual of 2 n variables over n rows -- variable v stands for row v mod n with the sign +1

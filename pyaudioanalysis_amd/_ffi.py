@@ -20,6 +20,11 @@ c_i16p = C.POINTER(C.c_int16)
 c_f64p = C.POINTER(C.c_double)
 c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
+c_u8p = C.POINTER(C.c_uint8)
+# paa_silence_batch_*, after the samples: offsets .. row_cap_off, then the outputs in the order of paa_hip.h
+_SILENCE_BATCH_ARGS = [c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int, c_i32p, c_f64p, c_i64p, C.c_int64, c_i64p, c_u8p, c_u8p, c_u8p,
+                       c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p,
+                       c_i32p, c_i32p, c_i32p, c_f64p]
 
 
 class HipLibraryError(RuntimeError):
@@ -129,6 +134,12 @@ _SIGNATURES = {
                                         C.c_int, C.c_double, C.c_int, C.c_int, c_i64p, C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p,
                                         c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p]),
     "paa_debug_smo_geometry": (C.c_int, [c_i32p]),
+    "paa_silence_batch_i16": (C.c_int, [c_i16p] + _SILENCE_BATCH_ARGS),
+    "paa_silence_batch_f64": (C.c_int, [c_f64p] + _SILENCE_BATCH_ARGS),
+    "paa_onset_training_sets_f64": (C.c_int, [c_f64p, c_i32p, C.c_int, C.c_int, C.c_int64, C.c_int64, c_f64p, c_i32p, c_u8p, c_u8p, c_i32p,
+                                              c_f64p, c_f64p, c_f64p]),
+    "paa_onset_activity_f64": (C.c_int, [c_f64p, c_i32p, C.c_int, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_f64p,
+                                         C.c_int64, c_f64p, c_f64p, c_f64p, c_u8p]),
     "paa_svr_tasks_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p,
                                     C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p, c_i32p]),
     "paa_svr_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
@@ -309,6 +320,10 @@ def as_i32p(a):
 
 def as_i64p(a):
     return a.ctypes.data_as(c_i64p)
+
+
+def as_u8p(a):
+    return a.ctypes.data_as(c_u8p)
 
 
 def classify_signal(signal):

@@ -13,7 +13,10 @@ features and the similarity matrix in HBM: only the filtered matrix it returns c
 `silence_removal` trains its two-class SVM exactly where the reference does -- with scikit-learn (:739,
 audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744-748) by one kernel over all frames
 (svm_onset_probability); with svm_fit="device" the SVM is trained on the GPU instead (audioTrainTest.train_svm_device: the full
-fit, libsvm's five cross-validation fits and the sigmoid fit) and scikit-learn is not needed.  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
+fit, libsvm's five cross-validation fits and the sigmoid fit) and scikit-learn is not needed.  silence_removal_batch /
+silence_removal_files do that for many clips in one call, on the GPU end to end: energy selection, training sets and scalers, the
+fits of all clips as one solver batch, probabilities, smoothing and thresholds (onset_training_sets and onset_activity give the
+stages around the fit alone).  The HMM segmenter (train_hmm_compute_statistics, train_hmm_from_file / _from_directory, save_hmm,
 hmm_segmentation, :287-492) runs on the GPU as well: class GaussianHmm stands in for hmmlearn's GaussianHMM (hmmlearn is not
 needed, also not to read a model file the reference wrote).  Speaker diarization (speaker_diarization, diarize_features,
 evaluate_speaker_diarization, speaker_diarization_evaluation, :251-284, :815-1090) runs its standardisation, k-means sweep and
@@ -264,6 +267,266 @@ def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, w
     if plot:
         _plot_segments(mono, sampling_rate, prob, st_step, seg_limits)
     return seg_limits
+
+
+# ---------------------------------------------------------------------------------------------------------
+# silence removal of many clips in one call (kernels_onset.hpp, lib_onset.hpp)
+# ---------------------------------------------------------------------------------------------------------
+ONSET_MIN_FRAMES = 20      # int(T / 10) >= 2: the reference's ranked[-tenth:-1] is not empty
+
+
+def _per_clip(value, n, name):
+    """a scalar or one value per clip -> float64 [n]"""
+    a = np.asarray(value, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(n, float(a))
+    if a.shape != (n,):
+        raise ValueError("%s: a scalar or one value per clip (%d clips, shape %s)" % (name, n, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def _batch_seeds(random_state, n):
+    """libsvm's random_seed of n fits, one draw each in clip order: None draws from NumPy's global state exactly as
+    audioTrainTest._libsvm_seed does in n calls, an int makes ONE RandomState that is drawn from n times, a RandomState is
+    used as is."""
+    from . import audioTrainTest as aT
+    if random_state is None:
+        return [aT._libsvm_seed(None) for _ in range(n)]
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    return [aT._libsvm_seed(rs) for _ in range(n)]
+
+
+def _onset_plan(lengths, sampling_rate, st_win, st_step, smooth_window, weight):
+    """The argument half of silence_removal_batch, without the device: (window, step, frames, widths, weights) or the
+    ValueError of the first clip that cannot be served."""
+    n = len(lengths)
+    window, step = int(st_win * sampling_rate), int(st_step * sampling_rate)      # ShortTermFeatures.py:563-564
+    if window < 2 or step < 1:
+        raise ValueError("st_win = %r, st_step = %r at %r Hz: a window of %d and a step of %d samples" % (st_win, st_step, sampling_rate, window, step))
+    smooth = _per_clip(smooth_window, n, "smooth_window")
+    weights = _per_clip(weight, n, "weight")
+    weights = np.where((weights > 0) & (weights < 1), weights, np.minimum(np.maximum(weights, 0.01), 0.99))   # :697-700
+    frames = np.array([(int(m) - window) // step + 1 if int(m) >= window else 0 for m in lengths], dtype=np.int64)
+    widths = np.array([int(s / st_step) for s in smooth], dtype=np.int32)          # smooth_moving_avg's int(window)
+    for c in range(n):
+        if frames[c] < ONSET_MIN_FRAMES:
+            raise ValueError("clip %d: %d short-term frames: at least %d are needed (the mean of the loudest tenth leaves its "
+                             "maximum out)" % (c, frames[c], ONSET_MIN_FRAMES))
+        if frames[c] < widths[c]:
+            raise ValueError("clip %d: Input vector needs to be bigger than window size. (%d frames, a smoothing window of %d)"
+                             % (c, frames[c], widths[c]))
+    return window, step, frames, widths, np.ascontiguousarray(weights, dtype=np.float64)
+
+
+def _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms):
+    """The call of paa_silence_batch_* for clips of one sample type; returns the per-clip detail records.  The library's refusals
+    after the selection (an empty set: ValueError; more than 8192 rows: NotImplementedError) name the clip themselves."""
+    from . import audioTrainTest as aT
+    n, D = len(clips), 68
+    lens = np.array([c.shape[0] for c in clips], dtype=np.int64)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    packed = np.concatenate(clips) if n > 1 else clips[0]
+    frame_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(frames, out=frame_off[1:])
+    cap_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.minimum(2 * frames, aT.SMO_MAX_ROWS), out=cap_off[1:])
+    nf, nr = int(frame_off[-1]), int(cap_off[-1])
+    quiet, loud, active = (np.zeros(nf, dtype=np.uint8) for _ in range(3))
+    raw, prob = np.zeros(nf), np.zeros(nf)
+    limits, counts = np.zeros((n, 2)), np.zeros((n, 2), dtype=np.int32)
+    mean, scale = np.zeros((n, D)), np.zeros((n, D))
+    src, alpha_y = np.zeros(nr, dtype=np.int32), np.zeros(nr)
+    rho, prob_a, prob_b, thr = (np.zeros(n) for _ in range(4))
+    n_sv, sig_it, sig_stop = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    iterations, status = np.zeros((n, 6), dtype=np.int32), np.zeros((n, 6), dtype=np.int32)
+    seed = np.ascontiguousarray(seeds, dtype=np.int64)
+    lib = _ffi.lib()
+    fn = lib.paa_silence_batch_i16 if as_i16 else lib.paa_silence_batch_f64
+    rc = fn(_ffi.as_i16p(packed) if as_i16 else _ffi.as_f64p(packed), _ffi.as_i64p(offsets), n, float(sampling_rate), window, step,
+            _ffi.as_i32p(widths), _ffi.as_f64p(weights), _ffi.as_i64p(seed), int(chunk_bytes or 0), _ffi.as_i64p(cap_off),
+            _ffi.as_u8p(quiet), _ffi.as_u8p(loud), _ffi.as_u8p(active), _ffi.as_f64p(raw), _ffi.as_f64p(prob), _ffi.as_f64p(limits),
+            _ffi.as_i32p(counts), _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_i32p(src), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
+            _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b), _ffi.as_f64p(thr), _ffi.as_i32p(n_sv), _ffi.as_i32p(iterations),
+            _ffi.as_i32p(status), _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(stage_ms) if stage_ms is not None else None)
+    _ffi.check(rc)
+    aT._warn_not_converged(status.reshape(-1), 10 ** 7)
+    out = []
+    for c in range(n):
+        f0, f1, r0 = int(frame_off[c]), int(frame_off[c + 1]), int(cap_off[c])
+        nq, nl = int(counts[c, 0]), int(counts[c, 1])
+        out.append(dict(quiet_idx=src[r0:r0 + nq].astype(np.int64), loud_idx=src[r0 + nq:r0 + nq + nl].astype(np.int64),
+                        quiet_limit=float(limits[c, 0]), loud_limit=float(limits[c, 1]), mean=mean[c].copy(), scale=scale[c].copy(),
+                        seed=int(seed[c]), alpha_y=alpha_y[r0:r0 + nq + nl].copy(), rho=float(rho[c]), prob_a=float(prob_a[c]),
+                        prob_b=float(prob_b[c]), n_sv=int(n_sv[c]), status=status[c].copy(), iterations=iterations[c].copy(),
+                        sigmoid_iterations=int(sig_it[c]), sigmoid_stop=int(sig_stop[c]), raw_prob=raw[f0:f1].copy(),
+                        prob=prob[f0:f1].copy(), threshold=float(thr[c]), active=np.flatnonzero(active[f0:f1])))
+    return out
+
+
+def _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weight, seeds, chunk_bytes, stage_ms=None):
+    """silence_removal_batch with the seeds given (a callable that draws them once the arguments have passed).  The whole batch is
+    ONE library call, so that every refusal that follows the selection comes before any fit: int16 clips travel as int16; if
+    any clip has another dtype the whole batch goes through np.double (feature_extraction_batch's rule).  Returns the per-clip
+    detail records in clip order."""
+    monos = [np.asarray(audioBasicIO.stereo_to_mono(s)) for s in signals]
+    for c, m in enumerate(monos):
+        if m.ndim != 1:
+            raise ValueError("clip %d: a signal of %d dimensions (mono, or two channels)" % (c, m.ndim))
+    window, step, frames, widths, weights = _onset_plan([m.shape[0] for m in monos], sampling_rate, st_win, st_step, smooth_window, weight)
+    seeds = seeds(len(monos)) if callable(seeds) else list(seeds)
+    as_i16 = all(m.dtype == np.int16 for m in monos)
+    clips = [np.ascontiguousarray(m if as_i16 else np.double(m)) for m in monos]
+    return _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms)
+
+
+def silence_removal_batch(signals, sampling_rate, st_win, st_step, smooth_window=0.5, weight=0.5, *, random_state=None,
+                          return_details=False, chunk_bytes=None):
+    """silence_removal(.., svm_fit="device") for a list of clips of ONE sampling rate, on the GPU end to end: the short-term
+    matrices of the batched plan stay in device memory, and energy selection, training sets with their scalers, the SVM fits
+    of all clips (one solver batch), the per-frame probabilities, smoothing and thresholds are kernels over the whole batch.
+    Returns one list of [start, end] segments in seconds per clip, as silence_removal gives them; scikit-learn is not needed.
+
+    signals: the clips (each through audioBasicIO.stereo_to_mono); st_win, st_step in seconds, one pair per call;
+    smooth_window and weight: a scalar, or one value per clip (weight is pulled into 0.01 .. 0.99 as in the single call).
+    random_state: None draws one seed per clip from NumPy's global state -- clip i sees the seed that the i-th call of a loop
+    of silence_removal(.., svm_fit="device") would see; an int makes ONE RandomState(int) that is drawn from once per clip; a
+    RandomState is used as is.  The seeds are drawn on the host in clip order before any device work, after the arguments
+    have passed.  int16 clips travel as int16; if any clip has another dtype the whole batch goes through np.double.  return_details=True returns (segments, details): per clip a dict of quiet_idx, loud_idx, quiet_limit,
+    loud_limit, mean, scale, seed, alpha_y (over the quiet rows, then the loud rows), rho, prob_a, prob_b, n_sv, status and
+    iterations [6] (the full fit, the five folds), sigmoid_iterations, sigmoid_stop, raw_prob, prob (smoothed), threshold and
+    active.  chunk_bytes: a bound below the library's 1 GiB for the device scratch of one chunk of clips (tests); no result
+    depends on it.
+
+    ValueError names the clip: fewer than 20 frames, or fewer than int(smooth_window / st_step) (both before the device is
+    touched); an empty quiet or loud set (after the selection, before any fit).  NotImplementedError for a clip whose quiet
+    and loud rows exceed the solver's 8192."""
+    signals = list(signals)
+    if not signals:
+        return ([], []) if return_details else []
+    details = _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weight,
+                             lambda n: _batch_seeds(random_state, n), chunk_bytes)
+    segments = [_onset_segments(d["active"], st_step) for d in details]
+    return (segments, details) if return_details else segments
+
+
+def _as_path_index(exc, ids):
+    """the refusal of clip k of a group, renamed to the path it came from"""
+    msg = str(exc)
+    if not msg.startswith("clip "):
+        return exc
+    head, _, rest = msg.partition(":")
+    return type(exc)("clip %d:%s" % (ids[int(head[5:])], rest))
+
+
+def silence_removal_files(paths, st_win, st_step, smooth_window=0.5, weight=0.5, *, random_state=None):
+    """silence_removal_batch over audio files: they are read and grouped by sampling rate, one device batch per rate; the
+    seeds are drawn in path order and the segment lists come back in path order.  smooth_window and weight: a scalar or one
+    value per path.  A file that cannot be read raises ValueError naming its index.  As in silence_removal_batch the arguments
+    of EVERY file are checked before a seed is drawn or the device is touched; a refusal that follows the selection comes before
+    the fits of its own rate's batch (the batches of other rates may have run)."""
+    paths = list(paths)
+    n = len(paths)
+    smooth, weights = _per_clip(smooth_window, n, "smooth_window"), _per_clip(weight, n, "weight")
+    groups = {}
+    for i, path in enumerate(paths):
+        fs, sig = audioBasicIO.read_audio_file(path)
+        if fs <= 0:
+            raise ValueError("file %d (%s) cannot be read" % (i, path))
+        groups.setdefault(fs, []).append((i, np.asarray(audioBasicIO.stereo_to_mono(sig))))
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        try:
+            _onset_plan([s.shape[0] for _, s in members], fs, st_win, st_step, smooth[ids], weights[ids])
+        except ValueError as exc:
+            raise _as_path_index(exc, ids)
+    seeds = _batch_seeds(random_state, n)
+    out = [None] * n
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        try:
+            details = _silence_batch([s for _, s in members], fs, st_win, st_step, smooth[ids], weights[ids], [seeds[i] for i in ids], None)
+        except (ValueError, NotImplementedError) as exc:
+            raise _as_path_index(exc, ids)
+        for i, d in zip(ids, details):
+            out[i] = _onset_segments(d["active"], st_step)
+    return out
+
+
+def _stack_matrices(st_feats_list):
+    """list of (n_dims x T_c) matrices -> (packed float64, frames int32 [n], n_dims)"""
+    mats = [np.ascontiguousarray(np.asarray(f, dtype=np.float64)) for f in st_feats_list]
+    if not mats:
+        raise ValueError("need at least one short-term matrix")
+    if any(m.ndim != 2 for m in mats) or any(m.shape[0] != mats[0].shape[0] for m in mats):
+        raise ValueError("the short-term matrices must be (n_dims x frames) with one n_dims")
+    frames = np.array([m.shape[1] for m in mats], dtype=np.int32)
+    for c, t in enumerate(frames):
+        if t < ONSET_MIN_FRAMES:
+            raise ValueError("clip %d: %d short-term frames: at least %d are needed" % (c, t, ONSET_MIN_FRAMES))
+    packed = np.concatenate([m.reshape(-1) for m in mats]) if len(mats) > 1 else mats[0].reshape(-1)
+    return packed, frames, mats[0].shape[0]
+
+
+def onset_training_sets(st_feats_list, *, chunk_bytes=None):
+    """Stages 1 and 2 of silence_removal_batch for short-term matrices in host memory (onset_select_kernel,
+    onset_gather_kernel): per clip a dict of quiet_limit, loud_limit, quiet_idx, loud_idx (frames with energy <= / >= the
+    limit; a frame may be in both), features (np.vstack([quiet.T, loud.T]) of _energy_extremes), mean and scale (NumPy's
+    features.mean(axis=0) and sqrt(var(axis=0)) bit for bit, a scale below 10 eps set to 1).  An empty set is reported, not
+    refused (silence_removal_batch raises for it)."""
+    packed, frames, D = _stack_matrices(st_feats_list)
+    n, nf = len(frames), int(frames.sum())
+    cap = 2 * nf
+    limits, counts = np.zeros((n, 2)), np.zeros((n, 2), dtype=np.int32)
+    quiet, loud = np.zeros(nf, dtype=np.uint8), np.zeros(nf, dtype=np.uint8)
+    src, X = np.zeros(cap, dtype=np.int32), _ffi.result_array((cap, D))
+    mean, scale = np.zeros((n, D)), np.zeros((n, D))
+    _ffi.check(_ffi.lib().paa_onset_training_sets_f64(
+        _ffi.as_f64p(packed), _ffi.as_i32p(frames), n, D, int(chunk_bytes or 0), cap, _ffi.as_f64p(limits), _ffi.as_i32p(counts),
+        _ffi.as_u8p(quiet), _ffi.as_u8p(loud), _ffi.as_i32p(src), _ffi.as_f64p(X), _ffi.as_f64p(mean), _ffi.as_f64p(scale)))
+    out, r0, f0 = [], 0, 0
+    for c in range(n):
+        nq, nl = int(counts[c, 0]), int(counts[c, 1])
+        out.append(dict(quiet_limit=float(limits[c, 0]), loud_limit=float(limits[c, 1]), quiet_idx=src[r0:r0 + nq].astype(np.int64),
+                        loud_idx=src[r0 + nq:r0 + nq + nl].astype(np.int64), features=X[r0:r0 + nq + nl].copy(), mean=mean[c].copy(),
+                        scale=scale[c].copy(), quiet_flags=quiet[f0:f0 + frames[c]].astype(bool), loud_flags=loud[f0:f0 + frames[c]].astype(bool)))
+        r0 += nq + nl
+        f0 += int(frames[c])
+    return out
+
+
+def onset_activity(st_feats_list, models, widths, weights, *, chunk_bytes=None):
+    """Stages 4 and 5 of silence_removal_batch for short-term matrices in host memory and one linear model per clip
+    (onset_proba_kernel, onset_threshold_kernel).  models: per clip (w, intercept, prob_a, prob_b, mean, scale) -- scikit-learn's
+    decision_function is <w, (x - mean) / scale> + intercept; widths: the smoothing box in frames (int(smooth_window /
+    st_step)), weights: the threshold weight, each a scalar or one per clip.  Per clip a dict of raw_prob, prob (smoothed),
+    threshold and active (the frames with prob > threshold)."""
+    packed, frames, D = _stack_matrices(st_feats_list)
+    n, nf = len(frames), int(frames.sum())
+    models = list(models)
+    if len(models) != n or any(len(m) != 6 for m in models):
+        raise ValueError("one model (w, intercept, prob_a, prob_b, mean, scale) per clip")
+    vec = lambda k: np.ascontiguousarray(np.stack([np.asarray(m[k], dtype=np.float64).reshape(-1) for m in models]))
+    w, mean, scale = vec(0), vec(4), vec(5)
+    if w.shape != (n, D) or mean.shape != (n, D) or scale.shape != (n, D):
+        raise ValueError("feature dimension mismatch between the matrices and the models")
+    icpt, pa, pb = (np.array([float(m[k]) for m in models]) for k in (1, 2, 3))
+    wd = np.ascontiguousarray(_per_clip(widths, n, "widths").astype(np.int32))
+    wt = _per_clip(weights, n, "weights")
+    for c in range(n):
+        if frames[c] < wd[c]:
+            raise ValueError("clip %d: Input vector needs to be bigger than window size." % c)
+    raw, prob, thr, active = np.zeros(nf), np.zeros(nf), np.zeros(n), np.zeros(nf, dtype=np.uint8)
+    _ffi.check(_ffi.lib().paa_onset_activity_f64(
+        _ffi.as_f64p(packed), _ffi.as_i32p(frames), n, D, _ffi.as_f64p(w), _ffi.as_f64p(icpt), _ffi.as_f64p(pa), _ffi.as_f64p(pb),
+        _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_i32p(wd), _ffi.as_f64p(wt), int(chunk_bytes or 0), _ffi.as_f64p(raw),
+        _ffi.as_f64p(prob), _ffi.as_f64p(thr), _ffi.as_u8p(active)))
+    out, f0 = [], 0
+    for c in range(n):
+        f1 = f0 + int(frames[c])
+        out.append(dict(raw_prob=raw[f0:f1].copy(), prob=prob[f0:f1].copy(), threshold=float(thr[c]), active=np.flatnonzero(active[f0:f1])))
+        f0 = f1
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------

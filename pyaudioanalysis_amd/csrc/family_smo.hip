@@ -1,9 +1,10 @@
 // The batched SMO solver and the one-against-one vote of the SVM split sweep (kernels_smo.hpp: the SVM fits of
 // audioTrainTest.evaluate_classifier) and the sigmoid fit of probabilistic SVMs (kernels_platt.hpp) -- own translation unit,
-// see model_launch.hpp.
+// see model_launch.hpp.  The glue kernels of batched silence removal (kernels_onset.hpp) live here with the fit they surround.
 #include "model_launch.hpp"
 #include "kernels_smo.hpp"
 #include "kernels_platt.hpp"
+#include "kernels_onset.hpp"
 
 namespace paa {
 namespace launch {
@@ -38,6 +39,37 @@ int platt_sigmoid(const platt::PlattDev &p, int n_problems, int l_max, hipStream
     const size_t lds = ((size_t)l_max * 9 + 7) / 8 * 8;
     if (raise_lds(reinterpret_cast<const void *>(&platt::platt_sigmoid_kernel), lds)) return -1;
     hipLaunchKernelGGL(platt::platt_sigmoid_kernel, dim3((unsigned)n_problems), dim3(platt::kThreads), lds, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int onset_select(const onset::OnsetDev &m, int n_clips, hipStream_t stream) {
+    if (n_clips < 1) return -1;
+    hipLaunchKernelGGL(onset::onset_select_kernel, dim3((unsigned)n_clips), dim3(onset::kThreads), 0, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int onset_gather(const onset::OnsetDev &m, int n_clips, hipStream_t stream) {
+    if (n_clips < 1 || m.n_dims < 1 || m.n_dims > onset::kMaxDims) return -1;
+    hipLaunchKernelGGL(onset::onset_gather_kernel, dim3((unsigned)n_clips), dim3(onset::kThreads), 0, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int onset_weights(const onset::OnsetDev &m, int n_clips, hipStream_t stream) {
+    if (n_clips < 1 || m.n_dims < 1 || m.n_dims > onset::kMaxDims) return -1;
+    hipLaunchKernelGGL(onset::onset_weights_kernel, dim3((unsigned)n_clips), dim3(onset::kThreads), 0, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int onset_proba(const onset::OnsetDev &m, int n_clips, long long n_frames, hipStream_t stream) {
+    const long long blocks = (n_frames + onset::kThreads - 1) / onset::kThreads;
+    if (n_clips < 1 || n_frames < 1 || blocks > 0x7fffffffLL) return -1;
+    hipLaunchKernelGGL(onset::onset_proba_kernel, dim3((unsigned)blocks), dim3(onset::kThreads), 0, stream, m, n_clips, n_frames);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int onset_threshold(const onset::OnsetDev &m, int n_clips, hipStream_t stream) {
+    if (n_clips < 1) return -1;
+    hipLaunchKernelGGL(onset::onset_threshold_kernel, dim3((unsigned)n_clips), dim3(onset::kThreads), 0, stream, m);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

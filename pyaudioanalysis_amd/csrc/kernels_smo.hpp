@@ -199,8 +199,9 @@ __global__ __launch_bounds__(kThreads) void svc_pairs_kernel(SvcFitDev f, int *_
     const knn::SplitBlock blk = f.blocks[blockIdx.x];
     const long long q0 = f.test_off[blk.job];
     const int n_test = (int)(f.test_off[blk.job + 1] - q0), k = f.job_k[blk.job], task0 = f.job_task[blk.job];
-    const double *__restrict__ mean = f.mean + (long long)blk.job * n_dims;
-    const double *__restrict__ scale = f.scale + (long long)blk.job * n_dims;
+    const int stat = f.job_stat ? f.job_stat[blk.job] : blk.job;
+    const double *__restrict__ mean = f.mean + (long long)stat * n_dims;
+    const double *__restrict__ scale = f.scale + (long long)stat * n_dims;
     const int qi = blk.first + group;
     const bool live = qi < n_test;
     const long long q = q0 + qi;

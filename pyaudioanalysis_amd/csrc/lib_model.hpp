@@ -40,7 +40,8 @@ struct BlockPart {
     size_t bytes, align;
     void *dev;              // out: its place in the block
 };
-// allocates b for the parts in order, each at its alignment, and uploads them; `what` names the model in the error message
+// allocates b for the parts in order, each at its alignment, and uploads them (a part without a source is room only); `what`
+// names the model in the error message
 static int block_upload(DevBlock &b, BlockPart *parts, int n, const char *what) {
     size_t total = 0;
     for (int i = 0; i < n; ++i) total = (total + parts[i].align - 1) / parts[i].align * parts[i].align + parts[i].bytes;
@@ -49,7 +50,7 @@ static int block_upload(DevBlock &b, BlockPart *parts, int n, const char *what) 
     for (int i = 0; i < n; ++i) {
         at = (at + parts[i].align - 1) / parts[i].align * parts[i].align;
         parts[i].dev = (char *)b.p + at;
-        if (hipMemcpy(parts[i].dev, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice) != hipSuccess)
+        if (parts[i].src && hipMemcpy(parts[i].dev, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice) != hipSuccess)
             return fail(PAA_ERR_HIP, "uploading %s failed", what);
         at += parts[i].bytes;
     }

@@ -424,6 +424,120 @@ static int platt_folds(PlattFolds &f, PairTasks &p, const int64_t *seed, std::ve
     return PAA_OK;
 }
 
+// What svc_fit_proba_resident gives back: host arrays, paa_svc_fit_proba_f64's outputs of the same names (cv_dec and n_launches may
+// be null)
+struct ProbaFitOut {
+    double *alpha_y, *rho, *prob_a, *prob_b;
+    int32_t *n_sv, *task_iterations, *task_status, *sig_iterations, *sig_stop;
+    double *cv_dec;
+    int32_t *n_launches;
+};
+
+// The fits of SVC(probability=True) over a sample matrix that is already RESIDENT (d_X [..][n_dims], with d_mean / d_scale
+// [n_jobs][n_dims] on the device too): p holds the pair tasks of the jobs (svc_pair_tasks) and receives the folds; the full fits
+// and the fold fits are one solver batch, svc_pairs_kernel scores every fold's held-out rows, platt_sigmoid_kernel fits every
+// pair.  Runs on the caller's stream (cs()) and has finished when it returns
+static int svc_fit_proba_resident(const double *d_X, const double *d_mean, const double *d_scale, int n_dims, PairTasks &p,
+                                  const int64_t *seed, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                  const ProbaFitOut &o) {
+    int rc;
+    const size_t np = p.tasks.size(), rows_full = p.idx.size();
+    std::vector<int64_t> prob_off(np + 1, 0);
+    int l_max = 0;
+    for (size_t t = 0; t < np; ++t) {
+        prob_off[t + 1] = prob_off[t] + p.tasks[t].n;
+        l_max = std::max(l_max, p.tasks[t].n);
+    }
+    std::vector<double> cv(rows_full, 0.0);
+    PlattFolds f;
+    if ((rc = platt_folds(f, p, seed, cv, kernel_type))) return rc;
+    if (p.tasks.size() > 0x3fffffffULL || f.test_idx.size() > (size_t)kSweepMaxQ) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
+    // upload: a fold with held-out rows is a scoring job of one pair, standardised as its job
+    const int n_score = (int)f.job_task.size();
+    const int64_t n_q = f.test_off[n_score];
+    const std::vector<knn::SplitBlock> blocks = sweep_blocks(f.test_off.data(), n_score, smo::kQueriesPerBlock);
+    std::vector<int> job_k((size_t)std::max(n_score, 1), 2);
+    f.job_task.push_back((int)p.tasks.size());
+    if (f.job_stat.empty()) f.job_stat.push_back(0);
+    const size_t rows = p.idx.size(), nt = p.tasks.size();
+    const knn::SplitBlock none{0, 0};
+    DevBlock block;
+    BlockPart parts[] = {{p.tasks.data(), nt * sizeof(smo::SmoTask), 8},
+                         {f.test_off.data(), (size_t)(n_score + 1) * 8, 8},
+                         {prob_off.data(), (np + 1) * 8, 8},
+                         {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
+                         {nullptr, (size_t)std::max<int64_t>(n_q, 1) * 8, 8},           // the held-out decision values
+                         {p.idx.data(), rows * 4, 4},
+                         {n_q ? f.test_idx.data() : p.idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
+                         {f.job_task.data(), (size_t)(n_score + 1) * 4, 4},
+                         {job_k.data(), job_k.size() * 4, 4},
+                         {f.job_stat.data(), f.job_stat.size() * 4, 4},
+                         {nullptr, (size_t)std::max<int64_t>(n_q, 1) * 4, 4},           // their labels (not read)
+                         {p.sign.data(), rows, 1}};
+    if ((rc = block_upload(block, parts, 12, "the probabilistic SVM jobs"))) return rc;
+    std::vector<double> q_dec((size_t)n_q);
+    // solve the batch
+    smo::SmoDev m{};
+    m.X = d_X;
+    m.tasks = (const smo::SmoTask *)parts[0].dev;
+    m.mean = d_mean;
+    m.scale = d_scale;
+    m.idx = (const int *)parts[5].dev;
+    m.sign = (const signed char *)parts[11].dev;
+    m.n_dims = n_dims;
+    m.rbf = kernel_type == 2;
+    m.max_iter = max_iter;
+    m.eps = eps;
+    SmoState s;
+    std::vector<int> st_words;
+    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, o.n_launches))) return rc;
+    std::vector<int32_t> iters(nt);
+    HIP_TRY(hipMemcpyAsync(iters.data(), m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(o.alpha_y, m.alpha_y, rows_full * 8, hipMemcpyDeviceToHost, cs()));      // the full fits come first
+    HIP_TRY(hipMemcpyAsync(o.rho, m.rho, np * 8, hipMemcpyDeviceToHost, cs()));
+    HIP_TRY(hipMemcpyAsync(o.n_sv, m.n_sv, np * 4, hipMemcpyDeviceToHost, cs()));
+    // score the held-out rows of every fold
+    if (n_q) {
+        smo::SvcFitDev v{};
+        v.X = d_X;
+        v.test_off = (const long long *)parts[1].dev;
+        v.blocks = (const knn::SplitBlock *)parts[3].dev;
+        v.test_idx = (const int *)parts[6].dev;
+        v.job_task = (const int *)parts[7].dev;
+        v.job_k = (const int *)parts[8].dev;
+        v.job_stat = (const int *)parts[9].dev;
+        v.mean = d_mean;
+        v.scale = d_scale;
+        v.tasks = m.tasks;
+        v.idx = m.idx;
+        v.alpha_y = m.alpha_y;
+        v.rho = m.rho;
+        v.n_dims = n_dims;
+        v.rbf = m.rbf;
+        v.max_pairs = 1;
+        LAUNCH_TRY("fold scoring", launch::svc_pairs(v, (long long)blocks.size(), (int32_t *)parts[10].dev, (double *)parts[4].dev, cs()));
+        HIP_TRY(hipMemcpyAsync(q_dec.data(), parts[4].dev, (size_t)n_q * 8, hipMemcpyDeviceToHost, cs()));
+    }
+    HIP_TRY(hipStreamSynchronize(cs()));
+    for (int64_t q = 0; q < n_q; ++q) cv[f.where[q]] = q_dec[q];
+    for (size_t t = 0; t < np; ++t) {
+        o.task_iterations[t * 6] = iters[t];
+        o.task_status[t * 6] = st_words[t];
+        for (int fold = 0; fold < 5; ++fold) {
+            const int ft = f.fold_task[t * 5 + fold];
+            o.task_iterations[t * 6 + 1 + fold] = ft < 0 ? 0 : iters[ft];
+            o.task_status[t * 6 + 1 + fold] = ft < 0 ? 0 : st_words[ft];
+        }
+    }
+    if (o.cv_dec) std::copy(cv.begin(), cv.end(), o.cv_dec);
+    // the sigmoid of every pair: its held-out values in pair-row order with the signs of its full task
+    DevBlock d_cv;
+    BlockPart cv_part[] = {{cv.data(), rows_full * 8, 8}};
+    if ((rc = block_upload(d_cv, cv_part, 1, "the held-out decision values"))) return rc;
+    return platt_run((const double *)cv_part[0].dev, m.sign, (const long long *)parts[2].dev, (int)np, l_max, o.prob_a, o.prob_b,
+                     o.sig_iterations, o.sig_stop);
+}
+
 // SVC(probability=True).fit for every job: the full fits, Platt's folds and the sigmoid fits; see paa_hip.h
 extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
                                      const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
@@ -447,103 +561,20 @@ extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_d
         if (labels[train_idx[i]] < 0) return fail(PAA_ERR_ARG, "training sample %d has the label %d: class indices are >= 0", train_idx[i], labels[train_idx[i]]);
     for (int j = 0; j < n_jobs; ++j)
         if (seed[j] < 0 || seed[j] > 0x7fffffffLL) return fail(PAA_ERR_ARG, "job %d: seed %lld: libsvm's random_seed is in 0 .. 2^31 - 1", j, (long long)seed[j]);
-    // the tasks: the full fit of every pair, then the folds
+    // the tasks: the full fit of every pair (the folds follow in svc_fit_proba_resident)
     PairTasks p;
     if ((rc = svc_pair_tasks(p, labels, n_jobs, train_off, train_idx, C, gamma, kernel_type))) return rc;
-    const size_t np = p.tasks.size(), rows_full = p.idx.size();
-    if (n_pairs != (int)np || n_rows != (int64_t)rows_full)
-        return fail(PAA_ERR_ARG, "n_pairs = %d, n_rows = %lld: the jobs make %d pairs of %lld rows", n_pairs, (long long)n_rows, (int)np, (long long)rows_full);
-    std::vector<int64_t> prob_off(np + 1, 0);
-    int l_max = 0;
-    for (size_t t = 0; t < np; ++t) {
-        prob_off[t + 1] = prob_off[t] + p.tasks[t].n;
-        l_max = std::max(l_max, p.tasks[t].n);
-    }
-    std::vector<double> cv(rows_full, 0.0);
-    PlattFolds f;
-    if ((rc = platt_folds(f, p, seed, cv, kernel_type))) return rc;
-    if (p.tasks.size() > 0x3fffffffULL || f.test_idx.size() > (size_t)kSweepMaxQ) return fail(PAA_ERR_UNSUPPORTED, "too many tasks");
+    if (n_pairs != (int)p.tasks.size() || n_rows != (int64_t)p.idx.size())
+        return fail(PAA_ERR_ARG, "n_pairs = %d, n_rows = %lld: the jobs make %d pairs of %lld rows", n_pairs, (long long)n_rows, (int)p.tasks.size(), (long long)p.idx.size());
     if ((rc = ensure_init())) return rc;
-    // upload: a fold with held-out rows is a scoring job of one pair, standardised as its job
-    const int n_score = (int)f.job_task.size();
-    const int64_t n_q = f.test_off[n_score];
-    const std::vector<knn::SplitBlock> blocks = sweep_blocks(f.test_off.data(), n_score, smo::kQueriesPerBlock);
-    std::vector<double> s_mean((size_t)std::max(n_score, 1) * n_dims, 0.0), s_std((size_t)std::max(n_score, 1) * n_dims, 1.0);
-    for (int s = 0; s < n_score; ++s) {
-        std::copy(mean + (size_t)f.job_stat[s] * n_dims, mean + (size_t)(f.job_stat[s] + 1) * n_dims, s_mean.begin() + (size_t)s * n_dims);
-        std::copy(std + (size_t)f.job_stat[s] * n_dims, std + (size_t)(f.job_stat[s] + 1) * n_dims, s_std.begin() + (size_t)s * n_dims);
-    }
-    std::vector<int> job_k((size_t)std::max(n_score, 1), 2);
-    f.job_task.push_back((int)p.tasks.size());
-    const size_t sb = (size_t)n_jobs * n_dims * 8, rows = p.idx.size(), nt = p.tasks.size();
-    const knn::SplitBlock none{0, 0};
-    DevBlock block;
-    BlockPart parts[] = {{p.tasks.data(), nt * sizeof(smo::SmoTask), 8},
-                         {mean, sb, 8},
-                         {std, sb, 8},
-                         {s_mean.data(), s_mean.size() * 8, 8},
-                         {s_std.data(), s_std.size() * 8, 8},
-                         {f.test_off.data(), (size_t)(n_score + 1) * 8, 8},
-                         {prob_off.data(), (np + 1) * 8, 8},
-                         {blocks.empty() ? &none : blocks.data(), std::max<size_t>(blocks.size(), 1) * sizeof(knn::SplitBlock), 8},
-                         {p.idx.data(), rows * 4, 4},
-                         {n_q ? f.test_idx.data() : p.idx.data(), (size_t)std::max<int64_t>(n_q, 1) * 4, 4},
-                         {f.job_task.data(), (size_t)(n_score + 1) * 4, 4},
-                         {job_k.data(), job_k.size() * 4, 4},
-                         {p.sign.data(), rows, 1}};
-    if ((rc = block_upload(block, parts, 13, "the probabilistic SVM jobs"))) return rc;
-    std::vector<int32_t> q_label((size_t)n_q);
-    std::vector<double> q_dec((size_t)n_q);
-    Staged st;                                        // X goes up once, through the lane's scratch
-    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0,
-                    {{n_q ? q_label.data() : nullptr, (size_t)n_q * 4}, {n_q ? q_dec.data() : nullptr, (size_t)n_q * 8}})))
-        return rc;
-    // solve the batch
-    smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[8], parts[12], n_dims, kernel_type, eps, max_iter);
-    SmoState s;
-    std::vector<int> st_words;
-    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches))) return rc;
-    std::vector<int32_t> iters(nt);
-    HIP_TRY(hipMemcpyAsync(iters.data(), m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipMemcpyAsync(alpha_y, m.alpha_y, rows_full * 8, hipMemcpyDeviceToHost, cs()));      // the full fits come first
-    HIP_TRY(hipMemcpyAsync(rho, m.rho, np * 8, hipMemcpyDeviceToHost, cs()));
-    HIP_TRY(hipMemcpyAsync(n_sv, m.n_sv, np * 4, hipMemcpyDeviceToHost, cs()));
-    // score the held-out rows of every fold
-    if (n_q) {
-        smo::SvcFitDev v{};
-        v.X = st.feats;
-        v.test_off = (const long long *)parts[5].dev;
-        v.blocks = (const knn::SplitBlock *)parts[7].dev;
-        v.test_idx = (const int *)parts[9].dev;
-        v.job_task = (const int *)parts[10].dev;
-        v.job_k = (const int *)parts[11].dev;
-        v.mean = (const double *)parts[3].dev;
-        v.scale = (const double *)parts[4].dev;
-        v.tasks = m.tasks;
-        v.idx = m.idx;
-        v.alpha_y = m.alpha_y;
-        v.rho = m.rho;
-        v.n_dims = n_dims;
-        v.rbf = m.rbf;
-        v.max_pairs = 1;
-        LAUNCH_TRY("fold scoring", launch::svc_pairs(v, (long long)blocks.size(), (int32_t *)st.out[0], (double *)st.out[1], cs()));
-    }
-    if ((rc = finish(st))) return rc;
-    for (int64_t q = 0; q < n_q; ++q) cv[f.where[q]] = q_dec[q];
-    for (size_t t = 0; t < np; ++t) {
-        task_iterations[t * 6] = iters[t];
-        task_status[t * 6] = st_words[t];
-        for (int fold = 0; fold < 5; ++fold) {
-            const int ft = f.fold_task[t * 5 + fold];
-            task_iterations[t * 6 + 1 + fold] = ft < 0 ? 0 : iters[ft];
-            task_status[t * 6 + 1 + fold] = ft < 0 ? 0 : st_words[ft];
-        }
-    }
-    if (cv_dec) std::copy(cv.begin(), cv.end(), cv_dec);
-    // the sigmoid of every pair: its held-out values in pair-row order with the signs of its full task
-    DevBlock d_cv;
-    BlockPart cv_part[] = {{cv.data(), rows_full * 8, 8}};
-    if ((rc = block_upload(d_cv, cv_part, 1, "the held-out decision values"))) return rc;
-    return platt_run((const double *)cv_part[0].dev, m.sign, (const long long *)parts[6].dev, (int)np, l_max, prob_a, prob_b,
-                     sig_iterations, sig_stop);
+    // X goes up once, through the lane's scratch, with every job's mean and scale behind it
+    const size_t sb = (size_t)n_jobs * n_dims * 8;
+    DevBlock stats;
+    BlockPart parts[] = {{mean, sb, 8}, {std, sb, 8}};
+    if ((rc = block_upload(stats, parts, 2, "the probabilistic SVM jobs"))) return rc;
+    Staged st;
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    const ProbaFitOut o{alpha_y, rho, prob_a, prob_b, n_sv, task_iterations, task_status, sig_iterations, sig_stop, cv_dec, n_launches};
+    return svc_fit_proba_resident(st.feats, (const double *)parts[0].dev, (const double *)parts[1].dev, n_dims, p, seed, kernel_type, eps,
+                                  max_iter, iters_per_launch, o);
 }

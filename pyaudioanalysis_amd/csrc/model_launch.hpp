@@ -107,7 +107,8 @@ struct SvcFitDev {
     const int *test_idx;
     const knn::SplitBlock *blocks;
     const int *job_task, *job_k;
-    const double *mean, *scale;   // [n_jobs][n_dims]
+    const int *job_stat;          // [n_jobs] the row of mean / scale a job standardises with (null: its own index)
+    const double *mean, *scale;   // [..][n_dims]
     const SmoTask *tasks;
     const int *idx;
     const double *alpha_y, *rho;
@@ -130,6 +131,33 @@ struct PlattDev {
     int *iter, *stop;         // out per problem: Newton iterations; Stop
 };
 }  // namespace platt
+namespace onset {
+constexpr int kThreads = 256;             // kernels_onset.hpp: one workgroup per clip (one thread per frame in onset_proba_kernel)
+constexpr int kMaxDims = 256;             // feature rows of a short-term matrix (a thread per row forms the scaler)
+// a clip of a silence-removal batch: its short-term matrix [n_dims][T] at feats + feat_off, its frames at frame_off in every
+// per-frame array; after stage 1 the host fills the counts and row_off, the clip's first row in the training matrix
+struct ClipRec {
+    long long feat_off, frame_off, row_off;
+    int T, n_quiet, n_loud, width;        // width: the smoothing box in frames
+    double weight;                        // of the highest tenth in the threshold
+};
+// a batch: device pointers.  Per frame: quiet, loud, raw, prob, active; per clip: limits [2], counts [2], mean / scale / w
+// [n_dims], rho, intercept, A, B, thr; per training row: src (its frame), X [n_dims], alpha_y
+struct OnsetDev {
+    const double *feats;
+    const ClipRec *clips;
+    double *limits;
+    int *counts;
+    unsigned char *quiet, *loud, *active;
+    int *src;
+    double *X, *mean, *scale;
+    const double *alpha_y, *rho;
+    double *w, *intercept;
+    const double *A, *B;
+    double *raw, *prob, *thr;
+    int n_dims;
+};
+}  // namespace onset
 namespace svrfit {
 // a batch of epsilon-SVR dual problems and their state (kernels_svrfit.hpp): device pointers.  A task is an smo::SmoTask (its n rows
 // are idx[off ..]); its 2 n dual variables -- variable v stands for row v mod n, with the sign +1 for v < n and -1 for v >= n --
@@ -329,6 +357,16 @@ void smo_geometry(int out6[6]);
 // kernels_platt.hpp: libsvm's sigmoid_train for each of the n_problems problems of p (one workgroup each; l_max: the longest
 // of them, which sizes the LDS); -2 when l_max exceeds platt::kMaxRows
 int platt_sigmoid(const platt::PlattDev &p, int n_problems, int l_max, hipStream_t stream);
+// kernels_onset.hpp (silence removal of a batch of clips): the energy limits, flags and counts of every clip; ...
+int onset_select(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
+// ... the training rows, their matrix and its scaler (the clip records carry the counts and row offsets)
+int onset_gather(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
+// ... the fits (alpha_y, rho) folded into w and intercept
+int onset_weights(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
+// ... the onset probability raw of every one of the batch's n_frames frames
+int onset_proba(const onset::OnsetDev &m, int n_clips, long long n_frames, hipStream_t stream);
+// ... smoothing, threshold and activity flags
+int onset_threshold(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
 // kernels_svrfit.hpp: smo_step for a batch of epsilon-SVR tasks (the limits are the SMO solver's)
 int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cmath>
@@ -549,6 +550,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_sweep.hpp"
 #include "lib_knn.hpp"
 #include "lib_smo.hpp"
+#include "lib_onset.hpp"
 #include "lib_svrfit.hpp"
 #include "lib_forest.hpp"
 #include "lib_treefit.hpp"
