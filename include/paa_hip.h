@@ -502,6 +502,37 @@ int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const
                            double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
                            int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches);
 
+/* ---- the same solver over a RESIDENT kernel matrix ---------------------------------------------------------------------------------
+ * paa_svr_tasks_f64 forms two kernel rows per iteration.  Here the n x n matrix of a task is formed once, by the whole device
+ * (standardised rows Z, then K in tiles of 32 x 32 values over the upper triangle, mirrored: every value has the bits the solver's own
+ * kernel value has), and a second solver reads K(row i, .) and K(row j, .) from it, one thread per row.  Every output is BYTE-EQUAL
+ * to the parent's.  The tasks are packed into chunks in task order: the matrix of a task of n rows takes 8 n^2 bytes; a task whose
+ * matrix exceeds cache_bytes is solved by the parent's kernel in the same call (cached = 0); any other joins the open chunk when the
+ * chunk's matrices and its own fit cache_bytes together, and otherwise opens the next chunk (cached = 1).  Device memory: the largest
+ * chunk's matrices plus 8 n pitch bytes of standardised rows per task of it (pitch: n_dims rounded up to 8).
+ *
+ * paa_svr_tasks_cached_f64, paa_svr_fit_splits_cached_f64 -- the arguments of their parents, then
+ *   cache_bytes            the budget in bytes, > 0 (PAA_ERR_ARG otherwise; judged after every argument of the parent)
+ *   cached / job_cached    [n_tasks] / [n_jobs] out, not NULL: 1 when the task was solved from its resident matrix
+ * Errors are the parents', before the device is touched.
+ *
+ * paa_svr_gram_f64 -- the matrices alone, for tests: tasks as in paa_svr_tasks_f64 (task_off, task_idx, mean, std, gamma [n_tasks],
+ * read for kernel_type 2 only); K_out [sum_t n_t^2]: the full row-major matrix of every task, one after the other; qd_out
+ * [task_off[n_tasks]] (may be NULL): the K_tt that the PARENT's solver forms at a task's start (1 for RBF).                          */
+int paa_svr_tasks_cached_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                             const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                             const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
+                             double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
+                             int32_t *n_launches, int64_t cache_bytes, int32_t *cached);
+int paa_svr_fit_splits_cached_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
+                                  const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                                  const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type,
+                                  double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
+                                  int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches,
+                                  int64_t cache_bytes, int32_t *job_cached);
+int paa_svr_gram_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off, const int32_t *task_idx,
+                     const double *mean, const double *std, const double *gamma, int kernel_type, double *K_out, double *qd_out);
+
 /* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
  * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as
  * train_svm_regression makes them, audioTrainTest.py:222-226) for many feature vectors and many models at once: what

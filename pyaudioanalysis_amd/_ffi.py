@@ -145,6 +145,13 @@ _SIGNATURES = {
     "paa_svr_fit_splits_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p, c_f64p,
                                          c_f64p, c_f64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p, c_i32p,
                                          c_i32p, c_i32p]),
+    "paa_svr_tasks_cached_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p,
+                                           c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p,
+                                           c_f64p, c_i32p, C.c_int64, c_i32p]),
+    "paa_svr_fit_splits_cached_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_f64p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p,
+                                                c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p,
+                                                c_i32p, c_i32p, c_i32p, c_i32p, C.c_int64, c_i32p]),
+    "paa_svr_gram_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int, c_f64p, c_f64p]),
     "paa_forest_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.c_void_p,
                                     c_f64p, C.c_int, C.c_int, C.c_double, c_f64p, C.POINTER(C.c_void_p)]),
     "paa_forest_destroy": (C.c_int, [C.c_void_p]),

@@ -22,6 +22,8 @@ pyAudioAnalysis/audioTrainTest.py).
     svm_split_fit_predict(X, labels, jobs, kernel, ...), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
     train_svm_device(features, labels, c_param, kernel, random_state=None), to_sklearn_svc(model)   SVC(probability=True).fit on the GPU
     svc_fit_proba(X, labels, jobs, kernel, ...), platt_sigmoid(dec, signs, offsets)   its stages: fits, folds and sigmoids; the sigmoid alone
+    svr_split_fit_predict(X, y, jobs, kernel, ..., kernel_cache="none"), svr_solve(X, y, tasks, ...)   every SVR fit of a sweep side by side on the GPU
+    train_svm_regression_device(features, labels, c_param, kernel), to_sklearn_svr(model), svr_kernel_matrix(X, tasks, kernel)   SVR.fit on the GPU
     forest_split_fit_predict(X, labels, jobs, kind, proba=False), tree_fit(X, tasks, splitter)   every forest fit of a sweep side by side on the GPU
     train_forest_device(features, labels, n_estimators, kind, random_state=None), to_sklearn_forest(arrays, kind)   the forests' fit on the GPU
 
@@ -67,7 +69,8 @@ without scikit-learn; the fits of the trainers and of evaluate_regression are sc
 by default.  With svm_fit="device" evaluate_regression fits "svm" / "svm_rbf" on the GPU too: every split of every parameter
 value is one epsilon-SVR problem of svr_smo_kernel (libsvm's solver without shrinking, FP64; a dual of 2 n variables over n
 rows whose kernel rows are formed once per row), all of them side by side, scored in the same call
-(paa_svr_fit_splits_f64); the final fit of feature_extraction_train_regression and its model file stay scikit-learn's.
+(paa_svr_fit_splits_f64); kernel_cache="gram" solves from resident kernel matrices with the same bytes out, and
+final_fit="device" makes the final fit of feature_extraction_train_regression and its model file the device's too.
 With forest_fit="device" evaluate_regression fits "randomforest" on the GPU: one workgroup per tree builds scikit-learn's
 squared-error regression tree (the MSE instance of tree_fit_kernel through paa_tree_fit_reg_tasks_f64 /
 paa_forest_reg_fit_splits_f64), every floating-point sum in a fixed order -- scikit-learn's bits when the targets make the sums
@@ -1333,11 +1336,13 @@ def to_sklearn_svc(model):
 class SvrSolveResult:
     """What svr_solve returns: beta and train_pred (lists of one array per task, in the task's row order: alpha_t - alpha_{t+n}
     and the prediction of the row), rho, iterations, gap, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv (rows with
-    beta != 0) per task and the number of kernel launches."""
+    beta != 0) per task and the number of kernel launches; cached [n_tasks] (bool): the task was solved from its resident
+    kernel matrix (all False under kernel_cache="none")."""
 
-    def __init__(self, beta, train_pred, rho, iterations, gap, status, n_sv, n_launches):
+    def __init__(self, beta, train_pred, rho, iterations, gap, status, n_sv, n_launches, cached=None):
         self.beta, self.train_pred, self.rho, self.iterations, self.gap = beta, train_pred, rho, iterations, gap
         self.status, self.n_sv, self.n_launches = status, n_sv, n_launches
+        self.cached = np.zeros(len(rho), dtype=bool) if cached is None else cached
 
 
 def _targets(y, n_samples):
@@ -1347,14 +1352,53 @@ def _targets(y, n_samples):
     return y
 
 
-def svr_solve(X, y, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0):
+SVR_CACHE_BYTES = 4 << 30                        # the default budget of kernel_cache="gram": 4 GiB of resident kernel matrices
+SVR_GRAM_TILE = 32                               # rows of a tile of svr_gram_kernel (svrfit::kGramTile)
+
+
+def _cache_mode(kernel_cache, cache_bytes):
+    """cache_bytes of a call (None without a cache): kernel_cache is "none" or "gram", cache_bytes None (the default budget)
+    or a positive number of bytes, read under "gram" only."""
+    if kernel_cache not in ("none", "gram"):
+        raise ValueError("kernel_cache=%r: 'none' or 'gram'" % (kernel_cache,))
+    if kernel_cache == "none":
+        return None
+    cache_bytes = SVR_CACHE_BYTES if cache_bytes is None else int(cache_bytes)
+    if cache_bytes <= 0:
+        raise ValueError("cache_bytes = %d: a positive budget is needed" % cache_bytes)
+    return cache_bytes
+
+
+def svr_cache_chunks(rows, cache_bytes):
+    """The packing rule of the resident kernel matrices, restated (lib_svrfit.hpp: svr_cache_pack): rows [n_tasks] are the
+    tasks' row counts; the matrix of a task of n rows takes 8 n^2 bytes.  In task order, a task whose matrix exceeds
+    cache_bytes is not cached; any other joins the open chunk when the chunk's matrices and its own fit cache_bytes together
+    and otherwise opens the next.  Returns the chunk of every task from 0, -1 for a task that is not cached."""
+    chunk_of, n_chunks, used = [], 0, 0
+    for n in rows:
+        size = 8 * int(n) * int(n)
+        if size > cache_bytes:
+            chunk_of.append(-1)
+            continue
+        if n_chunks == 0 or used + size > cache_bytes:
+            n_chunks, used = n_chunks + 1, 0
+        used += size
+        chunk_of.append(n_chunks - 1)
+    return np.array(chunk_of, dtype=np.int64)
+
+
+def svr_solve(X, y, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0, *, kernel_cache="none", cache_bytes=None):
     """Epsilon-SVR dual problems over ONE sample matrix and its targets, all solved side by side (paa_svr_tasks_f64,
     svr_smo_kernel: libsvm's solve_epsilon_svr over its Solver without shrinking, FP64).  X [n_samples][n_dims]; y [n_samples];
     a task is (rows, mean, scale, C, gamma, epsilon): the rows X[rows] standardised as (x - mean) / scale with the targets
     y[rows], gamma read for kernel="rbf" only (None: 1 / n_dims).  iters_per_launch bounds one kernel launch (0: the library's
     default); results do not depend on it.  A task that stops at max_iter has the status SMO_NOT_CONVERGED and a warning is
     issued, as scikit-learn does.  The prediction for a standardised z is sum_t beta_t K(z_t, z) - rho; train_pred holds it
-    for the task's own rows, read from the solver's gradient.  Returns an SvrSolveResult."""
+    for the task's own rows, read from the solver's gradient.  kernel_cache="gram" (keyword only) forms every task's n x n
+    kernel matrix once on the device and solves from it (paa_svr_tasks_cached_f64, DESIGN K22): every output is byte-equal to
+    kernel_cache="none"; the matrices are packed into chunks of at most cache_bytes (None: 4 GiB; see svr_cache_chunks), and
+    a task whose matrix alone exceeds it is solved as under "none" (its `cached` is False).  Returns an SvrSolveResult."""
+    cache_bytes = _cache_mode(kernel_cache, cache_bytes)
     X = np.ascontiguousarray(X, dtype=np.float64)
     tasks = list(tasks)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
@@ -1382,24 +1426,64 @@ def svr_solve(X, y, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_
     beta, train_pred, rho, gap = np.zeros(total), np.zeros(total), np.zeros(n_tasks), np.zeros(n_tasks)
     iterations, status, n_sv = (np.zeros(n_tasks, dtype=np.int32) for _ in range(3))
     launches = np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_svr_tasks_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, _ffi.as_f64p(y), n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_f64p(mean),
-        _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps),
-        int(max_iter), int(iters_per_launch), _ffi.as_f64p(beta), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
-        _ffi.as_i32p(status), _ffi.as_i32p(n_sv), _ffi.as_f64p(train_pred), _ffi.as_i32p(launches)))
+    cached = np.zeros(n_tasks, dtype=np.int32)
+    args = (_ffi.as_f64p(X), n_samples, n_dims, _ffi.as_f64p(y), n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_f64p(mean),
+            _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps),
+            int(max_iter), int(iters_per_launch), _ffi.as_f64p(beta), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
+            _ffi.as_i32p(status), _ffi.as_i32p(n_sv), _ffi.as_f64p(train_pred), _ffi.as_i32p(launches))
+    if cache_bytes is None:
+        _ffi.check(_ffi.lib().paa_svr_tasks_f64(*args))
+    else:
+        _ffi.check(_ffi.lib().paa_svr_tasks_cached_f64(*args, cache_bytes, _ffi.as_i32p(cached)))
     _warn_not_converged(status, int(max_iter))
     per_task = lambda a: [a[off[t]:off[t + 1]] for t in range(n_tasks)]
-    return SvrSolveResult(per_task(beta), per_task(train_pred), rho, iterations, gap, status, n_sv, int(launches[0]))
+    return SvrSolveResult(per_task(beta), per_task(train_pred), rho, iterations, gap, status, n_sv, int(launches[0]), cached != 0)
+
+
+def svr_kernel_matrix(X, tasks, kernel, *, with_qd=False):
+    """The output of the Gram kernel alone (paa_svr_gram_f64: svr_standardise_kernel, svr_gram_kernel): X [n_samples][n_dims];
+    a task is (rows, mean, scale, gamma) (gamma None: 1 / n_dims; read for kernel="rbf" only).  Returns the list of the tasks'
+    full kernel matrices [n][n] over their standardised rows; with_qd=True (keyword only) returns (that list, the list of
+    K_tt [n] that the recomputing solver forms at a task's start)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    tasks = list(tasks)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("sample matrix of shape %s" % (X.shape,))
+    if not tasks:
+        raise ValueError("no tasks")
+    _check_kernel(kernel)
+    n_samples, n_dims = X.shape
+    rows, means, scales, gammas = [], [], [], []
+    for t, task in enumerate(tasks):
+        if len(task) != 4:
+            raise ValueError("task %d: (rows, mean, scale, gamma) expected" % t)
+        rows.append(_index_list(task[0], "row", t))
+        mean, scale = _stats(task[1], task[2], n_dims)
+        means.append(mean)
+        scales.append(scale)
+        gammas.append(1.0 / n_dims if task[3] is None else float(task[3]))
+    idx, off = _packed(rows, np.int32)
+    sizes = [int(off[t + 1] - off[t]) ** 2 for t in range(len(tasks))]
+    K, qd = np.zeros(sum(sizes)), np.zeros(int(off[-1]))
+    _ffi.check(_ffi.lib().paa_svr_gram_f64(
+        _ffi.as_f64p(X), n_samples, n_dims, len(tasks), _ffi.as_i64p(off), _ffi.as_i32p(idx), _ffi.as_f64p(np.stack(means)),
+        _ffi.as_f64p(np.stack(scales)), _ffi.as_f64p(np.array(gammas, dtype=np.float64)), _KERNEL_TYPES[kernel], _ffi.as_f64p(K),
+        _ffi.as_f64p(qd) if with_qd else None))
+    at = np.concatenate([[0], np.cumsum(sizes)])
+    mats = [K[at[t]:at[t + 1]].reshape(int(off[t + 1] - off[t]), -1) for t in range(len(tasks))]
+    return (mats, [qd[off[t]:off[t + 1]] for t in range(len(tasks))]) if with_qd else mats
 
 
 class SvrSplitResult(_SplitResult):
     """What svr_split_fit_predict returns: pred [Q] (the test predictions), train_pred [T] or None (the training predictions,
     job j owns train_off[j] .. train_off[j + 1] - 1), test_off / train_off [n_jobs + 1], gamma [n_jobs] (the values the fits ran
-    with) and per job iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel."""
+    with) and per job iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel; cached
+    [n_jobs] (bool): the job was solved from its resident kernel matrix (all False under kernel_cache="none")."""
 
-    def __init__(self, pred, train_pred, test_off, train_off, gamma, iterations, status, n_sv, n_launches):
+    def __init__(self, pred, train_pred, test_off, train_off, gamma, iterations, status, n_sv, n_launches, cached=None):
         self.pred, self.train_pred, self.test_off, self.train_off, self.gamma = pred, train_pred, test_off, train_off, gamma
         self.iterations, self.status, self.n_sv, self.n_launches = iterations, status, n_sv, n_launches
+        self.cached = np.zeros(len(gamma), dtype=bool) if cached is None else cached
 
     def job(self, j):
         """(test predictions, training predictions or None, iterations, status, n_sv) of job j."""
@@ -1409,14 +1493,16 @@ class SvrSplitResult(_SplitResult):
 
 
 def svr_split_fit_predict(X, y, jobs, kernel="linear", gamma=None, epsilon=0.1, eps=1e-3, train_pred=False, max_iter=10**7,
-                          iters_per_launch=0):
+                          iters_per_launch=0, *, kernel_cache="none", cache_bytes=None):
     """SVR(C, kernel, gamma, epsilon).fit(train).predict(test) for every job of a sweep over ONE sample matrix
     (paa_svr_fit_splits_f64: every job is one epsilon-SVR problem of svr_smo_kernel, all of them side by side; then the test
     rows of every job are scored).  X [n_samples][n_dims]; y [n_samples]; a job is (train_idx, test_idx, mean, scale, C).
     gamma=None is scikit-learn's SVR default, 'scale': per job 1 / (n_dims * Z.var()) of its standardised training rows Z (1
     when that variance is 0), formed with NumPy on the host.  train_pred=True also returns the predictions of every job's
-    training rows, which the solver reads from its final gradient: no training row is scored again.  Returns an
-    SvrSplitResult."""
+    training rows, which the solver reads from its final gradient: no training row is scored again.  kernel_cache and
+    cache_bytes (keyword only) are svr_solve's: "gram" solves every job from its resident kernel matrix
+    (paa_svr_fit_splits_cached_f64) with byte-equal results.  Returns an SvrSplitResult."""
+    cache_bytes = _cache_mode(kernel_cache, cache_bytes)
     p = _pack_jobs(X, y, jobs, "C", float, kernel)
     n_samples, n_dims = p.X.shape
     targets = _targets(p.raw, n_samples)
@@ -1436,14 +1522,18 @@ def svr_split_fit_predict(X, y, jobs, kernel="linear", gamma=None, epsilon=0.1, 
     tp = np.zeros(T) if train_pred else None
     iterations, status, n_sv = (np.zeros(n_jobs, dtype=np.int32) for _ in range(3))
     launches = np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_svr_fit_splits_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_f64p(targets), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
-        _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch),
-        _ffi.as_f64p(pred), _ffi.as_f64p(tp) if train_pred else None, _ffi.as_i32p(iterations), _ffi.as_i32p(status),
-        _ffi.as_i32p(n_sv), _ffi.as_i32p(launches)))
+    cached = np.zeros(n_jobs, dtype=np.int32)
+    args = (_ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_f64p(targets), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+            _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
+            _ffi.as_f64p(g_arr), _ffi.as_f64p(e_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch),
+            _ffi.as_f64p(pred), _ffi.as_f64p(tp) if train_pred else None, _ffi.as_i32p(iterations), _ffi.as_i32p(status),
+            _ffi.as_i32p(n_sv), _ffi.as_i32p(launches))
+    if cache_bytes is None:
+        _ffi.check(_ffi.lib().paa_svr_fit_splits_f64(*args))
+    else:
+        _ffi.check(_ffi.lib().paa_svr_fit_splits_cached_f64(*args, cache_bytes, _ffi.as_i32p(cached)))
     _warn_not_converged(status, int(max_iter))
-    return SvrSplitResult(pred, tp, p.test_off, p.train_off, g_arr, iterations, status, n_sv, int(launches[0]))
+    return SvrSplitResult(pred, tp, p.test_off, p.train_off, g_arr, iterations, status, n_sv, int(launches[0]), cached != 0)
 
 
 TREE_MAX_ROWS = 8192                             # PAA_TREE_MAX_ROWS: rows of one tree's training list
@@ -2413,6 +2503,61 @@ def train_svm_regression(features, labels, c_param, kernel='linear'):
     return svm, np.mean(np.abs(pred - labels))
 
 
+def train_svm_regression_device(features, labels, c_param, kernel='linear', *, kernel_cache="gram"):
+    """train_svm_regression on the GPU: SVR(C=c_param, kernel=kernel).fit(features, labels) as ONE task of svr_solve over all
+    rows (mean 0, scale 1, epsilon 0.1, tol 1e-3; gamma 'scale' = 1 / (n_dims * features.var()), 1 when that variance is 0, as
+    evaluate_regression's sweep forms it).  kernel_cache (keyword only) is svr_solve's, "gram" by default here: the one task
+    is solved from its resident kernel matrix.  Returns (an SvrArrays-shaped model that also carries support_, dual_coef_,
+    intercept_, C, epsilon, shape_fit_, n_features_in_ and fit_result, the mean absolute training error read from the
+    solver's gradient).  More than 8192 rows raise NotImplementedError before the library is asked; there is no CPU
+    fallback.  Agreement with scikit-learn is bounded by libsvm's stopping tolerance, not bit-exact."""
+    kernel = _svr_kernel(kernel)
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError("feature matrix of shape %s" % (X.shape,))
+    if X.shape[0] > SMO_MAX_ROWS:
+        raise NotImplementedError("%d training rows: the device solver serves at most %d per task" % (X.shape[0], SMO_MAX_ROWS))
+    n, n_dims = X.shape
+    y = _targets(labels, n)
+    var = X.var()
+    gamma = 1.0 / (n_dims * var) if kernel == "rbf" and var != 0 else 1.0
+    res = svr_solve(X, y, [(np.arange(n), np.zeros(n_dims), np.ones(n_dims), float(c_param), gamma, 0.1)], kernel=kernel,
+                    kernel_cache=kernel_cache)
+    beta = res.beta[0]
+    support = np.flatnonzero(beta != 0).astype(np.int32)
+    model = SvrArrays(X[support], beta[support], [-res.rho[0]], gamma, kernel)
+    model.support_ = support
+    model.dual_coef_, model.intercept_ = model._dual_coef_, model._intercept_
+    model.C, model.epsilon, model.shape_fit_, model.n_features_in_, model.fit_result = float(c_param), 0.1, X.shape, n_dims, res
+    return model, np.mean(np.abs(res.train_pred[0] - y))
+
+
+def to_sklearn_svr(model):
+    """A real sklearn.svm.SVR with the fitted attributes of train_svm_regression_device's model, filled as to_sklearn_svc fills
+    an SVC: it predicts as scikit-learn predicts from those arrays and pickles as the reference's model files do; regress,
+    regression_wrapper, load_model(..., is_regression=True) and file_regression read it unchanged.  Needs scikit-learn."""
+    import sklearn.svm
+    svr = sklearn.svm.SVR(C=float(model.C), kernel=model.kernel, epsilon=float(model.epsilon))
+    svr.support_ = np.asarray(model.support_, dtype=np.int32)
+    svr.support_vectors_ = np.ascontiguousarray(model.support_vectors_, dtype=np.float64)
+    svr._n_support = np.array([svr.support_.shape[0]] * 2, dtype=np.int32)     # as SVR.fit leaves it: the count, twice
+    svr._dual_coef_ = np.ascontiguousarray(model._dual_coef_, dtype=np.float64).reshape(1, -1)
+    svr._intercept_ = np.ascontiguousarray(model._intercept_, dtype=np.float64).reshape(-1)
+    svr.dual_coef_ = svr._dual_coef_
+    svr.intercept_ = svr._intercept_
+    svr._probA = np.zeros(0)
+    svr._probB = np.zeros(0)
+    svr._gamma = float(model._gamma)
+    svr._sparse = False
+    svr.shape_fit_ = tuple(model.shape_fit_)
+    svr.fit_status_ = 0
+    svr.n_features_in_ = int(model.n_features_in_)
+    fit = getattr(model, "fit_result", None)
+    svr._num_iter = np.array([0 if fit is None else fit.iterations[0]], dtype=np.int32)
+    svr.n_iter_ = int(svr._num_iter[0])
+    return svr
+
+
 def train_random_forest_regression(features, labels, n_estimators):
     """(fitted RandomForestRegressor, mean absolute training error) (reference :229-233), as train_svm_regression."""
     import sklearn.ensemble
@@ -2448,7 +2593,8 @@ def _check_forest_regression_fit(forest_fit, method_name):
         raise ValueError("forest_fit='device' serves the regression method 'randomforest', not %r" % (method_name,))
 
 
-def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit="sklearn", forest_fit="sklearn"):
+def evaluate_regression(features, labels, n_exp, method_name, params, *, kernel_cache="none", cache_bytes=None, svm_fit="sklearn",
+                        forest_fit="sklearn"):
     """Picks the parameter value with the lowest cross-validated squared error (reference :774-855): for every value,
     n_exp random 90 / 10 splits of the standardised samples.  np.random.permutation is consumed and the models are
     fitted in the reference's order (RandomForestRegressor draws from the same global state), by scikit-learn; the
@@ -2461,7 +2607,8 @@ def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit
     same splits under one seed), and ONE sweep (svr_split_fit_predict: epsilon-SVR with scikit-learn's defaults epsilon 0.1,
     gamma 'scale', tol 1e-3) fits and scores every split; the training errors come from the solver's gradient.  The errors,
     the baseline, the table and the return value are formed as above.  svm_fit="sklearn" (the default) is the behaviour
-    described above, untouched.
+    described above, untouched.  kernel_cache / cache_bytes (keyword only, read under svm_fit="device") are
+    svr_split_fit_predict's: "gram" solves every split from its resident kernel matrix, with the same bytes out.
     forest_fit="device" (keyword only; "randomforest", any other method raises ValueError): ALL len(params) x n_exp permutations
     are drawn up front, in the reference's order, THEN one forest seed per split with np.random.randint(np.iinfo(np.int32).max), in
     job order (the default mode interleaves every permutation with its forest's own draws, so the two modes see different splits
@@ -2472,6 +2619,7 @@ def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit
         raise NotImplementedError("regression method %r: 'svm', 'svm_rbf' or 'randomforest'" % (method_name,))
     _check_svr_fit(svm_fit, method_name)
     _check_forest_regression_fit(forest_fit, method_name)
+    _cache_mode(kernel_cache, cache_bytes)
     from sklearn.preprocessing import StandardScaler
     features_norm = StandardScaler().fit_transform(features)
     labels = np.asarray(labels)
@@ -2484,7 +2632,8 @@ def evaluate_regression(features, labels, n_exp, method_name, params, *, svm_fit
         all_perms = [[np.random.permutation(range(n_samples)) for _ in range(n_exp)] for _ in params]
         sweep = svr_split_fit_predict(features_norm, labels, [(perm[:n_train], perm[n_train:], zeros, ones, float(param))
                                                               for param, perms in zip(params, all_perms) for perm in perms],
-                                      kernel="rbf" if method_name == "svm_rbf" else "linear", train_pred=True)
+                                      kernel="rbf" if method_name == "svm_rbf" else "linear", train_pred=True,
+                                      kernel_cache=kernel_cache, cache_bytes=cache_bytes)
     if forest_fit == "device":                         # likewise: every permutation, then every forest's seed, then one sweep
         _check_targets(labels)
         _check_tree_rows(n_train, "a training split")
@@ -2531,7 +2680,8 @@ def save_parameters(path, *parameters):
 
 
 def feature_extraction_train_regression(folder_name, mid_window, mid_step, short_window, short_step, model_type, model_name,
-                                        compute_beat=False, *, svm_fit="sklearn", forest_fit="sklearn"):
+                                        compute_beat=False, *, svm_fit="sklearn", forest_fit="sklearn", final_fit="sklearn",
+                                        kernel_cache="none"):
     """Trains one regression model per CSV file of a folder of audio files (reference :370-489): every `<task>.csv` pairs
     file names with target values; features come from multiple_directory_feature_extraction (GPU), the parameter from
     evaluate_regression, the final fit from scikit-learn; `model_name_<task>` and `model_name_<task>MEANS` are written as
@@ -2539,9 +2689,17 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
     and the model file, a pickled SVR, stay scikit-learn's.  forest_fit (keyword only, "randomforest") goes to evaluate_regression
     too; with "device" the final fit is train_random_forest_regression_device and the model file is the pickled
     to_sklearn_forest_regressor of its arrays, a real RandomForestRegressor that load_model(..., is_regression=True) and
-    file_regression read unchanged.  Returns (errors, baseline errors, best parameters)."""
+    file_regression read unchanged.  final_fit="device" (keyword only; "svm" / "svm_rbf", any other type raises ValueError):
+    the final model is to_sklearn_svr(train_svm_regression_device(...)) at the chosen C, a real SVR pickled in the reference's
+    format; svm_fit="device" alone keeps writing scikit-learn's fit.  kernel_cache (keyword only) goes to evaluate_regression
+    and to that final fit.  Returns (errors, baseline errors, best parameters)."""
     _check_svr_fit(svm_fit, model_type)
     _check_forest_regression_fit(forest_fit, model_type)
+    if final_fit not in ("sklearn", "device"):
+        raise ValueError("final_fit=%r: 'sklearn' or 'device'" % (final_fit,))
+    if final_fit == "device" and model_type not in _SVM_TYPES:
+        raise ValueError("final_fit='device' serves the regression methods %s, not %r" % (" and ".join(_SVM_TYPES), model_type))
+    _cache_mode(kernel_cache, None)
     import csv
     import glob
     import ntpath
@@ -2575,7 +2733,8 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
     errors, errors_base, best_params = [], [], []
     for X, y, name in zip(task_features, task_labels, task_names):
         print("Regression task " + name)
-        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params, svm_fit=svm_fit, forest_fit=forest_fit)
+        best, error, base_error = evaluate_regression(X, y, 100, model_type, model_params, svm_fit=svm_fit, forest_fit=forest_fit,
+                                                      kernel_cache=kernel_cache)
         errors.append(error)
         errors_base.append(base_error)
         best_params.append(best)
@@ -2585,6 +2744,9 @@ def feature_extraction_train_regression(folder_name, mid_window, mid_step, short
         if model_type in _REGRESSION_TYPES:
             if forest_fit == "device":
                 model = to_sklearn_forest_regressor(train_random_forest_regression_device(X_norm, y, int(best))[0])
+            elif final_fit == "device":
+                model = to_sklearn_svr(train_svm_regression_device(X_norm, y, best, "rbf" if model_type == "svm_rbf" else "linear",
+                                                                   kernel_cache=kernel_cache)[0])
             else:
                 model = _fit_regressor(X_norm, y, model_type, best)
             with open(model_name + "_" + name, "wb") as fo:

@@ -8,6 +8,7 @@
 #include "model_launch.hpp"
 #include "kernels_svr.hpp"
 #include "kernels_svrfit.hpp"
+#include "kernels_svrcache.hpp"
 
 namespace paa {
 namespace launch {
@@ -33,6 +34,31 @@ int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_m
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return -1;
     hipLaunchKernelGGL(svrfit::svr_smo_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), lds, stream, m, d_live, budget);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int svr_gram(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_chunk, int n_chunk, int n_max,
+             const svrfit::GramTile *d_tiles, long long n_tiles, hipStream_t stream) {
+    static_assert(svrfit::kGramTile == smo::kGroups && svrfit::kPitchLanes == smo::kGroupLanes, "one row of a tile per group");
+    if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > smo::kMaxRows) return -2;
+    if (n_chunk < 1 || n_tiles < 1 || n_tiles > 0x7fffffffLL) return -1;
+    const int pitch = (m.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
+    const unsigned row_blocks = (unsigned)((n_max + svrfit::kGramTile - 1) / svrfit::kGramTile);
+    hipLaunchKernelGGL(svrfit::svr_standardise_kernel, dim3((unsigned)n_chunk, row_blocks), dim3(smo::kThreads), 0, stream, m, c, d_chunk);
+    if (hipGetLastError() != hipSuccess) return -1;
+    const size_t lds = ((size_t)svrfit::kGramTile * pitch + svrfit::kGramTile * (svrfit::kGramTile + 1)) * sizeof(double);
+    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&svrfit::svr_gram_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL(svrfit::svr_gram_kernel, dim3((unsigned)n_tiles), dim3(smo::kThreads), lds, stream, m, c, d_tiles);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int svr_smo_cached_step(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_live, int n_live, int n_max, int budget,
+                        hipStream_t stream) {
+    if (n_max < 1 || n_max > smo::kMaxRows) return -2;
+    if (n_live < 1 || budget < 1) return -1;
+    hipLaunchKernelGGL(svrfit::svr_smo_cached_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), 0, stream, m, c, d_live, budget);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -54,22 +54,20 @@ static int smo_state_alloc(SmoState &s, smo::SmoDev &m, size_t rows, size_t n_ta
     return PAA_OK;
 }
 
-// The relaunch loop of a batch of solver tasks (smo_kernel; svr_smo_kernel of lib_svrfit.hpp): step(n_live, n_max, budget) gives
-// each of the n_live unfinished tasks listed in d_live (n_max: the longest of them) at most `budget` iterations
-// (iters_per_launch, 0: the default), the host reads the status words d_status [n_tasks], compacts the unfinished tasks and
-// launches again.  status [n_tasks] ends as smo::kConverged / kNotConverged
+// The relaunch loop of a batch of solver tasks (smo_kernel; svr_smo_kernel and svr_smo_cached_kernel of lib_svrfit.hpp):
+// step(n_live, n_max, budget) gives each of the n_live unfinished tasks listed in d_live (n_max: the longest of them) at most `budget`
+// iterations (iters_per_launch, 0: the default), the host reads the status words d_status [n_tasks], compacts the unfinished tasks
+// and launches again.  smo_relaunch_some runs the tasks of `live` alone and adds its launches to `launches`; status [n_tasks] is the
+// caller's and ends as smo::kConverged / kNotConverged for those tasks
 template <typename Step>
-static int smo_relaunch(const std::vector<smo::SmoTask> &tasks, int max_iter, int iters_per_launch, int *d_live, const int *d_status,
-                        std::vector<int> &status, int *n_launches, Step step) {
+static int smo_relaunch_some(const std::vector<smo::SmoTask> &tasks, std::vector<int> live, int max_iter, int iters_per_launch, int *d_live,
+                             const int *d_status, std::vector<int> &status, long long &launches, Step step) {
     const int budget = iters_per_launch ? iters_per_launch : smo::kDefaultItersPerLaunch;
     const int n_tasks = (int)tasks.size();
-    std::vector<int> live(n_tasks);
-    for (int t = 0; t < n_tasks; ++t) live[t] = t;
-    status.assign(n_tasks, smo::kFresh);
     const long long launch_cap = (long long)max_iter / budget + 2;       // every launch advances every live task by `budget`
-    long long launches = 0;
+    long long mine = 0;
     while (!live.empty()) {
-        if (launches++ >= launch_cap) return fail(PAA_ERR_HIP, "the solver made no progress in %lld launches", launch_cap);
+        if (mine++ >= launch_cap) return fail(PAA_ERR_HIP, "the solver made no progress in %lld launches", launch_cap);
         int n_max = 0;
         for (int t : live) n_max = std::max(n_max, tasks[t].n);
         HIP_TRY(hipMemcpyAsync(d_live, live.data(), live.size() * 4, hipMemcpyHostToDevice, cs()));
@@ -82,6 +80,19 @@ static int smo_relaunch(const std::vector<smo::SmoTask> &tasks, int max_iter, in
             if (status[t] < smo::kConverged) live[kept++] = t;
         live.resize(kept);
     }
+    launches += mine;
+    return PAA_OK;
+}
+template <typename Step>
+static int smo_relaunch(const std::vector<smo::SmoTask> &tasks, int max_iter, int iters_per_launch, int *d_live, const int *d_status,
+                        std::vector<int> &status, int *n_launches, Step step) {
+    const int n_tasks = (int)tasks.size();
+    std::vector<int> live(n_tasks);
+    for (int t = 0; t < n_tasks; ++t) live[t] = t;
+    status.assign(n_tasks, smo::kFresh);
+    long long launches = 0;
+    int rc;
+    if ((rc = smo_relaunch_some(tasks, live, max_iter, iters_per_launch, d_live, d_status, status, launches, step))) return rc;
     if (n_launches) *n_launches = (int)launches;
     return PAA_OK;
 }

@@ -2,7 +2,10 @@
 // a batch of epsilon-SVR dual problems (tasks) over ONE uploaded sample matrix and its targets, solved by relaunching
 // svr_smo_kernel until every task has stopped (smo_relaunch, lib_smo.hpp), and the split sweep built on it: one task per job,
 // then svc_pairs_kernel over the test rows, a job being one "pair" whose alpha_y is beta -- its decision value is the prediction.
-// Kernels: kernels_svrfit.hpp (family_svr.hip), kernels_smo.hpp (family_smo.hip).
+// With a resident kernel matrix (DESIGN K22, the *_cached_f64 entry points) the tasks are packed into chunks whose n x n matrices fit
+// `cache_bytes`; per chunk: svr_standardise_kernel, svr_gram_kernel, then smo_relaunch_some with svr_smo_cached_kernel, then the
+// scratch serves the next chunk.  A task whose matrix alone exceeds the budget goes to svr_smo_kernel in the same call.
+// Kernels: kernels_svrfit.hpp and kernels_svrcache.hpp (family_svr.hip), kernels_smo.hpp (family_smo.hip).
 #pragma once
 
 // what a task adds to smo_task_check: the width of its tube
@@ -53,6 +56,129 @@ static int svr_solve_batch(svrfit::SvrDev &m, SvrFitState &s, const std::vector<
     });
 }
 
+// The packing rule of the resident matrices: the matrix of a task of n rows takes 8 n^2 bytes (its standardised rows and the tile list
+// ride along uncounted).  In task order: a task whose matrix exceeds `cache_bytes` is not cached; any other joins the open chunk when
+// the chunk's matrices and its own fit the budget together, and otherwise closes it and opens the next.  chunk_of [n_tasks]: the
+// task's chunk from 0, -1 when it is not cached.  Returns the number of chunks
+static int svr_cache_pack(const std::vector<smo::SmoTask> &tasks, int64_t cache_bytes, std::vector<int> &chunk_of) {
+    chunk_of.assign(tasks.size(), -1);
+    int n_chunks = 0;
+    int64_t used = 0;
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        const int64_t bytes = (int64_t)tasks[t].n * tasks[t].n * 8;
+        if (bytes > cache_bytes) continue;
+        if (n_chunks == 0 || used + bytes > cache_bytes) { ++n_chunks; used = 0; }
+        used += bytes;
+        chunk_of[t] = n_chunks - 1;
+    }
+    return n_chunks;
+}
+
+// The resident matrices of a call, freed on return: K | Z of the largest chunk, k_off | z_off [tasks], the chunk's task list and its
+// tile pairs
+struct SvrCache {
+    DevBlock block;
+    svrfit::SvrCacheDev dev{};
+    int *chunk = nullptr;
+    svrfit::GramTile *tiles = nullptr;
+    std::vector<int> chunk_of;
+    int n_chunks = 0;
+    std::vector<long long> off;           // k_off | z_off on the host
+};
+static long long svr_tile_pairs(int n) {
+    const long long nt = (n + svrfit::kGramTile - 1) / svrfit::kGramTile;
+    return nt * (nt + 1) / 2;
+}
+// packs the tasks and allocates for the largest chunk (nothing when no task is cached)
+static int svr_cache_alloc(SvrCache &c, const std::vector<smo::SmoTask> &tasks, int n_dims, int64_t cache_bytes) {
+    const size_t n_tasks = tasks.size();
+    c.n_chunks = svr_cache_pack(tasks, cache_bytes, c.chunk_of);
+    if (!c.n_chunks) return PAA_OK;
+    const long long pitch = (n_dims + svrfit::kPitchLanes - 1) / svrfit::kPitchLanes * svrfit::kPitchLanes;
+    std::vector<long long> k_sum(c.n_chunks, 0), z_sum(c.n_chunks, 0), tile_sum(c.n_chunks, 0), count(c.n_chunks, 0);
+    c.off.assign(2 * n_tasks, 0);
+    for (size_t t = 0; t < n_tasks; ++t) {
+        const int ch = c.chunk_of[t];
+        if (ch < 0) continue;
+        const long long n = tasks[t].n;
+        c.off[t] = k_sum[ch];
+        c.off[n_tasks + t] = z_sum[ch];
+        k_sum[ch] += n * n;
+        z_sum[ch] += n * pitch;
+        tile_sum[ch] += svr_tile_pairs(tasks[t].n);
+        ++count[ch];
+    }
+    const size_t b_k = up256((size_t)*std::max_element(k_sum.begin(), k_sum.end()) * 8);
+    const size_t b_z = up256((size_t)*std::max_element(z_sum.begin(), z_sum.end()) * 8);
+    const size_t b_off = up256(2 * n_tasks * 8), b_chunk = up256((size_t)*std::max_element(count.begin(), count.end()) * 4);
+    const size_t b_tiles = (size_t)*std::max_element(tile_sum.begin(), tile_sum.end()) * sizeof(svrfit::GramTile);
+    HIP_TRY(hipMalloc(&c.block.p, b_k + b_z + b_off + b_chunk + b_tiles));
+    char *p = (char *)c.block.p;
+    c.dev.K = (double *)p;                  p += b_k;
+    c.dev.Z = (double *)p;                  p += b_z;
+    c.dev.k_off = (const long long *)p;
+    c.dev.z_off = (const long long *)p + n_tasks;
+    HIP_TRY(hipMemcpyAsync(p, c.off.data(), 2 * n_tasks * 8, hipMemcpyHostToDevice, cs()));
+    p += b_off;
+    c.chunk = (int *)p;                     p += b_chunk;
+    c.tiles = (svrfit::GramTile *)p;
+    return PAA_OK;
+}
+// forms Z and K of chunk `ch`; `members` returns its tasks
+static int svr_cache_fill(const SvrCache &c, const svrfit::SvrDev &m, const std::vector<smo::SmoTask> &tasks, int ch, std::vector<int> &members) {
+    members.clear();
+    std::vector<svrfit::GramTile> tiles;
+    int n_max = 0;
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        if (c.chunk_of[t] != ch) continue;
+        members.push_back((int)t);
+        n_max = std::max(n_max, tasks[t].n);
+        const int nt = (tasks[t].n + svrfit::kGramTile - 1) / svrfit::kGramTile;
+        for (int a = 0; a < nt; ++a)
+            for (int b = a; b < nt; ++b) tiles.push_back({(int)t, a, b});
+    }
+    HIP_TRY(hipMemcpy(c.chunk, members.data(), members.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c.tiles, tiles.data(), tiles.size() * sizeof(svrfit::GramTile), hipMemcpyHostToDevice));
+    LAUNCH_TRY("SVR Gram", launch::svr_gram(m, c.dev, c.chunk, (int)members.size(), n_max, c.tiles, (long long)tiles.size(), cs()));
+    return PAA_OK;
+}
+
+// svr_solve_batch with resident matrices under the budget cache_bytes; cached [tasks]: 1 for a task solved from its matrix
+static int svr_solve_batch_cached(svrfit::SvrDev &m, SvrFitState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, size_t n_q,
+                                  int iters_per_launch, std::vector<int> &status, int *n_launches, int64_t cache_bytes, int32_t *cached) {
+    int rc;
+    if ((rc = svr_state_alloc(s, m, rows, tasks.size(), n_q))) return rc;
+    SvrCache c;
+    if ((rc = svr_cache_alloc(c, tasks, m.n_dims, cache_bytes))) return rc;
+    status.assign(tasks.size(), smo::kFresh);
+    long long launches = 0;
+    std::vector<int> members;
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        cached[t] = c.chunk_of[t] >= 0;
+        if (!cached[t]) members.push_back((int)t);
+    }
+    if (!members.empty() &&
+        (rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, [&](int n_live, int n_max, int budget) {
+             LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
+             return (int)PAA_OK;
+         })))
+        return rc;
+    for (int ch = 0; ch < c.n_chunks; ++ch) {
+        if ((rc = svr_cache_fill(c, m, tasks, ch, members))) return rc;
+        if ((rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, [&](int n_live, int n_max, int budget) {
+                 LAUNCH_TRY("cached SVR SMO", launch::svr_smo_cached_step(m, c.dev, s.live, n_live, n_max, budget, cs()));
+                 return (int)PAA_OK;
+             })))
+            return rc;
+    }
+    if (n_launches) *n_launches = (int)launches;
+    return PAA_OK;
+}
+static int svr_cache_args_check(int64_t cache_bytes) {
+    if (cache_bytes <= 0) return fail(PAA_ERR_ARG, "cache_bytes = %lld: a positive budget is needed", (long long)cache_bytes);
+    return PAA_OK;
+}
+
 // the solver's view of an uploaded batch: the staged matrix, the uploaded y | tasks | epsilon | mean | scale | idx and the parameters
 static svrfit::SvrDev svr_dev(const double *X, const BlockPart &y, const BlockPart &tasks, const BlockPart &epsilon, const BlockPart &mean,
                               const BlockPart &scale, const BlockPart &idx, int n_dims, int kernel_type, double eps, int max_iter) {
@@ -85,13 +211,14 @@ static int svr_tasks(std::vector<smo::SmoTask> &tasks, int n, const int64_t *lis
 }
 
 // The solver alone (libsvm's solve_epsilon_svr over Solver::Solve, svm.cpp, as svm_train_one runs it under SVR.fit): see paa_hip.h
-extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
-                                 const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
-                                 const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
-                                 double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
-                                 int32_t *n_launches) {
+// (use_cache false: paa_svr_tasks_f64; true: paa_svr_tasks_cached_f64 with its budget and flags)
+static int svr_tasks_run(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                         const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                         const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta, double *rho,
+                         int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred, int32_t *n_launches,
+                         bool use_cache, int64_t cache_bytes, int32_t *cached) {
     if (!X || !y || !task_off || !task_idx || !mean || !std || !C || !gamma || !epsilon || !beta || !rho || !iterations || !gap || !status ||
-        !n_sv || !train_pred)
+        !n_sv || !train_pred || (use_cache && !cached))
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -103,6 +230,7 @@ extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     if ((rc = svr_tasks(tasks, n_tasks, task_off, C, gamma, epsilon, kernel_type))) return rc;
     if ((rc = sweep_index_check(task_idx, rows, n_samples, "row"))) return rc;
     if ((rc = svr_targets_check(y, n_samples))) return rc;
+    if (use_cache && (rc = svr_cache_args_check(cache_bytes))) return rc;
     if ((rc = ensure_init())) return rc;
     const size_t sb = (size_t)n_tasks * n_dims * 8;
     DevBlock block;
@@ -114,7 +242,9 @@ extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[5], n_dims, kernel_type, eps, max_iter);
     SvrFitState s;
     std::vector<int> st_words;
-    if ((rc = svr_solve_batch(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches))) return rc;
+    if ((rc = use_cache ? svr_solve_batch_cached(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches, cache_bytes, cached)
+                        : svr_solve_batch(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches)))
+        return rc;
     HIP_TRY(hipMemcpyAsync(beta, m.beta, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(train_pred, m.train_pred, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(rho, m.rho, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
@@ -125,16 +255,88 @@ extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     std::copy(st_words.begin(), st_words.end(), status);
     return PAA_OK;
 }
+extern "C" int paa_svr_tasks_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                                 const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                                 const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
+                                 double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
+                                 int32_t *n_launches) {
+    return svr_tasks_run(X, n_samples, n_dims, y, n_tasks, task_off, task_idx, mean, std, C, gamma, epsilon, kernel_type, eps, max_iter,
+                         iters_per_launch, beta, rho, iterations, gap, status, n_sv, train_pred, n_launches, false, 0, nullptr);
+}
+extern "C" int paa_svr_tasks_cached_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_tasks, const int64_t *task_off,
+                                        const int32_t *task_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                                        const double *epsilon, int kernel_type, double eps, int max_iter, int iters_per_launch, double *beta,
+                                        double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_sv, double *train_pred,
+                                        int32_t *n_launches, int64_t cache_bytes, int32_t *cached) {
+    return svr_tasks_run(X, n_samples, n_dims, y, n_tasks, task_off, task_idx, mean, std, C, gamma, epsilon, kernel_type, eps, max_iter,
+                         iters_per_launch, beta, rho, iterations, gap, status, n_sv, train_pred, n_launches, true, cache_bytes, cached);
+}
+
+// The matrices alone (svr_standardise_kernel, svr_gram_kernel) of a task list, all in one chunk, and on request the K_tt that
+// svr_smo_kernel itself forms at a task's start: see paa_hip.h
+extern "C" int paa_svr_gram_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off, const int32_t *task_idx,
+                                const double *mean, const double *std, const double *gamma, int kernel_type, double *K_out, double *qd_out) {
+    if (!X || !task_off || !task_idx || !mean || !std || !gamma || !K_out) return fail(PAA_ERR_ARG, "null argument");
+    int rc;
+    if ((rc = sweep_samples_check(n_samples))) return rc;
+    if ((rc = smo_params_check(n_dims, kernel_type, 1.0, 1, 0))) return rc;
+    if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
+    if ((rc = sweep_offsets_check(task_off, n_tasks, "task"))) return rc;
+    const int64_t rows = task_off[n_tasks];
+    std::vector<smo::SmoTask> tasks(n_tasks);
+    for (int t = 0; t < n_tasks; ++t) {
+        if ((rc = smo_task_check(t, task_off[t + 1] - task_off[t], 1.0, gamma[t], kernel_type))) return rc;
+        tasks[t] = {(long long)task_off[t], (int)(task_off[t + 1] - task_off[t]), t, 1.0, gamma[t]};
+    }
+    if ((rc = sweep_index_check(task_idx, rows, n_samples, "row"))) return rc;
+    if ((rc = ensure_init())) return rc;
+    // zero targets and a zero tube: svr_smo_kernel forms K_tt, finds no violating pair and stops
+    const std::vector<double> zeros((size_t)std::max<int64_t>(n_samples, n_tasks), 0.0);
+    const size_t sb = (size_t)n_tasks * n_dims * 8;
+    DevBlock block;
+    BlockPart parts[] = {{zeros.data(), (size_t)n_samples * 8, 8}, {tasks.data(), tasks.size() * sizeof(smo::SmoTask), 8},
+                         {zeros.data(), (size_t)n_tasks * 8, 8}, {mean, sb, 8}, {std, sb, 8}, {task_idx, (size_t)rows * 4, 4}};
+    if ((rc = block_upload(block, parts, 6, "the SVR tasks"))) return rc;
+    Staged st;
+    if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
+    svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[5], n_dims, kernel_type, 1.0, 1);
+    SvrFitState s;
+    if ((rc = svr_state_alloc(s, m, (size_t)rows, tasks.size(), 0))) return rc;
+    SvrCache c;
+    if ((rc = svr_cache_alloc(c, tasks, n_dims, INT64_MAX))) return rc;
+    std::vector<int> members;
+    if ((rc = svr_cache_fill(c, m, tasks, 0, members))) return rc;
+    for (int t = 0; t < n_tasks; ++t) {
+        const size_t n = (size_t)tasks[t].n;
+        HIP_TRY(hipMemcpyAsync(K_out, c.dev.K + c.off[t], n * n * 8, hipMemcpyDeviceToHost, cs()));
+        K_out += n * n;
+    }
+    if (qd_out) {
+        std::vector<int> st_words(n_tasks, smo::kFresh);
+        long long launches = 0;
+        if ((rc = smo_relaunch_some(tasks, members, 1, 1, s.live, m.status, st_words, launches, [&](int n_live, int n_max, int budget) {
+                 LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
+                 return (int)PAA_OK;
+             })))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(qd_out, m.QD, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
+    }
+    HIP_TRY(hipStreamSynchronize(cs()));
+    return PAA_OK;
+}
 
 // The SVR half of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855): every split a job, every job one task over its
 // training list; see paa_hip.h
-extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
-                                      const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
-                                      const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type,
-                                      double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
-                                      int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches) {
+// (use_cache false: paa_svr_fit_splits_f64; true: paa_svr_fit_splits_cached_f64 with its budget and flags)
+static int svr_fit_splits_run(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
+                              const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                              const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type, double eps,
+                              int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out, int32_t *job_iterations,
+                              int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches, bool use_cache, int64_t cache_bytes,
+                              int32_t *cached) {
     // check
-    if (!X || !y || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !epsilon || !pred_out)
+    if (!X || !y || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !epsilon || !pred_out ||
+        (use_cache && !cached))
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -146,6 +348,7 @@ extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_
     std::vector<smo::SmoTask> tasks;
     if ((rc = svr_tasks(tasks, n_jobs, train_off, C, gamma, epsilon, kernel_type))) return rc;
     if ((rc = svr_targets_check(y, n_samples))) return rc;
+    if (use_cache && (rc = svr_cache_args_check(cache_bytes))) return rc;
     if ((rc = ensure_init())) return rc;
     // upload: a job is the one pair of two "classes" for the scoring kernel, its task the job's own number
     const std::vector<knn::SplitBlock> blocks = sweep_blocks(test_off, n_jobs, smo::kQueriesPerBlock);
@@ -172,7 +375,9 @@ extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_
     svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[7], n_dims, kernel_type, eps, max_iter);
     SvrFitState s;
     std::vector<int> st_words;
-    if ((rc = svr_solve_batch(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches))) return rc;
+    if ((rc = use_cache ? svr_solve_batch_cached(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches, cache_bytes, cached)
+                        : svr_solve_batch(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches)))
+        return rc;
     if (job_iterations) HIP_TRY(hipMemcpyAsync(job_iterations, m.iter, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
     if (job_n_sv) HIP_TRY(hipMemcpyAsync(job_n_sv, m.n_sv, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
     if (train_pred_out) HIP_TRY(hipMemcpyAsync(train_pred_out, m.train_pred, (size_t)n_t * 8, hipMemcpyDeviceToHost, cs()));
@@ -198,4 +403,24 @@ extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_
         LAUNCH_TRY("SVR scoring", launch::svc_pairs(f, (long long)blocks.size(), s.label, (double *)st.out[0], cs()));
     }
     return finish(st);
+}
+extern "C" int paa_svr_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs, const int64_t *train_off,
+                                      const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                                      const double *std, const double *C, const double *gamma, const double *epsilon, int kernel_type,
+                                      double eps, int max_iter, int iters_per_launch, double *pred_out, double *train_pred_out,
+                                      int32_t *job_iterations, int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches) {
+    return svr_fit_splits_run(X, n_samples, n_dims, y, n_jobs, train_off, train_idx, test_off, test_idx, mean, std, C, gamma, epsilon,
+                              kernel_type, eps, max_iter, iters_per_launch, pred_out, train_pred_out, job_iterations, job_status, job_n_sv,
+                              n_launches, false, 0, nullptr);
+}
+extern "C" int paa_svr_fit_splits_cached_f64(const double *X, int64_t n_samples, int n_dims, const double *y, int n_jobs,
+                                             const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                             const int32_t *test_idx, const double *mean, const double *std, const double *C,
+                                             const double *gamma, const double *epsilon, int kernel_type, double eps, int max_iter,
+                                             int iters_per_launch, double *pred_out, double *train_pred_out, int32_t *job_iterations,
+                                             int32_t *job_status, int32_t *job_n_sv, int32_t *n_launches, int64_t cache_bytes,
+                                             int32_t *job_cached) {
+    return svr_fit_splits_run(X, n_samples, n_dims, y, n_jobs, train_off, train_idx, test_off, test_idx, mean, std, C, gamma, epsilon,
+                              kernel_type, eps, max_iter, iters_per_launch, pred_out, train_pred_out, job_iterations, job_status, job_n_sv,
+                              n_launches, true, cache_bytes, job_cached);
 }

@@ -178,6 +178,18 @@ struct SvrDev {
     int n_dims, rbf, max_iter;
     double eps;
 };
+// the resident kernel matrices of a chunk of tasks (kernels_svrcache.hpp): Z [n][pitch], a task's standardised rows (pitch = 8 ceil(n_dims
+// / 8), zero beyond n_dims), at z_off[task]; K [n][n], full, at k_off[task].  Offsets count doubles and are 64-bit: a chunk may pass 4 GiB
+constexpr int kGramTile = 32;             // svr_gram_kernel: rows of a tile, one per 8-lane group of the workgroup
+constexpr int kPitchLanes = 8;            // kv::kGroupLanes: a row of Z is padded to a multiple of it
+struct SvrCacheDev {
+    double *Z, *K;
+    const long long *z_off, *k_off;       // [n_tasks]; read for the tasks of the current chunk only
+};
+// a workgroup of svr_gram_kernel: the tile pair (a, b), a <= b, of a task
+struct GramTile {
+    int task, a, b;
+};
 }  // namespace svrfit
 namespace forest {
 constexpr int kMaxClasses = 64;
@@ -369,6 +381,12 @@ int onset_proba(const onset::OnsetDev &m, int n_clips, long long n_frames, hipSt
 int onset_threshold(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
 // kernels_svrfit.hpp: smo_step for a batch of epsilon-SVR tasks (the limits are the SMO solver's)
 int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
+// kernels_svrcache.hpp: Z then K of the n_chunk tasks listed in d_chunk (n_max: the longest of them; d_tiles: every tile pair of every
+// one of them), and svr_smo_step over resident matrices
+int svr_gram(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_chunk, int n_chunk, int n_max,
+             const svrfit::GramTile *d_tiles, long long n_tiles, hipStream_t stream);
+int svr_smo_cached_step(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_live, int n_live, int n_max, int budget,
+                        hipStream_t stream);
 // kernels_forest.hpp: tree-ensemble classification of the columns of feats [n_dims][ld] (per chunk of forest::kChunk windows
 // two kernels: every (window, tree)'s leaf slot goes to `leaves` [n_trees][kChunk]; then labels [n_vec] (-1: a value is
 // infinite in float32, -2: boosted and a value is NaN), the tree sums / raw scores raw [n_vec][n_outputs] and the

@@ -14,6 +14,15 @@ below libsvm's 10^7 its timing is skipped for a kernel whose capped sweep left t
 speed-up is promised by this script: it states what was measured.
 
     python scripts/bench_svr_fit.py [--samples 2000] [--n-exp 100] [--sklearn-jobs 1]
+
+--cache compares the resident kernel matrix (kernel_cache="gram", kernels_svrcache.hpp) with the recomputing solver
+(kernel_cache="none") instead and writes profiles/bench_svr_cache_n1_local.json: per kernel and mode the device time of the
+sweep and of the final fit (ONE task over all samples at the value of C with the least test error of the sweep, what
+train_svm_regression_device solves), medians of --rounds rounds after a warm-up; the same sweep with max_iter = 1 under "gram"
+(uploads, the standardise and Gram kernels, one iteration, scoring: an upper bound of the Gram pass's share); whether the two
+modes returned the same bytes; scikit-learn on one core on one split per value of C, under the same iteration cap.
+
+    python scripts/bench_svr_fit.py --cache --n-exp 10 --max-iter 200000
 """
 import argparse
 import contextlib
@@ -45,6 +54,100 @@ def regression_data(n, seed=23):
     return U * rng.uniform(0.5, 3.0, DIMS) + rng.uniform(-2.0, 2.0, DIMS), y
 
 
+def cache_compare(args, aT, Z, y, jobs):
+    """The --cache record (see the module docstring)."""
+    n = Z.shape[0]
+    geo = aT.smo_geometry()
+    out = {"samples": n, "dims": DIMS, "params": PARAMS, "n_exp": args.n_exp, "jobs": len(jobs), "rows_per_task": len(jobs[0][0]),
+           "max_iter": args.max_iter, "iters_per_launch": geo[4], "rounds": args.rounds, "cache_bytes": aT.SVR_CACHE_BYTES,
+           "matrix_bytes_per_task": 8 * len(jobs[0][0]) ** 2, "kernels": {}}
+
+    def save():
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+    def timed(fn, slow_s=120.0):
+        """(median device seconds, every round, the last result): --rounds rounds, one when the first takes longer than slow_s."""
+        times, res = [], None
+        for _ in range(args.rounds):
+            t, res = event_time(fn)
+            times.append(t)
+            if t > slow_s:
+                break
+        return float(np.median(times)), times, res
+
+    all_rows, zeros, ones = np.arange(n), np.zeros(DIMS), np.ones(DIMS)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for mode in ("none", "gram"):                    # warm-up: library, lane scratch, both solvers' code
+            aT.svr_split_fit_predict(Z, y, jobs[:2], max_iter=10, kernel_cache=mode)
+        for kind in args.kinds.split(","):
+            kernel = "rbf" if kind == "svm_rbf" else "linear"
+            rec = {}
+            out["kernels"][kind] = rec
+            sweeps = {}
+            for mode in ("gram", "none"):
+                med, times, res = timed(lambda: aT.svr_split_fit_predict(Z, y, jobs, kernel=kernel, train_pred=True, max_iter=args.max_iter,
+                                                                         kernel_cache=mode))
+                sweeps[mode] = res
+                rec["sweep_%s_device_s" % mode], rec["sweep_%s_rounds_s" % mode] = med, times
+                print("%s %s: sweep %.3f s (%d rounds), %d launches" % (kind, mode, med, len(times), res.n_launches), file=sys.stderr, flush=True)
+                save()
+            a, b = sweeps["none"], sweeps["gram"]
+            rec["sweep_bytes_equal"] = bool(a.pred.tobytes() == b.pred.tobytes() and a.train_pred.tobytes() == b.train_pred.tobytes() and
+                                            np.array_equal(a.iterations, b.iterations) and np.array_equal(a.n_sv, b.n_sv))
+            rec.update({"tasks_cached": int(b.cached.sum()), "iterations_total": int(b.iterations.sum()), "iterations_max": int(b.iterations.max()),
+                        "not_converged": int(np.count_nonzero(b.status == aT.SMO_NOT_CONVERGED)), "solver_launches": b.n_launches})
+            rec["sweep_gram_max_iter_1_device_s"], rec["sweep_gram_max_iter_1_rounds_s"], _ = timed(
+                lambda: aT.svr_split_fit_predict(Z, y, jobs, kernel=kernel, train_pred=True, max_iter=1, kernel_cache="gram"))
+            rec["gram_pass_share_of_sweep_at_most"] = rec["sweep_gram_max_iter_1_device_s"] / rec["sweep_gram_device_s"]
+            rec["sweep_speedup_gram_over_none"] = rec["sweep_none_device_s"] / rec["sweep_gram_device_s"]
+            # the sweep lasts as long as its longest task: its time over that task's iterations bounds the time per iteration from above
+            rec["device_us_per_iteration_of_the_longest_task_none"] = 1e6 * rec["sweep_none_device_s"] / rec["iterations_max"]
+            rec["device_us_per_iteration_of_the_longest_task_gram"] = 1e6 * rec["sweep_gram_device_s"] / rec["iterations_max"]
+            mse = [float(np.mean([np.mean((b.job(p * args.n_exp + e)[0] - y[jobs[p * args.n_exp + e][1]]) ** 2) for e in range(args.n_exp)]))
+                   for p in range(len(PARAMS))]
+            C = PARAMS[int(np.argmin(mse))]
+            gamma = 1.0 / (DIMS * Z.var()) if kernel == "rbf" else 1.0
+            rec["final_fit_C"], rec["final_fit_rows"] = C, n
+            fits = {}
+            for mode in ("gram", "none"):
+                med, times, fits[mode] = timed(lambda: aT.svr_solve(Z, y, [(all_rows, zeros, ones, C, gamma, 0.1)], kernel=kernel,
+                                                                    max_iter=args.max_iter, kernel_cache=mode))
+                rec["final_fit_%s_device_s" % mode], rec["final_fit_%s_rounds_s" % mode] = med, times
+            rec["final_fit_iterations"] = int(fits["gram"].iterations[0])
+            rec["final_fit_bytes_equal"] = bool(fits["gram"].beta[0].tobytes() == fits["none"].beta[0].tobytes() and
+                                                fits["gram"].rho.tobytes() == fits["none"].rho.tobytes())
+            rec["final_fit_speedup_gram_over_none"] = rec["final_fit_none_device_s"] / rec["final_fit_gram_device_s"]
+            save()
+            rec["sklearn_sweep_s"] = rec["sklearn_final_fit_s"] = None
+            try:
+                import sklearn.svm
+                from threadpoolctl import threadpool_limits
+                with threadpool_limits(limits=1):
+                    per_param = []
+                    for p, Cp in enumerate(PARAMS):
+                        tr, te = jobs[p * args.n_exp][:2]
+                        t0 = time.perf_counter()
+                        sklearn.svm.SVR(C=Cp, kernel=kernel, max_iter=args.max_iter).fit(Z[tr], y[tr]).predict(Z[te])
+                        per_param.append(time.perf_counter() - t0)
+                        print("%s: scikit-learn C=%g %.2f s" % (kind, Cp, per_param[-1]), file=sys.stderr, flush=True)
+                    t0 = time.perf_counter()
+                    sklearn.svm.SVR(C=C, kernel=kernel, max_iter=args.max_iter).fit(Z, y)
+                    rec["sklearn_final_fit_s"] = time.perf_counter() - t0
+                rec["sklearn_s_per_fit_per_param"] = per_param
+                rec["sklearn_sweep_s"] = float(np.sum(per_param) * args.n_exp)
+                rec["sklearn_note"] = ("one fit + predict per value of C on one core under max_iter = %d, scaled to %d experiments; one "
+                                       "round" % (args.max_iter, args.n_exp))
+            except ImportError:
+                pass
+            save()
+    out["note"] = args.note
+    save()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--samples", type=int, default=2000)
@@ -53,8 +156,12 @@ def main():
     ap.add_argument("--kinds", default="svm_rbf,svm")
     ap.add_argument("--sklearn-jobs", type=int, default=1, help="jobs per value of C timed with scikit-learn (0: none)")
     ap.add_argument("--no-evaluate", action="store_true", help="skip the evaluate_regression(svm_fit='device') timing")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_svr_fit_n1_local.json"))
+    ap.add_argument("--cache", action="store_true", help="compare kernel_cache='gram' with 'none' (see above)")
+    ap.add_argument("--rounds", type=int, default=3, help="--cache: timed rounds per figure (the median is recorded)")
+    ap.add_argument("--note", default="", help="--cache: a note kept in the record")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "bench_svr_cache_n1_local.json" if args.cache else "bench_svr_fit_n1_local.json")
     from pyaudioanalysis_amd import _ffi, audioTrainTest as aT
     if _ffi.device_count() < 1:
         raise SystemExit("bench_svr_fit.py needs a HIP device")
@@ -70,6 +177,9 @@ def main():
         for _ in range(args.n_exp):
             perm = rng.permutation(n)
             jobs.append((perm[:n_train], perm[n_train:], zeros, ones, C))
+    if args.cache:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        return cache_compare(args, aT, Z, y, jobs)
     geo = aT.smo_geometry()
     out = {"samples": n, "dims": DIMS, "params": PARAMS, "n_exp": args.n_exp, "jobs": len(jobs), "rows_per_task": n_train,
            "max_iter": args.max_iter, "iters_per_launch": geo[4], "threads_per_workgroup": geo[0], "kernels": {}}
