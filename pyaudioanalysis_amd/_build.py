@@ -4,6 +4,7 @@ The library is several translation units: csrc/paa_lib.hip (host side: state, pl
 -- itself made of the lib_*.hpp units -- plus the small kernels) and one family_*.hip per feature-kernel family, whose
 kernels are instantiated there and nowhere else.  The units compile in parallel and are linked into one shared object."""
 import concurrent.futures
+import hashlib
 import os
 import shutil
 import subprocess
@@ -33,6 +34,16 @@ UNIT_FLAGS = {
 }   # family_wgr / wgs / svc / svr / knn / smo / forest / hmm / diar / lda.hip keep the default flags
 
 
+def unit_id_flag(src):
+    """-cuid= for a translation unit, from the unit's NAME.  hipcc's default id hashes the source PATH; the symbol
+    __hip_cuid_<hex> of the unit's code object is derived from it and printed without leading zeros, so in another directory it can
+    be a digit or two shorter.  That shrinks .dynstr, which can move .rodata and .text across an alignment boundary and with them
+    the entry offsets in the kernel descriptors: the same sources then give other code-object bytes (seen: the HMM unit's .rodata
+    in a checkout under another path), and tests/test_abi_cpu.py::test_device_code_is_the_validated_one fails there.  With an id
+    that does not depend on the path every checkout builds the same bytes; with these ids they are the validated record's."""
+    return "-cuid=" + hashlib.sha256(src.encode()).hexdigest()[:16]
+
+
 def hipcc_path():
     for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if cand and os.path.exists(cand):
@@ -57,7 +68,7 @@ def build_to(lib, extra_flags=(), opt="-O3", verbose=False, jobs=None):
     with tempfile.TemporaryDirectory(prefix="paa_build_") as tmp:
         def compile_one(src):
             obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
-            cmd = [hipcc] + BASE_FLAGS + UNIT_FLAGS.get(src, []) + [opt] + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [hipcc] + BASE_FLAGS + [unit_id_flag(src)] + UNIT_FLAGS.get(src, []) + [opt] + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             res = subprocess.run(cmd, capture_output=True, text=True)

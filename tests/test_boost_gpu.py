@@ -12,10 +12,12 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import boost_edge_cases as E
 import boost_ref as B
 import train_ref
 from pyaudioanalysis_amd import audioTrainTest as aT
 from test_boost_cpu import FIELDS, builder_golden, golden, rel, same_tree, stage0_golden, whole_golden
+from test_boost_edges_ref_cpu import whole_golden as edge_whole_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -97,18 +99,20 @@ def test_stage_0_of_balanced_jobs_equals_scikit_learn(gpu_lib, name):
 
 
 _FITS = {}
+# the whole fits: boost_ref.WHOLE (at most 240 training rows: one row per thread) and boost_edge_cases.WHOLE (600 and 777 rows; 63 classes)
+WHOLE_NAMES = list(B.WHOLE) + list(E.WHOLE)
 
 
 def whole_fit(name):
     """The device's fit of a whole case, once per session: (golden, prefix, X, y, tr, te, K, stages, rs, the result)."""
     if name not in _FITS:
-        g, p, X, y, tr, te, K, stages, rs = whole_golden(name)
+        g, p, X, y, tr, te, K, stages, rs = (edge_whole_golden if name in E.WHOLE else whole_golden)(name)
         res = aT.boosting_split_fit_predict(X, y, [whole_job(X, tr, te, stages, rs)], proba=True, train_score=True, trees=True)
         _FITS[name] = (g, p, X, y, tr, te, K, stages, rs, res)
     return _FITS[name]
 
 
-@pytest.mark.parametrize("name", list(B.WHOLE))
+@pytest.mark.parametrize("name", WHOLE_NAMES)
 def test_whole_fits_against_scikit_learn(gpu_lib, name):
     g, p, X, y, tr, te, K, stages, rs, res = whole_fit(name)
     score, raw = rel(res.train_score[0], g[p + "train_score"]), rel(res.train_raw[0], g[p + "train_raw"])
@@ -117,7 +121,7 @@ def test_whole_fits_against_scikit_learn(gpu_lib, name):
     assert score <= 1e-9 and raw <= 1e-9
 
 
-@pytest.mark.parametrize("name", list(B.WHOLE))
+@pytest.mark.parametrize("name", WHOLE_NAMES)
 def test_gradients_agree_with_the_host_to_4_ulp_of_1(gpu_lib, name):
     """Element by element, stage by stage: ONE call fits the case with 1 .. S stages (the same seed: the first s stages of every job are
     the same model, and a model is a function of its job alone); job s returns the negative gradients its last stage was fitted to, which
@@ -139,7 +143,7 @@ def test_gradients_agree_with_the_host_to_4_ulp_of_1(gpu_lib, name):
     assert worst <= 4 * 2.0 ** -52
 
 
-@pytest.mark.parametrize("name", list(B.WHOLE))
+@pytest.mark.parametrize("name", WHOLE_NAMES)
 def test_traced_replay_on_the_host(gpu_lib, name):
     """Independent of scikit-learn: replay the fit stage by stage from the device's own trees.  With the gradients held to 4 ulp of 1 (the
     test above), every tree a valid stage tree for the host gradients (bounds widened by that error), every leaf value within the bound derived from the sums
@@ -188,7 +192,7 @@ def test_traced_replay_on_the_host(gpu_lib, name):
     assert abs(B.gradient_and_loss(raw, yt, K)[1] - res.train_score[0][-1]) <= 1e-10 * abs(res.train_score[0][-1])
 
 
-@pytest.mark.parametrize("name", list(B.WHOLE))
+@pytest.mark.parametrize("name", WHOLE_NAMES)
 def test_held_out_rows_are_scored_as_the_model_scores_them(gpu_lib, name):
     """Labels and probabilities of the sweep equal to_sklearn_boosting(model).predict / predict_proba within 1e-14 (the bound of
     test_forest_gpu.py for boosted models) -- not scikit-learn's own fit, whose held-out labels move with splits that part the training
