@@ -9,11 +9,6 @@
 namespace paa {
 namespace launch {
 
-static int raise_lds(const void *kernel, size_t lds) {
-    if (lds <= 32 * 1024) return 0;
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -1;
-}
-
 int smo_step(const smo::SmoDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream) {
     if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > smo::kMaxRows) return -2;
     if (n_live < 1 || budget < 1) return -1;

@@ -30,9 +30,7 @@ int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_m
     if (n_live < 1 || budget < 1) return -1;
     const int pitch = (m.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
     const size_t lds = ((size_t)4 * pitch + n_max) * sizeof(double);
-    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&svrfit::svr_smo_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -1;
+    if (raise_lds(reinterpret_cast<const void *>(&svrfit::svr_smo_kernel), lds)) return -1;
     hipLaunchKernelGGL(svrfit::svr_smo_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), lds, stream, m, d_live, budget);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -47,9 +45,7 @@ int svr_gram(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d
     hipLaunchKernelGGL(svrfit::svr_standardise_kernel, dim3((unsigned)n_chunk, row_blocks), dim3(smo::kThreads), 0, stream, m, c, d_chunk);
     if (hipGetLastError() != hipSuccess) return -1;
     const size_t lds = ((size_t)svrfit::kGramTile * pitch + svrfit::kGramTile * (svrfit::kGramTile + 1)) * sizeof(double);
-    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&svrfit::svr_gram_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -1;
+    if (raise_lds(reinterpret_cast<const void *>(&svrfit::svr_gram_kernel), lds)) return -1;
     hipLaunchKernelGGL(svrfit::svr_gram_kernel, dim3((unsigned)n_tiles), dim3(smo::kThreads), lds, stream, m, c, d_tiles);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

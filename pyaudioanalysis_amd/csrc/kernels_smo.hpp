@@ -4,21 +4,16 @@
 // A task is a list of rows of the resident sample matrix X, a sign per row, the mean / scale of its job (rows are
 // standardised on the load path, (x - mean) / scale with an IEEE division, as in knn_split_kernel), C and gamma.
 //
-// smo_kernel: the lane split of kernels_kv.hpp -- a group of 8 lanes owns the rows g, g + 32, g + 64, ... of the task and
-// lane l the dims l, l + 8, ... of a row; three xor shuffles give every lane of the group the kernel value, so all eight
-// lanes carry the same scalars and lane 0 stores.  Per iteration:
-//   1. every group scans its rows for max v over I_up (v = -y G) and max -v over I_low; the workgroup reduces (value, index)
-//      pairs with "greater value, then greater index" -- exact, associative and commutative, so the order of the reduction
-//      cannot matter and no lane's timing does;
+// smo_kernel, over the solver core of kernels_smo_core.hpp: the lane split of kernels_kv.hpp -- a group of 8 lanes owns the rows g,
+// g + 32, g + 64, ... of the task and lane l the dims l, l + 8, ... of a row; three xor shuffles give every lane of the group the
+// kernel value, so all eight lanes carry the same scalars and lane 0 stores.  Per iteration:
+//   1. every group scans its rows for max v over I_up (v = -y G) and max -v over I_low; the workgroup reduces (block_max);
 //   2. z_i is staged in LDS, every group forms K_it for its rows (kept in LDS: the gradient update needs it again), and in
 //      the same pass the second-order objective -b^2 / eta of its rows; the workgroup reduces to j (least value, then
 //      greatest index);
-//   3. every thread computes the two-variable update from the same values, z_j is staged, every group forms K_jt and
-//      updates G_t of its rows.
-// alpha, G and K_tt live in device memory between launches; a launch runs at most `budget` iterations of a task and an
-// iteration reads nothing but (alpha, G): the result is bit-identical for any budget, alone or in any batch.
-// At a stop (converged or max_iter) the workgroup writes rho, the gap, alpha_t y_t and the number of support vectors; the
-// sum behind rho adds the groups' partial sums (each in row order) in group order.
+//   3. every thread computes the two-variable update from the same values (pair_update), z_j is staged, every group forms K_jt
+//      and updates G_t of its rows.
+// At a stop (converged or max_iter) the workgroup writes rho, the gap, alpha_t y_t and the number of support vectors (RhoPartial).
 //
 // svc_pairs_kernel: one group per test row of a job (32 rows per workgroup); per pair of the job the task's rows go through
 // LDS tiles, standardised once per tile, and the rows with alpha != 0 add alpha_t y_t K(z_t, z) in train-list order.
@@ -31,41 +26,27 @@ namespace smo {
 constexpr int kClassSlots = kMaxClasses / kGroupLanes;
 
 __global__ __launch_bounds__(kThreads) void smo_kernel(SmoDev m, const int *__restrict__ live, int budget) {
-    extern __shared__ double lds[];                     // mean [pitch] | scale [pitch] | zi [pitch] | zj [pitch] | Ki [n_max]
-    __shared__ double red_v[kWaves];
-    __shared__ int red_i[kWaves];
-    __shared__ double red_sum[kGroups], red_ub[kGroups], red_lb[kGroups];
-    __shared__ int red_free[kGroups], red_sv[kGroups];
+    extern __shared__ double lds[];
+    const SolverLds s = solver_lds();
     const int tid = threadIdx.x, lane = tid % kGroupLanes, group = tid / kGroupLanes;
     const int task = live[blockIdx.x];
     const SmoTask T = m.tasks[task];
     const int n = T.n, n_dims = m.n_dims;
     const int M = (n_dims + kGroupLanes - 1) / kGroupLanes, pitch = M * kGroupLanes;
-    double *s_mean = lds, *s_scale = lds + pitch, *zi = lds + 2 * pitch, *zj = lds + 3 * pitch, *Ki = lds + 4 * pitch;
+    const PointLds p(lds, pitch);
     const int *__restrict__ idx = m.idx + T.off;
     const signed char *__restrict__ sign = m.sign + T.off;
     double *alpha = m.alpha + T.off, *G = m.G + T.off, *QD = m.QD + T.off;
     const bool rbf = m.rbf != 0;
     const double C = T.C, gamma = T.gamma;
-    for (int d = tid; d < pitch; d += kThreads) {
-        s_mean[d] = d < n_dims ? m.mean[(long long)T.stat * n_dims + d] : 0.0;
-        s_scale[d] = d < n_dims ? m.scale[(long long)T.stat * n_dims + d] : 1.0;
-    }
+    stage_stats(p.mean, p.scale, m.mean, m.scale, T.stat, n_dims, pitch, tid);
     __syncthreads();
     int iter = m.iter[task];
     if (m.status[task] == kFresh) {                     // alpha = 0, G = -1, K_tt once per task
         for (int t = group; t < n; t += kGroups) {
-            const double *__restrict__ x = m.X + (long long)idx[t] * n_dims;
-            double acc = 0.0;
-            if (!rbf)
-                for (int i = 0; i < M; ++i) {
-                    const int d = lane + kGroupLanes * i;
-                    const double z = d < n_dims ? (x[d] - s_mean[d]) / s_scale[d] : 0.0;
-                    acc = fma(z, z, acc);
-                }
-            acc = kv::group_sum(acc);
+            const double qd = rbf ? 1.0 : self_kernel(m.X, idx[t], p.mean, p.scale, n_dims, M, lane);
             if (lane == 0) {
-                QD[t] = rbf ? 1.0 : acc;                // exp(-gamma * 0)
+                QD[t] = qd;
                 alpha[t] = 0.0;
                 G[t] = -1.0;
             }
@@ -87,8 +68,8 @@ __global__ __launch_bounds__(kThreads) void smo_kernel(SmoDev m, const int *__re
             if (pos ? a < C : a > 0.0) take_max(bv, bi, v, t);
             if (pos ? a > 0.0 : a < C) take_max(b2, b2i, -v, t);
         }
-        block_max(bv, bi, red_v, red_i, tid);
-        block_max(b2, b2i, red_v, red_i, tid);
+        block_max(bv, bi, s, tid);
+        block_max(b2, b2i, s, tid);
         gmax = bv;
         gmax2 = b2;
         const int i = bi;
@@ -98,92 +79,50 @@ __global__ __launch_bounds__(kThreads) void smo_kernel(SmoDev m, const int *__re
         if (done >= budget) break;
 
         // 2. K_it for every row, and j: the least -b^2 / eta over I_low with b > 0 (ties: the greatest index)
-        stage_point(zi, m.X, idx[i], n_dims, s_mean, s_scale, pitch, tid);
+        stage_point(p.zi, m.X, idx[i], n_dims, p.mean, p.scale, pitch, tid);
         __syncthreads();
         const double qd_i = QD[i];
         double jv = 0.0;
         int ji = -1;
         for (int t = group; t < n; t += kGroups) {
-            const double k = kernel_value(m.X, idx[t], zi, s_mean, s_scale, n_dims, M, lane, rbf, gamma);
-            if (lane == 0) Ki[t] = k;
+            const double k = kernel_value(m.X, idx[t], p.zi, p.mean, p.scale, n_dims, M, lane, rbf, gamma);
+            if (lane == 0) p.Ki[t] = k;
             const double a = alpha[t], v = sign[t] > 0 ? -G[t] : G[t];
             const bool pos = sign[t] > 0;
             const double b = gmax - v;
-            if ((pos ? a > 0.0 : a < C) && b > 0.0) {
-                double eta = qd_i + QD[t] - 2.0 * k;
-                if (!(eta > 0.0)) eta = kTau;
-                take_max(jv, ji, (b * b) / eta, t);       // the greatest b^2 / eta is the least -b^2 / eta
-            }
+            // the greatest b^2 / eta is the least -b^2 / eta
+            if ((pos ? a > 0.0 : a < C) && b > 0.0) take_max(jv, ji, (b * b) / clamp_eta(qd_i, QD[t], k), t);
         }
-        block_max(jv, ji, red_v, red_i, tid);           // (its barriers also publish Ki)
+        block_max(jv, ji, s, tid);                      // (its barriers also publish Ki)
         const int j = ji;
         if (j < 0) { status = kConverged; break; }
 
         // 3. the two-variable update (every thread, from the same values), then G
         const double yi = sign[i], yj = sign[j], ai = alpha[i], aj = alpha[j];
-        double eta = qd_i + QD[j] - 2.0 * Ki[j];
-        if (!(eta > 0.0)) eta = kTau;
         double ni, nj;
-        if (yi != yj) {
-            const double delta = (-G[i] - G[j]) / eta, d = ai - aj;
-            ni = ai + delta;
-            nj = aj + delta;
-            if (d > 0.0) { if (nj < 0.0) { nj = 0.0; ni = d; } }
-            else { if (ni < 0.0) { ni = 0.0; nj = -d; } }
-            if (d > 0.0) { if (ni > C) { ni = C; nj = C - d; } }
-            else { if (nj > C) { nj = C; ni = C + d; } }
-        } else {
-            const double delta = (G[i] - G[j]) / eta, s = ai + aj;
-            ni = ai - delta;
-            nj = aj + delta;
-            if (s > C) { if (ni > C) { ni = C; nj = s - C; } }
-            else { if (nj < 0.0) { nj = 0.0; ni = s; } }
-            if (s > C) { if (nj > C) { nj = C; ni = s - C; } }
-            else { if (ni < 0.0) { ni = 0.0; nj = s; } }
-        }
+        pair_update(yi, yj, ai, aj, G, i, j, clamp_eta(qd_i, QD[j], p.Ki[j]), C, ni, nj);
         const double ci = yi * (ni - ai), cj = yj * (nj - aj);
-        stage_point(zj, m.X, idx[j], n_dims, s_mean, s_scale, pitch, tid);
+        stage_point(p.zj, m.X, idx[j], n_dims, p.mean, p.scale, pitch, tid);
         __syncthreads();                                // every thread has read alpha and G of i and j
         for (int t = group; t < n; t += kGroups) {
-            const double k = kernel_value(m.X, idx[t], zj, s_mean, s_scale, n_dims, M, lane, rbf, gamma);
-            if (lane == 0) G[t] += (double)sign[t] * (Ki[t] * ci + k * cj);
+            const double k = kernel_value(m.X, idx[t], p.zj, p.mean, p.scale, n_dims, M, lane, rbf, gamma);
+            if (lane == 0) G[t] += (double)sign[t] * (p.Ki[t] * ci + k * cj);
         }
         if (tid == 0) { alpha[i] = ni; alpha[j] = nj; }
         ++iter;
         __syncthreads();                                // G and alpha of this iteration before the next scan
     }
 
-    if (status == kRunning) {
-        if (tid == 0) { m.iter[task] = iter; m.status[task] = kRunning; }
-        return;
-    }
+    if (status == kRunning) { suspend(m.iter, m.status, task, iter, tid); return; }
     // rho (calculate_rho), alpha_t y_t and the support-vector count
-    double sum = 0.0, ub = __builtin_inf(), lb = -__builtin_inf();
-    int n_free = 0, n_sv = 0;
+    RhoPartial r;
     for (int t = group; t < n; t += kGroups) {
-        const double a = alpha[t], y = sign[t], yG = y * G[t];
-        if (a > 0.0 && a < C) { sum += yG; ++n_free; }
-        else if ((a >= C) == (y < 0.0)) ub = fmin(ub, yG);          // {alpha = C, y = -1} and {alpha = 0, y = +1}
-        else lb = fmax(lb, yG);
-        n_sv += a != 0.0;
+        const double a = alpha[t], y = sign[t];
+        r.add(a, y, y * G[t], C);
+        r.n_sv += a != 0.0;
         if (lane == 0) m.alpha_y[T.off + t] = a * y;
     }
-    if (lane == 0) { red_sum[group] = sum; red_ub[group] = ub; red_lb[group] = lb; red_free[group] = n_free; red_sv[group] = n_sv; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int g = 1; g < kGroups; ++g) {
-            sum += red_sum[g];
-            ub = fmin(ub, red_ub[g]);
-            lb = fmax(lb, red_lb[g]);
-            n_free += red_free[g];
-            n_sv += red_sv[g];
-        }
-        m.rho[task] = n_free > 0 ? sum / (double)n_free : (ub + lb) / 2.0;
-        m.gap[task] = both ? gmax + gmax2 : 0.0;
-        m.n_sv[task] = n_sv;
-        m.iter[task] = iter;
-        m.status[task] = status;
-    }
+    r.finish<false>(m, task, both ? gmax + gmax2 : 0.0, iter, status, s, tid);
 }
 
 // The one-against-one vote over the fitted tasks of a sweep (svm_predict, svm.cpp): workgroup b serves the test rows

@@ -7,10 +7,11 @@
 //                            the dims l, l + 8, ... in that order, kv::group_sum, then exp(-gamma acc) for RBF.  The chain is
 //                            symmetric in its two rows (a product commutes, (a - b)^2 = (b - a)^2), so a tile pair is formed once and
 //                            written twice, both times along rows, through an LDS tile.  No FP64 matrix core: it sums in another order
-//   svr_smo_cached_kernel    the iteration of svr_smo_kernel with K_i[t] and K_j[t] read from the matrix, one THREAD per row in the
-//                            scan, the j pass and the G update (the selections are exact: the greatest value, then the greatest
-//                            index, whatever the order); calculate_rho's sum keeps the group mapping of svr_smo_kernel, the one place
-//                            where another mapping would change bits.  Bit-identical to svr_smo_kernel in every output.
+//   svr_smo_cached_kernel    the iteration of svr_smo_kernel on the same pieces of the solver core (kernels_smo_core.hpp: block_max,
+//                            clamp_eta, pair_update, RhoPartial, suspend), with K_i[t], K_j[t] and K_tt read from the matrix and one
+//                            THREAD per row in the scan, the j pass and the G update (the selections are exact: the greatest value,
+//                            then the greatest index, whatever the order); calculate_rho's sum runs on RhoPartial's group mapping,
+//                            the one place where another mapping would change bits.  Bit-identical to svr_smo_kernel in every output
 // All offsets into Z and K are 64-bit.
 #pragma once
 #include "kernels_svrfit.hpp"
@@ -82,12 +83,10 @@ __global__ __launch_bounds__(kThreads) void svr_gram_kernel(SvrDev m, SvrCacheDe
     }
 }
 
+// a body of its own beside svr_smo_kernel's: as two instances of one template over the rows' owner and source this one measured 0.7 %
+// slower (3.113 / 3.119 s against 3.091 / 3.094 s for the capped linear sweep), with the same instructions in its loop
 __global__ __launch_bounds__(kThreads) void svr_smo_cached_kernel(SvrDev m, SvrCacheDev c, const int *__restrict__ live, int budget) {
-    __shared__ double red_v[kWaves];
-    __shared__ int red_i[kWaves];
-    __shared__ double red_sum[kGroups], red_ub[kGroups], red_lb[kGroups];
-    __shared__ int red_free[kGroups], red_sv[kGroups];
-    __shared__ double s_rho;
+    const SolverLds s = solver_lds();
     const int tid = threadIdx.x, lane = tid % kGroupLanes, group = tid / kGroupLanes;
     const int task = live[blockIdx.x];
     const SmoTask T = m.tasks[task];
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void svr_smo_cached_kernel(SvrDev m, SvrC
     double gmax = 0.0, gmax2 = 0.0;
     bool both = false;
     for (int done = 0;; ++done) {
-        // 1. i and Gmax2, as svr_smo_kernel
+        // 1. i and Gmax2
         double bv = 0.0, b2 = 0.0;
         int bi = -1, b2i = -1;
         for (int t = tid; t < n; t += kThreads) {
@@ -125,8 +124,8 @@ __global__ __launch_bounds__(kThreads) void svr_smo_cached_kernel(SvrDev m, SvrC
             if (ap > 0.0) take_max(b2, b2i, -vp, t);
             if (an < C) take_max(b2, b2i, -vn, t + n);
         }
-        block_max(bv, bi, red_v, red_i, tid);
-        block_max(b2, b2i, red_v, red_i, tid);
+        block_max(bv, bi, s, tid);
+        block_max(b2, b2i, s, tid);
         gmax = bv;
         gmax2 = b2;
         const int i = bi;
@@ -143,39 +142,20 @@ __global__ __launch_bounds__(kThreads) void svr_smo_cached_kernel(SvrDev m, SvrC
         int ji = -1;
         for (int t = tid; t < n; t += kThreads) {
             const double k = Ki[t];
-            double eta = qd_i + QD[t] - 2.0 * k;
-            if (!(eta > 0.0)) eta = kTau;
+            const double eta = clamp_eta(qd_i, QD[t], k);
             const double bp = gmax + G[t], bn = gmax - G[t + n];
             if (alpha[t] > 0.0 && bp > 0.0) take_max(jv, ji, (bp * bp) / eta, t);
             if (alpha[t + n] < C && bn > 0.0) take_max(jv, ji, (bn * bn) / eta, t + n);
         }
-        block_max(jv, ji, red_v, red_i, tid);
+        block_max(jv, ji, s, tid);
         const int j = ji;
         if (j < 0) { status = kConverged; break; }
 
         // 3. the two-variable update (every thread, from the same values), then G over the rows K(row i, .) and K(row j, .)
         const int rj = j < n ? j : j - n;
         const double yi = i < n ? 1.0 : -1.0, yj = j < n ? 1.0 : -1.0, ai = alpha[i], aj = alpha[j];
-        double eta = qd_i + QD[rj] - 2.0 * Ki[rj];
-        if (!(eta > 0.0)) eta = kTau;
         double ni, nj;
-        if (yi != yj) {
-            const double delta = (-G[i] - G[j]) / eta, d = ai - aj;
-            ni = ai + delta;
-            nj = aj + delta;
-            if (d > 0.0) { if (nj < 0.0) { nj = 0.0; ni = d; } }
-            else { if (ni < 0.0) { ni = 0.0; nj = -d; } }
-            if (d > 0.0) { if (ni > C) { ni = C; nj = C - d; } }
-            else { if (nj > C) { nj = C; ni = C + d; } }
-        } else {
-            const double delta = (G[i] - G[j]) / eta, s = ai + aj;
-            ni = ai - delta;
-            nj = aj + delta;
-            if (s > C) { if (ni > C) { ni = C; nj = s - C; } }
-            else { if (nj < 0.0) { nj = 0.0; ni = s; } }
-            if (s > C) { if (nj > C) { nj = C; ni = s - C; } }
-            else { if (ni < 0.0) { ni = 0.0; nj = s; } }
-        }
+        pair_update(yi, yj, ai, aj, G, i, j, clamp_eta(qd_i, QD[rj], Ki[rj]), C, ni, nj);
         const double ci = yi * (ni - ai), cj = yj * (nj - aj);
         const double *__restrict__ Kj = K + (long long)rj * n;
         __syncthreads();                                // every thread has read alpha and G of i and j
@@ -190,45 +170,20 @@ __global__ __launch_bounds__(kThreads) void svr_smo_cached_kernel(SvrDev m, SvrC
         __syncthreads();                                // G and alpha of this iteration before the next scan
     }
 
-    if (status == kRunning) {
-        if (tid == 0) { m.iter[task] = iter; m.status[task] = kRunning; }
-        return;
-    }
-    // rho, beta and the support-vector count: the loop of svr_smo_kernel, group for group -- the order of `sum` is part of the result
-    double sum = 0.0, ub = __builtin_inf(), lb = -__builtin_inf();
-    int n_free = 0, n_sv = 0;
+    if (status == kRunning) { suspend(m.iter, m.status, task, iter, tid); return; }
+    // rho, beta and the support-vector count on the group mapping (the solver core's order of rho's sum), then the training predictions
+    RhoPartial r;
     for (int t = group; t < n; t += kGroups) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const double a = alpha[t + h * n], y = h ? -1.0 : 1.0, yG = y * G[t + h * n];
-            if (a > 0.0 && a < C) { sum += yG; ++n_free; }
-            else if ((a >= C) == (y < 0.0)) ub = fmin(ub, yG);
-            else lb = fmax(lb, yG);
+            const double y = h ? -1.0 : 1.0;
+            r.add(alpha[t + h * n], y, y * G[t + h * n], C);
         }
         const double beta = alpha[t] - alpha[t + n];
-        n_sv += beta != 0.0;
+        r.n_sv += beta != 0.0;
         if (lane == 0) m.beta[T.off + t] = beta;
     }
-    if (lane == 0) { red_sum[group] = sum; red_ub[group] = ub; red_lb[group] = lb; red_free[group] = n_free; red_sv[group] = n_sv; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int g = 1; g < kGroups; ++g) {
-            sum += red_sum[g];
-            ub = fmin(ub, red_ub[g]);
-            lb = fmax(lb, red_lb[g]);
-            n_free += red_free[g];
-            n_sv += red_sv[g];
-        }
-        const double rho = n_free > 0 ? sum / (double)n_free : (ub + lb) / 2.0;
-        s_rho = rho;
-        m.rho[task] = rho;
-        m.gap[task] = both ? gmax + gmax2 : 0.0;
-        m.n_sv[task] = n_sv;
-        m.iter[task] = iter;
-        m.status[task] = status;
-    }
-    __syncthreads();
-    const double rho = s_rho;
+    const double rho = r.finish<true>(m, task, both ? gmax + gmax2 : 0.0, iter, status, s, tid);
     for (int t = tid; t < n; t += kThreads) m.train_pred[T.off + t] = G[t] - epsilon + m.y[idx[t]] - rho;
 }
 

@@ -125,6 +125,32 @@ static smo::SmoDev smo_dev(const double *X, const BlockPart &tasks, const BlockP
     return m;
 }
 
+// the scoring kernel's view of the fitted tasks of a solver batch m (smo::SmoDev, svrfit::SvrDev): the uploaded test_off | blocks |
+// test_idx | job_task | job_k, the device array job_stat (null: a job standardises with its own row) and the tasks' coefficients
+template <typename Dev>
+static smo::SvcFitDev svc_fit_dev(const Dev &m, const double *alpha_y, const BlockPart &test_off, const BlockPart &blocks,
+                                  const BlockPart &test_idx, const BlockPart &job_task, const BlockPart &job_k, const int *job_stat,
+                                  int max_pairs) {
+    smo::SvcFitDev f{};
+    f.X = m.X;
+    f.test_off = (const long long *)test_off.dev;
+    f.blocks = (const knn::SplitBlock *)blocks.dev;
+    f.test_idx = (const int *)test_idx.dev;
+    f.job_task = (const int *)job_task.dev;
+    f.job_k = (const int *)job_k.dev;
+    f.job_stat = job_stat;
+    f.mean = m.mean;
+    f.scale = m.scale;
+    f.tasks = m.tasks;
+    f.idx = m.idx;
+    f.alpha_y = alpha_y;
+    f.rho = m.rho;
+    f.n_dims = m.n_dims;
+    f.rbf = m.rbf;
+    f.max_pairs = max_pairs;
+    return f;
+}
+
 // The solver alone (libsvm's Solver::Solve for C-SVC, svm.cpp, as svm_train_one runs it under SVC.fit): see paa_hip.h
 extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
                                  const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
@@ -274,22 +300,7 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
     if (task_status) std::copy(st_words.begin(), st_words.end(), task_status);
     // vote
     if (n_q) {
-        smo::SvcFitDev f{};
-        f.X = st.feats;
-        f.test_off = (const long long *)parts[3].dev;
-        f.blocks = (const knn::SplitBlock *)parts[4].dev;
-        f.test_idx = (const int *)parts[6].dev;
-        f.job_task = (const int *)parts[7].dev;
-        f.job_k = (const int *)parts[8].dev;
-        f.mean = m.mean;
-        f.scale = m.scale;
-        f.tasks = m.tasks;
-        f.idx = m.idx;
-        f.alpha_y = m.alpha_y;
-        f.rho = m.rho;
-        f.n_dims = n_dims;
-        f.rbf = m.rbf;
-        f.max_pairs = max_pairs;
+        const smo::SvcFitDev f = svc_fit_dev(m, m.alpha_y, parts[3], parts[4], parts[6], parts[7], parts[8], nullptr, max_pairs);
         if (st.out[1]) HIP_TRY(hipMemsetAsync(st.out[1], 0, (size_t)n_q * max_pairs * 8, cs()));     // zeros past a job's pairs
         LAUNCH_TRY("SVM vote", launch::svc_pairs(f, (long long)blocks.size(), (int32_t *)st.out[0], (double *)st.out[1], cs()));
     }
@@ -509,23 +520,7 @@ static int svc_fit_proba_resident(const double *d_X, const double *d_mean, const
     HIP_TRY(hipMemcpyAsync(o.n_sv, m.n_sv, np * 4, hipMemcpyDeviceToHost, cs()));
     // score the held-out rows of every fold
     if (n_q) {
-        smo::SvcFitDev v{};
-        v.X = d_X;
-        v.test_off = (const long long *)parts[1].dev;
-        v.blocks = (const knn::SplitBlock *)parts[3].dev;
-        v.test_idx = (const int *)parts[6].dev;
-        v.job_task = (const int *)parts[7].dev;
-        v.job_k = (const int *)parts[8].dev;
-        v.job_stat = (const int *)parts[9].dev;
-        v.mean = d_mean;
-        v.scale = d_scale;
-        v.tasks = m.tasks;
-        v.idx = m.idx;
-        v.alpha_y = m.alpha_y;
-        v.rho = m.rho;
-        v.n_dims = n_dims;
-        v.rbf = m.rbf;
-        v.max_pairs = 1;
+        const smo::SvcFitDev v = svc_fit_dev(m, m.alpha_y, parts[1], parts[3], parts[6], parts[7], parts[8], (const int *)parts[9].dev, 1);
         LAUNCH_TRY("fold scoring", launch::svc_pairs(v, (long long)blocks.size(), (int32_t *)parts[10].dev, (double *)parts[4].dev, cs()));
         HIP_TRY(hipMemcpyAsync(q_dec.data(), parts[4].dev, (size_t)n_q * 8, hipMemcpyDeviceToHost, cs()));
     }

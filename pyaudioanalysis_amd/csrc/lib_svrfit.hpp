@@ -1,6 +1,6 @@
 // The SVR fits of audioTrainTest.evaluate_regression (audioTrainTest.py:774-855 with train_svm_regression :222-226) on the device:
 // a batch of epsilon-SVR dual problems (tasks) over ONE uploaded sample matrix and its targets, solved by relaunching
-// svr_smo_kernel until every task has stopped (smo_relaunch, lib_smo.hpp), and the split sweep built on it: one task per job,
+// svr_smo_kernel until every task has stopped (smo_relaunch_some, lib_smo.hpp), and the split sweep built on it: one task per job,
 // then svc_pairs_kernel over the test rows, a job being one "pair" whose alpha_y is beta -- its decision value is the prediction.
 // With a resident kernel matrix (DESIGN K22, the *_cached_f64 entry points) the tasks are packed into chunks whose n x n matrices fit
 // `cache_bytes`; per chunk: svr_standardise_kernel, svr_gram_kernel, then smo_relaunch_some with svr_smo_cached_kernel, then the
@@ -45,16 +45,24 @@ static int svr_state_alloc(SvrFitState &s, svrfit::SvrDev &m, size_t rows, size_
     return PAA_OK;
 }
 
-// Solves a batch: allocates its state into s and m, then runs every task to its stop (smo_relaunch)
-static int svr_solve_batch(svrfit::SvrDev &m, SvrFitState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, size_t n_q,
-                           int iters_per_launch, std::vector<int> &status, int *n_launches) {
-    int rc;
-    if ((rc = svr_state_alloc(s, m, rows, tasks.size(), n_q))) return rc;
-    return smo_relaunch(tasks, m.max_iter, iters_per_launch, s.live, m.status, status, n_launches, [&](int n_live, int n_max, int budget) {
-        LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
-        return (int)PAA_OK;
-    });
-}
+// The steps of smo_relaunch_some: svr_smo_kernel, and svr_smo_cached_kernel over the resident matrices c, for the tasks listed in `live`
+struct SvrStep {
+    const svrfit::SvrDev &m;
+    const int *live;
+    int operator()(int n_live, int n_max, int budget) const {
+        LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, live, n_live, n_max, budget, cs()));
+        return PAA_OK;
+    }
+};
+struct SvrCachedStep {
+    const svrfit::SvrDev &m;
+    const svrfit::SvrCacheDev &c;
+    const int *live;
+    int operator()(int n_live, int n_max, int budget) const {
+        LAUNCH_TRY("cached SVR SMO", launch::svr_smo_cached_step(m, c, live, n_live, n_max, budget, cs()));
+        return PAA_OK;
+    }
+};
 
 // The packing rule of the resident matrices: the matrix of a task of n rows takes 8 n^2 bytes (its standardised rows and the tile list
 // ride along uncounted).  In task order: a task whose matrix exceeds `cache_bytes` is not cached; any other joins the open chunk when
@@ -143,9 +151,11 @@ static int svr_cache_fill(const SvrCache &c, const svrfit::SvrDev &m, const std:
     return PAA_OK;
 }
 
-// svr_solve_batch with resident matrices under the budget cache_bytes; cached [tasks]: 1 for a task solved from its matrix
-static int svr_solve_batch_cached(svrfit::SvrDev &m, SvrFitState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, size_t n_q,
-                                  int iters_per_launch, std::vector<int> &status, int *n_launches, int64_t cache_bytes, int32_t *cached) {
+// Solves a batch: allocates its state into s and m, then runs every task to its stop (smo_relaunch_some), from resident matrices
+// under the budget cache_bytes where they fit; cached [tasks] (may be null): 1 for a task solved from its matrix.  cache_bytes = 0 is
+// "no cache": no matrix fits, no chunk is formed and every task goes to svr_smo_kernel in one relaunch loop
+static int svr_solve_batch(svrfit::SvrDev &m, SvrFitState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, size_t n_q,
+                           int iters_per_launch, std::vector<int> &status, int *n_launches, int64_t cache_bytes, int32_t *cached) {
     int rc;
     if ((rc = svr_state_alloc(s, m, rows, tasks.size(), n_q))) return rc;
     SvrCache c;
@@ -154,21 +164,16 @@ static int svr_solve_batch_cached(svrfit::SvrDev &m, SvrFitState &s, const std::
     long long launches = 0;
     std::vector<int> members;
     for (size_t t = 0; t < tasks.size(); ++t) {
-        cached[t] = c.chunk_of[t] >= 0;
-        if (!cached[t]) members.push_back((int)t);
+        if (cached) cached[t] = c.chunk_of[t] >= 0;
+        if (c.chunk_of[t] < 0) members.push_back((int)t);
     }
     if (!members.empty() &&
-        (rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, [&](int n_live, int n_max, int budget) {
-             LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
-             return (int)PAA_OK;
-         })))
+        (rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, SvrStep{m, s.live})))
         return rc;
     for (int ch = 0; ch < c.n_chunks; ++ch) {
         if ((rc = svr_cache_fill(c, m, tasks, ch, members))) return rc;
-        if ((rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, [&](int n_live, int n_max, int budget) {
-                 LAUNCH_TRY("cached SVR SMO", launch::svr_smo_cached_step(m, c.dev, s.live, n_live, n_max, budget, cs()));
-                 return (int)PAA_OK;
-             })))
+        if ((rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches,
+                                    SvrCachedStep{m, c.dev, s.live})))
             return rc;
     }
     if (n_launches) *n_launches = (int)launches;
@@ -242,8 +247,7 @@ static int svr_tasks_run(const double *X, int64_t n_samples, int n_dims, const d
     svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[5], n_dims, kernel_type, eps, max_iter);
     SvrFitState s;
     std::vector<int> st_words;
-    if ((rc = use_cache ? svr_solve_batch_cached(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches, cache_bytes, cached)
-                        : svr_solve_batch(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches)))
+    if ((rc = svr_solve_batch(m, s, tasks, (size_t)rows, 0, iters_per_launch, st_words, n_launches, use_cache ? cache_bytes : 0, cached)))
         return rc;
     HIP_TRY(hipMemcpyAsync(beta, m.beta, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(train_pred, m.train_pred, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
@@ -314,11 +318,7 @@ extern "C" int paa_svr_gram_f64(const double *X, int64_t n_samples, int n_dims, 
     if (qd_out) {
         std::vector<int> st_words(n_tasks, smo::kFresh);
         long long launches = 0;
-        if ((rc = smo_relaunch_some(tasks, members, 1, 1, s.live, m.status, st_words, launches, [&](int n_live, int n_max, int budget) {
-                 LAUNCH_TRY("SVR SMO", launch::svr_smo_step(m, s.live, n_live, n_max, budget, cs()));
-                 return (int)PAA_OK;
-             })))
-            return rc;
+        if ((rc = smo_relaunch_some(tasks, members, 1, 1, s.live, m.status, st_words, launches, SvrStep{m, s.live}))) return rc;
         HIP_TRY(hipMemcpyAsync(qd_out, m.QD, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     }
     HIP_TRY(hipStreamSynchronize(cs()));
@@ -375,8 +375,8 @@ static int svr_fit_splits_run(const double *X, int64_t n_samples, int n_dims, co
     svrfit::SvrDev m = svr_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], parts[7], n_dims, kernel_type, eps, max_iter);
     SvrFitState s;
     std::vector<int> st_words;
-    if ((rc = use_cache ? svr_solve_batch_cached(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches, cache_bytes, cached)
-                        : svr_solve_batch(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches)))
+    if ((rc = svr_solve_batch(m, s, tasks, (size_t)n_t, (size_t)n_q, iters_per_launch, st_words, n_launches, use_cache ? cache_bytes : 0,
+                              cached)))
         return rc;
     if (job_iterations) HIP_TRY(hipMemcpyAsync(job_iterations, m.iter, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
     if (job_n_sv) HIP_TRY(hipMemcpyAsync(job_n_sv, m.n_sv, (size_t)n_jobs * 4, hipMemcpyDeviceToHost, cs()));
@@ -384,22 +384,7 @@ static int svr_fit_splits_run(const double *X, int64_t n_samples, int n_dims, co
     if (job_status) std::copy(st_words.begin(), st_words.end(), job_status);
     // score: the decision value of a job's one pair is sum_t beta_t K(z_t, z) - rho
     if (n_q) {
-        smo::SvcFitDev f{};
-        f.X = st.feats;
-        f.test_off = (const long long *)parts[5].dev;
-        f.blocks = (const knn::SplitBlock *)parts[6].dev;
-        f.test_idx = (const int *)parts[8].dev;
-        f.job_task = (const int *)parts[9].dev;
-        f.job_k = (const int *)parts[10].dev;
-        f.mean = m.mean;
-        f.scale = m.scale;
-        f.tasks = m.tasks;
-        f.idx = m.idx;
-        f.alpha_y = m.beta;
-        f.rho = m.rho;
-        f.n_dims = n_dims;
-        f.rbf = m.rbf;
-        f.max_pairs = 1;
+        const smo::SvcFitDev f = svc_fit_dev(m, m.beta, parts[5], parts[6], parts[8], parts[9], parts[10], nullptr, 1);
         LAUNCH_TRY("SVR scoring", launch::svc_pairs(f, (long long)blocks.size(), s.label, (double *)st.out[0], cs()));
     }
     return finish(st);

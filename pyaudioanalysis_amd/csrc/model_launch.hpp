@@ -333,6 +333,12 @@ int dispatch_int(int v, F &&f) {
 
 namespace launch {
 
+// for a launch unit: lets `kernel` take `lds` bytes of dynamic LDS (above 32 KB a kernel has to be told); 0, or -1 when refused
+inline int raise_lds(const void *kernel, size_t lds) {
+    if (lds <= 32 * 1024) return 0;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 0 : -1;
+}
+
 // kernels_svc.hpp: multi-class probabilistic SVC over the columns of feats [n_dims][ld] (two kernels: the per-class sums go to
 // `sums`, n_vec * k * (k - 1) doubles; then labels [n_vec] and probabilities [n_vec][k])
 int svc(const svc::SvcDev &m, const double *d_feats, long long ld, long long n_vec, const double *d_mean, const double *d_scale,
