@@ -1544,6 +1544,8 @@ _FOREST_FIT_KINDS = {"randomforest": "best", "extratrees": "random"}
 _TREE_RS = np.random.RandomState(0)              # tree_inputs' own generator, re-seeded per tree; never NumPy's global state
 _TREE_FIELDS = ("children_left", "children_right", "feature", "threshold", "impurity", "n_node_samples", "weighted_n_node_samples",
                 "missing_go_to_left", "value")
+_TREE_DTYPES = (np.int32, np.int32, np.int32, np.float64, np.float64, np.int32, np.float64, np.uint8, np.float64)
+_AS_POINTER = {np.int32: _ffi.as_i32p, np.float64: _ffi.as_f64p, np.uint8: _ffi.as_u8p}
 
 
 def tree_fit_geometry():
@@ -1552,6 +1554,14 @@ def tree_fit_geometry():
     geo = np.zeros(6, dtype=np.int32)
     _ffi.check(_ffi.lib().paa_debug_tree_fit_geometry(geo.ctypes.data_as(_ffi.c_i32p)))
     return tuple(int(v) for v in geo)
+
+
+def _tree_outputs(n_trees, total_nodes, total_values):
+    """The arrays a library call writes trees to -- (node counts [n_trees], {field: array} by _TREE_FIELDS: value with total_values
+    entries, the others one per node; no array is empty) -- and their ten pointers, the tail of the C signatures' tree arguments."""
+    count = np.zeros(max(n_trees, 1), dtype=np.int32)
+    out = {name: np.zeros(max(total_values if name == "value" else total_nodes, 1), dtype=dtype) for name, dtype in zip(_TREE_FIELDS, _TREE_DTYPES)}
+    return count, out, (_ffi.as_i32p(count),) + tuple(_AS_POINTER[dtype](out[name]) for name, dtype in zip(_TREE_FIELDS, _TREE_DTYPES))
 
 
 def _raise_tree_flags(flags):
@@ -1708,18 +1718,12 @@ def _tree_fit(X, tasks, splitter, max_depth=None):
     node_off = _offsets(caps)
     val_off = _offsets(caps * k[task_job])
     total_nodes, total_values, n_tasks = int(node_off[-1]), int(val_off[-1]), len(tasks)
-    i32 = lambda: np.zeros(max(total_nodes, 1), dtype=np.int32)          # noqa: E731
-    f64 = lambda: np.zeros(max(total_nodes, 1), dtype=np.float64)        # noqa: E731
-    out = {"children_left": i32(), "children_right": i32(), "feature": i32(), "threshold": f64(), "impurity": f64(),
-           "n_node_samples": i32(), "weighted_n_node_samples": f64(), "missing_go_to_left": np.zeros(max(total_nodes, 1), dtype=np.uint8)}
-    value = np.zeros(max(total_values, 1), dtype=np.float64)
-    flags, count = np.zeros(len(rows_l), dtype=np.int32), np.zeros(n_tasks, dtype=np.int32)
+    count, out, pointers = _tree_outputs(n_tasks, total_nodes, total_values)
+    value = out.pop("value")
+    flags = np.zeros(len(rows_l), dtype=np.int32)
     head = (_ffi.as_f64p(X), n_samples, n_dims, len(rows_l), _ffi.as_i64p(off), _ffi.as_i32p(idx))
     middle = (_ffi.as_f64p(mean), _ffi.as_f64p(scale), n_tasks, _ffi.as_i32p(task_job), _ffi.as_i64p(seed), _ffi.as_i32p(weight))
-    tail = (total_nodes, total_values, _ffi.as_i32p(flags), _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
-            _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
-            _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
-            out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(value))
+    tail = (total_nodes, total_values, _ffi.as_i32p(flags)) + pointers
     if regression and max_depth is not None:
         _ffi.check(_ffi.lib().paa_tree_fit_boost_tasks_f64(*head, _ffi.as_f64p(label), *middle, max_depth, *tail))
     elif regression:
@@ -1736,7 +1740,14 @@ def _tree_fit(X, tasks, splitter, max_depth=None):
     return TreeFitResult(trees, None if regression else [classes_l[j] for j in task_job])
 
 
-class ForestSplitResult(_SplitResult):
+class _ClassSplitResult(_SplitResult):
+    def job(self, j):
+        """(labels, probabilities [n_test][classes present in job j] or None) of job j."""
+        r = self._rows(j)
+        return self.label[r], None if self.proba is None else self.proba[r, :len(self.classes[j])]
+
+
+class ForestSplitResult(_ClassSplitResult):
     """What forest_split_fit_predict returns: label [Q] (class values as in `labels`), proba [Q][max_classes] or None (column c:
     the job's c-th present class; zeros past a job's classes), test_off [n_jobs + 1], classes (per job the classes present in its
     training list, ascending), n_estimators [n_jobs] and the number of chunks the trees were fitted in."""
@@ -1744,10 +1755,38 @@ class ForestSplitResult(_SplitResult):
     def __init__(self, label, proba, test_off, classes, n_estimators, n_chunks):
         self.label, self.proba, self.test_off, self.classes, self.n_estimators, self.n_chunks = label, proba, test_off, classes, n_estimators, n_chunks
 
-    def job(self, j):
-        """(labels, probabilities [n_test][classes present in job j] or None) of job j."""
-        r = self._rows(j)
-        return self.label[r], None if self.proba is None else self.proba[r, :len(self.classes[j])]
+
+_TreeSweep = collections.namedtuple("_TreeSweep", "counts n_est head flags chunks")
+
+
+def _tree_sweep(p, y_pointer):
+    """The shared opening of a tree sweep over the packed jobs p: every training list is checked against TREE_MAX_ROWS; counts (rows
+    per training list), n_est [n_jobs], head (the arguments X .. n_estimators of the library call, y_pointer as the labels or
+    targets) and the flags [n_jobs] and chunks [1] the call writes."""
+    n_jobs = len(p.last)
+    counts = np.diff(p.train_off)
+    for j in range(n_jobs):
+        _check_tree_rows(int(counts[j]), "job %d" % j)
+    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
+    head = (_ffi.as_f64p(p.X), p.X.shape[0], p.X.shape[1], y_pointer, n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+            _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est))
+    return _TreeSweep(counts, n_est, head, np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32))
+
+
+def _forest_sweep(p, y_pointer, bootstrap):
+    """_tree_sweep and what NumPy draws for the forests of the jobs: per job forest_tree_seeds(seed, n_estimators), per tree
+    tree_inputs (bootstrap: with the in-bag counts).  Returns (the _TreeSweep, the (seed, weight) arguments of the library call)."""
+    sw = _tree_sweep(p, y_pointer)
+    seeds, weights = [], []
+    for j in range(len(p.last)):
+        for s in forest_tree_seeds(p.last[j][1], sw.n_est[j]):
+            rand_r, w = tree_inputs(s, int(sw.counts[j]), bootstrap and sw.counts[j] > 0)
+            seeds.append(rand_r)
+            if w is not None:
+                weights.append(w)
+    seed = np.array(seeds, dtype=np.int64)
+    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32) if weights else None
+    return sw, (_ffi.as_i64p(seed), _ffi.as_i32p(weight) if weight is not None else None)
 
 
 def forest_split_fit_predict(X, labels, jobs, kind, proba=False):
@@ -1762,35 +1801,50 @@ def forest_split_fit_predict(X, labels, jobs, kind, proba=False):
     if kind not in _FOREST_FIT_KINDS:
         raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
     p = _pack_jobs(X, labels, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
-    n_samples, n_dims = p.X.shape
-    n_jobs = len(p.last)
-    counts = np.diff(p.train_off)
-    for j in range(n_jobs):
-        _check_tree_rows(int(counts[j]), "job %d" % j)
+    sw, drawn = _forest_sweep(p, _ffi.as_i32p(p.labels), kind == "randomforest")
     classes = [np.unique(p.labels[rows]) for rows in p.inside]
-    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
-    bootstrap = kind == "randomforest"
-    seeds, weights = [], []
-    for j in range(n_jobs):
-        for s in forest_tree_seeds(p.last[j][1], n_est[j]):
-            rand_r, w = tree_inputs(s, int(counts[j]), bootstrap and counts[j] > 0)
-            seeds.append(rand_r)
-            if w is not None:
-                weights.append(w)
-    seed = np.array(seeds, dtype=np.int64)
-    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32) if weights else None
     Q, max_classes = int(p.test_off[-1]), max(max(len(c) for c in classes), 1)
     label = np.zeros(Q, dtype=np.int32)
     P = np.zeros((Q, max_classes), dtype=np.float64) if proba else None
-    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
     _ffi.check(_ffi.lib().paa_forest_fit_splits_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
-        _TREE_SPLITTERS[_FOREST_FIT_KINDS[kind]], _ffi.as_i64p(seed), _ffi.as_i32p(weight) if weight is not None else None,
-        _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None, max_classes, _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
-    _raise_tree_flags(flags)
+        *sw.head, _TREE_SPLITTERS[_FOREST_FIT_KINDS[kind]], *drawn, _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None, max_classes,
+        _ffi.as_i32p(sw.flags), _ffi.as_i32p(sw.chunks)))
+    _raise_tree_flags(sw.flags)
     ForestModel._raise_invalid(label)
-    return ForestSplitResult(label.astype(np.int64), P, p.test_off, classes, n_est, int(chunks[0]))
+    return ForestSplitResult(label.astype(np.int64), P, p.test_off, classes, sw.n_est, int(sw.chunks[0]))
+
+
+def _device_fit_inputs(features, labels, n_estimators, random_state=None, bootstrap=None, regression=False):
+    """The shared opening of the train_*_device functions: the checks of the sample matrix, the labels (regression: float targets,
+    validated as scikit-learn does), n_estimators and the row limit; rows, mean and scale of the one job over all rows; the
+    tree_fit tasks of a forest, drawn as scikit-learn draws them (bootstrap None: no forest, nothing is drawn).  Returns (X, y,
+    rows, mean, scale, tasks)."""
+    X = np.ascontiguousarray(features, dtype=np.float64)
+    y = np.asarray(labels, dtype=np.float64 if regression else None).reshape(-1)
+    if X.ndim != 2 or X.shape[0] < 1 or y.shape[0] != X.shape[0]:
+        raise ValueError("sample matrix of shape %s with %d %s" % (X.shape, y.shape[0], "targets" if regression else "labels"))
+    if int(n_estimators) < 1:
+        raise ValueError("n_estimators = %r" % (n_estimators,))
+    if regression:
+        _check_targets(y)
+    n, n_dims = X.shape
+    _check_tree_rows(n, "the training set")
+    rows, mean, scale = np.arange(n), np.zeros(n_dims), np.ones(n_dims)
+    tasks = []
+    for s in forest_tree_seeds(random_state, n_estimators) if bootstrap is not None else ():
+        rand_r, w = tree_inputs(s, n, bootstrap)
+        tasks.append((rows, y, w, rand_r, mean, scale))
+    return X, y, rows, mean, scale, tasks
+
+
+def _forest_of_trees(kind, trees, classes, n_dims):
+    """The ForestArrays of kind "averaged" / "regressor" of tree_fit's trees, with impurity, n_node_samples and
+    weighted_n_node_samples beside them."""
+    cat = lambda name: np.concatenate([t[name] for t in trees])        # noqa: E731
+    arrays = ForestArrays(kind, _offsets([t["feature"].shape[0] for t in trees]), cat("children_left"), cat("children_right"), cat("feature"),
+                          cat("threshold"), cat("missing_go_to_left"), cat("value") if kind == "averaged" else cat("value")[:, 0], classes, n_dims)
+    arrays.impurity, arrays.n_node_samples, arrays.weighted_n_node_samples = cat("impurity"), cat("n_node_samples"), cat("weighted_n_node_samples")
+    return arrays
 
 
 def train_forest_device(features, labels, n_estimators, kind="randomforest", *, random_state=None):
@@ -1803,25 +1857,9 @@ def train_forest_device(features, labels, n_estimators, kind="randomforest", *, 
     NotImplementedError before the device is touched; there is no CPU fallback."""
     if kind not in _FOREST_FIT_KINDS:
         raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
-    X = np.ascontiguousarray(features, dtype=np.float64)
-    raw = np.asarray(labels).reshape(-1)
-    if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
-        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
-    if int(n_estimators) < 1:
-        raise ValueError("n_estimators = %r" % (n_estimators,))
-    n, n_dims = X.shape
-    _check_tree_rows(n, "the training set")
-    rows, mean, scale = np.arange(n), np.zeros(n_dims), np.ones(n_dims)
-    tasks = []
-    for s in forest_tree_seeds(random_state, n_estimators):
-        rand_r, w = tree_inputs(s, n, kind == "randomforest")
-        tasks.append((rows, raw, w, rand_r, mean, scale))
+    X, _, _, _, _, tasks = _device_fit_inputs(features, labels, n_estimators, random_state, kind == "randomforest")
     res = tree_fit(X, tasks, kind)
-    cat = lambda name: np.concatenate([t[name] for t in res.trees])        # noqa: E731
-    arrays = ForestArrays("averaged", _offsets([t["feature"].shape[0] for t in res.trees]), cat("children_left"), cat("children_right"),
-                          cat("feature"), cat("threshold"), cat("missing_go_to_left"), cat("value"), res.classes[0], n_dims)
-    arrays.impurity, arrays.n_node_samples, arrays.weighted_n_node_samples = cat("impurity"), cat("n_node_samples"), cat("weighted_n_node_samples")
-    return arrays
+    return _forest_of_trees("averaged", res.trees, res.classes[0], X.shape[1])
 
 
 def _tree_depth(left, right):
@@ -1835,13 +1873,29 @@ def _tree_depth(left, right):
         depth += 1
 
 
+def _sklearn_tree(a, lo, hi, n_outputs_of_value, value):
+    """The sklearn.tree._tree.Tree (built through __setstate__) of the nodes lo .. hi - 1 of the ForestArrays a, whose values are
+    value[lo:hi] with n_outputs_of_value columns; impurity, n_node_samples and weighted_n_node_samples where a carries them."""
+    from sklearn.tree._tree import NODE_DTYPE, Tree
+    nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
+    nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
+    nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
+    nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
+    for name in ("impurity", "n_node_samples", "weighted_n_node_samples"):
+        if getattr(a, name, None) is not None:
+            nodes[name] = getattr(a, name)[lo:hi]
+    tree = Tree(a.n_dims, np.array([n_outputs_of_value], dtype=np.intp), 1)
+    tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
+                       "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, n_outputs_of_value))})
+    return tree
+
+
 def to_sklearn_forest(arrays, kind):
     """A real fitted sklearn.ensemble.RandomForestClassifier ('randomforest') / ExtraTreesClassifier ('extratrees') with the trees of
     a ForestArrays of kind "averaged" (every Tree is built through __setstate__): it predicts as scikit-learn predicts from those
     arrays and pickles as the reference's model files do.  impurity, n_node_samples and weighted_n_node_samples are those of
     train_forest_device when the arrays carry them, zeros otherwise (prediction reads none of them).  Needs scikit-learn."""
     import sklearn.ensemble
-    from sklearn.tree._tree import NODE_DTYPE, Tree
     if kind not in _FOREST_FIT_KINDS:
         raise ValueError("tree ensemble %r: 'randomforest' or 'extratrees'" % (kind,))
     a = forest_arrays(arrays)
@@ -1856,20 +1910,9 @@ def to_sklearn_forest(arrays, kind):
     forest.n_features_in_ = a.n_dims
     forest.n_outputs_ = 1
     value = a.value.reshape(-1, k)
-    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
     forest.estimators_ = []
     for t in range(n_trees):
-        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
-        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
-        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
-        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
-        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
-        for name in extra:
-            if extra[name] is not None:
-                nodes[name] = extra[name][lo:hi]
-        tree = Tree(a.n_dims, np.array([k], dtype=np.intp), 1)
-        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
-                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, k))})
+        tree = _sklearn_tree(a, int(a.node_offsets[t]), int(a.node_offsets[t + 1]), k, value)
         est = forest._make_estimator(append=False)
         est.tree_ = tree
         est.classes_, est.n_classes_ = forest.classes_, k
@@ -1903,34 +1946,16 @@ def forest_regression_split_fit_predict(X, y, jobs, train_pred=False):
     tree_fit_regression); otherwise they are those of valid CART trees.  NaN / infinity in y raise scikit-learn's ValueError and a
     training list above 8192 rows NotImplementedError, before the library is asked.  Returns a ForestRegressionSplitResult."""
     p = _pack_jobs(X, y, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
-    n_samples, n_dims = p.X.shape
-    targets = _targets(p.raw, n_samples)
+    targets = _targets(p.raw, p.X.shape[0])
     _check_targets(targets)
-    n_jobs = len(p.last)
-    counts = np.diff(p.train_off)
-    for j in range(n_jobs):
-        _check_tree_rows(int(counts[j]), "job %d" % j)
-    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
-    seeds, weights = [], []
-    for j in range(n_jobs):
-        for s in forest_tree_seeds(p.last[j][1], n_est[j]):
-            rand_r, w = tree_inputs(s, int(counts[j]), counts[j] > 0)
-            seeds.append(rand_r)
-            if w is not None:
-                weights.append(w)
-    seed = np.array(seeds, dtype=np.int64)
-    weight = np.ascontiguousarray(np.concatenate(weights), dtype=np.int32) if weights else None
+    sw, drawn = _forest_sweep(p, _ffi.as_f64p(targets), True)
     Q, T = int(p.test_off[-1]), int(p.train_off[-1])
     pred = np.zeros(Q)
     tp = np.zeros(T) if train_pred else None
-    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_forest_reg_fit_splits_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_f64p(targets), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
-        _ffi.as_i64p(seed), _ffi.as_i32p(weight) if weight is not None else None, _ffi.as_f64p(pred),
-        _ffi.as_f64p(tp) if train_pred else None, _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
-    _raise_tree_flags(flags)
-    return ForestRegressionSplitResult(pred, tp, p.test_off, p.train_off, n_est, int(chunks[0]))
+    _ffi.check(_ffi.lib().paa_forest_reg_fit_splits_f64(*sw.head, *drawn, _ffi.as_f64p(pred), _ffi.as_f64p(tp) if train_pred else None,
+                                                        _ffi.as_i32p(sw.flags), _ffi.as_i32p(sw.chunks)))
+    _raise_tree_flags(sw.flags)
+    return ForestRegressionSplitResult(pred, tp, p.test_off, p.train_off, sw.n_est, int(sw.chunks[0]))
 
 
 def train_random_forest_regression_device(features, labels, n_estimators, *, random_state=None):
@@ -1941,25 +1966,8 @@ def train_random_forest_regression_device(features, labels, n_estimators, *, ran
     weighted_n_node_samples for to_sklearn_forest_regressor; the mean absolute training error, from the device prediction).  The
     arrays equal those of scikit-learn's estimators_ bit for bit when the targets make the trees' sums exact (tree_fit_regression).
     More than 8192 rows raise NotImplementedError before the device is touched; there is no CPU fallback."""
-    X = np.ascontiguousarray(features, dtype=np.float64)
-    y = np.asarray(labels, dtype=np.float64).reshape(-1)
-    if X.ndim != 2 or X.shape[0] < 1 or y.shape[0] != X.shape[0]:
-        raise ValueError("sample matrix of shape %s with %d targets" % (X.shape, y.shape[0]))
-    if int(n_estimators) < 1:
-        raise ValueError("n_estimators = %r" % (n_estimators,))
-    _check_targets(y)
-    n, n_dims = X.shape
-    _check_tree_rows(n, "the training set")
-    rows, mean, scale = np.arange(n), np.zeros(n_dims), np.ones(n_dims)
-    tasks = []
-    for s in forest_tree_seeds(random_state, n_estimators):
-        rand_r, w = tree_inputs(s, n, True)
-        tasks.append((rows, y, w, rand_r, mean, scale))
-    res = tree_fit_regression(X, tasks)
-    cat = lambda name: np.concatenate([t[name] for t in res.trees])        # noqa: E731
-    arrays = ForestArrays("regressor", _offsets([t["feature"].shape[0] for t in res.trees]), cat("children_left"), cat("children_right"),
-                          cat("feature"), cat("threshold"), cat("missing_go_to_left"), cat("value")[:, 0], None, n_dims)
-    arrays.impurity, arrays.n_node_samples, arrays.weighted_n_node_samples = cat("impurity"), cat("n_node_samples"), cat("weighted_n_node_samples")
+    X, y, _, mean, scale, tasks = _device_fit_inputs(features, labels, n_estimators, random_state, True, regression=True)
+    arrays = _forest_of_trees("regressor", tree_fit_regression(X, tasks).trees, None, X.shape[1])
     pred = regress([arrays], "randomforest", X.T, mean, scale)[0]
     return arrays, np.mean(np.abs(pred - y))
 
@@ -1970,7 +1978,6 @@ def to_sklearn_forest_regressor(arrays):
     files do.  impurity, n_node_samples and weighted_n_node_samples are those of train_random_forest_regression_device when the
     arrays carry them, zeros otherwise (prediction reads none of them).  Needs scikit-learn."""
     import sklearn.ensemble
-    from sklearn.tree._tree import NODE_DTYPE, Tree
     a = forest_arrays(arrays)
     if a.kind != "regressor":
         raise ValueError("a tree ensemble of kind %r: 'regressor' expected" % (a.kind,))
@@ -1980,20 +1987,9 @@ def to_sklearn_forest_regressor(arrays):
     forest.n_features_in_ = a.n_dims
     forest.n_outputs_ = 1
     value = a.value.reshape(-1)
-    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
     forest.estimators_ = []
     for t in range(n_trees):
-        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
-        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
-        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
-        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
-        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
-        for name in extra:
-            if extra[name] is not None:
-                nodes[name] = extra[name][lo:hi]
-        tree = Tree(a.n_dims, np.array([1], dtype=np.intp), 1)
-        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
-                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, 1))})
+        tree = _sklearn_tree(a, int(a.node_offsets[t]), int(a.node_offsets[t + 1]), 1, value)
         est = forest._make_estimator(append=False)
         est.tree_ = tree
         est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, a.n_dims
@@ -2035,7 +2031,7 @@ def _boost_tree_cap(n, max_depth):
     return min(2 * n - 1, 2 ** (max_depth + 1) - 1)
 
 
-class BoostingSplitResult(_SplitResult):
+class BoostingSplitResult(_ClassSplitResult):
     """What boosting_split_fit_predict returns: label [Q] (class values as in `labels`), proba [Q][max_classes] or None (column c: the
     job's c-th present class; zeros past a job's classes), test_off [n_jobs + 1], classes (per job the classes present in its training
     list, ascending), n_estimators [n_jobs], the number of chunks the jobs were fitted in and, with train_score=True, per job
@@ -2045,11 +2041,6 @@ class BoostingSplitResult(_SplitResult):
     def __init__(self, label, proba, test_off, classes, n_estimators, n_chunks, train_score, train_raw, train_resid, models):
         self.label, self.proba, self.test_off, self.classes, self.n_estimators, self.n_chunks = label, proba, test_off, classes, n_estimators, n_chunks
         self.train_score, self.train_raw, self.train_resid, self.models = train_score, train_raw, train_resid, models
-
-    def job(self, j):
-        """(labels, probabilities [n_test][classes present in job j] or None) of job j."""
-        r = self._rows(j)
-        return self.label[r], None if self.proba is None else self.proba[r, :len(self.classes[j])]
 
 
 def boosting_split_fit_predict(X, labels, jobs, proba=False, train_score=False, *, trees=False, chunk_bytes=None):
@@ -2066,17 +2057,13 @@ def boosting_split_fit_predict(X, labels, jobs, proba=False, train_score=False, 
     chunk_bytes (keyword only): a bound below the library's 1 GiB for the device scratch of one chunk of jobs (tests).  Returns a
     BoostingSplitResult."""
     p = _pack_jobs(X, labels, jobs, "(n_estimators, seed)", lambda v: (int(v[0]), v[1]))
-    n_samples, n_dims = p.X.shape
-    n_jobs = len(p.last)
-    counts = np.diff(p.train_off)
-    for j in range(n_jobs):
-        _check_tree_rows(int(counts[j]), "job %d" % j)
+    sw = _tree_sweep(p, _ffi.as_i32p(p.labels))
+    n_dims, n_jobs, counts, n_est = p.X.shape[1], len(p.last), sw.counts, sw.n_est
     classes = [np.unique(p.labels[rows]) for rows in p.inside]
     for j in range(n_jobs):
         if counts[j] > 0 and len(classes[j]) < 2:
             raise ValueError("y contains %d class after sample_weight trimmed classes with zero weights, while a minimum of 2 classes "
                              "are required." % len(classes[j]))
-    n_est = np.array([max(v[0], 0) for v in p.last], dtype=np.int32)
     k_out = [1 if len(c) == 2 else len(c) for c in classes]
     max_classes = max(max(len(c) for c in classes), 2)
     init = np.zeros((n_jobs, max_classes), dtype=np.float64)
@@ -2098,23 +2085,13 @@ def boosting_split_fit_predict(X, labels, jobs, proba=False, train_score=False, 
                      [int(n_est[j]) * k_out[j] for j in range(n_jobs)]).astype(np.int64) if trees else np.zeros(0, dtype=np.int64)
     node_off = _offsets(caps)
     total_nodes = int(node_off[-1]) if trees else 0
-    i32 = lambda n: np.zeros(max(n, 1), dtype=np.int32)          # noqa: E731
-    f64 = lambda n: np.zeros(max(n, 1), dtype=np.float64)        # noqa: E731
-    out = {"children_left": i32(total_nodes), "children_right": i32(total_nodes), "feature": i32(total_nodes), "threshold": f64(total_nodes),
-           "impurity": f64(total_nodes), "n_node_samples": i32(total_nodes), "weighted_n_node_samples": f64(total_nodes),
-           "missing_go_to_left": np.zeros(max(total_nodes, 1), dtype=np.uint8), "value": f64(total_nodes)}
-    count = i32(len(caps) if trees else 0)
-    flags, chunks = np.zeros(n_jobs, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    count, out, pointers = _tree_outputs(len(caps), total_nodes, total_nodes)
     _ffi.check(_ffi.lib().paa_boost_fit_splits_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), n_jobs, _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_i32p(n_est),
-        _ffi.as_i64p(seed), _ffi.as_f64p(init), max_classes, BOOST_LEARNING_RATE, BOOST_MAX_DEPTH, int(chunk_bytes or 0),
+        *sw.head, _ffi.as_i64p(seed), _ffi.as_f64p(init), max_classes, BOOST_LEARNING_RATE, BOOST_MAX_DEPTH, int(chunk_bytes or 0),
         _ffi.as_i32p(label), _ffi.as_f64p(P) if proba else None, _ffi.as_f64p(score) if train_score else None,
-        _ffi.as_f64p(raw) if train_score else None, _ffi.as_f64p(resid) if train_score else None, total_nodes, _ffi.as_i32p(count), _ffi.as_i32p(out["children_left"]),
-        _ffi.as_i32p(out["children_right"]), _ffi.as_i32p(out["feature"]), _ffi.as_f64p(out["threshold"]), _ffi.as_f64p(out["impurity"]),
-        _ffi.as_i32p(out["n_node_samples"]), _ffi.as_f64p(out["weighted_n_node_samples"]),
-        out["missing_go_to_left"].ctypes.data_as(C.POINTER(C.c_uint8)), _ffi.as_f64p(out["value"]), _ffi.as_i32p(flags), _ffi.as_i32p(chunks)))
-    _raise_tree_flags(flags)
+        _ffi.as_f64p(raw) if train_score else None, _ffi.as_f64p(resid) if train_score else None, total_nodes, *pointers,
+        _ffi.as_i32p(sw.flags), _ffi.as_i32p(sw.chunks)))
+    _raise_tree_flags(sw.flags)
     ForestModel._raise_invalid(label)
     scores = [score[int(score_off[j]):int(score_off[j + 1])].copy() for j in range(n_jobs)] if train_score else None
     raws = [raw[int(raw_off[j]):int(raw_off[j + 1])].reshape(int(counts[j]), k_out[j]).copy() for j in range(n_jobs)] if train_score else None
@@ -2135,7 +2112,7 @@ def boosting_split_fit_predict(X, labels, jobs, proba=False, train_score=False, 
                 m.train_score_ = scores[j]
             models.append(m)
             t0 += n_trees
-    return BoostingSplitResult(label.astype(np.int64), P, p.test_off, classes, n_est, int(chunks[0]), scores, raws, resids, models)
+    return BoostingSplitResult(label.astype(np.int64), P, p.test_off, classes, n_est, int(sw.chunks[0]), scores, raws, resids, models)
 
 
 def train_gradient_boosting_device(features, labels, n_estimators, *, random_state=None):
@@ -2145,16 +2122,9 @@ def train_gradient_boosting_device(features, labels, n_estimators, *, random_sta
     classifier_wrapper and device_model take, with train_score_ attached (and impurity, n_node_samples, weighted_n_node_samples for
     to_sklearn_boosting).  More than 8192 rows raise NotImplementedError and a single class scikit-learn's ValueError before the
     device is touched; there is no CPU fallback."""
-    X = np.ascontiguousarray(features, dtype=np.float64)
-    raw = np.asarray(labels).reshape(-1)
-    if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
-        raise ValueError("sample matrix of shape %s with %d labels" % (X.shape, raw.shape[0]))
-    if int(n_estimators) < 1:
-        raise ValueError("n_estimators = %r" % (n_estimators,))
-    n, n_dims = X.shape
-    _check_tree_rows(n, "the training set")
+    X, raw, rows, mean, scale, _ = _device_fit_inputs(features, labels, n_estimators)
     classes, idx = np.unique(raw, return_inverse=True)
-    job = (np.arange(n), np.zeros(0, dtype=np.int64), np.zeros(n_dims), np.ones(n_dims), (int(n_estimators), random_state))
+    job = (rows, np.zeros(0, dtype=np.int64), mean, scale, (int(n_estimators), random_state))
     res = boosting_split_fit_predict(X, idx.reshape(-1), [job], train_score=True, trees=True)
     model = res.models[0]
     model.classes_ = classes
@@ -2170,7 +2140,6 @@ def to_sklearn_boosting(arrays):
     import sklearn.ensemble
     from sklearn.dummy import DummyClassifier
     from sklearn.tree import DecisionTreeRegressor
-    from sklearn.tree._tree import NODE_DTYPE, Tree
     a = forest_arrays(arrays)
     if a.kind != "boosted":
         raise ValueError("a tree ensemble of kind %r: 'boosted' expected" % (a.kind,))
@@ -2203,20 +2172,9 @@ def to_sklearn_boosting(arrays):
     gb.init_ = init
     gb.train_score_ = np.asarray(getattr(a, "train_score_", np.zeros(n_stages)), dtype=np.float64)
     value = a.value.reshape(-1)
-    extra = {name: getattr(a, name, None) for name in ("impurity", "n_node_samples", "weighted_n_node_samples")}
     gb.estimators_ = np.empty((n_stages, k_out), dtype=object)
     for t in range(n_trees):
-        lo, hi = int(a.node_offsets[t]), int(a.node_offsets[t + 1])
-        nodes = np.zeros(hi - lo, dtype=NODE_DTYPE)
-        nodes["left_child"], nodes["right_child"] = a.children_left[lo:hi], a.children_right[lo:hi]
-        nodes["feature"], nodes["threshold"] = a.feature[lo:hi], a.threshold[lo:hi]
-        nodes["missing_go_to_left"] = a.missing_go_to_left[lo:hi]
-        for name in extra:
-            if extra[name] is not None:
-                nodes[name] = extra[name][lo:hi]
-        tree = Tree(a.n_dims, np.array([1], dtype=np.intp), 1)
-        tree.__setstate__({"max_depth": _tree_depth(nodes["left_child"], nodes["right_child"]), "node_count": hi - lo, "nodes": nodes,
-                           "values": np.ascontiguousarray(value[lo:hi].reshape(hi - lo, 1, 1))})
+        tree = _sklearn_tree(a, int(a.node_offsets[t]), int(a.node_offsets[t + 1]), 1, value)
         est = DecisionTreeRegressor(criterion="friedman_mse", max_depth=max_depth)
         est.tree_ = tree
         est.n_features_in_, est.n_outputs_, est.max_features_ = a.n_dims, 1, a.n_dims

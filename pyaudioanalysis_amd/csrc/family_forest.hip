@@ -50,72 +50,53 @@ int tree_prep(const treefit::TreeDev &m, int n_jobs, int n_max, hipStream_t stre
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// The launch of tree_fit_kernel<SPLITTER, CRIT>.  configure: size the LDS for inbag_max (and k_max classes) and write the geometry into
+// m; false: m holds it already.  LDS: the sort words (best: a power of two of 64-bit words; random: the partition's 32-bit buffer) |
+// the rows | kGini under the best splitter: the class histogram, 256 columns (128 above 32 classes, which keeps the largest launch
+// below the CU's 160 KB) | the feature arrays.  The regression criteria keep the chunk sums of the candidate scan in registers (one
+// chunk per thread), so they have no histogram: 96.5 KB at 8192 rows.  The callers below instantiate tree_fit_kernel<kBest, kGini>,
+// tree_fit_kernel<kRandom, kGini>, tree_fit_kernel<kBest, kMse> and tree_fit_kernel<kBest, kFriedman>
+template <int SPLITTER, int CRIT>
+static int tree_fit_launch(treefit::TreeDev &m, int n_tasks, int inbag_max, int k_max, hipStream_t stream, bool configure) {
+    using namespace paa::treefit;
+    if (configure) {
+        int p2 = 2;
+        while (p2 < inbag_max) p2 <<= 1;
+        m.lds_keys = SPLITTER == kBest ? p2 : (inbag_max + 1) / 2;
+        m.lds_rows = (inbag_max + 1) / 2 * 2;
+        m.hist_cols = CRIT != kGini ? kThreads : k_max > 32 ? 128 : 256;
+        const size_t hist = SPLITTER == kBest && CRIT == kGini ? (size_t)k_max * (m.hist_cols + 1) * sizeof(int) : 0;
+        m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4 + hist);
+    }
+    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
+    if (lds > 152 * 1024 || m.lds_rows < inbag_max) return -2;
+    if (configure && lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&tree_fit_kernel<SPLITTER, CRIT>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL((tree_fit_kernel<SPLITTER, CRIT>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int tree_fit(treefit::TreeDev &m, int n_tasks, int splitter, int inbag_max, int k_max, hipStream_t stream) {
     using namespace paa::treefit;
     if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows || k_max < 1 || k_max > kMaxClasses) return -2;
     if (n_tasks < 1 || (splitter != kBest && splitter != kRandom)) return -1;
-    // LDS: the sort words (best: a power of two of 64-bit words; random: the partition's 32-bit buffer) | the rows | best: the class
-    // histogram, 256 columns (128 above 32 classes, which keeps the largest launch below the CU's 160 KB) | the feature arrays
-    int p2 = 2;
-    while (p2 < inbag_max) p2 <<= 1;
-    m.lds_keys = splitter == kBest ? p2 : (inbag_max + 1) / 2;
-    m.lds_rows = (inbag_max + 1) / 2 * 2;
-    m.hist_cols = k_max > 32 ? 128 : 256;
-    const size_t hist = splitter == kBest ? (size_t)k_max * (m.hist_cols + 1) * sizeof(int) : 0;
-    m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4 + hist);
-    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
-    if (lds > 152 * 1024) return -2;
-    const void *kernel = splitter == kBest ? reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kGini>)
-                                           : reinterpret_cast<const void *>(&tree_fit_kernel<kRandom, kGini>);
-    if (lds > 32 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-    if (splitter == kBest)
-        hipLaunchKernelGGL((tree_fit_kernel<kBest, kGini>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
-    else
-        hipLaunchKernelGGL((tree_fit_kernel<kRandom, kGini>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return splitter == kBest ? tree_fit_launch<kBest, kGini>(m, n_tasks, inbag_max, k_max, stream, true)
+                             : tree_fit_launch<kRandom, kGini>(m, n_tasks, inbag_max, k_max, stream, true);
 }
 
 int tree_fit_reg(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream) {
     using namespace paa::treefit;
     if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows) return -2;
     if (n_tasks < 1 || !m.target) return -1;
-    // LDS: the sort words (a power of two of 64-bit words) | the rows | the feature arrays; the chunk sums of the candidate scan stay
-    // in registers (one chunk per thread), so there is no histogram: 96.5 KB at 8192 rows
-    int p2 = 2;
-    while (p2 < inbag_max) p2 <<= 1;
-    m.lds_keys = p2;
-    m.lds_rows = (inbag_max + 1) / 2 * 2;
-    m.hist_cols = kThreads;
-    m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4);
-    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
-    if (lds > 152 * 1024) return -2;
-    if (lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kMse>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -1;
-    hipLaunchKernelGGL((tree_fit_kernel<kBest, kMse>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return tree_fit_launch<kBest, kMse>(m, n_tasks, inbag_max, 1, stream, true);
 }
 
 int tree_fit_boost(treefit::TreeDev &m, int n_tasks, int inbag_max, hipStream_t stream, bool configure) {
     using namespace paa::treefit;
     if (m.n_dims < 1 || m.n_dims > kMaxDims || inbag_max < 1 || inbag_max > kMaxRows) return -2;
     if (n_tasks < 1 || !m.target || m.max_depth < 0 || (m.raw && (!m.boost || !m.label))) return -1;
-    // LDS: as the squared-error instance (96.5 KB at 8192 rows)
-    if (configure) {
-        int p2 = 2;
-        while (p2 < inbag_max) p2 <<= 1;
-        m.lds_keys = p2;
-        m.lds_rows = (inbag_max + 1) / 2 * 2;
-        m.hist_cols = kThreads;
-        m.lds_feat = (int)((size_t)m.lds_keys * 8 + (size_t)m.lds_rows * 4);
-    }
-    const size_t lds = ((size_t)m.lds_feat + 2 * (size_t)m.n_dims * sizeof(unsigned short) + 7) / 8 * 8;
-    if (lds > 152 * 1024 || m.lds_rows < inbag_max) return -2;
-    if (configure && lds > 32 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&tree_fit_kernel<kBest, kFriedman>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -1;
-    hipLaunchKernelGGL((tree_fit_kernel<kBest, kFriedman>), dim3((unsigned)n_tasks), dim3(kThreads), lds, stream, m);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return tree_fit_launch<kBest, kFriedman>(m, n_tasks, inbag_max, 1, stream, configure);
 }
 
 int boost_gradient(const boost::BoostDev &m, int n_jobs, int stage, hipStream_t stream) {
