@@ -349,6 +349,28 @@ __device__ __forceinline__ double dpp_bcast15(double v) { return group_bcast<15>
 
 // fast_sqrt / mag_sqrt / fast_div / fast_log2 / fast_log10: device_common.hpp (shared with the other feature kernels)
 
+// Maximum of two doubles that are known not to be NaN (spectrum magnitudes), as the one v_max_f64 it is.  fmax() must
+// quieten a signalling NaN, and the compiler cannot see that a value that came through LDS or a DPP move is none: it puts a
+// canonicalising v_max_f64 x, x in front of every such operand (30 of them in the loop).  Same instruction on the same
+// operands in the same order, so the same bits.
+__device__ __forceinline__ double max_nn(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double max_nn0(double a) {          // max(0, a)
+    double r;
+    asm("v_max_f64 %0, 0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ double group_max_nn(double v) {     // group_max (device_common.hpp) of values that are not NaN
+    v = max_nn(v, dpp_mov<PAA_DPP_X1>(v));
+    v = max_nn(v, dpp_mov<PAA_DPP_X2>(v));
+    v = max_nn(v, dpp_mov<PAA_DPP_HM>(v));
+    v = max_nn(v, dpp_mov<PAA_DPP_RM>(v));
+    return v;
+}
+
 // wave-uniform values computed with vector instructions: pin them into scalar registers
 __device__ __forceinline__ double uni(double v) {
     const unsigned long long b = __double_as_longlong(v);
@@ -862,9 +884,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             sMa = fma((double)m, X0, sMa); sMb = fma((double)(m + 1), X1, sMb);
             sQa = fma((double)(m * m), X0, sQa); sQb = fma((double)((m + 1) * (m + 1)), X1, sQb);
             c5[m / 5] = fma(X0, X0, c5[m / 5]); c5[(m + 1) / 5] = fma(X1, X1, c5[(m + 1) / 5]);
-            mx = fmax(mx, fmax(X0, X1));
+            mx = (m == 0) ? max_nn0(max_nn(X0, X1)) : max_nn(mx, max_nn(X0, X1));       // (magnitudes: never NaN)
         }
-        sXa += Xc[24]; sMa = fma(24.0, Xc[24], sMa); sQa = fma(576.0, Xc[24], sQa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = fmax(mx, Xc[24]);
+        sXa += Xc[24]; sMa = fma(24.0, Xc[24], sMa); sQa = fma(576.0, Xc[24], sQa); c5[4] = fma(Xc[24], Xc[24], c5[4]); mx = max_nn(mx, Xc[24]);
         // the lane's energy as the running sum of its chunks: the prefixes pc[1..4] serve the roll-off below, which so uses
         // the SAME sums as cs, the scan and the total sP (the energy up to a chunk's end is one and the same number everywhere)
         const double pc2 = c5[0] + c5[1], pc3 = pc2 + c5[2], pc4 = pc3 + c5[3];
@@ -892,7 +914,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         const double sXl = sX, sMl = sMa + sMb;        // the lane's own sum X, sum m X (spread)
         double sIX = f0 * fma(base_k, sX, sMl);
         sX = group_sum(sX);
-        sIX = group_sum(sIX); mx = group_max(mx);
+        sIX = group_sum(sIX); mx = group_max_nn(mx);
         // np.sum(X + eps) (:118-119) = sum X + 400 eps up to rounding
         const double sXe = sX + (double)NF * kEps;
         const double run_incl = group_scan_incl(cs);
@@ -953,9 +975,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
         // defined as [energy before the lane (scan)] + [the lane's whole chunks before the bin (pc)] + [the squares inside the
         // bin's chunk, added in order]; it never decreases along the chunk ends, so the chunk that holds the crossing is the
         // number of chunk ends that do not qualify (five compares; the lane's last end is the scan value itself, whose last
-        // is sP) and only that chunk's five bins are scanned.  Registers are chosen by selects on the compare masks: a
-        // dynamically indexed array would go to scratch.  (A crossing the chunk ends place in a chunk whose in-order sums
-        // all miss it by a rounding lands on the chunk's last bin.)
+        // is sP) and only that chunk's five bins are scanned.  The start value is chosen by selects on the compare masks (a
+        // dynamically indexed array would go to scratch), the five bins are read back from LDS.  (A crossing the chunk ends
+        // place in a chunk whose in-order sums all miss it by a rounding lands on the chunk's last bin.)
         int below;
         {
             const double thr = 0.90 * sP;
@@ -967,9 +989,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
             const unsigned long long m1 = __ballot(nb >= 1), m2 = __ballot(nb >= 2), m3 = __ballot(nb >= 3), m4 = __ballot(nb >= 4);
             double run = sel64(m4, s4, sel64(m3, s3, sel64(m2, s2, sel64(m1, s1, base))));
             int in = 0;
+            // the crossing chunk's five bins come from the lane's own LDS address (25 i + 5 min(nb, 4) + u <= 399): the frame's
+            // spectrum slot is intact through the feature phase -- only the PREVIOUS slot is aliased -- and five reads of the
+            // same doubles replace forty selects over Xc[]; the run's start value keeps its select chain
+            const double *x5 = cur + 25 * i + 5 * min(nb, 4);
 #pragma unroll
             for (int u = 0; u < 5; ++u) {
-                const double x = sel64(m4, Xc[20 + u], sel64(m3, Xc[15 + u], sel64(m2, Xc[10 + u], sel64(m1, Xc[5 + u], Xc[u]))));
+                const double x = x5[u];
                 run = fma(x, x, run);
                 in += (run + kEps > thr) ? 0 : 1;
             }
