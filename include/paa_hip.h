@@ -533,6 +533,67 @@ int paa_svr_fit_splits_cached_f64(const double *X, int64_t n_samples, int n_dims
 int paa_svr_gram_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off, const int32_t *task_idx,
                      const double *mean, const double *std, const double *gamma, int kernel_type, double *K_out, double *qd_out);
 
+/* ---- the C-SVC solver over RESIDENT kernel matrices, shared across a job's tasks --------------------------------------------------
+ * paa_smo_tasks_f64 forms two kernel rows per iteration.  The tasks of the classification side share rows: every pair of a job's
+ * classes is a task, and with probabilities every pair adds five fold fits over subsets of its rows.  A GROUP is a set of tasks that
+ * standardise with the same mean / std and use the same gamma.  Its row list is the distinct sample indices of its tasks in order of
+ * first appearance over the tasks in task order; its matrix K [N][N] over that list (8 N^2 bytes) is formed once, by the Gram pass of
+ * paa_svr_tasks_cached_f64 (every value has the bits of the solver's own kernel value), and every task of the group reads it through
+ * its position list: row t of the task is row pos[t] of the matrix (a sample listed twice maps to one row).  A second solver reads
+ * K(row i, .) and K(row j, .) from the matrix, one thread per row; every output is BYTE-EQUAL to the parent's.  The groups are packed
+ * into chunks in group order (order of first appearance) by the rule of paa_svr_tasks_cached_f64, applied to the groups' N; the tasks
+ * of a group whose matrix alone exceeds cache_bytes are solved by the parent's kernel in the same call.
+ *
+ * paa_smo_tasks_cached_f64 -- the arguments of paa_smo_tasks_f64, then
+ *   group [n_tasks]        tasks with equal ids form a group; NULL: every task is its own group
+ *   cache_bytes            the budget in bytes, > 0
+ *   cached [n_tasks]       out, not NULL: 1 when the task was solved from its group's resident matrix
+ * paa_svc_fit_splits_cached_f64, paa_svc_fit_proba_cached_f64, paa_silence_batch_i16_cached / _f64_cached -- the arguments of their
+ * parents, then cache_bytes and job_cached [n_jobs] / clip_cached [n_clips] (out, not NULL).  The group is the JOB (one clip's fit is
+ * one job): the full pair fits and all fold fits of a job share one matrix.
+ * Errors are the parents', plus PAA_ERR_ARG for cache_bytes <= 0 and for a group whose tasks differ in any byte of their mean, std or
+ * gamma (the message names the two tasks); all before the device is touched.
+ *
+ * paa_debug_smo_cache_layout -- the layout alone, on the host (no device is needed), for tests: the task row lists task_off /
+ * task_idx (indices >= 0), group (may be NULL) and cache_bytes as above.  Outputs: n_groups; group_of [n_tasks], the group of every
+ * task, numbered in order of first appearance; group_off [n_groups + 1] (room for n_tasks + 1) and group_rows [group_off[n_groups]]
+ * (room for task_off[n_tasks]), the groups' row lists; pos [task_off[n_tasks]]; group_chunk [n_groups] (room for n_tasks), the chunk
+ * of every group from 0, -1 for a group that is not cached.                                                                        */
+int paa_smo_tasks_cached_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
+                             const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std, const double *C,
+                             const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch, double *alpha_y,
+                             double *rho, int32_t *iterations, double *gap, int32_t *status, int32_t *n_launches,
+                             const int32_t *group, int64_t cache_bytes, int32_t *cached);
+int paa_svc_fit_splits_cached_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                  const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx,
+                                  const double *mean, const double *std, const double *C, const double *gamma, int kernel_type,
+                                  double eps, int max_iter, int iters_per_launch, int32_t *label_out, double *dec_out, int max_pairs,
+                                  int n_tasks, int32_t *task_iterations, int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches,
+                                  int64_t cache_bytes, int32_t *job_cached);
+int paa_svc_fit_proba_cached_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                 const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
+                                 const double *C, const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                 const int64_t *seed, int n_pairs, int64_t n_rows, double *alpha_y, double *rho, double *prob_a,
+                                 double *prob_b, int32_t *n_sv, int32_t *task_iterations, int32_t *task_status, int32_t *sig_iterations,
+                                 int32_t *sig_stop, double *cv_dec, int32_t *n_launches, int64_t cache_bytes, int32_t *job_cached);
+int paa_silence_batch_i16_cached(const int16_t *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                                 const int32_t *widths, const double *weights, const int64_t *seeds, int64_t chunk_bytes,
+                                 const int64_t *row_cap_off, uint8_t *quiet, uint8_t *loud, uint8_t *active, double *raw, double *prob,
+                                 double *limits, int32_t *counts, double *mean, double *scale, int32_t *src, double *alpha_y,
+                                 double *rho, double *prob_a, double *prob_b, double *threshold, int32_t *n_sv, int32_t *iterations,
+                                 int32_t *status, int32_t *sig_iterations, int32_t *sig_stop, double *stage_ms, int64_t cache_bytes,
+                                 int32_t *clip_cached);
+int paa_silence_batch_f64_cached(const double *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                                 const int32_t *widths, const double *weights, const int64_t *seeds, int64_t chunk_bytes,
+                                 const int64_t *row_cap_off, uint8_t *quiet, uint8_t *loud, uint8_t *active, double *raw, double *prob,
+                                 double *limits, int32_t *counts, double *mean, double *scale, int32_t *src, double *alpha_y,
+                                 double *rho, double *prob_a, double *prob_b, double *threshold, int32_t *n_sv, int32_t *iterations,
+                                 int32_t *status, int32_t *sig_iterations, int32_t *sig_stop, double *stage_ms, int64_t cache_bytes,
+                                 int32_t *clip_cached);
+int paa_debug_smo_cache_layout(int n_tasks, const int64_t *task_off, const int32_t *task_idx, const int32_t *group, int64_t cache_bytes,
+                               int32_t *n_groups, int32_t *group_of, int64_t *group_off, int32_t *group_rows, int32_t *pos,
+                               int32_t *group_chunk);
+
 /* ---- audioTrainTest.regression_wrapper for SVM models (audioTrainTest.py:96-111) ------------------------------------
  * predict() of TRAINED scikit-learn epsilon-SVR models (sklearn.svm.SVR, kernel 'rbf' or 'linear', as
  * train_svm_regression makes them, audioTrainTest.py:222-226) for many feature vectors and many models at once: what

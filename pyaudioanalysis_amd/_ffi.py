@@ -152,6 +152,18 @@ _SIGNATURES = {
                                                 c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p,
                                                 c_i32p, c_i32p, c_i32p, c_i32p, C.c_int64, c_i32p]),
     "paa_svr_gram_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, C.c_int, c_f64p, c_f64p]),
+    "paa_smo_tasks_cached_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, C.POINTER(C.c_int8), c_f64p, c_f64p, c_f64p,
+                                           c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p,
+                                           c_i32p, C.c_int64, c_i32p]),
+    "paa_svc_fit_splits_cached_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_i64p, c_i32p, c_f64p,
+                                                c_f64p, c_f64p, c_f64p, C.c_int, C.c_double, C.c_int, C.c_int, c_i32p, c_f64p, C.c_int,
+                                                C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int64, c_i32p]),
+    "paa_svc_fit_proba_cached_f64": (C.c_int, [c_f64p, C.c_int64, C.c_int, c_i32p, C.c_int, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p,
+                                               C.c_int, C.c_double, C.c_int, C.c_int, c_i64p, C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p,
+                                               c_f64p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p, C.c_int64, c_i32p]),
+    "paa_silence_batch_i16_cached": (C.c_int, [c_i16p] + _SILENCE_BATCH_ARGS + [C.c_int64, c_i32p]),
+    "paa_silence_batch_f64_cached": (C.c_int, [c_f64p] + _SILENCE_BATCH_ARGS + [C.c_int64, c_i32p]),
+    "paa_debug_smo_cache_layout": (C.c_int, [C.c_int, c_i64p, c_i32p, c_i32p, C.c_int64, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, c_i32p]),
     "paa_forest_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p, C.c_void_p,
                                     c_f64p, C.c_int, C.c_int, C.c_double, c_f64p, C.POINTER(C.c_void_p)]),
     "paa_forest_destroy": (C.c_int, [C.c_void_p]),

@@ -227,7 +227,7 @@ def _plot_segments(signal, sampling_rate, prob, st_step, seg_limits):
     plt.show()
 
 
-def _train_onset_svm_device(low_energy, high_energy, random_state):
+def _train_onset_svm_device(low_energy, high_energy, random_state, kernel_cache="none", cache_bytes=None):
     """_train_onset_svm without scikit-learn: StandardScaler's mean_ / scale_ (a constant feature keeps scale 1), applied on the
     load path of audioTrainTest.train_svm_device's fits (C = 1, linear, gamma='auto', probability=True)."""
     from . import audioTrainTest as aT
@@ -236,11 +236,12 @@ def _train_onset_svm_device(low_energy, high_energy, random_state):
     mean = features.mean(axis=0)
     scale = np.sqrt(features.var(axis=0))
     scale[scale < 10 * np.finfo(np.float64).eps] = 1.0                                     # sklearn's _handle_zeros_in_scale
-    return aT._train_svm_device(features, labels, 1.0, 'linear', random_state, mean, scale), mean, scale
+    cache = () if kernel_cache == "none" else (kernel_cache, cache_bytes)
+    return aT._train_svm_device(features, labels, 1.0, 'linear', random_state, mean, scale, *cache), mean, scale
 
 
 def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, weight=0.5, plot=False, *, svm_fit="sklearn",
-                    random_state=None):
+                    random_state=None, kernel_cache="none", cache_bytes=None):
     """Event detection (silence removal), reference :672-815.  Returns the list of [start, end] segments in seconds.
 
     signal, sampling_rate: the audio; st_win, st_step: short-term window and step in SECONDS; smooth_window: length of
@@ -248,16 +249,21 @@ def silence_removal(signal, sampling_rate, st_win, st_step, smooth_window=0.5, w
     0.01 / 0.99, :697-700).  svm_fit (keyword only): "sklearn" (the default) trains the onset SVM with scikit-learn; "device"
     trains it on the GPU (audioTrainTest.train_svm_device: the full fit, libsvm's five cross-validation fits and the sigmoid
     fit) and needs no scikit-learn; random_state is read by that mode alone (None: one draw from NumPy's global state, as
-    scikit-learn's fit makes).  Any other value of svm_fit raises ValueError."""
+    scikit-learn's fit makes).  Any other value of svm_fit raises ValueError.  kernel_cache / cache_bytes (keyword only, read
+    under svm_fit="device"; anything but their defaults raises ValueError otherwise) are audioTrainTest.train_svm_device's:
+    under "gram" the full fit and the five fold fits read one resident kernel matrix, with the same segments."""
     if svm_fit not in ("sklearn", "device"):
         raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
+    from . import audioTrainTest as aT
+    aT._svc_cache_mode(kernel_cache, cache_bytes, svm_fit == "device", "svm_fit")
     from . import ShortTermFeatures as stf
     weight = min(max(weight, 0.01), 0.99) if not 0 < weight < 1 else weight
     mono = audioBasicIO.stereo_to_mono(signal)
     st_feats, _ = stf.feature_extraction(mono, sampling_rate, st_win * sampling_rate, st_step * sampling_rate)   # :707-710
     quiet, loud = _energy_extremes(st_feats)
     if svm_fit == "device":
-        svm, mean, std = _train_onset_svm_device(quiet.T, loud.T, random_state)
+        cache = () if kernel_cache == "none" else (kernel_cache, cache_bytes)
+        svm, mean, std = _train_onset_svm_device(quiet.T, loud.T, random_state, *cache)
     else:
         svm, mean, std = _train_onset_svm(quiet.T, loud.T)                                 # :730-739, scikit-learn
     # onset probability of every frame in one kernel (replaces the predict_proba loop :741-748), then smoothing (:751)
@@ -318,9 +324,11 @@ def _onset_plan(lengths, sampling_rate, st_win, st_step, smooth_window, weight):
     return window, step, frames, widths, np.ascontiguousarray(weights, dtype=np.float64)
 
 
-def _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms):
+def _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms, cache_bytes=None):
     """The call of paa_silence_batch_* for clips of one sample type; returns the per-clip detail records.  The library's refusals
-    after the selection (an empty set: ValueError; more than 8192 rows: NotImplementedError) name the clip themselves."""
+    after the selection (an empty set: ValueError; more than 8192 rows: NotImplementedError) name the clip themselves.
+    cache_bytes (None: no resident kernel matrices) selects paa_silence_batch_*_cached; a record's `cached` tells whether the
+    clip's fits read one."""
     from . import audioTrainTest as aT
     n, D = len(clips), 68
     lens = np.array([c.shape[0] for c in clips], dtype=np.int64)
@@ -342,13 +350,18 @@ def _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, w
     iterations, status = np.zeros((n, 6), dtype=np.int32), np.zeros((n, 6), dtype=np.int32)
     seed = np.ascontiguousarray(seeds, dtype=np.int64)
     lib = _ffi.lib()
-    fn = lib.paa_silence_batch_i16 if as_i16 else lib.paa_silence_batch_f64
+    cached = np.zeros(n, dtype=np.int32)
+    if cache_bytes is None:
+        fn, tail = lib.paa_silence_batch_i16 if as_i16 else lib.paa_silence_batch_f64, ()
+    else:
+        fn, tail = lib.paa_silence_batch_i16_cached if as_i16 else lib.paa_silence_batch_f64_cached, (int(cache_bytes), _ffi.as_i32p(cached))
     rc = fn(_ffi.as_i16p(packed) if as_i16 else _ffi.as_f64p(packed), _ffi.as_i64p(offsets), n, float(sampling_rate), window, step,
             _ffi.as_i32p(widths), _ffi.as_f64p(weights), _ffi.as_i64p(seed), int(chunk_bytes or 0), _ffi.as_i64p(cap_off),
             _ffi.as_u8p(quiet), _ffi.as_u8p(loud), _ffi.as_u8p(active), _ffi.as_f64p(raw), _ffi.as_f64p(prob), _ffi.as_f64p(limits),
             _ffi.as_i32p(counts), _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_i32p(src), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
             _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b), _ffi.as_f64p(thr), _ffi.as_i32p(n_sv), _ffi.as_i32p(iterations),
-            _ffi.as_i32p(status), _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(stage_ms) if stage_ms is not None else None)
+            _ffi.as_i32p(status), _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(stage_ms) if stage_ms is not None else None,
+            *tail)
     _ffi.check(rc)
     aT._warn_not_converged(status.reshape(-1), 10 ** 7)
     out = []
@@ -360,11 +373,11 @@ def _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, w
                         seed=int(seed[c]), alpha_y=alpha_y[r0:r0 + nq + nl].copy(), rho=float(rho[c]), prob_a=float(prob_a[c]),
                         prob_b=float(prob_b[c]), n_sv=int(n_sv[c]), status=status[c].copy(), iterations=iterations[c].copy(),
                         sigmoid_iterations=int(sig_it[c]), sigmoid_stop=int(sig_stop[c]), raw_prob=raw[f0:f1].copy(),
-                        prob=prob[f0:f1].copy(), threshold=float(thr[c]), active=np.flatnonzero(active[f0:f1])))
+                        prob=prob[f0:f1].copy(), threshold=float(thr[c]), active=np.flatnonzero(active[f0:f1]), cached=bool(cached[c])))
     return out
 
 
-def _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weight, seeds, chunk_bytes, stage_ms=None):
+def _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weight, seeds, chunk_bytes, stage_ms=None, cache_bytes=None):
     """silence_removal_batch with the seeds given (a callable that draws them once the arguments have passed).  The whole batch is
     ONE library call, so that every refusal that follows the selection comes before any fit: int16 clips travel as int16; if
     any clip has another dtype the whole batch goes through np.double (feature_extraction_batch's rule).  Returns the per-clip
@@ -377,11 +390,12 @@ def _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weigh
     seeds = seeds(len(monos)) if callable(seeds) else list(seeds)
     as_i16 = all(m.dtype == np.int16 for m in monos)
     clips = [np.ascontiguousarray(m if as_i16 else np.double(m)) for m in monos]
-    return _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms)
+    cache = () if cache_bytes is None else (cache_bytes,)
+    return _silence_group(clips, as_i16, sampling_rate, window, step, frames, widths, weights, seeds, chunk_bytes, stage_ms, *cache)
 
 
 def silence_removal_batch(signals, sampling_rate, st_win, st_step, smooth_window=0.5, weight=0.5, *, random_state=None,
-                          return_details=False, chunk_bytes=None):
+                          return_details=False, chunk_bytes=None, kernel_cache="none", cache_bytes=None):
     """silence_removal(.., svm_fit="device") for a list of clips of ONE sampling rate, on the GPU end to end: the short-term
     matrices of the batched plan stay in device memory, and energy selection, training sets with their scalers, the SVM fits
     of all clips (one solver batch), the per-frame probabilities, smoothing and thresholds are kernels over the whole batch.
@@ -396,16 +410,20 @@ def silence_removal_batch(signals, sampling_rate, st_win, st_step, smooth_window
     loud_limit, mean, scale, seed, alpha_y (over the quiet rows, then the loud rows), rho, prob_a, prob_b, n_sv, status and
     iterations [6] (the full fit, the five folds), sigmoid_iterations, sigmoid_stop, raw_prob, prob (smoothed), threshold and
     active.  chunk_bytes: a bound below the library's 1 GiB for the device scratch of one chunk of clips (tests); no result
-    depends on it.
+    depends on it.  kernel_cache / cache_bytes (keyword only) are audioTrainTest.svc_fit_proba's with the clip as the job: under
+    "gram" a clip's full fit and fold fits read one resident kernel matrix (paa_silence_batch_*_cached), every result is
+    byte-equal, and the details carry `cached`.
 
     ValueError names the clip: fewer than 20 frames, or fewer than int(smooth_window / st_step) (both before the device is
     touched); an empty quiet or loud set (after the selection, before any fit).  NotImplementedError for a clip whose quiet
     and loud rows exceed the solver's 8192."""
+    from . import audioTrainTest as aT
+    cache_bytes = aT._cache_mode(kernel_cache, cache_bytes)
     signals = list(signals)
     if not signals:
         return ([], []) if return_details else []
     details = _silence_batch(signals, sampling_rate, st_win, st_step, smooth_window, weight,
-                             lambda n: _batch_seeds(random_state, n), chunk_bytes)
+                             lambda n: _batch_seeds(random_state, n), chunk_bytes, cache_bytes=cache_bytes)
     segments = [_onset_segments(d["active"], st_step) for d in details]
     return (segments, details) if return_details else segments
 
@@ -419,12 +437,16 @@ def _as_path_index(exc, ids):
     return type(exc)("clip %d:%s" % (ids[int(head[5:])], rest))
 
 
-def silence_removal_files(paths, st_win, st_step, smooth_window=0.5, weight=0.5, *, random_state=None):
+def silence_removal_files(paths, st_win, st_step, smooth_window=0.5, weight=0.5, *, random_state=None, kernel_cache="none",
+                          cache_bytes=None):
     """silence_removal_batch over audio files: they are read and grouped by sampling rate, one device batch per rate; the
     seeds are drawn in path order and the segment lists come back in path order.  smooth_window and weight: a scalar or one
     value per path.  A file that cannot be read raises ValueError naming its index.  As in silence_removal_batch the arguments
     of EVERY file are checked before a seed is drawn or the device is touched; a refusal that follows the selection comes before
-    the fits of its own rate's batch (the batches of other rates may have run)."""
+    the fits of its own rate's batch (the batches of other rates may have run).  kernel_cache / cache_bytes (keyword only) are
+    silence_removal_batch's."""
+    from . import audioTrainTest as aT
+    cache_bytes = aT._cache_mode(kernel_cache, cache_bytes)
     paths = list(paths)
     n = len(paths)
     smooth, weights = _per_clip(smooth_window, n, "smooth_window"), _per_clip(weight, n, "weight")
@@ -445,7 +467,8 @@ def silence_removal_files(paths, st_win, st_step, smooth_window=0.5, weight=0.5,
     for fs, members in groups.items():
         ids = [i for i, _ in members]
         try:
-            details = _silence_batch([s for _, s in members], fs, st_win, st_step, smooth[ids], weights[ids], [seeds[i] for i in ids], None)
+            details = _silence_batch([s for _, s in members], fs, st_win, st_step, smooth[ids], weights[ids], [seeds[i] for i in ids], None,
+                                     cache_bytes=cache_bytes)
         except (ValueError, NotImplementedError) as exc:
             raise _as_path_index(exc, ids)
         for i, d in zip(ids, details):

@@ -19,7 +19,8 @@ pyAudioAnalysis/audioTrainTest.py).
     evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, ...)   audioTrainTest.py:576-771
     extract_features_and_train(paths, ..., classifier_type, model_name, ...)                   audioTrainTest.py:236-361
     knn_split_predict(X, labels, jobs, proba=False, neighbors=False)   every kNN split of a sweep in one launch
-    svm_split_fit_predict(X, labels, jobs, kernel, ...), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
+    svm_split_fit_predict(X, labels, jobs, kernel, ..., kernel_cache="none"), smo_solve(X, tasks, ...)   every SVM fit of a sweep side by side on the GPU
+    smo_cache_layout(task_rows, groups, cache_bytes)              the layout of kernel_cache="gram": one resident kernel matrix per group of tasks
     train_svm_device(features, labels, c_param, kernel, random_state=None), to_sklearn_svc(model)   SVC(probability=True).fit on the GPU
     svc_fit_proba(X, labels, jobs, kernel, ...), platt_sigmoid(dec, signs, offsets)   its stages: fits, folds and sigmoids; the sigmoid alone
     svr_split_fit_predict(X, y, jobs, kernel, ..., kernel_cache="none"), svr_solve(X, y, tasks, ...)   every SVR fit of a sweep side by side on the GPU
@@ -1024,20 +1025,69 @@ def _warn_not_converged(status, max_iter):
 
 class SmoResult:
     """What smo_solve returns: alpha_y (a list of one array per task, alpha_t y_t in the task's row order), rho, iterations,
-    gap and status per task (SMO_CONVERGED / SMO_NOT_CONVERGED) and the number of kernel launches."""
+    gap and status per task (SMO_CONVERGED / SMO_NOT_CONVERGED) and the number of kernel launches; cached [n_tasks] (bool): the
+    task was solved from its group's resident kernel matrix (all False under kernel_cache="none")."""
 
-    def __init__(self, alpha_y, rho, iterations, gap, status, n_launches):
+    def __init__(self, alpha_y, rho, iterations, gap, status, n_launches, cached=None):
         self.alpha_y, self.rho, self.iterations, self.gap, self.status, self.n_launches = alpha_y, rho, iterations, gap, status, n_launches
+        self.cached = np.zeros(len(rho), dtype=bool) if cached is None else cached
 
 
-def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0):
+def _svc_cache_mode(kernel_cache, cache_bytes, device, keyword):
+    """_cache_mode for a caller whose SVM fits run on the device only under `keyword`="device": without it kernel_cache and
+    cache_bytes must be left at their defaults."""
+    cache_bytes_checked = _cache_mode(kernel_cache, cache_bytes)
+    if not device and (kernel_cache != "none" or cache_bytes is not None):
+        raise ValueError("kernel_cache / cache_bytes are read under %s='device' only" % keyword)
+    return cache_bytes_checked
+
+
+def smo_cache_layout(task_rows, groups, cache_bytes):
+    """The layout of the resident kernel matrices of smo_solve(kernel_cache="gram"), restated in plain NumPy (lib_smo.hpp:
+    smo_groups_form; the library's own answer is paa_debug_smo_cache_layout).  task_rows: per task its sample indices; groups:
+    per task an id, tasks with equal ids form a group (None: every task its own); groups are numbered in order of first
+    appearance.  A group's row list is the distinct sample indices of its tasks in order of first appearance over the tasks in
+    task order; pos maps every task row to its place in that list (a sample listed twice maps to one place).  The groups'
+    matrices, 8 N^2 bytes each, are packed in group order by svr_cache_chunks.  Returns (group_of [n_tasks], the list of the
+    groups' row lists, the list of the tasks' pos, chunk [n_groups] from 0 with -1 for a group that is not cached)."""
+    task_rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in task_rows]
+    ids = list(range(len(task_rows))) if groups is None else [int(g) for g in np.asarray(groups).reshape(-1)]
+    if len(ids) != len(task_rows):
+        raise ValueError("%d group ids for %d tasks" % (len(ids), len(task_rows)))
+    number, group_of, place = {}, [], []
+    for g in ids:
+        group_of.append(number.setdefault(g, len(number)))
+    for _ in number:
+        place.append({})
+    pos = []
+    for rows, g in zip(task_rows, group_of):
+        at = place[g]
+        pos.append(np.array([at.setdefault(int(r), len(at)) for r in rows], dtype=np.int32))
+    group_rows = [np.array(list(at), dtype=np.int32) for at in place]       # a dict keeps insertion order
+    return np.array(group_of, dtype=np.int32), group_rows, pos, svr_cache_chunks([len(r) for r in group_rows], cache_bytes)
+
+
+def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_launch=0, *, kernel_cache="none", cache_bytes=None,
+              groups=None):
     """Binary C-SVC dual problems over ONE sample matrix, all solved side by side (paa_smo_tasks_f64, smo_kernel: libsvm's
     Solver without shrinking, FP64).  X [n_samples][n_dims]; a task is (rows, signs, mean, scale, C, gamma): the rows X[rows]
     standardised as (x - mean) / scale, signs +1 (the first class) or -1, gamma read for kernel="rbf" only (None: 1 / n_dims).
     iters_per_launch bounds one kernel launch (0: the library's default); results do not depend on it.  A task that stops at
-    max_iter has the status SMO_NOT_CONVERGED and a warning is issued, as scikit-learn does.  Returns an SmoResult."""
+    max_iter has the status SMO_NOT_CONVERGED and a warning is issued, as scikit-learn does.  kernel_cache="gram" (keyword only)
+    solves from resident kernel matrices (paa_smo_tasks_cached_f64, smo_cached_kernel, DESIGN K23) with every output byte-equal
+    to kernel_cache="none": groups (one id per task, read under "gram" only; None: every task its own group) names the tasks
+    that share one matrix over their distinct rows -- they must have the same mean, scale and gamma, byte for byte; the
+    matrices are packed into chunks of at most cache_bytes (None: 4 GiB; see smo_cache_layout), and the tasks of a group whose
+    matrix alone exceeds it are solved as under "none" (their `cached` is False).  Returns an SmoResult."""
+    cache_bytes = _cache_mode(kernel_cache, cache_bytes)
     X = np.ascontiguousarray(X, dtype=np.float64)
     tasks = list(tasks)
+    if groups is not None:
+        if cache_bytes is None:
+            raise ValueError("groups are read under kernel_cache='gram' only")
+        groups = np.ascontiguousarray(np.asarray(groups).reshape(-1), dtype=np.int32)
+        if groups.shape[0] != len(tasks):
+            raise ValueError("%d group ids for %d tasks" % (groups.shape[0], len(tasks)))
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
         raise ValueError("sample matrix of shape %s" % (X.shape,))
     if not tasks:
@@ -1066,24 +1116,31 @@ def smo_solve(X, tasks, kernel="linear", eps=1e-3, max_iter=10**7, iters_per_lau
     n_tasks, total = len(tasks), int(off[-1])
     alpha_y, rho, gap = np.zeros(total), np.zeros(n_tasks), np.zeros(n_tasks)
     iterations, status, launches = np.zeros(n_tasks, dtype=np.int32), np.zeros(n_tasks, dtype=np.int32), np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_smo_tasks_f64(
-        _ffi.as_f64p(X), n_samples, n_dims, n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), sign.ctypes.data_as(C.POINTER(C.c_int8)),
-        _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
-        int(max_iter), int(iters_per_launch), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
-        _ffi.as_i32p(status), _ffi.as_i32p(launches)))
+    cached = np.zeros(n_tasks, dtype=np.int32)
+    args = (_ffi.as_f64p(X), n_samples, n_dims, n_tasks, _ffi.as_i64p(off), _ffi.as_i32p(idx), sign.ctypes.data_as(C.POINTER(C.c_int8)),
+            _ffi.as_f64p(mean), _ffi.as_f64p(scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
+            int(max_iter), int(iters_per_launch), _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho), _ffi.as_i32p(iterations), _ffi.as_f64p(gap),
+            _ffi.as_i32p(status), _ffi.as_i32p(launches))
+    if cache_bytes is None:
+        _ffi.check(_ffi.lib().paa_smo_tasks_f64(*args))
+    else:
+        _ffi.check(_ffi.lib().paa_smo_tasks_cached_f64(*args, None if groups is None else _ffi.as_i32p(groups), cache_bytes,
+                                                       _ffi.as_i32p(cached)))
     _warn_not_converged(status, int(max_iter))
-    return SmoResult([alpha_y[off[t]:off[t + 1]] for t in range(n_tasks)], rho, iterations, gap, status, int(launches[0]))
+    return SmoResult([alpha_y[off[t]:off[t + 1]] for t in range(n_tasks)], rho, iterations, gap, status, int(launches[0]), cached != 0)
 
 
 class SvmSplitResult(_SplitResult):
     """What svm_split_fit_predict returns: label [Q] (class values as in `labels`), decision [Q][max_pairs] or None (zeros past
     a job's pairs), test_off [n_jobs + 1], classes (per job the classes present in its training list, ascending), task_off
     [n_jobs + 1] (job j owns the tasks task_off[j] .. task_off[j + 1] - 1, its pairs (a, b), a < b, row-major) and per task
-    iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel."""
+    iterations, status (SMO_CONVERGED / SMO_NOT_CONVERGED) and n_sv; n_launches of the solver kernel; cached [n_jobs] (bool): the
+    job's tasks were solved from its resident kernel matrix (all False under kernel_cache="none")."""
 
-    def __init__(self, label, decision, test_off, classes, task_off, iterations, status, n_sv, n_launches):
+    def __init__(self, label, decision, test_off, classes, task_off, iterations, status, n_sv, n_launches, cached=None):
         self.label, self.decision, self.test_off, self.classes, self.task_off = label, decision, test_off, classes, task_off
         self.iterations, self.status, self.n_sv, self.n_launches = iterations, status, n_sv, n_launches
+        self.cached = np.zeros(len(classes), dtype=bool) if cached is None else cached
 
     def job(self, j):
         """(labels, decision values [n_test][pairs_j] or None, iterations [pairs_j], status [pairs_j], n_sv [pairs_j]) of job j."""
@@ -1093,12 +1150,16 @@ class SvmSplitResult(_SplitResult):
                 self.status[t0:t1], self.n_sv[t0:t1])
 
 
-def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, decision=False, max_iter=10**7, iters_per_launch=0):
+def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, decision=False, max_iter=10**7, iters_per_launch=0, *,
+                          kernel_cache="none", cache_bytes=None):
     """SVC(C, kernel, gamma).fit(train).predict(test) for every job of a sweep over ONE sample matrix (paa_svc_fit_splits_f64:
     every pair of the classes present in a job's training list is a binary problem of smo_kernel, all of them side by side;
     then libsvm's one-against-one vote of every test row).  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the
     training rows); a job is (train_idx, test_idx, mean, scale, C).  gamma=None is 1 / n_dims, the reference's gamma='auto'.
-    No probabilities are fitted: the sweep reads vote labels only.  Returns an SvmSplitResult."""
+    No probabilities are fitted: the sweep reads vote labels only.  kernel_cache and cache_bytes (keyword only) are smo_solve's
+    with the JOB as the group: "gram" solves every pair of a job from the job's one resident kernel matrix
+    (paa_svc_fit_splits_cached_f64) with byte-equal results.  Returns an SvmSplitResult."""
+    cache_bytes = _cache_mode(kernel_cache, cache_bytes)
     p = _pack_jobs(X, labels, jobs, "C", float, kernel)
     n_samples, n_dims = p.X.shape
     classes = [np.unique(p.labels[rows]) for rows in p.inside]
@@ -1111,15 +1172,20 @@ def svm_split_fit_predict(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3
     dec = np.zeros((Q, max_pairs), dtype=np.float64) if decision else None
     iterations, status, n_sv = (np.zeros(max(n_tasks, 1), dtype=np.int32) for _ in range(3))
     launches = np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_svc_fit_splits_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(classes), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
-        _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch), _ffi.as_i32p(label),
-        _ffi.as_f64p(dec) if decision else None, max_pairs, n_tasks, _ffi.as_i32p(iterations), _ffi.as_i32p(status), _ffi.as_i32p(n_sv),
-        _ffi.as_i32p(launches)))
+    cached = np.zeros(max(len(classes), 1), dtype=np.int32)
+    args = (_ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(classes), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+            _ffi.as_i64p(p.test_off), _ffi.as_i32p(p.test_idx), _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr),
+            _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps), int(max_iter), int(iters_per_launch), _ffi.as_i32p(label),
+            _ffi.as_f64p(dec) if decision else None, max_pairs, n_tasks, _ffi.as_i32p(iterations), _ffi.as_i32p(status), _ffi.as_i32p(n_sv),
+            _ffi.as_i32p(launches))
+    if cache_bytes is None:
+        _ffi.check(_ffi.lib().paa_svc_fit_splits_f64(*args))
+    else:
+        _ffi.check(_ffi.lib().paa_svc_fit_splits_cached_f64(*args, cache_bytes, _ffi.as_i32p(cached)))
     iterations, status, n_sv = iterations[:n_tasks], status[:n_tasks], n_sv[:n_tasks]
     _warn_not_converged(status, int(max_iter))
-    return SvmSplitResult(label.astype(np.int64), dec, p.test_off, classes, task_off, iterations, status, n_sv, int(launches[0]))
+    return SvmSplitResult(label.astype(np.int64), dec, p.test_off, classes, task_off, iterations, status, n_sv, int(launches[0]),
+                          cached[:len(classes)] != 0)
 
 
 PLATT_CONVERGED, PLATT_LINE_SEARCH_FAILED, PLATT_MAX_ITERATIONS = 0, 1, 2      # PAA_PLATT_*
@@ -1165,7 +1231,8 @@ class SvcProbaResult:
     indices in pair-row order: the rows of a in train-list order, then those of b), signs (+1 / -1), alpha_y (the full fit's
     alpha_t y_t over those rows), rho, prob_a, prob_b, n_sv, iterations / status [6] (slot 0: the full fit, 1..5: the folds;
     status 0: the fold made no task), sigmoid_iterations, sigmoid_stop (PLATT_*) and cv_dec (the held-out decision values over
-    the rows, or None); n_launches of the solver kernel."""
+    the rows, or None); n_launches of the solver kernel; cached [n_jobs] (bool): the job's full fits and fold fits were solved
+    from its resident kernel matrix (all False under kernel_cache="none")."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -1181,13 +1248,17 @@ def _seeds(seeds, n_jobs):
     return s
 
 
-def svc_fit_proba(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, seeds=0, return_cv=False, max_iter=10**7, iters_per_launch=0):
+def svc_fit_proba(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, seeds=0, return_cv=False, max_iter=10**7, iters_per_launch=0, *,
+                  kernel_cache="none", cache_bytes=None):
     """SVC(C, kernel, gamma, probability=True).fit(train) for every job over ONE sample matrix (paa_svc_fit_proba_f64): per pair
     of the classes present in a job the full fit and the fits of libsvm's five cross-validation folds are binary problems of
     smo_kernel, all of them side by side; svc_pairs_kernel scores every fold's held-out rows; one platt_sigmoid_kernel launch
     fits probA / probB of every pair.  X [n_samples][n_dims]; labels [n_samples] (integers >= 0 on the training rows); a job is
     (train_idx, mean, scale, C).  seeds: libsvm's random_seed of every job (what scikit-learn draws from random_state), one int
-    for all jobs or one per job; the folds are libsvm's for that seed.  gamma=None is 1 / n_dims.  Returns an SvcProbaResult."""
+    for all jobs or one per job; the folds are libsvm's for that seed.  gamma=None is 1 / n_dims.  kernel_cache and cache_bytes
+    (keyword only) are smo_solve's with the JOB as the group: under "gram" the full fits and all fold fits of a job read the
+    job's one resident kernel matrix (paa_svc_fit_proba_cached_f64) with byte-equal results.  Returns an SvcProbaResult."""
+    cache_bytes = _cache_mode(kernel_cache, cache_bytes)
     jobs = list(jobs)
     for j, job in enumerate(jobs):
         if len(job) != 4:
@@ -1216,18 +1287,22 @@ def svc_fit_proba(X, labels, jobs, kernel="linear", gamma=None, eps=1e-3, seeds=
     n_sv, sig_it, sig_stop = (np.zeros(m, dtype=np.int32) for _ in range(3))
     iterations, status = np.zeros((m, 6), dtype=np.int32), np.zeros((m, 6), dtype=np.int32)
     launches = np.zeros(1, dtype=np.int32)
-    _ffi.check(_ffi.lib().paa_svc_fit_proba_f64(
-        _ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(jobs), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
-        _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
-        int(max_iter), int(iters_per_launch), _ffi.as_i64p(seed), n_pairs, n_rows, _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
-        _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b), _ffi.as_i32p(n_sv), _ffi.as_i32p(iterations), _ffi.as_i32p(status),
-        _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(cv) if return_cv else None, _ffi.as_i32p(launches)))
+    cached = np.zeros(max(len(jobs), 1), dtype=np.int32)
+    args = (_ffi.as_f64p(p.X), n_samples, n_dims, _ffi.as_i32p(p.labels), len(jobs), _ffi.as_i64p(p.train_off), _ffi.as_i32p(p.train_idx),
+            _ffi.as_f64p(p.mean), _ffi.as_f64p(p.scale), _ffi.as_f64p(C_arr), _ffi.as_f64p(g_arr), _KERNEL_TYPES[kernel], float(eps),
+            int(max_iter), int(iters_per_launch), _ffi.as_i64p(seed), n_pairs, n_rows, _ffi.as_f64p(alpha_y), _ffi.as_f64p(rho),
+            _ffi.as_f64p(prob_a), _ffi.as_f64p(prob_b), _ffi.as_i32p(n_sv), _ffi.as_i32p(iterations), _ffi.as_i32p(status),
+            _ffi.as_i32p(sig_it), _ffi.as_i32p(sig_stop), _ffi.as_f64p(cv) if return_cv else None, _ffi.as_i32p(launches))
+    if cache_bytes is None:
+        _ffi.check(_ffi.lib().paa_svc_fit_proba_f64(*args))
+    else:
+        _ffi.check(_ffi.lib().paa_svc_fit_proba_cached_f64(*args, cache_bytes, _ffi.as_i32p(cached)))
     _warn_not_converged(status[:n_pairs].reshape(-1), int(max_iter))
     per_pair = lambda a: [a[row_off[t]:row_off[t + 1]] for t in range(n_pairs)]
     return SvcProbaResult(classes=classes, pair_off=pair_off, rows=rows, signs=signs, alpha_y=per_pair(alpha_y), rho=rho[:n_pairs],
                           prob_a=prob_a[:n_pairs], prob_b=prob_b[:n_pairs], n_sv=n_sv[:n_pairs], iterations=iterations[:n_pairs],
                           status=status[:n_pairs], sigmoid_iterations=sig_it[:n_pairs], sigmoid_stop=sig_stop[:n_pairs],
-                          cv_dec=per_pair(cv) if return_cv else None, n_launches=int(launches[0]))
+                          cv_dec=per_pair(cv) if return_cv else None, n_launches=int(launches[0]), cached=cached[:len(jobs)] != 0)
 
 
 class DeviceSvc:
@@ -1252,8 +1327,9 @@ def _libsvm_seed(random_state):
     return int(np.random.RandomState(random_state).randint(np.iinfo('i').max))
 
 
-def _train_svm_device(features, labels, c_param, kernel, random_state, mean, scale):
+def _train_svm_device(features, labels, c_param, kernel, random_state, mean, scale, kernel_cache="none", cache_bytes=None):
     """train_svm_device over the rows (features - mean) / scale, standardised on the load path."""
+    _cache_mode(kernel_cache, cache_bytes)
     X = np.ascontiguousarray(features, dtype=np.float64)
     raw = np.asarray(labels).reshape(-1)
     if X.ndim != 2 or X.shape[0] < 1 or raw.shape[0] != X.shape[0]:
@@ -1269,7 +1345,8 @@ def _train_svm_device(features, labels, c_param, kernel, random_state, mean, sca
         raise NotImplementedError("a pair of classes has %d rows: the GPU solver serves at most %d rows per pair" % (top, SMO_MAX_ROWS))
     seed = _libsvm_seed(random_state)
     n, n_dims = X.shape
-    res = svc_fit_proba(X, y.astype(np.int32), [(np.arange(n), mean, scale, float(c_param))], kernel=kernel, seeds=seed)
+    res = svc_fit_proba(X, y.astype(np.int32), [(np.arange(n), mean, scale, float(c_param))], kernel=kernel, seeds=seed,
+                        kernel_cache=kernel_cache, cache_bytes=cache_bytes)
     # libsvm's model: the support vectors are the union over the pairs, grouped by class ascending, in sample order within a class
     coef = np.zeros((k - 1, n))
     is_sv = np.zeros(n, dtype=bool)
@@ -1295,15 +1372,18 @@ def _train_svm_device(features, labels, c_param, kernel, random_state, mean, sca
                      n_features_in_=n_dims, random_seed=seed, fit_result=res)
 
 
-def train_svm_device(features, labels, c_param, kernel='linear', *, random_state=None):
+def train_svm_device(features, labels, c_param, kernel='linear', *, random_state=None, kernel_cache="none", cache_bytes=None):
     """train_svm on the GPU: SVC(C=c_param, kernel=kernel, probability=True, gamma='auto', random_state=random_state).fit(features,
     labels) by svc_fit_proba -- every pair's full fit, libsvm's five cross-validation fits per pair for that seed and the
     sigmoid fits.  Returns a DeviceSvc.  random_state=None draws the seed from NumPy's global state exactly as scikit-learn
     does (one randint), an int goes through np.random.RandomState.  A pair of classes above 8192 rows raises
     NotImplementedError; there is no CPU fallback.  Agreement with scikit-learn is bounded by libsvm's stopping tolerance (its
-    kernel cache is float32), not bit-exact."""
+    kernel cache is float32), not bit-exact.  kernel_cache / cache_bytes (keyword only) are svc_fit_proba's: under "gram" every
+    pair's full fit and fold fits read ONE resident kernel matrix over all rows, and the model is the same, byte for byte
+    (fit_result.cached tells whether the matrix fitted the budget)."""
+    _cache_mode(kernel_cache, cache_bytes)
     n_dims = np.asarray(features).shape[1] if np.asarray(features).ndim == 2 else 0
-    return _train_svm_device(features, labels, c_param, kernel, random_state, np.zeros(n_dims), np.ones(n_dims))
+    return _train_svm_device(features, labels, c_param, kernel, random_state, np.zeros(n_dims), np.ones(n_dims), kernel_cache, cache_bytes)
 
 
 def to_sklearn_svc(model):
@@ -1370,7 +1450,7 @@ def _cache_mode(kernel_cache, cache_bytes):
 
 
 def svr_cache_chunks(rows, cache_bytes):
-    """The packing rule of the resident kernel matrices, restated (lib_svrfit.hpp: svr_cache_pack): rows [n_tasks] are the
+    """The packing rule of the resident kernel matrices, restated (lib_gramcache.hpp: svr_cache_pack): rows [n_tasks] are the
     tasks' row counts; the matrix of a task of n rows takes 8 n^2 bytes.  In task order, a task whose matrix exceeds
     cache_bytes is not cached; any other joins the open chunk when the chunk's matrices and its own fit cache_bytes together
     and otherwise opens the next.  Returns the chunk of every task from 0, -1 for a task that is not cached."""
@@ -2198,7 +2278,8 @@ def _draw_split(n_samples, train_percentage):
 
 
 def evaluate_classifier(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                        train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
+                        train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn",
+                        kernel_cache="none", cache_bytes=None):
     """Picks the classifier parameter with the best cross-validated accuracy (parameter_mode 0) or macro F1 (1)
     (reference :576-771): for every value, n_exp random splits (n_exp = -1: int(50000 / n_samples) + 1), each with its own
     StandardScaler; with list_of_ids the n_exp GroupShuffleSplit(train_size=.8) splits are drawn once and shared by every value.
@@ -2216,6 +2297,9 @@ def evaluate_classifier(features, class_names, classifier_name, params, paramete
     and classifies every test row.  The one visible difference to the default: scikit-learn's probabilistic fits draw a libsvm
     seed from NumPy's global state between the splits, the device mode consumes that state for the splits only, so for one seed
     the two modes see different splits.  svm_fit="sklearn" (the default) is the behaviour described above, untouched.
+    kernel_cache / cache_bytes (keyword only, read under svm_fit="device"; anything but their defaults raises ValueError
+    otherwise) are svm_split_fit_predict's: "gram" solves every split's pairs from the split's one resident kernel matrix, with
+    the same predictions.
     forest_fit="device" (keyword only; "randomforest" / "extratrees", any other type raises ValueError before any work): the same
     path -- ALL splits are drawn up front in parameter-major order, then ONE seed per split is drawn from NumPy's global state in
     job order (np.random.randint(np.iinfo(np.int32).max)), and ONE forest_split_fit_predict call fits the n_estimators trees of
@@ -2230,17 +2314,20 @@ def evaluate_classifier(features, class_names, classifier_name, params, paramete
     random_state=<that seed> (stage 0 of balanced 2-, 4- and 8-class splits bit for bit; see boosting_split_fit_predict).
     boosting_fit="sklearn" (the default): untouched."""
     return evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids, n_exp,
-                                    train_percentage, smote, svm_fit=svm_fit, forest_fit=forest_fit, boosting_fit=boosting_fit)[0]
+                                    train_percentage, smote, svm_fit=svm_fit, forest_fit=forest_fit, boosting_fit=boosting_fit,
+                                    kernel_cache=kernel_cache, cache_bytes=cache_bytes)[0]
 
 
 def evaluate_classifier_full(features, class_names, classifier_name, params, parameter_mode, list_of_ids=None, n_exp=-1,
-                             train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
+                             train_percentage=0.90, smote=False, *, svm_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn",
+                             kernel_cache="none", cache_bytes=None):
     """evaluate_classifier, returning (the chosen parameter, the confusion matrix of every parameter value, the predictions
     [parameter][experiment] of every split's test rows)."""
     if svm_fit not in ("sklearn", "device"):
         raise ValueError("svm_fit=%r: 'sklearn' or 'device'" % (svm_fit,))
     if svm_fit == "device" and classifier_name not in _SVM_TYPES:
         raise ValueError("svm_fit='device' serves the classifier types %s, not %r" % (" and ".join(_SVM_TYPES), classifier_name))
+    _svc_cache_mode(kernel_cache, cache_bytes, svm_fit == "device", "svm_fit")
     if forest_fit not in ("sklearn", "device"):
         raise ValueError("forest_fit=%r: 'sklearn' or 'device'" % (forest_fit,))
     if forest_fit == "device" and classifier_name not in _FOREST_FIT_KINDS:
@@ -2286,7 +2373,8 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
         jobs = [(tr, te, mean, scale, cast(C_param)) for C_param, row in zip(params, splits) for tr, te, mean, scale in row]
         res = knn_split_predict(X, y, jobs) if knn else forest_split_fit_predict(X, y, jobs, classifier_name) if forest_fit == "device" else \
             boosting_split_fit_predict(X, y, jobs) if boosting_fit == "device" else \
-            svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear")
+            svm_split_fit_predict(X, y, jobs, kernel="rbf" if classifier_name == "svm_rbf" else "linear", kernel_cache=kernel_cache,
+                                  cache_bytes=cache_bytes)
         as_label = (lambda v: v) if knn else y.dtype.type      # kNN: the result's int64 as it is
         predictions = [[[as_label(v) for v in res.job(i * n_exp + e)[0]] for e in range(n_exp)] for i in range(len(splits))]
 
@@ -2351,7 +2439,7 @@ def evaluate_classifier_full(features, class_names, classifier_name, params, par
 
 def extract_features_and_train(paths, mid_window, mid_step, short_window, short_step, classifier_type, model_name,
                                compute_beat=False, train_percentage=0.90, dict_of_ids=None, use_smote=False, *, svm_fit="sklearn",
-                               final_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn"):
+                               final_fit="sklearn", forest_fit="sklearn", boosting_fit="sklearn", kernel_cache="none", cache_bytes=None):
     """Segment-based feature extraction of one folder per class, parameter tuning and training of a classifier (reference
     :236-361): features from multiple_directory_feature_extraction (GPU), rows with NaN / Inf dropped, the parameter from
     evaluate_classifier (macro F1, n_exp = -1), a StandardScaler over all rows, the final fit, and the model files in the
@@ -2365,7 +2453,9 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     train_forest_device; the model file is a pickled RandomForestClassifier / ExtraTreesClassifier made by to_sklearn_forest.
     boosting_fit (keyword only): "device" ("gradientboosting" only, any other type raises ValueError before any work) tunes
     n_estimators with evaluate_classifier(boosting_fit="device") AND makes the final fit with train_gradient_boosting_device; the model
-    file is a pickled GradientBoostingClassifier made by to_sklearn_boosting."""
+    file is a pickled GradientBoostingClassifier made by to_sklearn_boosting.  kernel_cache / cache_bytes (keyword only, read under
+    svm_fit="device" and final_fit="device"; anything but their defaults raises ValueError when neither is set) go to the tuning
+    step under svm_fit="device" and to train_svm_device under final_fit="device": the model file has the same bytes."""
     _check_boosting_fit(boosting_fit, classifier_type)
     if forest_fit not in ("sklearn", "device") or (forest_fit == "device" and classifier_type not in _FOREST_FIT_KINDS):
         raise ValueError("forest_fit=%r with the classifier type %r" % (forest_fit, classifier_type))
@@ -2373,6 +2463,8 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
         raise ValueError("svm_fit=%r with the classifier type %r" % (svm_fit, classifier_type))
     if final_fit not in ("sklearn", "device") or (final_fit == "device" and classifier_type not in _SVM_TYPES):
         raise ValueError("final_fit=%r with the classifier type %r" % (final_fit, classifier_type))
+    _svc_cache_mode(kernel_cache, cache_bytes, svm_fit == "device" or final_fit == "device", "svm_fit / final_fit")
+    tune_cache = dict(kernel_cache=kernel_cache, cache_bytes=cache_bytes) if svm_fit == "device" else {}
     if use_smote:
         raise NotImplementedError("use_smote=True: this package does not resample (see evaluate_classifier)")
     from sklearn.preprocessing import StandardScaler
@@ -2409,7 +2501,7 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     features = kept
     best_param = evaluate_classifier(features, class_names, classifier_type, classifier_par, 1, list_of_ids, n_exp=-1,
                                      train_percentage=train_percentage, smote=use_smote, svm_fit=svm_fit,
-                                     forest_fit=forest_fit, boosting_fit=boosting_fit)
+                                     forest_fit=forest_fit, boosting_fit=boosting_fit, **tune_cache)
     print("Selected params: {0:.5f}".format(best_param))
     features, labels = features_to_matrix(features)
     scaler = StandardScaler()
@@ -2422,7 +2514,8 @@ def extract_features_and_train(paths, mid_window, mid_step, short_window, short_
     else:
         if final_fit == "device":
             classifier = to_sklearn_svc(train_svm_device(features, labels, best_param,
-                                                         kernel="rbf" if classifier_type == "svm_rbf" else "linear"))
+                                                         kernel="rbf" if classifier_type == "svm_rbf" else "linear",
+                                                         kernel_cache=kernel_cache, cache_bytes=cache_bytes))
         elif forest_fit == "device":
             classifier = to_sklearn_forest(train_forest_device(features, labels, int(best_param), kind=classifier_type), classifier_type)
         elif boosting_fit == "device":

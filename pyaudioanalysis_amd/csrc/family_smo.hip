@@ -1,8 +1,9 @@
 // The batched SMO solver and the one-against-one vote of the SVM split sweep (kernels_smo.hpp: the SVM fits of
-// audioTrainTest.evaluate_classifier) and the sigmoid fit of probabilistic SVMs (kernels_platt.hpp) -- own translation unit,
+// audioTrainTest.evaluate_classifier; kernels_smocache.hpp: the same solver over resident kernel matrices) and the sigmoid fit of probabilistic SVMs (kernels_platt.hpp) -- own translation unit,
 // see model_launch.hpp.  The glue kernels of batched silence removal (kernels_onset.hpp) live here with the fit they surround.
 #include "model_launch.hpp"
 #include "kernels_smo.hpp"
+#include "kernels_smocache.hpp"
 #include "kernels_platt.hpp"
 #include "kernels_onset.hpp"
 
@@ -16,6 +17,12 @@ int smo_step(const smo::SmoDev &m, const int *d_live, int n_live, int n_max, int
     const size_t lds = ((size_t)4 * pitch + n_max) * sizeof(double);
     if (raise_lds(reinterpret_cast<const void *>(&smo::smo_kernel), lds)) return -1;
     hipLaunchKernelGGL(smo::smo_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), lds, stream, m, d_live, budget);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int smo_cached_step(const smo::SmoDev &m, const smo::SmoCacheDev &c, const int *d_live, int n_live, int budget, hipStream_t stream) {
+    if (n_live < 1 || budget < 1) return -1;
+    hipLaunchKernelGGL(smo::smo_cached_kernel, dim3((unsigned)n_live), dim3(smo::kThreads), 0, stream, m, c, d_live, budget);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -38,7 +38,7 @@ int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_m
 int svr_gram(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_chunk, int n_chunk, int n_max,
              const svrfit::GramTile *d_tiles, long long n_tiles, hipStream_t stream) {
     static_assert(svrfit::kGramTile == smo::kGroups && svrfit::kPitchLanes == smo::kGroupLanes, "one row of a tile per group");
-    if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > smo::kMaxRows) return -2;
+    if (m.n_dims < 1 || m.n_dims > smo::kMaxDims || n_max < 1 || n_max > svrfit::kGramMaxRows) return -2;
     if (n_chunk < 1 || n_tiles < 1 || n_tiles > 0x7fffffffLL) return -1;
     const int pitch = (m.n_dims + smo::kGroupLanes - 1) / smo::kGroupLanes * smo::kGroupLanes;
     const unsigned row_blocks = (unsigned)((n_max + svrfit::kGramTile - 1) / svrfit::kGramTile);

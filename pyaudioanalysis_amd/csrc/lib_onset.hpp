@@ -240,6 +240,8 @@ struct SilenceOut {
     double *alpha_y, *rho, *prob_a, *prob_b, *threshold;
     int32_t *n_sv, *iterations, *status, *sig_iterations, *sig_stop;
     double *stage_ms;         // [6] or null: features, selection, training sets, fits, probability and threshold, copy-back
+    int32_t *clip_cached = nullptr;       // [n_clips], paa_silence_batch_*_cached: the clip's fits read a resident kernel matrix under the
+    int64_t cache_bytes = 0;              // budget cache_bytes (null: no resident matrices)
 };
 
 struct StageClock {
@@ -329,7 +331,8 @@ static int silence_chunk(Lane &lane, const void *packed, const int64_t *offsets,
     if ((rc = svc_pair_tasks(p, labels.data(), n, train_off.data(), train_idx.data(), C_one.data(), gamma.data(), 0))) return rc;
     alpha_y.resize(rows);
     const ProbaFitOut fit{alpha_y.data(), o.rho + c0, o.prob_a + c0, o.prob_b + c0, o.n_sv + c0, o.iterations + 6 * (size_t)c0,
-                          o.status + 6 * (size_t)c0, o.sig_iterations + c0, o.sig_stop + c0, nullptr, nullptr};
+                          o.status + 6 * (size_t)c0, o.sig_iterations + c0, o.sig_stop + c0, nullptr, nullptr,
+                          o.clip_cached ? o.clip_cached + c0 : nullptr, o.cache_bytes};
     if ((rc = svc_fit_proba_resident(b.m.X, b.m.mean, b.m.scale, n_dims, p, seeds + c0, 0, 1e-3, 10000000, 0, fit))) return rc;
     if ((rc = clock.mark(3))) return rc;
     // stages 4 and 5
@@ -370,6 +373,7 @@ static int run_silence_batch(const void *packed, const int64_t *offsets, int64_t
         !o.limits || !o.counts || !o.mean || !o.scale || !o.src || !o.alpha_y || !o.rho || !o.prob_a || !o.prob_b || !o.threshold ||
         !o.n_sv || !o.iterations || !o.status || !o.sig_iterations || !o.sig_stop)
         return fail(PAA_ERR_ARG, "null argument");
+    if (o.clip_cached && o.cache_bytes <= 0) return fail(PAA_ERR_ARG, "cache_bytes = %lld: a positive budget is needed", (long long)o.cache_bytes);
     if (n_clips < 1 || n_clips > 0x3fffffffLL) return fail(PAA_ERR_ARG, "%lld clips", (long long)n_clips);
     if (window < 2 || step < 1) return fail(PAA_ERR_ARG, "window=%d step=%d: need window >= 2, step >= 1", window, step);
     const int n_dims = 2 * kBase;
@@ -423,6 +427,23 @@ extern "C" int paa_silence_batch_i16(const int16_t *packed, PAA_SILENCE_BATCH_AR
 }
 extern "C" int paa_silence_batch_f64(const double *packed, PAA_SILENCE_BATCH_ARGS) {
     return run_silence_batch(packed, offsets, n_clips, 1, fs, window, step, widths, weights, seeds, chunk_bytes, row_cap_off, PAA_SILENCE_BATCH_OUT);
+}
+// ... with every clip's full fit and fold fits on one resident kernel matrix (paa_svc_fit_proba_cached_f64's form: a clip is a job)
+static int run_silence_batch_cached(const void *packed, const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window,
+                                    int step, const int32_t *widths, const double *weights, const int64_t *seeds, int64_t chunk_bytes,
+                                    const int64_t *row_cap_off, SilenceOut o, int64_t cache_bytes, int32_t *clip_cached) {
+    if (!clip_cached) return fail(PAA_ERR_ARG, "null argument");
+    o.clip_cached = clip_cached;
+    o.cache_bytes = cache_bytes;
+    return run_silence_batch(packed, offsets, n_clips, sample_kind, fs, window, step, widths, weights, seeds, chunk_bytes, row_cap_off, o);
+}
+extern "C" int paa_silence_batch_i16_cached(const int16_t *packed, PAA_SILENCE_BATCH_ARGS, int64_t cache_bytes, int32_t *clip_cached) {
+    return run_silence_batch_cached(packed, offsets, n_clips, 0, fs, window, step, widths, weights, seeds, chunk_bytes, row_cap_off,
+                                    PAA_SILENCE_BATCH_OUT, cache_bytes, clip_cached);
+}
+extern "C" int paa_silence_batch_f64_cached(const double *packed, PAA_SILENCE_BATCH_ARGS, int64_t cache_bytes, int32_t *clip_cached) {
+    return run_silence_batch_cached(packed, offsets, n_clips, 1, fs, window, step, widths, weights, seeds, chunk_bytes, row_cap_off,
+                                    PAA_SILENCE_BATCH_OUT, cache_bytes, clip_cached);
 }
 #undef PAA_SILENCE_BATCH_ARGS
 #undef PAA_SILENCE_BATCH_OUT

@@ -1,7 +1,12 @@
 // The SVM fits of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700 with train_svm :132-155) on the device: a batch
 // of binary C-SVC dual problems (tasks) over ONE uploaded sample matrix, solved by relaunching smo_kernel until every task has
 // stopped, and the split sweep built on it (pair tasks per job, then the one-against-one vote of every test row).
-// Kernels: kernels_smo.hpp (family_smo.hip).
+// With resident kernel matrices (DESIGN K23, the *_cached_f64 entry points) the tasks of a GROUP -- one mean / scale / gamma: the pair
+// fits and the fold fits of a job -- share one matrix over the group's distinct rows (SmoGroups).  The groups are packed into chunks
+// whose matrices fit `cache_bytes` (svr_cache_pack, lib_gramcache.hpp); per chunk: the Gram pass over the groups' row lists, then
+// smo_relaunch_some with smo_cached_kernel over the chunk's tasks.  The tasks of a group whose matrix alone exceeds the budget go to
+// smo_kernel in the same call.
+// Kernels: kernels_smo.hpp and kernels_smocache.hpp (family_smo.hip), kernels_svrcache.hpp (family_svr.hip).
 #pragma once
 
 // the limits, for callers and tests: threads per workgroup, groups, rows per task, test rows per scoring workgroup, the default
@@ -108,6 +113,153 @@ static int smo_solve_batch(smo::SmoDev &m, SmoState &s, const std::vector<smo::S
     });
 }
 
+// ---- resident kernel matrices (DESIGN K23) ----------------------------------------------------------------------------------------
+
+// The groups of a batch: tasks with equal ids form a group (ids null: every task its own), numbered in order of first appearance.  A
+// group's row list is the distinct sample indices of its tasks in order of first appearance over the tasks in task order; `groups`
+// holds it as a task of the Gram pass (off into `rows`, n = N, the stat and gamma of the group's first task).  pos [rows of the
+// batch]: per task row its place in the group's row list -- a sample listed twice maps to one place
+struct SmoGroups {
+    std::vector<smo::SmoTask> groups;
+    std::vector<int> rows, pos, group_of, first_task;     // group_of [n_tasks]; first_task [n_groups]
+};
+static void smo_groups_form(SmoGroups &g, const std::vector<smo::SmoTask> &tasks, const int *idx, const int32_t *ids) {
+    const size_t nt = tasks.size();
+    g.group_of.resize(nt);
+    std::vector<std::vector<int>> members;
+    std::map<int32_t, int> seen;
+    size_t total = 0;
+    int top = 0;
+    for (size_t t = 0; t < nt; ++t) {
+        int gi = (int)members.size();
+        if (ids) {
+            const auto it = seen.find(ids[t]);
+            if (it != seen.end()) gi = it->second;
+            else seen[ids[t]] = gi;
+        }
+        if (gi == (int)members.size()) { members.emplace_back(); g.first_task.push_back((int)t); }
+        members[gi].push_back((int)t);
+        g.group_of[t] = gi;
+        total = std::max(total, (size_t)(tasks[t].off + tasks[t].n));
+    }
+    for (size_t i = 0; i < total; ++i) top = std::max(top, idx[i]);
+    g.pos.assign(total, 0);
+    std::vector<int> slot((size_t)top + 1, -1);
+    for (size_t gi = 0; gi < members.size(); ++gi) {
+        const size_t start = g.rows.size();
+        for (int t : members[gi])
+            for (long long r = tasks[t].off; r < tasks[t].off + tasks[t].n; ++r) {
+                int &at = slot[idx[r]];
+                if (at < 0) { at = (int)(g.rows.size() - start); g.rows.push_back(idx[r]); }
+                g.pos[r] = at;
+            }
+        for (size_t k = start; k < g.rows.size(); ++k) slot[g.rows[k]] = -1;
+        const smo::SmoTask &F = tasks[g.first_task[gi]];
+        g.groups.push_back({(long long)start, (int)(g.rows.size() - start), F.stat, 1.0, F.gamma});
+    }
+}
+// a group's tasks standardise and weigh alike: every byte of their rows of mean / std [..][n_dims] and of their gamma
+static int smo_groups_check(const SmoGroups &g, const std::vector<smo::SmoTask> &tasks, const double *mean, const double *std, int n_dims) {
+    for (size_t t = 0; t < tasks.size(); ++t) {
+        const int f = g.first_task[g.group_of[t]];
+        const smo::SmoTask &A = tasks[f], &B = tasks[t];
+        const size_t row = (size_t)n_dims * 8;
+        const char *what = nullptr;
+        if (memcmp(mean + (size_t)A.stat * n_dims, mean + (size_t)B.stat * n_dims, row)) what = "mean";
+        else if (memcmp(std + (size_t)A.stat * n_dims, std + (size_t)B.stat * n_dims, row)) what = "scale";
+        else if (memcmp(&A.gamma, &B.gamma, 8)) what = "gamma";
+        if (what) return fail(PAA_ERR_ARG, "tasks %d and %d are one group and differ in their %s: a group shares one kernel matrix", f, (int)t, what);
+    }
+    return PAA_OK;
+}
+
+// smo_solve_batch from resident matrices under the budget cache_bytes: the groups g of the batch are packed in group order; cached
+// [n_groups] (may be null): 1 for a group whose tasks were solved from its matrix
+static int smo_solve_batch_cached(smo::SmoDev &m, SmoState &s, const std::vector<smo::SmoTask> &tasks, size_t rows, int iters_per_launch,
+                                  std::vector<int> &status, int *n_launches, const SmoGroups &g, int64_t cache_bytes, int32_t *cached) {
+    int rc;
+    if ((rc = smo_state_alloc(s, m, rows, tasks.size()))) return rc;
+    SvrCache c;
+    if ((rc = svr_cache_alloc(c, g.groups, m.n_dims, cache_bytes))) return rc;
+    const size_t nt = tasks.size(), ng = g.groups.size();
+    std::vector<long long> k_off(nt, 0);
+    std::vector<int> group_n(nt), members;
+    for (size_t t = 0; t < nt; ++t) {
+        const int gi = g.group_of[t];
+        if (c.chunk_of[gi] >= 0) k_off[t] = c.off[gi];
+        else members.push_back((int)t);
+        group_n[t] = g.groups[gi].n;
+    }
+    for (size_t gi = 0; cached && gi < ng; ++gi) cached[gi] = c.chunk_of[gi] >= 0;
+    DevBlock block;
+    BlockPart parts[] = {{g.groups.data(), ng * sizeof(smo::SmoTask), 8}, {k_off.data(), nt * 8, 8}, {g.rows.data(), g.rows.size() * 4, 4},
+                         {g.pos.data(), g.pos.size() * 4, 4}, {group_n.data(), nt * 4, 4}};
+    if (c.n_chunks && (rc = block_upload(block, parts, 5, "the SMO groups"))) return rc;
+    svrfit::SvrDev gm{};                              // the Gram pass's view: a group's row list is its task
+    gm.X = m.X;
+    gm.idx = (const int *)parts[2].dev;
+    gm.tasks = (const smo::SmoTask *)parts[0].dev;
+    gm.mean = m.mean;
+    gm.scale = m.scale;
+    gm.n_dims = m.n_dims;
+    gm.rbf = m.rbf;
+    const smo::SmoCacheDev cd{c.dev.K, (const long long *)parts[1].dev, (const int *)parts[4].dev, (const int *)parts[3].dev};
+    status.assign(nt, smo::kFresh);
+    long long launches = 0;
+    const auto plain = [&](int n_live, int n_max, int budget) {
+        LAUNCH_TRY("SMO", launch::smo_step(m, s.live, n_live, n_max, budget, cs()));
+        return (int)PAA_OK;
+    };
+    const auto from_matrix = [&](int n_live, int, int budget) {
+        LAUNCH_TRY("cached SMO", launch::smo_cached_step(m, cd, s.live, n_live, budget, cs()));
+        return (int)PAA_OK;
+    };
+    if (!members.empty() && (rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, plain)))
+        return rc;
+    std::vector<int> chunk_groups;
+    for (int ch = 0; ch < c.n_chunks; ++ch) {
+        if ((rc = svr_cache_fill(c, gm, g.groups, ch, chunk_groups))) return rc;
+        members.clear();
+        for (size_t t = 0; t < nt; ++t)
+            if (c.chunk_of[g.group_of[t]] == ch) members.push_back((int)t);
+        if ((rc = smo_relaunch_some(tasks, members, m.max_iter, iters_per_launch, s.live, m.status, status, launches, from_matrix))) return rc;
+    }
+    if (n_launches) *n_launches = (int)launches;
+    return PAA_OK;
+}
+
+// The layout alone, on the host, for tests: the groups of the task row lists task_off / task_idx under the ids `group` (null: every
+// task its own) and the chunk of every group under cache_bytes; see paa_hip.h
+extern "C" int paa_debug_smo_cache_layout(int n_tasks, const int64_t *task_off, const int32_t *task_idx, const int32_t *group,
+                                          int64_t cache_bytes, int32_t *n_groups, int32_t *group_of, int64_t *group_off,
+                                          int32_t *group_rows, int32_t *pos, int32_t *group_chunk) {
+    if (!task_off || !task_idx || !n_groups || !group_of || !group_off || !group_rows || !pos || !group_chunk) return fail(PAA_ERR_ARG, "null argument");
+    if (n_tasks < 1) return fail(PAA_ERR_ARG, "no tasks");
+    int rc;
+    if ((rc = sweep_offsets_check(task_off, n_tasks, "task"))) return rc;
+    if ((rc = svr_cache_args_check(cache_bytes))) return rc;
+    std::vector<smo::SmoTask> tasks(n_tasks);
+    for (int t = 0; t < n_tasks; ++t) {
+        const int64_t n = task_off[t + 1] - task_off[t];
+        if (n < 1 || n > 0x7fffffffLL) return fail(PAA_ERR_ARG, "task %d: %lld rows", t, (long long)n);
+        tasks[t] = {(long long)task_off[t], (int)n, t, 1.0, 1.0};
+    }
+    for (int64_t i = 0; i < task_off[n_tasks]; ++i)
+        if (task_idx[i] < 0) return fail(PAA_ERR_ARG, "row index %d", task_idx[i]);
+    SmoGroups g;
+    smo_groups_form(g, tasks, task_idx, group);
+    std::vector<int> chunk_of;
+    svr_cache_pack(g.groups, cache_bytes, chunk_of);
+    *n_groups = (int32_t)g.groups.size();
+    std::copy(g.group_of.begin(), g.group_of.end(), group_of);
+    std::copy(g.rows.begin(), g.rows.end(), group_rows);
+    std::copy(g.pos.begin(), g.pos.end(), pos);
+    std::copy(chunk_of.begin(), chunk_of.end(), group_chunk);
+    for (size_t gi = 0; gi < g.groups.size(); ++gi) group_off[gi] = g.groups[gi].off;
+    group_off[g.groups.size()] = (int64_t)g.rows.size();
+    return PAA_OK;
+}
+
 // the solver's view of an uploaded batch: the staged matrix, the uploaded tasks | mean | scale | idx | sign and the parameters
 static smo::SmoDev smo_dev(const double *X, const BlockPart &tasks, const BlockPart &mean, const BlockPart &scale, const BlockPart &idx,
                            const BlockPart &sign, int n_dims, int kernel_type, double eps, int max_iter) {
@@ -152,12 +304,14 @@ static smo::SvcFitDev svc_fit_dev(const Dev &m, const double *alpha_y, const Blo
 }
 
 // The solver alone (libsvm's Solver::Solve for C-SVC, svm.cpp, as svm_train_one runs it under SVC.fit): see paa_hip.h
-extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
-                                 const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
-                                 const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
-                                 int iters_per_launch, double *alpha_y, double *rho, int32_t *iterations, double *gap,
-                                 int32_t *status, int32_t *n_launches) {
-    if (!X || !task_off || !task_idx || !task_sign || !mean || !std || !C || !gamma || !alpha_y || !rho || !iterations || !gap || !status)
+// (use_cache false: paa_smo_tasks_f64; true: paa_smo_tasks_cached_f64 with its groups, budget and flags)
+static int smo_tasks_run(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off, const int32_t *task_idx,
+                         const int8_t *task_sign, const double *mean, const double *std, const double *C, const double *gamma,
+                         int kernel_type, double eps, int max_iter, int iters_per_launch, double *alpha_y, double *rho,
+                         int32_t *iterations, double *gap, int32_t *status, int32_t *n_launches, bool use_cache, const int32_t *group,
+                         int64_t cache_bytes, int32_t *cached) {
+    if (!X || !task_off || !task_idx || !task_sign || !mean || !std || !C || !gamma || !alpha_y || !rho || !iterations || !gap || !status ||
+        (use_cache && !cached))
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -173,6 +327,12 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     if ((rc = sweep_index_check(task_idx, rows, n_samples, "row"))) return rc;
     for (int64_t i = 0; i < rows; ++i)
         if (task_sign[i] != 1 && task_sign[i] != -1) return fail(PAA_ERR_ARG, "sign %d of row %lld: +1 or -1", (int)task_sign[i], (long long)i);
+    SmoGroups g;
+    if (use_cache) {
+        if ((rc = svr_cache_args_check(cache_bytes))) return rc;
+        smo_groups_form(g, tasks, task_idx, group);
+        if ((rc = smo_groups_check(g, tasks, mean, std, n_dims))) return rc;
+    }
     if ((rc = ensure_init())) return rc;
     const size_t sb = (size_t)n_tasks * n_dims * 8;
     DevBlock block;
@@ -184,7 +344,14 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[3], parts[4], n_dims, kernel_type, eps, max_iter);
     SmoState s;
     std::vector<int> st_words;
-    if ((rc = smo_solve_batch(m, s, tasks, (size_t)rows, iters_per_launch, st_words, n_launches))) return rc;
+    if (use_cache) {
+        std::vector<int32_t> group_cached(g.groups.size());
+        if ((rc = smo_solve_batch_cached(m, s, tasks, (size_t)rows, iters_per_launch, st_words, n_launches, g, cache_bytes, group_cached.data())))
+            return rc;
+        for (int t = 0; t < n_tasks; ++t) cached[t] = group_cached[g.group_of[t]];
+    } else if ((rc = smo_solve_batch(m, s, tasks, (size_t)rows, iters_per_launch, st_words, n_launches))) {
+        return rc;
+    }
     HIP_TRY(hipMemcpyAsync(alpha_y, m.alpha_y, (size_t)rows * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(rho, m.rho, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(gap, m.gap, (size_t)n_tasks * 8, hipMemcpyDeviceToHost, cs()));
@@ -192,6 +359,30 @@ extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims,
     HIP_TRY(hipStreamSynchronize(cs()));
     std::copy(st_words.begin(), st_words.end(), status);
     return PAA_OK;
+}
+extern "C" int paa_smo_tasks_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
+                                 const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
+                                 const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                 int iters_per_launch, double *alpha_y, double *rho, int32_t *iterations, double *gap,
+                                 int32_t *status, int32_t *n_launches) {
+    return smo_tasks_run(X, n_samples, n_dims, n_tasks, task_off, task_idx, task_sign, mean, std, C, gamma, kernel_type, eps, max_iter,
+                         iters_per_launch, alpha_y, rho, iterations, gap, status, n_launches, false, nullptr, 0, nullptr);
+}
+extern "C" int paa_smo_tasks_cached_f64(const double *X, int64_t n_samples, int n_dims, int n_tasks, const int64_t *task_off,
+                                        const int32_t *task_idx, const int8_t *task_sign, const double *mean, const double *std,
+                                        const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                        int iters_per_launch, double *alpha_y, double *rho, int32_t *iterations, double *gap,
+                                        int32_t *status, int32_t *n_launches, const int32_t *group, int64_t cache_bytes,
+                                        int32_t *cached) {
+    return smo_tasks_run(X, n_samples, n_dims, n_tasks, task_off, task_idx, task_sign, mean, std, C, gamma, kernel_type, eps, max_iter,
+                         iters_per_launch, alpha_y, rho, iterations, gap, status, n_launches, true, group, cache_bytes, cached);
+}
+
+// the ids that make every job of a sweep one group: a task's stat is its job
+static std::vector<int32_t> smo_job_ids(const std::vector<smo::SmoTask> &tasks) {
+    std::vector<int32_t> ids(tasks.size());
+    for (size_t t = 0; t < tasks.size(); ++t) ids[t] = tasks[t].stat;
+    return ids;
 }
 
 // The pair tasks of a split sweep: per job the classes present in its training list, ascending; per pair (a, b), a < b, one task
@@ -244,14 +435,16 @@ static int svc_pair_tasks(PairTasks &p, const int32_t *labels, int n_jobs, const
 
 // The SVM half of audioTrainTest.evaluate_classifier (audioTrainTest.py:631-700): every split a job, every pair of the classes
 // present in its training list a task; see paa_hip.h
-extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
-                                      const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
-                                      const int32_t *test_idx, const double *mean, const double *std, const double *C,
-                                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
-                                      int32_t *label_out, double *dec_out, int max_pairs, int n_tasks, int32_t *task_iterations,
-                                      int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches) {
+// (use_cache false: paa_svc_fit_splits_f64; true: paa_svc_fit_splits_cached_f64 with its budget and flags: a job is a group)
+static int svc_fit_splits_run(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs, const int64_t *train_off,
+                              const int32_t *train_idx, const int64_t *test_off, const int32_t *test_idx, const double *mean,
+                              const double *std, const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                              int iters_per_launch, int32_t *label_out, double *dec_out, int max_pairs, int n_tasks,
+                              int32_t *task_iterations, int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches, bool use_cache,
+                              int64_t cache_bytes, int32_t *job_cached) {
     // check
-    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !label_out)
+    if (!X || !labels || !train_off || !train_idx || !test_off || !test_idx || !mean || !std || !C || !gamma || !label_out ||
+        (use_cache && !job_cached))
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -269,6 +462,7 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
     if ((task_iterations || task_status || task_n_sv) && n_tasks != (int)p.tasks.size())
         return fail(PAA_ERR_ARG, "n_tasks = %d, the jobs make %d tasks", n_tasks, (int)p.tasks.size());
     if (!dec_out) max_pairs = p.pairs_max;
+    if (use_cache && (rc = svr_cache_args_check(cache_bytes))) return rc;
     if ((rc = ensure_init())) return rc;
     // upload
     const std::vector<knn::SplitBlock> blocks = sweep_blocks(test_off, n_jobs, smo::kQueriesPerBlock);
@@ -294,7 +488,13 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
     smo::SmoDev m = smo_dev(st.feats, parts[0], parts[1], parts[2], parts[5], parts[9], n_dims, kernel_type, eps, max_iter);
     SmoState s;
     std::vector<int> st_words;
-    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches))) return rc;
+    if (use_cache) {                                  // every job has a task, in job order: group j is job j
+        SmoGroups g;
+        smo_groups_form(g, p.tasks, p.idx.data(), smo_job_ids(p.tasks).data());
+        if ((rc = smo_solve_batch_cached(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches, g, cache_bytes, job_cached))) return rc;
+    } else if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, n_launches))) {
+        return rc;
+    }
     if (task_iterations) HIP_TRY(hipMemcpyAsync(task_iterations, m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
     if (task_n_sv) HIP_TRY(hipMemcpyAsync(task_n_sv, m.n_sv, nt * 4, hipMemcpyDeviceToHost, cs()));
     if (task_status) std::copy(st_words.begin(), st_words.end(), task_status);
@@ -309,6 +509,27 @@ extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_
     for (int j = 0; j < n_jobs; ++j)
         for (int64_t q = test_off[j]; q < test_off[j + 1]; ++q) label_out[q] = p.job_class[p.job_class_off[j] + label_out[q]];
     return PAA_OK;
+}
+extern "C" int paa_svc_fit_splits_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                      const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                      const int32_t *test_idx, const double *mean, const double *std, const double *C,
+                                      const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                      int32_t *label_out, double *dec_out, int max_pairs, int n_tasks, int32_t *task_iterations,
+                                      int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches) {
+    return svc_fit_splits_run(X, n_samples, n_dims, labels, n_jobs, train_off, train_idx, test_off, test_idx, mean, std, C, gamma,
+                              kernel_type, eps, max_iter, iters_per_launch, label_out, dec_out, max_pairs, n_tasks, task_iterations,
+                              task_status, task_n_sv, n_launches, false, 0, nullptr);
+}
+extern "C" int paa_svc_fit_splits_cached_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                             const int64_t *train_off, const int32_t *train_idx, const int64_t *test_off,
+                                             const int32_t *test_idx, const double *mean, const double *std, const double *C,
+                                             const double *gamma, int kernel_type, double eps, int max_iter, int iters_per_launch,
+                                             int32_t *label_out, double *dec_out, int max_pairs, int n_tasks,
+                                             int32_t *task_iterations, int32_t *task_status, int32_t *task_n_sv, int32_t *n_launches,
+                                             int64_t cache_bytes, int32_t *job_cached) {
+    return svc_fit_splits_run(X, n_samples, n_dims, labels, n_jobs, train_off, train_idx, test_off, test_idx, mean, std, C, gamma,
+                              kernel_type, eps, max_iter, iters_per_launch, label_out, dec_out, max_pairs, n_tasks, task_iterations,
+                              task_status, task_n_sv, n_launches, true, cache_bytes, job_cached);
 }
 
 // ---- probability=True's second half (svm.cpp: svm_binary_svc_probability, sigmoid_train) ----------------------------------------
@@ -447,18 +668,21 @@ static int platt_folds(PlattFolds &f, PairTasks &p, const int64_t *seed, std::ve
 }
 
 // What svc_fit_proba_resident gives back: host arrays, paa_svc_fit_proba_f64's outputs of the same names (cv_dec and n_launches may
-// be null)
+// be null) and paa_svc_fit_proba_cached_f64's job_cached (null: no resident matrices; else with the budget cache_bytes)
 struct ProbaFitOut {
     double *alpha_y, *rho, *prob_a, *prob_b;
     int32_t *n_sv, *task_iterations, *task_status, *sig_iterations, *sig_stop;
     double *cv_dec;
     int32_t *n_launches;
+    int32_t *job_cached = nullptr;
+    int64_t cache_bytes = 0;
 };
 
 // The fits of SVC(probability=True) over a sample matrix that is already RESIDENT (d_X [..][n_dims], with d_mean / d_scale
 // [n_jobs][n_dims] on the device too): p holds the pair tasks of the jobs (svc_pair_tasks) and receives the folds; the full fits
 // and the fold fits are one solver batch, svc_pairs_kernel scores every fold's held-out rows, platt_sigmoid_kernel fits every
-// pair.  Runs on the caller's stream (cs()) and has finished when it returns
+// pair.  With o.job_cached the full fits and the fold fits of a job are one group and read one resident matrix
+// (smo_solve_batch_cached).  Runs on the caller's stream (cs()) and has finished when it returns
 static int svc_fit_proba_resident(const double *d_X, const double *d_mean, const double *d_scale, int n_dims, PairTasks &p,
                                   const int64_t *seed, int kernel_type, double eps, int max_iter, int iters_per_launch,
                                   const ProbaFitOut &o) {
@@ -512,7 +736,14 @@ static int svc_fit_proba_resident(const double *d_X, const double *d_mean, const
     m.eps = eps;
     SmoState s;
     std::vector<int> st_words;
-    if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, o.n_launches))) return rc;
+    if (o.job_cached) {                               // every job has a pair task, in job order: group j is job j
+        SmoGroups g;
+        smo_groups_form(g, p.tasks, p.idx.data(), smo_job_ids(p.tasks).data());
+        if ((rc = smo_solve_batch_cached(m, s, p.tasks, rows, iters_per_launch, st_words, o.n_launches, g, o.cache_bytes, o.job_cached)))
+            return rc;
+    } else if ((rc = smo_solve_batch(m, s, p.tasks, rows, iters_per_launch, st_words, o.n_launches))) {
+        return rc;
+    }
     std::vector<int32_t> iters(nt);
     HIP_TRY(hipMemcpyAsync(iters.data(), m.iter, nt * 4, hipMemcpyDeviceToHost, cs()));
     HIP_TRY(hipMemcpyAsync(o.alpha_y, m.alpha_y, rows_full * 8, hipMemcpyDeviceToHost, cs()));      // the full fits come first
@@ -545,16 +776,16 @@ static int svc_fit_proba_resident(const double *d_X, const double *d_mean, const
 }
 
 // SVC(probability=True).fit for every job: the full fits, Platt's folds and the sigmoid fits; see paa_hip.h
-extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
-                                     const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
-                                     const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
-                                     int iters_per_launch, const int64_t *seed, int n_pairs, int64_t n_rows, double *alpha_y,
-                                     double *rho, double *prob_a, double *prob_b, int32_t *n_sv, int32_t *task_iterations,
-                                     int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
-                                     int32_t *n_launches) {
+// (use_cache false: paa_svc_fit_proba_f64; true: paa_svc_fit_proba_cached_f64 with its budget and flags: a job is a group)
+static int svc_fit_proba_run(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs, const int64_t *train_off,
+                             const int32_t *train_idx, const double *mean, const double *std, const double *C, const double *gamma,
+                             int kernel_type, double eps, int max_iter, int iters_per_launch, const int64_t *seed, int n_pairs,
+                             int64_t n_rows, double *alpha_y, double *rho, double *prob_a, double *prob_b, int32_t *n_sv,
+                             int32_t *task_iterations, int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
+                             int32_t *n_launches, bool use_cache, int64_t cache_bytes, int32_t *job_cached) {
     // check
     if (!X || !labels || !train_off || !train_idx || !mean || !std || !C || !gamma || !seed || !alpha_y || !rho || !prob_a || !prob_b ||
-        !n_sv || !task_iterations || !task_status || !sig_iterations || !sig_stop)
+        !n_sv || !task_iterations || !task_status || !sig_iterations || !sig_stop || (use_cache && !job_cached))
         return fail(PAA_ERR_ARG, "null argument");
     int rc;
     if ((rc = sweep_samples_check(n_samples))) return rc;
@@ -572,6 +803,7 @@ extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_d
     if ((rc = svc_pair_tasks(p, labels, n_jobs, train_off, train_idx, C, gamma, kernel_type))) return rc;
     if (n_pairs != (int)p.tasks.size() || n_rows != (int64_t)p.idx.size())
         return fail(PAA_ERR_ARG, "n_pairs = %d, n_rows = %lld: the jobs make %d pairs of %lld rows", n_pairs, (long long)n_rows, (int)p.tasks.size(), (long long)p.idx.size());
+    if (use_cache && (rc = svr_cache_args_check(cache_bytes))) return rc;
     if ((rc = ensure_init())) return rc;
     // X goes up once, through the lane's scratch, with every job's mean and scale behind it
     const size_t sb = (size_t)n_jobs * n_dims * 8;
@@ -580,7 +812,30 @@ extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_d
     if ((rc = block_upload(stats, parts, 2, "the probabilistic SVM jobs"))) return rc;
     Staged st;
     if ((rc = stage(st, X, n_dims, n_samples, nullptr, nullptr, 0, {}))) return rc;
-    const ProbaFitOut o{alpha_y, rho, prob_a, prob_b, n_sv, task_iterations, task_status, sig_iterations, sig_stop, cv_dec, n_launches};
+    const ProbaFitOut o{alpha_y, rho, prob_a, prob_b, n_sv, task_iterations, task_status, sig_iterations, sig_stop, cv_dec, n_launches,
+                        use_cache ? job_cached : nullptr, cache_bytes};
     return svc_fit_proba_resident(st.feats, (const double *)parts[0].dev, (const double *)parts[1].dev, n_dims, p, seed, kernel_type, eps,
                                   max_iter, iters_per_launch, o);
+}
+extern "C" int paa_svc_fit_proba_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                     const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
+                                     const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                     int iters_per_launch, const int64_t *seed, int n_pairs, int64_t n_rows, double *alpha_y,
+                                     double *rho, double *prob_a, double *prob_b, int32_t *n_sv, int32_t *task_iterations,
+                                     int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
+                                     int32_t *n_launches) {
+    return svc_fit_proba_run(X, n_samples, n_dims, labels, n_jobs, train_off, train_idx, mean, std, C, gamma, kernel_type, eps, max_iter,
+                             iters_per_launch, seed, n_pairs, n_rows, alpha_y, rho, prob_a, prob_b, n_sv, task_iterations, task_status,
+                             sig_iterations, sig_stop, cv_dec, n_launches, false, 0, nullptr);
+}
+extern "C" int paa_svc_fit_proba_cached_f64(const double *X, int64_t n_samples, int n_dims, const int32_t *labels, int n_jobs,
+                                            const int64_t *train_off, const int32_t *train_idx, const double *mean, const double *std,
+                                            const double *C, const double *gamma, int kernel_type, double eps, int max_iter,
+                                            int iters_per_launch, const int64_t *seed, int n_pairs, int64_t n_rows, double *alpha_y,
+                                            double *rho, double *prob_a, double *prob_b, int32_t *n_sv, int32_t *task_iterations,
+                                            int32_t *task_status, int32_t *sig_iterations, int32_t *sig_stop, double *cv_dec,
+                                            int32_t *n_launches, int64_t cache_bytes, int32_t *job_cached) {
+    return svc_fit_proba_run(X, n_samples, n_dims, labels, n_jobs, train_off, train_idx, mean, std, C, gamma, kernel_type, eps, max_iter,
+                             iters_per_launch, seed, n_pairs, n_rows, alpha_y, rho, prob_a, prob_b, n_sv, task_iterations, task_status,
+                             sig_iterations, sig_stop, cv_dec, n_launches, true, cache_bytes, job_cached);
 }

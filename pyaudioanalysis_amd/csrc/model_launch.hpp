@@ -99,6 +99,15 @@ struct SmoDev {
     int n_dims, rbf, max_iter;
     double eps;
 };
+// the resident kernel matrices of a chunk of groups (kernels_smocache.hpp).  A group is a set of tasks with one mean / scale / gamma; its
+// matrix K [N][N] runs over the group's distinct rows.  Per task: k_off, where its group's matrix begins in K (in doubles, 64-bit: a
+// chunk may pass 4 GiB), and group_n, that matrix's N; per row of every task (at the task's off): pos, its row of the matrix
+struct SmoCacheDev {
+    const double *K;
+    const long long *k_off;   // [n_tasks]; read for the tasks of the current chunk only
+    const int *group_n;       // [n_tasks]
+    const int *pos;
+};
 // the fitted tasks of a split sweep and its test lists (job j owns the tasks job_task[j] .. job_task[j + 1] - 1, the pairs
 // (a, b), a < b, of its job_k[j] present classes in row-major order): device pointers
 struct SvcFitDev {
@@ -182,6 +191,7 @@ struct SvrDev {
 // / 8), zero beyond n_dims), at z_off[task]; K [n][n], full, at k_off[task].  Offsets count doubles and are 64-bit: a chunk may pass 4 GiB
 constexpr int kGramTile = 32;             // svr_gram_kernel: rows of a tile, one per 8-lane group of the workgroup
 constexpr int kPitchLanes = 8;            // kv::kGroupLanes: a row of Z is padded to a multiple of it
+constexpr int kGramMaxRows = 65535 * kGramTile;   // rows of a matrix: svr_standardise_kernel's grid has a block row per tile of rows
 struct SvrCacheDev {
     double *Z, *K;
     const long long *z_off, *k_off;       // [n_tasks]; read for the tasks of the current chunk only
@@ -366,6 +376,8 @@ void knn_split_geometry(int out10[10]);
 // kernels_smo.hpp: at most `budget` SMO iterations of each of the n_live tasks d_live [n_live] of the batch m (one workgroup
 // each; n_max: the longest of them, which sizes the LDS); -2 when n_max or n_dims exceeds the limits
 int smo_step(const smo::SmoDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
+// kernels_smocache.hpp: smo_step over the resident matrices c (no LDS row: n_max is not bounded)
+int smo_cached_step(const smo::SmoDev &m, const smo::SmoCacheDev &c, const int *d_live, int n_live, int budget, hipStream_t stream);
 // ... and the one-against-one vote over fitted tasks: labels [Q] (position among the job's classes) and, when d_dec is not null,
 // decision values [Q][max_pairs]
 int svc_pairs(const smo::SvcFitDev &f, long long n_blocks, int *d_label, double *d_dec, hipStream_t stream);
@@ -387,8 +399,9 @@ int onset_proba(const onset::OnsetDev &m, int n_clips, long long n_frames, hipSt
 int onset_threshold(const onset::OnsetDev &m, int n_clips, hipStream_t stream);
 // kernels_svrfit.hpp: smo_step for a batch of epsilon-SVR tasks (the limits are the SMO solver's)
 int svr_smo_step(const svrfit::SvrDev &m, const int *d_live, int n_live, int n_max, int budget, hipStream_t stream);
-// kernels_svrcache.hpp: Z then K of the n_chunk tasks listed in d_chunk (n_max: the longest of them; d_tiles: every tile pair of every
-// one of them), and svr_smo_step over resident matrices
+// kernels_svrcache.hpp: Z then K of the n_chunk tasks listed in d_chunk (n_max: the longest of them, at most svrfit::kGramMaxRows; d_tiles:
+// every tile pair of every one of them), and svr_smo_step over resident matrices.  The C-SVC solver forms its groups' matrices with
+// the same call: a group's row list is a task here (lib_gramcache.hpp)
 int svr_gram(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_chunk, int n_chunk, int n_max,
              const svrfit::GramTile *d_tiles, long long n_tiles, hipStream_t stream);
 int svr_smo_cached_step(const svrfit::SvrDev &m, const svrfit::SvrCacheDev &c, const int *d_live, int n_live, int n_max, int budget,

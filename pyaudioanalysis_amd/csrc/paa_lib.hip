@@ -549,6 +549,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_svr.hpp"
 #include "lib_sweep.hpp"
 #include "lib_knn.hpp"
+#include "lib_gramcache.hpp"
 #include "lib_smo.hpp"
 #include "lib_onset.hpp"
 #include "lib_svrfit.hpp"
