@@ -936,6 +936,11 @@ int paa_debug_lane_peak(void);     /* most host-buffer calls in flight at once s
 int paa_debug_phase_cycles(uint64_t *out16);
 /* radix plan chosen for a window: returns number of passes, fills radices (capacity 32)      */
 int paa_debug_fft_plan(int window, int32_t *radices, int32_t *fft_len);
+/* HBM-pass path (csrc/kernels_big.hpp: what no other kernel takes) and the frame-list chunks of the workgroup-wide paths, host only:
+ * info8 = {complex points Nc, bins Nf, even, passes, scratch bytes per frame, frames per scratch chunk C of a plan whose longest
+ * clip has max_frames (>= 1) frames, scratch bytes of that plan, frames per chunk of the workgroup-wide paths' frame list}.  The
+ * numbers hold for the window whichever kernel a plan would choose for it                                                        */
+int paa_debug_big_plan(int window, int64_t max_frames, int64_t *info8);
 /* file name (inside PAA_COMM_MARKER_DIR / TMPDIR) of the one-process-per-GPU marker that `rank` of the job `unique_id`
  * drops for the selected device before RCCL is called (comm_rccl.hpp); needs a device                                */
 int paa_debug_comm_marker_name(const void *unique_id, int rank, char *out, int capacity);

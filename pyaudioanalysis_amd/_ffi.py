@@ -231,6 +231,7 @@ _SIGNATURES = {
     "paa_debug_wave_trace": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "paa_debug_lane_peak": (C.c_int, []),
     "paa_debug_fft_plan": (C.c_int, [C.c_int, c_i32p, c_i32p]),
+    "paa_debug_big_plan": (C.c_int, [C.c_int, C.c_int64, c_i64p]),
     "paa_debug_comm_marker_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "paa_debug_tri_plan": (C.c_int, [C.c_int, C.c_double, c_i32p, c_i32p, C.c_void_p, C.c_int]),
     "paa_debug_wg_plan": (C.c_int, [C.c_int, c_i32p, C.POINTER(C.c_uint16), C.c_int]),

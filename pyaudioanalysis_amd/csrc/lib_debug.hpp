@@ -306,6 +306,21 @@ extern "C" int paa_debug_fft_plan(int window, int32_t *radices, int32_t *fft_len
     for (int i = 0; i < n && i < 32; ++i) radices[i] = p.radix[i];
     return n;
 }
+// host side of the HBM-pass path (kernels_big.hpp, run_big) and of the frame-list chunks of the workgroup-wide paths
+// (wg_build_work) for a window, no device needed: info8 = {complex points Nc, bins Nf, even, passes, scratch bytes per frame,
+// frames per chunk C of a plan whose longest clip has max_frames frames, scratch bytes of such a plan, frames per chunk of
+// wg_build_work}.  Says nothing about which family takes the window.
+extern "C" int paa_debug_big_plan(int window, int64_t max_frames, int64_t *info8) {
+    if (window < 2 || max_frames < 1 || !info8) return fail(PAA_ERR_ARG, "bad argument");
+    FftPlan p;
+    build_fft_plan(window, p);
+    const long long Nc = p.len, Nf = window / 2;
+    const long long C = big_chunk_frames(Nc, Nf, max_frames);
+    info8[0] = Nc; info8[1] = Nf; info8[2] = p.even; info8[3] = (int64_t)p.radix.size();
+    info8[4] = (int64_t)big_frame_bytes(Nc, Nf); info8[5] = C; info8[6] = (int64_t)big_scratch_bytes(Nc, Nf, C);
+    info8[7] = wg_chunk_frames(Nf);
+    return PAA_OK;
+}
 
 // host side of the three-pass register-FFT kernels for a window (no device needed): the shape (R1, R2, R3, packed, plane row
 // pitch P, waves per workgroup, pass-3 lane jobs, LDS bytes) into shape8, and the whole table blob (LDS part followed by the

@@ -242,7 +242,7 @@ static int fam_wg_select(const FamilyCtx &c, FamilyChoice &f, std::vector<unsign
 static int wg_build_work(paa_plan *p, int wgs_r0) {
     // spectrum scratch: one row of Nf doubles per frame of a chunk, at most 1 GiB; a chunk that starts inside a clip
     // begins with that clip's previous frame once more (halo: only its spectrum row is wanted)
-    const long long cap = std::max<long long>(2, ((long long)1 << 30) / ((long long)p->P.Nf * 8));
+    const long long cap = wg_chunk_frames(p->P.Nf);
     long long first = 0;
     for (size_t c = 0; c < p->clips.size(); ++c)
         for (long long t = 0; t < p->clips[c].T; ++t) {

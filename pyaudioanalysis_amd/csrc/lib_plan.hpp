@@ -251,17 +251,31 @@ static int grow_big(paa_plan *p, size_t need, bool *fresh) {
     return PAA_OK;
 }
 
+// the scratch budget of the big-window paths and what follows from it (one formula each; paa_debug_big_plan reports them):
+// run_big keeps per frame two packed-complex sequences (Nc double2 each), one spectrum row (Nf doubles) and three time features;
+// a chunk is at most a launch's gridDim.y and never more than the longest clip
+constexpr long long kBigScratchBytes = 1LL << 30;
+static size_t big_frame_bytes(long long Nc, long long Nf) { return (size_t)Nc * 32 + (size_t)Nf * 8 + 24; }
+static long long big_chunk_frames(long long Nc, long long Nf, long long max_frames) {
+    const long long C = (long long)std::max<size_t>(1, (size_t)kBigScratchBytes / big_frame_bytes(Nc, Nf));
+    return std::min<long long>(std::min<long long>(C, 65535), std::max<long long>(max_frames, 1));
+}
+// (one spectrum row more than frames: row 0 of a chunk is the previous chunk's last)
+static size_t big_scratch_bytes(long long Nc, long long Nf, long long C) {
+    return (size_t)C * Nc * 32 + (size_t)(C + 1) * Nf * 8 + (size_t)C * 24 + 256;
+}
+// wg_build_work (lib_dispatch.hpp): frames of a chunk of the workgroup-wide paths, one spectrum row of Nf doubles each
+static long long wg_chunk_frames(long long Nf) { return std::max<long long>(2, kBigScratchBytes / (Nf * 8)); }
+
 // windows beyond the LDS envelope: chunked Stockham passes through HBM scratch (kernels_big.hpp)
 template <typename T>
 static int run_big(paa_plan *p, const void *d_packed, double *d_out) {
     const PlanDev &P = p->P;
     const long long Nc = P.Nc, Nf = P.Nf;
-    const size_t per_frame = (size_t)Nc * 32 + (size_t)Nf * 8 + 24;
     long long maxT = 0;
     for (auto &cd : p->clips) maxT = std::max<long long>(maxT, cd.T);
-    long long C = (long long)std::max<size_t>(1, ((size_t)1 << 30) / per_frame);
-    C = std::min<long long>(std::min<long long>(C, 65535), std::max<long long>(maxT, 1));
-    const size_t need = (size_t)C * Nc * 32 + (size_t)(C + 1) * Nf * 8 + (size_t)C * 24 + 256;
+    const long long C = big_chunk_frames(Nc, Nf, maxT);
+    const size_t need = big_scratch_bytes(Nc, Nf, C);
     bool fresh;
     { const int rc_g = grow_big(p, need, &fresh); if (rc_g) return rc_g; }
     double2 *bufA = reinterpret_cast<double2 *>(p->d_big);

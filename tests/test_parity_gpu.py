@@ -411,6 +411,10 @@ def test_big_window_kernel_choice(gpu_lib):
     assert name(16000, 65536, 32768) == "st_wg_split_fft"              # the largest table: 32 768 points = 8 x 4096
     assert name(16000, 80000, 40000) == "big_window_hbm_passes"        # 40 000 points: beyond the two-level twiddle table
     assert name(16000, 9001, 4500) == "big_window_hbm_passes"          # prime
+    # composite, beyond the Bluestein kernel's 5 462 samples, a prime factor above 13 (tests/test_big_kernel_gpu.py runs them)
+    for w in (5474, 5491, 5472, 5508, 5510, 5463):
+        assert name(16000, w, w // 2 + 3) == "big_window_hbm_passes", w
+    assert name(11025, 16537, 8000) == "big_window_hbm_passes"         # 1.5 s at 11.025 kHz: 23 x 719
 
 
 @pytest.mark.parametrize("kind,fs,window,step,seconds,deltas", [
