@@ -215,6 +215,57 @@ int paa_thumbnail_f64(const double *feats, int n_dims, int64_t n_vec, int m_filt
 int paa_dev_thumbnail_filter(const double *d_sim, int64_t n_vec, int m_filter, double band, double limit_1,
                              double limit_2, double *d_filt, int64_t *pos2);
 
+/* ---- music thumbnailing for a batch of clips ------------------------------------------------
+ * The stages above for n_clips RAGGED clips in one call: clip c has n_vec[c] vectors and R_c = n_vec[c] - m_filter + 1
+ * filtered rows; the Gram tiles, the diagonal blocks and the folds of all clips are one launch each, and the arg-max cell is
+ * grown on the device (audioSegmentation.py:1167-1182).  Clip c of any batch gets the bits of its own single call
+ * (paa_self_similarity_f64, paa_thumbnail_f64, paa_dev_thumbnail_filter), at any position, beside any other clips, under
+ * any chunk_bytes.  pos is [n_clips][2] (row, column of the arg-max), bounds [n_clips][4] = (i1, i2, j1, j2): the two
+ * thumbnail instances in vectors.  Refused before the device is touched: null buffers, n_clips < 1, n_dims < 1, negative
+ * or NaN limits, a clip with n_vec < m_filter (PAA_ERR_ARG) or past paa_dev_self_similarity's size bound
+ * (PAA_ERR_UNSUPPORTED); the message names the clip.
+ * Host buffers, packed clip after clip: feats holds the [n_dims][n_vec[c]] row-major matrices, sims / sim the
+ * n_vec[c] x n_vec[c] matrices, filt (may be null) the R_c x R_c matrices.  Whole clips are taken in chunks whose device
+ * scratch (Z, both matrices, candidates, lists) stays within chunk_bytes (0: 1 GiB, the bound for larger values too); a
+ * clip that alone needs more is a chunk of its own; no result depends on it.                         */
+int paa_self_similarity_batch_f64(const double *feats, int n_dims, int64_t n_clips, const int64_t *n_vec, int64_t chunk_bytes,
+                                  double *sim);
+int paa_thumbnail_filter_batch_f64(const double *sims, int64_t n_clips, const int64_t *n_vec, int m_filter, double band,
+                                   double limit_1, double limit_2, int64_t chunk_bytes, int64_t *pos, int64_t *bounds, double *filt);
+int paa_thumbnail_batch_f64(const double *feats, int n_dims, int64_t n_clips, const int64_t *n_vec, int m_filter, double band,
+                            double limit_1, double limit_2, int64_t chunk_bytes, int64_t *pos, int64_t *bounds, double *filt);
+/* end to end: packed samples (clip c = [offsets[c], offsets[c + 1]), ascending) -> ONE plan per chunk with 68 rows -> the
+ * stages on the plan's slabs in HBM; only pos, bounds and -- when filt is given -- the filtered matrices come back.  A
+ * clip shorter than one window is PAA_ERR_ARG as well.                                               */
+int paa_music_thumbnail_batch_i16(const int16_t *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                                  int m_filter, double band, double limit_1, double limit_2, int64_t chunk_bytes, int64_t *pos,
+                                  int64_t *bounds, double *filt);
+int paa_music_thumbnail_batch_f64(const double *packed, const int64_t *offsets, int64_t n_clips, double fs, int window, int step,
+                                  int m_filter, double band, double limit_1, double limit_2, int64_t chunk_bytes, int64_t *pos,
+                                  int64_t *bounds, double *filt);
+/* the same with one HOST pointer per clip in place of the packed array (offsets still give the lengths): clips that sit in
+ * memory one by one go to the device without being copied together first                              */
+int paa_music_thumbnail_batch_ptrs_i16(const int16_t *const *clips, const int64_t *offsets, int64_t n_clips, double fs, int window,
+                                       int step, int m_filter, double band, double limit_1, double limit_2, int64_t chunk_bytes,
+                                       int64_t *pos, int64_t *bounds, double *filt);
+int paa_music_thumbnail_batch_ptrs_f64(const double *const *clips, const int64_t *offsets, int64_t n_clips, double fs, int window,
+                                       int step, int m_filter, double band, double limit_1, double limit_2, int64_t chunk_bytes,
+                                       int64_t *pos, int64_t *bounds, double *filt);
+/* the two stages on device buffers; offsets (in doubles) and counts are HOST int64 arrays [n_clips].  Asynchronous on the
+ * library stream, no synchronisation inside: d_pos [n_clips][2] and d_bounds [n_clips][4] are DEVICE int64 arrays.  ld[c]
+ * is the row pitch of clip c's matrix, so the slabs of a batched plan can be passed as they are.     */
+int paa_dev_self_similarity_batch(const double *d_feats, int n_dims, int64_t n_clips, const int64_t *feat_off,
+                                  const int64_t *n_vec, const int64_t *ld, double *d_sim, const int64_t *sim_off);
+int paa_dev_thumbnail_filter_batch(const double *d_sim, const int64_t *sim_off, const int64_t *n_vec, int64_t n_clips,
+                                   int m_filter, double band, double limit_1, double limit_2, double *d_filt,
+                                   const int64_t *filt_off, int64_t *d_pos, int64_t *d_bounds);
+/* host only (tests): the layout a batch of these clips gets.  counts [3] = Gram tiles, diagonal blocks, fill row blocks;
+ * tiles / blocks / rows [cap][3] = (clip, ti, tj) / (clip, bx, by) / (clip, 0, by); clip_off [n_clips][3] = the clip's
+ * offsets into the Z, norm and candidate scratch                                                     */
+int paa_debug_thumbnail_batch_layout(const int64_t *n_vec, int64_t n_clips, int n_dims, int m_filter, int64_t *counts,
+                                     int32_t *tiles, int64_t tiles_cap, int32_t *blocks, int64_t blocks_cap, int32_t *rows,
+                                     int64_t rows_cap, int64_t *clip_off);
+
 /* ---- silence_removal's per-frame SVM loop (audioSegmentation.py:744-748) ------------------------------
  * P(class index 1) of a TRAINED binary probabilistic scikit-learn SVC for every column of feats [n_dims][n_frames]
  * (host, feature-major like the short-term matrix): (x - mean) / scale (:746), decision value from the support vectors

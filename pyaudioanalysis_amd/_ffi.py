@@ -21,6 +21,8 @@ c_f64p = C.POINTER(C.c_double)
 c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
 c_u8p = C.POINTER(C.c_uint8)
+# the thumbnail batch entry points, after the clips: m_filter, band, limit_1, limit_2, chunk_bytes, pos, bounds, filt (may be null)
+_THUMB_BATCH_TAIL = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int64, c_i64p, c_i64p, c_f64p]
 # paa_silence_batch_*, after the samples: offsets .. row_cap_off, then the outputs in the order of paa_hip.h
 _SILENCE_BATCH_ARGS = [c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int, c_i32p, c_f64p, c_i64p, C.c_int64, c_i64p, c_u8p, c_u8p, c_u8p,
                        c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p,
@@ -98,6 +100,18 @@ _SIGNATURES = {
                                     c_i64p]),
     "paa_dev_thumbnail_filter": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double,
                                            C.c_void_p, c_i64p]),
+    "paa_self_similarity_batch_f64": (C.c_int, [c_f64p, C.c_int, C.c_int64, c_i64p, C.c_int64, c_f64p]),
+    "paa_thumbnail_filter_batch_f64": (C.c_int, [c_f64p, C.c_int64, c_i64p] + _THUMB_BATCH_TAIL),
+    "paa_thumbnail_batch_f64": (C.c_int, [c_f64p, C.c_int, C.c_int64, c_i64p] + _THUMB_BATCH_TAIL),
+    "paa_music_thumbnail_batch_i16": (C.c_int, [c_i16p, c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int] + _THUMB_BATCH_TAIL),
+    "paa_music_thumbnail_batch_f64": (C.c_int, [c_f64p, c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int] + _THUMB_BATCH_TAIL),
+    "paa_music_thumbnail_batch_ptrs_i16": (C.c_int, [C.POINTER(C.c_void_p), c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int] + _THUMB_BATCH_TAIL),
+    "paa_music_thumbnail_batch_ptrs_f64": (C.c_int, [C.POINTER(C.c_void_p), c_i64p, C.c_int64, C.c_double, C.c_int, C.c_int] + _THUMB_BATCH_TAIL),
+    "paa_dev_self_similarity_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_i64p, c_i64p, c_i64p, C.c_void_p, c_i64p]),
+    "paa_dev_thumbnail_filter_batch": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                 C.c_void_p, c_i64p, C.c_void_p, C.c_void_p]),
+    "paa_debug_thumbnail_batch_layout": (C.c_int, [c_i64p, C.c_int64, C.c_int, C.c_int, c_i64p, c_i32p, C.c_int64, c_i32p, C.c_int64,
+                                                   c_i32p, C.c_int64, c_i64p]),
     "paa_svm_binary_proba_f64": (C.c_int, [c_f64p, C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int, C.c_double,
                                            C.c_double, C.c_double, C.c_double, c_f64p]),
     "paa_svc_create": (C.c_int, [c_f64p, C.c_int, C.c_int, c_i32p, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int,

@@ -10,6 +10,9 @@ Same names, argument meaning and return values as the reference.  Everything num
 (standardisation, FP64 matrix-core Gram matrix, diagonal filter, masks, arg-max; short-term features and the per-frame
 SVM probability of silence_removal); there is no CPU fallback for those.  `music_thumbnailing` keeps the short-term
 features and the similarity matrix in HBM: only the filtered matrix it returns comes back to the host.
+music_thumbnailing_batch / music_thumbnailing_files do that for a collection of clips in one call: one batched plan, the stages of
+all clips one launch each, the arg-max cell grown on the device, 48 bytes per clip back (self_similarity_batch,
+thumbnail_filter_batch and thumbnail_batch give the stages alone); clip i equals its own music_thumbnailing call bit for bit.
 `silence_removal` trains its two-class SVM exactly where the reference does -- with scikit-learn (:739,
 audioTrainTest.train_svm) -- and replaces the per-frame predict_proba loop (:744-748) by one kernel over all frames
 (svm_onset_probability); with svm_fit="device" the SVM is trained on the GPU instead (audioTrainTest.train_svm_device: the full
@@ -97,6 +100,228 @@ def music_thumbnailing(signal, sampling_rate, short_window=1.0, short_step=0.5, 
         plan.destroy()
     i1, i2, j1, j2 = _grow_thumbnail(filtered, pos[0], pos[1], m_filter)
     return short_step * i1, short_step * i2, short_step * j1, short_step * j2, filtered
+
+
+# ---------------------------------------------------------------------------------------------------------
+# music thumbnailing for a batch of clips (the stages of :40-55 and :1141-1182 as one launch each over all clips)
+# ---------------------------------------------------------------------------------------------------------
+def _feature_mats(mats):
+    """list of (n_dims x T_c) matrices of one n_dims -> (contiguous float64 matrices, n_vec int64 [n], n_dims)"""
+    mats = [np.ascontiguousarray(np.asarray(f, dtype=np.float64)) for f in mats]
+    for c, f in enumerate(mats):
+        if f.ndim != 2 or f.shape[0] < 1 or f.shape[1] < 1:
+            raise ValueError("clip %d: feature_vectors must be a non-empty (nDims x nVectors) matrix" % c)
+        if f.shape[0] != mats[0].shape[0]:
+            raise ValueError("clip %d: %d feature rows, clip 0 has %d" % (c, f.shape[0], mats[0].shape[0]))
+    return mats, np.array([f.shape[1] for f in mats], dtype=np.int64), (mats[0].shape[0] if mats else 0)
+
+
+def _pack(arrays):
+    return np.concatenate([a.reshape(-1) for a in arrays]) if len(arrays) > 1 else arrays[0].reshape(-1)
+
+
+def _check_filter_length(n_vec, m_filter):
+    m_filter = int(m_filter)
+    if m_filter < 1:
+        raise ValueError("thumbnail filter length %d" % m_filter)
+    for c, t in enumerate(n_vec):
+        if t < m_filter:
+            raise ValueError("clip %d: %d feature vectors are fewer than the thumbnail filter length %d" % (c, t, m_filter))
+    return m_filter
+
+
+def _split_squares(flat, sizes):
+    out, at = [], 0
+    for r in sizes:
+        out.append(flat[at:at + r * r].reshape(r, r))
+        at += r * r
+    return out
+
+
+def _thumb_outputs(n_vec, m_filter, want_filtered):
+    """(pos [n][2], bounds [n][4], filt or None, R [n]) of one thumbnail batch call"""
+    R = [int(t) - m_filter + 1 for t in n_vec]
+    filt = _ffi.result_array((sum(r * r for r in R),)) if want_filtered else None
+    return np.zeros((len(R), 2), dtype=np.int64), np.zeros((len(R), 4), dtype=np.int64), filt, R
+
+
+def _thumb_records(pos, bounds, filt, R):
+    """per clip ((row, column), (i1, i2, j1, j2), filtered or None)"""
+    mats = _split_squares(filt, R) if filt is not None else [None] * len(R)
+    return [(tuple(int(v) for v in pos[c]), tuple(int(v) for v in bounds[c]), mats[c]) for c in range(len(R))]
+
+
+def self_similarity_batch(mats, *, chunk_bytes=None):
+    """self_similarity_matrix for a list of (nDims x T_c) matrices of one nDims in one library call: the Gram tiles of all
+    clips are one launch.  Returns the T_c x T_c matrices; clip i equals self_similarity_matrix(mats[i]) bit for bit."""
+    mats, n_vec, n_dims = _feature_mats(mats)
+    if not mats:
+        return []
+    sim = _ffi.result_array((int((n_vec * n_vec).sum()),))
+    _ffi.check(_ffi.lib().paa_self_similarity_batch_f64(_ffi.as_f64p(_pack(mats)), n_dims, len(mats), _ffi.as_i64p(n_vec),
+                                                        int(chunk_bytes or 0), _ffi.as_f64p(sim)))
+    return _split_squares(sim, [int(t) for t in n_vec])
+
+
+def thumbnail_filter_batch(sims, m_filter, band, limit_1=0, limit_2=1, *, return_filtered=True, chunk_bytes=None):
+    """The matrix part of music_thumbnailing after the similarity matrix, for a list of symmetric T_c x T_c matrices: diagonal
+    filter of m_filter cells, masks (band is the reference's 5.0 / short_step), arg-max and the grown thumbnail.  Returns per
+    clip (filtered, (row, column), (i1, i2, j1, j2)), without `filtered` when return_filtered is False."""
+    sims = [np.ascontiguousarray(np.asarray(s, dtype=np.float64)) for s in sims]
+    for c, s in enumerate(sims):
+        if s.ndim != 2 or s.shape[0] != s.shape[1] or s.shape[0] < 1:
+            raise ValueError("clip %d: a similarity matrix is square and not empty (shape %s)" % (c, s.shape))
+    if not sims:
+        return []
+    n_vec = np.array([s.shape[0] for s in sims], dtype=np.int64)
+    m_filter = _check_filter_length(n_vec, m_filter)
+    pos, bounds, filt, R = _thumb_outputs(n_vec, m_filter, return_filtered)
+    _ffi.check(_ffi.lib().paa_thumbnail_filter_batch_f64(_ffi.as_f64p(_pack(sims)), len(sims), _ffi.as_i64p(n_vec), m_filter, float(band),
+                                                         float(limit_1), float(limit_2), int(chunk_bytes or 0), _ffi.as_i64p(pos),
+                                                         _ffi.as_i64p(bounds), _ffi.as_f64p(filt) if filt is not None else None))
+    return [(f, p, b) if return_filtered else (p, b) for p, b, f in _thumb_records(pos, bounds, filt, R)]
+
+
+def thumbnail_batch(mats, m_filter, band, limit_1=0, limit_2=1, *, return_filtered=True, chunk_bytes=None):
+    """self_similarity_batch and thumbnail_filter_batch in one call, the similarity matrices staying in device memory: per clip
+    (filtered, (row, column), (i1, i2, j1, j2)) from its (nDims x T_c) feature matrix."""
+    mats, n_vec, n_dims = _feature_mats(mats)
+    if not mats:
+        return []
+    m_filter = _check_filter_length(n_vec, m_filter)
+    pos, bounds, filt, R = _thumb_outputs(n_vec, m_filter, return_filtered)
+    _ffi.check(_ffi.lib().paa_thumbnail_batch_f64(_ffi.as_f64p(_pack(mats)), n_dims, len(mats), _ffi.as_i64p(n_vec), m_filter, float(band),
+                                                  float(limit_1), float(limit_2), int(chunk_bytes or 0), _ffi.as_i64p(pos),
+                                                  _ffi.as_i64p(bounds), _ffi.as_f64p(filt) if filt is not None else None))
+    return [(f, p, b) if return_filtered else (p, b) for p, b, f in _thumb_records(pos, bounds, filt, R)]
+
+
+def _thumb_plan(lengths, sampling_rate, short_window, short_step, thumb_size):
+    """The argument half of music_thumbnailing_batch, without the device: (window, step, m_filter, frames) or the ValueError
+    of the first clip that cannot be served."""
+    window, step = int(sampling_rate * short_window), int(sampling_rate * short_step)     # int() of :563-564
+    if window < 2 or step < 1:
+        raise ValueError("short_window = %r, short_step = %r at %r Hz: a window of %d and a step of %d samples"
+                         % (short_window, short_step, sampling_rate, window, step))
+    m_filter = int(round(thumb_size / short_step))                           # :1142
+    if m_filter < 1:
+        raise ValueError("thumb_size = %r, short_step = %r: a thumbnail filter of %d cells" % (thumb_size, short_step, m_filter))
+    frames = [(int(m) - window) // step + 1 if int(m) >= window else 0 for m in lengths]
+    for c, t in enumerate(frames):
+        if t < 1:
+            raise ValueError("clip %d: need at least one array to concatenate (%d samples, a window of %d)"
+                             % (c, lengths[c], window))                       # ShortTermFeatures.py:684
+        if t < m_filter:
+            raise ValueError("clip %d: %d feature vectors are fewer than the thumbnail filter length %d (the reference's "
+                             "convolve2d silently swaps its operands in that case)" % (c, t, m_filter))
+    return window, step, m_filter, np.array(frames, dtype=np.int64)
+
+
+def _thumb_group(clips, as_i16, sampling_rate, window, step, frames, m_filter, band, limit_1, limit_2, want_filtered, chunk_bytes):
+    """The call of paa_music_thumbnail_batch_* for clips of one sample type: per clip ((row, column), (i1, i2, j1, j2), filtered)"""
+    n = len(clips)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([c.shape[0] for c in clips], out=offsets[1:])
+    ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])               # one pointer per clip: no packing copy on the host
+    pos, bounds, filt, R = _thumb_outputs(frames, m_filter, want_filtered)
+    lib = _ffi.lib()
+    fn = lib.paa_music_thumbnail_batch_ptrs_i16 if as_i16 else lib.paa_music_thumbnail_batch_ptrs_f64
+    _ffi.check(fn(ptrs, _ffi.as_i64p(offsets), n, float(sampling_rate), window, step,
+                  m_filter, float(band), float(limit_1), float(limit_2), int(chunk_bytes or 0), _ffi.as_i64p(pos), _ffi.as_i64p(bounds),
+                  _ffi.as_f64p(filt) if filt is not None else None))
+    return _thumb_records(pos, bounds, filt, R)
+
+
+def _thumb_batch(monos, sampling_rate, short_window, short_step, thumb_size, limit_1, limit_2, want_filtered, chunk_bytes):
+    """music_thumbnailing_batch on mono clips whose arguments have passed: the int16 clips and the others are one library call
+    each, so that every clip takes the sample path of its own single call.  Records in clip order."""
+    window, step, m_filter, frames = _thumb_plan([m.shape[0] for m in monos], sampling_rate, short_window, short_step, thumb_size)
+    out = [None] * len(monos)
+    for as_i16 in (True, False):
+        ids = [c for c, m in enumerate(monos) if (m.dtype == np.int16) == as_i16]
+        if not ids:
+            continue
+        clips = [np.ascontiguousarray(monos[c] if as_i16 else np.double(monos[c])) for c in ids]
+        try:
+            records = _thumb_group(clips, as_i16, sampling_rate, window, step, frames[ids], m_filter, 5.0 / short_step, limit_1, limit_2,
+                                   want_filtered, chunk_bytes)
+        except (ValueError, NotImplementedError) as exc:
+            raise _as_path_index(exc, ids)
+        for c, r in zip(ids, records):
+            out[c] = r
+    return out
+
+
+def _thumb_result(record, short_step, return_filtered, return_details):
+    pos, (i1, i2, j1, j2), filtered = record
+    res = (short_step * i1, short_step * i2, short_step * j1, short_step * j2)
+    if return_filtered:
+        res += (filtered,)
+    if return_details:
+        res += (pos,)
+    return res
+
+
+def _mono_clips(signals):
+    monos = [np.asarray(audioBasicIO.stereo_to_mono(s)) for s in signals]
+    for c, m in enumerate(monos):
+        if m.ndim != 1:
+            raise ValueError("clip %d: a signal of %d dimensions (mono, or two channels)" % (c, m.ndim))
+    return monos
+
+
+def music_thumbnailing_batch(signals, sampling_rate, short_window=1.0, short_step=0.5, thumb_size=10.0, limit_1=0, limit_2=1, *,
+                             return_filtered=False, return_details=False, chunk_bytes=None):
+    """music_thumbnailing for a list of clips of ONE sampling rate, on the GPU end to end: the short-term matrices of one batched
+    plan stay in device memory; standardisation, the Gram tiles of all clips on the FP64 matrix cores, the diagonal filter,
+    the folds and the growth of the arg-max cell are one launch each over the whole batch, and 48 bytes per clip come back.
+    Returns one (A1, A2, B1, B2) per clip in seconds, exactly what music_thumbnailing returns for that clip alone;
+    return_filtered=True appends the filtered matrix (then it is copied back as well), return_details=True the (row, column)
+    of the arg-max.  Each clip goes through audioBasicIO.stereo_to_mono; int16 clips travel as int16, the others through
+    np.double (two library calls when both kinds are present).  chunk_bytes: a bound below the library's 1 GiB for the device
+    scratch of one chunk of clips (tests); no result depends on it.  An empty list returns [].
+
+    ValueError names the clip and comes before any device work: a clip shorter than one window (the reference's "need at
+    least one array to concatenate"), or with fewer vectors than round(thumb_size / short_step).  NotImplementedError for a
+    clip past self_similarity_matrix's size bound."""
+    signals = list(signals)
+    if not signals:
+        return []
+    records = _thumb_batch(_mono_clips(signals), sampling_rate, short_window, short_step, thumb_size, limit_1, limit_2, return_filtered,
+                           chunk_bytes)
+    return [_thumb_result(r, short_step, return_filtered, return_details) for r in records]
+
+
+def music_thumbnailing_files(paths, short_window=1.0, short_step=0.5, thumb_size=10.0, limit_1=0, limit_2=1, *,
+                             return_filtered=False, return_details=False):
+    """music_thumbnailing_batch over audio files: they are read and grouped by sampling rate, one device batch per rate, and
+    the results come back in path order.  A file that cannot be read raises ValueError naming its index; the arguments of
+    EVERY file are checked before the device is touched."""
+    paths = list(paths)
+    groups = {}
+    for i, path in enumerate(paths):
+        fs, sig = audioBasicIO.read_audio_file(path)
+        if fs <= 0:
+            raise ValueError("file %d (%s) cannot be read" % (i, path))
+        groups.setdefault(fs, []).append((i, sig))
+    monos = {}
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        try:
+            monos[fs] = _mono_clips([s for _, s in members])
+            _thumb_plan([m.shape[0] for m in monos[fs]], fs, short_window, short_step, thumb_size)
+        except ValueError as exc:
+            raise _as_path_index(exc, ids)
+    out = [None] * len(paths)
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        try:
+            records = _thumb_batch(monos[fs], fs, short_window, short_step, thumb_size, limit_1, limit_2, return_filtered, None)
+        except (ValueError, NotImplementedError) as exc:
+            raise _as_path_index(exc, ids)
+        for i, r in zip(ids, records):
+            out[i] = _thumb_result(r, short_step, return_filtered, return_details)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------

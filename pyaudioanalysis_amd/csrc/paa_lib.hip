@@ -33,6 +33,7 @@
 #include "kernels_wgr.hpp"
 #include "kernels_wgs.hpp"
 #include "kernels_sim.hpp"
+#include "kernels_simbatch.hpp"
 #include "kernels_svm.hpp"
 #include "tables.hpp"
 
@@ -165,6 +166,7 @@ static long long g_prof_n = 0;
 static int comm_wait_buffer_free(const void *d_out);
 static void comm_forget_buffer(const void *ptr);
 static int comm_sync();
+static void simb_release();      // (lib_similarity_batch.hpp)
 
 // HIP's current device is a per-thread setting (device 0 until hipSetDevice): a host thread other than the one that
 // called paa_init(d) would otherwise allocate on device 0 while the library's streams and tables live on device d.
@@ -404,6 +406,7 @@ extern "C" void paa_shutdown(void) {
     for (auto &kv : g_tables) free_tables(*kv.second);
     g_tables.clear();
     pool_release_all();
+    simb_release();
     for (GlobalScratch *s = g_global_scratch; s; s = s->next) scratch_release(*s);
     for (Lane &ln : g_lanes) {
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); ln.stream = nullptr; }
@@ -552,6 +555,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_gramcache.hpp"
 #include "lib_smo.hpp"
 #include "lib_onset.hpp"
+#include "lib_similarity_batch.hpp"
 #include "lib_svrfit.hpp"
 #include "lib_forest.hpp"
 #include "lib_treefit.hpp"
