@@ -1051,6 +1051,28 @@ int paa_debug_run_plan_shrink(const int64_t *frames, int64_t n_clips, int quantu
  * after clip to lens[capacity]; returns their number, 0 when the equal runs of `run_cap` stay                              */
 int64_t paa_debug_balanced_runs(const int64_t *frames, int64_t n_clips, int run_cap, int quantum, int shrink, int wg_runs,
                                 int num_cu, int min_run, int32_t *lens, int64_t capacity);
+/* ---- placement of the short runs by XCD (csrc/lib_xcd_order.hpp).  The workgroups of a label (workgroup mod 8) share an XCD;
+ * an order is the eight labels, the slowest XCD's first.  PAA_XCD_ORDER=0 in the environment switches probes and orders off.
+ * The same cut with the short runs dealt to the labels in `order8` (null: paa_debug_balanced_runs exactly)                  */
+int64_t paa_debug_balanced_runs_ordered(const int64_t *frames, int64_t n_clips, int run_cap, int quantum, int shrink, int wg_runs,
+                                        int num_cu, int min_run, const int32_t *order8, int32_t *lens, int64_t capacity);
+/* puts an order in force on the device until it is cleared (order8 = null: the order the probes had put in force before, or
+ * none, is back); probes do not move a forced order.  Plans of paa_plan_create re-cut their tile list at their next execute,
+ * plans created later are cut under it                                                                                       */
+int paa_debug_xcd_force_order(const int32_t *order8);
+/* the calibration of the device: order8 = the order in force (identity when none), tau8 = averaged 100 MHz ticks per iteration of
+ * every label (zeros before the first probe), epoch = number of changes of the order in force.  Returns a bit mask: 1 switched
+ * on (environment), 2 the device maps labels to XCDs differently (calibration switched itself off), 4 the order is a forced
+ * one, 8 an order is in force                                                                                              */
+int paa_debug_xcd_state(int32_t *order8, double *tau8, uint64_t *epoch);
+/* the run lengths of a balanced plan of paa_plan_create as its next launch would use them (0: not such a plan) and, in info8,
+ * {run cap, quantum, shrink, runs per workgroup, shortest run, CUs, 0, 0}: the arguments of paa_debug_balanced_runs for it;
+ * epoch = the epoch its list was cut under (0: no order)                                                                      */
+int64_t paa_debug_plan_runs(const paa_plan_t *plan, int32_t *lens, int64_t capacity, int32_t *info8, uint64_t *epoch);
+/* one execute of such a plan as a probe launch, waited for: record = two words per run (100 MHz counter at the entry of the run's
+ * wave; at its exit, with the XCC id the wave ran on in bits 60 .. 63).  The record is checked (a label on more than one XCD
+ * switches the calibration off) but not averaged.  Returns the number of runs, 0 when the plan has no probe                   */
+int64_t paa_debug_plan_probe(paa_plan_t *plan, const void *d_packed, double *d_out, uint64_t *record, int64_t capacity_runs);
 
 #ifdef __cplusplus
 }

@@ -261,6 +261,12 @@ _SIGNATURES = {
                                      c_i64p, c_i32p]),
     "paa_debug_balanced_runs": (C.c_int64, [c_i64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
                                             C.c_int64]),
+    "paa_debug_balanced_runs_ordered": (C.c_int64, [c_i64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i32p,
+                                                    c_i32p, C.c_int64]),
+    "paa_debug_xcd_force_order": (C.c_int, [c_i32p]),
+    "paa_debug_xcd_state": (C.c_int, [c_i32p, c_f64p, C.POINTER(C.c_uint64)]),
+    "paa_debug_plan_runs": (C.c_int64, [C.c_void_p, c_i32p, C.c_int64, c_i32p, C.POINTER(C.c_uint64)]),
+    "paa_debug_plan_probe": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int64]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -10,7 +10,9 @@ namespace launch {
 template <int S, int DELTAS, int FIXED, int NW>
 static int fast_one(const FastLaunch &fl, const TileArgs &a) {
     static LdsAttrCache attr;
-    return tile_launch(&f800::st_fast_800_kernel<S, DELTAS, FIXED, NW>, attr, NW, fl.lds, fl.layout, a);
+    f800::TabLayout layout = fl.layout;
+    layout.probe = FIXED ? a.probe : nullptr;          // a calibration launch (lib_xcd_order.hpp), else null
+    return tile_launch(&f800::st_fast_800_kernel<S, DELTAS, FIXED, NW>, attr, NW, fl.lds, layout, a);
 }
 template <int S, int NW>
 static int fast_step(const FastLaunch &fl, const TileArgs &a) {

@@ -30,6 +30,7 @@ struct TileArgs {
     long long n_tiles;
     double *d_out;
     hipStream_t stream;
+    unsigned long long *probe = nullptr;      // fast family, calibration launches: two words per tile (kernels_fast.hpp: TabLayout::probe)
 };
 // the launch of every one-wave family: `waves` tiles per workgroup, one wave each.  `attr` is the cache of THIS kernel
 // instance (a static of the caller, which is a template over the instance); the attribute is raised to exactly `lds`

@@ -48,6 +48,10 @@ struct TabLayout {
     int fixed_lists;                                       // 1: lengths are exactly 8/16/16/8 without clamping
     int pace_mode;                                         // NW = 8: 0 none, 1 the two waves of a SIMD keep equal progress
     int total;                                             // bytes, multiple of 16
+    // calibration launches only (lib_xcd_order.hpp), else null: two words per tile, lane 0 of the tile's wave leaves the 100 MHz
+    // real-time counter at wave entry in [2 tile] and at wave exit, with the XCC id in bits 60 .. 63, in [2 tile + 1].  Read by the
+    // FIXED = 1 instances only (the run-time-list ones have no scalar register to spare for it: they never probe, launch::fast)
+    unsigned long long *probe;
 };
 }  // namespace f800
 struct FastLaunch {
@@ -576,6 +580,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     const int lane = threadIdx.x & 63;
     int g = lane >> 4, i = lane & 15;          // NW = 8 makes them opaque per iteration (see the loop head)
     PAA_T0()
+    if (FIXED && L.probe && lane == 0) L.probe[2 * tile_id] = __builtin_amdgcn_s_memrealtime();
     const Tile tl = tiles[tile_id];
     const ClipDev c = clips[tl.clip];
     const int16_t *xc = sig + c.sample_off;
@@ -1147,6 +1152,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void st_fast_800_kernel(PlanDev P,
     }
     if (NW == 8 && lane == 0) pace[8 + wave] = 0x7fffffff;
     PAA_TEND()
+    if (FIXED && L.probe && lane == 0)          // (HW_REG_XCC_ID[3:0])
+        L.probe[2 * tile_id + 1] = __builtin_amdgcn_s_memrealtime() | ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u) << 60);
 }
 
 }  // namespace f800
@@ -1160,6 +1167,7 @@ inline int fast_select(int window, int step, int sample_kind, double fs, FastTab
     int wave_bytes = (step == 400) ? (nw == 8 ? f800::Geo<400, 8>::WAVE_BYTES : f800::Geo<400, 4>::WAVE_BYTES)
                                    : (nw == 8 ? f800::Geo<800, 8>::WAVE_BYTES : f800::Geo<800, 4>::WAVE_BYTES);
     f800::TabLayout &L = fl.layout;
+    L.probe = nullptr;          // (set per launch: launch::fast)
     auto up4 = [](int n) { return std::max(8, (n + 7) / 8 * 8); };      // lists are unrolled by 8 on the device
     int c0 = 0, c1 = 0, c2 = 0, cc = 0;
     for (int m = 0; m < 16; ++m) c0 = std::max(c0, (int)mel.cnt[m]);

@@ -152,14 +152,17 @@ extern "C" int paa_debug_lane_jobs(const int32_t *first, const int32_t *wfirst, 
 }
 // the run lengths paa_plan_create gives a plan that fills less than one round of a one-workgroup-per-CU kernel (lib_plan.hpp:
 // balanced_runs).  Returns the number of runs written to `lens` (clip after clip), 0 when the equal runs stay, < 0 on error.
-extern "C" int64_t paa_debug_balanced_runs(const int64_t *frames, int64_t n_clips, int run_cap, int quantum, int shrink, int wg_runs,
-                                           int num_cu, int min_run, int32_t *lens, int64_t capacity) {
+// ... and with the short runs dealt to the labels of `order8`, the slowest XCD's first (null: the even spread)
+extern "C" int64_t paa_debug_balanced_runs_ordered(const int64_t *frames, int64_t n_clips, int run_cap, int quantum, int shrink, int wg_runs,
+                                                   int num_cu, int min_run, const int32_t *order8, int32_t *lens, int64_t capacity) {
     if (!frames || n_clips < 0 || !lens || quantum < 1 || run_cap < quantum || wg_runs < 1 || num_cu < 1 || min_run < 1)
         return fail(PAA_ERR_ARG, "bad argument");
     std::vector<ClipDev> clips((size_t)n_clips);
     for (int64_t c = 0; c < n_clips; ++c) { memset(&clips[(size_t)c], 0, sizeof(ClipDev)); clips[(size_t)c].T = (int)frames[c]; }
     std::vector<std::vector<int>> out;
-    if (!balanced_runs(clips, run_cap, quantum, shrink, wg_runs, num_cu, min_run, out)) return 0;
+    int order[kXcdLabels];
+    if (order8) std::copy(order8, order8 + kXcdLabels, order);
+    if (!balanced_runs(clips, run_cap, quantum, shrink, wg_runs, num_cu, min_run, out, order8 ? order : nullptr)) return 0;
     int64_t n = 0;
     for (const auto &l : out)
         for (int v : l) {
@@ -167,6 +170,99 @@ extern "C" int64_t paa_debug_balanced_runs(const int64_t *frames, int64_t n_clip
             lens[n++] = v;
         }
     return n;
+}
+extern "C" int64_t paa_debug_balanced_runs(const int64_t *frames, int64_t n_clips, int run_cap, int quantum, int shrink, int wg_runs,
+                                           int num_cu, int min_run, int32_t *lens, int64_t capacity) {
+    return paa_debug_balanced_runs_ordered(frames, n_clips, run_cap, quantum, shrink, wg_runs, num_cu, min_run, nullptr, lens, capacity);
+}
+// puts an order in force (null: clears it) -- lib_xcd_order.hpp.  An order that is no permutation of the labels is refused
+extern "C" int paa_debug_xcd_force_order(const int32_t *order8) {
+    if (order8) {
+        int seen = 0;
+        for (int r = 0; r < kXcdLabels; ++r)
+            if (order8[r] >= 0 && order8[r] < kXcdLabels) seen |= 1 << order8[r];
+        if (seen != 0xff) return fail(PAA_ERR_ARG, "an order is a permutation of the labels 0 .. 7");
+    }
+    std::lock_guard<std::mutex> lk(g_xcd.mu);
+    if (order8) {
+        if (!g_xcd.forced) {          // (the measured order it replaces, if one was in force)
+            std::copy(g_xcd.order, g_xcd.order + kXcdLabels, g_xcd.kept);
+            g_xcd.kept_have = g_xcd.have_order;
+        }
+        std::copy(order8, order8 + kXcdLabels, g_xcd.order);
+        g_xcd.forced = true;
+    } else if (g_xcd.forced) {
+        // back to the order the probes had put in force, or to none: a new one needs two consecutive probes as ever
+        g_xcd.forced = false;
+        std::copy(g_xcd.kept, g_xcd.kept + kXcdLabels, g_xcd.order);
+        g_xcd.have_order = g_xcd.kept_have;
+    } else {
+        return PAA_OK;
+    }
+    g_xcd.cand_seen = 0;
+    ++g_xcd.epoch;
+    return PAA_OK;
+}
+extern "C" int paa_debug_xcd_state(int32_t *order8, double *tau8, uint64_t *epoch) {
+    std::lock_guard<std::mutex> lk(g_xcd.mu);
+    if (order8) std::copy(g_xcd.order, g_xcd.order + kXcdLabels, order8);
+    if (tau8) std::copy(g_xcd.tau, g_xcd.tau + kXcdLabels, tau8);
+    if (epoch) *epoch = g_xcd.epoch;
+    return (xcd_enabled() ? 1 : 0) | (g_xcd.off ? 2 : 0) | (g_xcd.forced ? 4 : 0) | ((g_xcd.forced || g_xcd.have_order) ? 8 : 0);
+}
+// the run lengths the plan's next launch uses: a list cut under another order than the one in force is cut again first, as
+// the execute would do it
+extern "C" int64_t paa_debug_plan_runs(const paa_plan_t *plan, int32_t *lens, int64_t capacity, int32_t *info8, uint64_t *epoch) {
+    if (!plan || !lens) return fail(PAA_ERR_ARG, "null plan / buffer");
+    const XcdPlan &x = plan->xcd;
+    if (!x.balanced || !x.resident) return 0;
+    std::lock_guard<std::mutex> lk(g_mu);
+    int order[kXcdLabels];
+    unsigned long long now = 0;
+    const bool on = xcd_current(order, &now);
+    std::vector<Tile> recut;
+    if (now != x.epoch) {
+        std::vector<std::vector<int>> run_lens;
+        if (balanced_runs(plan->clips, x.run, x.quantum, x.shrink, x.wg_runs, g_num_cu, x.min_run, run_lens, on ? order : nullptr))
+            balanced_tiles(run_lens, recut);
+    }
+    // (a re-cut that balanced_runs declines leaves the list as it is, in the execute as here: xcd_recut)
+    const std::vector<Tile> &tiles = (long long)recut.size() == plan->n_tiles ? recut : x.tiles;
+    if ((int64_t)tiles.size() > capacity) return fail(PAA_ERR_ARG, "capacity %lld too small", (long long)capacity);
+    for (size_t i = 0; i < tiles.size(); ++i) lens[i] = tiles[i].cnt;
+    if (info8) {
+        const int32_t info[8] = {x.run, x.quantum, x.shrink, x.wg_runs, x.min_run, g_num_cu, 0, 0};
+        std::copy(info, info + 8, info8);
+    }
+    if (epoch) *epoch = now;
+    return (int64_t)tiles.size();
+}
+extern "C" int64_t paa_debug_plan_probe(paa_plan_t *plan, const void *d_packed, double *d_out, uint64_t *record, int64_t capacity_runs) {
+    if (!plan || !d_packed || !d_out || !record) return fail(PAA_ERR_ARG, "null plan / buffer");
+    { const int rc_init = ensure_init(); if (rc_init) return rc_init; }
+    std::lock_guard<std::mutex> lk(g_mu);
+    XcdPlan &x = plan->xcd;
+    if (!x.balanced || !x.resident || !plan->fam.fl.layout.fixed_lists || kFamilies[plan->fam.family].execute != fam_fast_execute) return 0;
+    if (capacity_runs < plan->n_tiles) return fail(PAA_ERR_ARG, "capacity %lld < %lld runs", (long long)capacity_runs, plan->n_tiles);
+    // (queued like any execute, behind whatever the stream holds: a probe of back-to-back launches sees the chip under load)
+    if (x.probe_pending) HIP_TRY(hipEventSynchronize(x.probe_ev));
+    xcd_consume(plan);
+    int rc = comm_wait_buffer_free(d_out);      // (as paa_plan_execute)
+    if (rc) return rc;
+    rc = launch_stats(plan, d_packed);
+    if (rc) return rc;
+    if ((rc = fam_fast_execute_probe(plan, d_packed, d_out, plan->d_tiles, plan->n_tiles, true))) return rc;
+    if (!x.probe_pending) return 0;
+    HIP_TRY(hipEventSynchronize(x.probe_ev));
+    x.probe_pending = false;
+    memcpy(record, x.h_probe, (size_t)plan->n_tiles * 16);
+    long long t_label[kXcdLabels];
+    int xcc_label[kXcdLabels];
+    if (xcd_read_record(x.h_probe, plan->n_tiles, x.wg_runs, g_num_cu, t_label, xcc_label) < 0) {
+        std::lock_guard<std::mutex> lx(g_xcd.mu);
+        g_xcd.off = true;
+    }
+    return plan->n_tiles;
 }
 // host side of the mixed-radix kernel for a window (no device needed): radix schedule of the in-place DIF transform and the
 // position that holds Z[k] afterwards.  Returns the number of passes, 0 when the window is not for that kernel.

@@ -22,6 +22,8 @@ struct RunRule {
     int fill_wg_runs = 0;        // > 0: runs per workgroup of a kernel with ONE workgroup per CU -- a plan whose equal runs fill less than
                                  // one round of the chip is re-cut into num_cu x fill_wg_runs runs of two lengths (lib_plan.hpp: balanced_runs)
     int fill_min_run = 16;       // ... none of them shorter than this
+    bool fill_by_xcd = false;    // ... and the short ones go to the slow XCDs (lib_xcd_order.hpp).  The fast family only: st_ct shares
+                                 // fill_wg_runs but has had no A/B of the placement, it keeps the even spread
 };
 struct Family {
     const char *id;
@@ -46,6 +48,17 @@ static int two_round_run(long long total_frames, int waves, int num_cu) {
     return (int)std::min<long long>(64, std::max<long long>(8, (per + 3) / 4 * 4));
 }
 
+// the tiles of balanced_runs' lengths, clip after clip in frame order
+static void balanced_tiles(const std::vector<std::vector<int>> &run_lens, std::vector<Tile> &tiles) {
+    for (size_t ci = 0; ci < run_lens.size(); ++ci) {
+        long long t0 = 0;
+        for (int cnt : run_lens[ci]) {
+            Tile tl; tl.clip = (int)ci; tl.t0 = (int)t0; tl.cnt = cnt; tl.pad = 0;
+            tiles.push_back(tl);
+            t0 += cnt;
+        }
+    }
+}
 // the tile list of a one-wave family: runs of its RunRule, balanced or equal, clip after clip in frame order
 static void build_tiles(FamilyCtx &c, const RunRule &rr, std::vector<Tile> &tiles) {
     const std::vector<ClipDev> &clips = c.p->clips;
@@ -55,20 +68,27 @@ static void build_tiles(FamilyCtx &c, const RunRule &rr, std::vector<Tile> &tile
 #ifndef PAA_BALANCED_RUNS
 #define PAA_BALANCED_RUNS 1           // (0: A/B build of scripts/rounds/r05/gpu_r05w.sh -- equal runs, 250 workgroups for the one-hour clip)
 #endif
+    int order[kXcdLabels];
+    unsigned long long epoch = 0;
+    const bool by_xcd = rr.fill_by_xcd && xcd_current(order, &epoch);
     const bool balanced = PAA_BALANCED_RUNS && rr.fill_wg_runs > 0 && c.ranges <= 1 &&
-                          balanced_runs(clips, run, run_quantum, run_halo, rr.fill_wg_runs, g_num_cu, rr.fill_min_run, run_lens);
+                          balanced_runs(clips, run, run_quantum, run_halo, rr.fill_wg_runs, g_num_cu, rr.fill_min_run, run_lens,
+                                        by_xcd ? order : nullptr);
+    if (balanced) {
+        balanced_tiles(run_lens, tiles);
+        if (rr.fill_by_xcd) {          // what a later re-cut under another order needs (fam_fast_execute)
+            XcdPlan &x = c.p->xcd;
+            x.balanced = true;
+            x.run = run; x.quantum = run_quantum; x.shrink = run_halo; x.wg_runs = rr.fill_wg_runs; x.min_run = rr.fill_min_run;
+            x.epoch = epoch;
+            xcd_label_totals(tiles.data(), (long long)tiles.size(), x.wg_runs, x.quantum, x.shrink, x.n_label);
+            if (x.resident) x.tiles = tiles;
+        }
+        return;
+    }
     for (size_t ci = 0; ci < clips.size(); ++ci) {
         const long long T = clips[ci].T;
         if (T <= 0) continue;
-        if (balanced) {
-            long long t0 = 0;
-            for (int cnt : run_lens[ci]) {
-                Tile tl; tl.clip = (int)ci; tl.t0 = (int)t0; tl.cnt = cnt; tl.pad = 0;
-                tiles.push_back(tl);
-                t0 += cnt;
-            }
-            continue;
-        }
         const int len = clip_run_length(T, run, run_quantum);          // equal runs per clip
         for (long long t0 = 0; t0 < T;) {
             const long long want = (t0 > 0) ? len - run_halo : len;
@@ -114,12 +134,95 @@ static void fam_fast_rule(FamilyCtx &c, RunRule &r) {
     r.halo_inside = c.deltas ? 2 : 1;
     r.run = choose_run_cap(c.p->clips, 4, 16, fl.run, 0, fl.waves_per_cu, c.num_cu(), r.halo_inside);
     r.fill_wg_runs = fl.waves_per_cu;
+    r.fill_by_xcd = true;
     if (const char *rc_env = experiment_env("PAA_RUN_CAP")) r.run = std::max(16, atoi(rc_env) / 4 * 4);      // A/B experiments only
 }
 static int fam_fast_launch(const paa_plan *p, const TileArgs &a) {
     TileArgs af = a;          // (its tables belong to the table set, not to the choice)
     af.blob = reinterpret_cast<const unsigned char *>(p->tab->fast.d_blob);
     return launch::fast(p->fam.fl, af);
+}
+// ---- ... and the placement of its short runs by XCD (lib_xcd_order.hpp), for the balanced plans of paa_plan_create
+// the record of the plan's last probe launch, if its copy has arrived: into the device's averages
+static void xcd_consume(paa_plan *p) {
+    XcdPlan &x = p->xcd;
+    if (!x.probe_pending) return;
+    if (hipEventQuery(x.probe_ev) != hipSuccess) { (void)hipGetLastError(); return; }      // (not ready is not an error of this execute)
+    x.probe_pending = false;
+    xcd_fold(x.h_probe, p->n_tiles, x.wg_runs, g_num_cu, x.pending_n);
+}
+// the plan's list was cut under another order than the one in force: cut it again on the host and upload it, stream-ordered in front
+// of the launch that follows (the executes of a plan share a stream).  A handful of times per process
+static int xcd_recut(paa_plan *p, const int *order8, unsigned long long epoch) {
+    XcdPlan &x = p->xcd;
+    std::vector<std::vector<int>> run_lens;
+    std::vector<Tile> tiles;
+    if (balanced_runs(p->clips, x.run, x.quantum, x.shrink, x.wg_runs, g_num_cu, x.min_run, run_lens, order8)) balanced_tiles(run_lens, tiles);
+    x.epoch = epoch;
+    if ((long long)tiles.size() != p->n_tiles) return PAA_OK;          // (cannot happen: an order moves runs, it does not add any)
+    const size_t bytes = tiles.size() * sizeof(Tile);
+    if (!x.h_tiles) HIP_TRY(hipHostMalloc((void **)&x.h_tiles, bytes, hipHostMallocDefault));
+    if (!x.upload_ev) HIP_TRY(hipEventCreateWithFlags(&x.upload_ev, hipEventDisableTiming));
+    if (x.upload_pending) HIP_TRY(hipEventSynchronize(x.upload_ev));          // (the staging buffer of the last re-cut)
+    memcpy(x.h_tiles, tiles.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(p->d_tiles, x.h_tiles, bytes, hipMemcpyHostToDevice, cs()));
+    HIP_TRY(hipEventRecord(x.upload_ev, cs()));
+    x.upload_pending = true;
+    xcd_label_totals(tiles.data(), p->n_tiles, x.wg_runs, x.quantum, x.shrink, x.n_label);
+    x.tiles.swap(tiles);
+    return PAA_OK;
+}
+// the probe buffers of a plan, at its first probe launch
+static int xcd_probe_buffers(paa_plan *p) {
+    XcdPlan &x = p->xcd;
+    const size_t bytes = (size_t)p->n_tiles * 16;
+    if (!x.d_probe) { const int rc = pool_alloc((void **)&x.d_probe, bytes); if (rc) return rc; }
+    if (!x.h_probe) HIP_TRY(hipHostMalloc((void **)&x.h_probe, bytes, hipHostMallocDefault));
+    if (!x.probe_ev) HIP_TRY(hipEventCreateWithFlags(&x.probe_ev, hipEventDisableTiming));
+    return PAA_OK;
+}
+// force_probe: paa_debug_plan_probe's launch (the caller waits for the record itself)
+static int fam_fast_execute_probe(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles, bool force_probe) {
+    if (n_tiles == 0) return PAA_OK;
+    XcdPlan &x = p->xcd;
+    bool probe = false;
+    if (x.balanced && x.resident && tiles == p->d_tiles && n_tiles == p->n_tiles) {
+        if (xcd_enabled()) {
+            xcd_consume(p);
+            int order[kXcdLabels];
+            unsigned long long epoch = 0;
+            const bool on = xcd_current(order, &epoch);
+            if (epoch != x.epoch) { const int rc = xcd_recut(p, on ? order : nullptr, epoch); if (rc) return rc; }
+            // (the kernel's run-time-list instances carry no probe: launch::fast; a forced probe is not one of the device's own)
+            probe = xcd_want_probe(p->fam.fl.layout.fixed_lists && !x.probe_pending && !force_probe);
+        } else if (x.epoch != 0) {          // switched off after an ordered cut: back to the even spread
+            const int rc = xcd_recut(p, nullptr, 0);
+            if (rc) return rc;
+        }
+        probe = (probe || force_probe) && p->fam.fl.layout.fixed_lists && !x.probe_pending;
+        if (probe) {
+            const int rc = xcd_probe_buffers(p);
+            if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(x.d_probe, 0, (size_t)n_tiles * 16, cs()));          // (a wave that left no times shows)
+        }
+    }
+    {
+        ProfScope prof_scope;
+        { const int rc_p = prof_scope.begin(); if (rc_p) return rc_p; }
+        TileArgs a{p->P, p->fam.d_blob, d_packed, p->sample_kind, p->d_clips, p->d_norms, tiles, n_tiles, d_out, cs()};
+        a.probe = probe ? x.d_probe : nullptr;
+        if (fam_fast_launch(p, a)) return launch_failed(p);
+    }
+    if (probe) {
+        HIP_TRY(hipMemcpyAsync(x.h_probe, x.d_probe, (size_t)n_tiles * 16, hipMemcpyDeviceToHost, cs()));
+        HIP_TRY(hipEventRecord(x.probe_ev, cs()));
+        std::copy(x.n_label, x.n_label + kXcdLabels, x.pending_n);
+        x.probe_pending = true;
+    }
+    return PAA_OK;
+}
+static int fam_fast_execute(paa_plan *p, const void *d_packed, double *d_out, const Tile *tiles, long long n_tiles) {
+    return fam_fast_execute_probe(p, d_packed, d_out, tiles, n_tiles, false);
 }
 
 // ---- kernels_ct.hpp: windows 2 RA RB (800, 640, 400, 320), any step / sample type / mode
@@ -344,7 +447,7 @@ static int fam_hbm_execute(paa_plan *p, const void *d_packed, double *d_out, con
 
 // in choice order; ranged / norms_inline: the one-wave families only
 static const Family kFamilies[] = {
-    {"fast", fam_fast_select, tile_work<fam_fast_rule>, tile_execute<fam_fast_launch>, true, true},
+    {"fast", fam_fast_select, tile_work<fam_fast_rule>, fam_fast_execute, true, true},
     {"ct", fam_ct_select, tile_work<fam_ct_rule>, tile_execute<fam_ct_launch>, true, true},
     {"tri", fam_tri_select, tile_work<fam_tri_rule>, tile_execute<fam_tri_launch>, true, true},
     {"mix", fam_mix_select, tile_work<fam_mix_rule>, tile_execute<fam_mix_launch>, true, true},

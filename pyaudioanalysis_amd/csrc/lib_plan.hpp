@@ -71,9 +71,22 @@ static inline int clip_run_length(long long T, int cap, int quantum) {
 // clip's first hold `shrink` halo frames inside their first iteration, i.e. store that many frames less.  Along the order
 // (workgroup, SIMD, wave of the SIMD) long and short runs alternate, so the waves that share a SIMD (w, w + 4, ...) get long and
 // short ones in the plan's overall ratio.  Returns false (lens untouched) when the equal runs stay.
+// xcd_order (optional; eight labels, label = workgroup mod 8, the slowest XCD's first -- lib_xcd_order.hpp): a launch lasts as long as
+// its slowest XCD needs for its largest SIMD total, so the SHORT runs go where they shorten that: a clip keeps its numbers of long
+// and short runs, but the shorts are dealt one per SIMD group (the `per` waves of a SIMD), label after label in the given order,
+// workgroup after workgroup inside a label, and only then a second one per group.  Inside a group the member the even spread
+// makes short is taken first, then the last one.  Without an order (or a permutation, or a chip of num_cu % 8 workgroups more,
+// or waves that do not pair up on the SIMDs) the even spread stays, byte for byte.
 static bool balanced_runs(const std::vector<ClipDev> &clips, int run, int quantum, int shrink, int wg_runs, int num_cu, int min_run,
-                          std::vector<std::vector<int>> &lens) {
+                          std::vector<std::vector<int>> &lens, const int *xcd_order = nullptr) {
     if (wg_runs < 2 || quantum < 1 || shrink < 0 || (shrink > 0 && shrink >= quantum)) return false;
+    int rank[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (xcd_order) {
+        int seen = 0;
+        for (int r = 0; r < 8; ++r)
+            if (xcd_order[r] >= 0 && xcd_order[r] < 8) { rank[xcd_order[r]] = r; seen |= 1 << xcd_order[r]; }
+        if (seen != 0xff || num_cu % 8 != 0 || wg_runs % 4 != 0) xcd_order = nullptr;
+    }
     long long total = 0, runs = 0;
     std::vector<long long> need(clips.size(), 0);
     for (size_t c = 0; c < clips.size(); ++c) {
@@ -115,8 +128,34 @@ static bool balanced_runs(const std::vector<ClipDev> &clips, int run, int quantu
             order.emplace_back(per ? (j * 4 + w % 4) * per + w / 4 : tile, i);
         }
         std::sort(order.begin(), order.end());
+        std::vector<char> is_long((size_t)kc, 0);          // by position u
+        for (long long u = 0; u < kc; ++u) is_long[(size_t)u] = (u + 1) * longs / kc > u * longs / kc;
+        if (xcd_order && longs > 0) {
+            struct Group { long long key, u0; int n, given; };          // key: (rank of the label, workgroup, SIMD); positions [u0, u0 + n)
+            std::vector<Group> groups;
+            for (long long u = 0; u < kc; ++u) {
+                const long long gid = order[(size_t)u].first / per, j = gid / 4;
+                const long long key = ((long long)rank[j % 8] << 40) | gid;
+                if (groups.empty() || groups.back().key != key) groups.push_back(Group{key, u, 0, 0});
+                ++groups.back().n;
+            }
+            std::sort(groups.begin(), groups.end(), [](const Group &a, const Group &b) { return a.key < b.key; });
+            const std::vector<char> even = is_long;
+            std::fill(is_long.begin(), is_long.end(), 1);
+            for (long long left = kc - longs; left > 0;)
+                for (Group &g : groups) {          // one round: a short run more for every group that still has a long one
+                    if (left == 0) break;
+                    if (g.given == g.n) continue;
+                    long long pick = -1;
+                    for (long long u = g.u0 + g.n - 1; u >= g.u0; --u)
+                        if (is_long[(size_t)u] && (pick < 0 || (!even[(size_t)u] && even[(size_t)pick]))) pick = u;
+                    is_long[(size_t)pick] = 0;
+                    ++g.given;
+                    --left;
+                }
+        }
         for (long long u = 0; u < kc; ++u)
-            if ((u + 1) * longs / kc > u * longs / kc) l[(size_t)order[(size_t)u].second] += quantum;
+            if (is_long[(size_t)u]) l[(size_t)order[(size_t)u].second] += quantum;
         long long sum = 0;
         for (size_t i = 0; i < l.size(); ++i) { if (i > 0) l[i] -= shrink; sum += l[i]; }
         l.back() -= (int)(sum - T);          // the iterations cover whole quanta: the last run gives back what the clip does not have
@@ -126,6 +165,8 @@ static bool balanced_runs(const std::vector<ClipDev> &clips, int run, int quantu
     lens.swap(out);
     return true;
 }
+
+#include "lib_xcd_order.hpp"
 
 // the kernel choice of a plan: its entry of kFamilies (lib_dispatch.hpp), the layout of that entry's kernel (only its own member
 // is meaningful) and the table blob on the device.  Cached per (table set, mode, rows) in TableSet::choices.
@@ -177,6 +218,7 @@ struct paa_plan {
     long long mid_off_step = -1;
     long long n_tiles = 0, n_chunks = 0;
     std::vector<Tile> tiles_host;    // host copy of the tile list (plans built for a ranged launch only)
+    XcdPlan xcd;                     // balanced plans of the fast family: placement of the short runs by XCD (lib_xcd_order.hpp)
 };
 
 static std::atomic<int> g_live_plans{0};          // plans hold raw pointers into the device's table sets (freed outside g_mu too)
@@ -188,6 +230,8 @@ static void plan_free(paa_plan *p) {
     pool_free(p->d_mid_off);
     pool_free(p->d_wg_frames);
     pool_free(p->d_wg_tasks);
+    pool_free(p->xcd.d_probe);
+    xcd_plan_free(p->xcd);
     if (!p->blob_cached) pool_free(p->fam.d_blob);
     if (p->d_big) (void)hipFree(p->d_big);
     delete p;
@@ -517,7 +561,7 @@ static int run_wgr(paa_plan *p, const WgArgs &a, const Tile *runs, long long n_r
 
 // ranges > 1: the caller will launch the plan's tiles in that many consecutive groups (run_host_st's copy-back pipeline)
 static int plan_build(const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window, int step,
-                      int deltas, int mode, paa_plan **out, int ranges = 1) {
+                      int deltas, int mode, paa_plan **out, int ranges = 1, bool resident = false) {
     int rc = ensure_init();
     if (rc) return rc;
     if (!offsets || n_clips < 1 || !out) return fail(PAA_ERR_ARG, "null offsets / no clips");
@@ -530,6 +574,7 @@ static int plan_build(const int64_t *offsets, int64_t n_clips, int sample_kind, 
     p->n_clips = n_clips;
     p->sample_kind = sample_kind;
     p->mode = mode;
+    p->xcd.resident = resident;
     TableSet *tab = nullptr;
     if ((rc = get_tables(fs, window, mode == 0, mode != 1, &tab))) return rc;
     p->tab = tab;
@@ -666,7 +711,7 @@ extern "C" int paa_plan_execute(paa_plan_t *plan, const void *d_packed, double *
 extern "C" int paa_plan_create(const int64_t *offsets, int64_t n_clips, int sample_kind, double fs, int window,
                                int step, int deltas, paa_plan_t **out_plan) {
     std::lock_guard<std::mutex> lk(g_mu);
-    return plan_build(offsets, n_clips, sample_kind, fs, window, step, deltas, 0, out_plan);
+    return plan_build(offsets, n_clips, sample_kind, fs, window, step, deltas, 0, out_plan, 1, true);
 }
 
 // device-resident plan of the spectrogram (mode 1, :389-452) / chromagram (mode 2, :324-386) rows of one or more clips:

@@ -420,6 +420,7 @@ extern "C" void paa_shutdown(void) {
     g_ev0 = g_ev1 = nullptr;
     g_main_stream = nullptr;
     ++lds_attr_generation();                 // the next device has not seen any hipFuncSetAttribute
+    xcd_reset();                             // ... and its XCDs have not been measured (lib_xcd_order.hpp)
     g_device.store(-1, std::memory_order_release);
 }
 
