@@ -935,6 +935,35 @@ int paa_diar_dev_kmeans_f64(const double *d_z, int n_dims, int64_t ld, int64_t n
 int paa_diar_dev_pair_sums_f64(const double *d_z, int n_dims, int64_t ld, int64_t n_vec, const int32_t *d_labels,
                                const int32_t *ks, int nk, double *sums);
 
+/* ---- speaker diarization of a batch of clips (audioSegmentation.diarize_features_batch) ---------------------------------------
+ * The calls above over MANY clips at once.  The clips lie side by side in ONE device matrix, feature-major [n_dims][ld]
+ * (n_dims 1..256): clip i owns the columns cols[i] .. cols[i] + ns[i] - 1 (at most 65535 clips per call).  Clip i's results
+ * carry the bits of its own single calls, at any position and beside any other clips.  Both calls are synchronous.
+ * prepare: standardize and the all-window dim_distances of every clip; d_z (a buffer of its own, layout of d_feats), stats
+ * [n_clips][3][n_dims] = mean, variance, scale, colsum [n_clips][n_dims].  One wait.
+ * sweep: k-means for every (clip, k) job and the silhouette's inputs.  Clip i clusters the dims[i] feature rows rows[..] of d_z
+ * (the lists of all clips one after the other; the rows are read in place, never compacted) for its nks[i] cluster counts;
+ * ks, seeded, first, n_iter and inertia run over the jobs, clip after clip; tols [n_clips] as kmeans' tol.  A job with
+ * seeded[j] != 0 is seeded on the device by greedy k-means++ (2 + int(ln k) candidates per step) from numbers the caller drew:
+ * first[j] = the first centre's window and, in u (the seeded jobs one after the other), [k - 1][trials] numbers in [0, 1); the
+ * potentials, the candidates' sums and the cumulative sum are formed in NumPy's order (pairwise summation per 8192 elements,
+ * serial cumsum).  Any other job starts from centers.  centers: [k][dims[i]] per job, one after the other, the given initial
+ * centres on entry, the final ones on return.  d_labels (device): [n] per job, one after the other.  a_mean [jobs][32]: the
+ * pair_mean of dim_distances per cluster; pair_sums [jobs][32][32] as pair_sums.  stage_ms: null, or [4] = the milliseconds
+ * of seeding, k-means and the silhouette inputs (the stream is drained between them) and the Lloyd iterations of the slowest
+ * job.  The host waits once per Lloyd iteration of the slowest job and a constant number of times besides.
+ * gather: the [n_rows][ns[i]] slabs of a batched plan (clip i at d_slabs + slab_offsets[i]) become the column ranges cols[i] of
+ * the matrix d_out [>= n_rows][ld]; queued on the library stream, no wait.                                                */
+int paa_diar_batch_gather_f64(const double *d_slabs, int n_rows, const int64_t *slab_offsets, const int64_t *cols,
+                              const int64_t *ns, int n_clips, double *d_out, int64_t ld);
+int paa_diar_batch_prepare_f64(const double *d_feats, int n_dims, int64_t ld, const int64_t *cols, const int64_t *ns, int n_clips,
+                               double *d_z, double *stats, double *colsum);
+int paa_diar_batch_sweep_f64(const double *d_z, int n_dims, int64_t ld, int n_clips, const int64_t *cols, const int64_t *ns,
+                             const int32_t *dims, const int32_t *rows, const int32_t *nks, const int32_t *ks, const double *tols,
+                             int max_iter, const int32_t *seeded, const int64_t *first, const double *u, double *centers,
+                             int32_t *d_labels, int32_t *n_iter, double *inertia, double *a_mean, double *pair_sums,
+                             double *stage_ms);
+
 /* ---- the LDA step of speaker diarization (audioSegmentation.py:880-934, lda_dim > 0) ------------------------------------------
  * The O(n) parts of scikit-learn's LinearDiscriminantAnalysis (svd solver) on a device matrix, feature-major [n_dims][ld]
  * (n_dims 1..256), window t in column t.  Classes are CONTIGUOUS runs of windows: class c = windows run_offsets[c] ..

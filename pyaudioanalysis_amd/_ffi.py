@@ -226,6 +226,11 @@ _SIGNATURES = {
     "paa_diar_dev_kmeans_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i32p, C.c_int, c_f64p, C.c_double,
                                           C.c_int, C.c_void_p, c_i32p, c_f64p]),
     "paa_diar_dev_pair_sums_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, c_i32p, C.c_int, c_f64p]),
+    "paa_diar_batch_prepare_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_i64p, c_i64p, C.c_int, C.c_void_p, c_f64p, c_f64p]),
+    "paa_diar_batch_gather_f64": (C.c_int, [C.c_void_p, C.c_int, c_i64p, c_i64p, c_i64p, C.c_int, C.c_void_p, C.c_int64]),
+    "paa_diar_batch_sweep_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_i64p, c_i64p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                           c_f64p, C.c_int, c_i32p, c_i64p, c_f64p, c_f64p, C.c_void_p, c_i32p, c_f64p, c_f64p,
+                                           c_f64p, c_f64p]),
     "paa_lda_dev_class_stats_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64, c_f64p, c_f64p]),
     "paa_lda_dev_within_gram_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, c_i64p, C.c_int64, c_f64p, c_f64p,
                                               C.c_double, c_f64p]),

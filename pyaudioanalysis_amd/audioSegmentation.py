@@ -30,6 +30,7 @@ speaker_diarization(lda_dim > 0) itself refuses and names them.
 """
 import contextlib
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -1689,10 +1690,11 @@ def _score_diarization(filename, cls, details, mid_step, duration, n_speakers, p
     return cls, purities[0], purities[1]
 
 
-def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, models_dir=None, random_state=None):
+def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, models_dir=None, random_state=None, batch=False):
     """Prints the purities of every WAV file of a folder for every LDA dimension of the list (reference :1059-1090): the
     number of speakers comes from the file's .segments ground truth (-1: unknown).  Dimension 0 runs speaker_diarization,
-    a dimension above 0 speaker_diarization_lda, both with the reference's settings (2.0 / 0.2 / 0.05 s)."""
+    a dimension above 0 speaker_diarization_lda, both with the reference's settings (2.0 / 0.2 / 0.05 s).  batch=True sends
+    the dimension-0 pass through speaker_diarization_files: one device batch per sampling rate, the same lines printed."""
     import glob
     import os
     wav_files = sorted(glob.glob(os.path.join(folder_name, '*.wav')))
@@ -1707,6 +1709,10 @@ def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, 
             num_speakers.append(-1)
     for dim in lda_dimensions:
         print("LDA = {0:d}".format(dim))
+        if batch and dim <= 0:
+            speaker_diarization_files(wav_files, num_speakers, 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
+                                      random_state=random_state)
+            continue
         for i, wav_file in enumerate(wav_files):
             if dim > 0:
                 speaker_diarization_lda(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
@@ -1714,6 +1720,529 @@ def speaker_diarization_evaluation(folder_name, lda_dimensions, *, models=None, 
             else:
                 speaker_diarization(wav_file, num_speakers[i], 2.0, 0.2, 0.05, dim, plot_res=False, models=loaded,
                                     random_state=random_state)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# speaker diarization of many clips in one call (lda_dim = 0)
+# ---------------------------------------------------------------------------------------------------------
+_DIAR_BATCH_MAX_JOBS = 8192        # (clip, k) jobs and (job, cluster) slots of one chunk: every grid stays below the y limit
+_DIAR_BATCH_MAX_SLOTS = 65535
+_DIAR_PAIR_TILE = 128              # kernels_diarbatch.hpp: windows per side of a pair tile, tiles per first-stage sum
+_DIAR_PAIR_CHUNK = 256
+
+
+class _DeviceView:
+    """Columns of a device matrix as the object the single-clip entry points take: .ptr, nothing owned."""
+
+    def __init__(self, buf, offset_bytes):
+        self.ptr = C.c_void_p(buf.ptr.value + int(offset_bytes))
+
+
+def _diar_batch_ks(n_speakers):
+    return list(range(2, 10)) if n_speakers <= 0 else [int(n_speakers)]
+
+
+def _diar_batch_check(n_dims_list, ns, n_speakers, init_centers):
+    """The argument half of diarize_features_batch, without the device: (n_dims, ks per clip, init_centers per clip) or the
+    ValueError of the first clip that cannot be served, named by its index."""
+    n_clips = len(ns)
+    if np.ndim(n_speakers) == 0:
+        speakers = [int(n_speakers)] * n_clips
+    else:
+        speakers = [int(s) for s in n_speakers]
+        if len(speakers) != n_clips:
+            raise ValueError("n_speakers: an int or one int per clip (%d clips, %d values)" % (n_clips, len(speakers)))
+    if init_centers is None:
+        inits = [None] * n_clips
+    else:
+        inits = list(init_centers)
+        if len(inits) != n_clips:
+            raise ValueError("init_centers: None or one dict (or None) per clip (%d clips, %d entries)" % (n_clips, len(inits)))
+    n_dims = int(n_dims_list[0]) if n_clips else 0
+    ks_list = []
+    for c in range(n_clips):
+        d, n = int(n_dims_list[c]), int(ns[c])
+        if d != n_dims:
+            raise ValueError("clip %d: %d feature dims, clip 0 has %d (one batch shares n_dims)" % (c, d, n_dims))
+        if d < 1 or d > _DIAR_MAX_DIMS or n < 1:
+            raise ValueError("clip %d: feature matrix of %d dims x %d windows: 1..%d dims and at least one window"
+                             % (c, d, n, _DIAR_MAX_DIMS))
+        ks = _diar_batch_ks(speakers[c])
+        if min(ks) < 1 or max(ks) > _DIAR_MAX_K:
+            raise ValueError("clip %d: %d speakers: 1..%d clusters are supported" % (c, ks[0], _DIAR_MAX_K))
+        if n < max(ks):
+            raise ValueError("clip %d: %d windows are fewer than %d clusters" % (c, n, max(ks)))
+        if inits[c] is not None:
+            checked = {}
+            for k, init in dict(inits[c]).items():
+                init = np.asarray(init, dtype=np.float64)
+                if k in ks and (init.ndim != 2 or init.shape[0] != k or not 1 <= init.shape[1] <= d):
+                    raise ValueError("clip %d: init_centers[%d] has shape %s, (%d, kept dims <= %d) expected" % (c, k, init.shape, k, d))
+                checked[k] = init
+            inits[c] = checked
+        ks_list.append(ks)
+    return n_dims, ks_list, inits
+
+
+def _diar_clip_bytes(n_dims, n, ks):
+    """Device scratch of one clip's jobs in paa_diar_batch_sweep_f64 (labels, d2, the seeding's candidate rows, the feature-row
+    distance matrices with every row kept, the pair partials and their first-stage sums) and in paa_diar_batch_prepare_f64."""
+    nb = (n + _DIAR_PAIR_TILE - 1) // _DIAR_PAIR_TILE
+    tiles = nb * (nb + 1) // 2
+    bins = sum(k * k for k in ks)
+    trials = sum(2 + int(np.log(k)) for k in ks)
+    return (12 * len(ks) + 8 * trials) * n + 8 * (tiles + (tiles + _DIAR_PAIR_CHUNK - 1) // _DIAR_PAIR_CHUNK + 1) * bins \
+        + 8 * (sum(ks) + 1) * n_dims * n_dims + 8 * 2 * sum(ks) * n_dims
+
+
+def _diar_batch_chunks(n_dims, ns, ks_list, chunk_bytes=None):
+    """Clips packed into chunks in order: [(first, last + 1)].  A chunk's scratch stays under chunk_bytes (1 GiB when None) and
+    its jobs under _DIAR_BATCH_MAX_JOBS; a clip that is over the bound by itself is a chunk of one."""
+    bound = int(chunk_bytes) if chunk_bytes else 1 << 30
+    chunks, first, used, jobs, slots = [], 0, 0, 0, 0
+    for c in range(len(ns)):
+        need = _diar_clip_bytes(n_dims, int(ns[c]), ks_list[c])
+        if c > first and (used + need > bound or jobs + len(ks_list[c]) > _DIAR_BATCH_MAX_JOBS
+                          or slots + sum(ks_list[c]) > _DIAR_BATCH_MAX_SLOTS):
+            chunks.append((first, c))
+            first, used, jobs, slots = c, 0, 0, 0
+        used += need
+        jobs += len(ks_list[c])
+        slots += sum(ks_list[c])
+    if len(ns) > first:
+        chunks.append((first, len(ns)))
+    return chunks
+
+
+def _diar_batch_draws(rs, n, ks, init, dims=None):
+    """What one clip's sweep takes from `rs`, drawn up front in the order of the loop: per k without given centres randint(n),
+    then (k - 1) times uniform(size = 2 + int(ln k)) -- the count does not depend on the data.  Returns ([(k, first, u)], exc):
+    a given init_centers[k] whose shape is not (k, dims) stops the draws where the loop would raise, and exc is that ValueError
+    (dims None: the shapes are not looked at)."""
+    out = []
+    for k in ks:
+        if init is not None and k in init:
+            if dims is not None and init[k].shape != (k, dims):
+                return out, ValueError("init_centers[%d] has shape %s, %s expected" % (k, init[k].shape, (k, dims)))
+            out.append((k, None, None))
+            continue
+        trials = 2 + int(np.log(k))
+        first = int(rs.randint(n))
+        u = np.empty((k - 1, trials))
+        for step in range(k - 1):
+            u[step] = rs.uniform(size=trials)
+        out.append((k, first, u))
+    return out, None
+
+
+def _diar_sweep_chunk(d_z, n_dims, ld, cols, ns, kept_list, tols, draws_list, inits, max_iter, d_labels, stage_ms):
+    """paa_diar_batch_sweep_f64 for the clips of one chunk (all of them good): per clip the per-k half of the details dict"""
+    lib = _ffi.lib()
+    n_clips = len(ns)
+    dims = np.array([len(k) for k in kept_list], dtype=np.int32)
+    rows = np.ascontiguousarray(np.concatenate(kept_list), dtype=np.int32)
+    nks = np.array([len(d) for d in draws_list], dtype=np.int32)
+    ks = np.array([k for d in draws_list for k, _, _ in d], dtype=np.int32)
+    n_jobs = ks.shape[0]
+    seeded, first = np.zeros(n_jobs, dtype=np.int32), np.zeros(n_jobs, dtype=np.int64)
+    us, cen, cen_off, job = [], [], [0], 0
+    for c, draws in enumerate(draws_list):
+        for k, f, u in draws:
+            if f is None:
+                cen.append(np.ascontiguousarray(inits[c][k], dtype=np.float64).reshape(-1))
+            else:
+                seeded[job], first[job] = 1, f
+                us.append(u.reshape(-1))
+                cen.append(np.zeros(k * int(dims[c])))
+            cen_off.append(cen_off[-1] + k * int(dims[c]))
+            job += 1
+    centers = np.ascontiguousarray(np.concatenate(cen))
+    u_all = np.ascontiguousarray(np.concatenate(us)) if us else np.zeros(1)
+    n_iter, inertia = np.zeros(n_jobs, dtype=np.int32), np.empty(n_jobs)
+    a_mean, pair = np.empty((n_jobs, _DIAR_MAX_K)), np.empty((n_jobs, _DIAR_MAX_K, _DIAR_MAX_K))
+    ms = np.zeros(4)
+    _ffi.check(lib.paa_diar_batch_sweep_f64(
+        d_z.ptr, n_dims, ld, n_clips, _ffi.as_i64p(np.ascontiguousarray(cols, dtype=np.int64)),
+        _ffi.as_i64p(np.ascontiguousarray(ns, dtype=np.int64)), _ffi.as_i32p(dims), _ffi.as_i32p(rows), _ffi.as_i32p(nks), _ffi.as_i32p(ks),
+        _ffi.as_f64p(np.ascontiguousarray(tols, dtype=np.float64)), int(max_iter), _ffi.as_i32p(seeded), _ffi.as_i64p(first),
+        _ffi.as_f64p(u_all), _ffi.as_f64p(centers), d_labels.ptr, _ffi.as_i32p(n_iter), _ffi.as_f64p(inertia), _ffi.as_f64p(a_mean),
+        _ffi.as_f64p(pair), _ffi.as_f64p(ms) if stage_ms is not None else None))
+    if stage_ms is not None:
+        for name, v in zip(("seeding", "kmeans", "silhouette_inputs"), ms[:3]):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(v)
+        stage_ms["kmeans_rounds"] = stage_ms.get("kmeans_rounds", 0) + int(ms[3])
+    total = int(sum(int(nks[c]) * int(ns[c]) for c in range(n_clips)))
+    t0 = time.perf_counter()
+    labels_all = d_labels.to_host(np.int32, total)                 # ONE read-back for the labels of every job of the chunk
+    if stage_ms is not None:
+        stage_ms["copy_back"] = stage_ms.get("copy_back", 0.0) + 1e3 * (time.perf_counter() - t0)
+    out, job, at = [], 0, 0
+    for c, draws in enumerate(draws_list):
+        n = int(ns[c])
+        details = {"ks": [k for k, _, _ in draws], "labels": {}, "centers": {}, "n_iter": {}, "inertia": {}, "sil_a": {}, "sil_b": {},
+                   "sil": {}, "pair_sums": {}}
+        scores = []
+        for k, _, _ in draws:
+            labels = labels_all[at:at + n].astype(np.int64)
+            a, b, sil = _diar_silhouette(n, k, labels, a_mean[job], pair[job])
+            details["labels"][k] = labels
+            details["centers"][k] = centers[cen_off[job]:cen_off[job + 1]].reshape(k, int(dims[c])).copy()
+            details["n_iter"][k] = int(n_iter[job])
+            details["inertia"][k] = float(inertia[job])
+            details["sil_a"][k], details["sil_b"][k], details["sil"][k] = a, b, sil
+            details["pair_sums"][k] = pair[job, :k, :k].copy()
+            scores.append(np.mean(sil))
+            job += 1
+            at += n
+        details["scores"] = np.array(scores)
+        details["imax"] = int(np.argmax(scores))
+        out.append(details)
+    return out
+
+
+def diarize_clusters_batch_device(d_m, n_dims, ld, cols, ns, n_speakers, *, random_state=None, init_centers=None, max_iter=300,
+                                  tol=1e-4, chunk_bytes=None):
+    """The batch form of diarize_clusters_device: steps 3-6 of diarize_features for MANY clips that lie side by side in one
+    device matrix (DeviceBuffer of [n_dims][ld] doubles, clip c in the columns cols[c] .. cols[c] + ns[c] - 1).  Returns
+    (results, d_z): per clip the details dict of diarize_clusters_device -- or the exception its single call would raise (no
+    dimension passes the filter, an init_centers entry of the wrong shape) -- and the DeviceBuffer of the standardised,
+    UNFILTERED matrix [n_dims][ld] (the caller frees it).  Clip c's entries equal its own single call bit for bit.
+
+    Per chunk of clips (chunk_bytes bounds the device scratch, 1 GiB when None) the host waits once for the standardisation
+    and the dimension distances of all clips, once per Lloyd iteration of the slowest (clip, k) job, and twice for the
+    silhouette inputs and the labels.  The filter colsum < 1.1 * mean, the k-means tolerance and the silhouette arithmetic stay
+    in NumPy on the host, so their bits are the loop's.  The k-means++ draws are made up front in clip order (see
+    _diar_batch_draws): an int random_state seeds every clip afresh, a RandomState instance is consumed as the loop would."""
+    return _diar_clusters_batch(d_m, n_dims, ld, cols, ns, n_speakers, random_state, init_centers, max_iter, tol, chunk_bytes)
+
+
+def _diar_clusters_batch(d_m, n_dims, ld, cols, ns, n_speakers, random_state, init_centers, max_iter=300, tol=1e-4, chunk_bytes=None,
+                         stage_ms=None, given_draws=None):
+    """diarize_clusters_batch_device; stage_ms: a dict that collects the milliseconds per stage (the benchmark's), given_draws:
+    per clip the draws its caller made in ITS clip order (speaker_diarization_files)"""
+    lib = _ffi.lib()
+    cols, ns = np.ascontiguousarray(cols, dtype=np.int64), np.ascontiguousarray(ns, dtype=np.int64)
+    n_clips = ns.shape[0]
+    _, ks_list, inits = _diar_batch_check([n_dims] * n_clips, ns, n_speakers, init_centers)
+    results = [None] * n_clips
+    d_z = _ffi.DeviceBuffer(n_dims * ld * 8)
+    d_labels = None
+    try:
+        for lo, hi in _diar_batch_chunks(n_dims, ns, ks_list, chunk_bytes):
+            m = hi - lo
+            stats, colsum = np.empty((m, 3, n_dims)), np.empty((m, n_dims))
+            t0 = time.perf_counter()
+            _ffi.check(lib.paa_diar_batch_prepare_f64(d_m.ptr, n_dims, ld, _ffi.as_i64p(cols[lo:hi].copy()), _ffi.as_i64p(ns[lo:hi].copy()),
+                                                      m, d_z.ptr, _ffi.as_f64p(stats), _ffi.as_f64p(colsum)))
+            if stage_ms is not None:
+                stage_ms["prepare"] = stage_ms.get("prepare", 0.0) + 1e3 * (time.perf_counter() - t0)
+            good, kept_list, tols, draws_list, heads = [], [], [], [], {}
+            for c in range(lo, hi):
+                cs, st = colsum[c - lo], stats[c - lo]
+                kept = np.nonzero(cs < 1.1 * np.mean(cs))[0]
+                if kept.shape[0] < 1:
+                    results[c] = ValueError("no feature dimension passes the reference's distance filter (a single dimension never does)")
+                    continue
+                if given_draws is not None:
+                    exc = None
+                    for k, f, u in given_draws[c]:
+                        if f is None and inits[c][k].shape != (k, int(kept.shape[0])):
+                            exc = ValueError("init_centers[%d] has shape %s, %s expected" % (k, inits[c][k].shape, (k, int(kept.shape[0]))))
+                            break
+                    draws = given_draws[c]
+                else:
+                    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+                    draws, exc = _diar_batch_draws(rs, int(ns[c]), ks_list[c], inits[c], int(kept.shape[0]))
+                if exc is not None:
+                    results[c] = exc
+                    continue
+                good.append(c)
+                kept_list.append(kept)
+                # tol of scikit-learn: 1e-4 * mean(var(Zk, axis=0)); a standardised row has variance var / scale^2
+                tols.append(tol * float(np.mean(st[1, kept] / st[2, kept] ** 2)))
+                draws_list.append(draws)
+                heads[c] = {"kept_dims": kept, "dim_colsum": cs.copy(), "mean": st[0].copy(), "var": st[1].copy(), "scale": st[2].copy()}
+            if not good:
+                continue
+            total = int(sum(len(ks_list[c]) * int(ns[c]) for c in good))
+            d_labels = _ffi.DeviceBuffer(max(4 * total, 8))
+            swept = _diar_sweep_chunk(d_z, n_dims, ld, cols[good], ns[good], kept_list, tols, draws_list, [inits[c] for c in good], max_iter,
+                                      d_labels, stage_ms)
+            d_labels.free()
+            d_labels = None
+            for c, details in zip(good, swept):
+                heads[c].update(details)
+                results[c] = heads[c]
+    except BaseException:
+        d_z.free()
+        raise
+    finally:
+        if d_labels is not None:
+            d_labels.free()
+    return results, d_z
+
+
+def diarize_hmm_batch_device(d_z, n_dims, ld, cols, ns, labels_list):
+    """The HMM smoothing of a batch alone (steps 7-8 before the median filter): per clip the Viterbi states of the HMM trained
+    on that clip's columns of the device matrix d_z [n_dims][ld] and its labels -- or the exception the single call raises
+    (IndexError: a cluster without windows; ValueError: a zero deviation or a state that is never left).  labels_list[c] is
+    None for a clip to skip (its slot stays None).  The clips run one after the other through the single-clip entry points
+    (train_hmm_compute_statistics_device, GaussianHmm.predict_device) on the resident matrix: this stage still waits per clip."""
+    out = [None] * len(ns)
+    for c, labels in enumerate(labels_list):
+        if labels is None:
+            continue
+        view = _DeviceView(d_z, 8 * int(cols[c]))
+        try:
+            priors, trans, means, cov = train_hmm_compute_statistics_device(view, n_dims, ld, int(ns[c]), labels)
+            _, out[c] = GaussianHmm(priors, trans, means, cov).predict_device(view, ld, int(ns[c]))
+        except (ValueError, IndexError) as exc:
+            out[c] = exc
+    return out
+
+
+def _diar_batch_finish(results, states, return_details, on_error):
+    """per clip (cls, details) or the exception; on_error = "raise" raises the first exception, named by its clip"""
+    out = []
+    for c, (details, st) in enumerate(zip(results, states)):
+        failed = details if isinstance(details, BaseException) else st if isinstance(st, BaseException) else None
+        if failed is not None:
+            failed.details = None if failed is details else details      # what the clustering gave before the HMM refused
+            if on_error == "raise":
+                raise type(failed)("clip %d: %s" % (c, failed))
+            out.append(failed)
+            continue
+        cls = median_filter5(st)
+        if return_details:
+            details["hmm_states"] = st
+            out.append((cls, details))
+        else:
+            out.append(cls)
+    return out
+
+
+def _diarize_batch_device(d_m, n_dims, ld, cols, ns, n_speakers, random_state, init_centers, return_details, on_error, chunk_bytes,
+                          stage_ms=None, draws=None):
+    if on_error not in ("raise", "record"):
+        raise ValueError("on_error must be 'raise' or 'record', not %r" % (on_error,))
+    results, d_z = _diar_clusters_batch(d_m, n_dims, ld, cols, ns, n_speakers, random_state, init_centers, chunk_bytes=chunk_bytes,
+                                        stage_ms=stage_ms, given_draws=draws)
+    try:
+        t0 = time.perf_counter()
+        # the reference trains the HMM on the labels its loop variable holds when the sweep ends: the LAST k, not imax
+        last = [None if isinstance(r, BaseException) else r["labels"][r["ks"][-1]] for r in results]
+        states = diarize_hmm_batch_device(d_z, n_dims, ld, cols, ns, last)
+        if stage_ms is not None:
+            stage_ms["hmm"] = stage_ms.get("hmm", 0.0) + 1e3 * (time.perf_counter() - t0)
+    finally:
+        d_z.free()
+    return _diar_batch_finish(results, states, return_details, on_error)
+
+
+def diarize_features_batch(mats, n_speakers, *, random_state=None, init_centers=None, return_details=False, on_error="raise",
+                           chunk_bytes=None):
+    """diarize_features for a list of (n_dims x n_c) matrices with the same n_dims and ragged n_c, as ONE device batch: the
+    matrices lie side by side in one device matrix, and standardisation, the dimension distances, k-means++ seeding, k-means
+    over all (clip, k) jobs, the per-cluster dimension distances and the cluster-pair sums are each one launch (k-means: one
+    per Lloyd iteration) over every clip of a chunk -- see diarize_clusters_batch_device for what the host waits for.  The
+    HMM smoothing runs clip by clip on the resident matrix (diarize_hmm_batch_device).
+
+    n_speakers: an int or one int per clip, <= 0 sweeps k = 2..9 for that clip.  init_centers: None, or one {k: [k][kept
+    dims]} dict (or None) per clip.  random_state: an int seeds every clip afresh, as a loop of diarize_features calls with
+    that int; a numpy.random.RandomState is consumed in clip order exactly as that loop would consume it.  Returns a list: per
+    clip what diarize_features returns (with return_details the (labels, details) pair), EQUAL to that clip's own call bit for
+    bit at any position, beside any other clips and under any chunk_bytes (a bound on the device scratch of one chunk of clips,
+    1 GiB when None).
+
+    ValueError names the clip and comes before any device work: differing n_dims, n_dims outside 1..256, k outside 1..32, fewer
+    windows than the largest k, an init_centers entry that cannot be [k][kept dims].  What the loop raises from the data -- no
+    dimension passes the filter (ValueError), an init_centers entry whose width is not the kept dims (ValueError), a cluster
+    of the last k without windows (IndexError), a zero deviation or a never-left state in the HMM (ValueError) -- is raised
+    after the batch has run, named by its clip (on_error="raise", the first of them), or put into that clip's slot as the
+    exception object while every other clip's result stays intact (on_error="record"; when it was the HMM that refused, the
+    exception's .details holds the clustering details of that clip).  An empty list returns []."""
+    mats = [np.asarray(m, dtype=np.float64) for m in mats]
+    if not mats:
+        return []
+    for c, m in enumerate(mats):
+        if m.ndim != 2 or m.shape[1] < 1:
+            raise ValueError("clip %d: M must be a (n_dims x n_windows) matrix with at least one window" % c)
+    if on_error not in ("raise", "record"):
+        raise ValueError("on_error must be 'raise' or 'record', not %r" % (on_error,))
+    ns = np.array([m.shape[1] for m in mats], dtype=np.int64)
+    n_dims, _, _ = _diar_batch_check([m.shape[0] for m in mats], ns, n_speakers, init_centers)
+    cols = np.concatenate(([0], np.cumsum(ns)[:-1])).astype(np.int64)
+    d_m = _ffi.DeviceBuffer.from_host(np.ascontiguousarray(np.concatenate(mats, axis=1)))
+    try:
+        return _diarize_batch_device(d_m, n_dims, int(ns.sum()), cols, ns, n_speakers, random_state, init_centers, return_details,
+                                     on_error, chunk_bytes)
+    finally:
+        d_m.free()
+
+
+def _diar_batch_plan(lengths, sampling_rate, mid_window, mid_step):
+    """The argument half of speaker_diarization_batch, without the device: (short-term window = step in samples, mid ratio, mid
+    step ratio, mid-term windows per clip) or the ValueError of the first clip that cannot be served."""
+    from . import MidTermFeatures
+    st = round(sampling_rate * 0.05)
+    ratio, step_ratio = MidTermFeatures._ratios(mid_window * sampling_rate, mid_step * sampling_rate, st, st)
+    if step_ratio < 1:
+        raise ValueError("mid_step / short_step rounds to 0: the reference never terminates")
+    lib = _ffi.lib()
+    st = int(st)
+    windows = []
+    for c, n in enumerate(lengths):
+        if st < 1 or n < st:
+            raise ValueError("clip %d: need at least one array to concatenate (%d samples, a window of %d)" % (c, n, st))
+        windows.append(int(lib.paa_num_mid_windows(int(lib.paa_num_frames(int(n), st, st)), step_ratio)))
+    return st, ratio, step_ratio, np.array(windows, dtype=np.int64)
+
+
+def _diar_extra_rows(loaded):
+    """the probability rows the two speaker SVMs add below the mid-term rows (read from the classifiers, no device copy)"""
+    return sum(len(np.asarray(m[0].classes_)) for m in loaded)
+
+
+def _diar_svcs(loaded):
+    from . import audioTrainTest
+    return [(audioTrainTest.svc_model(m[0]), np.asarray(m[1], dtype=np.float64), np.asarray(m[2], dtype=np.float64)) for m in loaded]
+
+
+def _speaker_batch(monos, sampling_rate, n_speakers, mid_window, mid_step, loaded, random_state, init_centers, return_details, on_error,
+                   chunk_bytes, stage_ms=None, draws=None):
+    """speaker_diarization_batch on mono clips: one batched plan per sample kind writes the mid-term slabs of its clips into
+    ONE device matrix [136 + extra][total windows], one predict_device call per speaker SVM covers every window of every clip,
+    and the clustering batch runs on that matrix."""
+    lib = _ffi.lib()
+    classified = [_ffi.classify_signal(m) for m in monos]
+    st, ratio, step_ratio, M = _diar_batch_plan([s.shape[0] for _, s in classified], sampling_rate, mid_window, mid_step)
+    rows, extra = 2 * 68, _diar_extra_rows(loaded)
+    n_dims, n = rows + extra, len(monos)
+    _diar_batch_check([n_dims] * n, M, n_speakers, init_centers)
+    if on_error not in ("raise", "record"):
+        raise ValueError("on_error must be 'raise' or 'record', not %r" % (on_error,))
+    svcs = _diar_svcs(loaded)                       # the first call that may touch the device
+    cols = np.concatenate(([0], np.cumsum(M)[:-1])).astype(np.int64)
+    total = int(M.sum())
+    t0 = time.perf_counter()
+    d_all = _ffi.DeviceBuffer(n_dims * total * 8)
+    try:
+        for kind in (0, 1):
+            ids = [c for c in range(n) if classified[c][0] == kind]
+            if not ids:
+                continue
+            offsets = np.zeros(len(ids) + 1, dtype=np.int64)
+            np.cumsum([classified[c][1].shape[0] for c in ids], out=offsets[1:])
+            plan = _ffi.Plan(offsets, sampling_rate, st, st, deltas=True, sample_kind=kind)
+            bufs = []
+            try:
+                bufs.append(_ffi.DeviceBuffer.from_host(np.concatenate([classified[c][1] for c in ids])))
+                bufs.append(_ffi.DeviceBuffer(plan.out_doubles * 8))
+                plan.execute(bufs[0], bufs[1])
+                n_mid = plan.mid_doubles(step_ratio)
+                if n_mid != rows * int(M[ids].sum()):
+                    raise RuntimeError("the batched plan has %d mid-term values, %d expected" % (n_mid, rows * int(M[ids].sum())))
+                bufs.append(_ffi.DeviceBuffer(n_mid * 8))
+                plan.mid_execute(bufs[1], ratio, step_ratio, bufs[2])
+                slabs = np.concatenate(([0], np.cumsum(rows * M[ids])[:-1])).astype(np.int64)
+                _ffi.check(lib.paa_diar_batch_gather_f64(bufs[2].ptr, rows, _ffi.as_i64p(slabs), _ffi.as_i64p(cols[ids].copy()),
+                                                         _ffi.as_i64p(M[ids].copy()), len(ids), d_all.ptr, total))
+            finally:
+                for b in bufs:
+                    b.free()
+                plan.destroy()
+        at = rows                                   # the probability rows go below the mid-term rows
+        for model, mean, std in svcs:
+            _, proba = model.predict_device(d_all, total, total, mean, std)
+            block = np.ascontiguousarray(proba.T + 1e-4)
+            _ffi.check(lib.paa_memcpy_h2d(C.c_void_p(d_all.ptr.value + at * total * 8), block.ctypes.data_as(C.c_void_p), block.nbytes))
+            at += block.shape[0]
+        if stage_ms is not None:
+            stage_ms["features_svms"] = stage_ms.get("features_svms", 0.0) + 1e3 * (time.perf_counter() - t0)
+        return _diarize_batch_device(d_all, n_dims, total, cols, M, n_speakers, random_state, init_centers, return_details, on_error,
+                                     chunk_bytes, stage_ms, draws)
+    finally:
+        d_all.free()
+
+
+def speaker_diarization_batch(signals, sampling_rate, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=0, *,
+                              models=None, models_dir=None, random_state=None, init_centers=None, return_details=False,
+                              on_error="raise", chunk_bytes=None):
+    """speaker_diarization_signal for a list of clips of ONE sampling rate, on the GPU end to end: one batched plan gives the
+    mid-term matrices of all clips in one [136 + extra][total windows] device matrix, ONE predict_device call per speaker SVM
+    covers all windows of all clips and writes the probability rows + 1e-4 below the mid-term rows, and diarize_features_batch's
+    stages run on that matrix, which never leaves the device.  Returns a list: per clip what speaker_diarization_signal returns
+    for that clip alone, bit for bit.  n_speakers, random_state, init_centers, return_details, on_error and chunk_bytes: see
+    diarize_features_batch; models: see speaker_diarization.  Each clip goes through audioBasicIO.stereo_to_mono; int16 clips
+    travel as int16, the others through np.double.  lda_dim > 0 raises NotImplementedError, as the single call does.  An empty
+    list returns [].  ValueError names the clip and comes before any device work."""
+    if lda_dim > 0:
+        raise NotImplementedError(_LDA_ELSEWHERE)
+    signals = list(signals)
+    if not signals:
+        return []
+    loaded = _diar_models(models, models_dir)
+    return _speaker_batch(_mono_clips(signals), sampling_rate, n_speakers, mid_window, mid_step, loaded, random_state, init_centers,
+                          return_details, on_error, chunk_bytes)
+
+
+def speaker_diarization_files(paths, n_speakers, mid_window=1.0, mid_step=0.1, short_window=0.1, lda_dim=0, plot_res=False, *,
+                              models=None, models_dir=None, random_state=None, init_centers=None, chunk_bytes=None):
+    """speaker_diarization over audio files: they are read and grouped by sampling rate, one device batch per rate
+    (speaker_diarization_batch), and every file is scored against its .segments file as speaker_diarization scores it (the
+    purities are printed in path order).  Returns the list of (cls, purity_cluster_m, purity_speaker_m) in path order, each
+    equal to speaker_diarization of that file.  n_speakers: an int or one per path; init_centers: None or one dict (or None)
+    per path; a RandomState instance is consumed in PATH order, as the loop over the files would.  A file that cannot be read
+    or served raises ValueError naming its index before the device is touched; what the data of a file makes the loop raise
+    is raised after ALL batches have run and before any file is scored, named by the lowest such index: unlike the loop, no
+    purity line of the files in front of it is printed then (speaker_diarization_evaluation(batch=True) prints none for that
+    dimension).  A refusal of the arguments names the first file that fails within the first sampling-rate group that has one
+    (groups in the order their rate first appears), which need not be the lowest index overall."""
+    if lda_dim > 0:
+        raise NotImplementedError(_LDA_ELSEWHERE)
+    paths = list(paths)
+    n = len(paths)
+    if not n:
+        return []
+    loaded = _diar_models(models, models_dir)
+    extra = _diar_extra_rows(loaded)
+    groups, durations = {}, [0.0] * n
+    for i, path in enumerate(paths):
+        fs, sig = audioBasicIO.read_audio_file(path)
+        if fs <= 0:
+            raise ValueError("file %d (%s) cannot be read" % (i, path))
+        mono = np.asarray(audioBasicIO.stereo_to_mono(sig))
+        durations[i] = len(mono) / fs
+        groups.setdefault(fs, []).append((i, mono))
+    speakers = [int(n_speakers)] * n if np.ndim(n_speakers) == 0 else [int(s) for s in n_speakers]
+    inits = [None] * n if init_centers is None else list(init_centers)
+    if len(speakers) != n or len(inits) != n:
+        raise ValueError("n_speakers and init_centers: one value per path (%d paths)" % n)
+    windows, checked = [0] * n, [None] * n
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        try:
+            monos = _mono_clips([s for _, s in members])
+            _, _, _, M = _diar_batch_plan([m.shape[0] for m in monos], fs, mid_window, mid_step)
+            _, ks_list, group_inits = _diar_batch_check([2 * 68 + extra] * len(ids), M, [speakers[i] for i in ids], [inits[i] for i in ids])
+        except ValueError as exc:
+            raise _as_path_index(exc, ids)
+        for j, i in enumerate(ids):
+            windows[i], checked[i] = (int(M[j]), ks_list[j]), group_inits[j]
+    draws = None
+    if isinstance(random_state, np.random.RandomState):      # the loop consumes it file after file: draw in that order
+        draws = [_diar_batch_draws(random_state, windows[i][0], windows[i][1], checked[i])[0] for i in range(n)]
+    results = [None] * n
+    for fs, members in groups.items():
+        ids = [i for i, _ in members]
+        out = _speaker_batch([s for _, s in members], fs, [speakers[i] for i in ids], mid_window, mid_step, loaded, random_state,
+                             [inits[i] for i in ids], True, "record", chunk_bytes, None, None if draws is None else [draws[i] for i in ids])
+        for i, r in zip(ids, out):
+            results[i] = r
+    for i, r in enumerate(results):
+        if isinstance(r, BaseException):
+            raise type(r)("clip %d: %s" % (i, r))
+    return [_score_diarization(paths[i], results[i][0], results[i][1], mid_step, durations[i], speakers[i], plot_res) for i in range(n)]
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -1,10 +1,12 @@
-// Speaker diarization (kernels_diar.hpp: standardisation, feature-row distances, k-means, cluster-pair distance sums) -- own
-// translation unit, see model_launch.hpp.
+// Speaker diarization (kernels_diar.hpp: standardisation, feature-row distances, k-means, cluster-pair distance sums; and
+// kernels_diarbatch.hpp: the same over a batch of clips, with k-means++ seeding on the device) -- own translation unit, see
+// model_launch.hpp.
 #include <cstdlib>
 #include <cstring>
 
 #include "model_launch.hpp"
 #include "kernels_diar.hpp"
+#include "kernels_diarbatch.hpp"
 
 namespace paa {
 namespace launch {
@@ -121,6 +123,106 @@ int diar_pair_sums(const double *d_Zk, long long ld, long long n, int D, const i
     hipLaunchKernelGGL(diar::pair_reduce_kernel, dim3(bb, 1), dim3(diar::kThreads), 0, stream, (const double *)d_stage, chunks, nbins,
                        chunks, d_S);
     return diar_status();
+}
+
+// ---- the batch of clips (kernels_diarbatch.hpp) ------------------------------------------------------------------------------
+static int diarb_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+static unsigned diarb_blocks(long long n) { return (unsigned)((n + diarb::kThreads - 1) / diarb::kThreads); }
+constexpr int kDiarbMaxGridY = 65535;
+
+int diarb_standardize(const double *d_M, long long ld, const diar::BatchClip *d_clips, int n_clips, int n_dims, double *d_Z,
+                      double *d_stats, hipStream_t stream) {
+    if (n_clips < 1 || n_clips > kDiarbMaxGridY || n_dims < 1 || n_dims > hmm::kMaxDims) return -1;
+    hipLaunchKernelGGL(diarb::standardize_kernel, dim3((unsigned)n_dims, (unsigned)n_clips), dim3(diarb::kThreads), 0, stream, d_M, ld,
+                       d_clips, n_dims, d_Z, d_stats);
+    return diarb_status();
+}
+
+int diarb_dim_distances(const double *d_Z, long long ld, const int *d_rows, const diar::BatchSlot *d_slots, int n_slots, int max_D,
+                        const int *d_labels, double *d_dist, double *d_colsum, double *d_pmean, hipStream_t stream) {
+    if (n_slots < 1 || n_slots > kDiarbMaxGridY || max_D < 1 || max_D > hmm::kMaxDims) return -1;
+    const int nt = (max_D + diarb::kDimTile - 1) / diarb::kDimTile;
+    hipLaunchKernelGGL(diarb::dimdist_kernel, dim3((unsigned)(nt * nt), (unsigned)n_slots), dim3(diarb::kThreads), 0, stream, d_Z, ld,
+                       d_rows, d_slots, d_labels, d_dist);
+    hipLaunchKernelGGL(diarb::dimdist_reduce_kernel, dim3((unsigned)n_slots), dim3(diarb::kThreads), 0, stream, (const double *)d_dist,
+                       d_slots, d_colsum, d_pmean);
+    return diarb_status();
+}
+
+int diarb_seed(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, const double *d_u,
+               double *d_closest, double *d_tmp, double *d_centers, hipStream_t stream) {
+    if (n_jobs < 1) return -1;
+    hipLaunchKernelGGL(diarb::seed_kernel, dim3((unsigned)n_jobs), dim3(diarb::kThreads), 0, stream, d_Z, ld, d_rows, d_jobs, d_u,
+                       d_closest, d_tmp, d_centers);
+    return diarb_status();
+}
+
+template <int KP>
+static void diarb_assign(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, long long max_n,
+                         const double *d_centers, const diar::KmState *d_state, int mode, int *d_labels, double *d_d2, int *d_ints,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(diarb::assign_kernel<KP>, dim3(diarb_blocks(max_n), (unsigned)n_jobs), dim3(diarb::kThreads), 0, stream, d_Z, ld,
+                       d_rows, d_jobs, d_centers, d_state, mode, d_labels, d_d2, d_ints);
+}
+
+static void diarb_assign_any(int kmax, const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs,
+                             long long max_n, const double *d_centers, const diar::KmState *d_state, int mode, int *d_labels,
+                             double *d_d2, int *d_ints, hipStream_t stream) {
+    if (kmax <= 8) diarb_assign<8>(d_Z, ld, d_rows, d_jobs, n_jobs, max_n, d_centers, d_state, mode, d_labels, d_d2, d_ints, stream);
+    else if (kmax <= 16) diarb_assign<16>(d_Z, ld, d_rows, d_jobs, n_jobs, max_n, d_centers, d_state, mode, d_labels, d_d2, d_ints, stream);
+    else diarb_assign<32>(d_Z, ld, d_rows, d_jobs, n_jobs, max_n, d_centers, d_state, mode, d_labels, d_d2, d_ints, stream);
+}
+
+static bool diarb_jobs_ok(int n_jobs, int kmax, long long max_n) {
+    return n_jobs >= 1 && n_jobs <= kDiarbMaxGridY && kmax >= 1 && kmax <= hmm::kMaxStates && max_n >= 1 && max_n <= 0x7fffffffLL / 64;
+}
+
+int diarb_kmeans_step(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, int kmax,
+                      long long max_n, int max_D, double *d_centers, diar::KmState *d_state, int *d_labels, double *d_d2,
+                      int *d_ints, double *d_sums, int max_iter, hipStream_t stream) {
+    if (!diarb_jobs_ok(n_jobs, kmax, max_n) || max_D < 1 || max_D > hmm::kMaxDims) return -1;
+    if (hipMemsetAsync(d_ints, 0, (size_t)n_jobs * diar::kIntsPerK * sizeof(int), stream) != hipSuccess) return -1;
+    diarb_assign_any(kmax, d_Z, ld, d_rows, d_jobs, n_jobs, max_n, d_centers, d_state, 0, d_labels, d_d2, d_ints, stream);
+    const dim3 grid((unsigned)max_D, (unsigned)n_jobs), block(diarb::kThreads);
+    if (kmax <= 8)
+        hipLaunchKernelGGL(diarb::update_kernel<8>, grid, block, 0, stream, d_Z, ld, d_rows, d_jobs, (const diar::KmState *)d_state,
+                           (const int *)d_labels, d_sums);
+    else if (kmax <= 16)
+        hipLaunchKernelGGL(diarb::update_kernel<16>, grid, block, 0, stream, d_Z, ld, d_rows, d_jobs, (const diar::KmState *)d_state,
+                           (const int *)d_labels, d_sums);
+    else
+        hipLaunchKernelGGL(diarb::update_kernel<32>, grid, block, 0, stream, d_Z, ld, d_rows, d_jobs, (const diar::KmState *)d_state,
+                           (const int *)d_labels, d_sums);
+    hipLaunchKernelGGL(diarb::finish_kernel, dim3((unsigned)n_jobs), block, 0, stream, d_Z, ld, d_rows, d_jobs, (const int *)d_labels,
+                       d_d2, (const int *)d_ints, d_sums, d_centers, d_state, max_iter);
+    return diarb_status();
+}
+
+int diarb_kmeans_last(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, int kmax,
+                      long long max_n, const double *d_centers, const diar::KmState *d_state, int *d_labels, double *d_d2,
+                      double *d_inertia, hipStream_t stream) {
+    if (!diarb_jobs_ok(n_jobs, kmax, max_n)) return -1;
+    diarb_assign_any(kmax, d_Z, ld, d_rows, d_jobs, n_jobs, max_n, d_centers, d_state, 1, d_labels, d_d2, nullptr, stream);
+    hipLaunchKernelGGL(diarb::row_sum_kernel, dim3((unsigned)n_jobs), dim3(diarb::kThreads), 0, stream, (const double *)d_d2, d_jobs,
+                       d_inertia);
+    return diarb_status();
+}
+
+int diarb_pair_sums(const double *d_Z, long long ld, const int *d_rows, const diar::BatchClip *d_clips, const diar::BatchJob *d_jobs,
+                    const diar::BatchTile *d_items, int n_items, const int *d_labels, const int *d_bintab, double *d_partial,
+                    const diar::BatchRed *d_red1, int n_red1, double *d_stage, const diar::BatchRed *d_red2, int n_red2,
+                    double *d_S, int max_bins, int workgroups, hipStream_t stream) {
+    if (n_items < 1 || n_red1 < 1 || n_red1 > kDiarbMaxGridY || n_red2 < 1 || n_red2 > kDiarbMaxGridY || max_bins < 1 || workgroups < 1)
+        return -1;
+    const int wgs = n_items < workgroups ? n_items : workgroups;
+    hipLaunchKernelGGL(diarb::pair_kernel, dim3((unsigned)wgs), dim3(diarb::kThreads), 0, stream, d_Z, ld, d_rows, d_clips, d_jobs,
+                       d_items, n_items, d_labels, d_bintab, d_partial);
+    const unsigned bb = (unsigned)((max_bins + diarb::kThreads - 1) / diarb::kThreads);
+    hipLaunchKernelGGL(diarb::pair_reduce_kernel, dim3(bb, (unsigned)n_red1), dim3(diarb::kThreads), 0, stream,
+                       (const double *)d_partial, d_red1, d_stage);
+    hipLaunchKernelGGL(diarb::pair_reduce_kernel, dim3(bb, (unsigned)n_red2), dim3(diarb::kThreads), 0, stream,
+                       (const double *)d_stage, d_red2, d_S);
+    return diarb_status();
 }
 
 }  // namespace launch

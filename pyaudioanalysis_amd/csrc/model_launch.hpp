@@ -331,6 +331,32 @@ struct KmState {
 };
 constexpr int kMaxPoints = 8;                         // candidate windows per sqdist_points_kernel launch
 constexpr int kIntsPerK = hmm::kMaxStates + 1;      // cluster sizes and the number of changed labels of one assignment
+// The records of a batch of clips (kernels_diarbatch.hpp).  Every clip is the column range [col, col + n) of one matrix
+// [n_dims][ld]; its kept feature rows are rows[rows_off .. rows_off + D - 1]; its (clip, k) jobs are consecutive.  Offsets are
+// in elements of the array they index.
+constexpr int kBatchPairTile = 128;                   // windows per side of a pair tile, as kPairTile of kernels_diar.hpp
+constexpr int kBatchTrials = 5;                       // 2 + int(ln 32) k-means++ candidates per step at most
+struct BatchClip {
+    long long col, n, lab_off;          // lab_off: the labels of the clip's first job ([nk][n] from there)
+    int D, rows_off, first_job, nk, bin_tab, pad;
+};
+struct BatchJob {
+    long long col, n, lab_off, tmp_off, u_off, cen_off, first;
+    double tol;
+    int D, rows_off, k, seeded, trials, pad;
+};
+struct BatchSlot {                      // the feature-row distances over the windows labelled `cluster` (lab_off < 0: all)
+    long long col, n, lab_off, dist_off, sum_off;
+    int D, rows_off, cluster, pad;      // rows_off < 0: rows 0 .. D - 1
+};
+struct BatchTile {
+    long long part_off;
+    int clip, bi, bj, pad;
+};
+struct BatchRed {
+    long long in_off, rows, out_off;
+    int nbins, pad;
+};
 }  // namespace diar
 
 // f(std::integral_constant<int, v>) for Lo <= v <= Hi, one instance per value; -1 outside the range
@@ -467,6 +493,27 @@ long long diar_pair_tiles(long long n);
 long long diar_pair_chunks(long long n);
 int diar_pair_sums(const double *d_Zk, long long ld, long long n, int D, const int *d_labels, const int *d_ks, int nk,
                    const int *d_binoff, int nbins, double *d_partial, double *d_stage, double *d_S, hipStream_t stream);
+// kernels_diarbatch.hpp (speaker diarization of a batch of clips); the records are diar::Batch* arrays on the device
+constexpr long long kDiarbPairChunk = 256;            // tiles added up by one thread of the first reduction stage, as the single call
+int diarb_standardize(const double *d_M, long long ld, const diar::BatchClip *d_clips, int n_clips, int n_dims, double *d_Z,
+                      double *d_stats, hipStream_t stream);
+// dist is scratch (slot.dist_off); colsum at slot.sum_off, pmean [n_slots]; max_D: the widest slot
+int diarb_dim_distances(const double *d_Z, long long ld, const int *d_rows, const diar::BatchSlot *d_slots, int n_slots, int max_D,
+                        const int *d_labels, double *d_dist, double *d_colsum, double *d_pmean, hipStream_t stream);
+int diarb_seed(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, const double *d_u,
+               double *d_closest, double *d_tmp, double *d_centers, hipStream_t stream);
+// one Lloyd iteration of every unfinished job (ints [n_jobs][33] is zeroed here), and the last pass (labels, d2, inertia)
+int diarb_kmeans_step(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, int kmax,
+                      long long max_n, int max_D, double *d_centers, diar::KmState *d_state, int *d_labels, double *d_d2,
+                      int *d_ints, double *d_sums, int max_iter, hipStream_t stream);
+int diarb_kmeans_last(const double *d_Z, long long ld, const int *d_rows, const diar::BatchJob *d_jobs, int n_jobs, int kmax,
+                      long long max_n, const double *d_centers, const diar::KmState *d_state, int *d_labels, double *d_d2,
+                      double *d_inertia, hipStream_t stream);
+// tiles of the list, then the two reduction stages (records red1 -> stage, red2 -> S); max_bins: the widest clip
+int diarb_pair_sums(const double *d_Z, long long ld, const int *d_rows, const diar::BatchClip *d_clips, const diar::BatchJob *d_jobs,
+                    const diar::BatchTile *d_items, int n_items, const int *d_labels, const int *d_bintab, double *d_partial,
+                    const diar::BatchRed *d_red1, int n_red1, double *d_stage, const diar::BatchRed *d_red2, int n_red2,
+                    double *d_S, int max_bins, int workgroups, hipStream_t stream);
 // kernels_lda.hpp (the LDA step of speaker diarization); classes are the runs off[c] .. off[c + 1] - 1 of windows (off [C + 1] on
 // the device).  means [C][D] and std [D] (pooled within-class deviation, zeros replaced by 1); dev and sq [C][D] are scratch
 int lda_class_stats(const double *d_X, long long ld, long long n, int D, const long long *d_off, long long C, double *d_means,

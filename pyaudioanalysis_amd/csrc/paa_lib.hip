@@ -563,6 +563,7 @@ extern "C" int64_t paa_chromagram_rows(int64_t n, int window, int step, int64_t 
 #include "lib_boost.hpp"
 #include "lib_hmm.hpp"
 #include "lib_diar.hpp"
+#include "lib_diar_batch.hpp"
 #include "lib_lda.hpp"
 
 // ------------------------------------------------------------------------------------------
